@@ -27,6 +27,9 @@ and without the reference's per-node gc.collect() and with one BLAS thread), "ho
 
 --config c5 (BASELINE config 5 geometry, 2048^2 grid, M=8, r0=64) adds "mle": Nelder-Mead objective evaluations
 per second on the resident plan (likelihood-only passes with a new kernel parameter each).
+
+--dump-outputs DIR (e.g. bench_outputs) writes what the last timed step computed - likelihood and the predictive mean / var / sd -
+as DIR/<name>.npy in float64 (dump_outputs); the inputs are seeded, so two builds can be compared output for output.
 """
 import argparse
 import json
@@ -232,6 +235,45 @@ def traffic_from_profiles(kernel_family, profiles_dir=None):
             src, None)
 
 
+DUMP_LIMIT_BYTES = 64 << 20     # --dump-outputs: all .npy files together stay below this
+DUMP_SAMPLE_SEED = 20240601     # fixed: the sampled rows are the same in every run and every build
+
+
+def dump_outputs(out_dir, pl, predict, dist=None, rank=0):
+    """--dump-outputs DIR: what the last timed step handed its caller, as float64 .npy files - likelihood = d + u
+    (MRATree.getLikelihood), likelihood_terms = [d, u] (HipPlan.likelihood) and, unless --likelihood-only, the predictive
+    mean / var / sd of every location in the caller's row order (HipPlan.predict).  If the three predictive vectors would
+    exceed DUMP_LIMIT_BYTES, a fixed seeded sample of rows is written instead, with the row numbers in predict_rows.npy.
+    With N > 1 ranks every rank takes part (the predictive rows of the shards are disjoint, so their sum is the whole
+    vector) and rank 0 writes.  Returns the record for the JSON line (rank 0)."""
+    d, u = pl.likelihood()
+    arrays = {"likelihood": np.array([d + u]), "likelihood_terms": np.array([d, u])}
+    sampled = None
+    if predict:
+        mean, var, sd = pl.predict(with_sd=True)
+        if dist is not None:
+            import torch
+            for a in (mean, var, sd):
+                t = torch.from_numpy(a)                    # shares memory with a: the sum lands in place
+                dist.all_reduce(t)
+        n = mean.size
+        per_row = 3 * 8
+        if n * per_row > DUMP_LIMIT_BYTES - (1 << 20):
+            k = (DUMP_LIMIT_BYTES - (1 << 20)) // (per_row + 8)
+            rows = np.sort(np.random.RandomState(DUMP_SAMPLE_SEED).choice(n, k, replace=False))
+            mean, var, sd = mean[rows], var[rows], sd[rows]
+            arrays["predict_rows"] = rows.astype(np.float64)
+            sampled = int(k)
+        arrays.update(predict_mean=mean, predict_var=var, predict_sd=sd)
+    if rank != 0:
+        return None
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+    return {"dir": out_dir, "files": sorted(name + ".npy" for name in arrays), "dtype": "f64",
+            "predict_rows_sampled": sampled}
+
+
 def relaunch_with_ranks(n):
     """`python bench.py --gpus N` without a launcher (WORLD_SIZE unset): start the N ranks ourselves, as a CHILD process -
     `python -m torch.distributed.run --nproc-per-node N ... bench.py <same arguments>` on a free local port - before anything
@@ -274,7 +316,14 @@ def main():
     ap.add_argument("--exchange", default="rccl", choices=["rccl", "gloo"],
                     help="transport of the one front all-reduce for --gpus > 1: RCCL on the device (default) or "
                          "host export/import + torch.distributed gloo (rehearsal on a box with fewer GPUs than ranks)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last one computed (likelihood, predictive mean / var / sd) "
+                         "as DIR/<name>.npy in float64, at most 64 MB in all")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
     c = CONFIGS[args.config]
 
     rank = int(os.environ.get("RANK", "0"))
@@ -407,6 +456,7 @@ def main():
         tt = torch.tensor([elapsed_plain], dtype=torch.float64)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed_plain = float(tt[0])
+    dumped = dump_outputs(args.dump_outputs, pl, predict, dist, rank) if args.dump_outputs else None
 
     n_nodes = topo.n_nodes
     out = None
@@ -469,6 +519,8 @@ def main():
             "roofline": roof,
             "host": {"input_synthesis_s": t1 - t0, "tree_build_s": t2 - t1, "plan_and_upload_s": t3 - t2},
         }
+        if dumped is not None:
+            out["dump_outputs"] = dumped
     if args.config == "c5" or args.mle:
         # every rank takes part: the objective is the sharded pass (one all-reduce per evaluation), rank 0 drives Nelder-Mead
         m = mle_throughput(pl, c, kind, y_obs, red, host_allreduce, rank, dist)
