@@ -203,6 +203,10 @@ int mra_get_timers(mra_plan *plan, double *out_ms, int capacity);
 #define MRA_OPT_LIK_ROWS       17  /* 1 (default): likelihood-only passes of the fused path compute the whitened basis W at the OBSERVED rows only
                                       (gathered row tiles: a likelihood needs nothing else; W's other rows keep what an earlier pass left there);
                                       0: at every row - what mra_get_buffer(W) callers and the node-block diagnostics want */
+#define MRA_OPT_CASCADE_GROUP  18  /* fused path, row cascades that stage all their levels at once: 1 = one workgroup per family of sibling
+                                      leaves (one operand image staged for all of them), 0 = one per leaf.  Default: a cost model at plan build
+                                      (families when that still fills the CUs); get returns the plan's current decision, set forces it.  Regular trees
+                                      only: on any other plan set is accepted and ignored, get returns 0 */
 int mra_plan_set_option(mra_plan *plan, int option, int64_t value);
 /* current value of an option (so that a caller can change one temporarily and put it back) */
 int mra_plan_get_option(mra_plan *plan, int option, int64_t *value);

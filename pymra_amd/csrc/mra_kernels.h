@@ -514,6 +514,9 @@ __global__ __launch_bounds__(256, 4) void k_gemm_nt_lds(const GemmProb* __restri
     // walks the step table, the prefetch running ahead across segment boundaries
     const bool segmented = SEGS && pb.nseg > 0;
     int nk = pb.K >> 4;
+    // K = 0 (a leaf without observations: its Ut / Tt pointers sit at its panel offset, one past the panel's end behind the last
+    // observed leaf): the unconditional prefetches below must not read there
+    if (!segmented && nk <= 0) { ap = bp = (const double*)probs; nk = 0; }
     int it_s = 0, it_k = 0, it_sgn = 0;
     if (SEGS && segmented) {
         const int nseg = pb.nseg;
@@ -1609,7 +1612,8 @@ __device__ __forceinline__ double chol16_ldl(const double* tile, int ldt, double
         double d3 = __builtin_fma(-u32, c32, __builtin_fma(-u31, c31, __builtin_fma(-u30, b[3][0], b[3][3])));
         const double i3 = rcp_pos(d3);
         // not positive definite (or NaN): flagged once per panel off the chain; the numbers that follow are garbage either way
-        if (!(fmin(fmin(d0, d1), fmin(d2, d3)) > 0.0)) bad = true;
+        // (each pivot compared on its own: fmin drops a NaN operand, so a NaN first met at pivot 1-3 of the last panel went unflagged)
+        if (!(d0 > 0.0) | !(d1 > 0.0) | !(d2 > 0.0) | !(d3 > 0.0)) bad = true;
         // U_pp^-1 (unit lower), this lane's element of the zero-padded A operand: V[r][q], q <= r < 4
         const double v20 = __builtin_fma(u21, u10, -u20), v31 = __builtin_fma(u32, u21, -u31);
         const double v30 = -__builtin_fma(u32, v20, __builtin_fma(-u31, u10, u30));

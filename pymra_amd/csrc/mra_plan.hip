@@ -206,6 +206,24 @@ static int fail(mra_plan* p, const MraError& e) {
 
 static void fill_knot_arrays(mra_plan* pl);
 
+// Workgroups of the full row cascade when it stages all its levels at once (ft_wg0_leaf / ft_wgn_leaf; tile numbers as in ft_row0,
+// leaves in order): one per leaf ... or one per family of sibling leaves (same parent = same operand image on every level, staged
+// once for all of them) when cascade_group_siblings holds - the cost model of build_static or MRA_OPT_CASCADE_GROUP.
+static void build_leaf_workgroups(mra_plan* pl) {
+    std::vector<long> wg0;
+    std::vector<int> wgn;
+    long tile = 0;
+    for (size_t t = 0; t < pl->leaf_nodes.size(); ++t) {
+        const int i = pl->leaf_nodes[t];
+        const int nt = (int)((pl->row1[i] - pl->row0[i]) / 16);
+        const bool join = pl->cascade_group_siblings && t > 0 && pl->parent[i] >= 0 && pl->parent[i] == pl->parent[pl->leaf_nodes[t - 1]] && !wgn.empty();
+        if (join) wgn.back() += nt;
+        else { wg0.push_back(tile); wgn.push_back(nt); }
+        tile += nt;
+    }
+    pl->ft_wg0_leaf.upload(wg0); pl->ft_wgn_leaf.upload(wgn); pl->n_fwg_leaf = (long)wg0.size();
+}
+
 // ------------------------------------------------------------------------------------------------
 static void build_static(mra_plan* pl) {
     PlanTrace tr("build_static");
@@ -598,8 +616,8 @@ static void build_static(mra_plan* pl) {
             pl->knot_chain_ok = pl->knot_chain_lds <= 160 * 1024;
         }
         tr.mark("fused levels, knot chain");
-        std::vector<long> r0s, fwg0, lwg0;
-        std::vector<int> chains, fwgn, tleaf, lwgn;
+        std::vector<long> r0s, fwg0;
+        std::vector<int> chains, fwgn, tleaf;
         {
             int ndev_cu = 256;
             hipDeviceProp_t prop;
@@ -617,17 +635,12 @@ static void build_static(mra_plan* pl) {
             const size_t nl_ = std::max<size_t>(1, pl->leaf_nodes.size()), np_ = std::max<size_t>(1, nparents);
             const double t_leaf = std::ceil((double)ntiles_all / nl_ / 8.0), t_fam = std::ceil((double)ntiles_all / np_ / 8.0);
             const double cost_leaf = std::ceil((double)nl_ / ndev_cu) * (5.0 + 32.0 * t_leaf), cost_fam = std::ceil((double)np_ / ndev_cu) * (5.0 + 32.0 * t_fam);
-            pl->cascade_group_siblings = cost_fam < cost_leaf;
+            pl->cascade_group_siblings = cost_fam < cost_leaf;      // (MRA_OPT_CASCADE_GROUP overrides it)
         }
         for (size_t t = 0; t < pl->leaf_nodes.size(); ++t) {
             const int i = pl->leaf_nodes[t];
             int ch[8];
             chain_of(i, ch);
-            // one workgroup per leaf ... or per family of sibling leaves (same parent = same operand image on every level,
-            // staged once for all of them) when that still leaves at least two workgroups per CU
-            const bool join = pl->cascade_group_siblings && t > 0 && pl->parent[i] >= 0 && pl->parent[i] == pl->parent[pl->leaf_nodes[t - 1]] && !lwgn.empty();
-            if (join) lwgn.back() += (int)((pl->row1[i] - pl->row0[i]) / 16);
-            else { lwg0.push_back((long)r0s.size()); lwgn.push_back((int)((pl->row1[i] - pl->row0[i]) / 16)); }
             for (long p = pl->row0[i]; p < pl->row1[i]; p += 16) {
                 if (((p - pl->row0[i]) / 16) % pl->cascade_wpw == 0) {
                     fwg0.push_back((long)r0s.size());
@@ -661,7 +674,7 @@ static void build_static(mra_plan* pl) {
             const int nl = pl->NL;
             pl->cascade_lds_all = (size_t)(cwt * cwt * (nl * (nl - 1) / 2) + nl * (cwt * (cwt - 1) / 2 + cwt)) * 2048;
             pl->cascade_stage_all = pl->cascade_lds_all <= 160 * 1024;
-            pl->ft_wg0_leaf.upload(lwg0); pl->ft_wgn_leaf.upload(lwgn); pl->n_fwg_leaf = (long)lwg0.size();
+            build_leaf_workgroups(pl);
         }
         tr.mark("row tiles of the cascades");
     }
@@ -1215,8 +1228,10 @@ static void ensure_lik_tiles(mra_plan* pl) {
         if (!nt) continue;
         int ch[8] = {0, 0, 0, 0, 0, 0, 0, 0};
         for (int a = pl->parent[i]; a >= 0; a = pl->parent[a]) ch[pl->node_level[a]] = pl->node_slot[a];
-        const bool join = pl->cascade_group_siblings && !wg0.empty() && t > 0 && pl->parent[i] >= 0 && pl->parent[i] == pl->parent[pl->leaf_nodes[t - 1]] &&
-                          wg0.back() + wgn.back() == pl->obs_off_host[t] / 16;
+        // the kernel stages the chain of a workgroup's FIRST tile for all of its tiles: join only a workgroup with this very chain (leaf
+        // t - 1 may own no tile, and the last workgroup then belongs to another family)
+        const bool join = pl->cascade_group_siblings && !wg0.empty() && wg0.back() + wgn.back() == pl->obs_off_host[t] / 16 &&
+                          std::equal(ch, ch + 8, chains.begin() + wg0.back() * 8);
         if (join) wgn.back() += (int)nt;
         else { wg0.push_back(pl->obs_off_host[t] / 16); wgn.push_back((int)nt); }
         for (long k = 0; k < nt; ++k) { tleaf.push_back((int)t); for (int c = 0; c < 8; ++c) chains.push_back(ch[c]); }
@@ -2434,6 +2449,16 @@ int mra_plan_set_option(mra_plan* pl, int option, int64_t value) {
     if (option == 16) { pl->use_hi_fold = (int)value; return MRA_OK; }
     if (option == 17) { pl->use_lik_rows = value != 0; return MRA_OK; }
     if (option == 13) { pl->ut_gather = value != 0; return MRA_OK; }
+    if (option == 18) {
+        if (!pl->regular) return MRA_OK;          // (no fused cascade: nothing is grouped, the decision stays 0)
+        try {
+            pl->cascade_group_siblings = value != 0;
+            pl->lik_tiles_valid = false;
+            HIP_TRY(mraSetDevice(pl->device));
+            build_leaf_workgroups(pl);
+            return MRA_OK;
+        } catch (const MraError& e) { return fail(pl, e); }
+    }
     if (option == 99) {
         // kernel-shape switches for A/B runs.  Bits 8 and 32 keep the results (predictive cascade at two workgroups per CU, the
         // wide leaf-residual shape); bits 1, 2, 4 (no Ut scatter / no W stores / constant instead of the kernel) give WRONG results
@@ -2468,6 +2493,7 @@ int mra_plan_get_option(mra_plan* pl, int option, int64_t* value) {
         case 16: *value = pl->use_hi_fold; break;
         case 17: *value = pl->use_lik_rows; break;
         case 13: *value = pl->ut_gather; break;
+        case 18: *value = pl->cascade_group_siblings; break;
         case 99: *value = pl->dbg; break;
         default: return fail(pl, MraError(MRA_ERR_INVALID, "unknown option"));
     }

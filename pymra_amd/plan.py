@@ -34,6 +34,7 @@ MRA_OPT_SYRK_BLK = 14
 MRA_OPT_PRIOR_LEVEL = 15
 MRA_OPT_HI_FOLD = 16
 MRA_OPT_LIK_ROWS = 17
+MRA_OPT_CASCADE_GROUP = 18
 MRA_BLOCK_W_ROWS, MRA_BLOCK_LPRIOR, MRA_BLOCK_FRONT, MRA_BLOCK_LEAF = 0, 1, 2, 3
 
 ERR_NAMES = {-1: "MRA_ERR_INVALID", -2: "MRA_ERR_HIP", -3: "MRA_ERR_NOT_SPD", -4: "MRA_ERR_STATE",

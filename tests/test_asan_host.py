@@ -34,6 +34,10 @@ def build(topo, locs, y_obs, R, host_cov=None):
         pl.upload_host_cov(host_cov, locs, y_obs)
         y2 = np.array(y_obs, dtype=float); y2[np.nonzero(np.isfinite(y2.ravel()))[0][:3]] = np.nan
         pl.set_obs(y2, R)                                  # invalidates the blocks (state path)
+    g = pl.get_option(P.MRA_OPT_CASCADE_GROUP)
+    for v in (1 - g, g, 1):                                # sibling grouping forced: the leaf workgroup lists are rebuilt
+        pl.set_option(P.MRA_OPT_CASCADE_GROUP, v)          # (regular trees; any other plan keeps 0)
+        assert pl.get_option(P.MRA_OPT_CASCADE_GROUP) in (v, 0)
     try:
         pl.run(True, True)
         raise SystemExit("a dry-run plan must refuse to run")

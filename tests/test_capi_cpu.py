@@ -115,3 +115,36 @@ assert counts[0] >= 10 and counts[0] == counts[1] == counts[2]
     env = dict(os.environ, MRA_ROOT=K.ROOT, MRA_HOST_DRYRUN="1")
     res = subprocess.run([sys.executable, str(child)], env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0 and "LDS_ATTR_OK" in res.stdout, (res.stdout + res.stderr)[-2000:]
+
+
+def test_cascade_group_option_round_trip(built_library, tmp_path):
+    """MRA_OPT_CASCADE_GROUP reports the plan's own decision (the cost model: off for a 64 x 64 tree, on for 512^2, r=32, M=5
+    at 256 CUs) and forcing it either way rebuilds the leaf workgroup lists.  Host dry run, no GPU."""
+    import subprocess
+    import sys
+    child = tmp_path / "child.py"
+    child.write_text(r"""
+import os, sys
+import numpy as np
+sys.path.insert(0, os.environ["MRA_ROOT"]); sys.path.insert(0, os.path.join(os.environ["MRA_ROOT"], "tests"))
+import _cases as K
+import pymra_amd.MRATools as mt
+from pymra_amd import plan as P
+from pymra_amd.topology import build_topology
+cs = K.load_case("g64")
+np.random.seed(2)
+locs = mt.genLocations2d(Nx=512, Ny=512)
+big = build_topology(locs, 32, 5, 4)
+y = np.where(np.random.uniform(size=(512 * 512, 1)) < 0.4, 1.0, np.nan)
+for topo, lc, yo, want in ((cs["topo"], cs["locs"], cs["y_obs"], 0), (big, locs, y, 1)):
+    pl = P.HipPlan(topo, 0)
+    pl.set_locs(lc); pl.set_obs(yo, 1e-2); pl.set_kernel(mt.KIND_EXP, 0.3, 1.0, 1.0)
+    assert pl.get_option(P.MRA_OPT_CASCADE_GROUP) == want, (topo.N, pl.get_option(P.MRA_OPT_CASCADE_GROUP))
+    for v in (1, 0, 1, want):
+        pl.set_option(P.MRA_OPT_CASCADE_GROUP, v); assert pl.get_option(P.MRA_OPT_CASCADE_GROUP) == v
+    pl.close()
+print("CASCADE_GROUP_OK")
+""")
+    env = dict(os.environ, MRA_ROOT=K.ROOT, MRA_HOST_DRYRUN="1")
+    res = subprocess.run([sys.executable, str(child)], env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and "CASCADE_GROUP_OK" in res.stdout, (res.stdout + res.stderr)[-2000:]
