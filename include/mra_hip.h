@@ -122,6 +122,28 @@ int mra_get_likelihood(mra_plan *plan, double *d, double *u);
  * (pyMRA/MRANode.py:510-520) in padded leaf order, P values each. */
 int mra_get_predict(mra_plan *plan, double *mean_perm, double *var_perm);
 
+/* Simulation from the model (the reference's dense-Cholesky simulate1D / simulateGRF, pyMRA/MRATools.py:395-484, at any size):
+ * exact draws from the MRA prior covariance Sigma = sum_j B_j k_j B_j^T of the reported rows, or, with MRA_SAMPLE_CONDITIONAL,
+ * from the posterior given the plan's observations and nugget R ("conditioning by kriging": x + mean_MRA(y - x_o - sqrt(R) eps),
+ * one likelihood + predict pass per conditional draw).  A prior draw is
+ *     x = sum_{non-leaf j} W^m(j)[rows_j] z_j + sum_{leaf j} L_j zeta_j,   L_j L_j^T = v_M(K_j, K_j)  (K_j: the leaf's knot rows)
+ * Latent slots (mra_sample_slots gives their number, Kn + 2 P):
+ *     [0, Kn)            the non-leaf nodes in node order, cw[level] slots each, in knot-column order (phantom knots: unused)
+ *     [Kn, Kn + P)       leaf terms by padded row; read only at the knot rows of the row's leaf
+ *     [Kn + P, Kn + 2P)  observation noise by padded row; read only with MRA_SAMPLE_CONDITIONAL, at observed rows
+ * z: NULL = draw on the device: slot k of sample s is Philox4x32-10 with key = seed (lo, hi) and counter = (k lo, k hi, s' lo, s' hi),
+ * s' = sample0 + s, output words w0..w3; a = w0 + 2^32 w1, b = w2 + 2^32 w3, u1 = ((a >> 11) + 0.5) 2^-53, u2 likewise from b,
+ * z = sqrt(-2 log u1) cospi(2 u2) - a pure function of (seed, slot, sample).  Otherwise z is n_samples x n_slots, row-major.
+ * out: n_samples x P, padded leaf order; unreported rows (phantoms, rows a 1-D split drops) are exactly 0.
+ * Needs set_locs, set_obs and set_kernel (MRA_ERR_STATE); MRA_ERR_INVALID for MRA_KERNEL_HOST plans, sharded plans and
+ * n_samples < 0; MRA_ERR_NOT_SPD when a leaf's v_M(K, K) does not factor (no jitter is added).  The device y and every option
+ * are as the caller left them afterwards, mra_get_likelihood / mra_get_predict still return the last mra_run's values
+ * (mra_get_timers / mra_get_kernel_stats describe the sampler's own passes).  Blocking. */
+#define MRA_SAMPLE_CONDITIONAL 1u
+int mra_sample_slots(mra_plan *plan, int64_t *n_slots);
+int mra_sample(mra_plan *plan, uint32_t flags, int64_t n_samples, uint64_t seed, int64_t sample0,
+               const double *z, double *out);
+
 /* Diagnostics for tests (the reference exposes these as attributes of Node objects):
  * what = 0: whitened basis W (P x ldw, row-major) ; 1: per-node log-det terms (n_nodes);
  * copies min(capacity, available) doubles into out, returns the available count in *n_avail.

@@ -157,6 +157,25 @@ class MRATree(object):
         sdP = self._sd if self._sd is not None else np.sqrt(self.root.var)
         return xP, sdP
 
+    def simulate(self, nsim=1, distr="prior", seed=None):
+        """(N, nsim) exact draws of the field in the caller's row order: from the MRA prior (distr="prior") or from the posterior
+        given this tree's observations (distr="posterior"; conditioning by kriging, one device pass per draw).  Rows outside every
+        leaf are 0, as in predict().  seed=None takes a 64-bit seed from NumPy's global RNG (np.random.seed makes runs repeatable).
+        The scalable counterpart of pyMRA's dense simulate1D / simulateGRF (pyMRA/MRATools.py:395-484); getLikelihood() and
+        predict() are unchanged afterwards."""
+        if distr not in ("prior", "posterior"):
+            raise ValueError('distr must be "prior" or "posterior"')
+        if self.kernel is None:
+            raise NotImplementedError("simulate needs a device kernel: trees built from an opaque callable or a dense matrix cannot sample")
+        if seed is None:
+            seed = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64)) * 2 + int(np.random.randint(0, 2))
+        x = self.plan.sample(nsim, seed=seed, conditional=(distr == "posterior"))
+        t = self.topology
+        rows = (t.perm >= 0) & np.asarray(t.in_leaf, dtype=bool)
+        out = np.zeros((len(self.locs), int(nsim)))
+        out[t.perm[rows], :] = x[:, rows].T
+        return out
+
     # ---- diagnostics surface (pyMRA/MRATree.py:101-132, 445-511); host-side de-whitening, see pymra_amd.diagnostics
     def getNodeBlocks(self, posterior=True):
         """Per-node ``B, kInv, k, kC`` (+ ``A, omg, kTil, kTilC, BTil[res]``, cumulative ``d, u``) of every node

@@ -4333,3 +4333,136 @@ __global__ __launch_bounds__(256) void k_sum_dnode(const double* __restrict__ dn
     }
 }
 #endif
+
+// ------------------------------------------------------------------------------------------------
+//  Sampler (mra_sample): x = sum_{non-leaf j} W^m(j)[rows_j] z_j + sum_{leaf j} L_j zeta_j, L_j L_j^T = v_M(K_j, K_j).
+//  Latent draw of (slot, sample): Philox4x32-10 with key = seed (lo, hi) and counter = (slot lo, slot hi, sample lo, sample hi);
+//  a = w0 + 2^32 w1, b = w2 + 2^32 w3, u1 = ((a >> 11) + 0.5) 2^-53, u2 likewise from b, z = sqrt(-2 log u1) cospi(2 u2).
+//  A pure function of (seed, slot, sample): the launch shape and the chunking of samples do not enter.
+// ------------------------------------------------------------------------------------------------
+struct SampleZ {
+    const double* z;            // caller-given draws, sample s at z[s * ldz + slot]; nullptr: Philox
+    long ldz;
+    unsigned long long seed;
+    long sample0;               // global number of the block's sample 0
+    int ns;                     // samples in the block (<= 16); draws of samples >= ns are 0
+};
+struct SampleLeaf {             // one leaf of a Gram batch
+    double* G;                  // nr x nr, row-major (ld = nr): C - W_anc W_anc^T, masked, then its lower Cholesky factor
+    long row0;
+    int nr;
+};
+struct SampleChain { int col0, zoff, width, pad; };   // one ancestor of a leaf: its W columns and its latent slots
+
+__device__ __forceinline__ double philox_normal(unsigned long long seed, unsigned long long slot, unsigned long long sample) {
+    unsigned c0 = (unsigned)slot, c1 = (unsigned)(slot >> 32), c2 = (unsigned)sample, c3 = (unsigned)(sample >> 32);
+    unsigned k0 = (unsigned)seed, k1 = (unsigned)(seed >> 32);
+#pragma unroll
+    for (int i = 0; i < 10; ++i) {
+        const unsigned lo0 = 0xD2511F53u * c0, hi0 = __umulhi(0xD2511F53u, c0);
+        const unsigned lo1 = 0xCD9E8D57u * c2, hi1 = __umulhi(0xCD9E8D57u, c2);
+        c0 = hi1 ^ c1 ^ k0; c1 = lo1; c2 = hi0 ^ c3 ^ k1; c3 = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    const unsigned long long a = ((unsigned long long)c1 << 32) | c0, b = ((unsigned long long)c3 << 32) | c2;
+    const double u1 = ((double)(a >> 11) + 0.5) * 0x1p-53, u2 = ((double)(b >> 11) + 0.5) * 0x1p-53;
+    return sqrt(-2.0 * log(u1)) * cospi(2.0 * u2);
+}
+__device__ __forceinline__ double sample_z(const SampleZ& zs, long slot, int s) {
+    if (s >= zs.ns) return 0.0;
+    return zs.z ? gld(zs.z + (long)s * zs.ldz + slot) : philox_normal(zs.seed, (unsigned long long)slot, (unsigned long long)(zs.sample0 + s));
+}
+
+#ifndef MRA_KERNELS_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_plan.hip */
+// the non-leaf draws of a block of 16 samples, slot-major: zc[slot * 16 + s]
+__global__ __launch_bounds__(256) void k_sample_draw(SampleZ zs, long n_slots, double* __restrict__ zc) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n_slots * 16) zc[i] = sample_z(zs, i >> 4, (int)(i & 15));
+}
+
+// coarse term, one wave per 16-row tile: X[tile, 0:16] = sum over the tile's ancestor chain of W[tile, block] Z[block, 0:16] on
+// v_mfma_f64_16x16x4_f64 (A = 16 W columns in row-on-lane form, B = the chain's draws; lane (r,q) ends up with
+// X[row0 + q + 4 j][sample r]).  Unreported rows are written as 0.  out: 16 x P, sample-major.  (256, 4): within 128 registers the
+// accumulator stays in VGPRs - with the full budget hipcc parks it in AGPRs.
+__global__ __launch_bounds__(256, 4) void k_sample_coarse(const double* __restrict__ W, long ldw, const int* __restrict__ tile_leaf,
+                                                       const int* __restrict__ chain_ptr, const SampleChain* __restrict__ chain,
+                                                       const double* __restrict__ zc, const unsigned char* __restrict__ rep,
+                                                       double* __restrict__ out, long P) {
+    const long tile = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (tile * 16 >= P) return;
+    const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    const long row0 = tile * 16;
+    d4 acc = {0, 0, 0, 0};
+    const int t = tile_leaf[tile];
+    if (t >= 0) {
+        const int e1 = chain_ptr[t + 1];
+        for (int e = chain_ptr[t]; e < e1; ++e) {
+            const SampleChain c = chain[e];
+            for (int k0 = 0; k0 < c.width; k0 += 16) {
+                const d4 a = load_rowlane(W + row0 * ldw + c.col0 + k0, ldw, r, q);
+                const double* zp = zc + (long)(c.zoff + k0 + q) * 16 + r;
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acc = mfma16(a[s], gld(zp + 64 * s), acc);
+            }
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long row = row0 + q + 4 * j;
+        gst(out + (long)r * P + row, rep[row] ? acc[j] : 0.0);
+    }
+}
+
+// leaf Gram blocks: every row / column that is not one of the leaf's knots becomes a row / column of the identity
+__global__ __launch_bounds__(256) void k_sample_mask(const SampleLeaf* __restrict__ lv, const unsigned char* __restrict__ knot) {
+    const SampleLeaf L = lv[blockIdx.y];
+    const long n2 = (long)L.nr * L.nr;
+    for (long e = (long)blockIdx.x * blockDim.x + threadIdx.x; e < n2; e += (long)gridDim.x * blockDim.x) {
+        const long i = e / L.nr, j = e - i * L.nr;
+        if (!(knot[L.row0 + i] && knot[L.row0 + j])) gst(L.G + e, i == j ? 1.0 : 0.0);
+    }
+}
+
+// leaf term, one workgroup per (16-row tile, leaf): out[s][row0 + i] += sum_{j <= i} L[i][j] zeta_s[j], zeta read at knot rows only
+// (slot n_coarse + row); thread (i = tid & 15, s = tid >> 4), 16 draws per chunk of 16 columns staged in LDS
+__global__ __launch_bounds__(256) void k_sample_leaf(const SampleLeaf* __restrict__ lv, const unsigned char* __restrict__ knot,
+                                                     const unsigned char* __restrict__ rep, SampleZ zs, long n_coarse,
+                                                     double* __restrict__ out, long P) {
+    const SampleLeaf L = lv[blockIdx.y];
+    const int tile = blockIdx.x;
+    if (tile * 16 >= L.nr) return;
+    __shared__ double zl[16][17];
+    const int il = threadIdx.x & 15, s = threadIdx.x >> 4;
+    const int i = tile * 16 + il;
+    double acc = 0.0;
+    for (int j0 = 0; j0 <= tile * 16; j0 += 16) {
+        {
+            const int jl = threadIdx.x & 15;              // thread (jl, s) draws zeta_s[j0 + jl]
+            const long row = L.row0 + j0 + jl;
+            zl[s][jl] = knot[row] ? sample_z(zs, n_coarse + row, s) : 0.0;
+        }
+        __syncthreads();
+        const double* lp = L.G + (long)i * L.nr + j0;
+#pragma unroll
+        for (int k = 0; k < 16; ++k)
+            if (j0 + k <= i) acc += gld(lp + k) * zl[s][k];
+        __syncthreads();
+    }
+    const long row = L.row0 + i;
+    if (rep[row]) out[(long)s * P + row] += acc;
+}
+
+// conditional glue: pseudo-data y_o - x_o - sqrt(R) eps_o into the device y (unobserved rows keep their NaN), and x += mean
+__global__ __launch_bounds__(256) void k_sample_pseudo(const double* __restrict__ y_in, const double* __restrict__ x, SampleZ zs, int s,
+                                                       long noise0, double sqrtR, double* __restrict__ y_out, long P) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    const double yo = y_in[i];
+    y_out[i] = (yo == yo) ? yo - x[i] - sqrtR * sample_z(zs, noise0 + i, s) : yo;
+}
+__global__ __launch_bounds__(256) void k_sample_addmean(double* __restrict__ x, const double* __restrict__ mean,
+                                                        const unsigned char* __restrict__ rep, long P) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < P && rep[i]) x[i] += mean[i];
+}
+#endif

@@ -1968,6 +1968,209 @@ static void run_all(mra_plan* pl, uint32_t flags) {
     run_fronts_and_predict(pl, pl->n_levels - 1, false);
 }
 
+// ---- sampler (mra_sample) ------------------------------------------------------------------------------
+// Latent slots: [0, Kn) the non-leaf nodes in node order, cw[level] each; [Kn, Kn + P) leaf terms by padded row (read at leaf knot
+// rows); [Kn + P, Kn + 2P) observation noise by padded row (read at observed rows of a conditional draw).
+static const size_t SAMPLE_GRAM_BUDGET = (size_t)1536 << 20;   // bytes of leaf Gram blocks + inverted diagonal blocks per batch
+
+static void sampler_build(mra_plan* pl) {
+    mra_plan::Sampler& S = pl->smp;
+    if (S.built) return;
+    const long P = pl->P;
+    S.zoff.assign(pl->n_nodes, -1);
+    long kn = 0;
+    for (int i = 0; i < pl->n_nodes; ++i)
+        if (!pl->leaf[i]) { S.zoff[i] = kn; kn += pl->cw[pl->node_level[i]]; }
+    S.n_coarse = kn;
+    std::vector<unsigned char> is_knot(P, 0), knot(P, 0), rep(P, 0);
+    for (int i = 0; i < pl->n_nodes; ++i)
+        for (long k = pl->knot_ptr[i]; k < pl->knot_ptr[i + 1]; ++k) {
+            const long row = pl->knot_rows[k];
+            if (row < 0 || row >= P) throw MraError(MRA_ERR_INVALID, "knot row out of range");
+            is_knot[row] = 1;
+            if (pl->leaf[i]) knot[row] = 1;
+        }
+    const size_t nl = pl->leaf_nodes.size();
+    std::vector<int> tile_leaf((size_t)(P / 16), -1), chain_ptr(nl + 1, 0);
+    std::vector<SampleChain> chain;
+    for (size_t t = 0; t < nl; ++t) {
+        const int i = pl->leaf_nodes[t];
+        for (long r = pl->row0[i]; r < pl->row1[i]; ++r) rep[r] = is_knot[r];
+        for (long tl = pl->row0[i] / 16; tl < pl->row1[i] / 16; ++tl) tile_leaf[tl] = (int)t;
+        for (int p = pl->parent[i]; p >= 0; p = pl->parent[p]) {
+            const int k = pl->node_level[p];
+            if (pl->cw[k]) chain.push_back(SampleChain{pl->coff[k], (int)S.zoff[p], pl->cw[k], 0});
+        }
+        chain_ptr[t + 1] = (int)chain.size();
+    }
+    // Gram batches: consecutive leaves while their nr^2 + 16 nr doubles stay within the budget (at least one leaf per batch)
+    S.bat.assign(1, 0);
+    S.bat_rows.clear();
+    size_t cur = 0, gmax = 0, imax = 0, ncur = 0, nmax = 0, icur = 0;
+    long rmax = 0;
+    std::vector<long> goff(nl), ioff(nl);
+    for (size_t t = 0; t < nl; ++t) {
+        const int i = pl->leaf_nodes[t];
+        const long nr = pl->row1[i] - pl->row0[i];
+        const size_t need = (size_t)nr * nr + 16 * (size_t)nr;
+        if (ncur && (cur + need) * sizeof(double) > SAMPLE_GRAM_BUDGET) {
+            S.bat.push_back(t); S.bat_rows.push_back(rmax);
+            cur = 0; icur = 0; ncur = 0; rmax = 0;
+        }
+        goff[t] = (long)(cur - icur); ioff[t] = (long)icur;     // cur: Gram + inverted blocks of the batch so far, icur: the latter
+        cur += need; icur += 16 * (size_t)nr; ++ncur; rmax = std::max(rmax, nr);
+        gmax = std::max(gmax, cur - icur); imax = std::max(imax, icur); nmax = std::max(nmax, ncur);
+    }
+    if (nl) { S.bat.push_back(nl); S.bat_rows.push_back(rmax); }
+    S.G.alloc(std::max<size_t>(gmax, 1)); S.invd.alloc(std::max<size_t>(imax, 1));
+    S.dn.alloc(std::max<size_t>(nmax, 1)); S.err.alloc(1);
+    std::vector<SampleLeaf> lv(nl);
+    std::vector<GemmProb> gp(nl);
+    std::vector<PanelProb> cp(nl);
+    for (size_t b = 0; b + 1 < S.bat.size(); ++b)
+        for (size_t t = S.bat[b]; t < S.bat[b + 1]; ++t) {
+            const int i = pl->leaf_nodes[t];
+            const long r0 = pl->row0[i], nr = pl->row1[i] - r0;
+            const int a0 = pl->asuf[pl->node_level[i]];
+            double* G = S.G.p + goff[t];
+            lv[t] = SampleLeaf{G, r0, (int)nr};
+            GemmProb g{};                                    // v_M(S, S) = C(S, S) - W_anc[S] W_anc[S]^T: the residual GEMM's COV epilogue
+            g.A = pl->W.p + r0 * pl->ldw + a0; g.lda = pl->ldw;
+            g.B = g.A; g.ldb = pl->ldw;
+            g.C = G; g.ldc = nr;
+            g.XA = pl->X.p + r0 * pl->d; g.XB = g.XA;
+            g.M = (int)nr; g.N = (int)nr; g.K = pl->Ka - a0;
+            gp[t] = g;
+            cp[t] = PanelProb{G, S.invd.p + ioff[t], nr, (int)(nr / 16), (int)(nr / 16), (int)(t - S.bat[b])};
+        }
+    S.rep.upload(rep); S.knot.upload(knot); S.tile_leaf.upload(tile_leaf); S.chain_ptr.upload(chain_ptr);
+    if (chain.empty()) chain.push_back(SampleChain{0, 0, 0, 0});
+    S.chain.upload(chain);
+    if (nl) { S.leaves.upload(lv); S.gram.upload(gp); S.chol.upload(cp); }
+    S.ysave.alloc(P); S.msave.alloc(P); S.vsave.alloc(P);
+    S.factored = -1;
+    S.built = true;
+}
+
+// v_M(K_j, K_j) of a batch of leaves, masked to the identity off the knots, factorised in place
+static void sampler_factor(mra_plan* pl, size_t b) {
+    mra_plan::Sampler& S = pl->smp;
+    const size_t t0 = S.bat[b], n = S.bat[b + 1] - t0;
+    const long rmax = S.bat_rows[b];
+    launch_gemm<EPI_COV>(pl, S.gram.p + t0, n, rmax, rmax);
+    hipLaunchKernelGGL(k_sample_mask, dim3((unsigned)std::min<long>((rmax * rmax + 255) / 256, 64), (unsigned)n), dim3(256), 0, pl->stream,
+                       S.leaves.p + t0, S.knot.p);
+    HIP_TRY(hipMemsetAsync(S.err.p, 0, sizeof(int), pl->stream));
+    hipLaunchKernelGGL(k_panel_chol, dim3((unsigned)n), dim3(256), 0, pl->stream, S.chol.p + t0, S.dn.p, S.err.p, 0);
+    int e = 0;
+    HIP_TRY(hipMemcpyAsync(&e, S.err.p, sizeof(int), hipMemcpyDeviceToHost, pl->stream));
+    HIP_TRY(hipStreamSynchronize(pl->stream));
+    HIP_TRY(hipGetLastError());
+    S.factored = (int)b;
+    if (e) {
+        S.factored = -1;
+        char m[160];
+        snprintf(m, sizeof m, "leaf %d: v_M(K, K) is not positive definite (Cholesky pivot <= 0 or NaN)", pl->leaf_nodes[t0 + e - 1]);
+        throw MraError(MRA_ERR_NOT_SPD, m);
+    }
+}
+
+// the likelihood pass with W at every row: the prior basis the sampler reads (option 17 is overridden here, not through the option)
+static void sampler_prior(mra_plan* pl) {
+    const bool keep = pl->use_lik_rows;
+    pl->use_lik_rows = false;
+    try { run_all(pl, MRA_RUN_LIKELIHOOD); } catch (...) { pl->use_lik_rows = keep; throw; }
+    pl->use_lik_rows = keep;
+}
+
+static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, int64_t sample0, const double* z, double* out) {
+    if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
+    const bool cond = flags & MRA_SAMPLE_CONDITIONAL;
+    if (flags & ~MRA_SAMPLE_CONDITIONAL) throw MraError(MRA_ERR_INVALID, "unknown mra_sample flags");
+    if (!(pl->have_locs && pl->have_kernel)) throw MraError(MRA_ERR_STATE, "mra_sample needs set_locs and set_kernel first");
+    // (the prior basis is computed by the plan's likelihood pass, which reads the observation layout: set_obs comes first either way)
+    if (!pl->have_obs) throw MraError(MRA_ERR_STATE, "mra_sample needs set_obs first");
+    if (pl->host_cov || pl->kp.kind == MRA_KERNEL_HOST) throw MraError(MRA_ERR_INVALID, "mra_sample: MRA_KERNEL_HOST plans cannot sample (leaf C(S, S) is not available)");
+    if (pl->reduce_level >= 0 || pl->comm || pl->n_ranks > 1) throw MraError(MRA_ERR_INVALID, "mra_sample: sharded plans cannot sample");
+    if (n < 0) throw MraError(MRA_ERR_INVALID, "n_samples < 0");
+    if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
+    if (n == 0) return;
+    if (!out) throw MraError(MRA_ERR_INVALID, "out is NULL");
+    HIP_TRY(mraSetDevice(pl->device));
+    sampler_build(pl);
+    mra_plan::Sampler& S = pl->smp;
+    const long P = pl->P, Kn = S.n_coarse, n_slots = Kn + 2 * P;
+    const size_t nb = S.bat.size() - 1;
+    // caller-given draws are staged a block of samples at a time (at most 512 MB of them)
+    const int nsb = z ? (int)std::max<long>(1, std::min<long>(16, ((long)512 << 20) / (8 * n_slots))) : 16;
+    if (S.zc.n < (size_t)std::max<long>(Kn, 1) * 16) S.zc.alloc((size_t)std::max<long>(Kn, 1) * 16);
+    if (S.out.n < (size_t)16 * P) S.out.alloc((size_t)16 * P);
+    if (z && S.zh.n < (size_t)nsb * n_slots) S.zh.alloc((size_t)nsb * n_slots);
+    // what the caller will read back afterwards: the last mra_run's results and the device y
+    const bool had_ran = pl->ran;
+    const uint32_t had_flags = pl->run_flags;
+    const double had_d = pl->res_d, had_u = pl->res_u;
+    const bool had_pred = had_ran && (had_flags & MRA_RUN_PREDICT);
+    HIP_TRY(hipMemcpyAsync(S.ysave.p, pl->y.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+    if (had_pred) {
+        HIP_TRY(hipMemcpyAsync(S.msave.p, pl->mean.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+        HIP_TRY(hipMemcpyAsync(S.vsave.p, pl->var.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+    }
+    auto restore = [&]() {
+        hipMemcpyAsync(pl->y.p, S.ysave.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream);
+        if (had_pred) {
+            hipMemcpyAsync(pl->mean.p, S.msave.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream);
+            hipMemcpyAsync(pl->var.p, S.vsave.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream);
+        }
+        hipStreamSynchronize(pl->stream);
+        pl->ran = had_ran; pl->run_flags = had_flags; pl->res_d = had_d; pl->res_u = had_u;
+    };
+    try {
+        S.factored = -1;                      // the kernel, the locations or the observations may have changed since the last call
+        bool w_prior = false;
+        for (int64_t s0 = 0; s0 < n; s0 += nsb) {
+            const int ns = (int)std::min<int64_t>(nsb, n - s0);
+            SampleZ zs{nullptr, n_slots, (unsigned long long)seed, (long)(sample0 + s0), ns};
+            if (z) {
+                HIP_TRY(hipMemcpyAsync(S.zh.p, z + s0 * n_slots, (size_t)ns * n_slots * sizeof(double), hipMemcpyHostToDevice, pl->stream));
+                zs.z = S.zh.p;
+            }
+            if (!w_prior) { sampler_prior(pl); w_prior = true; }
+            // coarse term: all non-leaf draws of the block, then one wave per row tile
+            if (Kn) hipLaunchKernelGGL(k_sample_draw, dim3((unsigned)((Kn * 16 + 255) / 256)), dim3(256), 0, pl->stream, zs, Kn, S.zc.p);
+            hipLaunchKernelGGL(k_sample_coarse, dim3((unsigned)((P / 16 + 3) / 4)), dim3(256), 0, pl->stream, pl->W.p, (long)pl->ldw,
+                               S.tile_leaf.p, S.chain_ptr.p, S.chain.p, S.zc.p, S.rep.p, S.out.p, P);
+            // leaf term, batch by batch (a single batch is factorised once per call)
+            for (size_t b = 0; b < nb; ++b) {
+                if (S.factored != (int)b) sampler_factor(pl, b);
+                const size_t t0 = S.bat[b], cnt = S.bat[b + 1] - t0;
+                hipLaunchKernelGGL(k_sample_leaf, dim3((unsigned)((S.bat_rows[b] + 15) / 16), (unsigned)cnt), dim3(256), 0, pl->stream,
+                                   S.leaves.p + t0, S.knot.p, S.rep.p, zs, Kn, S.out.p, P);
+            }
+            if (cond) {
+                // conditioning by kriging: x + mean_MRA(y - x_o - sqrt(R) eps), one likelihood + predict pass per sample
+                for (int s = 0; s < ns; ++s) {
+                    double* xs = S.out.p + (long)s * P;
+                    hipLaunchKernelGGL(k_sample_pseudo, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, pl->stream, S.ysave.p, xs, zs, s,
+                                       Kn + P, std::sqrt(pl->R), pl->y.p, P);
+                    run_all(pl, MRA_RUN_LIKELIHOOD | MRA_RUN_PREDICT);
+                    hipLaunchKernelGGL(k_sample_addmean, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, pl->stream, xs, pl->mean.p, S.rep.p, P);
+                }
+                w_prior = false;              // the predict passes rewrote W
+            }
+            HIP_TRY(hipMemcpyAsync(out + s0 * P, S.out.p, (size_t)ns * P * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
+            HIP_TRY(hipStreamSynchronize(pl->stream));
+            HIP_TRY(hipGetLastError());
+            if (nb > 1) S.factored = -1;      // G holds the last batch only
+        }
+    } catch (...) {
+        restore();
+        throw;
+    }
+    restore();
+    HIP_TRY(hipGetLastError());
+}
+
 // ---- caller-order variants: the permutation work of an end-to-end MRATree(...) call done inside the library -----------------
 // A process-wide pinned staging area (grow-only): gathers land in it, the H2D / D2H copies run at the pinned rate (a pageable
 // 16 MB copy costs ~5 ms, a pinned one ~0.7 ms), and a second plan in the same process does not pay for the allocation again.
@@ -2343,6 +2546,23 @@ int mra_run_resume(mra_plan* pl) {
         if (!pl->split_pending) throw MraError(MRA_ERR_STATE, "no split run pending");
         HIP_TRY(mraSetDevice(pl->device));
         run_fronts_and_predict(pl, pl->reduce_level, true);
+        return MRA_OK;
+    } catch (const MraError& e) { return fail(pl, e); }
+}
+
+int mra_sample_slots(mra_plan* pl, int64_t* n_slots) {
+    if (!pl || !n_slots) return MRA_ERR_INVALID;
+    long kn = 0;
+    for (int i = 0; i < pl->n_nodes; ++i)
+        if (!pl->leaf[i]) kn += pl->cw[pl->node_level[i]];
+    *n_slots = kn + 2 * pl->P;
+    return MRA_OK;
+}
+
+int mra_sample(mra_plan* pl, uint32_t flags, int64_t n_samples, uint64_t seed, int64_t sample0, const double* z, double* out) {
+    if (!pl) return MRA_ERR_INVALID;
+    try {
+        sample_all(pl, flags, n_samples, seed, sample0, z, out);
         return MRA_OK;
     } catch (const MraError& e) { return fail(pl, e); }
 }

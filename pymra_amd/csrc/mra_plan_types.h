@@ -401,6 +401,24 @@ struct mra_plan {
     bool ktiming = false;
     struct KStat { int launches = 0; double ms = 0, flops = 0, flops_exec = 0, bytes = 0; } kstat[KF_COUNT];
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> kev;
+    // sampler (mra_sample): index maps built and device buffers allocated on the first call, so that a plan that never samples keeps
+    // its footprint.  Leaves go through their Gram / factor stage in batches of bounded size (batch b = leaves [bat[b], bat[b+1])).
+    struct Sampler {
+        bool built = false;
+        long n_coarse = 0;                        // latent slots of the non-leaf nodes
+        std::vector<long> zoff;                   // per node: its first latent slot (-1: leaf)
+        DevVec<unsigned char> rep, knot;          // [P] reported row; knot row of its leaf
+        DevVec<int> tile_leaf, chain_ptr;         // [P / 16] leaf of a row tile (-1: none); [n_leaves + 1] into chain
+        DevVec<SampleChain> chain;
+        DevVec<SampleLeaf> leaves;                // every leaf, G pointing into the batch buffer
+        DevVec<GemmProb> gram;
+        DevVec<PanelProb> chol;
+        std::vector<size_t> bat;
+        std::vector<long> bat_rows;               // largest leaf of a batch
+        DevVec<double> G, invd, zc, out, zh, ysave, msave, vsave, dn;
+        DevVec<int> err;
+        int factored = -1;                        // batch whose factors G holds (-1: none)
+    } smp;
     // comm
     void* rccl = nullptr;
     ncclComm_t comm = nullptr;

@@ -35,6 +35,7 @@ MRA_OPT_PRIOR_LEVEL = 15
 MRA_OPT_HI_FOLD = 16
 MRA_OPT_LIK_ROWS = 17
 MRA_OPT_CASCADE_GROUP = 18
+MRA_SAMPLE_CONDITIONAL = 1
 MRA_BLOCK_W_ROWS, MRA_BLOCK_LPRIOR, MRA_BLOCK_FRONT, MRA_BLOCK_LEAF = 0, 1, 2, 3
 
 ERR_NAMES = {-1: "MRA_ERR_INVALID", -2: "MRA_ERR_HIP", -3: "MRA_ERR_NOT_SPD", -4: "MRA_ERR_STATE",
@@ -44,7 +45,7 @@ ERR_NAMES = {-1: "MRA_ERR_INVALID", -2: "MRA_ERR_HIP", -3: "MRA_ERR_NOT_SPD", -4
 EXPORTS = [
     "mra_device_count", "mra_release_cached_memory", "mra_plan_create", "mra_plan_destroy", "mra_plan_set_locs", "mra_plan_set_obs",
     "mra_plan_set_kernel", "mra_plan_set_locs_rows", "mra_plan_set_obs_rows", "mra_get_predict_rows", "mra_get_predict_rows_sd", "mra_eval_kernel", "mra_plan_set_cov_block", "mra_run", "mra_get_likelihood", "mra_get_predict",
-    "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
+    "mra_sample_slots", "mra_sample", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
     "mra_get_kernel_stats", "mra_get_kernel_work", "mra_device_synchronize", "mra_plan_info", "mra_comm_unique_id", "mra_comm_init",
     "mra_plan_set_reduce_level", "mra_reduce_size", "mra_reduce_export", "mra_reduce_import",
     "mra_run_resume", "mra_last_error", "mra_version",
@@ -97,6 +98,8 @@ def load_library():
         "mra_run_resume": (C.c_int, [vp]),
         "mra_get_likelihood": (C.c_int, [vp, C.POINTER(dbl), C.POINTER(dbl)]),
         "mra_get_predict": (C.c_int, [vp, vp, vp]),
+        "mra_sample_slots": (C.c_int, [vp, C.POINTER(i64)]),
+        "mra_sample": (C.c_int, [vp, u32, i64, C.c_uint64, i64, vp, vp]),
         "mra_get_buffer": (C.c_int, [vp, C.c_int, vp, i64, C.POINTER(i64)]),
         "mra_get_node_block": (C.c_int, [vp, i32, C.c_int, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
         "mra_get_timers": (C.c_int, [vp, vp, C.c_int]),
@@ -301,6 +304,29 @@ class HipPlan:
         self._check(self.lib.mra_get_predict_rows_sd(self._h, _ptr(perm), _ptr(in_leaf), int(t.N), _ptr(mean), _ptr(var),
                                                      None if sd is None else _ptr(sd)))
         return (mean, var, sd) if with_sd else (mean, var)
+
+    def sample_slots(self):
+        """Number of latent slots of one draw (include/mra_hip.h: non-leaf nodes, leaf terms by padded row, noise by padded row)."""
+        n = C.c_int64()
+        self._check(self.lib.mra_sample_slots(self._h, C.byref(n)))
+        return int(n.value)
+
+    def sample(self, n, seed=0, z=None, conditional=False, sample0=0):
+        """(n, P) draws from the MRA prior (conditional=False) or posterior, padded leaf order, unreported rows 0.  z: None = Philox
+        draws on the device, a pure function of (seed, slot, sample0 + s); else an (n, sample_slots()) array of latent draws."""
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        out = np.empty((n, self.topo.P))
+        zp = None
+        if z is not None:
+            z = np.ascontiguousarray(z, dtype=np.float64)
+            if z.shape != (n, self.sample_slots()):
+                raise ValueError("z must have shape (n, sample_slots()) = (%d, %d)" % (n, self.sample_slots()))
+            zp = _ptr(z)
+        flags = MRA_SAMPLE_CONDITIONAL if conditional else 0
+        self._check(self.lib.mra_sample(self._h, flags, n, int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample0), zp, _ptr(out)))
+        return out
 
     def buffer(self, what):
         n = C.c_int64()
