@@ -9,8 +9,10 @@
  * pyMRA maintainer would add.
  *
  * Conventions: every function returns 0 on success and a negative MRA_ERR_* code on failure and
- * never throws; mra_last_error() gives the message.  Host pointers passed in are copied before the
- * call returns and never retained.  Results are written only into caller-allocated host buffers.
+ * never throws (a C++ exception from inside the library, std::bad_alloc included, comes back as
+ * MRA_ERR_INVALID with its what() text); mra_last_error() gives the message.  Host pointers
+ * passed in are copied before the call returns and never retained.  Results are written only
+ * into caller-allocated host buffers.
  * A plan is bound to one GPU and one internal HIP stream; it is not thread-safe.
  * All floating point data is IEEE binary64, all row indices refer to the caller's padded,
  * leaf-ordered row space (see mra_topology).

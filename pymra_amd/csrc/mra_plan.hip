@@ -12,6 +12,7 @@
 #include "mra_topology.h"
 #include <atomic>
 #include <chrono>
+#include <memory>
 #include <mutex>
 #include <thread>
 
@@ -2077,10 +2078,9 @@ static void sampler_factor(mra_plan* pl, size_t b) {
 
 // the likelihood pass with W at every row: the prior basis the sampler reads (option 17 is overridden here, not through the option)
 static void sampler_prior(mra_plan* pl) {
-    const bool keep = pl->use_lik_rows;
+    struct Keep { mra_plan* p; bool v; ~Keep() { p->use_lik_rows = v; } } keep{pl, pl->use_lik_rows};      // success and error paths
     pl->use_lik_rows = false;
-    try { run_all(pl, MRA_RUN_LIKELIHOOD); } catch (...) { pl->use_lik_rows = keep; throw; }
-    pl->use_lik_rows = keep;
+    run_all(pl, MRA_RUN_LIKELIHOOD);
 }
 
 static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, int64_t sample0, const double* z, double* out) {
@@ -2125,7 +2125,8 @@ static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, i
         hipStreamSynchronize(pl->stream);
         pl->ran = had_ran; pl->run_flags = had_flags; pl->res_d = had_d; pl->res_u = had_u;
     };
-    try {
+    {
+        struct OnExit { decltype(restore)& f; ~OnExit() { f(); } } on_exit{restore};     // success and error paths alike
         S.factored = -1;                      // the kernel, the locations or the observations may have changed since the last call
         bool w_prior = false;
         for (int64_t s0 = 0; s0 < n; s0 += nsb) {
@@ -2163,11 +2164,7 @@ static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, i
             HIP_TRY(hipGetLastError());
             if (nb > 1) S.factored = -1;      // G holds the last batch only
         }
-    } catch (...) {
-        restore();
-        throw;
     }
-    restore();
     HIP_TRY(hipGetLastError());
 }
 
@@ -2231,6 +2228,220 @@ static void set_knot_coords_src(mra_plan* pl, const double* locs, const int64_t*
     }
 }
 
+// ---- one plan lifetime ------------------------------------------------------------------------------------------------------
+// Every plan is released by destroy_plan (mra_plan_destroy and every failed construction alike), so all of them give back the
+// same things: the RCCL communicator, the streams' pending work, the events, the arena, the streams and the pinned buffers.
+static void destroy_plan(mra_plan* pl) {
+    if (!pl) return;
+    mraSetDevice(pl->device);
+    if (pl->comm && pl->rccl) {
+        typedef ncclResult_t (*destroy_t)(ncclComm_t);
+        destroy_t fn = (destroy_t)dlsym(pl->rccl, "ncclCommDestroy");
+        if (fn) fn(pl->comm);
+    }
+    // the plan's device blocks go back to the cache and may be handed to another plan at once: nothing of this plan may still run
+    if (pl->stream) hipStreamSynchronize(pl->stream);
+    if (pl->stream2) hipStreamSynchronize(pl->stream2);
+    for (int k = 0; k < 6; ++k) if (pl->ev[k]) hipEventDestroy(pl->ev[k]);
+    drop_arena(pl);
+    return_streams(pl);                              // (with the pinned result record and the arena's pinned mirror)
+    if (pl->ev_fork) hipEventDestroy(pl->ev_fork);
+    if (pl->ev_join) hipEventDestroy(pl->ev_join);
+    delete pl;
+}
+struct PlanDeleter { void operator()(mra_plan* pl) const { destroy_plan(pl); } };
+typedef std::unique_ptr<mra_plan, PlanDeleter> PlanPtr;
+
+// A new plan on `device` with its streams, events and descriptor arena; the caller copies the topology in and runs build_static.
+static PlanPtr new_plan(int device) {
+    if (!g_dry) {
+        int ndev = 0;
+        if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
+            throw MraError(MRA_ERR_HIP, "no HIP device available: libmra_hip needs an AMD GPU (gfx950); there is no CPU fallback");
+        if (device < 0 || device >= ndev) throw MraError(MRA_ERR_INVALID, "device ordinal out of range");
+    }
+    HIP_TRY(mraSetDevice(device));
+    PlanPtr pl(new mra_plan());
+    pl->device = device;
+    if (!g_dry) {
+        // The leaf update (one large GEMM) and [parent SYRK -> front Cholesky/Schur chain -> all-reduce of a sharded run]
+        // only meet again in the predictive cascade: they are issued on two streams, so the collective and the
+        // latency-bound chain never wait behind the update.  (On one GPU the update keeps every SIMD's register file
+        // full and the pass time does not change; the point is the sharded run.)
+        acquire_streams(pl.get());
+        HIP_TRY(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(&pl->ev_join, hipEventDisableTiming));
+        for (int k = 0; k < 6; ++k) HIP_TRY(hipEventCreate(&pl->ev[k]));
+    }
+    init_arena(pl.get());
+    return pl;
+}
+
+// ---- the C ABI's one exception boundary -------------------------------------------------------------------------------------
+// The exports run their bodies through guarded(): an MraError returns its code, any other C++ exception (std::bad_alloc, the
+// std::system_error of a thread that cannot start, ...) MRA_ERR_INVALID with its what(), anything else MRA_ERR_INVALID "unknown
+// C++ exception"; the message goes to pl->err (pl not NULL) and to the calling thread's g_last_error.  Only exports that read
+// plain fields stay outside it (tests/test_capi_cpu.py holds the same list): mra_version, mra_last_error, mra_device_count,
+// mra_kernel_family_count, mra_get_timers, mra_plan_info, mra_get_kernel_stats, mra_get_kernel_work, mra_tree_sizes.
+template <class F>
+static int guarded(mra_plan* pl, F&& body) {
+    try { return body(); }
+    catch (const MraError& e) { return fail(pl, e); }
+    catch (const std::exception& e) { return fail(pl, MraError(MRA_ERR_INVALID, e.what())); }
+    catch (...) { return fail(pl, MraError(MRA_ERR_INVALID, "unknown C++ exception")); }
+}
+// argument checks of the exports, inside guarded(): the message names the function
+static void require(bool ok, const char* msg) { if (!ok) throw MraError(MRA_ERR_INVALID, msg); }
+
+// ---- inputs and results in padded leaf order (the exports, their caller-order variants and the one-call constructor) ----------
+static void set_locs(mra_plan* pl, const double* locs) {
+    HIP_TRY(mraSetDevice(pl->device));
+    HIP_TRY(mraMemcpy(pl->X.p, locs, (size_t)pl->P * pl->d * sizeof(double), hipMemcpyHostToDevice));
+    if (!pl->knots_pending) set_knot_coords(pl, locs);
+    pl->have_locs = true;
+}
+
+static void set_obs(mra_plan* pl, const double* y, double R) {
+    if (!(R > 0.0)) throw MraError(MRA_ERR_INVALID, "R must be a positive scalar");
+    HIP_TRY(mraSetDevice(pl->device));
+    HIP_TRY(mraMemcpy(pl->y.p, y, (size_t)pl->P * sizeof(double), hipMemcpyHostToDevice));
+    pl->R = R;
+    if (pl->host_cov) {
+        // host-evaluated covariance blocks are per observed row: a new observation pattern invalidates them (and
+        // build_leaf rebuilds the leaf descriptors without their Csrc pointers).  The caller has to select
+        // MRA_KERNEL_HOST and upload the blocks again; until then mra_run reports MRA_ERR_STATE.
+        pl->host_cov = false;
+        pl->have_kernel = false;
+        pl->covsrc.release();
+        pl->covdiag.release();
+        for (auto& lv : pl->lev)
+            if (!lv.nodes.empty()) {
+                for (auto& g : lv.hResid) { g.Csrc = nullptr; g.ldcs = 0; }
+                lv.gResid.upload(lv.hResid);
+            }
+    }
+    build_leaf(pl, y);
+    pl->have_obs = true;
+}
+
+static void get_predict(mra_plan* pl, double* mean, double* var) {
+    if (!pl->ran || !(pl->run_flags & MRA_RUN_PREDICT)) throw MraError(MRA_ERR_STATE, "mra_run with MRA_RUN_PREDICT has not completed");
+    HIP_TRY(mraSetDevice(pl->device));
+    HIP_TRY(mraMemcpy(mean, pl->mean.p, (size_t)pl->P * sizeof(double), hipMemcpyDeviceToHost));
+    HIP_TRY(mraMemcpy(var, pl->var.p, (size_t)pl->P * sizeof(double), hipMemcpyDeviceToHost));
+}
+
+// mean, var (and sd when not NULL) in the caller's row order
+static void get_predict_rows(mra_plan* pl, const int64_t* perm, const uint8_t* in_leaf, int64_t N, double* mean, double* var, double* sd) {
+    PlanTrace tr("get_predict_rows");
+    std::lock_guard<std::mutex> lock(g_stage_mutex);
+    double* st = stage_buffer((size_t)pl->P * 2);
+    tr.mark("staging buffer");
+    get_predict(pl, st, st + pl->P);
+    tr.mark("D2H mean, var");
+    const double* mp = st; const double* vp = st + pl->P;
+    // rows that no leaf reports (dropped by a partition, or another rank's) read 0 - written only when there are such rows
+    std::atomic<int64_t> covered{0};
+    parallel_rows(pl->P, [&](int64_t a, int64_t b) {
+        int64_t c = 0;
+        for (int64_t p = a; p < b; ++p) c += (in_leaf[p] && perm[p] >= 0 && perm[p] < N) ? 1 : 0;
+        covered += c;
+    });
+    if (covered.load() != N) {
+        parallel_rows(N, [&](int64_t a, int64_t b) { for (int64_t i = a; i < b; ++i) { mean[i] = 0.0; var[i] = 0.0; if (sd) sd[i] = 0.0; } });
+        tr.mark("zero the caller's arrays");
+    }
+    // every caller row sits in at most one padded row, so the scatter has no write conflicts between threads
+    parallel_rows(pl->P, [&](int64_t a, int64_t b) {
+        for (int64_t p = a; p < b; ++p) if (in_leaf[p]) {
+            const int64_t i = perm[p];
+            if (i >= 0 && i < N) { mean[i] = mp[p]; var[i] = vp[p]; if (sd) sd[i] = std::sqrt(vp[p]); }
+        }
+    });
+}
+
+// ---- native tree replay (host only, no GPU needed) ---------------------------------------------------
+struct mra_tree { mra_topo::Result r; };
+
+// The replay behind the three replay exports; the tree is handed out only when the replay succeeds (nullptr: not a large-2-D tree).
+// perm, src, in_leaf, knot_rows: the caller's arrays that the replay fills in place, or all nullptr.
+static std::unique_ptr<mra_tree> replay_tree(const double* locs, int64_t N, int32_t r, int32_t M, uint32_t* mt_key, int32_t* mt_pos,
+                                             int64_t* perm = nullptr, int64_t* src = nullptr, uint8_t* in_leaf = nullptr,
+                                             int64_t* knot_rows = nullptr, mra_topo::LayoutHook hook = nullptr, void* hook_user = nullptr) {
+    std::unique_ptr<mra_tree> t(new mra_tree());
+    t->r.ext_perm = perm; t->r.ext_src = src; t->r.ext_in_leaf = in_leaf; t->r.ext_knot_rows = knot_rows;
+    if (mra_topo::replay_quadtree(locs, N, r, M, mt_key, mt_pos, t->r, hook, hook_user) != 0) t.reset();
+    return t;
+}
+
+// ---- MRATree.__init__ for large 2-D trees in one call ---------------------------------------------------------------------------
+// The tree replay and the plan construction of an end-to-end MRATree(...) call, overlapped: as soon as the replay has the
+// partition and the row layout (everything but the knots), a helper thread sizes and allocates the plan, gathers and uploads the
+// locations and the observations and builds the leaf descriptors - while the caller's thread is still drawing knots, the one
+// sequential part (it has to consume NumPy's MT19937 stream in the reference's order).  The knot rows, the leaves' knot
+// counts and the knot coordinates go in when both are done.
+namespace {
+struct ReplayPlanCtx {
+    const double* locs; const double* y; double R; int device;
+    PlanPtr pl;                       // destroyed with the context unless mra_plan_create_replay_2d hands it out
+    int rc = MRA_OK;
+    std::string err;
+};
+// (runs on a helper thread of the replay and must not throw: a failure reaches the caller's thread as rc and err)
+void replay_plan_hook(void* user, const mra_topo::Result& t) {
+    ReplayPlanCtx& c = *(ReplayPlanCtx*)user;
+    c.rc = guarded(nullptr, [&] {
+        PlanTrace tr("plan beside the knot draws");
+        PlanPtr pl = new_plan(c.device);
+        pl->knots_pending = true;
+        pl->P = t.P; pl->d = 2; pl->n_levels = t.n_levels; pl->n_nodes = t.n_nodes;
+        pl->level_ptr.assign(t.level_ptr.begin(), t.level_ptr.end());
+        pl->row0.assign(t.row0.begin(), t.row0.end());
+        pl->row1.assign(t.row1.begin(), t.row1.end());
+        pl->leaf.assign(t.leaf.begin(), t.leaf.end());
+        pl->parent.assign(t.parent.begin(), t.parent.end());
+        pl->child_ptr.assign(t.child_ptr.begin(), t.child_ptr.end());
+        pl->child_list.assign(t.child_list.begin(), t.child_list.end());
+        pl->knot_ptr.assign(t.knot_ptr.begin(), t.knot_ptr.end());      // non-leaf nodes final; the leaves' entries are provisional
+        pl->cw.assign(t.cw.begin(), t.cw.end());
+        tr.mark("streams, events, arena, copies of the topology");
+        const int64_t* src = t.ext_perm ? t.ext_src : t.src.data();
+        const int64_t* perm = t.ext_perm ? t.ext_perm : t.perm.data();
+        std::lock_guard<std::mutex> lock(g_stage_mutex);
+        double* xp = stage_buffer((size_t)pl->P * 3);
+        double* yp = xp + (size_t)pl->P * 2;
+        // the gather of locations and observations into leaf order runs beside build_static (neither needs the other)
+        const long P = pl->P;
+        bool gather_failed = false;
+        std::thread gather([&, P]() {
+            const double nan = std::nan("");
+            const double* locs = c.locs; const double* y = c.y;
+            try {
+                parallel_rows(P, [&](int64_t a, int64_t b) {
+                    for (int64_t p = a; p < b; ++p) {
+                        const int64_t q = src[p];
+                        xp[2 * p] = locs[2 * q]; xp[2 * p + 1] = locs[2 * q + 1];
+                        yp[p] = perm[p] < 0 ? nan : y[q];
+                    }
+                });
+            } catch (...) { gather_failed = true; }
+        });
+        struct Join { std::thread& t; ~Join() { if (t.joinable()) t.join(); } } join{gather};
+        build_static(pl.get());
+        tr.mark("build_static");
+        gather.join();
+        if (gather_failed) throw MraError(MRA_ERR_INVALID, "gathering locations / observations failed (thread creation)");
+        tr.mark("(gather of locations and observations: beside it)");
+        set_locs(pl.get(), xp);
+        set_obs(pl.get(), yp, c.R);
+        tr.mark("uploads, leaf descriptors");
+        c.pl = std::move(pl);
+        return MRA_OK;
+    });
+    if (c.rc != MRA_OK) c.err = g_last_error;                // (this thread's)
+}
+}  // namespace
+
 // ------------------------------------------------------------------------------------------------
 //  C ABI
 // ------------------------------------------------------------------------------------------------
@@ -2247,22 +2458,14 @@ int mra_device_count(void) {
 }
 
 int mra_plan_create(mra_plan** out, const mra_topology* t, int device) {
-    if (!out || !t) return MRA_ERR_INVALID;
-    *out = nullptr;
-    mra_plan* pl = nullptr;
-    try {
+    return guarded(nullptr, [&] {
+        require(out && t, "mra_plan_create: out or topology is NULL");
+        *out = nullptr;
         if (t->P <= 0 || (t->d != 1 && t->d != 2) || t->n_levels <= 0 || t->n_nodes <= 0)
             throw MraError(MRA_ERR_INVALID, "bad topology header");
-        int ndev = 0;
-        if (!g_dry) {
-            if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-                throw MraError(MRA_ERR_HIP, "no HIP device available: libmra_hip needs an AMD GPU (gfx950); there is no CPU fallback");
-            if (device < 0 || device >= ndev) throw MraError(MRA_ERR_INVALID, "device ordinal out of range");
-        }
         PlanTrace tr("mra_plan_create");
-        HIP_TRY(mraSetDevice(device));
-        pl = new mra_plan();
-        pl->device = device;
+        PlanPtr pl = new_plan(device);
+        tr.mark("streams, events, arena");
         pl->P = t->P; pl->d = t->d; pl->n_levels = t->n_levels; pl->n_nodes = t->n_nodes;
         pl->level_ptr.assign(t->level_ptr, t->level_ptr + t->n_levels + 1);
         pl->row0.assign(t->node_row0, t->node_row0 + t->n_nodes);
@@ -2276,88 +2479,41 @@ int mra_plan_create(mra_plan** out, const mra_topology* t, int device) {
         pl->cw.assign(t->cw, t->cw + t->n_levels);
         if (pl->level_ptr[0] != 0 || pl->level_ptr.back() != t->n_nodes) throw MraError(MRA_ERR_INVALID, "level_ptr inconsistent");
         tr.mark("copies of the topology");
-        if (!g_dry) {
-            // The leaf update (one large GEMM) and [parent SYRK -> front Cholesky/Schur chain -> all-reduce of a sharded run]
-            // only meet again in the predictive cascade: they are issued on two streams, so the collective and the
-            // latency-bound chain never wait behind the update.  (On one GPU the update keeps every SIMD's register file
-            // full and the pass time does not change; the point is the sharded run.)
-            acquire_streams(pl);
-            HIP_TRY(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&pl->ev_join, hipEventDisableTiming));
-        }
-        for (int k = 0; k < 6 && !g_dry; ++k) HIP_TRY(hipEventCreate(&pl->ev[k]));
-        tr.mark("streams, events");
-        init_arena(pl);
-        build_static(pl);
-        *out = pl;
+        build_static(pl.get());
+        *out = pl.release();
         return MRA_OK;
-    } catch (const MraError& e) {
-        int rc = fail(nullptr, e);
-        if (pl) drop_arena(pl);
-        if (pl && !g_dry) return_streams(pl);
-        delete pl;
-        return rc;
-    } catch (const std::exception& e) {
-        g_last_error = e.what();
-        if (pl) drop_arena(pl);
-        if (pl && !g_dry) return_streams(pl);
-        delete pl;
-        return MRA_ERR_INVALID;
-    }
+    });
 }
 
-int mra_plan_destroy(mra_plan* pl) {
-    if (!pl) return MRA_OK;
-    mraSetDevice(pl->device);
-    if (pl->comm && pl->rccl) {
-        typedef ncclResult_t (*destroy_t)(ncclComm_t);
-        destroy_t fn = (destroy_t)dlsym(pl->rccl, "ncclCommDestroy");
-        if (fn) fn(pl->comm);
-    }
-    // the plan's device blocks go back to the cache and may be handed to another plan at once: nothing of this plan may still run
-    if (pl->stream) hipStreamSynchronize(pl->stream);
-    if (pl->stream2) hipStreamSynchronize(pl->stream2);
-    for (int k = 0; k < 6; ++k) if (pl->ev[k]) hipEventDestroy(pl->ev[k]);
-    drop_arena(pl);
-    return_streams(pl);                              // (with the pinned result record and the arena's pinned mirror)
-    if (pl->ev_fork) hipEventDestroy(pl->ev_fork);
-    if (pl->ev_join) hipEventDestroy(pl->ev_join);
-    delete pl;
-    return MRA_OK;
-}
+int mra_plan_destroy(mra_plan* pl) { return guarded(nullptr, [&] { destroy_plan(pl); return MRA_OK; }); }     // (pl->err dies with pl)
 
 int mra_release_cached_memory(void) {
-    mra_topo::release_scratch();                      // the tree replay's work arrays (~100 MB at 1024^2, ~0.5 GB at config 5)
-    if (g_dry) return MRA_OK;
-    {
-        std::lock_guard<std::mutex> lock(g_streams_mu);
-        for (auto& e : g_streams) { hipStreamDestroy(e.second.hi); hipStreamDestroy(e.second.lo); if (e.second.host_res) hipHostFree(e.second.host_res); if (e.second.arena_host) hipHostFree(e.second.arena_host); }
-        g_streams.clear();
-    }
-    {
-        std::lock_guard<std::mutex> lock(g_stage_mutex);
-        if (g_stage) { hipHostFree(g_stage); g_stage = nullptr; g_stage_n = 0; }
-    }
-    std::lock_guard<std::mutex> lock(g_pool.mu);
-    g_pool.flush_locked();
-    return MRA_OK;
+    return guarded(nullptr, [&] {
+        mra_topo::release_scratch();                      // the tree replay's work arrays (~100 MB at 1024^2, ~0.5 GB at config 5)
+        if (g_dry) return MRA_OK;
+        {
+            std::lock_guard<std::mutex> lock(g_streams_mu);
+            for (auto& e : g_streams) { hipStreamDestroy(e.second.hi); hipStreamDestroy(e.second.lo); if (e.second.host_res) hipHostFree(e.second.host_res); if (e.second.arena_host) hipHostFree(e.second.arena_host); }
+            g_streams.clear();
+        }
+        {
+            std::lock_guard<std::mutex> lock(g_stage_mutex);
+            if (g_stage) { hipHostFree(g_stage); g_stage = nullptr; g_stage_n = 0; }
+        }
+        std::lock_guard<std::mutex> lock(g_pool.mu);
+        g_pool.flush_locked();
+        return MRA_OK;
+    });
 }
 
 int mra_plan_set_locs(mra_plan* pl, const double* locs) {
-    if (!pl || !locs) return MRA_ERR_INVALID;
-    try {
-        HIP_TRY(mraSetDevice(pl->device));
-        HIP_TRY(mraMemcpy(pl->X.p, locs, (size_t)pl->P * pl->d * sizeof(double), hipMemcpyHostToDevice));
-        if (!pl->knots_pending) set_knot_coords(pl, locs);
-        pl->have_locs = true;
-        return MRA_OK;
-    } catch (const MraError& e) { return fail(pl, e); }
+    return guarded(pl, [&] { require(pl && locs, "mra_plan_set_locs: plan or locs is NULL"); set_locs(pl, locs); return MRA_OK; });
 }
 
 // ---- caller-order variants (helpers above the extern "C" block)
 int mra_plan_set_locs_rows(mra_plan* pl, const double* locs, const int64_t* src) {
-    if (!pl || !locs || !src) return MRA_ERR_INVALID;
-    try {
+    return guarded(pl, [&] {
+        require(pl && locs && src, "mra_plan_set_locs_rows: plan, locs or src is NULL");
         PlanTrace tr("set_locs_rows");
         std::lock_guard<std::mutex> lock(g_stage_mutex);
         const int d = pl->d;
@@ -2368,97 +2524,50 @@ int mra_plan_set_locs_rows(mra_plan* pl, const double* locs, const int64_t* src)
             else for (int64_t p = a; p < b; ++p) xp[p] = locs[src[p]];
         });
         tr.mark("gather into leaf order");
-        const int rc = mra_plan_set_locs(pl, xp);
+        set_locs(pl, xp);
         tr.mark("upload X, knot coordinates");
-        return rc;
-    } catch (const MraError& e) { return fail(pl, e); }
-      catch (const std::exception& e) { return fail(pl, MraError(MRA_ERR_INVALID, e.what())); }       // bad_alloc, thread creation
+        return MRA_OK;
+    });
 }
 
 int mra_plan_set_obs_rows(mra_plan* pl, const double* y, const int64_t* src, const int64_t* perm, double R) {
-    if (!pl || !y || !src || !perm) return MRA_ERR_INVALID;
-    try {
+    return guarded(pl, [&] {
+        require(pl && y && src && perm, "mra_plan_set_obs_rows: plan, y, src or perm is NULL");
         PlanTrace tr("set_obs_rows");
         std::lock_guard<std::mutex> lock(g_stage_mutex);
         double* yp = stage_buffer((size_t)pl->P);
         const double nan = std::nan("");
         parallel_rows(pl->P, [&](int64_t a, int64_t b) { for (int64_t p = a; p < b; ++p) yp[p] = perm[p] < 0 ? nan : y[src[p]]; });
         tr.mark("gather into leaf order");
-        const int rc = mra_plan_set_obs(pl, yp, R);
+        set_obs(pl, yp, R);
         tr.mark("upload y, build_leaf");
-        return rc;
-    } catch (const MraError& e) { return fail(pl, e); }
-      catch (const std::exception& e) { return fail(pl, MraError(MRA_ERR_INVALID, e.what())); }       // bad_alloc, thread creation
+        return MRA_OK;
+    });
 }
 
 int mra_get_predict_rows(mra_plan* pl, const int64_t* perm, const uint8_t* in_leaf, int64_t N, double* mean, double* var) {
-    return mra_get_predict_rows_sd(pl, perm, in_leaf, N, mean, var, nullptr);
+    return guarded(pl, [&] {
+        require(pl && perm && in_leaf && mean && var && N > 0, "mra_get_predict_rows: plan, perm, in_leaf, mean or var is NULL, or N <= 0");
+        get_predict_rows(pl, perm, in_leaf, N, mean, var, nullptr);
+        return MRA_OK;
+    });
 }
 
 int mra_get_predict_rows_sd(mra_plan* pl, const int64_t* perm, const uint8_t* in_leaf, int64_t N, double* mean, double* var, double* sd) {
-    if (!pl || !perm || !in_leaf || !mean || !var || N <= 0) return MRA_ERR_INVALID;
-    try {
-        PlanTrace tr("get_predict_rows");
-        std::lock_guard<std::mutex> lock(g_stage_mutex);
-        double* st = stage_buffer((size_t)pl->P * 2);
-        tr.mark("staging buffer");
-        const int rc = mra_get_predict(pl, st, st + pl->P);
-        if (rc != MRA_OK) return rc;
-        tr.mark("D2H mean, var");
-        const double* mp = st; const double* vp = st + pl->P;
-        // rows that no leaf reports (dropped by a partition, or another rank's) read 0 - written only when there are such rows
-        std::atomic<int64_t> covered{0};
-        parallel_rows(pl->P, [&](int64_t a, int64_t b) {
-            int64_t c = 0;
-            for (int64_t p = a; p < b; ++p) c += (in_leaf[p] && perm[p] >= 0 && perm[p] < N) ? 1 : 0;
-            covered += c;
-        });
-        if (covered.load() != N) {
-            parallel_rows(N, [&](int64_t a, int64_t b) { for (int64_t i = a; i < b; ++i) { mean[i] = 0.0; var[i] = 0.0; if (sd) sd[i] = 0.0; } });
-            tr.mark("zero the caller's arrays");
-        }
-        // every caller row sits in at most one padded row, so the scatter has no write conflicts between threads
-        parallel_rows(pl->P, [&](int64_t a, int64_t b) {
-            for (int64_t p = a; p < b; ++p) if (in_leaf[p]) {
-                const int64_t i = perm[p];
-                if (i >= 0 && i < N) { mean[i] = mp[p]; var[i] = vp[p]; if (sd) sd[i] = std::sqrt(vp[p]); }
-            }
-        });
+    return guarded(pl, [&] {
+        require(pl && perm && in_leaf && mean && var && N > 0, "mra_get_predict_rows_sd: plan, perm, in_leaf, mean or var is NULL, or N <= 0");
+        get_predict_rows(pl, perm, in_leaf, N, mean, var, sd);
         return MRA_OK;
-    } catch (const MraError& e) { return fail(pl, e); }
-      catch (const std::exception& e) { return fail(pl, MraError(MRA_ERR_INVALID, e.what())); }       // bad_alloc, thread creation
+    });
 }
 
 int mra_plan_set_obs(mra_plan* pl, const double* y, double R) {
-    if (!pl || !y) return MRA_ERR_INVALID;
-    try {
-        if (!(R > 0.0)) throw MraError(MRA_ERR_INVALID, "R must be a positive scalar");
-        HIP_TRY(mraSetDevice(pl->device));
-        HIP_TRY(mraMemcpy(pl->y.p, y, (size_t)pl->P * sizeof(double), hipMemcpyHostToDevice));
-        pl->R = R;
-        if (pl->host_cov) {
-            // host-evaluated covariance blocks are per observed row: a new observation pattern invalidates them (and
-            // build_leaf rebuilds the leaf descriptors without their Csrc pointers).  The caller has to select
-            // MRA_KERNEL_HOST and upload the blocks again; until then mra_run reports MRA_ERR_STATE.
-            pl->host_cov = false;
-            pl->have_kernel = false;
-            pl->covsrc.release();
-            pl->covdiag.release();
-            for (auto& lv : pl->lev)
-                if (!lv.nodes.empty()) {
-                    for (auto& g : lv.hResid) { g.Csrc = nullptr; g.ldcs = 0; }
-                    lv.gResid.upload(lv.hResid);
-                }
-        }
-        build_leaf(pl, y);
-        pl->have_obs = true;
-        return MRA_OK;
-    } catch (const MraError& e) { return fail(pl, e); }
+    return guarded(pl, [&] { require(pl && y, "mra_plan_set_obs: plan or y is NULL"); set_obs(pl, y, R); return MRA_OK; });
 }
 
 int mra_plan_set_kernel(mra_plan* pl, int kind, const double* params, int n) {
-    if (!pl) return MRA_ERR_INVALID;
-    try {
+    return guarded(pl, [&] {
+        require(pl, "mra_plan_set_kernel: plan is NULL");
         if (kind == MRA_KERNEL_HOST) {
             if (!pl->have_obs) throw MraError(MRA_ERR_STATE, "MRA_KERNEL_HOST needs mra_plan_set_obs first (leaf blocks are per observed row)");
             HIP_TRY(mraSetDevice(pl->device));
@@ -2491,7 +2600,8 @@ int mra_plan_set_kernel(mra_plan* pl, int kind, const double* params, int n) {
             pl->have_kernel = true;
             return MRA_OK;
         }
-        if (kind < 0 || kind > MRA_KERNEL_KANTER || !params || n < 3) throw MraError(MRA_ERR_INVALID, "unknown kernel kind or too few parameters (need l, sig, scale)");
+        require(params, "mra_plan_set_kernel: params is NULL");
+        if (kind < 0 || kind > MRA_KERNEL_KANTER || n < 3) throw MraError(MRA_ERR_INVALID, "unknown kernel kind or too few parameters (need l, sig, scale)");
         if (!(params[0] > 0.0)) throw MraError(MRA_ERR_INVALID, "length scale must be positive");
         pl->kp.kind = kind; pl->kp.d = pl->d; pl->kp.l = params[0]; pl->kp.sig = params[1]; pl->kp.scale = params[2];
         pl->kp.circular = (n >= 4 && params[3] != 0.0) ? 1 : 0;
@@ -2500,12 +2610,12 @@ int mra_plan_set_kernel(mra_plan* pl, int kind, const double* params, int n) {
         pl->host_cov = false;
         pl->have_kernel = true;
         return MRA_OK;
-    } catch (const MraError& e) { return fail(pl, e); }
+    });
 }
 
 int mra_plan_set_cov_block(mra_plan* pl, int32_t node, const double* C, int64_t n_rows, int64_t n_cols, const double* diag) {
-    if (!pl || !C) return MRA_ERR_INVALID;
-    try {
+    return guarded(pl, [&] {
+        require(pl && C, "mra_plan_set_cov_block: plan or C is NULL");
         if (!pl->host_cov) throw MraError(MRA_ERR_STATE, "select MRA_KERNEL_HOST with mra_plan_set_kernel first");
         if (node < 0 || node >= pl->n_nodes) throw MraError(MRA_ERR_INVALID, "node out of range");
         HIP_TRY(mraSetDevice(pl->device));
@@ -2528,66 +2638,59 @@ int mra_plan_set_cov_block(mra_plan* pl, int32_t node, const double* C, int64_t 
                                 n_cols * sizeof(double), nr, hipMemcpyHostToDevice));
         if (diag) HIP_TRY(mraMemcpy(pl->covdiag.p + pl->row0[node], diag, nr * sizeof(double), hipMemcpyHostToDevice));
         return MRA_OK;
-    } catch (const MraError& e) { return fail(pl, e); }
+    });
 }
 
 int mra_run(mra_plan* pl, uint32_t flags) {
-    if (!pl) return MRA_ERR_INVALID;
-    try {
+    return guarded(pl, [&] {
+        require(pl, "mra_run: plan is NULL");
         if (!(flags & (MRA_RUN_LIKELIHOOD | MRA_RUN_PREDICT))) throw MraError(MRA_ERR_INVALID, "flags must request likelihood and/or predict");
         run_all(pl, flags);
         return MRA_OK;
-    } catch (const MraError& e) { return fail(pl, e); }
+    });
 }
 
 int mra_run_resume(mra_plan* pl) {
-    if (!pl) return MRA_ERR_INVALID;
-    try {
+    return guarded(pl, [&] {
+        require(pl, "mra_run_resume: plan is NULL");
         if (!pl->split_pending) throw MraError(MRA_ERR_STATE, "no split run pending");
         HIP_TRY(mraSetDevice(pl->device));
         run_fronts_and_predict(pl, pl->reduce_level, true);
         return MRA_OK;
-    } catch (const MraError& e) { return fail(pl, e); }
+    });
 }
 
 int mra_sample_slots(mra_plan* pl, int64_t* n_slots) {
-    if (!pl || !n_slots) return MRA_ERR_INVALID;
-    long kn = 0;
-    for (int i = 0; i < pl->n_nodes; ++i)
-        if (!pl->leaf[i]) kn += pl->cw[pl->node_level[i]];
-    *n_slots = kn + 2 * pl->P;
-    return MRA_OK;
+    return guarded(pl, [&] {
+        require(pl && n_slots, "mra_sample_slots: plan or n_slots is NULL");
+        long kn = 0;
+        for (int i = 0; i < pl->n_nodes; ++i)
+            if (!pl->leaf[i]) kn += pl->cw[pl->node_level[i]];
+        *n_slots = kn + 2 * pl->P;
+        return MRA_OK;
+    });
 }
 
 int mra_sample(mra_plan* pl, uint32_t flags, int64_t n_samples, uint64_t seed, int64_t sample0, const double* z, double* out) {
-    if (!pl) return MRA_ERR_INVALID;
-    try {
-        sample_all(pl, flags, n_samples, seed, sample0, z, out);
-        return MRA_OK;
-    } catch (const MraError& e) { return fail(pl, e); }
+    return guarded(pl, [&] { require(pl, "mra_sample: plan is NULL"); sample_all(pl, flags, n_samples, seed, sample0, z, out); return MRA_OK; });
 }
 
 int mra_get_likelihood(mra_plan* pl, double* d, double* u) {
-    if (!pl || !d || !u) return MRA_ERR_INVALID;
-    if (!pl->ran) return fail(pl, MraError(MRA_ERR_STATE, "mra_run has not completed"));
-    *d = pl->res_d; *u = pl->res_u;
-    return MRA_OK;
+    return guarded(pl, [&] {
+        require(pl && d && u, "mra_get_likelihood: plan, d or u is NULL");
+        if (!pl->ran) throw MraError(MRA_ERR_STATE, "mra_run has not completed");
+        *d = pl->res_d; *u = pl->res_u;
+        return MRA_OK;
+    });
 }
 
 int mra_get_predict(mra_plan* pl, double* mean, double* var) {
-    if (!pl || !mean || !var) return MRA_ERR_INVALID;
-    try {
-        if (!pl->ran || !(pl->run_flags & MRA_RUN_PREDICT)) throw MraError(MRA_ERR_STATE, "mra_run with MRA_RUN_PREDICT has not completed");
-        HIP_TRY(mraSetDevice(pl->device));
-        HIP_TRY(mraMemcpy(mean, pl->mean.p, (size_t)pl->P * sizeof(double), hipMemcpyDeviceToHost));
-        HIP_TRY(mraMemcpy(var, pl->var.p, (size_t)pl->P * sizeof(double), hipMemcpyDeviceToHost));
-        return MRA_OK;
-    } catch (const MraError& e) { return fail(pl, e); }
+    return guarded(pl, [&] { require(pl && mean && var, "mra_get_predict: plan, mean or var is NULL"); get_predict(pl, mean, var); return MRA_OK; });
 }
 
 int mra_get_buffer(mra_plan* pl, int what, double* out, int64_t cap, int64_t* n_avail) {
-    if (!pl || !n_avail) return MRA_ERR_INVALID;
-    try {
+    return guarded(pl, [&] {
+        require(pl && n_avail, "mra_get_buffer: plan or n_avail is NULL");
         HIP_TRY(mraSetDevice(pl->device));
         const double* src = nullptr; int64_t n = 0;
         if (what == 0) { src = pl->W.p; n = (int64_t)pl->W.n; }
@@ -2601,12 +2704,12 @@ int mra_get_buffer(mra_plan* pl, int what, double* out, int64_t cap, int64_t* n_
         *n_avail = n;
         if (out && cap > 0) HIP_TRY(mraMemcpy(out, src, (size_t)std::min(cap, n) * sizeof(double), hipMemcpyDeviceToHost));
         return MRA_OK;
-    } catch (const MraError& e) { return fail(pl, e); }
+    });
 }
 
 int mra_get_node_block(mra_plan* pl, int32_t node, int what, double* out, int64_t cap, int64_t* n_rows, int64_t* n_cols) {
-    if (!pl || !n_rows || !n_cols) return MRA_ERR_INVALID;
-    try {
+    return guarded(pl, [&] {
+        require(pl && n_rows && n_cols, "mra_get_node_block: plan, n_rows or n_cols is NULL");
         if (node < 0 || node >= pl->n_nodes) throw MraError(MRA_ERR_INVALID, "node out of range");
         if (!pl->ran) throw MraError(MRA_ERR_STATE, "mra_run has not completed");
         HIP_TRY(mraSetDevice(pl->device));
@@ -2638,7 +2741,7 @@ int mra_get_node_block(mra_plan* pl, int32_t node, int what, double* out, int64_
         if (out && n > 0) HIP_TRY(mraMemcpy(out, src, (size_t)n * sizeof(double), hipMemcpyDeviceToHost));
         (void)ld;
         return MRA_OK;
-    } catch (const MraError& e) { return fail(pl, e); }
+    });
 }
 
 int mra_get_timers(mra_plan* pl, double* out, int cap) {
@@ -2649,82 +2752,82 @@ int mra_get_timers(mra_plan* pl, double* out, int cap) {
 }
 
 int mra_plan_set_option(mra_plan* pl, int option, int64_t value) {
-    if (!pl) return MRA_ERR_INVALID;
-    // options that change which kernel produces or factorises the leaves' C blocks bring the phantom-row launch back; the others
-    // (timing, front / knot / solve / update variants) never touch C
-    if (option == 2 || option == 3 || option == 6 || option == 11) pl->cphantom_valid = false;
-    if (option == 1) { pl->ktiming = value != 0; return MRA_OK; }
-    if (option == 2) { pl->use_fused = value != 0; return MRA_OK; }
-    if (option == 3) { pl->gemm_lds = value != 0; return MRA_OK; }
-    if (option == 4) { pl->use_front_fused = value != 0; return MRA_OK; }
-    if (option == 5) { pl->use_knot_chain = value != 0; return MRA_OK; }
-    if (option == 6) { pl->use_leaf_gemm = value != 0; pl->leaf_gemm_update = value == 2; return MRA_OK; }
-    if (option == 7) { pl->use_leaf_solve = value != 0; pl->leaf_solve_mode = (int)value; return MRA_OK; }
-    if (option == 8) { pl->use_pred_update = value != 0; return MRA_OK; }
-    if (option == 10) { pl->leaf_solve_split = value == 2 ? 2 : 1; return MRA_OK; }
-    if (option == 11) { pl->use_chol_lds = (int)value; return MRA_OK; }
-    if (option == 12) { pl->seg_gemm_lds = value != 0; return MRA_OK; }
-    if (option == 14) { pl->use_syrk_blk = (int)value; return MRA_OK; }
-    if (option == 15) { pl->use_prior_level = value != 0; return MRA_OK; }
-    if (option == 16) { pl->use_hi_fold = (int)value; return MRA_OK; }
-    if (option == 17) { pl->use_lik_rows = value != 0; return MRA_OK; }
-    if (option == 13) { pl->ut_gather = value != 0; return MRA_OK; }
-    if (option == 18) {
-        if (!pl->regular) return MRA_OK;          // (no fused cascade: nothing is grouped, the decision stays 0)
-        try {
+    return guarded(pl, [&] {
+        require(pl, "mra_plan_set_option: plan is NULL");
+        // options that change which kernel produces or factorises the leaves' C blocks bring the phantom-row launch back; the others
+        // (timing, front / knot / solve / update variants) never touch C
+        if (option == 2 || option == 3 || option == 6 || option == 11) pl->cphantom_valid = false;
+        if (option == 1) { pl->ktiming = value != 0; return MRA_OK; }
+        if (option == 2) { pl->use_fused = value != 0; return MRA_OK; }
+        if (option == 3) { pl->gemm_lds = value != 0; return MRA_OK; }
+        if (option == 4) { pl->use_front_fused = value != 0; return MRA_OK; }
+        if (option == 5) { pl->use_knot_chain = value != 0; return MRA_OK; }
+        if (option == 6) { pl->use_leaf_gemm = value != 0; pl->leaf_gemm_update = value == 2; return MRA_OK; }
+        if (option == 7) { pl->use_leaf_solve = value != 0; pl->leaf_solve_mode = (int)value; return MRA_OK; }
+        if (option == 8) { pl->use_pred_update = value != 0; return MRA_OK; }
+        if (option == 10) { pl->leaf_solve_split = value == 2 ? 2 : 1; return MRA_OK; }
+        if (option == 11) { pl->use_chol_lds = (int)value; return MRA_OK; }
+        if (option == 12) { pl->seg_gemm_lds = value != 0; return MRA_OK; }
+        if (option == 14) { pl->use_syrk_blk = (int)value; return MRA_OK; }
+        if (option == 15) { pl->use_prior_level = value != 0; return MRA_OK; }
+        if (option == 16) { pl->use_hi_fold = (int)value; return MRA_OK; }
+        if (option == 17) { pl->use_lik_rows = value != 0; return MRA_OK; }
+        if (option == 13) { pl->ut_gather = value != 0; return MRA_OK; }
+        if (option == 18) {
+            if (!pl->regular) return MRA_OK;          // (no fused cascade: nothing is grouped, the decision stays 0)
             pl->cascade_group_siblings = value != 0;
             pl->lik_tiles_valid = false;
             HIP_TRY(mraSetDevice(pl->device));
             build_leaf_workgroups(pl);
             return MRA_OK;
-        } catch (const MraError& e) { return fail(pl, e); }
-    }
-    if (option == 99) {
-        // kernel-shape switches for A/B runs.  Bits 8 and 32 keep the results (predictive cascade at two workgroups per CU, the
-        // wide leaf-residual shape); bits 1, 2, 4 (no Ut scatter / no W stores / constant instead of the kernel) give WRONG results
-        // and exist only in the diagnostic what-if build (`make whatif`, -DMRA_WHATIF): the product library refuses them.
-#ifdef MRA_WHATIF
-        pl->dbg = (int)value;
-#else
-        if (value & ~(int64_t)(8 | 32)) return fail(pl, MraError(MRA_ERR_INVALID, "option 99: bits other than 8 and 32 need the -DMRA_WHATIF diagnostic build"));
-        pl->dbg = (int)value;
+        }
+        if (option == 99) {
+            // kernel-shape switches for A/B runs.  Bits 8 and 32 keep the results (predictive cascade at two workgroups per CU, the
+            // wide leaf-residual shape); bits 1, 2, 4 (no Ut scatter / no W stores / constant instead of the kernel) give WRONG results
+            // and exist only in the diagnostic what-if build (`make whatif`, -DMRA_WHATIF): the product library refuses them.
+#ifndef MRA_WHATIF
+            if (value & ~(int64_t)(8 | 32)) throw MraError(MRA_ERR_INVALID, "option 99: bits other than 8 and 32 need the -DMRA_WHATIF diagnostic build");
 #endif
-        return MRA_OK;
-    }
-    return fail(pl, MraError(MRA_ERR_INVALID, "unknown option"));
+            pl->dbg = (int)value;
+            return MRA_OK;
+        }
+        throw MraError(MRA_ERR_INVALID, "unknown option");
+    });
 }
 
 int mra_plan_get_option(mra_plan* pl, int option, int64_t* value) {
-    if (!pl || !value) return MRA_ERR_INVALID;
-    switch (option) {
-        case 1: *value = pl->ktiming; break;
-        case 2: *value = pl->use_fused; break;
-        case 3: *value = pl->gemm_lds; break;
-        case 4: *value = pl->use_front_fused; break;
-        case 5: *value = pl->use_knot_chain; break;
-        case 6: *value = pl->use_leaf_gemm ? (pl->leaf_gemm_update ? 2 : 1) : 0; break;
-        case 7: *value = pl->leaf_solve_mode; break;
-        case 8: *value = pl->use_pred_update; break;
-        case 10: *value = pl->leaf_solve_split; break;
-        case 11: *value = pl->use_chol_lds; break;
-        case 12: *value = pl->seg_gemm_lds; break;
-        case 14: *value = pl->use_syrk_blk; break;
-        case 15: *value = pl->use_prior_level; break;
-        case 16: *value = pl->use_hi_fold; break;
-        case 17: *value = pl->use_lik_rows; break;
-        case 13: *value = pl->ut_gather; break;
-        case 18: *value = pl->cascade_group_siblings; break;
-        case 99: *value = pl->dbg; break;
-        default: return fail(pl, MraError(MRA_ERR_INVALID, "unknown option"));
-    }
-    return MRA_OK;
+    return guarded(pl, [&] {
+        require(pl && value, "mra_plan_get_option: plan or value is NULL");
+        switch (option) {
+            case 1: *value = pl->ktiming; break;
+            case 2: *value = pl->use_fused; break;
+            case 3: *value = pl->gemm_lds; break;
+            case 4: *value = pl->use_front_fused; break;
+            case 5: *value = pl->use_knot_chain; break;
+            case 6: *value = pl->use_leaf_gemm ? (pl->leaf_gemm_update ? 2 : 1) : 0; break;
+            case 7: *value = pl->leaf_solve_mode; break;
+            case 8: *value = pl->use_pred_update; break;
+            case 10: *value = pl->leaf_solve_split; break;
+            case 11: *value = pl->use_chol_lds; break;
+            case 12: *value = pl->seg_gemm_lds; break;
+            case 14: *value = pl->use_syrk_blk; break;
+            case 15: *value = pl->use_prior_level; break;
+            case 16: *value = pl->use_hi_fold; break;
+            case 17: *value = pl->use_lik_rows; break;
+            case 13: *value = pl->ut_gather; break;
+            case 18: *value = pl->cascade_group_siblings; break;
+            case 99: *value = pl->dbg; break;
+            default: throw MraError(MRA_ERR_INVALID, "unknown option");
+        }
+        return MRA_OK;
+    });
 }
 
 // Raise the dynamic-LDS limit of every kernel this plan can launch on ITS device now instead of at first launch (the
 // attribute is per device and per kernel; plans on different devices each do it).  n_kernels: how many kernels are on record.
 int mra_plan_prepare(mra_plan* pl, int64_t* n_kernels) {
-    if (!pl) return MRA_ERR_INVALID;
-    try {
+    return guarded(pl, [&] {
+        require(pl, "mra_plan_prepare: plan is NULL");
         HIP_TRY(mraSetDevice(pl->device));
         pl->prepare_only = true;
         struct Guard { mra_plan* p; ~Guard() { p->prepare_only = false; } } guard{pl};
@@ -2746,7 +2849,7 @@ int mra_plan_prepare(mra_plan* pl, int64_t* n_kernels) {
         }
         if (n_kernels) *n_kernels = (int64_t)pl->big_lds_done.size();
         return MRA_OK;
-    } catch (const MraError& e) { return fail(pl, e); }
+    });
 }
 
 int mra_get_kernel_stats(mra_plan* pl, int which, char* name, int name_cap, int* launches, double* ms, double* flops) {
@@ -2768,9 +2871,7 @@ int mra_get_kernel_work(mra_plan* pl, int which, double* out, int cap) {
 }
 
 int mra_device_synchronize(int device) {
-    if (g_dry) return MRA_OK;
-    if (hipSetDevice(device) != hipSuccess || hipDeviceSynchronize() != hipSuccess) { g_last_error = "hipDeviceSynchronize failed"; return MRA_ERR_HIP; }
-    return MRA_OK;
+    return guarded(nullptr, [&] { if (!g_dry) { HIP_TRY(hipSetDevice(device)); HIP_TRY(hipDeviceSynchronize()); } return MRA_OK; });
 }
 
 int mra_kernel_family_count(void) { return KF_COUNT; }
@@ -2786,166 +2887,59 @@ int mra_plan_info(mra_plan* pl, int64_t* out, int cap) {
 
 // Diagnostics: evaluate a device kernel on n distances (pyMRA/MRATools.py:265-301 on D = dist(...)).
 int mra_eval_kernel(int kind, const double* params, int n_params, const double* D, int64_t n, double* out) {
-    if (!params || n_params < 3 || !D || !out || n <= 0 || kind < 0 || kind > MRA_KERNEL_KANTER) return MRA_ERR_INVALID;
-    KernelParams kp{};
-    kp.kind = kind; kp.d = 1; kp.l = params[0]; kp.sig = params[1]; kp.scale = params[2];
-    kp.circular = (n_params >= 4 && params[3] != 0.0) ? 1 : 0;
-    derive_kernel_params(kp);
-    if (g_dry) { g_last_error = "MRA_HOST_DRYRUN: nothing runs in this mode"; return MRA_ERR_STATE; }
-    double *dD = nullptr, *dO = nullptr;
-    if (mraMalloc((void**)&dD, n * sizeof(double)) != hipSuccess || mraMalloc((void**)&dO, n * sizeof(double)) != hipSuccess) {
-        g_last_error = "hipMalloc failed (no GPU?)";
-        if (dD) mraFree(dD);
-        return MRA_ERR_HIP;
-    }
-    mraMemcpy(dD, D, n * sizeof(double), hipMemcpyHostToDevice);
-    hipLaunchKernelGGL(k_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dD, dO, (long)n, kp);
-    hipError_t e = hipGetLastError();
-    if (e == hipSuccess) e = mraMemcpy(out, dO, n * sizeof(double), hipMemcpyDeviceToHost);
-    mraFree(dD); mraFree(dO);
-    if (e != hipSuccess) { g_last_error = hipGetErrorString(e); return MRA_ERR_HIP; }
-    return MRA_OK;
+    return guarded(nullptr, [&] {
+        require(params && D && out, "mra_eval_kernel: params, D or out is NULL");
+        require(n_params >= 3 && n > 0 && kind >= 0 && kind <= MRA_KERNEL_KANTER, "mra_eval_kernel: unknown kernel kind, too few parameters or n <= 0");
+        KernelParams kp{};
+        kp.kind = kind; kp.d = 1; kp.l = params[0]; kp.sig = params[1]; kp.scale = params[2];
+        kp.circular = (n_params >= 4 && params[3] != 0.0) ? 1 : 0;
+        derive_kernel_params(kp);
+        if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN: nothing runs in this mode");
+        DevVec<double> dD, dO;
+        dD.alloc(n);
+        dO.alloc(n);
+        HIP_TRY(mraMemcpy(dD.p, D, n * sizeof(double), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dD.p, dO.p, (long)n, kp);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(mraMemcpy(out, dO.p, n * sizeof(double), hipMemcpyDeviceToHost));
+        return MRA_OK;
+    });
 }
 
-// ---- native tree replay (host only, no GPU needed) ---------------------------------------------------
-struct mra_tree { mra_topo::Result r; };
-
 int mra_tree_replay_2d(const double* locs, int64_t N, int32_t r, int32_t M, uint32_t* mt_key, int32_t* mt_pos, mra_tree** out) {
-    if (!locs || !mt_key || !mt_pos || !out) return MRA_ERR_INVALID;
-    *out = nullptr;
-    mra_tree* t = new mra_tree();
-    int rc;
-    try { rc = mra_topo::replay_quadtree(locs, N, r, M, mt_key, mt_pos, t->r); }
-    catch (const std::exception& e) { g_last_error = e.what(); delete t; return MRA_ERR_INVALID; }
-    if (rc != 0) { delete t; return 1; }
-    *out = t;
-    return MRA_OK;
+    return guarded(nullptr, [&] {
+        require(locs && mt_key && mt_pos && out, "mra_tree_replay_2d: locs, mt_key, mt_pos or out is NULL");
+        *out = nullptr;
+        *out = replay_tree(locs, N, r, M, mt_key, mt_pos).release();
+        return *out ? MRA_OK : 1;
+    });
 }
 
 int mra_tree_replay_2d_into(const double* locs, int64_t N, int32_t r, int32_t M, uint32_t* mt_key, int32_t* mt_pos, int64_t cap_rows,
                             int64_t* perm, int64_t* src, uint8_t* in_leaf, int64_t* knot_rows, mra_tree** out) {
-    if (!locs || !mt_key || !mt_pos || !out || !perm || !src || !in_leaf || !knot_rows) return MRA_ERR_INVALID;
-    *out = nullptr;
-    if (M < 0 || M > 15 || cap_rows < N + 15 * ((int64_t)1 << (2 * M))) { g_last_error = "mra_tree_replay_2d_into: cap_rows must be at least N + 15 * 4^M"; return MRA_ERR_INVALID; }
-    mra_tree* t = new mra_tree();
-    t->r.ext_perm = perm; t->r.ext_src = src; t->r.ext_in_leaf = in_leaf; t->r.ext_knot_rows = knot_rows;
-    int rc;
-    try { rc = mra_topo::replay_quadtree(locs, N, r, M, mt_key, mt_pos, t->r); }
-    catch (const std::exception& e) { g_last_error = e.what(); delete t; return MRA_ERR_INVALID; }
-    if (rc != 0) { delete t; return 1; }
-    *out = t;
-    return MRA_OK;
+    return guarded(nullptr, [&] {
+        require(locs && mt_key && mt_pos && out && perm && src && in_leaf && knot_rows, "mra_tree_replay_2d_into: NULL array or out");
+        *out = nullptr;
+        require(M >= 0 && M <= 15 && cap_rows >= N + 15 * ((int64_t)1 << (2 * M)), "mra_tree_replay_2d_into: cap_rows must be at least N + 15 * 4^M");
+        *out = replay_tree(locs, N, r, M, mt_key, mt_pos, perm, src, in_leaf, knot_rows).release();
+        return *out ? MRA_OK : 1;
+    });
 }
-
-// ---- MRATree.__init__ for large 2-D trees in one call ---------------------------------------------------------------------------
-// The tree replay and the plan construction of an end-to-end MRATree(...) call, overlapped: as soon as the replay has the
-// partition and the row layout (everything but the knots), a helper thread sizes and allocates the plan, gathers and uploads the
-// locations and the observations and builds the leaf descriptors - while the caller's thread is still drawing knots, the one
-// sequential part (it has to consume NumPy's MT19937 stream in the reference's order).  The knot rows, the leaves' knot
-// counts and the knot coordinates go in when both are done.
-namespace {
-struct ReplayPlanCtx {
-    const double* locs; const double* y; double R; int device;
-    mra_plan* pl = nullptr;
-    int rc = MRA_OK;
-    std::string err;
-};
-void replay_plan_hook(void* user, const mra_topo::Result& t) {
-    ReplayPlanCtx& c = *(ReplayPlanCtx*)user;
-    mra_plan* pl = nullptr;
-    try {
-        PlanTrace tr("plan beside the knot draws");
-        int ndev = 0;
-        if (!g_dry) {
-            if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0)
-                throw MraError(MRA_ERR_HIP, "no HIP device available: libmra_hip needs an AMD GPU (gfx950); there is no CPU fallback");
-            if (c.device < 0 || c.device >= ndev) throw MraError(MRA_ERR_INVALID, "device ordinal out of range");
-        }
-        HIP_TRY(mraSetDevice(c.device));
-        pl = new mra_plan();
-        pl->device = c.device;
-        pl->knots_pending = true;
-        pl->P = t.P; pl->d = 2; pl->n_levels = t.n_levels; pl->n_nodes = t.n_nodes;
-        pl->level_ptr.assign(t.level_ptr.begin(), t.level_ptr.end());
-        pl->row0.assign(t.row0.begin(), t.row0.end());
-        pl->row1.assign(t.row1.begin(), t.row1.end());
-        pl->leaf.assign(t.leaf.begin(), t.leaf.end());
-        pl->parent.assign(t.parent.begin(), t.parent.end());
-        pl->child_ptr.assign(t.child_ptr.begin(), t.child_ptr.end());
-        pl->child_list.assign(t.child_list.begin(), t.child_list.end());
-        pl->knot_ptr.assign(t.knot_ptr.begin(), t.knot_ptr.end());      // non-leaf nodes final; the leaves' entries are provisional
-        pl->cw.assign(t.cw.begin(), t.cw.end());
-        if (!g_dry) {
-            acquire_streams(pl);
-            HIP_TRY(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&pl->ev_join, hipEventDisableTiming));
-        }
-        for (int k = 0; k < 6 && !g_dry; ++k) HIP_TRY(hipEventCreate(&pl->ev[k]));
-        tr.mark("copies of the topology, streams, events");
-        init_arena(pl);
-        const int64_t* src = t.ext_perm ? t.ext_src : t.src.data();
-        const int64_t* perm = t.ext_perm ? t.ext_perm : t.perm.data();
-        std::lock_guard<std::mutex> lock(g_stage_mutex);
-        double* xp = stage_buffer((size_t)pl->P * 3);
-        double* yp = xp + (size_t)pl->P * 2;
-        // the gather of locations and observations into leaf order runs beside build_static (neither needs the other)
-        const long P = pl->P;
-        bool gather_failed = false;
-        std::thread gather([&, P]() {
-            const double nan = std::nan("");
-            const double* locs = c.locs; const double* y = c.y;
-            try {
-                parallel_rows(P, [&](int64_t a, int64_t b) {
-                    for (int64_t p = a; p < b; ++p) {
-                        const int64_t q = src[p];
-                        xp[2 * p] = locs[2 * q]; xp[2 * p + 1] = locs[2 * q + 1];
-                        yp[p] = perm[p] < 0 ? nan : y[q];
-                    }
-                });
-            } catch (...) { gather_failed = true; }
-        });
-        struct Join { std::thread& t; ~Join() { if (t.joinable()) t.join(); } } join{gather};
-        build_static(pl);
-        tr.mark("build_static");
-        gather.join();
-        if (gather_failed) throw MraError(MRA_ERR_INVALID, "gathering locations / observations failed (thread creation)");
-        tr.mark("(gather of locations and observations: beside it)");
-        int rc = mra_plan_set_locs(pl, xp);
-        if (rc == MRA_OK) rc = mra_plan_set_obs(pl, yp, c.R);
-        if (rc != MRA_OK) throw MraError(rc, pl->err);
-        tr.mark("uploads, leaf descriptors");
-        c.pl = pl;
-    } catch (const MraError& e) {
-        c.rc = e.code; c.err = e.msg;
-        if (pl) { drop_arena(pl); if (!g_dry) return_streams(pl); delete pl; }
-    } catch (const std::exception& e) {
-        c.rc = MRA_ERR_INVALID; c.err = e.what();
-        if (pl) { drop_arena(pl); if (!g_dry) return_streams(pl); delete pl; }
-    }
-}
-}  // namespace
 
 int mra_plan_create_replay_2d(const double* locs, int64_t N, int32_t r, int32_t M, uint32_t* mt_key, int32_t* mt_pos,
                               const double* y, double R, int device, int64_t cap_rows,
                               int64_t* perm, int64_t* src, uint8_t* in_leaf, int64_t* knot_rows, mra_tree** tree_out, mra_plan** plan_out) {
-    if (!locs || !mt_key || !mt_pos || !y || !tree_out || !plan_out || !perm || !src || !in_leaf || !knot_rows) return MRA_ERR_INVALID;
-    *tree_out = nullptr; *plan_out = nullptr;
-    if (M < 0 || M > 15 || cap_rows < N + 15 * ((int64_t)1 << (2 * M))) { g_last_error = "mra_plan_create_replay_2d: cap_rows must be at least N + 15 * 4^M"; return MRA_ERR_INVALID; }
-    if (!(R > 0.0)) { g_last_error = "R must be a positive scalar"; return MRA_ERR_INVALID; }
-    mra_tree* t = new mra_tree();
-    t->r.ext_perm = perm; t->r.ext_src = src; t->r.ext_in_leaf = in_leaf; t->r.ext_knot_rows = knot_rows;
-    ReplayPlanCtx ctx{locs, y, R, device};
-    int rc;
-    try { rc = mra_topo::replay_quadtree(locs, N, r, M, mt_key, mt_pos, t->r, replay_plan_hook, &ctx); }
-    catch (const std::exception& e) { g_last_error = e.what(); rc = MRA_ERR_INVALID; }
-    mra_plan* pl = ctx.pl;
-    if (rc == 0 && ctx.rc != MRA_OK) { g_last_error = ctx.err; rc = ctx.rc; }
-    if (rc != 0) {                                           // not a large-2-D tree (1), or an error: nothing is handed out
-        if (pl) mra_plan_destroy(pl);
-        delete t;
-        return rc;
-    }
-    try {
+    return guarded(nullptr, [&] {
+        require(locs && mt_key && mt_pos && y && tree_out && plan_out && perm && src && in_leaf && knot_rows,
+                "mra_plan_create_replay_2d: NULL array or out");
+        *tree_out = nullptr; *plan_out = nullptr;
+        require(M >= 0 && M <= 15 && cap_rows >= N + 15 * ((int64_t)1 << (2 * M)), "mra_plan_create_replay_2d: cap_rows must be at least N + 15 * 4^M");
+        require(R > 0.0, "R must be a positive scalar");
+        ReplayPlanCtx ctx{locs, y, R, device};
+        std::unique_ptr<mra_tree> t = replay_tree(locs, N, r, M, mt_key, mt_pos, perm, src, in_leaf, knot_rows, replay_plan_hook, &ctx);
+        if (!t) return 1;                                    // not a large-2-D tree: nothing is handed out
+        if (ctx.rc != MRA_OK) throw MraError(ctx.rc, ctx.err);
+        mra_plan* pl = ctx.pl.get();
         PlanTrace tr("knots into the plan");
         HIP_TRY(mraSetDevice(pl->device));
         pl->knot_ptr.assign(t->r.knot_ptr.begin(), t->r.knot_ptr.end());
@@ -2953,15 +2947,10 @@ int mra_plan_create_replay_2d(const double* locs, int64_t N, int32_t r, int32_t 
         pl->knots_pending = false;
         fill_knot_arrays(pl);
         set_knot_coords_src(pl, locs, src);                  // knot coordinates straight from the caller's rows
-    } catch (const MraError& e) {
-        const int code = fail(nullptr, e);
-        mra_plan_destroy(pl);
-        delete t;
-        return code;
-    }
-    *tree_out = t;
-    *plan_out = pl;
-    return MRA_OK;
+        *tree_out = t.release();
+        *plan_out = ctx.pl.release();
+        return MRA_OK;
+    });
 }
 
 int mra_tree_sizes(mra_tree* t, int64_t* out5) {
@@ -2974,71 +2963,79 @@ int mra_tree_sizes(mra_tree* t, int64_t* out5) {
 int mra_tree_export(mra_tree* t, int64_t* perm, int64_t* src, uint8_t* in_leaf, int64_t* level_ptr, int32_t* node_level,
                     int64_t* row0, int64_t* row1, uint8_t* leaf, int32_t* parent, int32_t* child_ptr, int32_t* child_list,
                     int64_t* knot_ptr, int64_t* knot_rows, int32_t* cw, int32_t* preorder) {
-    if (!t) return MRA_ERR_INVALID;
-    const mra_topo::Result& r = t->r;
-    auto cp = [](auto* dst, const auto& v) { if (dst && !v.empty()) memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
-    cp(perm, r.perm); cp(src, r.src); cp(in_leaf, r.in_leaf); cp(level_ptr, r.level_ptr); cp(node_level, r.level);
-    cp(row0, r.row0); cp(row1, r.row1); cp(leaf, r.leaf); cp(parent, r.parent); cp(child_ptr, r.child_ptr);
-    cp(child_list, r.child_list); cp(knot_ptr, r.knot_ptr); cp(knot_rows, r.knot_rows); cp(cw, r.cw); cp(preorder, r.preorder);
-    return MRA_OK;
+    return guarded(nullptr, [&] {
+        require(t, "mra_tree_export: tree is NULL");
+        const mra_topo::Result& r = t->r;
+        auto cp = [](auto* dst, const auto& v) { if (dst && !v.empty()) memcpy(dst, v.data(), v.size() * sizeof(v[0])); };
+        cp(perm, r.perm); cp(src, r.src); cp(in_leaf, r.in_leaf); cp(level_ptr, r.level_ptr); cp(node_level, r.level);
+        cp(row0, r.row0); cp(row1, r.row1); cp(leaf, r.leaf); cp(parent, r.parent); cp(child_ptr, r.child_ptr);
+        cp(child_list, r.child_list); cp(knot_ptr, r.knot_ptr); cp(knot_rows, r.knot_rows); cp(cw, r.cw); cp(preorder, r.preorder);
+        return MRA_OK;
+    });
 }
 
-int mra_tree_free(mra_tree* t) { delete t; return MRA_OK; }
+int mra_tree_free(mra_tree* t) { return guarded(nullptr, [&] { delete t; return MRA_OK; }); }
 
 // ---- multi-GPU ------------------------------------------------------------------------------------
 int mra_plan_set_reduce_level(mra_plan* pl, int level) {
-    if (!pl) return MRA_ERR_INVALID;
-    if (level >= pl->n_levels) return fail(pl, MraError(MRA_ERR_INVALID, "reduce level out of range"));
-    if (pl->lowrank_parent && level >= pl->n_levels - 3)
-        return fail(pl, MraError(MRA_ERR_INVALID, "reduce level too deep: the fronts of the leaves' parents are kept as panels on this plan (set MRA_NO_LOWRANK_PARENT=1 before creating it)"));
-    pl->reduce_level = level;
-    return MRA_OK;
+    return guarded(pl, [&] {
+        require(pl, "mra_plan_set_reduce_level: plan is NULL");
+        if (level >= pl->n_levels) throw MraError(MRA_ERR_INVALID, "reduce level out of range");
+        if (pl->lowrank_parent && level >= pl->n_levels - 3)
+            throw MraError(MRA_ERR_INVALID, "reduce level too deep: the fronts of the leaves' parents are kept as panels on this plan (set MRA_NO_LOWRANK_PARENT=1 before creating it)");
+        pl->reduce_level = level;
+        return MRA_OK;
+    });
 }
 
 int mra_reduce_size(mra_plan* pl, int64_t* n) {
-    if (!pl || !n) return MRA_ERR_INVALID;
-    if (pl->reduce_level < 0) return fail(pl, MraError(MRA_ERR_STATE, "no reduce level set"));
-    *n = (int64_t)pl->lev[pl->reduce_level].F.n;
-    return MRA_OK;
+    return guarded(pl, [&] {
+        require(pl && n, "mra_reduce_size: plan or n is NULL");
+        if (pl->reduce_level < 0) throw MraError(MRA_ERR_STATE, "no reduce level set");
+        *n = (int64_t)pl->lev[pl->reduce_level].F.n;
+        return MRA_OK;
+    });
 }
 
 int mra_reduce_export(mra_plan* pl, double* out) {
-    if (!pl || !out) return MRA_ERR_INVALID;
-    try {
+    return guarded(pl, [&] {
+        require(pl && out, "mra_reduce_export: plan or out is NULL");
         if (!pl->split_pending) throw MraError(MRA_ERR_STATE, "no split run pending");
         HIP_TRY(mraSetDevice(pl->device));
         HIP_TRY(hipStreamSynchronize(pl->stream));
         LevelData& lv = pl->lev[pl->reduce_level];
         HIP_TRY(mraMemcpy(out, lv.F.p, lv.F.n * sizeof(double), hipMemcpyDeviceToHost));
         return MRA_OK;
-    } catch (const MraError& e) { return fail(pl, e); }
+    });
 }
 
 int mra_reduce_import(mra_plan* pl, const double* in) {
-    if (!pl || !in) return MRA_ERR_INVALID;
-    try {
+    return guarded(pl, [&] {
+        require(pl && in, "mra_reduce_import: plan or in is NULL");
         if (!pl->split_pending) throw MraError(MRA_ERR_STATE, "no split run pending");
         HIP_TRY(mraSetDevice(pl->device));
         LevelData& lv = pl->lev[pl->reduce_level];
         HIP_TRY(mraMemcpy(lv.F.p, in, lv.F.n * sizeof(double), hipMemcpyHostToDevice));
         return MRA_OK;
-    } catch (const MraError& e) { return fail(pl, e); }
+    });
 }
 
 int mra_comm_unique_id(char* out, int cap) {
-    if (!out || cap < 128) return MRA_ERR_INVALID;
-    void* h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-    if (!h) { g_last_error = "cannot load librccl.so"; return MRA_ERR_COMM; }
-    typedef ncclResult_t (*uid_t_)(ncclUniqueId*);
-    uid_t_ fn = (uid_t_)dlsym(h, "ncclGetUniqueId");
-    if (!fn || fn((ncclUniqueId*)out) != ncclSuccess) { g_last_error = "ncclGetUniqueId failed"; return MRA_ERR_COMM; }
-    return MRA_OK;
+    return guarded(nullptr, [&] {
+        require(out && cap >= 128, "mra_comm_unique_id: out is NULL or cap < 128");
+        void* h = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
+        if (!h) h = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
+        if (!h) throw MraError(MRA_ERR_COMM, "cannot load librccl.so");
+        typedef ncclResult_t (*uid_t_)(ncclUniqueId*);
+        uid_t_ fn = (uid_t_)dlsym(h, "ncclGetUniqueId");
+        if (!fn || fn((ncclUniqueId*)out) != ncclSuccess) throw MraError(MRA_ERR_COMM, "ncclGetUniqueId failed");
+        return MRA_OK;
+    });
 }
 
 int mra_comm_init(mra_plan* pl, const char* uid, int n_ranks, int rank) {
-    if (!pl || !uid) return MRA_ERR_INVALID;
-    try {
+    return guarded(pl, [&] {
+        require(pl && uid, "mra_comm_init: plan or uid is NULL");
         HIP_TRY(mraSetDevice(pl->device));
         pl->rccl = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
         if (!pl->rccl) pl->rccl = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
@@ -3054,7 +3051,7 @@ int mra_comm_init(mra_plan* pl, const char* uid, int n_ranks, int rank) {
         if (fn(&pl->comm, n_ranks, id, rank) != ncclSuccess) { pl->comm = nullptr; throw MraError(MRA_ERR_COMM, "ncclCommInitRank failed"); }
         pl->n_ranks = n_ranks; pl->rank = rank;
         return MRA_OK;
-    } catch (const MraError& e) { return fail(pl, e); }
+    });
 }
 
 }  // extern "C"

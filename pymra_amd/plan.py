@@ -67,6 +67,13 @@ class MraError(RuntimeError):
         self.code = code
 
 
+def _check(lib, rc, handle=None):
+    """Raise MraError for a nonzero return code, with mra_last_error of the plan `handle` (None: of the calling thread)."""
+    if rc != 0:
+        msg = lib.mra_last_error(handle)
+        raise MraError(rc, msg.decode() if msg else "")
+
+
 _lib = None
 
 
@@ -166,19 +173,13 @@ class HipPlan:
         )
         st = MraTopologyStruct(P=int(topo.P), d=int(topo.d), n_levels=int(topo.n_levels), n_nodes=int(topo.n_nodes),
                                **{k: _ptr(v) for k, v in arrs.items()})
-        rc = self.lib.mra_plan_create(C.byref(self._h), C.byref(st), int(device))
-        if rc != 0:
-            msg = self.lib.mra_last_error(None)
-            self._h = C.c_void_p()
-            raise MraError(rc, msg.decode() if msg else "")
+        _check(self.lib, self.lib.mra_plan_create(C.byref(self._h), C.byref(st), int(device)))
         self.P = int(topo.P)
         self.d = int(topo.d)
 
     # -- helpers -------------------------------------------------------------------------------
     def _check(self, rc):
-        if rc != 0:
-            msg = self.lib.mra_last_error(self._h)
-            raise MraError(rc, msg.decode() if msg else "")
+        _check(self.lib, rc, self._h)
 
     def close(self):
         if getattr(self, "_h", None) is not None and self._h:
@@ -413,11 +414,12 @@ def create_with_replay(locs, r, M, J, obs, R, device: int = 0):
                                        _ptr(perm), _ptr(src), _ptr(in_leaf), _ptr(knot_rows), C.byref(tree), C.byref(ph))
     if rc == 1:
         return None
-    if rc != 0:
-        msg = lib.mra_last_error(None)
-        raise MraError(rc, msg.decode() if msg else "")
+    _check(lib, rc)
     try:
         topo = topology_from_tree(lib, tree, N, int(r), int(M), int(J), perm, src, in_leaf, knot_rows)
+    except BaseException:
+        lib.mra_plan_destroy(ph)
+        raise
     finally:
         lib.mra_tree_free(tree)
     np.random.set_state((state[0], key, int(pos.value), state[3], state[4]))
@@ -427,9 +429,7 @@ def create_with_replay(locs, r, M, J, obs, R, device: int = 0):
 def comm_unique_id() -> bytes:
     lib = load_library()
     buf = C.create_string_buffer(128)
-    rc = lib.mra_comm_unique_id(buf, 128)
-    if rc != 0:
-        raise MraError(rc, (lib.mra_last_error(None) or b"").decode())
+    _check(lib, lib.mra_comm_unique_id(buf, 128))
     return buf.raw
 
 
@@ -439,9 +439,7 @@ def eval_kernel(kind, l, sig, scale, D):
     D = np.ascontiguousarray(D, dtype=np.float64).ravel()
     out = np.empty_like(D)
     par = np.array([l, sig, scale], dtype=np.float64)
-    rc = lib.mra_eval_kernel(int(kind), _ptr(par), 3, _ptr(D), D.size, _ptr(out))
-    if rc != 0:
-        raise MraError(rc, (lib.mra_last_error(None) or b"").decode())
+    _check(lib, lib.mra_eval_kernel(int(kind), _ptr(par), 3, _ptr(D), D.size, _ptr(out)))
     return out
 
 
@@ -451,9 +449,8 @@ def device_count() -> int:
 
 def device_synchronize(device: int = 0) -> None:
     """hipDeviceSynchronize on `device` through the library (no other GPU runtime needed for a barrier)."""
-    rc = load_library().mra_device_synchronize(int(device))
-    if rc != 0:
-        raise MraError(rc, "hipDeviceSynchronize failed")
+    lib = load_library()
+    _check(lib, lib.mra_device_synchronize(int(device)))
 
 
 def release_cached_memory() -> None:

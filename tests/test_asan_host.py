@@ -59,6 +59,20 @@ for name in ["kat1", "kat2", "kat3", "c1", "t201", "t1000", "kat4", "u3", "g32",
                 except (ValueError, NotImplementedError):
                     continue
                 build(lt, cs["locs"], cs["y_obs"], cs["c"]["R"])
+# failed constructions return -1 and release the half-built plan: one inside build_static (a cw that is not a multiple of 16),
+# one in the topology copy with a library exception (knot_ptr[n_nodes] = -1: std::length_error from the knot_rows copy before it
+# reads anything; 2**60 would overflow the pointer arithmetic, itself a UBSan report)
+import copy
+cs = K.load_case("g64")
+for field, k, value, msg in (("cw", 0, cs["topo"].cw[0] + 1, "multiple of 16"), ("knot_ptr", -1, -1, "vector")):
+    bad = copy.copy(cs["topo"])
+    setattr(bad, field, np.array(getattr(bad, field)))
+    getattr(bad, field)[k] = value
+    try:
+        P.HipPlan(bad, 0)
+        raise SystemExit("a plan with a bad %s must not be created" % field)
+    except P.MraError as e:
+        assert e.code == -1 and msg in str(e), (field, str(e))
 # native replay (C++) at three sizes, wide blocks, empty and full observation patterns
 for n, r, M in ((48, 16, 2), (128, 32, 3), (256, 64, 3), (200, 16, 4)):
     np.random.seed(3)

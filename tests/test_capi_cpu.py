@@ -148,3 +148,107 @@ print("CASCADE_GROUP_OK")
     env = dict(os.environ, MRA_ROOT=K.ROOT, MRA_HOST_DRYRUN="1")
     res = subprocess.run([sys.executable, str(child)], env=env, capture_output=True, text=True, timeout=600)
     assert res.returncode == 0 and "CASCADE_GROUP_OK" in res.stdout, (res.stdout + res.stderr)[-2000:]
+
+
+# exports that only read plain fields and stay outside the exception boundary (the list at guarded() in mra_plan.hip)
+_UNGUARDED = {"mra_version", "mra_last_error", "mra_device_count", "mra_kernel_family_count", "mra_get_timers", "mra_plan_info",
+              "mra_get_kernel_stats", "mra_get_kernel_work", "mra_tree_sizes"}
+
+
+def test_every_export_goes_through_the_exception_boundary():
+    """include/mra_hip.h promises that no C++ exception crosses the C ABI: every export of mra_plan.hip but the plain field
+    readers returns guarded(...), the one boundary helper above the extern "C" block, and no catch clause sits in the block."""
+    src = open(os.path.join(K.ROOT, "pymra_amd", "csrc", "mra_plan.hip")).read()
+    begin, end = src.index('extern "C" {'), src.index('}  // extern "C"')
+    assert src.index("static int guarded(") < begin
+    block = re.sub(r"//[^\n]*", "", src[begin:end])
+    assert not re.search(r"\bcatch\b", block), "catch clause inside the extern \"C\" block"
+    heads = list(re.finditer(r"^(?:int|const char\*) (mra_\w+)\([^{]*\{", block, flags=re.M))
+    assert sorted(m.group(1) for m in heads) == _header_functions()
+    for m, nxt in zip(heads, heads[1:] + [None]):
+        body = block[m.end():nxt.start() if nxt else len(block)].lstrip()
+        if m.group(1) not in _UNGUARDED:
+            assert body.startswith("return guarded("), "%s does not go through guarded()" % m.group(1)
+
+
+def test_null_arguments_report_their_own_error(built_library, tmp_path):
+    """A NULL argument returns MRA_ERR_INVALID and mra_last_error names the function that refused it (the plan's message, or the
+    thread's when the plan itself is NULL), not whatever an earlier failure left there.  Host dry run, no GPU."""
+    import subprocess
+    import sys
+    child = tmp_path / "child.py"
+    child.write_text(r'''
+import os, sys
+import ctypes as C
+import numpy as np
+sys.path.insert(0, os.environ["MRA_ROOT"]); sys.path.insert(0, os.path.join(os.environ["MRA_ROOT"], "tests"))
+import _cases as K
+import pymra_amd.MRATools as mt
+from pymra_amd import plan as P
+cs = K.load_case("g64")
+pl = P.HipPlan(cs["topo"], 0)
+pl.set_locs(cs["locs"]); pl.set_obs(cs["y_obs"], cs["c"]["R"]); pl.set_kernel(mt.KIND_EXP, 0.3, 1.0, 1.0)
+lib, h, N = pl.lib, pl._h, int(cs["topo"].N)
+x = np.zeros(4 * int(cs["topo"].P)); buf = P._ptr(x)
+def earlier_error():
+    try:
+        pl.set_kernel(mt.KIND_EXP, -1.0)
+        raise SystemExit("a negative length scale must be refused")
+    except P.MraError as e:
+        assert "length scale" in str(e) and "length scale" in lib.mra_last_error(None).decode()
+def refused(name, call, handle):
+    earlier_error()
+    assert call() == -1, name
+    msg = lib.mra_last_error(handle).decode()
+    assert msg.startswith(name + ":"), (name, msg)
+# plan-taking exports: (name, call with plan p and its other pointer arguments NULL, whether it has one)
+plan_calls = [
+    ("mra_plan_set_locs", lambda p: lib.mra_plan_set_locs(p, None), True),
+    ("mra_plan_set_obs", lambda p: lib.mra_plan_set_obs(p, None, 1.0), True),
+    ("mra_plan_set_locs_rows", lambda p: lib.mra_plan_set_locs_rows(p, buf, None), True),
+    ("mra_plan_set_obs_rows", lambda p: lib.mra_plan_set_obs_rows(p, buf, None, None, 1.0), True),
+    ("mra_get_predict_rows", lambda p: lib.mra_get_predict_rows(p, None, None, N, buf, buf), True),
+    ("mra_get_predict_rows_sd", lambda p: lib.mra_get_predict_rows_sd(p, None, None, N, buf, buf, None), True),
+    ("mra_plan_set_kernel", lambda p: lib.mra_plan_set_kernel(p, 0, None, 3), True),
+    ("mra_plan_set_cov_block", lambda p: lib.mra_plan_set_cov_block(p, 0, None, 0, 0, None), True),
+    ("mra_sample_slots", lambda p: lib.mra_sample_slots(p, None), True),
+    ("mra_get_likelihood", lambda p: lib.mra_get_likelihood(p, None, None), True),
+    ("mra_get_predict", lambda p: lib.mra_get_predict(p, None, None), True),
+    ("mra_get_buffer", lambda p: lib.mra_get_buffer(p, 0, None, 0, None), True),
+    ("mra_get_node_block", lambda p: lib.mra_get_node_block(p, 0, 0, None, 0, None, None), True),
+    ("mra_plan_get_option", lambda p: lib.mra_plan_get_option(p, 1, None), True),
+    ("mra_reduce_size", lambda p: lib.mra_reduce_size(p, None), True),
+    ("mra_reduce_export", lambda p: lib.mra_reduce_export(p, None), True),
+    ("mra_reduce_import", lambda p: lib.mra_reduce_import(p, None), True),
+    ("mra_comm_init", lambda p: lib.mra_comm_init(p, None, 1, 0), True),
+    ("mra_run", lambda p: lib.mra_run(p, 1), False),
+    ("mra_run_resume", lambda p: lib.mra_run_resume(p), False),
+    ("mra_sample", lambda p: lib.mra_sample(p, 0, 1, 0, 0, None, None), False),
+    ("mra_plan_set_option", lambda p: lib.mra_plan_set_option(p, 1, 0), False),
+    ("mra_plan_prepare", lambda p: lib.mra_plan_prepare(p, None), False),
+    ("mra_plan_set_reduce_level", lambda p: lib.mra_plan_set_reduce_level(p, 0), False),
+]
+for name, call, has_ptr in plan_calls:
+    if has_ptr:
+        refused(name, lambda: call(h), h)
+    refused(name, lambda: call(None), None)
+# exports without a plan
+i32 = C.c_int32(0)
+for name, call in (
+        ("mra_plan_create", lambda: lib.mra_plan_create(None, None, 0)),
+        ("mra_eval_kernel", lambda: lib.mra_eval_kernel(0, None, 3, None, 1, None)),
+        ("mra_comm_unique_id", lambda: lib.mra_comm_unique_id(None, 128)),
+        ("mra_tree_replay_2d", lambda: lib.mra_tree_replay_2d(None, 1, 16, 2, None, C.byref(i32), None)),
+        ("mra_tree_replay_2d_into", lambda: lib.mra_tree_replay_2d_into(None, 1, 16, 2, None, C.byref(i32), 100, None, None, None,
+                                                                         None, None)),
+        ("mra_plan_create_replay_2d", lambda: lib.mra_plan_create_replay_2d(None, 1, 16, 2, None, C.byref(i32), None, 1.0, 0, 100,
+                                                                             None, None, None, None, None, None)),
+        ("mra_tree_export", lambda: lib.mra_tree_export(*[None] * 16))):
+    refused(name, call, None)
+assert pl.get_option(P.MRA_OPT_FUSED) in (0, 1)              # the plan is still whole
+pl.close()
+print("NULL_ARGS_OK", len(plan_calls))
+''')
+    env = dict(os.environ, MRA_ROOT=K.ROOT, MRA_HOST_DRYRUN="1")
+    res = subprocess.run([sys.executable, str(child)], env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and "NULL_ARGS_OK" in res.stdout, (res.stdout + res.stderr)[-2000:]
