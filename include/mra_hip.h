@@ -137,8 +137,9 @@ int mra_get_predict(mra_plan *plan, double *mean_perm, double *var_perm);
  * s' = sample0 + s, output words w0..w3; a = w0 + 2^32 w1, b = w2 + 2^32 w3, u1 = ((a >> 11) + 0.5) 2^-53, u2 likewise from b,
  * z = sqrt(-2 log u1) cospi(2 u2) - a pure function of (seed, slot, sample).  Otherwise z is n_samples x n_slots, row-major.
  * out: n_samples x P, padded leaf order; unreported rows (phantoms, rows a 1-D split drops) are exactly 0.
- * Needs set_locs, set_obs and set_kernel (MRA_ERR_STATE); MRA_ERR_INVALID for MRA_KERNEL_HOST plans, sharded plans and
- * n_samples < 0; MRA_ERR_NOT_SPD when a leaf's v_M(K, K) does not factor (no jitter is added).  The device y and every option
+ * Needs set_locs, set_obs and set_kernel (MRA_ERR_STATE); MRA_ERR_INVALID for MRA_KERNEL_HOST plans, sharded plans,
+ * n_samples < 0, sample0 < 0 and sample0 + n_samples - 1 > 2^63 - 1 (sample numbers are non-negative int64);
+ * MRA_ERR_NOT_SPD when a leaf's v_M(K, K) does not factor (no jitter is added).  The device y and every option
  * are as the caller left them afterwards, mra_get_likelihood / mra_get_predict still return the last mra_run's values
  * (mra_get_timers / mra_get_kernel_stats describe the sampler's own passes).  Blocking. */
 #define MRA_SAMPLE_CONDITIONAL 1u
@@ -231,6 +232,9 @@ int mra_get_timers(mra_plan *plan, double *out_ms, int capacity);
                                       leaves (one operand image staged for all of them), 0 = one per leaf.  Default: a cost model at plan build
                                       (families when that still fills the CUs); get returns the plan's current decision, set forces it.  Regular trees
                                       only: on any other plan set is accepted and ignored, get returns 0 */
+#define MRA_OPT_SAMPLE_GRAM_BYTES 19 /* mra_sample: bytes of leaf Gram blocks (+ inverted diagonal blocks) per factorisation batch, at least one
+                                      leaf per batch; 0 (default): 1.5 GB.  A new value drops the sampler's index maps and buffers, which
+                                      the next mra_sample rebuilds.  The draws do not depend on it. */
 int mra_plan_set_option(mra_plan *plan, int option, int64_t value);
 /* current value of an option (so that a caller can change one temporarily and put it back) */
 int mra_plan_get_option(mra_plan *plan, int option, int64_t *value);

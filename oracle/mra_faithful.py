@@ -264,3 +264,52 @@ def run_subtree_sample(topo, locs, cov, obs, R: float, top: int, *, do_gc: bool 
     t0 = time.perf_counter()
     rec.visit(int(top))
     return rec.count, time.perf_counter() - t0, rec.tm
+
+
+def prior_sigma_rows(topo, locs, cov, rows):
+    """The MRA prior covariance Sigma[rows, rows] = sum_j B_j K_j B_j^T over padded rows ``rows`` (every node j, scattered to its
+    rows; for a leaf B_j K_j B_j^T is v_M on its knots), by the recursion of ``_Recursion.prior``:
+        B_j = C(S, Q_j) - sum_{a in lineage(j)} B_a[S] K_a B_a[Q_j]^T,   K_j = inv(B_j[Q_j]).
+    Restricted to the lineages of ``rows`` as ``run_subtree_sample`` prunes ancestors: node a's B is evaluated only at the given
+    rows inside it and at the knots of the lineage nodes below it, so a few leaves of a full-size tree cost what their chains cost.
+    Rows outside every leaf (padding, rows a 1-D split drops) get what the nodes that hold them give; callers compare reported
+    rows.  Returns a (len(rows), len(rows)) array."""
+    t = topo
+    rows = np.asarray(rows, dtype=np.int64)
+    coords = np.asarray(locs, dtype=np.float64)
+    if coords.ndim == 1:
+        coords = coords.reshape(-1, 1)
+    covf = _as_cov(cov, coords)
+    src = t.src
+    row0, row1 = np.asarray(t.node_row0), np.asarray(t.node_row1)
+    inside = (row0[:, None] <= rows[None, :]) & (rows[None, :] < row1[:, None])       # [node, row]
+    need = np.nonzero(inside.any(axis=1))[0]                                           # a row's nodes are its lineage
+    need = need[np.argsort(np.asarray(t.node_level)[need], kind="stable")]           # parents before children
+    knots = {int(i): t.knot_rows[t.knot_ptr[i]:t.knot_ptr[i + 1]] for i in need}
+    parent = np.asarray(t.node_parent)
+    below = {int(i): [] for i in need}                                                 # knots of needed nodes in i's subtree
+    for i in need:
+        a = int(i)
+        while a >= 0:
+            below[a].append(knots[int(i)])
+            a = int(parent[a])
+    B, K, E = {}, {}, {}
+    S = np.zeros((len(rows), len(rows)))
+    for i in need:
+        i = int(i)
+        sel = np.nonzero(inside[i])[0]
+        ev = np.unique(np.concatenate([rows[sel]] + below[i]))                         # where B_i is needed: sorted padded rows
+        q = knots[i]
+        Bi = covf(src[ev], src[q])
+        a, lin = int(parent[i]), []
+        while a >= 0:
+            lin.append(a)
+            a = int(parent[a])
+        for a in lin[::-1]:
+            Ea = E[a]
+            Bi = Bi - B[a][np.searchsorted(Ea, ev)] @ K[a] @ B[a][np.searchsorted(Ea, q)].T
+        B[i], E[i] = Bi, ev
+        K[i] = np.linalg.inv(Bi[np.searchsorted(ev, q)])
+        Bs = Bi[np.searchsorted(ev, rows[sel])]
+        S[np.ix_(sel, sel)] += Bs @ K[i] @ Bs.T
+    return S

@@ -649,7 +649,7 @@ __global__ __launch_bounds__(256, 4) void k_gemm_nt_lds(const GemmProb* __restri
     const int m0 = M0 + wr0, n0 = N0 + wc0;
     if (m0 >= pb.M || n0 >= pb.N) return;
     const bool mv1 = !narrow && (m0 + 16) < pb.M, nv1 = (n0 + 16) < pb.N;
-    int bc0 = n0 + r, bc1 = n0 + 16 + r;
+    int bc0 = n0 + r, bc1 = nv1 ? n0 + 16 + r : -1;        // (no second column half: its coordinates are not read past the problem)
     if (pb.idxB) { bc0 = gldi(pb.idxB + n0 + r); bc1 = nv1 ? gldi(pb.idxB + n0 + 16 + r) : -1; }
     // COV / HOSTCOV: everything the epilogue reads per row and per column (gather indices, coordinates, the leaf's observed-row
     // map) is fetched in rounds of independent loads, one 16-row half of the wave's tile at a time (both halves at once kept 64

@@ -1972,7 +1972,8 @@ static void run_all(mra_plan* pl, uint32_t flags) {
 // ---- sampler (mra_sample) ------------------------------------------------------------------------------
 // Latent slots: [0, Kn) the non-leaf nodes in node order, cw[level] each; [Kn, Kn + P) leaf terms by padded row (read at leaf knot
 // rows); [Kn + P, Kn + 2P) observation noise by padded row (read at observed rows of a conditional draw).
-static const size_t SAMPLE_GRAM_BUDGET = (size_t)1536 << 20;   // bytes of leaf Gram blocks + inverted diagonal blocks per batch
+static const size_t SAMPLE_GRAM_BUDGET = (size_t)1536 << 20;   // default bytes of leaf Gram blocks + inverted diagonal blocks per batch
+static const size_t SAMPLE_LEAF_GRID = 65535;                  // leaves per launch of the kernels that take the leaf from blockIdx.y
 
 static void sampler_build(mra_plan* pl) {
     mra_plan::Sampler& S = pl->smp;
@@ -2007,6 +2008,7 @@ static void sampler_build(mra_plan* pl) {
     // Gram batches: consecutive leaves while their nr^2 + 16 nr doubles stay within the budget (at least one leaf per batch)
     S.bat.assign(1, 0);
     S.bat_rows.clear();
+    const size_t budget = S.gram_bytes ? S.gram_bytes : SAMPLE_GRAM_BUDGET;
     size_t cur = 0, gmax = 0, imax = 0, ncur = 0, nmax = 0, icur = 0;
     long rmax = 0;
     std::vector<long> goff(nl), ioff(nl);
@@ -2014,7 +2016,7 @@ static void sampler_build(mra_plan* pl) {
         const int i = pl->leaf_nodes[t];
         const long nr = pl->row1[i] - pl->row0[i];
         const size_t need = (size_t)nr * nr + 16 * (size_t)nr;
-        if (ncur && (cur + need) * sizeof(double) > SAMPLE_GRAM_BUDGET) {
+        if (ncur && (cur + need) * sizeof(double) > budget) {
             S.bat.push_back(t); S.bat_rows.push_back(rmax);
             cur = 0; icur = 0; ncur = 0; rmax = 0;
         }
@@ -2059,8 +2061,9 @@ static void sampler_factor(mra_plan* pl, size_t b) {
     const size_t t0 = S.bat[b], n = S.bat[b + 1] - t0;
     const long rmax = S.bat_rows[b];
     launch_gemm<EPI_COV>(pl, S.gram.p + t0, n, rmax, rmax);
-    hipLaunchKernelGGL(k_sample_mask, dim3((unsigned)std::min<long>((rmax * rmax + 255) / 256, 64), (unsigned)n), dim3(256), 0, pl->stream,
-                       S.leaves.p + t0, S.knot.p);
+    for (size_t off = 0; off < n; off += SAMPLE_LEAF_GRID)
+        hipLaunchKernelGGL(k_sample_mask, dim3((unsigned)std::min<long>((rmax * rmax + 255) / 256, 64), (unsigned)std::min(SAMPLE_LEAF_GRID, n - off)),
+                           dim3(256), 0, pl->stream, S.leaves.p + t0 + off, S.knot.p);
     HIP_TRY(hipMemsetAsync(S.err.p, 0, sizeof(int), pl->stream));
     hipLaunchKernelGGL(k_panel_chol, dim3((unsigned)n), dim3(256), 0, pl->stream, S.chol.p + t0, S.dn.p, S.err.p, 0);
     int e = 0;
@@ -2093,6 +2096,7 @@ static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, i
     if (pl->host_cov || pl->kp.kind == MRA_KERNEL_HOST) throw MraError(MRA_ERR_INVALID, "mra_sample: MRA_KERNEL_HOST plans cannot sample (leaf C(S, S) is not available)");
     if (pl->reduce_level >= 0 || pl->comm || pl->n_ranks > 1) throw MraError(MRA_ERR_INVALID, "mra_sample: sharded plans cannot sample");
     if (n < 0) throw MraError(MRA_ERR_INVALID, "n_samples < 0");
+    if (sample0 < 0 || (n > 0 && sample0 > INT64_MAX - (n - 1))) throw MraError(MRA_ERR_INVALID, "sample0 < 0, or a sample number past 2^63 - 1");
     if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
     if (n == 0) return;
     if (!out) throw MraError(MRA_ERR_INVALID, "out is NULL");
@@ -2145,8 +2149,9 @@ static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, i
             for (size_t b = 0; b < nb; ++b) {
                 if (S.factored != (int)b) sampler_factor(pl, b);
                 const size_t t0 = S.bat[b], cnt = S.bat[b + 1] - t0;
-                hipLaunchKernelGGL(k_sample_leaf, dim3((unsigned)((S.bat_rows[b] + 15) / 16), (unsigned)cnt), dim3(256), 0, pl->stream,
-                                   S.leaves.p + t0, S.knot.p, S.rep.p, zs, Kn, S.out.p, P);
+                for (size_t off = 0; off < cnt; off += SAMPLE_LEAF_GRID)
+                    hipLaunchKernelGGL(k_sample_leaf, dim3((unsigned)((S.bat_rows[b] + 15) / 16), (unsigned)std::min(SAMPLE_LEAF_GRID, cnt - off)),
+                                       dim3(256), 0, pl->stream, S.leaves.p + t0 + off, S.knot.p, S.rep.p, zs, Kn, S.out.p, P);
             }
             if (cond) {
                 // conditioning by kriging: x + mean_MRA(y - x_o - sqrt(R) eps), one likelihood + predict pass per sample
@@ -2773,6 +2778,11 @@ int mra_plan_set_option(mra_plan* pl, int option, int64_t value) {
         if (option == 16) { pl->use_hi_fold = (int)value; return MRA_OK; }
         if (option == 17) { pl->use_lik_rows = value != 0; return MRA_OK; }
         if (option == 13) { pl->ut_gather = value != 0; return MRA_OK; }
+        if (option == 19) {
+            if (value < 0) throw MraError(MRA_ERR_INVALID, "option 19: the Gram batch budget is a byte count >= 0");
+            if ((size_t)value != pl->smp.gram_bytes) { pl->smp.gram_bytes = (size_t)value; pl->smp.built = false; }
+            return MRA_OK;
+        }
         if (option == 18) {
             if (!pl->regular) return MRA_OK;          // (no fused cascade: nothing is grouped, the decision stays 0)
             pl->cascade_group_siblings = value != 0;
@@ -2816,6 +2826,7 @@ int mra_plan_get_option(mra_plan* pl, int option, int64_t* value) {
             case 17: *value = pl->use_lik_rows; break;
             case 13: *value = pl->ut_gather; break;
             case 18: *value = pl->cascade_group_siblings; break;
+            case 19: *value = (int64_t)pl->smp.gram_bytes; break;
             case 99: *value = pl->dbg; break;
             default: throw MraError(MRA_ERR_INVALID, "unknown option");
         }

@@ -418,6 +418,7 @@ struct mra_plan {
         DevVec<double> G, invd, zc, out, zh, ysave, msave, vsave, dn;
         DevVec<int> err;
         int factored = -1;                        // batch whose factors G holds (-1: none)
+        size_t gram_bytes = 0;                    // MRA_OPT_SAMPLE_GRAM_BYTES (0: SAMPLE_GRAM_BUDGET); a change rebuilds the batches
     } smp;
     // comm
     void* rccl = nullptr;

@@ -35,6 +35,7 @@ MRA_OPT_PRIOR_LEVEL = 15
 MRA_OPT_HI_FOLD = 16
 MRA_OPT_LIK_ROWS = 17
 MRA_OPT_CASCADE_GROUP = 18
+MRA_OPT_SAMPLE_GRAM_BYTES = 19
 MRA_SAMPLE_CONDITIONAL = 1
 MRA_BLOCK_W_ROWS, MRA_BLOCK_LPRIOR, MRA_BLOCK_FRONT, MRA_BLOCK_LEAF = 0, 1, 2, 3
 
@@ -314,7 +315,8 @@ class HipPlan:
 
     def sample(self, n, seed=0, z=None, conditional=False, sample0=0):
         """(n, P) draws from the MRA prior (conditional=False) or posterior, padded leaf order, unreported rows 0.  z: None = Philox
-        draws on the device, a pure function of (seed, slot, sample0 + s); else an (n, sample_slots()) array of latent draws."""
+        draws on the device, a pure function of (seed, slot, sample0 + s); else an (n, sample_slots()) array of latent draws.
+        sample0 >= 0 (MraError MRA_ERR_INVALID otherwise)."""
         n = int(n)
         if n < 0:
             raise ValueError("n must be >= 0")

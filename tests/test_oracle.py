@@ -125,3 +125,49 @@ def test_data_loader_mirrors_the_reference():
     assert yo.shape == (100, 1) and lo.shape == (100, 2)
     with pytest.raises(ValueError):
         dl.load_data("medium")
+
+
+@pytest.mark.parametrize("name", ["g32", "c1", "kat3", "u3"])
+def test_prior_sigma_rows_matches_the_reference_node_blocks(name):
+    """oracle.mra_faithful.prior_sigma_rows (the lineage-restricted Sigma = sum_j B_j K_j B_j^T the sampler tests compare with) against
+    Sigma assembled from what the reference held on every Node (tests/golden/<name>_nodes.npz): on all reported rows, and on row
+    subsets that cut families apart, where it must give the corresponding sub-block."""
+    import _sampling as SM
+    from oracle.mra_faithful import prior_sigma_rows
+    cs = K.load_case(name)
+    t = cs["topo"]
+    rep = np.nonzero(SM.reported(t))[0]
+    S = SM.golden_prior_sigma(name, t)
+    scale = np.abs(S[np.ix_(rep, rep)]).max()
+    tol = (1e-6 if name == "u3" else 1e-10) * scale          # u3: R = 1e-6 Matern32, the reference's explicit inverses (test above)
+    A = prior_sigma_rows(t, cs["locs"], cs["covfun"], rep)
+    assert np.abs(A - S[np.ix_(rep, rep)]).max() <= tol
+    rng = np.random.RandomState(4)
+    for sub in (rep[::3], rng.choice(rep, min(len(rep), 17), replace=False), rep[-1:]):
+        assert np.abs(prior_sigma_rows(t, cs["locs"], cs["covfun"], sub) - S[np.ix_(sub, sub)]).max() <= tol
+
+
+def test_prior_sigma_rows_is_exact_within_a_leaf_of_a_deep_tree():
+    """Within one leaf the MRA prior is the covariance itself: on a 128^2 M = 4 tree the lineage-restricted
+    oracle, evaluated at the rows of two leaves of different families, gives C(S_j, S_j) on each leaf's knots and the MRA's
+    low-rank cross-covariance between them - what the full assembly gives for those rows."""
+    import _sampling as SM
+    import pymra_amd.MRATools as mt
+    from pymra_amd.topology import build_topology
+    from oracle.mra_faithful import prior_sigma_rows
+    np.random.seed(3)
+    locs = mt.genLocations2d(Nx=128, Ny=128)
+    t = build_topology(locs, 16, 4, 4)
+    spec = mt.KernelSpec(mt.KIND_MATERN32, 0.1, 1.0)
+    leaves = np.nonzero(np.asarray(t.node_leaf, dtype=bool))[0]
+    a, b = int(leaves[0]), int(leaves[-1])
+    ra, rb = K.node_real_rows(t, a), K.node_real_rows(t, b)
+    S = prior_sigma_rows(t, locs, spec.evaluate, np.concatenate([ra, rb]))
+    Sa = prior_sigma_rows(t, locs, spec.evaluate, ra)
+    assert np.abs(S[:len(ra), :len(ra)] - Sa).max() <= 1e-13
+    for r, blk in ((ra, Sa), (rb, S[len(ra):, len(ra):])):
+        kn = np.isin(r, t.knot_rows[t.knot_ptr[SM.leaf_of_row(t, r[0])]:t.knot_ptr[SM.leaf_of_row(t, r[0]) + 1]])
+        C = np.asarray(spec.evaluate(locs[t.perm[r[kn]]], locs[t.perm[r[kn]]]))
+        assert np.abs(blk[np.ix_(kn, kn)] - C).max() <= 1e-10
+    # the two leaves share only the root: their cross-covariance is B_0[ra] K_0 B_0[rb]^T, rank <= r
+    assert np.linalg.matrix_rank(S[:len(ra), len(ra):], tol=1e-9) <= 16

@@ -44,3 +44,34 @@ def test_sampler_surface_is_exported():
     assert plan.MRA_SAMPLE_CONDITIONAL == 1
     hdr = open(K.os.path.join(K.ROOT, "include", "mra_hip.h")).read()
     assert "#define MRA_SAMPLE_CONDITIONAL 1u" in hdr
+
+
+def test_gram_budget_option_round_trip(built_library, tmp_path):
+    """MRA_OPT_SAMPLE_GRAM_BYTES (19) reads back what was set, 0 is the default and a negative budget is refused.  Host dry run
+    (MRA_HOST_DRYRUN=1: the plan lives in host memory, nothing is launched), so this runs without a GPU."""
+    import os
+    import subprocess
+    import sys
+    child = tmp_path / "child.py"
+    child.write_text(r'''
+import os, sys
+sys.path.insert(0, os.environ["MRA_ROOT"]); sys.path.insert(0, os.path.join(os.environ["MRA_ROOT"], "tests"))
+import _cases as K
+from pymra_amd import plan as P
+cs = K.load_case("g32")
+pl = P.HipPlan(cs["topo"], 0)
+assert pl.get_option(P.MRA_OPT_SAMPLE_GRAM_BYTES) == 0
+for v in (1, 123456, 3 << 30, 0):
+    pl.set_option(P.MRA_OPT_SAMPLE_GRAM_BYTES, v); assert pl.get_option(P.MRA_OPT_SAMPLE_GRAM_BYTES) == v
+try:
+    pl.set_option(P.MRA_OPT_SAMPLE_GRAM_BYTES, -1)
+    raise SystemExit("a negative budget must be refused")
+except P.MraError as e:
+    assert e.code == -1
+assert pl.get_option(P.MRA_OPT_SAMPLE_GRAM_BYTES) == 0
+pl.close()
+print("GRAM_OPT_OK")
+''')
+    env = dict(os.environ, MRA_ROOT=K.ROOT, MRA_HOST_DRYRUN="1")
+    res = subprocess.run([sys.executable, str(child)], env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0 and "GRAM_OPT_OK" in res.stdout, (res.stdout + res.stderr)[-2000:]
