@@ -147,6 +147,25 @@ int mra_sample_slots(mra_plan *plan, int64_t *n_slots);
 int mra_sample(mra_plan *plan, uint32_t flags, int64_t n_samples, uint64_t seed, int64_t sample0,
                const double *z, double *out);
 
+/* Factor once, solve many (no counterpart in the reference, which re-runs calculatePosterior for every observation vector,
+ * pyMRA/MRANode.py:403-523): the leaves' L_c and Ut and the fronts' Lt and Zt of one likelihood pass are a complete factorisation of
+ * the posterior precision of the MRA weights; they do not depend on y.  For n_cols observation vectors Y (n_cols x P, row-major:
+ * vector k at Y + k P, padded leaf order, read at the plan's OBSERVED rows only - the mask of the last set_obs)
+ *     mean (n_cols x P, or NULL): mean[k] = E[x | Y[k] at the observed rows] = the mean mra_run + mra_get_predict give for y = Y[k];
+ *                                 unreported rows (phantoms, rows a 1-D split drops) are exactly 0
+ *     quad (n_cols x n_cols, or NULL): Y_o^T (Sigma_MRA[o, o] + R I)^-1 Y_o, so that quad[k][k] is the u of mra_get_likelihood for
+ *                                 y = Y[k] (the log-determinant d does not depend on y)
+ * Columns are processed in blocks of 16 (the N of v_mfma_f64_16x16x4_f64).  quad is returned BLOCK-DIAGONAL: entries whose row and
+ * column lie in the same block of 16 columns (k / 16 equal) are computed, all others are set to NaN - a cross-block entry needs the
+ * forward sweeps of both blocks at once.  Callers that need a full quad of more than 16 columns pass overlapping column sets.
+ * The first call (and the first after mra_run, mra_run_resume, mra_sample or any set_*) runs one likelihood pass with W at every
+ * row (MRA_OPT_LIK_ROWS overridden inside); later calls reuse the factors and launch only the solve kernels.  Afterwards y, every
+ * option and what mra_get_likelihood / mra_get_predict return are as the caller left them (mra_get_timers / mra_get_kernel_stats
+ * describe the call's own pass; all zero when none ran).  flags: 0.
+ * MRA_ERR_STATE before set_locs / set_obs / set_kernel; MRA_ERR_INVALID for MRA_KERNEL_HOST plans, sharded plans, n_cols < 0 and a
+ * non-finite Y at an observed row.  Work buffers are allocated on the first call.  Blocking. */
+int mra_solve(mra_plan *plan, uint32_t flags, int64_t n_cols, const double *Y, double *mean, double *quad);
+
 /* Diagnostics for tests (the reference exposes these as attributes of Node objects):
  * what = 0: whitened basis W (P x ldw, row-major) ; 1: per-node log-det terms (n_nodes);
  * copies min(capacity, available) doubles into out, returns the available count in *n_avail.
@@ -235,6 +254,9 @@ int mra_get_timers(mra_plan *plan, double *out_ms, int capacity);
 #define MRA_OPT_SAMPLE_GRAM_BYTES 19 /* mra_sample: bytes of leaf Gram blocks (+ inverted diagonal blocks) per factorisation batch, at least one
                                       leaf per batch; 0 (default): 1.5 GB.  A new value drops the sampler's index maps and buffers, which
                                       the next mra_sample rebuilds.  The draws do not depend on it. */
+#define MRA_OPT_SAMPLE_SOLVE   20  /* mra_sample with MRA_SAMPLE_CONDITIONAL: 0 (default): one likelihood + predict pass per draw; 1: the pseudo-data of
+                                      a block of up to 16 draws are 16 right-hand sides of mra_solve's sweeps over the factors of the
+                                      block's prior pass (one pass per block instead of 1 + 16) */
 int mra_plan_set_option(mra_plan *plan, int option, int64_t value);
 /* current value of an option (so that a caller can change one temporarily and put it back) */
 int mra_plan_get_option(mra_plan *plan, int option, int64_t *value);

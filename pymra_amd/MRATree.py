@@ -176,6 +176,35 @@ class MRATree(object):
         out[t.perm[rows], :] = x[:, rows].T
         return out
 
+    def solve(self, Y):
+        """Kriging means and the quadratic form for c observation vectors at once, from ONE factorisation of this tree (the
+        factors do not depend on the observed values).  Y: (N,) or (N, c) in the caller's row order, on this tree's observation
+        mask (values at unobserved locations are ignored).  -> (mean (N, c), quad (c, c)): mean[:, k] is what predict() gives for
+        observations Y[:, k] (rows outside every leaf 0), quad = Y_o^T (Sigma_MRA + R I)^-1 Y_o - exact within blocks of 16 columns,
+        NaN between columns of different blocks.  getLikelihood() and predict() are unchanged afterwards."""
+        if self.kernel is None:
+            raise NotImplementedError("solve needs a device kernel: trees built from an opaque callable or a dense matrix cannot solve")
+        Y = np.asarray(Y, dtype=np.float64)
+        if Y.ndim == 1:
+            Y = Y.reshape(-1, 1)
+        if Y.ndim != 2 or Y.shape[0] != len(self.locs):
+            raise ValueError("Y must have shape (N,) or (N, c) with N = %d" % len(self.locs))
+        t = self.topology
+        real = t.perm >= 0
+        Yp = np.zeros((Y.shape[1], t.P))
+        Yp[:, real] = Y[t.perm[real], :].T
+        m, quad = self.plan.solve(Yp)
+        rows = real & np.asarray(t.in_leaf, dtype=bool)
+        mean = np.zeros((len(self.locs), Y.shape[1]))
+        mean[t.perm[rows], :] = m[:, rows].T
+        return mean, quad
+
+    def getLikelihoods(self, Y):
+        """(c,) likelihoods d + u_k of the columns of Y on this tree's observation mask (getLikelihood() per column; the
+        log-determinant d is shared)."""
+        _, quad = self.solve(Y)
+        return float(np.asarray(self.root.d).ravel()[0]) + np.diag(quad)
+
     # ---- diagnostics surface (pyMRA/MRATree.py:101-132, 445-511); host-side de-whitening, see pymra_amd.diagnostics
     def getNodeBlocks(self, posterior=True):
         """Per-node ``B, kInv, k, kC`` (+ ``A, omg, kTil, kTilC, BTil[res]``, cumulative ``d, u``) of every node

@@ -1,0 +1,158 @@
+// mra_launch_solve.hip - mra_solve: descriptors, work buffers and the launch sequence of one block of at most
+// 16 right-hand sides over the factors a likelihood pass left in the plan.  A translation unit of its own: the kernels of the pass
+// keep their object code.
+#define MRA_KERNELS_TEMPLATES_ONLY
+#include "mra_solve_kernels.h"
+
+static const int SOLVE_QUAD_BLOCKS = 512;
+
+void mra_solver_build(mra_plan* pl) {
+    mra_plan::Solver& S = pl->slv;
+    if (S.built) return;
+    if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
+    const long P = pl->P;
+    const size_t nl = pl->leaf_nodes.size();
+    const int nn = pl->n_nodes;
+    // node buffers: a leaf's g / beta (anc x16), a front's [z ; g] / [alpha ; chain] ((cw + anc) x16)
+    std::vector<long> noff(nn + 1, 0);
+    std::vector<int> anc(nn, 0);
+    for (int i = 0; i < nn; ++i) {
+        const int m = pl->node_level[i];
+        anc[i] = pl->Ka - pl->asuf[m];
+        const int own = pl->leaf[i] ? 0 : pl->cw[m];
+        if (!pl->leaf[i] && pl->lev[m].nf != own + anc[i] + MRA_YB) throw MraError(MRA_ERR_STATE, "mra_solve: front size does not match the column layout");
+        const int p = pl->parent[i];
+        if (p >= 0 && anc[i] != pl->cw[pl->node_level[p]] + anc[p]) throw MraError(MRA_ERR_STATE, "mra_solve: ancestor chain does not match the column layout");
+        if (p < 0 && anc[i] != 0) throw MraError(MRA_ERR_STATE, "mra_solve: the root has ancestor columns");
+        noff[i + 1] = noff[i] + (long)(own + anc[i]) * 16;
+    }
+    const long n_uy = pl->obs_off_host.empty() ? 0 : pl->obs_off_host.back() * 16;
+    S.nb.alloc((size_t)std::max<long>(noff[nn], 1));
+    S.uy.alloc((size_t)std::max<long>(n_uy, 1));
+    S.yb.alloc((size_t)16 * P); S.out.alloc((size_t)16 * P);
+    S.qpart.alloc((size_t)SOLVE_QUAD_BLOCKS * 256); S.quad.alloc(256);
+    S.msave.alloc(P); S.vsave.alloc(P);
+    S.work_bytes = sizeof(double) * ((size_t)noff[nn] + (size_t)n_uy + (size_t)34 * P + (size_t)SOLVE_QUAD_BLOCKS * 256 + 256);
+    std::vector<SolveLeaf> lv(nl);
+    std::vector<SolveSeg> segs;
+    std::vector<int> tile_leaf((size_t)(P / 16), -1);
+    std::vector<unsigned char> is_knot(P, 0), rep(P, 0);
+    for (int i = 0; i < nn; ++i)
+        for (long k = pl->knot_ptr[i]; k < pl->knot_ptr[i + 1]; ++k) {
+            const long row = pl->knot_rows[k];
+            if (row < 0 || row >= P) throw MraError(MRA_ERR_INVALID, "knot row out of range");
+            is_knot[row] = 1;
+        }
+    for (size_t t = 0; t < nl; ++t) {
+        const int i = pl->leaf_nodes[t];
+        const int m = pl->node_level[i], nop = pl->leaf_nop[t], p = pl->parent[i];
+        const double* Pn = pl->panel.p + pl->leaf_poff[t];
+        SolveLeaf L{};
+        L.Lc = Pn; L.Ut = Pn + (size_t)nop * nop;
+        L.obs = pl->obs_idx.p + pl->obs_off_host[t];
+        L.uy = S.uy.p + pl->obs_off_host[t] * 16;
+        L.gb = S.nb.p + noff[i];
+        L.chain = p >= 0 ? S.nb.p + noff[p] : nullptr;
+        L.row0 = pl->row0[i]; L.nrows = (int)(pl->row1[i] - pl->row0[i]);
+        L.nop = nop; L.anc = anc[i]; L.a0 = pl->asuf[m];
+        lv[t] = L;
+        if (nop) segs.push_back(SolveSeg{L.uy, nop, 1});
+        for (long r = pl->row0[i]; r < pl->row1[i]; ++r) rep[r] = is_knot[r];
+        for (long tl = pl->row0[i] / 16; tl < pl->row1[i] / 16; ++tl) tile_leaf[tl] = (int)t;
+    }
+    std::vector<SolveFront> fv;
+    std::vector<const double*> kids;
+    S.lev_off.assign(pl->n_levels + 1, 0);
+    S.lev_lds.assign(pl->n_levels, 0);
+    for (int m = 0; m < pl->n_levels; ++m) {
+        const LevelData& lvl = pl->lev[m];
+        S.lev_off[m] = fv.size();
+        for (size_t s = 0; s < lvl.nodes.size(); ++s) {
+            const int i = lvl.nodes[s];
+            if (pl->node_slot[i] != (int)s) throw MraError(MRA_ERR_STATE, "mra_solve: node slot order");
+            const int p = pl->parent[i];
+            SolveFront N{};
+            N.F = lvl.F.p + s * (size_t)lvl.nf * lvl.ldf;
+            N.buf = S.nb.p + noff[i];
+            N.chain = p >= 0 ? S.nb.p + noff[p] : nullptr;
+            N.ld = lvl.ldf; N.cw = lvl.cw; N.anc = anc[i];
+            N.kid0 = (int)kids.size();
+            for (int k = pl->child_ptr[i]; k < pl->child_ptr[i + 1]; ++k) {
+                const int ch = pl->child_list[k];
+                kids.push_back(S.nb.p + noff[ch] + (pl->leaf[ch] ? 0 : (long)pl->cw[pl->node_level[ch]] * 16));
+            }
+            N.nkid = (int)kids.size() - N.kid0;
+            fv.push_back(N);
+            segs.push_back(SolveSeg{N.buf, lvl.cw, -1});
+        }
+        S.lev_lds[m] = sizeof(double) * ((size_t)lvl.cw * 16 + (lvl.cw <= SOLVE_FRONT_STAGE ? (size_t)lvl.cw * lvl.cw : 0));
+        if (S.lev_lds[m] > 64 * 1024) throw MraError(MRA_ERR_INVALID, "mra_solve: blocks wider than 512 columns are not supported");
+    }
+    S.lev_off[pl->n_levels] = fv.size();
+    if (kids.empty()) kids.push_back(nullptr);
+    if (segs.empty()) segs.push_back(SolveSeg{nullptr, 0, 1});
+    if (fv.empty()) fv.push_back(SolveFront{});
+    if (nl) S.leaves.upload(lv);
+    S.fronts.upload(fv); S.kids.upload(kids); S.segs.upload(segs);
+    S.tile_leaf.upload(tile_leaf); S.rep.upload(rep);
+    S.built = true;
+}
+
+template <int DIM>
+static void launch_rows(mra_plan* pl) {
+    mra_plan::Solver& S = pl->slv;
+    const dim3 grid((unsigned)((pl->P / 16 + 3) / 4)), block(256);
+#define MRA_SOLVE_ROWS(MD) hipLaunchKernelGGL((k_solve_rows<DIM, MD>), grid, block, 0, pl->stream, S.leaves.p, S.tile_leaf.p, pl->W.p, (long)pl->ldw, \
+                                              pl->X.p, S.rep.p, pl->kp, S.out.p, pl->P)
+    switch (pl->kp.mode) {
+        case 0: MRA_SOLVE_ROWS(0); break;
+        case 1: MRA_SOLVE_ROWS(1); break;
+        case 2: MRA_SOLVE_ROWS(2); break;
+        default: MRA_SOLVE_ROWS(3); break;
+    }
+#undef MRA_SOLVE_ROWS
+}
+
+void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad) {
+    mra_plan::Solver& S = pl->slv;
+    const unsigned nl = (unsigned)pl->leaf_nodes.size();
+    if (pl->d != 1 && pl->d != 2) throw MraError(MRA_ERR_INVALID, "mra_solve: 1-D and 2-D locations only");
+    // 1. forward, leaves
+    if (nl) {
+        hipLaunchKernelGGL(k_solve_leaf_trsm<false>, dim3(nl), dim3(64), 0, pl->stream, S.leaves.p, S.yb.p, pl->P);
+        hipLaunchKernelGGL(k_solve_leaf_g, dim3(nl), dim3(256), 0, pl->stream, S.leaves.p);
+    }
+    // 2. forward, fronts bottom-up
+    for (int m = pl->n_levels - 1; m >= 0; --m) {
+        const unsigned n = (unsigned)(S.lev_off[m + 1] - S.lev_off[m]);
+        if (n) hipLaunchKernelGGL(k_solve_front_fwd, dim3(n), dim3(256), S.lev_lds[m], pl->stream, S.fronts.p + S.lev_off[m], S.kids.p);
+    }
+    // 3. quadratic form (the z of the fronts are overwritten by the backward sweep)
+    if (want_quad) {
+        const int nseg = (int)S.segs.n;
+        const int nb = std::min(SOLVE_QUAD_BLOCKS, std::max(nseg, 1));
+        hipLaunchKernelGGL(k_solve_quad_part, dim3((unsigned)nb), dim3(256), 0, pl->stream, S.segs.p, nseg, S.qpart.p);
+        hipLaunchKernelGGL(k_solve_quad_sum, dim3(1), dim3(256), 0, pl->stream, S.qpart.p, nb, S.quad.p);
+    }
+    if (!want_mean) return;
+    // 4. backward, fronts top-down
+    for (int m = 0; m < pl->n_levels; ++m) {
+        const unsigned n = (unsigned)(S.lev_off[m + 1] - S.lev_off[m]);
+        if (n) hipLaunchKernelGGL(k_solve_front_bwd, dim3(n), dim3(256), S.lev_lds[m], pl->stream, S.fronts.p + S.lev_off[m]);
+    }
+    // 5. backward, leaves; 6. rows
+    if (nl) {
+        hipLaunchKernelGGL(k_solve_leaf_sbeta, dim3(nl), dim3(256), 0, pl->stream, S.leaves.p);
+        hipLaunchKernelGGL(k_solve_leaf_trsm<true>, dim3(nl), dim3(64), 0, pl->stream, S.leaves.p, S.yb.p, pl->P);
+    }
+    if (pl->d == 1) launch_rows<1>(pl); else launch_rows<2>(pl);
+}
+
+void mra_solver_pseudo(mra_plan* pl, const double* y, const double* x, const SampleZ& zs, long slot0) {
+    hipLaunchKernelGGL(k_solve_pseudo, dim3((unsigned)((pl->P + 255) / 256)), dim3(256), 0, pl->stream, y, x, zs, slot0, std::sqrt(pl->R),
+                       pl->slv.yb.p, pl->P);
+}
+void mra_solver_addmean(mra_plan* pl, double* x, int ns) {
+    const long n = (long)ns * pl->P;
+    hipLaunchKernelGGL(k_solve_addmean, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, pl->stream, x, pl->slv.out.p, n);
+}

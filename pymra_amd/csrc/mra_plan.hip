@@ -725,6 +725,7 @@ static void build_leaf(mra_plan* pl, const double* y) {
     ArenaScope arena(&pl->arena);
     const size_t nl = pl->leaf_nodes.size();
     pl->cphantom_valid = false;
+    pl->slv.valid = false; pl->slv.built = false;      // mra_solve's descriptors point into the leaves' panels
     pl->leaf_nop.assign(nl, 0);
     pl->leaf_poff.assign(nl + 1, 0);
     pl->leaf_ioff.assign(nl + 1, 0);
@@ -1519,6 +1520,7 @@ static void run_add_identity(mra_plan* pl, int m) {
 static void finish_run(mra_plan* pl);
 
 static void run_fronts_and_predict(mra_plan* pl, int m_from, bool resume) {
+    pl->slv.valid = false;
     for (int m = m_from; m >= 0; --m) {
         const bool is_red = (m == pl->reduce_level);
         bool red_summed = false;             // the reduce level's log-det sum was written by its assembly launch
@@ -1727,6 +1729,7 @@ static void run_all(mra_plan* pl, uint32_t flags) {
     pl->hi_fold_now = false;
     pl->pass_open = true;
     pl->run_flags = flags;
+    pl->slv.valid = false;               // whatever runs a pass rewrites the factors (mra_solve sets the mark again after its own)
     for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = mra_plan::KStat();
     const bool pred = flags & MRA_RUN_PREDICT;
     phase_mark(pl, 0);
@@ -2103,6 +2106,8 @@ static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, i
     HIP_TRY(mraSetDevice(pl->device));
     sampler_build(pl);
     mra_plan::Sampler& S = pl->smp;
+    S.use_solve = cond && pl->slv.in_sampler;
+    if (S.use_solve) mra_solver_build(pl);
     const long P = pl->P, Kn = S.n_coarse, n_slots = Kn + 2 * P;
     const size_t nb = S.bat.size() - 1;
     // caller-given draws are staged a block of samples at a time (at most 512 MB of them)
@@ -2153,7 +2158,13 @@ static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, i
                     hipLaunchKernelGGL(k_sample_leaf, dim3((unsigned)((S.bat_rows[b] + 15) / 16), (unsigned)std::min(SAMPLE_LEAF_GRID, cnt - off)),
                                        dim3(256), 0, pl->stream, S.leaves.p + t0 + off, S.knot.p, S.rep.p, zs, Kn, S.out.p, P);
             }
-            if (cond) {
+            if (cond && S.use_solve) {
+                // conditioning by kriging, all draws of the block at once: the factors of the prior pass above are those of the
+                // posterior mean (they do not depend on y), so the block's pseudo-data are 16 right-hand sides of mra_solve's sweeps
+                mra_solver_pseudo(pl, S.ysave.p, S.out.p, zs, Kn + P);
+                mra_solver_block(pl, true, false);
+                mra_solver_addmean(pl, S.out.p, ns);
+            } else if (cond) {
                 // conditioning by kriging: x + mean_MRA(y - x_o - sqrt(R) eps), one likelihood + predict pass per sample
                 for (int s = 0; s < ns; ++s) {
                     double* xs = S.out.p + (long)s * P;
@@ -2171,6 +2182,73 @@ static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, i
         }
     }
     HIP_TRY(hipGetLastError());
+}
+
+// ---- solver (mra_solve) ------------------------------------------------------------------------------------
+static void solve_all(mra_plan* pl, uint32_t flags, int64_t n, const double* Y, double* mean, double* quad) {
+    if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
+    if (flags) throw MraError(MRA_ERR_INVALID, "unknown mra_solve flags");
+    if (!(pl->have_locs && pl->have_kernel)) throw MraError(MRA_ERR_STATE, "mra_solve needs set_locs and set_kernel first");
+    if (!pl->have_obs) throw MraError(MRA_ERR_STATE, "mra_solve needs set_obs first");
+    if (pl->host_cov || pl->kp.kind == MRA_KERNEL_HOST) throw MraError(MRA_ERR_INVALID, "mra_solve: MRA_KERNEL_HOST plans cannot solve (C(S, o) is evaluated on the device)");
+    if (pl->reduce_level >= 0 || pl->comm || pl->n_ranks > 1) throw MraError(MRA_ERR_INVALID, "mra_solve: sharded plans cannot solve");
+    if (n < 0) throw MraError(MRA_ERR_INVALID, "n_cols < 0");
+    if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
+    if (n == 0) return;
+    if (!Y) throw MraError(MRA_ERR_INVALID, "Y is NULL");
+    const long P = pl->P;
+    for (int64_t k = 0; k < n; ++k)
+        for (long p = 0; p < P; ++p)
+            if (pl->y_finite_host[p] && !std::isfinite(Y[k * P + p])) {
+                char m[128];
+                snprintf(m, sizeof m, "mra_solve: Y is not finite at an observed row (column %lld, padded row %ld)", (long long)k, p);
+                throw MraError(MRA_ERR_INVALID, m);
+            }
+    HIP_TRY(mraSetDevice(pl->device));
+    mra_solver_build(pl);
+    mra_plan::Solver& S = pl->slv;
+    if (!S.valid) {
+        // the factors: one likelihood pass with W at every row (as sample_all's prior pass); what the caller reads back afterwards -
+        // the last mra_run's likelihood, mean and var - is put back.  y and the options are not touched.
+        const bool had_ran = pl->ran;
+        const uint32_t had_flags = pl->run_flags;
+        const double had_d = pl->res_d, had_u = pl->res_u;
+        const bool had_pred = had_ran && (had_flags & MRA_RUN_PREDICT);
+        if (had_pred) {
+            HIP_TRY(hipMemcpyAsync(S.msave.p, pl->mean.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+            HIP_TRY(hipMemcpyAsync(S.vsave.p, pl->var.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+        }
+        auto restore = [&]() {
+            if (had_pred) {
+                hipMemcpyAsync(pl->mean.p, S.msave.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream);
+                hipMemcpyAsync(pl->var.p, S.vsave.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream);
+            }
+            hipStreamSynchronize(pl->stream);
+            pl->ran = had_ran; pl->run_flags = had_flags; pl->res_d = had_d; pl->res_u = had_u;
+        };
+        struct OnExit { decltype(restore)& f; ~OnExit() { f(); } } on_exit{restore};     // success and error paths alike
+        sampler_prior(pl);
+        HIP_TRY(hipStreamSynchronize(pl->stream));
+        HIP_TRY(hipGetLastError());
+        S.valid = true;
+    } else {
+        for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = mra_plan::KStat();      // the kernel statistics describe this call: no pass ran
+    }
+    if (quad) for (int64_t e = 0; e < n * n; ++e) quad[e] = std::nan("");
+    for (int64_t c0 = 0; c0 < n; c0 += 16) {
+        const int nc = (int)std::min<int64_t>(16, n - c0);
+        HIP_TRY(hipMemcpyAsync(S.yb.p, Y + c0 * P, (size_t)nc * P * sizeof(double), hipMemcpyHostToDevice, pl->stream));
+        if (nc < 16) HIP_TRY(hipMemsetAsync(S.yb.p + (size_t)nc * P, 0, (size_t)(16 - nc) * P * sizeof(double), pl->stream));
+        mra_solver_block(pl, mean != nullptr, quad != nullptr);
+        if (mean) HIP_TRY(hipMemcpyAsync(mean + c0 * P, S.out.p, (size_t)nc * P * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
+        double qb[256];
+        if (quad) HIP_TRY(hipMemcpyAsync(qb, S.quad.p, sizeof qb, hipMemcpyDeviceToHost, pl->stream));
+        HIP_TRY(hipStreamSynchronize(pl->stream));
+        HIP_TRY(hipGetLastError());
+        if (quad)
+            for (int i = 0; i < nc; ++i)
+                for (int j = 0; j < nc; ++j) quad[(c0 + i) * n + c0 + j] = qb[i * 16 + j];
+    }
 }
 
 // ---- caller-order variants: the permutation work of an end-to-end MRATree(...) call done inside the library -----------------
@@ -2301,6 +2379,7 @@ static void require(bool ok, const char* msg) { if (!ok) throw MraError(MRA_ERR_
 // ---- inputs and results in padded leaf order (the exports, their caller-order variants and the one-call constructor) ----------
 static void set_locs(mra_plan* pl, const double* locs) {
     HIP_TRY(mraSetDevice(pl->device));
+    pl->slv.valid = false;
     HIP_TRY(mraMemcpy(pl->X.p, locs, (size_t)pl->P * pl->d * sizeof(double), hipMemcpyHostToDevice));
     if (!pl->knots_pending) set_knot_coords(pl, locs);
     pl->have_locs = true;
@@ -2573,6 +2652,7 @@ int mra_plan_set_obs(mra_plan* pl, const double* y, double R) {
 int mra_plan_set_kernel(mra_plan* pl, int kind, const double* params, int n) {
     return guarded(pl, [&] {
         require(pl, "mra_plan_set_kernel: plan is NULL");
+        pl->slv.valid = false;
         if (kind == MRA_KERNEL_HOST) {
             if (!pl->have_obs) throw MraError(MRA_ERR_STATE, "MRA_KERNEL_HOST needs mra_plan_set_obs first (leaf blocks are per observed row)");
             HIP_TRY(mraSetDevice(pl->device));
@@ -2621,6 +2701,7 @@ int mra_plan_set_kernel(mra_plan* pl, int kind, const double* params, int n) {
 int mra_plan_set_cov_block(mra_plan* pl, int32_t node, const double* C, int64_t n_rows, int64_t n_cols, const double* diag) {
     return guarded(pl, [&] {
         require(pl && C, "mra_plan_set_cov_block: plan or C is NULL");
+        pl->slv.valid = false;
         if (!pl->host_cov) throw MraError(MRA_ERR_STATE, "select MRA_KERNEL_HOST with mra_plan_set_kernel first");
         if (node < 0 || node >= pl->n_nodes) throw MraError(MRA_ERR_INVALID, "node out of range");
         HIP_TRY(mraSetDevice(pl->device));
@@ -2678,6 +2759,10 @@ int mra_sample_slots(mra_plan* pl, int64_t* n_slots) {
 
 int mra_sample(mra_plan* pl, uint32_t flags, int64_t n_samples, uint64_t seed, int64_t sample0, const double* z, double* out) {
     return guarded(pl, [&] { require(pl, "mra_sample: plan is NULL"); sample_all(pl, flags, n_samples, seed, sample0, z, out); return MRA_OK; });
+}
+
+int mra_solve(mra_plan* pl, uint32_t flags, int64_t n_cols, const double* Y, double* mean, double* quad) {
+    return guarded(pl, [&] { require(pl, "mra_solve: plan is NULL"); solve_all(pl, flags, n_cols, Y, mean, quad); return MRA_OK; });
 }
 
 int mra_get_likelihood(mra_plan* pl, double* d, double* u) {
@@ -2762,6 +2847,7 @@ int mra_plan_set_option(mra_plan* pl, int option, int64_t value) {
         // options that change which kernel produces or factorises the leaves' C blocks bring the phantom-row launch back; the others
         // (timing, front / knot / solve / update variants) never touch C
         if (option == 2 || option == 3 || option == 6 || option == 11) pl->cphantom_valid = false;
+        if (option != 1 && option != 20) pl->slv.valid = false;     // the next pass may run other kernels: mra_solve factorises again
         if (option == 1) { pl->ktiming = value != 0; return MRA_OK; }
         if (option == 2) { pl->use_fused = value != 0; return MRA_OK; }
         if (option == 3) { pl->gemm_lds = value != 0; return MRA_OK; }
@@ -2781,6 +2867,11 @@ int mra_plan_set_option(mra_plan* pl, int option, int64_t value) {
         if (option == 19) {
             if (value < 0) throw MraError(MRA_ERR_INVALID, "option 19: the Gram batch budget is a byte count >= 0");
             if ((size_t)value != pl->smp.gram_bytes) { pl->smp.gram_bytes = (size_t)value; pl->smp.built = false; }
+            return MRA_OK;
+        }
+        if (option == 20) {
+            if (value != 0 && value != 1) throw MraError(MRA_ERR_INVALID, "option 20: 0 or 1");
+            pl->slv.in_sampler = (int)value;
             return MRA_OK;
         }
         if (option == 18) {
@@ -2827,6 +2918,7 @@ int mra_plan_get_option(mra_plan* pl, int option, int64_t* value) {
             case 13: *value = pl->ut_gather; break;
             case 18: *value = pl->cascade_group_siblings; break;
             case 19: *value = (int64_t)pl->smp.gram_bytes; break;
+            case 20: *value = pl->slv.in_sampler; break;
             case 99: *value = pl->dbg; break;
             default: throw MraError(MRA_ERR_INVALID, "unknown option");
         }
@@ -2991,6 +3083,7 @@ int mra_tree_free(mra_tree* t) { return guarded(nullptr, [&] { delete t; return 
 int mra_plan_set_reduce_level(mra_plan* pl, int level) {
     return guarded(pl, [&] {
         require(pl, "mra_plan_set_reduce_level: plan is NULL");
+        pl->slv.valid = false;
         if (level >= pl->n_levels) throw MraError(MRA_ERR_INVALID, "reduce level out of range");
         if (pl->lowrank_parent && level >= pl->n_levels - 3)
             throw MraError(MRA_ERR_INVALID, "reduce level too deep: the fronts of the leaves' parents are kept as panels on this plan (set MRA_NO_LOWRANK_PARENT=1 before creating it)");

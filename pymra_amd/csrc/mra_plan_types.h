@@ -200,6 +200,26 @@ struct DevVec {
     ~DevVec() { release(); }
 };
 
+// ---- mra_solve: descriptors of the solve kernels (mra_solve_kernels.h, launched from mra_launch_solve.hip) ----
+struct SolveLeaf {              // one leaf
+    const double* Lc;           // nop x nop (ld nop): lower Cholesky factor of v_M(o, o) + R I, identity rows at phantom observations
+    const double* Ut;           // anc (+ the y block, not read) x nop: Ut[a][k] = (L_c^-1 W[o, a0 + a])[k]
+    const int* obs;             // nop padded rows of the observations (-1: padding)
+    double* uy;                 // nop x16: U_y, then s, then q
+    double* gb;                 // anc x16: g (forward), then beta (backward)
+    const double* chain;        // anc x16: the parent's [alpha ; chain] (nullptr when anc == 0)
+    long row0;
+    int nrows, nop, anc, a0;    // a0: first ancestor column in W
+};
+struct SolveFront {             // one non-leaf node
+    const double* F;            // Lt in rows [0, cw), Zt in rows [cw, cw + anc) (its y block below is not read); row stride ld
+    double* buf;                // (cw + anc) x16: [z ; g] after the forward sweep, [alpha ; chain] after the backward sweep
+    const double* chain;        // anc x16: the parent's buf (nullptr for the root)
+    int ld, cw, anc;
+    int kid0, nkid;             // children's g blocks ((cw + anc) x16 each) in the kid pointer list
+};
+struct SolveSeg { const double* p; int n; int sign; };      // rows of the quadratic form: sign * sum_rows v v^T
+
 struct LevelData {
     std::vector<int> nodes;          // non-leaf nodes of this level
     int cw = 0, cwt = 0, c0 = 0, a0 = 0, nf = 0, na = 0;
@@ -418,8 +438,26 @@ struct mra_plan {
         DevVec<double> G, invd, zc, out, zh, ysave, msave, vsave, dn;
         DevVec<int> err;
         int factored = -1;                        // batch whose factors G holds (-1: none)
+        bool use_solve = false;                   // this call conditions its draws through mra_solve's sweeps (MRA_OPT_SAMPLE_SOLVE)
         size_t gram_bytes = 0;                    // MRA_OPT_SAMPLE_GRAM_BYTES (0: SAMPLE_GRAM_BUDGET); a change rebuilds the batches
     } smp;
+    // solver (mra_solve): the factors of a likelihood pass with W at every row, kept for any number of right-hand sides.  Index maps,
+    // descriptors and work buffers are built on the first call (and again after new observations: the leaves' panels move).
+    struct Solver {
+        bool built = false;
+        bool valid = false;                       // "factors valid, W complete": set by mra_solve's own pass, cleared by mra_run,
+                                                  // mra_run_resume, mra_sample and every set_*
+        int in_sampler = 0;                       // MRA_OPT_SAMPLE_SOLVE
+        DevVec<SolveLeaf> leaves;
+        DevVec<SolveFront> fronts;                // by level, then slot
+        std::vector<size_t> lev_off, lev_lds;     // [level]: first front of the level in `fronts`; dynamic LDS of its launches
+        DevVec<const double*> kids;
+        DevVec<SolveSeg> segs;
+        DevVec<int> tile_leaf;                    // [P / 16] leaf of a row tile (-1: none)
+        DevVec<unsigned char> rep;                // [P] reported row
+        DevVec<double> yb, out, uy, nb, qpart, quad, msave, vsave;      // 16 x P in / out blocks; U_y / s / q; node buffers; Q
+        size_t work_bytes = 0;
+    } slv;
     // comm
     void* rccl = nullptr;
     ncclComm_t comm = nullptr;
@@ -458,3 +496,9 @@ static inline void launch_cascade_any(mra_plan* pl, const CascadeArgs& ar) { if 
 static inline void launch_knot_chain(mra_plan* pl, const KnotChainArgs& ka) { if (pl->d == 1) launch_knot_chain_d1(pl, ka); else launch_knot_chain_d2(pl, ka); }
 void launch_predict_any(mra_plan* pl, const PredArgs& ar, size_t lds);
 void launch_predict_hi(mra_plan* pl, const PredHiArgs& hi, const PredArgs& low, size_t lds_low, bool upd);
+// mra_launch_solve.hip: descriptors + work buffers of mra_solve; one block of <= 16 columns (slv.yb -> slv.out, slv.quad; launches
+// only, on pl->stream); the 16-column glue of the sampler's MRA_OPT_SAMPLE_SOLVE path
+void mra_solver_build(mra_plan* pl);
+void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad);
+void mra_solver_pseudo(mra_plan* pl, const double* y, const double* x, const SampleZ& zs, long slot0);
+void mra_solver_addmean(mra_plan* pl, double* x, int ns);

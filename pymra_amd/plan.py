@@ -36,6 +36,7 @@ MRA_OPT_HI_FOLD = 16
 MRA_OPT_LIK_ROWS = 17
 MRA_OPT_CASCADE_GROUP = 18
 MRA_OPT_SAMPLE_GRAM_BYTES = 19
+MRA_OPT_SAMPLE_SOLVE = 20
 MRA_SAMPLE_CONDITIONAL = 1
 MRA_BLOCK_W_ROWS, MRA_BLOCK_LPRIOR, MRA_BLOCK_FRONT, MRA_BLOCK_LEAF = 0, 1, 2, 3
 
@@ -46,7 +47,7 @@ ERR_NAMES = {-1: "MRA_ERR_INVALID", -2: "MRA_ERR_HIP", -3: "MRA_ERR_NOT_SPD", -4
 EXPORTS = [
     "mra_device_count", "mra_release_cached_memory", "mra_plan_create", "mra_plan_destroy", "mra_plan_set_locs", "mra_plan_set_obs",
     "mra_plan_set_kernel", "mra_plan_set_locs_rows", "mra_plan_set_obs_rows", "mra_get_predict_rows", "mra_get_predict_rows_sd", "mra_eval_kernel", "mra_plan_set_cov_block", "mra_run", "mra_get_likelihood", "mra_get_predict",
-    "mra_sample_slots", "mra_sample", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
+    "mra_sample_slots", "mra_sample", "mra_solve", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
     "mra_get_kernel_stats", "mra_get_kernel_work", "mra_device_synchronize", "mra_plan_info", "mra_comm_unique_id", "mra_comm_init",
     "mra_plan_set_reduce_level", "mra_reduce_size", "mra_reduce_export", "mra_reduce_import",
     "mra_run_resume", "mra_last_error", "mra_version",
@@ -108,6 +109,7 @@ def load_library():
         "mra_get_predict": (C.c_int, [vp, vp, vp]),
         "mra_sample_slots": (C.c_int, [vp, C.POINTER(i64)]),
         "mra_sample": (C.c_int, [vp, u32, i64, C.c_uint64, i64, vp, vp]),
+        "mra_solve": (C.c_int, [vp, u32, i64, vp, vp, vp]),
         "mra_get_buffer": (C.c_int, [vp, C.c_int, vp, i64, C.POINTER(i64)]),
         "mra_get_node_block": (C.c_int, [vp, i32, C.c_int, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
         "mra_get_timers": (C.c_int, [vp, vp, C.c_int]),
@@ -330,6 +332,20 @@ class HipPlan:
         flags = MRA_SAMPLE_CONDITIONAL if conditional else 0
         self._check(self.lib.mra_sample(self._h, flags, n, int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample0), zp, _ptr(out)))
         return out
+
+    def solve(self, Y, want_mean=True, want_quad=True):
+        """Factor once, solve many (include/mra_hip.h, mra_solve).  Y: (c, P) observation vectors in padded leaf order, read at the
+        plan's observed rows only.  -> (mean (c, P) or None, quad (c, c) or None): mean[k] is the predictive mean for y = Y[k]
+        (unreported rows 0), quad = Y_o^T (Sigma_MRA[o, o] + R I)^-1 Y_o, BLOCK-DIAGONAL in blocks of 16 columns (NaN elsewhere).
+        The factorisation is kept between calls; y, the options and likelihood() / predict() are unchanged afterwards."""
+        Y = np.ascontiguousarray(Y, dtype=np.float64)
+        if Y.ndim != 2 or Y.shape[1] != self.topo.P:
+            raise ValueError("Y must have shape (c, P) = (c, %d)" % self.topo.P)
+        c = Y.shape[0]
+        mean = np.empty((c, self.topo.P)) if want_mean else None
+        quad = np.empty((c, c)) if want_quad else None
+        self._check(self.lib.mra_solve(self._h, 0, c, _ptr(Y), None if mean is None else _ptr(mean), None if quad is None else _ptr(quad)))
+        return mean, quad
 
     def buffer(self, what):
         n = C.c_int64()

@@ -2,7 +2,11 @@
 predict pass each), against one likelihood + predict pass of the same plan.  Each timing is taken after a warm-up call of the same
 shape (the first call builds the sampler's index maps and allocates its buffers).  Prints one JSON line per configuration.
 
-    python tools/sample_timing.py [c3] [c5]"""
+    python tools/sample_timing.py [c3] [c5]
+
+With --solve, after those lines: 16 conditional draws with MRA_OPT_SAMPLE_SOLVE off and then on (same plan, same process, in that
+order), and mra_solve for 16 columns with the factors already valid (mean + quad, upload and 16 x P download included), each as the
+median of three repeats; one more JSON line per configuration (profiles/solve_timing.txt)."""
 import json
 import os
 import sys
@@ -50,7 +54,7 @@ def timed(fn):
     return 1e3 * (time.perf_counter() - t0), out
 
 
-def main(cfgs):
+def main(cfgs, solve=False):
     for cfg in cfgs:
         pl, topo = make(cfg)
         pl.run(True, True)
@@ -63,8 +67,25 @@ def main(cfgs):
                           "lik_predict_pass_ms": round(pass_ms, 2), "prior_16_draws_ms": round(prior_ms, 2),
                           "conditional_16_draws_ms": round(cond_ms, 2), "finite": bool(np.isfinite(x).all() and np.isfinite(xc).all())}),
               flush=True)
+        if solve:
+            med = lambda fn: float(np.median([timed(fn)[0] for _ in range(3)]))          # noqa: E731
+            off_ms = med(lambda: pl.sample(16, seed=4, conditional=True))
+            pl.set_option(P.MRA_OPT_SAMPLE_SOLVE, 1)
+            xs = pl.sample(16, seed=4, conditional=True)                                  # warm-up: the solver's buffers
+            on_ms = med(lambda: pl.sample(16, seed=4, conditional=True))
+            pl.set_option(P.MRA_OPT_SAMPLE_SOLVE, 0)
+            Y = np.random.default_rng(5).standard_normal((16, topo.P))
+            first_ms, _ = timed(lambda: pl.solve(Y))                                       # factorises: one likelihood pass inside
+            solve_ms = med(lambda: pl.solve(Y))
+            quad_ms = med(lambda: pl.solve(Y, want_mean=False))
+            print(json.dumps({"config": cfg, "conditional_16_draws_option_off_ms": round(off_ms, 2),
+                              "conditional_16_draws_option_on_ms": round(on_ms, 2),
+                              "max_abs_on_minus_off": float(np.abs(xs - xc).max()),
+                              "solve_16_columns_first_call_ms": round(first_ms, 2), "solve_16_columns_factors_valid_ms": round(solve_ms, 2),
+                              "solve_16_columns_quad_only_ms": round(quad_ms, 2)}), flush=True)
         pl.close()
 
 
 if __name__ == "__main__":
-    main(sys.argv[1:] or ["c3", "c5"])
+    args = [a for a in sys.argv[1:] if a != "--solve"]
+    main(args or ["c3", "c5"], solve="--solve" in sys.argv[1:])
