@@ -323,7 +323,8 @@ int mra_plan_set_reduce_level(mra_plan *plan, int level);
 
 /* Front exchange without RCCL (tests on one GPU, or another transport): mra_run stops before the
  * reduce level's factorisation when MRA_RUN_SPLIT is set in flags; export/import the summed
- * fronts, then call mra_run_resume. */
+ * fronts, then call mra_run_resume.  The resumed half runs the route (which kernels, in which
+ * order) fixed by that mra_run: an option set in between takes effect with the next mra_run. */
 #define MRA_RUN_SPLIT          4u
 int mra_reduce_size(mra_plan *plan, int64_t *n_doubles);
 int mra_reduce_export(mra_plan *plan, double *out);

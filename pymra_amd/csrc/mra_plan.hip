@@ -997,7 +997,7 @@ static void build_leaf(mra_plan* pl, const double* y) {
         pl->gLeafCholSorted.upload(ps);
     }
     for (int v = 0; v < 2; ++v) { pl->gBigPanel[v].clear(); pl->gBigTrail[v].clear(); pl->bigM[v].clear(); pl->bigN[v].clear(); }
-    if (pl->leaf_max_nop / 16 > 12) {
+    if (pl->leaf_max_nop / 16 > LEAF_MAX_TILES) {
         const int NBT = 4;                                        // column tiles per step
         const int nsteps = (pl->leaf_max_nop / 16 + NBT - 1) / NBT;
         for (int v = 0; v < 2; ++v) {
@@ -1174,9 +1174,6 @@ static void launch_gemm(mra_plan* pl, const GemmProb* probs, size_t nprob, long 
 }
 template <int EPI>
 static void launch_leaf_gemm(mra_plan* pl, const GemmProb* probs, size_t nprob) { mra_launch_leaf_gemm(pl, EPI, probs, nprob); }
-// the leaf-resident kernel pays off for leaves with many rows and a K loop of at least a few chunks; small leaves (config 5:
-// 64 rows, 32 observations) keep the 64x64-tile kernel
-static bool leaf_gemm_ok(const mra_plan* pl) { return pl->use_leaf_gemm && pl->leaf_max_rows >= 128 && pl->leaf_max_nop >= 64; }
 
 static void launch_panel(mra_plan* pl, const PanelProb* probs, size_t nprob, int accumulate = 0) {
     if (!nprob) return;
@@ -1186,8 +1183,8 @@ static void launch_panel(mra_plan* pl, const PanelProb* probs, size_t nprob, int
 // row-tile triangular solve with L in LDS; returns false when nt is too large for the LDS path
 static bool launch_trsm2(mra_plan* pl, const Trsm2Prob* probs, size_t nprob, int nt, long max_tiles, int tiles_per_wg) {
     if (!pl->prepare_only && (!nprob || max_tiles <= 0 || nt <= 0)) return true;
-    if (nt > 12) return false;
-    ensure_big_lds(pl, {(const void*)k_trsm_rows2<2>, (const void*)k_trsm_rows2<4>, (const void*)k_trsm_rows2<8>, (const void*)k_trsm_rows2<12>});
+    if (nt > TRSM2_MAX_NT) return false;
+    ensure_big_lds(pl, {(const void*)k_trsm_rows2<2>, (const void*)k_trsm_rows2<4>, (const void*)k_trsm_rows2<8>, (const void*)k_trsm_rows2<TRSM2_MAX_NT>});
     if (pl->prepare_only) return true;
     const size_t lds = (size_t)(nt * (nt - 1) / 2 + nt) * 2048 + (size_t)nt * 16 * sizeof(int);      // L image + the Ut gather list
     const unsigned gx = (unsigned)((max_tiles + tiles_per_wg - 1) / tiles_per_wg);
@@ -1208,7 +1205,7 @@ static bool launch_trsm2(mra_plan* pl, const Trsm2Prob* probs, size_t nprob, int
         if (nt <= 2) hipLaunchKernelGGL((k_trsm_rows2<2>), grid, dim3(tb), lds, pl->stream, probs + off, tiles_per_wg MRA_TSTAMP_VAL);
         else if (nt <= 4) hipLaunchKernelGGL((k_trsm_rows2<4>), grid, dim3(tb), lds, pl->stream, probs + off, tiles_per_wg MRA_TSTAMP_VAL);
         else if (nt <= 8) hipLaunchKernelGGL((k_trsm_rows2<8>), grid, dim3(tb), lds, pl->stream, probs + off, tiles_per_wg MRA_TSTAMP_VAL);
-        else hipLaunchKernelGGL((k_trsm_rows2<12>), grid, dim3(tb), lds, pl->stream, probs + off, tiles_per_wg MRA_TSTAMP_VAL);
+        else hipLaunchKernelGGL((k_trsm_rows2<TRSM2_MAX_NT>), grid, dim3(tb), lds, pl->stream, probs + off, tiles_per_wg MRA_TSTAMP_VAL);
     }
     return true;
 }
@@ -1309,7 +1306,86 @@ static bool ensure_lik_general(mra_plan* pl) {
     return true;
 }
 
+// ---- the route of a pass (PassRoute, mra_plan_types.h) ---------------------------------------------------------------------------
+static PassPath path_of(const mra_plan* pl) {
+    if (pl->regular && pl->use_fused && !pl->host_cov) return PassPath::Fused;
+    return (pl->regular_hi && pl->use_fused && !pl->host_cov) ? PassPath::Hi : PassPath::Levels;     // (sharded plans too: the walk is per row tile)
+}
+
+// Pure: reads the plan, decides, touches nothing.  full_rows: the caller reads W at every row afterwards (mra_sample, mra_solve).
+static PassRoute route_for(const mra_plan* pl, uint32_t flags, bool full_rows) {
+    PassRoute r;
+    const size_t nl = pl->leaf_nodes.size(), two_per_cu = (size_t)(2 * pl->n_cu);
+    const int ntl = pl->leaf_max_nop / 16;
+    const bool fit = ntl <= LEAF_MAX_TILES, obs = pl->leaf_max_nop > 0;      // every leaf's observation block fits k_chol_wave / the LDS row solve
+    r.path = path_of(pl); r.predict = flags & MRA_RUN_PREDICT;
+    const bool fused = r.path == PassPath::Fused, pred = r.predict;
+    // ---- prior.  Level-by-level: when every level's row solve takes the LDS path and the leaves' solve subtracts |Tt|^2, the variance is
+    // accumulated on the way instead of by a pass over all of W at the end
+    r.init_yblock = !fused; r.acc_var = !fused && fit;              // (the fused prior cascade writes the y block itself)
+    for (int m = 0; m < pl->n_levels; ++m) if (!pl->lev[m].nodes.empty() && pl->lev[m].cwt > TRSM2_MAX_NT) r.acc_var = false;
+    r.n_chain = (pl->use_knot_chain && pl->knot_chain_ok && pl->kc_levels >= 2) ? pl->kc_levels : 0;
+    r.prior_level = pl->use_prior_level && !pl->host_cov && pl->gemm_lds;
+    // likelihood-only passes never need V[S,o]: just C = v_m(o,o) + R I from a small gathered product (the row solve gathers Ut itself, or
+    // the row cascade has scattered it), and W at the rows they need only.  Fused: the row cascade walks gathered tiles of OBSERVED rows
+    // (the knots had their own pass; 7 of a leaf's 16 tiles at C3).  Level-by-level: the one-launch prior levels walk the observed rows
+    // and the knots when every level takes that path (ensure_lik_general's verdict; one not yet known counts as yes: run_all then has
+    // the list built and asks again).
+    r.c_only = !pred && !pl->host_cov && pl->gemm_lds && fit && obs;
+    const bool rows = r.c_only && !full_rows && pl->use_lik_rows;
+    r.lik_rows = fused && rows && pl->cascade_stage_all && !pl->obs_off_host.empty() && pl->obs_off_host.back() > 0;
+    r.lik_general = !fused && rows && pl->use_prior_level && (pl->lik_general_ok || !pl->lik_general_valid);
+    r.scatter_ut = fit && obs && !pl->ut_gather;
+    // ---- leaves.  The leaf-resident kernel pays off for leaves with many rows and a K loop of at least a few chunks; small leaves
+    // (config 5: 64 rows, 32 observations) keep the 64x64-tile kernel
+    r.leaf_resident = pl->use_leaf_gemm && pl->leaf_max_rows >= 128 && pl->leaf_max_nop >= 64;
+    r.c_fix = !obs ? LeafCFix::None : r.c_only ? LeafCFix::InProduct : fit ? LeafCFix::Phantom : LeafCFix::Fill;
+    // (round 4, with the blocked factorisation atom: one workgroup per matrix is at least as fast as one wave per matrix at
+    //  every shard size - 5.507 / 3.00 / 1.601 / 0.922 ms against 5.528 / 3.00 / 1.621 / 0.959 for 1 / 2 / 4 / 8-way C3 -
+    //  so option 11 = 1 (the default) takes it for matrices of five tiles and more at any count; small matrices - config 5:
+    //  65536 of at most three tiles - stay on one wave each unless a CU sees at most two of them; 0 forces k_chol_wave)
+    if (!fit) r.chol = LeafChol::BigPanels;
+    else if (ntl <= 10 && (pl->use_chol_lds == 2 || (pl->use_chol_lds == 1 && (ntl >= 5 || nl <= two_per_cu))))
+        r.chol = (pl->n_chol_small == nl || nl > two_per_cu) ? LeafChol::TilesSplit : LeafChol::TilesOne;
+    else r.chol = LeafChol::Wave;
+    // with the fused row solve + update the small leaves only need their Ut rows solved by the row solve
+    // (one 8-wave workgroup per CU: a gain when a CU sees at most two leaves - 1.21 -> 1.13 ms on an eighth of C3 -
+    // and a loss from four per CU on - 1.87 -> 1.90 ms on a quarter - where the update rides in the predictive
+    // cascade at three workgroups per CU)
+    r.solve_fused = fused && pred && nl && fit && pl->use_leaf_solve && pl->leaf_solve_ok && (pl->leaf_solve_mode == 1 || pl->n_trsm_small <= two_per_cu);
+    if (fused) {
+        const Trsm2Prob* likp = pl->ut_gather ? pl->gLeafTrsmLikPlainG.p : pl->gLeafTrsmLikPlain.p;
+        r.trsm_all = pred ? (pl->ut_gather ? pl->gLeafTrsmFullPlainG.p : pl->gLeafTrsmFullPlain.p) : likp;
+        r.trsm_small = r.solve_fused ? likp : r.trsm_all;
+    } else r.trsm_all = pred ? pl->gLeafTrsmFull.p : pl->gLeafTrsmLik.p;
+    // ---- fronts
+    r.direct_parent = pl->parent_syrk && pl->reduce_level != pl->NL - 1;
+    r.front_fused = pl->use_front_fused;
+    r.parent_front = r.direct_parent && pl->use_front_fused && pl->parent_front_nacc > 0;
+    r.syrk_blk = pl->use_syrk_blk && pl->grand_syrk_blk_ok; r.syrk_dma = pl->use_syrk_blk == 1 && pl->grand_syrk_dma_ok;
+    r.extract_mean = pred && r.path == PassPath::Levels;
+    if (!pred || !nl) return r;
+    // ---- what only feeds the predictive pass.  In a sharded run it goes to the side stream, so that the front chain and the all-reduce
+    // do not queue behind it (on one GPU it buys nothing); with per-kernel timing on it stays on the main stream so
+    // that the hipEvent brackets measure one kernel at a time.
+    r.side = !pl->ktiming && pl->reduce_level >= 0;
+    r.var = r.acc_var ? LeafVar::FinishVar : (!fused || !fit) ? LeafVar::Moments : LeafVar::None;
+    // deep 64-wide trees: the update rides in k_predict_hi (leaves of at most four observation tiles, 16 x 16-padded ancestors + y)
+    // (a sharded rank keeps the separate product: it runs on the side stream beside the front chain and the all-reduce, whereas
+    // k_predict_hi sits behind them on the rank's critical path; option 16 = 2 folds there too, for A/B runs)
+    if (r.path == PassPath::Hi && pl->use_hi_fold && (pl->reduce_level < 0 || pl->use_hi_fold == 2) && pl->leaf_max_nop <= 64 &&
+        pl->na[pl->NL] == (pl->NL * 4 + 1) * 16) r.update = LeafUpdate::InPredictHi;
+    else if (!r.solve_fused && fused && pl->use_pred_update && pl->leaf_solve_ok && fit && pl->na[pl->NL] == (pl->NL * pl->CWT + 1) * 16)
+        r.update = LeafUpdate::InCascade;
+    else if (r.solve_fused) r.update = (pl->leaf_solve_split == 2 && pl->n_leaf_solve_half) ? LeafUpdate::SolveHalves : LeafUpdate::SolveWhole;
+    // (measured: the leaf-resident form wins for the residual - 1.07 vs 1.15 ms at C3 - but not for the update,
+    // 1.34-1.39 vs 1.29 ms, whatever the pass structure; MRA_OPT_LEAF_GEMM = 2 selects it for A/B runs)
+    else r.update = (r.leaf_resident && pl->leaf_gemm_update) ? LeafUpdate::LeafGemm : LeafUpdate::Gemm;
+    return r;
+}
+
 static void run_prior_fused(mra_plan* pl) {
+    const PassRoute& r = pl->route;
     const int cw = pl->cw[0];
     CascadeArgs base{};
     base.ycol = -1;
@@ -1319,7 +1395,7 @@ static void run_prior_fused(mra_plan* pl) {
         base.coff[m] = pl->coff[m];
     }
     base.X = pl->X.p; base.W = pl->W.p; base.ldw = pl->ldw;
-    const int n_chain = (pl->use_knot_chain && pl->knot_chain_ok && pl->kc_levels >= 2) ? pl->kc_levels : 0;
+    const int n_chain = r.n_chain;
     if (n_chain) {
         Work fl;
         for (int m = 0; m < n_chain; ++m) fl += pl->lev[m].fl_pchol;
@@ -1357,11 +1433,8 @@ static void run_prior_fused(mra_plan* pl) {
         for (int m = 0; m < pl->NL; ++m) fl += pl->lev[m].fl_resid + pl->lev[m].fl_trsm;
         // one pass: coordinates and y in, W (all levels + y block) and the prior variance out, observed rows once more into Ut
         fl.bytes = 8.0 * pl->P * (pl->d + 1 + pl->ldw + 1) + pl->by_leaf_ut;
-        // a likelihood needs W at the OBSERVED rows only (Ut and the leaves' C = v(o,o) + R I are built from them; the knots had their
-        // own pass): the cascade then walks gathered tiles of observed rows - 7 of a leaf's 16 tiles at C3
-        const bool lik_rows = !(pl->run_flags & MRA_RUN_PREDICT) && pl->use_lik_rows && pl->cascade_stage_all && pl->gemm_lds &&
-                              pl->leaf_max_nop / 16 <= 12 && pl->leaf_max_nop > 0 && !pl->obs_off_host.empty() && pl->obs_off_host.back() > 0;
-        if (lik_rows) {
+        // a likelihood needs W at the OBSERVED rows only (Ut and the leaves' C = v(o,o) + R I are built from them)
+        if (r.lik_rows) {
             ensure_lik_tiles(pl);
             const double share = 16.0 * (double)pl->n_lik_tiles / (double)std::max<long>(pl->P, 1);
             fl.alg *= share; fl.exec *= share; fl.bytes = share * 8.0 * pl->P * (pl->d + 1 + pl->ldw) + pl->by_leaf_ut;
@@ -1375,7 +1448,7 @@ static void run_prior_fused(mra_plan* pl) {
 #endif
         ar.var_out = pl->var.p; ar.cov0 = kernel_cov0(pl);
         ar.ycol = pl->Ka; ar.y = pl->y.p;
-        if (pl->leaf_max_nop / 16 <= 12 && pl->leaf_max_nop > 0 && !pl->ut_gather) {
+        if (r.scatter_ut) {
             ar.obs_pos = pl->obs_pos.p; ar.tile_leaf = pl->ft_leaf.p; ar.leaf_ut = pl->leaf_ut.p; ar.leaf_nop = pl->leaf_nop_dev.p;
             ar.y = pl->y.p;
             // Ut rows follow W's ancestor columns of a last-level leaf: a = column - asuf[NL]
@@ -1385,7 +1458,7 @@ static void run_prior_fused(mra_plan* pl) {
         if (pl->cascade_stage_all) { ar.n_wg = pl->n_fwg_leaf; ar.wg_tile0 = pl->ft_wg0_leaf.p; ar.wg_ntiles = pl->ft_wgn_leaf.p; }
         else { ar.n_wg = pl->n_fwg; ar.wg_tile0 = pl->ft_wg0.p; ar.wg_ntiles = pl->ft_wgn.p; }
         ar.tile_row0 = pl->ft_row0.p; ar.tile_chain = pl->ft_chain.p;
-        if (lik_rows) {
+        if (r.lik_rows) {
             ar.row_gather = pl->obs_idx.p; ar.tile_chain = pl->lik_chain.p; ar.tile_leaf = pl->lik_leaf.p;
             ar.n_wg = pl->n_lik_wg; ar.wg_tile0 = pl->lik_wg0.p; ar.wg_ntiles = pl->lik_wgn.p;
             ar.var_out = nullptr;                          // the prior variance is the predictive pass's (the y block stays: Ut's y row is gathered from it)
@@ -1411,7 +1484,8 @@ static void run_predict_hi(mra_plan* pl) {
     hi.tile_row0 = pl->ft_row0.p; hi.tile_chain = pl->ft_chain.p; hi.wg_tile0 = pl->ft_wg0.p; hi.wg_ntiles = pl->ft_wgn.p;
     // W read once, its coarse columns and y block written once; var in and out
     fl_hi.bytes = 8.0 * pl->P * (pl->ldw + (pl->ldw - pl->coff[nlo - 1]) + 2);
-    if (pl->hi_fold_now) {
+    const bool fold = pl->route.update == LeafUpdate::InPredictHi;
+    if (fold) {
         // the leaf update rides in k_predict_hi (Tt and Ut in, nothing out)
         hi.wg_leaf = pl->hi_wgleaf.p; hi.leaf_ut = pl->leaf_ut.p; hi.leaf_nop = pl->leaf_nop_dev.p; hi.leaf_row0 = pl->leaf_row0_dev.p; hi.na = pl->na[NL];
         fl_hi += Work(pl->fl_leaf_update.alg, pl->fl_leaf_update.exec, pl->by_leaf_tt + pl->by_leaf_ut);
@@ -1431,7 +1505,7 @@ static void run_predict_hi(mra_plan* pl) {
     const size_t lds_low = (size_t)(4 * 3 / 2 + 4 + ((nlo - 1) * 4 + 1) * 4) * 2048;
     // two launches; the kernel timer brackets both (the coarse share is reported with them: they are one pass over W's coarse half)
     KTimer kt(pl, KF_PRED_UPDATE, fl_hi + fl_lo);
-    launch_predict_hi(pl, hi, lo, lds_low, pl->hi_fold_now);
+    launch_predict_hi(pl, hi, lo, lds_low, fold);
 }
 
 static void run_predict_fused(mra_plan* pl) {
@@ -1450,7 +1524,7 @@ static void run_predict_fused(mra_plan* pl) {
     Work fl;
     for (int m = 0; m < pl->NL; ++m) fl += pl->lev[m].fl_trsm + pl->lev[m].fl_update;
     fl.bytes = 8.0 * pl->P * (pl->ldw + 3);                // W once in, var in/out, mean out (the level operands stay in L2)
-    if (pl->pred_update_now) {
+    if (pl->route.update == LeafUpdate::InCascade) {
         // the leaf update rides in this launch (two Ut chunk stages share the LDS with the level operands)
         ar.tile_leaf = pl->ft_leaf.p; ar.wg_leaf = pl->ft_wgleaf_x.p; ar.leaf_ut = pl->leaf_ut.p; ar.leaf_nop = pl->leaf_nop_dev.p; ar.leaf_row0 = pl->leaf_row0_dev.p;
         ar.leaf_upd = pl->leaf_upd_dev.p; ar.na = pl->na[pl->NL];
@@ -1477,7 +1551,7 @@ static bool run_front_fused(mra_plan* pl, int m, bool do_assemble, bool add_iden
     LevelData& lv = pl->lev[m];
     const size_t nn = lv.nodes.size();
     if (!nn) return true;
-    if (!pl->use_front_fused || lv.front_mode == 0 || (do_assemble && lv.front_mode != 2)) return false;
+    if (!pl->route.front_fused || lv.front_mode == 0 || (do_assemble && lv.front_mode != 2)) return false;
     ensure_big_lds(pl, {(const void*)k_front<true>, (const void*)k_front<false>});
     KTimer kt(pl, KF_FRONT_CHOL, lv.fl_fchol + lv.fl_schur);
     if (lv.front_mode == 2)
@@ -1520,6 +1594,7 @@ static void run_add_identity(mra_plan* pl, int m) {
 static void finish_run(mra_plan* pl);
 
 static void run_fronts_and_predict(mra_plan* pl, int m_from, bool resume) {
+    const PassRoute& r = pl->route;
     pl->slv.valid = false;
     for (int m = m_from; m >= 0; --m) {
         const bool is_red = (m == pl->reduce_level);
@@ -1527,9 +1602,9 @@ static void run_fronts_and_predict(mra_plan* pl, int m_from, bool resume) {
         bool need_identity = false;          // front sits in global memory without its identity block
         bool assembled = true;
         if (!(resume && m == m_from)) {
-            if (pl->direct_parent && m == pl->NL - 1) {
+            if (r.direct_parent && m == pl->NL - 1) {
                 const LevelData& lvp = pl->lev[m];
-                if (pl->use_front_fused && pl->parent_front_nacc > 0) {
+                if (r.parent_front) {
                     // children's Ut -> front -> Lt, Zt, Schur block, all in one launch (the front never visits HBM unfactorised)
                     ensure_big_lds(pl, {(const void*)k_parent_front<2>, (const void*)k_parent_front<4>, (const void*)k_parent_front<8>, (const void*)k_parent_front<12>});
                     KTimer kt(pl, KF_LEAF_SYRK, (pl->fl_leaf_syrk + lvp.fl_fchol + lvp.fl_schur).with_bytes(pl->by_leaf_ut + 8.0 * lvp.nodes.size() * (0.5 * lvp.nf * (lvp.nf + 1))));
@@ -1562,11 +1637,11 @@ static void run_fronts_and_predict(mra_plan* pl, int m_from, bool resume) {
                 }
                 KTimer kt(pl, KF_LEAF_SYRK, pl->fl_leaf_syrk);
                 launch_gemm<EPI_SET>(pl, pl->gParentSyrk.p, lvp.nodes.size(), lvp.nf, lvp.nf, false, true);
-            } else if (pl->direct_parent && m == pl->NL - 2 && pl->lev[pl->NL - 1].panel_only) {
+            } else if (r.direct_parent && m == pl->NL - 2 && pl->lev[pl->NL - 1].panel_only) {
                 if (is_red) throw MraError(MRA_ERR_STATE, "the reduce level cannot be the level above panel-only fronts");
                 const LevelData& lg = pl->lev[m];
                 KTimer kt(pl, KF_FRONT_SCHUR, pl->fl_grand_syrk);
-                if (pl->use_syrk_blk && pl->grand_syrk_blk_ok) mra_launch_syrk_blk(pl, pl->gGrandSyrk.p, lg.nodes.size(), lg.nf, pl->use_syrk_blk == 1 && pl->grand_syrk_dma_ok);
+                if (r.syrk_blk) mra_launch_syrk_blk(pl, pl->gGrandSyrk.p, lg.nodes.size(), lg.nf, r.syrk_dma);
                 else launch_gemm<EPI_SET>(pl, pl->gGrandSyrk.p, lg.nodes.size(), lg.nf, lg.nf, false, true);      // (64 x 64 LDS-tiled: 24.2 vs 23.7 ms at config 5)
             } else if (is_red) {
                 // (the rank-local log-det sum of everything below rides in the same launch, see the reduce block)
@@ -1611,11 +1686,9 @@ static void run_fronts_and_predict(mra_plan* pl, int m_from, bool resume) {
         HIP_TRY(hipStreamWaitEvent(pl->stream, pl->ev_join, 0));
         pl->side_pending = false;
     }
-    const bool fusedp = pl->regular && pl->use_fused && !pl->host_cov;
-    const bool hip_ = !fusedp && pl->regular_hi && pl->use_fused && !pl->host_cov;      // sharded plans too: the walk is per row tile, the fronts above the reduce level are complete by now
-    if ((pl->run_flags & MRA_RUN_PREDICT) && fusedp) run_predict_fused(pl);
-    if ((pl->run_flags & MRA_RUN_PREDICT) && hip_) run_predict_hi(pl);
-    if ((pl->run_flags & MRA_RUN_PREDICT) && !fusedp && !hip_) {
+    if (r.predict && r.path == PassPath::Fused) run_predict_fused(pl);
+    if (r.predict && r.path == PassPath::Hi) run_predict_hi(pl);         // (sharded plans too: the fronts above the reduce level are complete by now)
+    if (r.predict && r.path == PassPath::Levels) {
         for (int m = pl->n_levels - 1; m >= 0; --m) {
             LevelData& lv = pl->lev[m];
             const size_t nn = lv.nodes.size();
@@ -1658,8 +1731,7 @@ static void finish_run(mra_plan* pl) {
             HIP_TRY(hipHostGetDevicePointer((void**)&pl->host_res_dev, pl->host_res, 0));
         }
         hipLaunchKernelGGL(k_sum_dnode, dim3(1), dim3(256), 0, pl->stream, pl->dnode.p, nsum, pl->host_res_dev, up, below, pl->errflag.p);
-        const bool hi_path = !(pl->regular && pl->use_fused && !pl->host_cov) && pl->regular_hi && pl->use_fused && !pl->host_cov;
-        if ((pl->run_flags & MRA_RUN_PREDICT) && !(pl->regular && pl->use_fused && !pl->host_cov) && !hi_path)
+        if (pl->route.extract_mean)
             hipLaunchKernelGGL(k_extract_mean, dim3((unsigned)((pl->P + 255) / 256)), dim3(256), 0, pl->stream,
                                pl->W.p, (long)pl->ldw, pl->Ka, pl->mean.p, pl->P);
     }
@@ -1706,7 +1778,8 @@ static void ensure_gt(mra_plan* pl) {
     pl->gLeafSyrk.upload(pl->hLeafSyrk);
 }
 
-static void run_all(mra_plan* pl, uint32_t flags) {
+// full_rows: the caller reads W at every row afterwards (sampler_prior); a likelihood-only pass then walks all rows
+static void run_all(mra_plan* pl, uint32_t flags, bool full_rows = false) {
     if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
     if (!(pl->have_locs && pl->have_obs && pl->have_kernel))
         throw MraError(MRA_ERR_STATE, "mra_run needs set_locs, set_obs and set_kernel first");
@@ -1725,43 +1798,33 @@ static void run_all(mra_plan* pl, uint32_t flags) {
     }
     pl->side_pending = false;
     pl->split_pending = false;
-    pl->pred_update_now = false;
-    pl->hi_fold_now = false;
     pl->pass_open = true;
     pl->run_flags = flags;
     pl->slv.valid = false;               // whatever runs a pass rewrites the factors (mra_solve sets the mark again after its own)
     for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = mra_plan::KStat();
-    const bool pred = flags & MRA_RUN_PREDICT;
+    if (!pl->lik_general_valid && route_for(pl, flags, full_rows).lik_general) ensure_lik_general(pl);      // (once; route_for reads the verdict)
+    const PassRoute& r = pl->route = route_for(pl, flags, full_rows);
+    const bool pred = r.predict, fused = r.path == PassPath::Fused;
     phase_mark(pl, 0);
-    if (!(pl->regular && pl->use_fused && !pl->host_cov)) {        // the fused prior cascade writes the y block itself
+    if (r.init_yblock) {
         KTimer kt(pl, KF_MISC, 0);
         const long n = pl->P * MRA_YB;
-        // every level's row solve takes the LDS path (block width <= 192) and the leaves' solve subtracts |Tt|^2: the variance is
-        // accumulated on the way instead of by a pass over all of W at the end
-        bool acc_var = pl->leaf_max_nop / 16 <= 12;
-        for (int m = 0; m < pl->n_levels; ++m) if (!pl->lev[m].nodes.empty() && pl->lev[m].cwt > 12) acc_var = false;
-        pl->var_accumulated = acc_var;
         hipLaunchKernelGGL(k_init_yblock, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, pl->stream, pl->W.p,
-                           (long)pl->ldw, pl->Ka, pl->y.p, pl->P, acc_var ? pl->var.p : (double*)nullptr, pl->host_cov ? 0.0 : kernel_cov0(pl),
+                           (long)pl->ldw, pl->Ka, pl->y.p, pl->P, r.acc_var ? pl->var.p : (double*)nullptr, pl->host_cov ? 0.0 : kernel_cov0(pl),
                            pl->host_cov ? pl->covdiag.p : (const double*)nullptr);
     }
     // ---- 1. prior, top-down
-    const bool fused = pl->regular && pl->use_fused && !pl->host_cov;
     if (fused) run_prior_fused(pl);
-    // likelihood-only: the one-launch prior levels walk the rows a likelihood needs (observed rows and knots) when every level takes
-    // that path and the leaf stage builds C from the gathered product (c_only below)
-    const bool lik_general = !fused && !pred && pl->use_lik_rows && pl->use_prior_level && !pl->host_cov && pl->gemm_lds &&
-                             pl->leaf_max_nop / 16 <= 12 && pl->leaf_max_nop > 0 && ensure_lik_general(pl);
     for (int m = 0; m < pl->n_levels && !fused; ++m) {
         LevelData& lv = pl->lev[m];
         const size_t nn = lv.nodes.size();
         if (!nn) continue;
-        if (pl->use_prior_level && lv.prior_level_ok && !pl->host_cov && pl->gemm_lds) {
+        if (r.prior_level && lv.prior_level_ok) {
             // knots' residual block -> Lp (both sides gathered), its Cholesky, then residual + kernel + row solve of every row in one
             // launch: the residual never visits HBM
             { KTimer kt(pl, KF_PRIOR_CHOL, lv.fl_knot_resid); launch_gemm<EPI_COV>(pl, lv.gKnotResid.p, nn, lv.cw, lv.cw); }
             { KTimer kt(pl, KF_PRIOR_CHOL, lv.fl_pchol); launch_panel(pl, lv.gPriorChol.p, nn); }
-            if (lik_general) {
+            if (r.lik_general) {
                 Work w = lv.fl_resid + lv.fl_trsm.with_bytes(0.0);
                 w.alg *= lv.lik_share; w.exec *= lv.lik_share; w.bytes *= lv.lik_share;
                 KTimer kt(pl, KF_PRIOR_RESID, w);
@@ -1797,24 +1860,20 @@ static void run_all(mra_plan* pl, uint32_t flags) {
     // ---- 2. leaves
     const size_t nl = pl->leaf_nodes.size();
     if (nl) {
-        // likelihood-only passes never need V[S,o]: just C = v_m(o,o) + R I from a small gathered product (the row solve gathers Ut itself
-        // on the level-by-level path, the row cascade has scattered it on the fused one)
-        const bool c_only = !pred && !pl->host_cov && pl->gemm_lds && pl->leaf_max_nop / 16 <= 12 && pl->leaf_max_nop > 0;
         {
-            KTimer kt(pl, KF_LEAF_RESID, c_only ? pl->fl_leaf_c_only : pl->fl_leaf_resid);
+            KTimer kt(pl, KF_LEAF_RESID, r.c_only ? pl->fl_leaf_c_only : pl->fl_leaf_resid);
             if (pl->host_cov) {
-                if (leaf_gemm_ok(pl)) launch_leaf_gemm<EPI_HOSTCOV>(pl, pl->gLeafResid.p, nl);
+                if (r.leaf_resident) launch_leaf_gemm<EPI_HOSTCOV>(pl, pl->gLeafResid.p, nl);
                 else launch_gemm<EPI_HOSTCOV>(pl, pl->gLeafResid.p, nl, pl->leaf_max_rows, pl->leaf_max_nop);
             }
-            else if (c_only) launch_gemm<EPI_COV>(pl, pl->gLeafResidLik.p, nl, pl->leaf_max_nop, pl->leaf_max_nop);
-            else if (leaf_gemm_ok(pl)) launch_leaf_gemm<EPI_COV>(pl, pl->gLeafResid.p, nl);
+            else if (r.c_only) launch_gemm<EPI_COV>(pl, pl->gLeafResidLik.p, nl, pl->leaf_max_nop, pl->leaf_max_nop);
+            else if (r.leaf_resident) launch_leaf_gemm<EPI_COV>(pl, pl->gLeafResid.p, nl);
             else launch_gemm<EPI_COV>(pl, pl->gLeafResid.p, nl, pl->leaf_max_rows, pl->leaf_max_nop);
         }
-        if (pl->leaf_max_nop > 0) {
+        if (r.c_fix != LeafCFix::None) {
             KTimer kt(pl, KF_MISC, 0);
-            if (c_only) {
-                // nothing to do: the gathered COV product wrote the whole C block including phantom identities
-            } else if (pl->leaf_max_nop / 16 <= 12) {
+            // (InProduct: nothing to do, the gathered COV product wrote the whole C block including phantom identities)
+            if (r.c_fix == LeafCFix::Phantom) {
                 // C comes from the COV epilogue, Ut from the gather inside k_trsm_rows2: only the phantom rows remain
                 // ... once: an identity row stays an identity row under the in-place factorisation (L[p][j] = 0, L[p][p] = 1 exactly) and
                 // no epilogue writes there, so later passes find them in place.  (A failed pass - NaN times 0 - a new observation pattern
@@ -1823,49 +1882,34 @@ static void run_all(mra_plan* pl, uint32_t flags) {
                     hipLaunchKernelGGL(k_leaf_cphantom, dim3((unsigned)nl), dim3(256), 0, pl->stream, pl->gLeaf.p, pl->leaf_nobs.p);
                     pl->cphantom_valid = true;
                 }
-            } else {
+            } else if (r.c_fix == LeafCFix::Fill) {
                 const long total = (long)(pl->leaf_max_nop + pl->leaf_max_na) * pl->leaf_max_nop;
                 dim3 grid((unsigned)std::min<long>((total + 255) / 256, 64), (unsigned)nl);
                 hipLaunchKernelGGL(k_leaf_fill, grid, dim3(256), 0, pl->stream, pl->gLeaf.p, pl->W.p, (long)pl->ldw, pl->R);
             }
         }
-        bool solve_fused = false;
         {
             KTimer kt(pl, KF_LEAF_CHOL, pred ? pl->fl_leaf_chol : pl->fl_leaf_chol_lik);
             const int ntl = pl->leaf_max_nop / 16;
-            if (ntl <= 12) {
-                // (round 4, with the blocked factorisation atom: one workgroup per matrix is at least as fast as one wave per matrix at
-                //  every shard size - 5.507 / 3.00 / 1.601 / 0.922 ms against 5.528 / 3.00 / 1.621 / 0.959 for 1 / 2 / 4 / 8-way C3 -
-                //  so option 11 = 1 (the default) takes it for matrices of five tiles and more at any count; small matrices - config 5:
-                //  65536 of at most three tiles - stay on one wave each unless a CU sees at most two of them; 0 forces k_chol_wave)
-                if (ntl <= 10 && (pl->use_chol_lds == 2 || (pl->use_chol_lds == 1 && (ntl >= 5 || nl <= (size_t)(2 * pl->n_cu))))) {
-                    // one workgroup per matrix, tiles in registers, next diagonal block factorised beside the trailing update
-                    const size_t ns = pl->n_chol_small;
-                    if (ns == nl || nl > (size_t)(2 * pl->n_cu)) {
-                        if (ns) hipLaunchKernelGGL((k_chol_tiles<8, 4>), dim3((unsigned)ns), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p, pl->dnode.p, pl->errflag.p);
-                        if (nl > ns) hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)(nl - ns)), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p + ns, pl->dnode.p, pl->errflag.p);
-                    }
-                    else hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)nl), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p, pl->dnode.p, pl->errflag.p);
-                } else
-                hipLaunchKernelGGL((k_chol_wave<12>), dim3((unsigned)((nl + 3) / 4)), dim3(256), 0, pl->stream, pl->gLeafCholC.p, (int)nl, pl->dnode.p, pl->errflag.p);
+            if (r.chol != LeafChol::BigPanels) {
+                // k_chol_tiles: one workgroup per matrix, tiles in registers, next diagonal block factorised beside the trailing update
+                const size_t ns = pl->n_chol_small;
+                if (r.chol == LeafChol::TilesSplit) {
+                    if (ns) hipLaunchKernelGGL((k_chol_tiles<8, 4>), dim3((unsigned)ns), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p, pl->dnode.p, pl->errflag.p);
+                    if (nl > ns) hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)(nl - ns)), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p + ns, pl->dnode.p, pl->errflag.p);
+                }
+                else if (r.chol == LeafChol::TilesOne) hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)nl), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p, pl->dnode.p, pl->errflag.p);
+                else hipLaunchKernelGGL((k_chol_wave<LEAF_MAX_TILES>), dim3((unsigned)((nl + 3) / 4)), dim3(256), 0, pl->stream, pl->gLeafCholC.p, (int)nl, pl->dnode.p, pl->errflag.p);
                 const int mt = pred ? pl->leaf_max_tiles_full : pl->leaf_max_tiles_lik;
                 if (fused) {
-                    // with the fused row solve + update the small leaves only need their Ut rows solved here
-                    // (one 8-wave workgroup per CU: a gain when a CU sees at most two leaves - 1.21 -> 1.13 ms on an eighth of C3 -
-                    // and a loss from four per CU on - 1.87 -> 1.90 ms on a quarter - where the update rides in the predictive
-                    // cascade at three workgroups per CU)
-                    solve_fused = pred && pl->use_leaf_solve && pl->leaf_solve_ok &&
-                                  (pl->leaf_solve_mode == 1 || pl->n_trsm_small <= (size_t)(2 * pl->n_cu));
-                    const Trsm2Prob* likp = pl->ut_gather ? pl->gLeafTrsmLikPlainG.p : pl->gLeafTrsmLikPlain.p;
-                    const Trsm2Prob* base = pred ? (pl->ut_gather ? pl->gLeafTrsmFullPlainG.p : pl->gLeafTrsmFullPlain.p) : likp;
-                    const size_t ns = pl->n_trsm_small;
-                    const int mts = (pred && !solve_fused) ? pl->trsm_small_tiles_full : pl->trsm_small_tiles_lik;
-                    if (ns) launch_trsm2(pl, solve_fused ? likp : base, ns, pl->trsm_small_nt, mts, mts);
+                    const size_t nts = pl->n_trsm_small;
+                    const int mts = (pred && !r.solve_fused) ? pl->trsm_small_tiles_full : pl->trsm_small_tiles_lik;
+                    if (nts) launch_trsm2(pl, r.trsm_small, nts, pl->trsm_small_nt, mts, mts);
                     // the few leaves with more than 128 observations: several workgroups per leaf when they are few
                     // (one leaf per workgroup would put a single 65 us workgroup on the critical path)
-                    if (nl > ns) launch_trsm2(pl, base + ns, nl - ns, ntl, mt, (nl - ns) < 512 ? 4 : mt);
+                    if (nl > nts) launch_trsm2(pl, r.trsm_all + nts, nl - nts, ntl, mt, (nl - nts) < 512 ? 4 : mt);
                 }
-                else launch_trsm2(pl, pred ? pl->gLeafTrsmFull.p : pl->gLeafTrsmLik.p, nl, ntl, mt, mt);
+                else launch_trsm2(pl, r.trsm_all, nl, ntl, mt, mt);
             } else {
                 // right-looking, 64 columns per step: the panel (factor + solve of ALL rows below, Ut and Tt included) on one
                 // workgroup per leaf, the rank-64 update of everything to its right as a batched GEMM over the whole GPU
@@ -1878,63 +1922,40 @@ static void run_all(mra_plan* pl, uint32_t flags) {
                 }
             }
         }
-        pl->direct_parent = pl->parent_syrk && pl->reduce_level != pl->NL - 1;
-        if (!pl->direct_parent) ensure_gt(pl);
-        if (!pl->direct_parent) { KTimer kt(pl, KF_LEAF_SYRK, pl->fl_leaf_syrk); launch_gemm<EPI_SET>(pl, pl->gLeafSyrk.p, nl, pl->leaf_max_na, pl->leaf_max_na, false, true); }
+        if (!r.direct_parent) { ensure_gt(pl); KTimer kt(pl, KF_LEAF_SYRK, pl->fl_leaf_syrk); launch_gemm<EPI_SET>(pl, pl->gLeafSyrk.p, nl, pl->leaf_max_na, pl->leaf_max_na, false, true); }
         if (pred) {
-            // fork: everything below only feeds the predictive pass.  In a sharded run it goes to the side stream, so that
-            // the front chain and the all-reduce do not queue behind it; with per-kernel timing on it stays on the main
-            // stream so that the hipEvent brackets measure one kernel at a time.
-            const bool side = !pl->ktiming && pl->reduce_level >= 0;   // sharded runs only: on one GPU it buys nothing
+            // fork: everything below only feeds the predictive pass (r.side: on the side stream)
             hipStream_t main_stream = pl->stream;
             struct StreamGuard {                                   // a throw below must not leave later launches on the side stream
                 mra_plan* p; hipStream_t s;
                 ~StreamGuard() { p->stream = s; }
             } guard{pl, main_stream};
-            if (side) {
+            if (r.side) {
                 HIP_TRY(hipEventRecord(pl->ev_fork, main_stream));
                 HIP_TRY(hipStreamWaitEvent(pl->stream2, pl->ev_fork, 0));
                 pl->stream = pl->stream2;                    // the launch helpers below use pl->stream
             }
-            if (!fused && pl->var_accumulated) {
+            if (r.var == LeafVar::FinishVar) {
                 KTimer kt(pl, KF_MISC, 0);
                 ensure_row_leaf(pl);
                 hipLaunchKernelGGL(k_leaf_finish_var, dim3((unsigned)((pl->P + 255) / 256)), dim3(256), 0, pl->stream, pl->row_leaf.p, pl->W.p,
                                    (long)pl->ldw, pl->Ka, pl->var.p, pl->P);
-            } else if (!fused || pl->leaf_max_nop / 16 > 12) {
+            } else if (r.var == LeafVar::Moments) {
                 KTimer kt(pl, KF_MISC, 0);
-                double cov0 = 0.0;
-                if (!pl->host_cov) {
-                    // stationary kernel: C(x,x) = scale * k(0)
-                    KernelParams kp = pl->kp;
-                    switch (kp.kind) {
-                        case 0: cov0 = kp.scale * 1.0; break;
-                        case 1: case 2: case 3: cov0 = kp.scale * kp.sig; break;
-                        default: cov0 = kp.scale; break;
-                    }
-                }
+                const double cov0 = pl->host_cov ? 0.0 : kernel_cov0(pl);
                 ensure_row_leaf(pl);
                 hipLaunchKernelGGL(k_leaf_moments, dim3((unsigned)((pl->P + 3) / 4)), dim3(256), 0, pl->stream, pl->gLeaf.p,
                                    pl->row_leaf.p, pl->W.p, (long)pl->ldw, pl->Ka, pl->var.p, cov0,
                                    pl->host_cov ? pl->covdiag.p : (const double*)nullptr, pl->P);
             }
-            pl->pred_update_now = !solve_fused && fused && pl->use_pred_update && pl->leaf_solve_ok && pl->leaf_max_nop / 16 <= 12 &&
-                                  pl->na[pl->NL] == (pl->NL * pl->CWT + 1) * 16;
-            // deep 64-wide trees: the update rides in k_predict_hi (leaves of at most four observation tiles, 16 x 16-padded ancestors + y)
-            // (a sharded rank keeps the separate product: it runs on the side stream beside the front chain and the all-reduce, whereas
-            // k_predict_hi sits behind them on the rank's critical path; option 16 = 2 folds there too, for A/B runs)
-            pl->hi_fold_now = !solve_fused && !fused && pl->use_hi_fold && (pl->reduce_level < 0 || pl->use_hi_fold == 2) && pl->regular_hi && pl->use_fused &&
-                              !pl->host_cov && pl->leaf_max_nop <= 64 && pl->na[pl->NL] == (pl->NL * 4 + 1) * 16;
-            if (pl->hi_fold_now) {
-                // nothing to launch here
-            } else if (pl->pred_update_now) {
+            if (r.update == LeafUpdate::InCascade) {          // (InPredictHi: nothing to launch here)
                 // the small leaves (<= 8 observation tiles) take their update inside the predictive cascade; the few larger ones here
                 const size_t ns = pl->n_trsm_small;
                 if (nl > ns) {
                     KTimer kt(pl, KF_LEAF_UPDATE, 0);
                     launch_gemm<EPI_SUB>(pl, pl->gLeafUpdatePlain.p + ns, nl - ns, pl->leaf_max_rows, pl->leaf_max_na);
                 }
-            } else if (solve_fused) {
+            } else if (r.update == LeafUpdate::SolveWhole || r.update == LeafUpdate::SolveHalves) {
                 // Tt = V Lc^-T, var -= |Tt|^2 and W -= Tt Ut^T in one launch for the leaves with <= 8 observation tiles; the few
                 // larger ones went through the full row solve above and take the plain update product
                 ensure_big_lds(pl, {(const void*)k_leaf_solve_update<8, 13, true>});
@@ -1948,19 +1969,17 @@ static void run_all(mra_plan* pl, uint32_t flags) {
 #define MRA_LSTAMP_VAL
 #define MRA_LSTAMP_NUL
 #endif
-                if (pl->leaf_solve_split == 2 && pl->n_leaf_solve_half)
+                if (r.update == LeafUpdate::SolveHalves)
                     hipLaunchKernelGGL((k_leaf_solve_update<8, 13, true>), dim3((unsigned)pl->n_leaf_solve_half), dim3(512), pl->leaf_solve_lds, pl->stream, pl->gLeafSolveHalf.p MRA_LSTAMP_VAL);
                 else
                     hipLaunchKernelGGL((k_leaf_solve_update<8, 13, true>), dim3((unsigned)ns), dim3(512), pl->leaf_solve_lds, pl->stream, pl->gLeafSolve.p MRA_LSTAMP_NUL);
                 if (nl > ns) launch_gemm<EPI_SUB>(pl, pl->gLeafUpdatePlain.p + ns, nl - ns, pl->leaf_max_rows, pl->leaf_max_na);
-            } else {
+            } else if (r.update != LeafUpdate::InPredictHi) {
                 KTimer kt(pl, KF_LEAF_UPDATE, pl->fl_leaf_update);
-                // (measured: the leaf-resident form wins for the residual - 1.07 vs 1.15 ms at C3 - but not for the update,
-                // 1.34-1.39 vs 1.29 ms, whatever the pass structure; MRA_OPT_LEAF_GEMM = 2 selects it for A/B runs)
-                if (leaf_gemm_ok(pl) && pl->leaf_gemm_update) launch_leaf_gemm<EPI_SUB>(pl, pl->gLeafUpdate.p, nl);
+                if (r.update == LeafUpdate::LeafGemm) launch_leaf_gemm<EPI_SUB>(pl, pl->gLeafUpdate.p, nl);
                 else launch_gemm<EPI_SUB>(pl, pl->gLeafUpdate.p, nl, pl->leaf_max_rows, pl->leaf_max_na);
             }
-            if (side) {
+            if (r.side) {
                 pl->stream = main_stream;
                 HIP_TRY(hipEventRecord(pl->ev_join, pl->stream2));
                 pl->side_pending = true;
@@ -2082,12 +2101,29 @@ static void sampler_factor(mra_plan* pl, size_t b) {
     }
 }
 
-// the likelihood pass with W at every row: the prior basis the sampler reads (option 17 is overridden here, not through the option)
-static void sampler_prior(mra_plan* pl) {
-    struct Keep { mra_plan* p; bool v; ~Keep() { p->use_lik_rows = v; } } keep{pl, pl->use_lik_rows};      // success and error paths
-    pl->use_lik_rows = false;
-    run_all(pl, MRA_RUN_LIKELIHOOD);
-}
+// What the caller reads back after a call that runs passes of its own (mra_sample, mra_solve): the last mra_run's likelihood, mean and
+// var - and the device y when ysave is given - are saved on pl->stream and put back when the scope ends, on success and error paths alike.
+struct KeepResults {
+    mra_plan* pl; double *ysave, *msave, *vsave;
+    const bool had_ran; const uint32_t had_flags; const double had_d, had_u; const bool had_pred; const size_t bytes;
+    KeepResults(mra_plan* p, double* ys, double* ms, double* vs)
+        : pl(p), ysave(ys), msave(ms), vsave(vs), had_ran(p->ran), had_flags(p->run_flags), had_d(p->res_d), had_u(p->res_u),
+          had_pred(p->ran && (p->run_flags & MRA_RUN_PREDICT)), bytes(p->P * sizeof(double)) {
+        if (ysave) HIP_TRY(hipMemcpyAsync(ysave, pl->y.p, bytes, hipMemcpyDeviceToDevice, pl->stream));
+        if (had_pred) HIP_TRY(hipMemcpyAsync(msave, pl->mean.p, bytes, hipMemcpyDeviceToDevice, pl->stream));
+        if (had_pred) HIP_TRY(hipMemcpyAsync(vsave, pl->var.p, bytes, hipMemcpyDeviceToDevice, pl->stream));
+    }
+    ~KeepResults() {
+        if (ysave) hipMemcpyAsync(pl->y.p, ysave, bytes, hipMemcpyDeviceToDevice, pl->stream);
+        if (had_pred) hipMemcpyAsync(pl->mean.p, msave, bytes, hipMemcpyDeviceToDevice, pl->stream);
+        if (had_pred) hipMemcpyAsync(pl->var.p, vsave, bytes, hipMemcpyDeviceToDevice, pl->stream);
+        hipStreamSynchronize(pl->stream);
+        pl->ran = had_ran; pl->run_flags = had_flags; pl->res_d = had_d; pl->res_u = had_u;
+    }
+};
+
+// the likelihood pass with W at every row: the prior basis the sampler reads (option 17 is overridden by the route, not through the option)
+static void sampler_prior(mra_plan* pl) { run_all(pl, MRA_RUN_LIKELIHOOD, true); }
 
 static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, int64_t sample0, const double* z, double* out) {
     if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
@@ -2115,27 +2151,8 @@ static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, i
     if (S.zc.n < (size_t)std::max<long>(Kn, 1) * 16) S.zc.alloc((size_t)std::max<long>(Kn, 1) * 16);
     if (S.out.n < (size_t)16 * P) S.out.alloc((size_t)16 * P);
     if (z && S.zh.n < (size_t)nsb * n_slots) S.zh.alloc((size_t)nsb * n_slots);
-    // what the caller will read back afterwards: the last mra_run's results and the device y
-    const bool had_ran = pl->ran;
-    const uint32_t had_flags = pl->run_flags;
-    const double had_d = pl->res_d, had_u = pl->res_u;
-    const bool had_pred = had_ran && (had_flags & MRA_RUN_PREDICT);
-    HIP_TRY(hipMemcpyAsync(S.ysave.p, pl->y.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
-    if (had_pred) {
-        HIP_TRY(hipMemcpyAsync(S.msave.p, pl->mean.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
-        HIP_TRY(hipMemcpyAsync(S.vsave.p, pl->var.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
-    }
-    auto restore = [&]() {
-        hipMemcpyAsync(pl->y.p, S.ysave.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream);
-        if (had_pred) {
-            hipMemcpyAsync(pl->mean.p, S.msave.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream);
-            hipMemcpyAsync(pl->var.p, S.vsave.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream);
-        }
-        hipStreamSynchronize(pl->stream);
-        pl->ran = had_ran; pl->run_flags = had_flags; pl->res_d = had_d; pl->res_u = had_u;
-    };
     {
-        struct OnExit { decltype(restore)& f; ~OnExit() { f(); } } on_exit{restore};     // success and error paths alike
+        KeepResults keep(pl, S.ysave.p, S.msave.p, S.vsave.p);      // the last mra_run's results and the device y
         S.factored = -1;                      // the kernel, the locations or the observations may have changed since the last call
         bool w_prior = false;
         for (int64_t s0 = 0; s0 < n; s0 += nsb) {
@@ -2210,23 +2227,7 @@ static void solve_all(mra_plan* pl, uint32_t flags, int64_t n, const double* Y, 
     if (!S.valid) {
         // the factors: one likelihood pass with W at every row (as sample_all's prior pass); what the caller reads back afterwards -
         // the last mra_run's likelihood, mean and var - is put back.  y and the options are not touched.
-        const bool had_ran = pl->ran;
-        const uint32_t had_flags = pl->run_flags;
-        const double had_d = pl->res_d, had_u = pl->res_u;
-        const bool had_pred = had_ran && (had_flags & MRA_RUN_PREDICT);
-        if (had_pred) {
-            HIP_TRY(hipMemcpyAsync(S.msave.p, pl->mean.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
-            HIP_TRY(hipMemcpyAsync(S.vsave.p, pl->var.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
-        }
-        auto restore = [&]() {
-            if (had_pred) {
-                hipMemcpyAsync(pl->mean.p, S.msave.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream);
-                hipMemcpyAsync(pl->var.p, S.vsave.p, P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream);
-            }
-            hipStreamSynchronize(pl->stream);
-            pl->ran = had_ran; pl->run_flags = had_flags; pl->res_d = had_d; pl->res_u = had_u;
-        };
-        struct OnExit { decltype(restore)& f; ~OnExit() { f(); } } on_exit{restore};     // success and error paths alike
+        KeepResults keep(pl, nullptr, S.msave.p, S.vsave.p);
         sampler_prior(pl);
         HIP_TRY(hipStreamSynchronize(pl->stream));
         HIP_TRY(hipGetLastError());
@@ -2841,48 +2842,48 @@ int mra_get_timers(mra_plan* pl, double* out, int cap) {
     return n;
 }
 
+static constexpr int OPT_KERNEL_SHAPE = 99;    // kernel-shape switches for A/B runs (no public name: tools only)
+
 int mra_plan_set_option(mra_plan* pl, int option, int64_t value) {
     return guarded(pl, [&] {
         require(pl, "mra_plan_set_option: plan is NULL");
         // options that change which kernel produces or factorises the leaves' C blocks bring the phantom-row launch back; the others
         // (timing, front / knot / solve / update variants) never touch C
-        if (option == 2 || option == 3 || option == 6 || option == 11) pl->cphantom_valid = false;
-        if (option != 1 && option != 20) pl->slv.valid = false;     // the next pass may run other kernels: mra_solve factorises again
-        if (option == 1) { pl->ktiming = value != 0; return MRA_OK; }
-        if (option == 2) { pl->use_fused = value != 0; return MRA_OK; }
-        if (option == 3) { pl->gemm_lds = value != 0; return MRA_OK; }
-        if (option == 4) { pl->use_front_fused = value != 0; return MRA_OK; }
-        if (option == 5) { pl->use_knot_chain = value != 0; return MRA_OK; }
-        if (option == 6) { pl->use_leaf_gemm = value != 0; pl->leaf_gemm_update = value == 2; return MRA_OK; }
-        if (option == 7) { pl->use_leaf_solve = value != 0; pl->leaf_solve_mode = (int)value; return MRA_OK; }
-        if (option == 8) { pl->use_pred_update = value != 0; return MRA_OK; }
-        if (option == 10) { pl->leaf_solve_split = value == 2 ? 2 : 1; return MRA_OK; }
-        if (option == 11) { pl->use_chol_lds = (int)value; return MRA_OK; }
-        if (option == 12) { pl->seg_gemm_lds = value != 0; return MRA_OK; }
-        if (option == 14) { pl->use_syrk_blk = (int)value; return MRA_OK; }
-        if (option == 15) { pl->use_prior_level = value != 0; return MRA_OK; }
-        if (option == 16) { pl->use_hi_fold = (int)value; return MRA_OK; }
-        if (option == 17) { pl->use_lik_rows = value != 0; return MRA_OK; }
-        if (option == 13) { pl->ut_gather = value != 0; return MRA_OK; }
-        if (option == 19) {
+        if (option == MRA_OPT_FUSED || option == MRA_OPT_GEMM_LDS || option == MRA_OPT_LEAF_GEMM || option == MRA_OPT_CHOL_TILES) pl->cphantom_valid = false;
+        if (option != MRA_OPT_KERNEL_TIMING && option != MRA_OPT_SAMPLE_SOLVE) pl->slv.valid = false;     // the next pass may run other kernels: mra_solve factorises again
+        switch (option) {
+        case MRA_OPT_KERNEL_TIMING: pl->ktiming = value != 0; return MRA_OK;
+        case MRA_OPT_FUSED: pl->use_fused = value != 0; return MRA_OK;
+        case MRA_OPT_GEMM_LDS: pl->gemm_lds = value != 0; return MRA_OK;
+        case MRA_OPT_FRONT_FUSED: pl->use_front_fused = value != 0; return MRA_OK;
+        case MRA_OPT_KNOT_CHAIN: pl->use_knot_chain = value != 0; return MRA_OK;
+        case MRA_OPT_LEAF_GEMM: pl->use_leaf_gemm = value != 0; pl->leaf_gemm_update = value == 2; return MRA_OK;
+        case MRA_OPT_LEAF_SOLVE: pl->use_leaf_solve = value != 0; pl->leaf_solve_mode = (int)value; return MRA_OK;
+        case MRA_OPT_PRED_UPDATE: pl->use_pred_update = value != 0; return MRA_OK;
+        case MRA_OPT_LEAF_SOLVE_SPLIT: pl->leaf_solve_split = value == 2 ? 2 : 1; return MRA_OK;
+        case MRA_OPT_CHOL_TILES: pl->use_chol_lds = (int)value; return MRA_OK;
+        case MRA_OPT_SEG_GEMM_LDS: pl->seg_gemm_lds = value != 0; return MRA_OK;
+        case MRA_OPT_SYRK_BLK: pl->use_syrk_blk = (int)value; return MRA_OK;
+        case MRA_OPT_PRIOR_LEVEL: pl->use_prior_level = value != 0; return MRA_OK;
+        case MRA_OPT_HI_FOLD: pl->use_hi_fold = (int)value; return MRA_OK;
+        case MRA_OPT_LIK_ROWS: pl->use_lik_rows = value != 0; return MRA_OK;
+        case MRA_OPT_UT_GATHER: pl->ut_gather = value != 0; return MRA_OK;
+        case MRA_OPT_SAMPLE_GRAM_BYTES:
             if (value < 0) throw MraError(MRA_ERR_INVALID, "option 19: the Gram batch budget is a byte count >= 0");
             if ((size_t)value != pl->smp.gram_bytes) { pl->smp.gram_bytes = (size_t)value; pl->smp.built = false; }
             return MRA_OK;
-        }
-        if (option == 20) {
+        case MRA_OPT_SAMPLE_SOLVE:
             if (value != 0 && value != 1) throw MraError(MRA_ERR_INVALID, "option 20: 0 or 1");
             pl->slv.in_sampler = (int)value;
             return MRA_OK;
-        }
-        if (option == 18) {
+        case MRA_OPT_CASCADE_GROUP:
             if (!pl->regular) return MRA_OK;          // (no fused cascade: nothing is grouped, the decision stays 0)
             pl->cascade_group_siblings = value != 0;
             pl->lik_tiles_valid = false;
             HIP_TRY(mraSetDevice(pl->device));
             build_leaf_workgroups(pl);
             return MRA_OK;
-        }
-        if (option == 99) {
+        case OPT_KERNEL_SHAPE:
             // kernel-shape switches for A/B runs.  Bits 8 and 32 keep the results (predictive cascade at two workgroups per CU, the
             // wide leaf-residual shape); bits 1, 2, 4 (no Ut scatter / no W stores / constant instead of the kernel) give WRONG results
             // and exist only in the diagnostic what-if build (`make whatif`, -DMRA_WHATIF): the product library refuses them.
@@ -2891,8 +2892,8 @@ int mra_plan_set_option(mra_plan* pl, int option, int64_t value) {
 #endif
             pl->dbg = (int)value;
             return MRA_OK;
+        default: throw MraError(MRA_ERR_INVALID, "unknown option");
         }
-        throw MraError(MRA_ERR_INVALID, "unknown option");
     });
 }
 
@@ -2900,26 +2901,26 @@ int mra_plan_get_option(mra_plan* pl, int option, int64_t* value) {
     return guarded(pl, [&] {
         require(pl && value, "mra_plan_get_option: plan or value is NULL");
         switch (option) {
-            case 1: *value = pl->ktiming; break;
-            case 2: *value = pl->use_fused; break;
-            case 3: *value = pl->gemm_lds; break;
-            case 4: *value = pl->use_front_fused; break;
-            case 5: *value = pl->use_knot_chain; break;
-            case 6: *value = pl->use_leaf_gemm ? (pl->leaf_gemm_update ? 2 : 1) : 0; break;
-            case 7: *value = pl->leaf_solve_mode; break;
-            case 8: *value = pl->use_pred_update; break;
-            case 10: *value = pl->leaf_solve_split; break;
-            case 11: *value = pl->use_chol_lds; break;
-            case 12: *value = pl->seg_gemm_lds; break;
-            case 14: *value = pl->use_syrk_blk; break;
-            case 15: *value = pl->use_prior_level; break;
-            case 16: *value = pl->use_hi_fold; break;
-            case 17: *value = pl->use_lik_rows; break;
-            case 13: *value = pl->ut_gather; break;
-            case 18: *value = pl->cascade_group_siblings; break;
-            case 19: *value = (int64_t)pl->smp.gram_bytes; break;
-            case 20: *value = pl->slv.in_sampler; break;
-            case 99: *value = pl->dbg; break;
+            case MRA_OPT_KERNEL_TIMING: *value = pl->ktiming; break;
+            case MRA_OPT_FUSED: *value = pl->use_fused; break;
+            case MRA_OPT_GEMM_LDS: *value = pl->gemm_lds; break;
+            case MRA_OPT_FRONT_FUSED: *value = pl->use_front_fused; break;
+            case MRA_OPT_KNOT_CHAIN: *value = pl->use_knot_chain; break;
+            case MRA_OPT_LEAF_GEMM: *value = pl->use_leaf_gemm ? (pl->leaf_gemm_update ? 2 : 1) : 0; break;
+            case MRA_OPT_LEAF_SOLVE: *value = pl->leaf_solve_mode; break;
+            case MRA_OPT_PRED_UPDATE: *value = pl->use_pred_update; break;
+            case MRA_OPT_LEAF_SOLVE_SPLIT: *value = pl->leaf_solve_split; break;
+            case MRA_OPT_CHOL_TILES: *value = pl->use_chol_lds; break;
+            case MRA_OPT_SEG_GEMM_LDS: *value = pl->seg_gemm_lds; break;
+            case MRA_OPT_SYRK_BLK: *value = pl->use_syrk_blk; break;
+            case MRA_OPT_PRIOR_LEVEL: *value = pl->use_prior_level; break;
+            case MRA_OPT_HI_FOLD: *value = pl->use_hi_fold; break;
+            case MRA_OPT_LIK_ROWS: *value = pl->use_lik_rows; break;
+            case MRA_OPT_UT_GATHER: *value = pl->ut_gather; break;
+            case MRA_OPT_CASCADE_GROUP: *value = pl->cascade_group_siblings; break;
+            case MRA_OPT_SAMPLE_GRAM_BYTES: *value = (int64_t)pl->smp.gram_bytes; break;
+            case MRA_OPT_SAMPLE_SOLVE: *value = pl->slv.in_sampler; break;
+            case OPT_KERNEL_SHAPE: *value = pl->dbg; break;
             default: throw MraError(MRA_ERR_INVALID, "unknown option");
         }
         return MRA_OK;
@@ -2957,9 +2958,9 @@ int mra_plan_prepare(mra_plan* pl, int64_t* n_kernels) {
 
 int mra_get_kernel_stats(mra_plan* pl, int which, char* name, int name_cap, int* launches, double* ms, double* flops) {
     if (!pl || which < 0 || which >= KF_COUNT) return MRA_ERR_INVALID;
-    const bool fused = pl->regular && pl->use_fused && !pl->host_cov;
-    const bool hi_path = !fused && pl->regular_hi && pl->use_fused && !pl->host_cov;
-    if (name && name_cap > 0) { strncpy(name, kfam_name[fused ? 0 : (hi_path ? 2 : 1)][which], name_cap - 1); name[name_cap - 1] = 0; }
+    const PassPath path = path_of(pl);         // (the plan's current state, not the pass that ran)
+    const bool hi_name = path == PassPath::Hi && (which == KF_PRED_TRSM || which == KF_PRED_UPDATE);
+    if (name && name_cap > 0) { strncpy(name, hi_name ? kfam_name_hi[which - KF_PRED_TRSM] : kfam_name[path == PassPath::Fused ? 0 : 1][which], name_cap - 1); name[name_cap - 1] = 0; }
     if (launches) *launches = pl->kstat[which].launches;
     if (ms) *ms = pl->kstat[which].ms;
     if (flops) *flops = pl->kstat[which].flops;

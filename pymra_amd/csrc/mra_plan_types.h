@@ -63,9 +63,10 @@ enum KFam {
     KF_PRIOR_RESID = 0, KF_PRIOR_CHOL, KF_PRIOR_TRSM, KF_LEAF_RESID, KF_LEAF_CHOL, KF_LEAF_SYRK,
     KF_LEAF_UPDATE, KF_FRONT_CHOL, KF_FRONT_SCHUR, KF_PRED_TRSM, KF_PRED_UPDATE, KF_MISC, KF_COUNT
 };
-// family names = the kernels that actually run (rocprofv3 kernel names), by path: [0] fused cascades on regular trees,
-// [1] general level-by-level path, [2] level-by-level prior and fronts with the two-kernel predictive cascade of deep 64-wide trees.  tools/summarize_profiles.py maps the trace's kernel names onto the same strings.
-static const char* kfam_name[3][KF_COUNT] = {
+// family names = the kernels that actually run (rocprofv3 kernel names), by path: [0] fused cascades on regular trees, [1] general
+// level-by-level path; kfam_name_hi: KF_PRED_TRSM and KF_PRED_UPDATE of [1] with the two-kernel predictive cascade of deep 64-wide trees.
+// tools/summarize_profiles.py maps the trace's kernel names onto the same strings.
+static const char* kfam_name[2][KF_COUNT] = {
     {"k_gemm_nt_lds<COV> prior residual (unused on the fused path)",
      "k_knot_chain + k_prior_cascade<KNOT> knot pass (knot rows, kInv, Cholesky)",
      "k_prior_cascade row pass (W of all levels)",
@@ -89,19 +90,9 @@ static const char* kfam_name[3][KF_COUNT] = {
      "k_gemm_nt<SUB> front Schur complement",
      "k_trsm_rows2 predict X = W Lt^-T per level",
      "k_gemm_nt_lds<SUB> predict update per level",
-     "small kernels (k_assemble, k_gather_kinv, k_leaf_moments, k_sum_dnode, ...)"},
-    {"k_leaf_gemm<COV,SOLVE> prior of a level: residual + kernel + row solve (or k_gemm_nt_lds<COV> residual only)",
-     "k_gemm_nt_lds<COV> knots' residual block + k_panel_chol prior kInv Cholesky per level",
-     "k_trsm_rows2 prior W = R L^-T per level",
-     "k_leaf_gemm<COV> leaf residual V[S,o] and C",
-     "k_chol_wave + k_trsm_rows2 (or k_panel_chol) leaf factor and solves",
-     "k_gemm_nt<SET> / k_parent_front leaf or parent SYRK",
-     "k_gemm_nt_lds<SUB> leaf update W[S,anc] -= Tt^T Ut",
-     "k_front / k_panel_chol front partial Cholesky",
-     "k_gemm_nt<SUB> front Schur complement",
-     "k_predict_cascade (the four coarse levels of a deep tree)",
-     "k_predict_hi (four deepest levels in registers + one sweep over the coarse columns)",
      "small kernels (k_assemble, k_gather_kinv, k_leaf_moments, k_sum_dnode, ...)"}};
+static const char* kfam_name_hi[2] = {"k_predict_cascade (the four coarse levels of a deep tree)",
+                                      "k_predict_hi (four deepest levels in registers + one sweep over the coarse columns)"};
 
 // Work of a launch (or a family of launches): algorithmic flops with TRUE sizes (true ranks, true observation counts, a
 // one-column y), the flops the MFMA tiles actually execute on the 16-padded layout, and the algorithmic HBM bytes of the
@@ -251,6 +242,35 @@ struct LevelData {
     Work fl_resid, fl_pchol, fl_trsm, fl_fchol, fl_schur, fl_update;
 };
 
+// ---- the route of a pass: WHICH launch sequence it runs, decided once by route_for (mra_plan.hip) from the tree's shape, the run
+// flags, the options and the capability marks, stored in the plan when the pass opens and constant until it ends -----------------
+constexpr int LEAF_MAX_TILES = 12;  // widest leaf observation block, in 16-row tiles, of k_chol_wave<LEAF_MAX_TILES> and the LDS row solve behind it
+constexpr int TRSM2_MAX_NT = 12;    // widest block of launch_trsm2 (k_trsm_rows2<TRSM2_MAX_NT>); wider levels take k_trsm_rows
+static_assert(LEAF_MAX_TILES <= TRSM2_MAX_NT, "the leaves' row solve goes through launch_trsm2 without a fall-back");
+enum class PassPath { Fused, Hi, Levels };      // one-kernel cascades of a regular tree / level-by-level with k_predict_hi (deep 64-wide trees) / level-by-level
+enum class LeafCFix { None, InProduct, Phantom, Fill };     // no observations / the gathered COV product wrote all of C / k_leaf_cphantom / k_leaf_fill
+enum class LeafChol { TilesOne, TilesSplit, Wave, BigPanels };      // k_chol_tiles<10,4> / <8,4> + <10,4> / k_chol_wave / right-looking panels + trailing GEMM
+enum class LeafVar { None, FinishVar, Moments };            // variance of a predict pass: the cascade's own / k_leaf_finish_var / k_leaf_moments
+// W[S,anc] -= Tt^T Ut: no predict / in k_predict_cascade (larger leaves: GEMM) / in k_predict_hi / k_leaf_solve_update, one or two workgroups per leaf / k_gemm_nt_lds<SUB> / k_leaf_gemm<SUB>
+enum class LeafUpdate { None, InCascade, InPredictHi, SolveWhole, SolveHalves, Gemm, LeafGemm };
+struct PassRoute {
+    PassPath path = PassPath::Levels;
+    bool predict = false, init_yblock = false, acc_var = false;     // k_init_yblock runs (every path but Fused); the row solves accumulate the variance on the way
+    int n_chain = 0;                            // Fused: levels of the k_knot_chain launch (0: one knot launch per level)
+    bool prior_level = false;                   // level-by-level prior: one launch per level where lv.prior_level_ok
+    bool c_only = false, lik_rows = false, lik_general = false;     // likelihood-only: C from a gathered product; W at the needed rows only (Fused / not)
+    bool scatter_ut = false;                    // Fused: the row cascade scatters the leaves' Ut rows (MRA_OPT_UT_GATHER off)
+    bool leaf_resident = false;                 // leaf residual on k_leaf_gemm
+    LeafCFix c_fix = LeafCFix::None; LeafChol chol = LeafChol::Wave; LeafVar var = LeafVar::None; LeafUpdate update = LeafUpdate::None;
+    bool solve_fused = false;                   // Fused + predict: the small leaves solve their Ut rows only, k_leaf_solve_update does the rest
+    const Trsm2Prob *trsm_small = nullptr, *trsm_all = nullptr;     // row-solve lists: leaves [0, n_trsm_small) (Fused only) and the others (same index)
+    // the leaves' parents' fronts straight from the children's Ut; by k_parent_front in one launch; k_front where the level's front_mode allows it
+    bool direct_parent = false, parent_front = false, front_fused = false;
+    bool syrk_blk = false, syrk_dma = false;    // the grandparents' signed SYRK on k_syrk_blk (its DMA-staged form)
+    bool side = false;                          // predict-only leaf work forked to the side stream (sharded runs, never with kernel timing)
+    bool extract_mean = false;                  // k_extract_mean after the level-by-level predictive pass
+};
+
 struct mra_plan {
     int device = 0;
     UploadArena arena;                   // the small descriptor arrays of this plan (device block + pinned mirror, see UploadArena)
@@ -315,14 +335,13 @@ struct mra_plan {
     bool ut_gather = true;                    // fused path: the leaves' Ut rows gathered from W by the row solve (no scatter in the row cascade: 1.21 -> 1.03 ms there, +0.16 ms in the solve)
     bool cphantom_valid = false;              // the phantom observation rows of the leaves' C blocks hold their identity rows
     int use_hi_fold = 1;                      // deep 64-wide trees: the leaf update W -= Tt Ut^T inside k_predict_hi instead of a pass over all of W (option 16)
-    bool hi_fold_now = false;                 // ... decided for the pass that is running
     bool use_prior_level = true;              // levels of the level-by-level prior with blocks <= 64 wide: residual + kernel + row solve in one launch (option 15)
     bool parent_panel_lds_ok = false;         // every parent-panel problem fits the step table of the LDS-tiled segmented product
     bool grand_syrk_dma_ok = false;           // ... and the smaller one of its DMA-staged form
     bool grand_syrk_blk_ok = false;           // every grandparent problem fits k_syrk_blk's step table
     int use_syrk_blk = 1;                     // the grandparents' signed SYRK on 96 x 96 blocks through LDS (k_syrk_blk) instead of 32 x 32 wave tiles (option 14)
     bool seg_gemm_lds = true;                 // the parents' panel product (segmented: sum over the children's Ut blocks) on the LDS-tiled GEMM (6.3 -> 5.4 ms at config 5)
-    bool use_pred_update = true, pred_update_now = false;   // leaf update folded into the predictive cascade
+    bool use_pred_update = true;              // leaf update folded into the predictive cascade
     DevVec<long> leaf_row0_dev;
     DevVec<unsigned char> leaf_upd_dev;
     size_t leaf_solve_lds = 0;
@@ -334,7 +353,7 @@ struct mra_plan {
     DevVec<FrontProb> gParentFront;      // the same nodes for k_parent_front (SYRK + factorisation in one launch)
     int parent_front_nacc = 0;           // 0: not available (front too large for the register-resident SYRK)
     size_t parent_front_lds = 0;
-    bool parent_syrk = false, direct_parent = false;
+    bool parent_syrk = false;
     // Large fronts at the level of the leaves' parents (config 5: 528^2 per node, 36 GB in all) are never formed: F = I + U U^T with
     // U = the children's Ut blocks side by side has rank <= sum(n_obs), so only its panel columns [F_oo ; F_ao] = U U_o^T (+ I) are
     // built and factorised ([Lt ; Zt]), and the grandparents' fronts come straight from the leaves and the panels:
@@ -361,13 +380,13 @@ struct mra_plan {
     // fused ("regular tree") path
     // deep trees with 64-wide blocks (5 - 8 non-leaf levels of four tiles: BASELINE config 5): too many tiles per row for the one-kernel
     // cascades; the predictive pass runs as k_predict_hi (four deepest levels) + k_predict_cascade (coarse levels)
-    bool var_accumulated = false;       // level-by-level path: the row solves have accumulated the prior / leaf variance (no k_leaf_moments pass)
     bool regular_hi = false;
     DevVec<long> hi_wg0_8;
     DevVec<int> hi_wgleaf;                    // [k_predict_hi workgroup] leaf slot of its tiles
     DevVec<int> hi_wgn_8;
     long n_hi_wg8 = 0;
     bool regular = false, use_fused = true, gemm_lds = true, use_front_fused = true, use_leaf_gemm = true, leaf_gemm_update = false;
+    PassRoute route;                    // the launch sequence of the open pass: fixed by run_all, read by every stage and by mra_run_resume
     int dbg = 0;
     int NL = 0, CWT = 0;
     struct FusedLevel {
