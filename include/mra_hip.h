@@ -173,6 +173,42 @@ int mra_solve(mra_plan *plan, uint32_t flags, int64_t n_cols, const double *Y, d
  * likelihood needs - the observed rows, and the knots on the level-by-level path - and leaves the others as they were.) */
 int mra_get_buffer(mra_plan *plan, int what, double *out, int64_t capacity, int64_t *n_avail);
 
+/* Diagnostics for tests: the route of the last pass - WHICH kernels it launched ("How a pass chooses its
+ * kernels"; PassRoute in mra_plan_types.h).  An accepted option is not yet a kernel that ran: thresholds on the tree (largest leaf
+ * in observation tiles, leaves per CU, block widths) override options, and this call shows the outcome.  It reads what mra_run
+ * (or the pass inside mra_sample / mra_solve) fixed when the pass opened and changes nothing.  out[k], k < min(capacity,
+ * MRA_ROUTE_FIELDS), in this order (booleans as 0 / 1):
+ *    0 path (MRA_ROUTE_PATH_*)   1 predict        2 init_yblock    3 acc_var        4 n_chain       5 prior_level    6 c_only
+ *    7 lik_rows                  8 lik_general    9 scatter_ut    10 leaf_resident 11 c_fix (MRA_ROUTE_CFIX_*)
+ *   12 chol (MRA_ROUTE_CHOL_*)  13 var (MRA_ROUTE_VAR_*)          14 update (MRA_ROUTE_UPDATE_*)   15 solve_fused
+ *   16 direct_parent            17 parent_front  18 front_fused   19 syrk_blk      20 syrk_dma     21 side          22 extract_mean
+ *   23 n_leaves   24 n_trsm_small (leaves of at most 8 observation tiles: first in the fused path's row-solve and update lists)
+ *   25 n_chol_small (the same count for the split k_chol_tiles launch)   26 n_cu (compute units the thresholds count leaves against)
+ * Returns the number of fields written, MRA_ERR_STATE before the first pass, MRA_ERR_INVALID for a NULL argument. */
+#define MRA_ROUTE_FIELDS            27
+#define MRA_ROUTE_PATH_FUSED         0   /* regular tree: one-kernel cascades                                         */
+#define MRA_ROUTE_PATH_HI            1   /* deep 64-wide tree: level-by-level prior and fronts, k_predict_hi          */
+#define MRA_ROUTE_PATH_LEVELS        2   /* level-by-level kernels                                                    */
+#define MRA_ROUTE_CFIX_NONE          0   /* no leaf has an observation                                                */
+#define MRA_ROUTE_CFIX_IN_PRODUCT    1   /* likelihood-only: the gathered COV product wrote all of C                  */
+#define MRA_ROUTE_CFIX_PHANTOM       2   /* k_leaf_cphantom                                                           */
+#define MRA_ROUTE_CFIX_FILL          3   /* k_leaf_fill (a leaf of more than 192 observations)                        */
+#define MRA_ROUTE_CHOL_TILES_ONE     0   /* k_chol_tiles<10,4> for every leaf                                         */
+#define MRA_ROUTE_CHOL_TILES_SPLIT   1   /* k_chol_tiles<8,4> for the n_chol_small leaves, <10,4> for the others      */
+#define MRA_ROUTE_CHOL_WAVE          2   /* k_chol_wave                                                               */
+#define MRA_ROUTE_CHOL_BIG_PANELS    3   /* right-looking panels + trailing GEMM                                      */
+#define MRA_ROUTE_VAR_NONE           0   /* the predictive cascade's own (or no predict pass)                         */
+#define MRA_ROUTE_VAR_FINISH_VAR     1   /* accumulated by the row solves, k_leaf_finish_var                          */
+#define MRA_ROUTE_VAR_MOMENTS        2   /* k_leaf_moments                                                            */
+#define MRA_ROUTE_UPDATE_NONE        0   /* no predict pass                                                           */
+#define MRA_ROUTE_UPDATE_IN_CASCADE  1   /* in k_predict_cascade (leaves of more than 8 observation tiles: GEMM)      */
+#define MRA_ROUTE_UPDATE_IN_PREDICT_HI 2 /* in k_predict_hi                                                           */
+#define MRA_ROUTE_UPDATE_SOLVE_WHOLE 3   /* k_leaf_solve_update, one workgroup per leaf (larger leaves: GEMM)         */
+#define MRA_ROUTE_UPDATE_SOLVE_HALVES 4  /* k_leaf_solve_update, two workgroups per leaf (larger leaves: GEMM)        */
+#define MRA_ROUTE_UPDATE_GEMM        5   /* k_gemm_nt_lds<SUB>                                                        */
+#define MRA_ROUTE_UPDATE_LEAF_GEMM   6   /* k_leaf_gemm<SUB>                                                          */
+int mra_get_route(mra_plan *plan, int32_t *out, int capacity);
+
 /* Replaces: the per-node attributes the reference leaves on its Node objects - B, kInv (pyMRA/MRANode.py:384-385),
  * kTil, A, omg (:426-445), BTil (:486-495) - which its diagnostics read (MRATree.getBasisFunctionsMatrix,
  * pyMRA/MRATree.py:445-511; pyMRA/tests/debug-posterior.py:97-109).  The device keeps them in whitened form

@@ -1804,6 +1804,7 @@ static void run_all(mra_plan* pl, uint32_t flags, bool full_rows = false) {
     for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = mra_plan::KStat();
     if (!pl->lik_general_valid && route_for(pl, flags, full_rows).lik_general) ensure_lik_general(pl);      // (once; route_for reads the verdict)
     const PassRoute& r = pl->route = route_for(pl, flags, full_rows);
+    pl->route_set = true;
     const bool pred = r.predict, fused = r.path == PassPath::Fused;
     phase_mark(pl, 0);
     if (r.init_yblock) {
@@ -2979,6 +2980,23 @@ int mra_device_synchronize(int device) {
 }
 
 int mra_kernel_family_count(void) { return KF_COUNT; }
+
+// Diagnostics: the route of the last pass as integers, in the order include/mra_hip.h documents.  Reads, changes nothing.
+int mra_get_route(mra_plan* pl, int32_t* out, int cap) {
+    return guarded(pl, [&] {
+        require(pl && out, "mra_get_route: plan or out is NULL");
+        if (!pl->route_set) throw MraError(MRA_ERR_STATE, "mra_get_route: no pass has run on this plan yet");
+        const PassRoute& r = pl->route;
+        const int32_t v[MRA_ROUTE_FIELDS] = {
+            (int32_t)r.path, r.predict, r.init_yblock, r.acc_var, r.n_chain, r.prior_level, r.c_only, r.lik_rows, r.lik_general, r.scatter_ut,
+            r.leaf_resident, (int32_t)r.c_fix, (int32_t)r.chol, (int32_t)r.var, (int32_t)r.update, r.solve_fused, r.direct_parent,
+            r.parent_front, r.front_fused, r.syrk_blk, r.syrk_dma, r.side, r.extract_mean,
+            (int32_t)pl->leaf_nodes.size(), (int32_t)pl->n_trsm_small, (int32_t)pl->n_chol_small, pl->n_cu};
+        const int n = std::max(0, std::min(cap, (int)MRA_ROUTE_FIELDS));
+        for (int k = 0; k < n; ++k) out[k] = v[k];
+        return n;
+    });
+}
 
 int mra_plan_info(mra_plan* pl, int64_t* out, int cap) {
     if (!pl || !out) return 0;

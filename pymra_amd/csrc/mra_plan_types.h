@@ -247,12 +247,16 @@ struct LevelData {
 constexpr int LEAF_MAX_TILES = 12;  // widest leaf observation block, in 16-row tiles, of k_chol_wave<LEAF_MAX_TILES> and the LDS row solve behind it
 constexpr int TRSM2_MAX_NT = 12;    // widest block of launch_trsm2 (k_trsm_rows2<TRSM2_MAX_NT>); wider levels take k_trsm_rows
 static_assert(LEAF_MAX_TILES <= TRSM2_MAX_NT, "the leaves' row solve goes through launch_trsm2 without a fall-back");
-enum class PassPath { Fused, Hi, Levels };      // one-kernel cascades of a regular tree / level-by-level with k_predict_hi (deep 64-wide trees) / level-by-level
-enum class LeafCFix { None, InProduct, Phantom, Fill };     // no observations / the gathered COV product wrote all of C / k_leaf_cphantom / k_leaf_fill
-enum class LeafChol { TilesOne, TilesSplit, Wave, BigPanels };      // k_chol_tiles<10,4> / <8,4> + <10,4> / k_chol_wave / right-looking panels + trailing GEMM
-enum class LeafVar { None, FinishVar, Moments };            // variance of a predict pass: the cascade's own / k_leaf_finish_var / k_leaf_moments
+// (the integer values are the MRA_ROUTE_* numbers of include/mra_hip.h: mra_get_route reports them)
+enum class PassPath { Fused = MRA_ROUTE_PATH_FUSED, Hi = MRA_ROUTE_PATH_HI, Levels = MRA_ROUTE_PATH_LEVELS };      // one-kernel cascades of a regular tree / level-by-level with k_predict_hi (deep 64-wide trees) / level-by-level
+// no observations / the gathered COV product wrote all of C / k_leaf_cphantom / k_leaf_fill
+enum class LeafCFix { None = MRA_ROUTE_CFIX_NONE, InProduct = MRA_ROUTE_CFIX_IN_PRODUCT, Phantom = MRA_ROUTE_CFIX_PHANTOM, Fill = MRA_ROUTE_CFIX_FILL };
+// k_chol_tiles<10,4> / <8,4> + <10,4> / k_chol_wave / right-looking panels + trailing GEMM
+enum class LeafChol { TilesOne = MRA_ROUTE_CHOL_TILES_ONE, TilesSplit = MRA_ROUTE_CHOL_TILES_SPLIT, Wave = MRA_ROUTE_CHOL_WAVE, BigPanels = MRA_ROUTE_CHOL_BIG_PANELS };
+enum class LeafVar { None = MRA_ROUTE_VAR_NONE, FinishVar = MRA_ROUTE_VAR_FINISH_VAR, Moments = MRA_ROUTE_VAR_MOMENTS };            // variance of a predict pass: the cascade's own / k_leaf_finish_var / k_leaf_moments
 // W[S,anc] -= Tt^T Ut: no predict / in k_predict_cascade (larger leaves: GEMM) / in k_predict_hi / k_leaf_solve_update, one or two workgroups per leaf / k_gemm_nt_lds<SUB> / k_leaf_gemm<SUB>
-enum class LeafUpdate { None, InCascade, InPredictHi, SolveWhole, SolveHalves, Gemm, LeafGemm };
+enum class LeafUpdate { None = MRA_ROUTE_UPDATE_NONE, InCascade = MRA_ROUTE_UPDATE_IN_CASCADE, InPredictHi = MRA_ROUTE_UPDATE_IN_PREDICT_HI, SolveWhole = MRA_ROUTE_UPDATE_SOLVE_WHOLE,
+                        SolveHalves = MRA_ROUTE_UPDATE_SOLVE_HALVES, Gemm = MRA_ROUTE_UPDATE_GEMM, LeafGemm = MRA_ROUTE_UPDATE_LEAF_GEMM };
 struct PassRoute {
     PassPath path = PassPath::Levels;
     bool predict = false, init_yblock = false, acc_var = false;     // k_init_yblock runs (every path but Fused); the row solves accumulate the variance on the way
@@ -387,6 +391,7 @@ struct mra_plan {
     long n_hi_wg8 = 0;
     bool regular = false, use_fused = true, gemm_lds = true, use_front_fused = true, use_leaf_gemm = true, leaf_gemm_update = false;
     PassRoute route;                    // the launch sequence of the open pass: fixed by run_all, read by every stage and by mra_run_resume
+    bool route_set = false;             // a pass has fixed `route` (mra_get_route)
     int dbg = 0;
     int NL = 0, CWT = 0;
     struct FusedLevel {

@@ -40,6 +40,19 @@ MRA_OPT_SAMPLE_SOLVE = 20
 MRA_SAMPLE_CONDITIONAL = 1
 MRA_BLOCK_W_ROWS, MRA_BLOCK_LPRIOR, MRA_BLOCK_FRONT, MRA_BLOCK_LEAF = 0, 1, 2, 3
 
+# mra_get_route (include/mra_hip.h): the fields in the order the library writes them, and the members of the four enums by value
+ROUTE_FIELDS = ("path", "predict", "init_yblock", "acc_var", "n_chain", "prior_level", "c_only", "lik_rows", "lik_general", "scatter_ut",
+                "leaf_resident", "c_fix", "chol", "var", "update", "solve_fused", "direct_parent", "parent_front", "front_fused",
+                "syrk_blk", "syrk_dma", "side", "extract_mean", "n_leaves", "n_trsm_small", "n_chol_small", "n_cu")
+ROUTE_ENUMS = {
+    "path": ("Fused", "Hi", "Levels"),
+    "c_fix": ("None", "InProduct", "Phantom", "Fill"),
+    "chol": ("TilesOne", "TilesSplit", "Wave", "BigPanels"),
+    "var": ("None", "FinishVar", "Moments"),
+    "update": ("None", "InCascade", "InPredictHi", "SolveWhole", "SolveHalves", "Gemm", "LeafGemm"),
+}
+ROUTE_COUNTS = ("n_chain", "n_leaves", "n_trsm_small", "n_chol_small", "n_cu")
+
 ERR_NAMES = {-1: "MRA_ERR_INVALID", -2: "MRA_ERR_HIP", -3: "MRA_ERR_NOT_SPD", -4: "MRA_ERR_STATE",
              -5: "MRA_ERR_COMM"}
 
@@ -48,7 +61,7 @@ EXPORTS = [
     "mra_device_count", "mra_release_cached_memory", "mra_plan_create", "mra_plan_destroy", "mra_plan_set_locs", "mra_plan_set_obs",
     "mra_plan_set_kernel", "mra_plan_set_locs_rows", "mra_plan_set_obs_rows", "mra_get_predict_rows", "mra_get_predict_rows_sd", "mra_eval_kernel", "mra_plan_set_cov_block", "mra_run", "mra_get_likelihood", "mra_get_predict",
     "mra_sample_slots", "mra_sample", "mra_solve", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
-    "mra_get_kernel_stats", "mra_get_kernel_work", "mra_device_synchronize", "mra_plan_info", "mra_comm_unique_id", "mra_comm_init",
+    "mra_get_kernel_stats", "mra_get_kernel_work", "mra_get_route", "mra_device_synchronize", "mra_plan_info", "mra_comm_unique_id", "mra_comm_init",
     "mra_plan_set_reduce_level", "mra_reduce_size", "mra_reduce_export", "mra_reduce_import",
     "mra_run_resume", "mra_last_error", "mra_version",
     "mra_tree_replay_2d", "mra_tree_replay_2d_into", "mra_plan_create_replay_2d", "mra_tree_sizes", "mra_tree_export", "mra_tree_free",
@@ -119,6 +132,7 @@ def load_library():
         "mra_kernel_family_count": (C.c_int, []),
         "mra_get_kernel_stats": (C.c_int, [vp, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.c_int), C.POINTER(dbl), C.POINTER(dbl)]),
         "mra_get_kernel_work": (C.c_int, [vp, C.c_int, vp, C.c_int]),
+        "mra_get_route": (C.c_int, [vp, vp, C.c_int]),
         "mra_device_synchronize": (C.c_int, [C.c_int]),
         "mra_plan_info": (C.c_int, [vp, vp, C.c_int]),
         "mra_comm_unique_id": (C.c_int, [C.c_char_p, C.c_int]),
@@ -378,6 +392,20 @@ class HipPlan:
             w = np.zeros(4)
             self._check(self.lib.mra_get_kernel_work(self._h, k, _ptr(w), 4))
             res.append(dict(name=name.value.decode(), launches=n.value, ms=ms.value, flops=fl.value, flops_exec=float(w[1]), bytes=float(w[2])))
+        return res
+
+    def route(self):
+        """Which kernels the last pass launched (mra_get_route): the fields of the library's PassRoute by name - the four enums as
+        their member names (ROUTE_ENUMS), the counts as ints, everything else as bools.  MraError MRA_ERR_STATE before the first pass."""
+        out = np.zeros(len(ROUTE_FIELDS), dtype=np.int32)
+        n = self.lib.mra_get_route(self._h, _ptr(out), len(out))
+        if n < 0:
+            self._check(n)
+        if n != len(ROUTE_FIELDS):
+            raise RuntimeError("mra_get_route wrote %d fields, this binding knows %d" % (n, len(ROUTE_FIELDS)))
+        res = {}
+        for k, v in zip(ROUTE_FIELDS, (int(x) for x in out)):
+            res[k] = ROUTE_ENUMS[k][v] if k in ROUTE_ENUMS else v if k in ROUTE_COUNTS else bool(v)
         return res
 
     def info(self):
