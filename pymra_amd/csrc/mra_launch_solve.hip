@@ -46,9 +46,8 @@ void mra_solver_build(mra_plan* pl) {
     for (size_t t = 0; t < nl; ++t) {
         const int i = pl->leaf_nodes[t];
         const int m = pl->node_level[i], nop = pl->leaf_nop[t], p = pl->parent[i];
-        const double* Pn = pl->panel.p + pl->leaf_poff[t];
         SolveLeaf L{};
-        L.Lc = Pn; L.Ut = Pn + (size_t)nop * nop;
+        L.Lc = leaf_C(pl, t); L.Ut = leaf_Ut(pl, t);
         L.obs = pl->obs_idx.p + pl->obs_off_host[t];
         L.uy = S.uy.p + pl->obs_off_host[t] * 16;
         L.gb = S.nb.p + noff[i];
@@ -72,7 +71,7 @@ void mra_solver_build(mra_plan* pl) {
             if (pl->node_slot[i] != (int)s) throw MraError(MRA_ERR_STATE, "mra_solve: node slot order");
             const int p = pl->parent[i];
             SolveFront N{};
-            N.F = lvl.F.p + s * (size_t)lvl.nf * lvl.ldf;
+            N.F = lvl.F_of(s);
             N.buf = S.nb.p + noff[i];
             N.chain = p >= 0 ? S.nb.p + noff[p] : nullptr;
             N.ld = lvl.ldf; N.cw = lvl.cw; N.anc = anc[i];

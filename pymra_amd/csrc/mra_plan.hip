@@ -209,7 +209,7 @@ static void fill_knot_arrays(mra_plan* pl);
 
 // Workgroups of the full row cascade when it stages all its levels at once (ft_wg0_leaf / ft_wgn_leaf; tile numbers as in ft_row0,
 // leaves in order): one per leaf ... or one per family of sibling leaves (same parent = same operand image on every level, staged
-// once for all of them) when cascade_group_siblings holds - the cost model of build_static or MRA_OPT_CASCADE_GROUP.
+// once for all of them) when cascade_group_siblings holds - the cost model of siblings_share_workgroup or MRA_OPT_CASCADE_GROUP.
 static void build_leaf_workgroups(mra_plan* pl) {
     std::vector<long> wg0;
     std::vector<int> wgn;
@@ -226,9 +226,24 @@ static void build_leaf_workgroups(mra_plan* pl) {
 }
 
 // ------------------------------------------------------------------------------------------------
-static void build_static(mra_plan* pl) {
-    PlanTrace tr("build_static");
-    ArenaScope arena(&pl->arena);
+//  plan construction, part one: what does not depend on the observations.  build_static, at the end of this section, calls the steps
+//  in order; the order of the allocations and uploads is part of the result (it is the layout of the descriptor arena).
+// ------------------------------------------------------------------------------------------------
+// slots of a node's non-leaf ancestors, by level (and of the node itself unless it is a leaf); 0 at the levels below it
+static void chain_of(const mra_plan* pl, int node, int* out) {
+    for (int k = 0; k < 8; ++k) out[k] = 0;
+    for (int i = node; i >= 0; i = pl->parent[i])
+        if (!pl->leaf[i]) out[pl->node_level[i]] = pl->node_slot[i];
+}
+
+static int device_cu_count(const mra_plan* pl) {
+    hipDeviceProp_t prop;
+    if (!g_dry && hipGetDeviceProperties(&prop, pl->device) == hipSuccess && prop.multiProcessorCount > 0) return prop.multiProcessorCount;
+    return 256;
+}
+
+// column layout of W, per-node level and ancestor ranks; the checks of the topology
+static void static_layout_and_checks(mra_plan* pl) {
     const int L = pl->n_levels;
     pl->Ka = 0;
     for (int m = 0; m < L; ++m) {
@@ -260,8 +275,10 @@ static void build_static(mra_plan* pl) {
         const long rk = pl->knot_ptr[i + 1] - pl->knot_ptr[i];
         if (!pl->leaf[i] && (rk > pl->cw[m] || rk <= 0)) throw MraError(MRA_ERR_INVALID, "non-leaf rank must be in 1..cw[level]");
     }
+}
 
-    // device arrays shared by everything
+// device arrays shared by everything
+static void alloc_shared_arrays(mra_plan* pl) {
     pl->X.alloc((size_t)pl->P * pl->d);
     pl->y.alloc(pl->P);
     pl->W.alloc((size_t)pl->P * pl->ldw);
@@ -275,33 +292,43 @@ static void build_static(mra_plan* pl) {
     HIP_TRY(mraMemset(pl->var.p, 0, pl->var.n * sizeof(double)));
     HIP_TRY(mraMemset(pl->dnode.p, 0, pl->dnode.n * sizeof(double)));
     pl->knots_dev.alloc((size_t)std::max<long>(pl->knot_ptr.back(), 1));       // contents: fill_knot_arrays
-    tr.mark("checks, allocations, memsets");
+}
 
-    // knot index arrays for the gather side of the prior GEMM (padded to cw with -1): offsets here, contents in fill_knot_arrays
+// The tree's shape, decided once.  shape_regular: every leaf sits on the last level, every other level holds non-leaf nodes only.
+// regular (the one-kernel cascades): also one block width of 1, 2 or 4 tiles on at most 8 non-leaf levels, within the cascades'
+// register budget.  regular_hi: 5 - 8 non-leaf levels of 64-wide blocks, too many tiles per row for those.  lowrank_parent: the
+// fronts of the leaves' parents are too large for the register-resident k_parent_front, only their panels are kept.
+static void classify_shape(mra_plan* pl) {
+    const int L = pl->n_levels, NL = L - 1;
+    bool last_only = true;
+    for (int m = 0; m < L && last_only; ++m)
+        for (long i = pl->level_ptr[m]; i < pl->level_ptr[m + 1] && last_only; ++i) if ((pl->leaf[i] != 0) != (m == L - 1)) last_only = false;
+    bool uniform = true;
+    for (int m = 0; m < NL; ++m) if (pl->cw[m] != pl->cw[0]) uniform = false;
+    const int cwt = pl->cw[0] / 16;
+    pl->shape_regular = L >= 2 && last_only;
+    pl->lowrank_parent = L >= 3 && last_only && pl->nf[L - 2] > 256 && pl->cw[L - 2] <= 7 * 16 && !getenv("MRA_NO_LOWRANK_PARENT");
+    pl->regular = pl->shape_regular && NL <= 8 && uniform && (cwt == 1 || cwt == 2 || cwt == 4) && cwt * NL <= 16;
+    pl->regular_hi = !pl->regular && pl->shape_regular && NL >= 5 && NL <= 8 && uniform && pl->cw[0] == 64;
+    if (pl->shape_regular) pl->NL = NL;
+    if (pl->regular || pl->regular_hi) pl->CWT = cwt;
+}
+
+// knot index arrays for the gather side of the prior GEMM (padded to cw with -1: offsets here, contents in fill_knot_arrays) and the
+// levels' factor and front buffers
+static void alloc_level_buffers(mra_plan* pl) {
+    const int L = pl->n_levels;
     pl->knot_idx_off.assign(pl->n_nodes, -1);
-    {
-        long tot = 0;
-        for (int i = 0; i < pl->n_nodes; ++i) {
-            if (pl->leaf[i]) continue;
-            pl->knot_idx_off[i] = tot;
-            tot += pl->cw[pl->node_level[i]];
-        }
-        pl->knot_idx.alloc((size_t)std::max<long>(tot, 1));
+    long tot = 0;
+    for (int i = 0; i < pl->n_nodes; ++i) {
+        if (pl->leaf[i]) continue;
+        pl->knot_idx_off[i] = tot;
+        tot += pl->cw[pl->node_level[i]];
     }
-
-    // per level buffers + static descriptors
+    pl->knot_idx.alloc((size_t)std::max<long>(tot, 1));
     pl->lev.clear();
     pl->lev.resize(L);
     pl->node_slot.assign(pl->n_nodes, -1);
-    {
-        // shape: every leaf on the last level, every other level non-leaf only (also decided again below for the fused paths)
-        bool ok = L >= 3;
-        for (int m = 0; m < L - 1 && ok; ++m)
-            for (long i = pl->level_ptr[m]; i < pl->level_ptr[m + 1] && ok; ++i) if (pl->leaf[i]) ok = false;
-        for (long i = pl->level_ptr[L - 1]; i < pl->level_ptr[L] && ok; ++i) if (!pl->leaf[i]) ok = false;
-        // fronts of the leaves' parents too large for the register-resident k_parent_front: keep their panels only
-        pl->lowrank_parent = ok && pl->nf[L - 2] > 256 && pl->cw[L - 2] <= 7 * 16 && !getenv("MRA_NO_LOWRANK_PARENT");
-    }
     for (int m = 0; m < L; ++m) {
         LevelData& lv = pl->lev[m];
         lv.cw = pl->cw[m]; lv.cwt = lv.cw / 16; lv.c0 = pl->coff[m]; lv.a0 = pl->asuf[m];
@@ -318,365 +345,347 @@ static void build_static(mra_plan* pl) {
         lv.F.alloc(nn * (size_t)lv.nf * lv.ldf + 16);
         lv.invF.alloc(nn * (size_t)lv.cwt * 256);
     }
-    tr.mark("knot_idx, level buffers");
-    // leaves
+}
+
+// leaf numbering and the leaves' Schur blocks Gt
+// (row_leaf - padded row -> leaf, 4 bytes per row - is read by two kernels of the general path only: built on first use, ensure_row_leaf)
+static void build_leaf_maps(mra_plan* pl) {
     pl->leaf_nodes.clear();
     pl->leaf_slot.assign(pl->n_nodes, -1);
     for (int i = 0; i < pl->n_nodes; ++i)
         if (pl->leaf[i]) { pl->leaf_slot[i] = (int)pl->leaf_nodes.size(); pl->leaf_nodes.push_back(i); }
-    // (row_leaf - padded row -> leaf, 4 bytes per row - is read by two kernels of the general path only: built on first use, ensure_row_leaf)
-    // Gt of the leaves
     pl->leaf_goff.assign(pl->leaf_nodes.size() + 1, 0);
     for (size_t t = 0; t < pl->leaf_nodes.size(); ++t) {
         const int na = pl->na[pl->node_level[pl->leaf_nodes[t]]];
         pl->leaf_goff[t + 1] = pl->leaf_goff[t] + (long)na * na;
     }
-    {
-        const int Lq = pl->n_levels;
-        bool ok = Lq >= 2;
-        for (int m = 0; m < Lq - 1 && ok; ++m)
-            for (long i = pl->level_ptr[m]; i < pl->level_ptr[m + 1] && ok; ++i) if (pl->leaf[i]) ok = false;
-        for (long i = pl->level_ptr[Lq - 1]; i < pl->level_ptr[Lq] && ok; ++i) if (!pl->leaf[i]) ok = false;
-        pl->shape_regular = ok;
-        if (ok) pl->NL = Lq - 1;
-    }
     // shape-regular trees build the leaves' parents straight from the children's Ut blocks (segmented SYRK),
     // so the per-leaf Schur blocks Gt (146 GB at 2048^2, M=8, r0=64) are only allocated on demand (ensure_gt)
     if (!pl->shape_regular) pl->Gt.alloc(pl->leaf_goff.back());
+}
 
+// one-launch prior of level m (blocks <= 64 wide: four column tiles in registers): the knots' residual block of every node, and the
+// level's residual problems cut into blocks of rows with the row solve attached
+static void build_prior_level(mra_plan* pl, int m, const std::vector<GemmProb>& resid) {
+    LevelData& lv = pl->lev[m];
+    const size_t nn = lv.nodes.size();
+    const int Kanc = pl->Ka - lv.a0;
+    lv.prior_level_ok = lv.cw <= 64 && lv.cw % 16 == 0;
+    lv.fl_knot_resid = Work();
+    if (!lv.prior_level_ok) return;
+    std::vector<GemmProb> kn(nn), fz;
+    const long blk = 512;                            // rows per workgroup: four passes of 4 waves x 2 row tiles
+    for (size_t s = 0; s < nn; ++s) {
+        const int i = lv.nodes[s];
+        const long r0 = pl->row0[i], nr = pl->row1[i] - r0;
+        const int* kix = pl->knot_idx.p + pl->knot_idx_off[i];
+        GemmProb c{};
+        c.A = pl->W.p + lv.a0; c.lda = pl->ldw; c.idxA = kix; c.B = c.A; c.ldb = pl->ldw; c.idxB = kix;
+        c.C = lv.Lp_of(s); c.ldc = lv.cw; c.XA = pl->X.p; c.XB = pl->X.p;
+        c.M = lv.cw; c.N = lv.cw; c.K = Kanc; c.lower = 0; c.sym_diag = 1; c.diag_add = 0.0;
+        kn[s] = c;
+        const double rkt = (double)(pl->knot_ptr[i + 1] - pl->knot_ptr[i]), anct = (double)pl->anc_rank[i];
+        lv.fl_knot_resid += Work(2.0 * rkt * rkt * anct, 2.0 * lv.cw * lv.cw * Kanc, 8.0 * (rkt * (Kanc + pl->d) + (double)lv.cw * lv.cw));
+        for (long b0 = 0; b0 < nr; b0 += blk) {
+            GemmProb g = resid[s];
+            g.A += b0 * pl->ldw; g.C += b0 * pl->ldw; g.XA += b0 * pl->d;
+            g.M = (int)std::min(blk, nr - b0);
+            g.solveL = lv.Lp_of(s); g.solveI = lv.invP_of(s); g.var = pl->var.p + r0 + b0;
+            fz.push_back(g);
+        }
+    }
+    lv.gKnotResid.upload(kn); lv.gResidFused.upload(fz);
+}
+
+// descriptors of level m's nodes: prior (residual, kInv, Cholesky, row solve), front (assembly, partial Cholesky, Schur complement)
+// and predictive update; the nodes' children are appended to `kids` (uploaded as one array behind the last level)
+static void build_level_descriptors(mra_plan* pl, int m, std::vector<AsmChild>& kids) {
+    LevelData& lv = pl->lev[m];
+    const size_t nn = lv.nodes.size();
+    if (!nn) return;
+    std::vector<GemmProb> resid(nn), schur(nn), upd(nn);
+    std::vector<KinvProb> kinv(nn);
+    std::vector<PanelProb> pch(nn), fch(nn);
+    std::vector<TrsmNode> tpr(nn), tpo(nn);
+    std::vector<Trsm2Prob> t2pr(nn), t2po(nn);
+    std::vector<AsmProb> as(nn);
+    std::vector<FrontProb> fr(nn);
+    const int Kanc = pl->Ka - lv.a0;
+    for (size_t s = 0; s < nn; ++s) {
+        const int i = lv.nodes[s];
+        const long r0 = pl->row0[i], nr = pl->row1[i] - r0;
+        lv.max_rows = std::max(lv.max_rows, nr);
+        const long rk = pl->knot_ptr[i + 1] - pl->knot_ptr[i];
+        double *Lp = lv.Lp_of(s), *invP = lv.invP_of(s), *F = lv.F_of(s), *invF = lv.invF_of(s);
+        double* Wown = pl->W.p + r0 * pl->ldw + lv.c0;       // the node's rows, its own columns
+        GemmProb g{};
+        g.A = pl->W.p + r0 * pl->ldw + lv.a0; g.lda = pl->ldw;
+        g.B = pl->W.p + lv.a0; g.ldb = pl->ldw; g.idxB = pl->knot_idx.p + pl->knot_idx_off[i];
+        g.C = Wown; g.ldc = pl->ldw;
+        g.XA = pl->X.p + r0 * pl->d; g.XB = pl->X.p;
+        g.M = (int)nr; g.N = lv.cw; g.K = Kanc; g.lower = 0;
+        resid[s] = g;
+        const double rkt = (double)rk, anct = (double)pl->anc_rank[i], nat = anct + 1.0;      // true rank, true ancestor columns, + y
+        lv.fl_resid += Work(2.0 * nr * rkt * anct, 2.0 * nr * lv.cw * Kanc, 8.0 * nr * (Kanc + lv.cw + pl->d));
+        kinv[s] = KinvProb{Lp, pl->knots_dev.p + pl->knot_ptr[i], (int)rk, lv.cw};
+        pch[s] = PanelProb{Lp, invP, lv.cw, lv.cwt, lv.cwt, i};
+        lv.fl_pchol += Work(rkt * rkt * rkt / 3.0, (double)lv.cw * lv.cw * lv.cw / 3.0, 8.0 * 2 * lv.cw * lv.cw);
+        tpr[s] = TrsmNode{Lp, invP, lv.cw, lv.cwt};
+        tpo[s] = TrsmNode{F, invF, lv.ldf, lv.cwt};
+        lv.fl_trsm += Work((double)nr * rkt * rkt, (double)nr * lv.cw * lv.cw, 8.0 * 2 * nr * lv.cw);
+        // (var -= |W^m[x]|^2 rides on the row solve: the prior variance of the level-by-level path, see k_init_yblock)
+        t2pr[s] = Trsm2Prob{Lp, invP, Wown, pl->var.p + r0, lv.cw, pl->ldw, lv.cwt, (int)(nr / 16), 0, -1.0, nullptr, nullptr, 0, 0};
+        t2po[s] = Trsm2Prob{F, invF, Wown, pl->var.p + r0, lv.ldf, pl->ldw, lv.cwt, (int)(nr / 16), 0, 1.0, nullptr, nullptr, 0, 0};
+        lv.max_tiles = std::max(lv.max_tiles, nr / 16);
+        fch[s] = PanelProb{F, invF, lv.ldf, lv.nf / 16, lv.cwt, i};
+        lv.fl_fchol += Work(rkt * rkt * rkt / 3.0 + nat * rkt * rkt, (double)lv.cw * lv.cw * lv.cw / 3.0 + (double)lv.na * lv.cw * lv.cw,
+                            8.0 * (2.5 * lv.nf * (lv.nf + 1) / 2));      // four children's Schur blocks in (lower halves; fewer for ragged trees), the front out
+        GemmProb sc{};
+        sc.A = F + (size_t)lv.cw * lv.ldf; sc.lda = lv.ldf; sc.B = sc.A; sc.ldb = lv.ldf;
+        sc.C = lv.panel_only ? nullptr : F + (size_t)lv.cw * lv.nf + lv.cw; sc.ldc = lv.nf;      // panel_only: no Schur block is ever formed
+        sc.M = lv.na; sc.N = lv.na; sc.K = lv.cw; sc.lower = 1;
+        schur[s] = sc;
+        lv.fl_schur += Work(nat * nat * rkt, (double)lv.na * lv.na * lv.cw, 0.0);
+        GemmProb u{};
+        u.A = Wown; u.lda = pl->ldw;
+        u.B = F + (size_t)lv.cw * lv.ldf; u.ldb = lv.ldf;
+        u.C = pl->W.p + r0 * pl->ldw + lv.a0; u.ldc = pl->ldw;
+        u.M = (int)nr; u.N = lv.na; u.K = lv.cw; u.lower = 0;
+        upd[s] = u;
+        lv.fl_update += Work(2.0 * nr * nat * rkt, 2.0 * nr * lv.na * lv.cw, 8.0 * 2 * nr * lv.na);
+        AsmProb a{};
+        a.F = F; a.nf = lv.nf; a.cw = lv.cw; a.child0 = (int)kids.size();
+        a.nchild = pl->child_ptr[i + 1] - pl->child_ptr[i]; a.add_identity = 1;
+        for (int c = pl->child_ptr[i]; c < pl->child_ptr[i + 1]; ++c) {
+            const int ch = pl->child_list[c];
+            if (pl->node_level[ch] != m + 1) throw MraError(MRA_ERR_INVALID, "child must be one level below its parent");
+            AsmChild k{};
+            pl->kid_leaf.push_back(pl->leaf[ch] ? pl->leaf_slot[ch] : -1);
+            if (pl->leaf[ch]) { k.G = pl->Gt.p ? pl->Gt.p + pl->leaf_goff[pl->leaf_slot[ch]] : nullptr; k.ld = pl->na[m + 1]; }
+            else {
+                const LevelData& cl = pl->lev[m + 1];
+                // (children whose fronts are kept as panels have no Schur block: their parents are built by the signed SYRK)
+                k.G = cl.panel_only ? nullptr : cl.F_of(pl->node_slot[ch]) + (size_t)cl.cw * cl.nf + cl.cw;
+                k.ld = cl.nf;
+            }
+            if (pl->na[m + 1] != lv.nf) throw MraError(MRA_ERR_INVALID, "front size mismatch");
+            kids.push_back(k);
+        }
+        as[s] = a;
+        fr[s] = FrontProb{F, invF, lv.nf, lv.cwt, i, a.child0, a.nchild};
+    }
+    const long nt = lv.nf / 16;
+    const size_t full = (size_t)(nt * (nt + 1) / 2 + lv.cwt) * FT_SZ * sizeof(double);
+    const size_t panel = (size_t)(lv.cwt * nt - lv.cwt * (lv.cwt - 1) / 2 + lv.cwt) * FT_SZ * sizeof(double);
+    lv.front_mode = full <= 160 * 1024 ? 2 : (panel <= 160 * 1024 ? 1 : 0);
+    if (lv.panel_only) lv.front_mode = 0;
+    lv.front_lds = lv.front_mode == 2 ? full : panel;
+    lv.gFront.upload(fr);
+    build_prior_level(pl, m, resid);
+    lv.hResid = resid;
+    lv.gResid.upload(resid); lv.gSchur.upload(schur); lv.gUpdate.upload(upd); lv.gKinv.upload(kinv);
+    lv.gPriorChol.upload(pch); lv.gFrontChol.upload(fch); lv.gTrsmPrior.upload(tpr); lv.gTrsmPost.upload(tpo);
+    lv.gAsm.upload(as);
+    lv.gTrsm2Prior.upload(t2pr); lv.gTrsm2Post.upload(t2po);
+    // (tile_node / tile_row0 - one entry per row tile of the level - serve the row solve of blocks wider than 192 only: ensure_tile_lists)
+}
+
+// deep 64-wide trees: row tiles of the leaves with their ancestor chains; one workgroup per leaf (<= 4 tiles) for k_predict_hi, groups
+// of eight consecutive tiles below one level-(NL-5) node for the coarse cascade
+static void build_hi_tiles(mra_plan* pl) {
+    std::vector<long> r0s, wg0, wg0_8;
+    std::vector<int> chains, wgn, wgn_8, wgl;
+    const int nlo = pl->NL - 4;
+    int prev_coarse = -1;
+    for (size_t t = 0; t < pl->leaf_nodes.size(); ++t) {
+        const int i = pl->leaf_nodes[t];
+        int ch[8];
+        chain_of(pl, i, ch);
+        const int coarse = ch[nlo - 1];                          // slot of the deepest coarse level: same slot = same coarse chain
+        for (long p = pl->row0[i]; p < pl->row1[i]; p += 16) {
+            const long k = (p - pl->row0[i]) / 16;
+            if (k % 4 == 0) { wg0.push_back((long)r0s.size()); wgn.push_back((int)std::min<long>(4, (pl->row1[i] - p) / 16)); wgl.push_back((int)t); }
+            if (wgn_8.empty() || wgn_8.back() == 8 || coarse != prev_coarse) { wg0_8.push_back((long)r0s.size()); wgn_8.push_back(0); }
+            ++wgn_8.back();
+            prev_coarse = coarse;
+            r0s.push_back(p);
+            for (int k2 = 0; k2 < 8; ++k2) chains.push_back(ch[k2]);
+        }
+    }
+    pl->ft_row0.upload(r0s); pl->ft_chain.upload(chains);
+    pl->n_ftiles = (long)r0s.size();
+    pl->ft_wg0.upload(wg0); pl->ft_wgn.upload(wgn); pl->n_fwg = (long)wg0.size();
+    pl->hi_wgleaf.upload(wgl);
+    pl->hi_wg0_8.upload(wg0_8); pl->hi_wgn_8.upload(wgn_8); pl->n_hi_wg8 = (long)wg0_8.size();
+}
+
+// regular trees, per non-leaf level: the knot pass's buffers, knot row tiles (with chains and workgroups) and kInv products
+static void build_fused_levels(mra_plan* pl) {
+    const int cw = pl->cw[0];
+    pl->fl.clear();
+    pl->fl.resize(pl->NL);
+    for (int m = 0; m < pl->NL; ++m) {
+        mra_plan::FusedLevel& f = pl->fl[m];
+        const LevelData& lv = pl->lev[m];
+        const size_t nn = lv.nodes.size();
+        f.kx.alloc(nn * (size_t)cw * pl->d);
+        f.Wk.alloc(std::max<size_t>(nn * (size_t)cw * (m * cw), 1));
+        std::vector<int> kv(nn * (size_t)cw), rows, chain, knot0, wgn;
+        std::vector<long> wg0;
+        for (size_t sl = 0; sl < nn; ++sl) {
+            const int i = lv.nodes[sl];
+            const long rk = pl->knot_ptr[i + 1] - pl->knot_ptr[i];
+            for (int c = 0; c < cw; ++c) kv[sl * cw + c] = c < rk ? 1 : 0;
+            int ch[8];
+            chain_of(pl, i, ch);
+            // one workgroup per family of siblings (same ancestor chain: the staged operands are shared),
+            // as long as it stays within 8 row tiles (one per wave on the level-by-level staging path)
+            // (only on levels with many nodes, where workgroups run in several rounds per CU: on small levels
+            // - the levels of a sharded rank - the longer per-workgroup chain costs more than it saves)
+            const bool same_family = nn >= 512 && sl > 0 && pl->parent[i] >= 0 && pl->parent[i] == pl->parent[lv.nodes[sl - 1]] &&
+                                     !wgn.empty() && wgn.back() + cw / 16 <= 8;
+            if (same_family) wgn.back() += cw / 16;
+            else { wg0.push_back((long)knot0.size()); wgn.push_back(cw / 16); }
+            for (int tt = 0; tt < cw / 16; ++tt) {
+                for (int r = 0; r < 16; ++r) rows.push_back(-1);          // contents: fill_knot_arrays
+                for (int k = 0; k < 8; ++k) chain.push_back(ch[k]);
+                knot0.push_back(tt * 16);
+            }
+        }
+        f.kvalid.upload(kv); f.kt_rows.upload(rows); f.kt_chain.upload(chain); f.kt_knot0.upload(knot0);
+        f.n_ktiles = (long)knot0.size();
+        f.kt_wg0.upload(wg0); f.kt_wgn.upload(wgn); f.n_kwg = (long)wg0.size();
+        f.k_threads = 256;
+        for (int v : wgn) if (v > 4) f.k_threads = 512;
+        // kInv of every node of the level: kernel(knots, knots) - Wk Wk^T as one batched COV product
+        std::vector<GemmProb> gk(nn);
+        for (size_t sl = 0; sl < nn; ++sl) {
+            GemmProb g{};
+            g.A = f.Wk.p + sl * (size_t)cw * (m * cw); g.lda = m * cw; g.B = g.A; g.ldb = m * cw;
+            g.C = lv.Lp_of(sl); g.ldc = cw;
+            g.XA = f.kx.p + sl * (size_t)cw * pl->d; g.XB = g.XA;
+            g.M = cw; g.N = cw; g.K = m * cw; g.lower = 0;
+            gk[sl] = g;
+        }
+        f.gKinv.upload(gk);
+    }
+}
+
+// k_knot_chain: one workgroup per node of the last non-leaf level; owner of an upper node = first workgroup below it
+// (it recomputes every ancestor in every workgroup, so it only pays while one round of workgroups covers the
+// level: the chain covers levels 0 .. kc_levels-1, the deepest level with at most one workgroup per CU; deeper
+// levels - many nodes, throughput-bound - keep their per-level launches)
+static void build_knot_chain(mra_plan* pl, int ncu) {
+    int nlv = 1;
+    while (nlv < pl->NL && (long)pl->lev[nlv].nodes.size() <= ncu) ++nlv;
+    pl->kc_levels = nlv;
+    const int cwt = pl->CWT;
+    const LevelData& lb = pl->lev[nlv - 1];
+    std::vector<int> kch(lb.nodes.size() * 8, 0);
+    std::vector<std::vector<int>> own(nlv);
+    for (int m = 0; m < nlv; ++m) own[m].assign(pl->lev[m].nodes.size(), -1);
+    for (size_t b = 0; b < lb.nodes.size(); ++b) {
+        int* ch = kch.data() + b * 8;
+        chain_of(pl, lb.nodes[b], ch);
+        for (int m = 0; m < nlv; ++m) if (own[m][ch[m]] < 0) own[m][ch[m]] = (int)b;
+    }
+    pl->kc_chain.upload(kch);
+    pl->kc_chain_host = kch;
+    std::vector<int> mask(lb.nodes.size(), 0);
+    for (size_t b = 0; b < lb.nodes.size(); ++b)
+        for (int m = 0; m < nlv; ++m) if (own[m][kch[b * 8 + m]] == (int)b) mask[b] |= 1 << m;
+    pl->kc_ownmask.upload(mask);
+    pl->kc_knots.alloc(lb.nodes.size() * (size_t)nlv * cwt * 16 * (pl->d + 1));        // filled by mra_plan_set_locs
+    const long off = (long)cwt * cwt * ((nlv - 1) * (nlv - 2) / 2) + (long)(nlv - 1) * (cwt * (cwt - 1) / 2 + cwt);
+    pl->knot_chain_lds = (size_t)off * 2048 + (size_t)(cwt * (cwt + 1) / 2 + cwt) * FT_SZ * sizeof(double)
+                         + (size_t)nlv * cwt * 16 * (pl->d + 1) * sizeof(double);    // + the chain's knots (coordinates, real/phantom flags)
+    pl->knot_chain_ok = pl->knot_chain_lds <= 160 * 1024;
+}
+
+// The full row cascade, all levels staged at once: one workgroup (8 waves, the whole LDS) per leaf or per family of sibling leaves?
+// Rounds of workgroups over the CUs times [staging the operand image (~5 us, exposed: one workgroup per CU) + rounds of 8 row tiles
+// (~32 us each)].  Measured on shards of C3: 256 families on 256 CUs = one round of 64 tiles (261 us) against four rounds of 16
+// (316 us); 128 families leave half the CUs idle (261 against 158 us).  (MRA_OPT_CASCADE_GROUP overrides the verdict.)
+static bool siblings_share_workgroup(const mra_plan* pl, int ncu) {
+    size_t nparents = 0;
+    long ntiles_all = 0;
+    for (size_t t = 0; t < pl->leaf_nodes.size(); ++t) {
+        if (t == 0 || pl->parent[pl->leaf_nodes[t]] != pl->parent[pl->leaf_nodes[t - 1]]) ++nparents;
+        ntiles_all += (pl->row1[pl->leaf_nodes[t]] - pl->row0[pl->leaf_nodes[t]]) / 16;
+    }
+    const size_t nl_ = std::max<size_t>(1, pl->leaf_nodes.size()), np_ = std::max<size_t>(1, nparents);
+    const double t_leaf = std::ceil((double)ntiles_all / nl_ / 8.0), t_fam = std::ceil((double)ntiles_all / np_ / 8.0);
+    const double cost_leaf = std::ceil((double)nl_ / ncu) * (5.0 + 32.0 * t_leaf), cost_fam = std::ceil((double)np_ / ncu) * (5.0 + 32.0 * t_fam);
+    return cost_fam < cost_leaf;
+}
+
+// regular trees: the row tiles of the leaves with their chains, the cascades' workgroups (in tile order, and dealt to the XCDs for
+// the predictive cascade), the cascades' LDS sizes
+static void build_cascade_tiles(mra_plan* pl) {
+    std::vector<long> r0s, fwg0;
+    std::vector<int> chains, fwgn, tleaf;
+    for (size_t t = 0; t < pl->leaf_nodes.size(); ++t) {
+        const int i = pl->leaf_nodes[t];
+        int ch[8];
+        chain_of(pl, i, ch);
+        for (long p = pl->row0[i]; p < pl->row1[i]; p += 16) {
+            if (((p - pl->row0[i]) / 16) % pl->cascade_wpw == 0) {
+                fwg0.push_back((long)r0s.size());
+                fwgn.push_back((int)std::min<long>(pl->cascade_wpw, (pl->row1[i] - p) / 16));
+            }
+            r0s.push_back(p);
+            tleaf.push_back((int)t);
+            for (int k = 0; k < 8; ++k) chains.push_back(ch[k]);
+        }
+    }
+    pl->ft_row0.upload(r0s); pl->ft_chain.upload(chains); pl->ft_leaf.upload(tleaf);
+    pl->n_ftiles = (long)r0s.size();
+    pl->ft_wg0.upload(fwg0); pl->ft_wgn.upload(fwgn); pl->n_fwg = (long)fwg0.size();
+    // the same workgroups ordered for the predictive cascade: workgroup b runs on XCD b % 8, and the workgroups of
+    // one leaf all stream that leaf's Ut block, so they are dealt to one XCD (one L2) -- empty slots pad the lanes
+    std::vector<std::vector<size_t>> lane(8);
+    for (size_t g = 0; g < fwg0.size(); ++g) lane[(size_t)tleaf[(size_t)fwg0[g]] % 8].push_back(g);
+    size_t deep = 0;
+    for (const auto& l : lane) deep = std::max(deep, l.size());
+    std::vector<long> x0(deep * 8, 0);
+    std::vector<int> xn(deep * 8, 0), xl(deep * 8, 0);
+    for (size_t k = 0; k < deep; ++k)
+        for (size_t x = 0; x < 8; ++x)
+            if (k < lane[x].size()) { x0[k * 8 + x] = fwg0[lane[x][k]]; xn[k * 8 + x] = fwgn[lane[x][k]]; xl[k * 8 + x] = tleaf[(size_t)fwg0[lane[x][k]]]; }
+    pl->ft_wg0_x.upload(x0); pl->ft_wgn_x.upload(xn); pl->ft_wgleaf_x.upload(xl); pl->n_fwg_x = (long)x0.size();
+    const int cwt = pl->CWT, nl = pl->NL;
+    pl->cascade_lds = (size_t)(cwt * (nl - 1) * cwt + cwt * (cwt - 1) / 2 + cwt) * 2048;
+    pl->cascade_lds_all = (size_t)(cwt * cwt * (nl * (nl - 1) / 2) + nl * (cwt * (cwt - 1) / 2 + cwt)) * 2048;
+    pl->cascade_stage_all = pl->cascade_lds_all <= 160 * 1024;
+    build_leaf_workgroups(pl);
+}
+
+static void build_static(mra_plan* pl) {
+    PlanTrace tr("build_static");
+    ArenaScope arena(&pl->arena);
+    static_layout_and_checks(pl);
+    alloc_shared_arrays(pl);
+    tr.mark("checks, allocations, memsets");
+    classify_shape(pl);                     // (before the level buffers: the parents' fronts are sized by lowrank_parent)
+    alloc_level_buffers(pl);
+    tr.mark("knot_idx, level buffers");
+    build_leaf_maps(pl);
     tr.mark("leaf maps (row_leaf upload)");
-    // descriptors that do not depend on the observations
     std::vector<AsmChild> kids;
     pl->kid_leaf.clear();
-    for (int m = 0; m < L; ++m) {
-        LevelData& lv = pl->lev[m];
-        const size_t nn = lv.nodes.size();
-        if (!nn) continue;
-        std::vector<GemmProb> resid(nn), schur(nn), upd(nn);
-        std::vector<KinvProb> kinv(nn);
-        std::vector<PanelProb> pch(nn), fch(nn);
-        std::vector<TrsmNode> tpr(nn), tpo(nn);
-        std::vector<Trsm2Prob> t2pr(nn), t2po(nn);
-        std::vector<AsmProb> as(nn);
-        std::vector<FrontProb> fr(nn);
-        const int Kanc = pl->Ka - lv.a0;
-        for (size_t s = 0; s < nn; ++s) {
-            const int i = lv.nodes[s];
-            const long r0 = pl->row0[i], nr = pl->row1[i] - r0;
-            lv.max_rows = std::max(lv.max_rows, nr);
-            const long rk = pl->knot_ptr[i + 1] - pl->knot_ptr[i];
-            double* Lp = lv.Lp.p + s * (size_t)lv.cw * lv.cw;
-            double* F = lv.F.p + s * (size_t)lv.nf * lv.ldf;
-            GemmProb g{};
-            g.A = pl->W.p + r0 * pl->ldw + lv.a0; g.lda = pl->ldw;
-            g.B = pl->W.p + lv.a0; g.ldb = pl->ldw; g.idxB = pl->knot_idx.p + pl->knot_idx_off[i];
-            g.C = pl->W.p + r0 * pl->ldw + lv.c0; g.ldc = pl->ldw;
-            g.XA = pl->X.p + r0 * pl->d; g.XB = pl->X.p;
-            g.M = (int)nr; g.N = lv.cw; g.K = Kanc; g.lower = 0;
-            resid[s] = g;
-            const double rkt = (double)rk, anct = (double)pl->anc_rank[i], nat = anct + 1.0;      // true rank, true ancestor columns, + y
-            lv.fl_resid += Work(2.0 * nr * rkt * anct, 2.0 * nr * lv.cw * Kanc, 8.0 * nr * (Kanc + lv.cw + pl->d));
-            kinv[s] = KinvProb{Lp, pl->knots_dev.p + pl->knot_ptr[i], (int)rk, lv.cw};
-            pch[s] = PanelProb{Lp, lv.invP.p + s * (size_t)lv.cwt * 256, lv.cw, lv.cwt, lv.cwt, i};
-            lv.fl_pchol += Work(rkt * rkt * rkt / 3.0, (double)lv.cw * lv.cw * lv.cw / 3.0, 8.0 * 2 * lv.cw * lv.cw);
-            tpr[s] = TrsmNode{Lp, lv.invP.p + s * (size_t)lv.cwt * 256, lv.cw, lv.cwt};
-            tpo[s] = TrsmNode{F, lv.invF.p + s * (size_t)lv.cwt * 256, lv.ldf, lv.cwt};
-            lv.fl_trsm += Work((double)nr * rkt * rkt, (double)nr * lv.cw * lv.cw, 8.0 * 2 * nr * lv.cw);
-            // (var -= |W^m[x]|^2 rides on the row solve: the prior variance of the level-by-level path, see k_init_yblock)
-            t2pr[s] = Trsm2Prob{Lp, lv.invP.p + s * (size_t)lv.cwt * 256, pl->W.p + r0 * pl->ldw + lv.c0, pl->var.p + r0, lv.cw, pl->ldw, lv.cwt, (int)(nr / 16), 0, -1.0, nullptr, nullptr, 0, 0};
-            t2po[s] = Trsm2Prob{F, lv.invF.p + s * (size_t)lv.cwt * 256, pl->W.p + r0 * pl->ldw + lv.c0, pl->var.p + r0, lv.ldf, pl->ldw, lv.cwt, (int)(nr / 16), 0, 1.0, nullptr, nullptr, 0, 0};
-            lv.max_tiles = std::max(lv.max_tiles, nr / 16);
-            fch[s] = PanelProb{F, lv.invF.p + s * (size_t)lv.cwt * 256, lv.ldf, lv.nf / 16, lv.cwt, i};
-            lv.fl_fchol += Work(rkt * rkt * rkt / 3.0 + nat * rkt * rkt, (double)lv.cw * lv.cw * lv.cw / 3.0 + (double)lv.na * lv.cw * lv.cw,
-                                8.0 * (2.5 * lv.nf * (lv.nf + 1) / 2));      // four children's Schur blocks in (lower halves; fewer for ragged trees), the front out
-            GemmProb sc{};
-            sc.A = F + (size_t)lv.cw * lv.ldf; sc.lda = lv.ldf; sc.B = sc.A; sc.ldb = lv.ldf;
-            sc.C = lv.panel_only ? nullptr : F + (size_t)lv.cw * lv.nf + lv.cw; sc.ldc = lv.nf;      // panel_only: no Schur block is ever formed
-            sc.M = lv.na; sc.N = lv.na; sc.K = lv.cw; sc.lower = 1;
-            schur[s] = sc;
-            lv.fl_schur += Work(nat * nat * rkt, (double)lv.na * lv.na * lv.cw, 0.0);
-            GemmProb u{};
-            u.A = pl->W.p + r0 * pl->ldw + lv.c0; u.lda = pl->ldw;
-            u.B = F + (size_t)lv.cw * lv.ldf; u.ldb = lv.ldf;
-            u.C = pl->W.p + r0 * pl->ldw + lv.a0; u.ldc = pl->ldw;
-            u.M = (int)nr; u.N = lv.na; u.K = lv.cw; u.lower = 0;
-            upd[s] = u;
-            lv.fl_update += Work(2.0 * nr * nat * rkt, 2.0 * nr * lv.na * lv.cw, 8.0 * 2 * nr * lv.na);
-            AsmProb a{};
-            a.F = F; a.nf = lv.nf; a.cw = lv.cw; a.child0 = (int)kids.size();
-            a.nchild = pl->child_ptr[i + 1] - pl->child_ptr[i]; a.add_identity = 1;
-            for (int c = pl->child_ptr[i]; c < pl->child_ptr[i + 1]; ++c) {
-                const int ch = pl->child_list[c];
-                if (pl->node_level[ch] != m + 1) throw MraError(MRA_ERR_INVALID, "child must be one level below its parent");
-                AsmChild k{};
-                pl->kid_leaf.push_back(pl->leaf[ch] ? pl->leaf_slot[ch] : -1);
-                if (pl->leaf[ch]) { k.G = pl->Gt.p ? pl->Gt.p + pl->leaf_goff[pl->leaf_slot[ch]] : nullptr; k.ld = pl->na[m + 1]; }
-                else {
-                    const LevelData& cl = pl->lev[m + 1];
-                    // (children whose fronts are kept as panels have no Schur block: their parents are built by the signed SYRK)
-                    k.G = cl.panel_only ? nullptr : cl.F.p + (size_t)pl->node_slot[ch] * cl.nf * cl.nf + (size_t)cl.cw * cl.nf + cl.cw;
-                    k.ld = cl.nf;
-                }
-                if (pl->na[m + 1] != lv.nf) throw MraError(MRA_ERR_INVALID, "front size mismatch");
-                kids.push_back(k);
-            }
-            as[s] = a;
-            fr[s] = FrontProb{F, lv.invF.p + s * (size_t)lv.cwt * 256, lv.nf, lv.cwt, i, a.child0, a.nchild};
-        }
-        {
-            const long nt = lv.nf / 16;
-            const size_t full = (size_t)(nt * (nt + 1) / 2 + lv.cwt) * FT_SZ * sizeof(double);
-            const size_t panel = (size_t)(lv.cwt * nt - lv.cwt * (lv.cwt - 1) / 2 + lv.cwt) * FT_SZ * sizeof(double);
-            lv.front_mode = full <= 160 * 1024 ? 2 : (panel <= 160 * 1024 ? 1 : 0);
-            if (lv.panel_only) lv.front_mode = 0;
-            lv.front_lds = lv.front_mode == 2 ? full : panel;
-            lv.gFront.upload(fr);
-        }
-        // one-launch prior of the level: blocks <= 64 wide (four column tiles in registers)
-        lv.prior_level_ok = lv.cw <= 64 && lv.cw % 16 == 0;
-        lv.fl_knot_resid = Work();
-        if (lv.prior_level_ok) {
-            std::vector<GemmProb> kn(nn), fz;
-            const long blk = 512;                            // rows per workgroup: four passes of 4 waves x 2 row tiles
-            for (size_t s = 0; s < nn; ++s) {
-                const int i = lv.nodes[s];
-                const long r0 = pl->row0[i], nr = pl->row1[i] - r0;
-                double* Lp = lv.Lp.p + s * (size_t)lv.cw * lv.cw;
-                const int* kix = pl->knot_idx.p + pl->knot_idx_off[i];
-                GemmProb c{};
-                c.A = pl->W.p + lv.a0; c.lda = pl->ldw; c.idxA = kix; c.B = c.A; c.ldb = pl->ldw; c.idxB = kix;
-                c.C = Lp; c.ldc = lv.cw; c.XA = pl->X.p; c.XB = pl->X.p;
-                c.M = lv.cw; c.N = lv.cw; c.K = Kanc; c.lower = 0; c.sym_diag = 1; c.diag_add = 0.0;
-                kn[s] = c;
-                const double rkt = (double)(pl->knot_ptr[i + 1] - pl->knot_ptr[i]), anct = (double)pl->anc_rank[i];
-                lv.fl_knot_resid += Work(2.0 * rkt * rkt * anct, 2.0 * lv.cw * lv.cw * Kanc, 8.0 * (rkt * (Kanc + pl->d) + (double)lv.cw * lv.cw));
-                for (long b0 = 0; b0 < nr; b0 += blk) {
-                    GemmProb g = resid[s];
-                    g.A += b0 * pl->ldw; g.C += b0 * pl->ldw; g.XA += b0 * pl->d;
-                    g.M = (int)std::min(blk, nr - b0);
-                    g.solveL = Lp; g.solveI = lv.invP.p + s * (size_t)lv.cwt * 256; g.var = pl->var.p + r0 + b0;
-                    fz.push_back(g);
-                }
-            }
-            lv.gKnotResid.upload(kn); lv.gResidFused.upload(fz);
-        }
-        lv.hResid = resid;
-        lv.gResid.upload(resid); lv.gSchur.upload(schur); lv.gUpdate.upload(upd); lv.gKinv.upload(kinv);
-        lv.gPriorChol.upload(pch); lv.gFrontChol.upload(fch); lv.gTrsmPrior.upload(tpr); lv.gTrsmPost.upload(tpo);
-        lv.gAsm.upload(as);
-        lv.gTrsm2Prior.upload(t2pr); lv.gTrsm2Post.upload(t2po);
-        // (tile_node / tile_row0 - one entry per row tile of the level - serve the row solve of blocks wider than 192 only: ensure_tile_lists)
-    }
+    for (int m = 0; m < pl->n_levels; ++m) build_level_descriptors(pl, m, kids);
     pl->asmKids.upload(kids);
     pl->hKids = kids;
     tr.mark("per-level descriptors");
-
-    // ---- fused path eligibility: uniform block width on all non-leaf levels, leaves only on the last level
-    pl->regular = false;
-    const int NL = L - 1;
-    if (NL >= 1 && NL <= 8) {
-        bool ok = true;
-        for (int m = 0; m < NL && ok; ++m) {
-            if (pl->cw[m] != pl->cw[0]) ok = false;
-            for (long i = pl->level_ptr[m]; i < pl->level_ptr[m + 1] && ok; ++i) if (pl->leaf[i]) ok = false;
-        }
-        for (long i = pl->level_ptr[NL]; i < pl->level_ptr[NL + 1] && ok; ++i) if (!pl->leaf[i]) ok = false;
-        const int cwt = pl->cw[0] / 16;
-        if (cwt != 1 && cwt != 2 && cwt != 4) ok = false;
-        if (cwt * NL > 16) ok = false;                       // register budget of the cascade kernels
-        if (ok) { pl->regular = true; pl->NL = NL; pl->CWT = cwt; }
-    }
-    pl->regular_hi = false;
-    if (!pl->regular && pl->shape_regular && NL >= 5 && NL <= 8) {
-        bool ok = true;
-        for (int m = 0; m < NL && ok; ++m) if (pl->cw[m] != 64) ok = false;
-        if (ok) {
-            pl->regular_hi = true; pl->NL = NL; pl->CWT = 4;
-            // row tiles of the leaves with their ancestor chains; one workgroup per leaf (<= 4 tiles) for k_predict_hi, groups of eight
-            // consecutive tiles below one level-(NL-5) node for the coarse cascade
-            std::vector<long> r0s, wg0, wg0_8;
-            std::vector<int> chains, wgn, wgn_8, wgl;
-            const int nlo = NL - 4;
-            int prev_coarse = -1;
-            for (size_t t = 0; t < pl->leaf_nodes.size(); ++t) {
-                const int i = pl->leaf_nodes[t];
-                int ch[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-                for (int a = pl->parent[i]; a >= 0; a = pl->parent[a]) ch[pl->node_level[a]] = pl->node_slot[a];
-                const int coarse = ch[nlo - 1];                          // slot of the deepest coarse level: same slot = same coarse chain
-                for (long p = pl->row0[i]; p < pl->row1[i]; p += 16) {
-                    const long k = (p - pl->row0[i]) / 16;
-                    if (k % 4 == 0) { wg0.push_back((long)r0s.size()); wgn.push_back((int)std::min<long>(4, (pl->row1[i] - p) / 16)); wgl.push_back((int)t); }
-                    if (wgn_8.empty() || wgn_8.back() == 8 || coarse != prev_coarse) { wg0_8.push_back((long)r0s.size()); wgn_8.push_back(0); }
-                    ++wgn_8.back();
-                    prev_coarse = coarse;
-                    r0s.push_back(p);
-                    for (int k2 = 0; k2 < 8; ++k2) chains.push_back(ch[k2]);
-                }
-            }
-            pl->ft_row0.upload(r0s); pl->ft_chain.upload(chains);
-            pl->n_ftiles = (long)r0s.size();
-            pl->ft_wg0.upload(wg0); pl->ft_wgn.upload(wgn); pl->n_fwg = (long)wg0.size();
-            pl->hi_wgleaf.upload(wgl);
-            pl->hi_wg0_8.upload(wg0_8); pl->hi_wgn_8.upload(wgn_8); pl->n_hi_wg8 = (long)wg0_8.size();
-        }
-    }
+    if (pl->regular_hi) build_hi_tiles(pl);
     if (pl->regular) {
-        const int cw = pl->cw[0];
-        pl->fl.clear();
-        pl->fl.resize(pl->NL);
-        auto chain_of = [&](int node, int* out) {            // slots of the ancestors (and the node itself)
-            for (int k = 0; k < 8; ++k) out[k] = 0;
-            int i = node;
-            while (i >= 0) {
-                if (!pl->leaf[i]) out[pl->node_level[i]] = pl->node_slot[i];
-                i = pl->parent[i];
-            }
-        };
-        for (int m = 0; m < pl->NL; ++m) {
-            mra_plan::FusedLevel& f = pl->fl[m];
-            const LevelData& lv = pl->lev[m];
-            const size_t nn = lv.nodes.size();
-            f.kx.alloc(nn * (size_t)cw * pl->d);
-            f.Wk.alloc(std::max<size_t>(nn * (size_t)cw * (m * cw), 1));
-            std::vector<int> kv(nn * (size_t)cw), rows, chain, knot0, wgn;
-            std::vector<long> wg0;
-            for (size_t sl = 0; sl < nn; ++sl) {
-                const int i = lv.nodes[sl];
-                const long rk = pl->knot_ptr[i + 1] - pl->knot_ptr[i];
-                for (int c = 0; c < cw; ++c) kv[sl * cw + c] = c < rk ? 1 : 0;
-                int ch[8];
-                chain_of(i, ch);
-                // one workgroup per family of siblings (same ancestor chain: the staged operands are shared),
-                // as long as it stays within 8 row tiles (one per wave on the level-by-level staging path)
-                // (only on levels with many nodes, where workgroups run in several rounds per CU: on small levels
-                // - the levels of a sharded rank - the longer per-workgroup chain costs more than it saves)
-                const bool same_family = nn >= 512 && sl > 0 && pl->parent[i] >= 0 && pl->parent[i] == pl->parent[lv.nodes[sl - 1]] &&
-                                         !wgn.empty() && wgn.back() + cw / 16 <= 8;
-                if (same_family) wgn.back() += cw / 16;
-                else { wg0.push_back((long)knot0.size()); wgn.push_back(cw / 16); }
-                for (int tt = 0; tt < cw / 16; ++tt) {
-                    for (int r = 0; r < 16; ++r) rows.push_back(-1);          // contents: fill_knot_arrays
-                    for (int k = 0; k < 8; ++k) chain.push_back(ch[k]);
-                    knot0.push_back(tt * 16);
-                }
-            }
-            f.kvalid.upload(kv); f.kt_rows.upload(rows); f.kt_chain.upload(chain); f.kt_knot0.upload(knot0);
-            f.n_ktiles = (long)knot0.size();
-            f.kt_wg0.upload(wg0); f.kt_wgn.upload(wgn); f.n_kwg = (long)wg0.size();
-            f.k_threads = 256;
-            for (int v : wgn) if (v > 4) f.k_threads = 512;
-            {
-                // kInv of every node of the level: kernel(knots, knots) - Wk Wk^T as one batched COV product
-                std::vector<GemmProb> gk(nn);
-                for (size_t sl = 0; sl < nn; ++sl) {
-                    GemmProb g{};
-                    g.A = f.Wk.p + sl * (size_t)cw * (m * cw); g.lda = m * cw; g.B = g.A; g.ldb = m * cw;
-                    g.C = pl->lev[m].Lp.p + sl * (size_t)cw * cw; g.ldc = cw;
-                    g.XA = f.kx.p + sl * (size_t)cw * pl->d; g.XB = g.XA;
-                    g.M = cw; g.N = cw; g.K = m * cw; g.lower = 0;
-                    gk[sl] = g;
-                }
-                f.gKinv.upload(gk);
-            }
-        }
-        {
-            // k_knot_chain: one workgroup per node of the last non-leaf level; owner of an upper node = first workgroup below it
-            // (it recomputes every ancestor in every workgroup, so it only pays while one round of workgroups covers the
-            // level: the chain covers levels 0 .. kc_levels-1, the deepest level with at most one workgroup per CU; deeper
-            // levels - many nodes, throughput-bound - keep their per-level launches)
-            int ncu = 256;
-            {
-                hipDeviceProp_t prop;
-                if (!g_dry && hipGetDeviceProperties(&prop, pl->device) == hipSuccess && prop.multiProcessorCount > 0) ncu = prop.multiProcessorCount;
-            }
-            pl->n_cu = ncu;
-            int nlv = 1;
-            while (nlv < pl->NL && (long)pl->lev[nlv].nodes.size() <= ncu) ++nlv;
-            pl->kc_levels = nlv;
-            const int cwt = pl->CWT;
-            const LevelData& lb = pl->lev[nlv - 1];
-            std::vector<int> kch(lb.nodes.size() * 8, 0);
-            std::vector<std::vector<int>> own(nlv);
-            for (int m = 0; m < nlv; ++m) own[m].assign(pl->lev[m].nodes.size(), -1);
-            for (size_t b = 0; b < lb.nodes.size(); ++b) {
-                int ch[8];
-                chain_of(lb.nodes[b], ch);
-                for (int k = 0; k < 8; ++k) kch[b * 8 + k] = ch[k];
-                for (int m = 0; m < nlv; ++m) if (own[m][ch[m]] < 0) own[m][ch[m]] = (int)b;
-            }
-            pl->kc_chain.upload(kch);
-            pl->kc_chain_host = kch;
-            std::vector<int> mask(lb.nodes.size(), 0);
-            for (size_t b = 0; b < lb.nodes.size(); ++b)
-                for (int m = 0; m < nlv; ++m) if (own[m][kch[b * 8 + m]] == (int)b) mask[b] |= 1 << m;
-            pl->kc_ownmask.upload(mask);
-            pl->kc_knots.alloc(lb.nodes.size() * (size_t)nlv * cwt * 16 * (pl->d + 1));        // filled by mra_plan_set_locs
-            const long off = (long)cwt * cwt * ((nlv - 1) * (nlv - 2) / 2) + (long)(nlv - 1) * (cwt * (cwt - 1) / 2 + cwt);
-            pl->knot_chain_lds = (size_t)off * 2048 + (size_t)(cwt * (cwt + 1) / 2 + cwt) * FT_SZ * sizeof(double)
-                                 + (size_t)nlv * cwt * 16 * (pl->d + 1) * sizeof(double);    // + the chain's knots (coordinates, real/phantom flags)
-            pl->knot_chain_ok = pl->knot_chain_lds <= 160 * 1024;
-        }
+        const int ncu = device_cu_count(pl);
+        pl->n_cu = ncu;                     // (regular trees only: route_for reads it on every path)
+        build_fused_levels(pl);
+        build_knot_chain(pl, ncu);
         tr.mark("fused levels, knot chain");
-        std::vector<long> r0s, fwg0;
-        std::vector<int> chains, fwgn, tleaf;
-        {
-            int ndev_cu = 256;
-            hipDeviceProp_t prop;
-            if (!g_dry && hipGetDeviceProperties(&prop, pl->device) == hipSuccess && prop.multiProcessorCount > 0) ndev_cu = prop.multiProcessorCount;
-            size_t nparents = 0;
-            long ntiles_all = 0;
-            for (size_t t = 0; t < pl->leaf_nodes.size(); ++t) {
-                if (t == 0 || pl->parent[pl->leaf_nodes[t]] != pl->parent[pl->leaf_nodes[t - 1]]) ++nparents;
-                ntiles_all += (pl->row1[pl->leaf_nodes[t]] - pl->row0[pl->leaf_nodes[t]]) / 16;
-            }
-            // one workgroup (8 waves, the whole LDS) per leaf or per family of sibling leaves: rounds of workgroups over the CUs times
-            // [staging the operand image (~5 us, exposed: one workgroup per CU) + rounds of 8 row tiles (~32 us each)].  Measured on
-            // shards of C3: 256 families on 256 CUs = one round of 64 tiles (261 us) against four rounds of 16 (316 us); 128 families
-            // leave half the CUs idle (261 against 158 us).
-            const size_t nl_ = std::max<size_t>(1, pl->leaf_nodes.size()), np_ = std::max<size_t>(1, nparents);
-            const double t_leaf = std::ceil((double)ntiles_all / nl_ / 8.0), t_fam = std::ceil((double)ntiles_all / np_ / 8.0);
-            const double cost_leaf = std::ceil((double)nl_ / ndev_cu) * (5.0 + 32.0 * t_leaf), cost_fam = std::ceil((double)np_ / ndev_cu) * (5.0 + 32.0 * t_fam);
-            pl->cascade_group_siblings = cost_fam < cost_leaf;      // (MRA_OPT_CASCADE_GROUP overrides it)
-        }
-        for (size_t t = 0; t < pl->leaf_nodes.size(); ++t) {
-            const int i = pl->leaf_nodes[t];
-            int ch[8];
-            chain_of(i, ch);
-            for (long p = pl->row0[i]; p < pl->row1[i]; p += 16) {
-                if (((p - pl->row0[i]) / 16) % pl->cascade_wpw == 0) {
-                    fwg0.push_back((long)r0s.size());
-                    fwgn.push_back((int)std::min<long>(pl->cascade_wpw, (pl->row1[i] - p) / 16));
-                }
-                r0s.push_back(p);
-                tleaf.push_back((int)t);
-                for (int k = 0; k < 8; ++k) chains.push_back(ch[k]);
-            }
-        }
-        pl->ft_row0.upload(r0s); pl->ft_chain.upload(chains); pl->ft_leaf.upload(tleaf);
-        pl->n_ftiles = (long)r0s.size();
-        pl->ft_wg0.upload(fwg0); pl->ft_wgn.upload(fwgn); pl->n_fwg = (long)fwg0.size();
-        {
-            // the same workgroups ordered for the predictive cascade: workgroup b runs on XCD b % 8, and the workgroups of
-            // one leaf all stream that leaf's Ut block, so they are dealt to one XCD (one L2) -- empty slots pad the lanes
-            std::vector<std::vector<size_t>> lane(8);
-            for (size_t g = 0; g < fwg0.size(); ++g) lane[(size_t)tleaf[(size_t)fwg0[g]] % 8].push_back(g);
-            size_t deep = 0;
-            for (const auto& l : lane) deep = std::max(deep, l.size());
-            std::vector<long> x0(deep * 8, 0);
-            std::vector<int> xn(deep * 8, 0), xl(deep * 8, 0);
-            for (size_t k = 0; k < deep; ++k)
-                for (size_t x = 0; x < 8; ++x)
-                    if (k < lane[x].size()) { x0[k * 8 + x] = fwg0[lane[x][k]]; xn[k * 8 + x] = fwgn[lane[x][k]]; xl[k * 8 + x] = tleaf[(size_t)fwg0[lane[x][k]]]; }
-            pl->ft_wg0_x.upload(x0); pl->ft_wgn_x.upload(xn); pl->ft_wgleaf_x.upload(xl); pl->n_fwg_x = (long)x0.size();
-        }
-        {
-            const int cwt = pl->CWT, mmax = pl->NL - 1;
-            pl->cascade_lds = (size_t)(cwt * mmax * cwt + cwt * (cwt - 1) / 2 + cwt) * 2048;
-            const int nl = pl->NL;
-            pl->cascade_lds_all = (size_t)(cwt * cwt * (nl * (nl - 1) / 2) + nl * (cwt * (cwt - 1) / 2 + cwt)) * 2048;
-            pl->cascade_stage_all = pl->cascade_lds_all <= 160 * 1024;
-            build_leaf_workgroups(pl);
-        }
+        pl->cascade_group_siblings = siblings_share_workgroup(pl, ncu);
+        build_cascade_tiles(pl);
         tr.mark("row tiles of the cascades");
     }
     arena.finish();
@@ -719,19 +728,30 @@ static void fill_knot_arrays(mra_plan* pl) {
     }
 }
 
-// leaf descriptors: depend on which rows are observed
-static void build_leaf(mra_plan* pl, const double* y) {
-    PlanTrace tr("build_leaf");
-    ArenaScope arena(&pl->arena);
+// ------------------------------------------------------------------------------------------------
+//  plan construction, part two: what depends on which rows are observed.  build_leaf, at the end of this section, runs on every
+//  set_obs (on a plan whose static part exists) and calls the steps in order; nothing is kept from one call to the next.
+// ------------------------------------------------------------------------------------------------
+// host copies of the per-leaf lists and descriptors, in leaf order, as they pass from step to step
+struct LeafDescs {
+    std::vector<int> nobs;                      // observed rows per leaf
+    std::vector<long> obs_off;                  // [leaf + 1] offset of the leaf's list in obs_idx (multiples of 16)
+    std::vector<LeafProb> lp;
+    std::vector<GemmProb> resid, resid_lik, syrk, upd;
+    std::vector<PanelProb> chol_full, chol_lik, chol_c;
+    std::vector<Trsm2Prob> trsm_full, trsm_lik;
+};
+
+// observed rows per leaf: counted and listed by a few threads over runs of leaves (one pass over y each); the panels' sizes
+static void build_obs_lists(mra_plan* pl, const double* y, LeafDescs& d) {
     const size_t nl = pl->leaf_nodes.size();
-    pl->cphantom_valid = false;
-    pl->slv.valid = false; pl->slv.built = false;      // mra_solve's descriptors point into the leaves' panels
     pl->leaf_nop.assign(nl, 0);
     pl->leaf_poff.assign(nl + 1, 0);
     pl->leaf_ioff.assign(nl + 1, 0);
-    // observed rows per leaf: counted and listed by a few threads over runs of leaves (one pass over y each)
-    std::vector<int> obs, opos(pl->P), nobs(nl, 0);
-    std::vector<long> obs_off(nl + 1, 0);
+    std::vector<int> obs, opos(pl->P);
+    std::vector<int>& nobs = d.nobs;
+    std::vector<long>& obs_off = d.obs_off;
+    nobs.assign(nl, 0); obs_off.assign(nl + 1, 0);
     const int64_t leaves_per_thread = std::max<int64_t>(1, (int64_t)(65536 * nl / std::max<long>(pl->P, 1)));
     parallel_rows((int64_t)nl, [&](int64_t a, int64_t b) {
         for (int64_t t = a; t < b; ++t) {
@@ -780,14 +800,15 @@ static void build_leaf(mra_plan* pl, const double* y) {
     pl->obs_off_host = obs_off; pl->lik_tiles_valid = false; pl->lik_general_valid = false;
     pl->y_finite_host.assign(pl->P, 0);
     for (long p2 = 0; p2 < pl->P; ++p2) pl->y_finite_host[p2] = std::isfinite(y[p2]) ? 1 : 0;
-    tr.mark("observation lists");
-    pl->panel.alloc(std::max<long>(pl->leaf_poff.back(), 1));
-    pl->leafInv.alloc(std::max<long>(pl->leaf_ioff.back(), 1));
-    tr.mark("panel allocation");
-    std::vector<LeafProb> lp(nl);
-    std::vector<GemmProb> gr(nl), gs(nl), gu(nl), grl(nl);
-    std::vector<PanelProb> pf(nl), pk(nl), pc(nl);
-    std::vector<Trsm2Prob> tf(nl), tk(nl);
+}
+
+// per leaf: residual (full and likelihood-only), factorisation, row solves, SYRK and update problems, with their work counts
+static void build_leaf_descriptors(mra_plan* pl, LeafDescs& d) {
+    const size_t nl = pl->leaf_nodes.size();
+    d.lp.resize(nl);
+    d.resid.resize(nl); d.syrk.resize(nl); d.upd.resize(nl); d.resid_lik.resize(nl);
+    d.chol_full.resize(nl); d.chol_lik.resize(nl); d.chol_c.resize(nl);
+    d.trsm_full.resize(nl); d.trsm_lik.resize(nl);
     pl->leaf_max_tiles_full = pl->leaf_max_tiles_lik = 0;
     pl->fl_leaf_resid = pl->fl_leaf_chol = pl->fl_leaf_chol_lik = pl->fl_leaf_syrk = pl->fl_leaf_update = pl->fl_leaf_c_only = Work();
     pl->by_leaf_ut = pl->by_leaf_tt = pl->by_leaf_c = 0;
@@ -797,37 +818,37 @@ static void build_leaf(mra_plan* pl, const double* y) {
         const int na = pl->na[m], a0 = pl->asuf[m], nop = pl->leaf_nop[t];
         const long r0 = pl->row0[i], nr = pl->row1[i] - r0;
         const int Kanc = pl->Ka - a0;
-        double* Pn = pl->panel.p + pl->leaf_poff[t];
+        double *Pn = leaf_C(pl, t), *Ut = leaf_Ut(pl, t), *V = leaf_V(pl, t);
         LeafProb q{};
-        q.Pn = Pn; q.obs = pl->obs_idx.p + obs_off[t]; q.row0 = r0; q.ld = nop; q.nrows = (int)nr;
+        q.Pn = Pn; q.obs = pl->obs_idx.p + d.obs_off[t]; q.row0 = r0; q.ld = nop; q.nrows = (int)nr;
         q.nop = nop; q.na = na; q.a0 = a0; q.node = i;
-        lp[t] = q;
+        d.lp[t] = q;
         GemmProb g{};
         g.A = pl->W.p + r0 * pl->ldw + a0; g.lda = pl->ldw;
         g.B = pl->W.p + a0; g.ldb = pl->ldw; g.idxB = q.obs;
-        g.C = Pn + (size_t)(nop + na) * nop; g.ldc = nop;
+        g.C = V; g.ldc = nop;
         g.XA = pl->X.p + r0 * pl->d; g.XB = pl->X.p;
         g.M = (int)nr; g.N = nop; g.K = Kanc; g.lower = 0;
         g.rowmap = pl->obs_pos.p + r0; g.C2 = Pn; g.diag_add = pl->R;
-        gr[t] = g;
+        d.resid[t] = g;
         {
             // likelihood-only runs need just C = v_m(o,o) + R I: both sides gathered through the observation list
             GemmProb c{};
             c.A = pl->W.p + a0; c.lda = pl->ldw; c.idxA = q.obs; c.B = c.A; c.ldb = pl->ldw; c.idxB = q.obs;
             c.C = Pn; c.ldc = nop; c.XA = pl->X.p; c.XB = pl->X.p;
             c.M = nop; c.N = nop; c.K = Kanc; c.lower = 1; c.sym_diag = 1; c.diag_add = pl->R;
-            grl[t] = c;
+            d.resid_lik[t] = c;
         }
-        const double no = (double)nobs[t], anct = (double)pl->anc_rank[i], nat = anct + 1.0;      // true sizes: observations, ancestor columns, + y
+        const double no = (double)d.nobs[t], anct = (double)pl->anc_rank[i], nat = anct + 1.0;      // true sizes: observations, ancestor columns, + y
         pl->by_leaf_ut += 8.0 * na * nop; pl->by_leaf_tt += 8.0 * nr * nop; pl->by_leaf_c += 8.0 * nop * nop;
         pl->fl_leaf_resid += Work(2.0 * nr * no * anct, 2.0 * nr * nop * Kanc, 8.0 * (nr * (Kanc + pl->d) + (double)nr * nop + (double)nop * nop));
         pl->fl_leaf_c_only += Work(no * no * anct, (double)nop * nop * Kanc, 8.0 * (no * (Kanc + pl->d) + (double)nop * nop));
         double* inv = pl->leafInv.p + pl->leaf_ioff[t];
-        pf[t] = PanelProb{Pn, inv, nop, (int)((nop + na + nr) / 16), nop / 16, i};
-        pk[t] = PanelProb{Pn, inv, nop, (nop + na) / 16, nop / 16, i};
-        pc[t] = PanelProb{Pn, inv, nop, nop / 16, nop / 16, i};
-        tf[t] = Trsm2Prob{Pn, inv, Pn + (size_t)nop * nop, pl->var.p + r0, nop, nop, nop / 16, (int)((na + nr) / 16), na / 16, -1.0, q.obs, pl->W.p + a0, pl->ldw, na / 16};
-        tk[t] = Trsm2Prob{Pn, inv, Pn + (size_t)nop * nop, nullptr, nop, nop, nop / 16, na / 16, 0, 1.0, q.obs, pl->W.p + a0, pl->ldw, na / 16};
+        d.chol_full[t] = PanelProb{Pn, inv, nop, (int)((nop + na + nr) / 16), nop / 16, i};
+        d.chol_lik[t] = PanelProb{Pn, inv, nop, (nop + na) / 16, nop / 16, i};
+        d.chol_c[t] = PanelProb{Pn, inv, nop, nop / 16, nop / 16, i};
+        d.trsm_full[t] = Trsm2Prob{Pn, inv, Ut, pl->var.p + r0, nop, nop, nop / 16, (int)((na + nr) / 16), na / 16, -1.0, q.obs, pl->W.p + a0, pl->ldw, na / 16};
+        d.trsm_lik[t] = Trsm2Prob{Pn, inv, Ut, nullptr, nop, nop, nop / 16, na / 16, 0, 1.0, q.obs, pl->W.p + a0, pl->ldw, na / 16};
         pl->leaf_max_tiles_full = std::max(pl->leaf_max_tiles_full, (int)((na + nr) / 16));
         pl->leaf_max_tiles_lik = std::max(pl->leaf_max_tiles_lik, na / 16);
         pl->fl_leaf_chol += Work(no * no * no / 3.0 + (nat + nr) * no * no, (double)nop * nop * nop / 3.0 + (double)(na + nr) * nop * nop,
@@ -835,289 +856,343 @@ static void build_leaf(mra_plan* pl, const double* y) {
         pl->fl_leaf_chol_lik += Work(no * no * no / 3.0 + nat * no * no, (double)nop * nop * nop / 3.0 + (double)na * nop * nop,
                                      8.0 * (1.5 * nop * nop + 2.0 * na * nop));
         GemmProb s{};
-        s.A = Pn + (size_t)nop * nop; s.lda = nop; s.B = s.A; s.ldb = nop;
+        s.A = Ut; s.lda = nop; s.B = s.A; s.ldb = nop;
         s.C = pl->Gt.p ? pl->Gt.p + pl->leaf_goff[t] : nullptr; s.ldc = na; s.M = na; s.N = na; s.K = nop; s.lower = 1;
-        gs[t] = s;
+        d.syrk[t] = s;
         pl->fl_leaf_syrk += Work(nat * nat * no, (double)na * na * nop, 8.0 * na * nop);
         GemmProb u{};
-        u.A = Pn + (size_t)(nop + na) * nop; u.lda = nop; u.B = Pn + (size_t)nop * nop; u.ldb = nop;
+        u.A = V; u.lda = nop; u.B = Ut; u.ldb = nop;
         u.C = pl->W.p + r0 * pl->ldw + a0; u.ldc = pl->ldw; u.M = (int)nr; u.N = na; u.K = nop; u.lower = 0;
         u.zc = na - MRA_YB;                  // y block: C_in = 0 (the column still holds y itself)
-        gu[t] = u;
+        d.upd[t] = u;
         pl->fl_leaf_update += Work(2.0 * nr * nat * no, 2.0 * nr * na * nop, 8.0 * ((double)nr * nop + (double)na * nop + 2.0 * nr * na));
     }
-    tr.mark("leaf descriptors (host)");
-    {
-        std::vector<double*> uts(nl);
-        for (size_t t = 0; t < nl; ++t) uts[t] = pl->panel.p + pl->leaf_poff[t] + (size_t)pl->leaf_nop[t] * pl->leaf_nop[t];
-        pl->leaf_ut.upload(uts);
-        pl->leaf_nop_dev.upload(pl->leaf_nop);
-        // the Ut blocks start from zero: rows of the y block beyond y itself and phantom observation columns stay zero
-        if (pl->panel.n) HIP_TRY(mraMemset(pl->panel.p, 0, pl->panel.n * sizeof(double)));
+}
+
+// the Ut pointer list of the leaves, and the panels cleared
+static void upload_leaf_ut_and_clear_panels(mra_plan* pl) {
+    const size_t nl = pl->leaf_nodes.size();
+    std::vector<double*> uts(nl);
+    for (size_t t = 0; t < nl; ++t) uts[t] = leaf_Ut(pl, t);
+    pl->leaf_ut.upload(uts);
+    pl->leaf_nop_dev.upload(pl->leaf_nop);
+    // the Ut blocks start from zero: rows of the y block beyond y itself and phantom observation columns stay zero
+    if (pl->panel.n) HIP_TRY(mraMemset(pl->panel.p, 0, pl->panel.n * sizeof(double)));
+}
+
+// where a node's K segments sit in a segment list: (first, count)
+typedef std::vector<std::pair<size_t, int>> SegRanges;
+
+// fronts of the leaves' parents straight from the children's Ut (segmented SYRK): one segment per child
+static void build_parent_syrk(mra_plan* pl, std::vector<GemmSeg>& segs, SegRanges& where) {
+    const LevelData& lv = pl->lev[pl->NL - 1];
+    std::vector<GemmProb> ps(lv.nodes.size());
+    where.resize(lv.nodes.size());
+    for (size_t sidx = 0; sidx < lv.nodes.size(); ++sidx) {
+        const int i = lv.nodes[sidx];
+        where[sidx] = {segs.size(), pl->child_ptr[i + 1] - pl->child_ptr[i]};
+        for (int c = pl->child_ptr[i]; c < pl->child_ptr[i + 1]; ++c) {
+            const int lt = pl->leaf_slot[pl->child_list[c]];
+            const int nop = pl->leaf_nop[lt];
+            double* ut = leaf_Ut(pl, lt);
+            segs.push_back(GemmSeg{ut, ut, nop, nop, nop, 0});
+        }
     }
-    tr.mark("panel memset");
-    pl->parent_syrk = false;
-    pl->hLeafSyrk = gs;
-    if (pl->shape_regular && pl->NL >= 1) {
-        const LevelData& lv = pl->lev[pl->NL - 1];
-        std::vector<GemmProb> ps(lv.nodes.size());
-        std::vector<GemmSeg> segs;
-        std::vector<std::pair<size_t, int>> where(lv.nodes.size());
-        for (size_t sidx = 0; sidx < lv.nodes.size(); ++sidx) {
-            const int i = lv.nodes[sidx];
-            where[sidx] = {segs.size(), pl->child_ptr[i + 1] - pl->child_ptr[i]};
-            for (int c = pl->child_ptr[i]; c < pl->child_ptr[i + 1]; ++c) {
-                const int lt = pl->leaf_slot[pl->child_list[c]];
+    pl->parentSegs.upload(segs);
+    for (size_t sidx = 0; sidx < lv.nodes.size(); ++sidx) {
+        GemmProb g{};
+        g.C = lv.panel_only ? nullptr : lv.F_of(sidx); g.ldc = lv.nf; g.M = lv.nf; g.N = lv.nf; g.lower = 1;      // (not launched when panel_only)
+        g.segs = pl->parentSegs.p + where[sidx].first; g.nseg = where[sidx].second; g.diag_one = lv.cw;
+        if (g.nseg == 0) { g.nseg = 0; g.K = 0; g.A = g.B = pl->W.p; }
+        ps[sidx] = g;
+    }
+    pl->gParentSyrk.upload(ps);
+    pl->parent_syrk = true;
+}
+
+// lowrank_parent - panels of the leaves' parents, in three launches: the own block F_oo = I + U_o U_o^T with its Cholesky
+// (k_parent_front on a front of cw rows: everything in registers / LDS), the rows below F_ao = U_a U_o^T (one GEMM over the children's
+// Ut segments, A = their ancestor rows, B = their own-block rows), and the row solve Zt = F_ao Lt^-T in place
+static void build_parent_panels(mra_plan* pl, const LeafDescs& d, const std::vector<GemmSeg>& segs, const SegRanges& where) {
+    const LevelData& lv = pl->lev[pl->NL - 1];
+    std::vector<GemmSeg> segs_ao;
+    for (const GemmSeg& sg : segs) segs_ao.push_back(GemmSeg{sg.A + (size_t)lv.cw * sg.lda, sg.B, sg.lda, sg.ldb, sg.K, 0});
+    pl->parentSegsAo.upload(segs_ao);
+    std::vector<GemmProb> pp(lv.nodes.size());
+    std::vector<FrontProb> pown(lv.nodes.size());
+    std::vector<Trsm2Prob> pzt(lv.nodes.size());
+    for (size_t sidx = 0; sidx < lv.nodes.size(); ++sidx) {
+        double* panel_s = lv.F_of(sidx);
+        double* inv_s = lv.invF_of(sidx);
+        GemmProb g{};
+        g.C = panel_s + (size_t)lv.cw * lv.ldf; g.ldc = lv.ldf; g.M = lv.na; g.N = lv.cw; g.lower = 0;
+        g.segs = pl->parentSegsAo.p + where[sidx].first; g.nseg = where[sidx].second; g.diag_one = 0;
+        if (g.nseg == 0) { g.K = 0; g.A = g.B = pl->W.p; }
+        pp[sidx] = g;
+        pown[sidx] = FrontProb{panel_s, inv_s, lv.cw, lv.cwt, lv.nodes[sidx], (int)where[sidx].first, where[sidx].second};
+        pzt[sidx] = Trsm2Prob{panel_s, inv_s, panel_s + (size_t)lv.cw * lv.ldf, nullptr, lv.ldf, lv.ldf, lv.cwt, lv.na / 16, 0, 1.0, nullptr, nullptr, 0, 0};
+        const int i = lv.nodes[sidx];
+        const double rkt = (double)(pl->knot_ptr[i + 1] - pl->knot_ptr[i]), nat = (double)pl->anc_rank[i] + 1.0;
+        double kobs = 0, kpad = 0;
+        for (int c = pl->child_ptr[i]; c < pl->child_ptr[i + 1]; ++c) { const int lt = pl->leaf_slot[pl->child_list[c]]; kobs += d.nobs[lt]; kpad += pl->leaf_nop[lt]; }
+        pl->fl_parent_panel += Work(2.0 * (rkt + nat) * rkt * kobs, 2.0 * lv.nf * lv.cw * kpad, 8.0 * (lv.nf * kpad + (double)lv.nf * lv.cw));
+    }
+    pl->gParentPanel.upload(pp);
+    // the LDS-tiled segmented product keeps its K steps as a table of SB_MAXST2 entries
+    pl->parent_panel_lds_ok = true;
+    for (size_t sidx = 0; sidx < lv.nodes.size() && pl->parent_panel_lds_ok; ++sidx) {
+        long steps = 0;
+        for (int k = 0; k < where[sidx].second; ++k) steps += segs_ao[where[sidx].first + k].K / 16;
+        if (where[sidx].second > SB_MAXST2 || steps > SB_MAXST2) pl->parent_panel_lds_ok = false;
+    }
+    pl->gParentOwn.upload(pown);
+    pl->gParentZt.upload(pzt);
+    const long nt = lv.cwt, npanel = lv.cwt * nt - lv.cwt * (lv.cwt - 1) / 2;
+    pl->parent_own_lds = (size_t)(2 * lv.cw * PF_LD + (npanel + lv.cwt) * FT_SZ) * sizeof(double);
+}
+
+// lowrank_parent - fronts of the grandparents: I + sum over grandchild leaves Ut[anc] Ut[anc]^T - sum over children Zt Zt^T
+static void build_grand_syrk(mra_plan* pl, const LeafDescs& d) {
+    const LevelData& lv = pl->lev[pl->NL - 1];
+    const LevelData& lg = pl->lev[pl->NL - 2];
+    std::vector<GemmSeg> gsegs;
+    SegRanges gwhere(lg.nodes.size());
+    for (size_t sidx = 0; sidx < lg.nodes.size(); ++sidx) {
+        const int i = lg.nodes[sidx];
+        const size_t first = gsegs.size();
+        const double rkt = (double)(pl->knot_ptr[i + 1] - pl->knot_ptr[i]), nft = rkt + (double)pl->anc_rank[i] + 1.0;
+        double kalg = 0, kpad = 0;
+        for (int c = pl->child_ptr[i]; c < pl->child_ptr[i + 1]; ++c) {
+            const int ch = pl->child_list[c];                  // a parent of leaves
+            for (int c2 = pl->child_ptr[ch]; c2 < pl->child_ptr[ch + 1]; ++c2) {
+                const int lt = pl->leaf_slot[pl->child_list[c2]];
                 const int nop = pl->leaf_nop[lt];
-                double* ut = pl->panel.p + pl->leaf_poff[lt] + (size_t)nop * nop;
-                segs.push_back(GemmSeg{ut, ut, nop, nop, nop, 0});
+                if (!nop) continue;
+                double* ut = leaf_Ut(pl, lt) + (size_t)lv.cw * nop;      // rows of the ancestors of `ch`
+                gsegs.push_back(GemmSeg{ut, ut, nop, nop, nop, 0});
+                kalg += d.nobs[lt]; kpad += nop;
             }
+            double* zt = lv.F_of(pl->node_slot[ch]) + (size_t)lv.cw * lv.ldf;
+            gsegs.push_back(GemmSeg{zt, zt, lv.ldf, lv.ldf, lv.cw, 1});
+            kalg += (double)(pl->knot_ptr[ch + 1] - pl->knot_ptr[ch]); kpad += lv.cw;
         }
-        pl->parentSegs.upload(segs);
-        for (size_t sidx = 0; sidx < lv.nodes.size(); ++sidx) {
-            GemmProb g{};
-            g.C = lv.panel_only ? nullptr : lv.F.p + sidx * (size_t)lv.nf * lv.nf; g.ldc = lv.nf; g.M = lv.nf; g.N = lv.nf; g.lower = 1;      // (not launched when panel_only)
-            g.segs = pl->parentSegs.p + where[sidx].first; g.nseg = where[sidx].second; g.diag_one = lv.cw;
-            if (g.nseg == 0) { g.nseg = 0; g.K = 0; g.A = g.B = pl->W.p; }
-            ps[sidx] = g;
-        }
-        pl->gParentSyrk.upload(ps);
-        pl->parent_syrk = true;
-        pl->fl_parent_panel = pl->fl_grand_syrk = Work();
-        if (pl->lowrank_parent && pl->NL >= 2) {
-            // panels of the leaves' parents, in three launches: the own block F_oo = I + U_o U_o^T with its Cholesky (k_parent_front on
-            // a front of cw rows: everything in registers / LDS), the rows below F_ao = U_a U_o^T (one GEMM over the children's Ut
-            // segments, A = their ancestor rows, B = their own-block rows), and the row solve Zt = F_ao Lt^-T in place
-            std::vector<GemmSeg> segs_ao;
-            for (const GemmSeg& sg : segs) segs_ao.push_back(GemmSeg{sg.A + (size_t)lv.cw * sg.lda, sg.B, sg.lda, sg.ldb, sg.K, 0});
-            pl->parentSegsAo.upload(segs_ao);
-            std::vector<GemmProb> pp(lv.nodes.size());
-            std::vector<FrontProb> pown(lv.nodes.size());
-            std::vector<Trsm2Prob> pzt(lv.nodes.size());
-            for (size_t sidx = 0; sidx < lv.nodes.size(); ++sidx) {
-                double* panel_s = lv.F.p + sidx * (size_t)lv.nf * lv.ldf;
-                double* inv_s = lv.invF.p + sidx * (size_t)lv.cwt * 256;
-                GemmProb g{};
-                g.C = panel_s + (size_t)lv.cw * lv.ldf; g.ldc = lv.ldf; g.M = lv.na; g.N = lv.cw; g.lower = 0;
-                g.segs = pl->parentSegsAo.p + where[sidx].first; g.nseg = where[sidx].second; g.diag_one = 0;
-                if (g.nseg == 0) { g.K = 0; g.A = g.B = pl->W.p; }
-                pp[sidx] = g;
-                pown[sidx] = FrontProb{panel_s, inv_s, lv.cw, lv.cwt, lv.nodes[sidx], (int)where[sidx].first, where[sidx].second};
-                pzt[sidx] = Trsm2Prob{panel_s, inv_s, panel_s + (size_t)lv.cw * lv.ldf, nullptr, lv.ldf, lv.ldf, lv.cwt, lv.na / 16, 0, 1.0, nullptr, nullptr, 0, 0};
-                const int i = lv.nodes[sidx];
-                const double rkt = (double)(pl->knot_ptr[i + 1] - pl->knot_ptr[i]), nat = (double)pl->anc_rank[i] + 1.0;
-                double kobs = 0, kpad = 0;
-                for (int c = pl->child_ptr[i]; c < pl->child_ptr[i + 1]; ++c) { const int lt = pl->leaf_slot[pl->child_list[c]]; kobs += nobs[lt]; kpad += pl->leaf_nop[lt]; }
-                pl->fl_parent_panel += Work(2.0 * (rkt + nat) * rkt * kobs, 2.0 * lv.nf * lv.cw * kpad, 8.0 * (lv.nf * kpad + (double)lv.nf * lv.cw));
-            }
-            pl->gParentPanel.upload(pp);
-            // the LDS-tiled segmented product keeps its K steps as a table of SB_MAXST2 entries
-            pl->parent_panel_lds_ok = true;
-            for (size_t sidx = 0; sidx < lv.nodes.size() && pl->parent_panel_lds_ok; ++sidx) {
-                long steps = 0;
-                for (int k = 0; k < where[sidx].second; ++k) steps += segs_ao[where[sidx].first + k].K / 16;
-                if (where[sidx].second > SB_MAXST2 || steps > SB_MAXST2) pl->parent_panel_lds_ok = false;
-            }
-            pl->gParentOwn.upload(pown);
-            pl->gParentZt.upload(pzt);
-            {
-                const long nt = lv.cwt, npanel = lv.cwt * nt - lv.cwt * (lv.cwt - 1) / 2;
-                pl->parent_own_lds = (size_t)(2 * lv.cw * PF_LD + (npanel + lv.cwt) * FT_SZ) * sizeof(double);
-            }
-            // fronts of the grandparents: I + sum over grandchild leaves Ut[anc] Ut[anc]^T - sum over children Zt Zt^T
-            const LevelData& lg = pl->lev[pl->NL - 2];
-            std::vector<GemmSeg> gsegs;
-            std::vector<std::pair<size_t, int>> gwhere(lg.nodes.size());
-            for (size_t sidx = 0; sidx < lg.nodes.size(); ++sidx) {
-                const int i = lg.nodes[sidx];
-                const size_t first = gsegs.size();
-                const double rkt = (double)(pl->knot_ptr[i + 1] - pl->knot_ptr[i]), nft = rkt + (double)pl->anc_rank[i] + 1.0;
-                double kalg = 0, kpad = 0;
-                for (int c = pl->child_ptr[i]; c < pl->child_ptr[i + 1]; ++c) {
-                    const int ch = pl->child_list[c];                  // a parent of leaves
-                    for (int c2 = pl->child_ptr[ch]; c2 < pl->child_ptr[ch + 1]; ++c2) {
-                        const int lt = pl->leaf_slot[pl->child_list[c2]];
-                        const int nop = pl->leaf_nop[lt];
-                        if (!nop) continue;
-                        double* ut = pl->panel.p + pl->leaf_poff[lt] + (size_t)nop * nop + (size_t)lv.cw * nop;      // rows of the ancestors of `ch`
-                        gsegs.push_back(GemmSeg{ut, ut, nop, nop, nop, 0});
-                        kalg += nobs[lt]; kpad += nop;
-                    }
-                    double* zt = lv.F.p + (size_t)pl->node_slot[ch] * lv.nf * lv.ldf + (size_t)lv.cw * lv.ldf;
-                    gsegs.push_back(GemmSeg{zt, zt, lv.ldf, lv.ldf, lv.cw, 1});
-                    kalg += (double)(pl->knot_ptr[ch + 1] - pl->knot_ptr[ch]); kpad += lv.cw;
-                }
-                gwhere[sidx] = {first, (int)(gsegs.size() - first)};
-                pl->fl_grand_syrk += Work(nft * nft * kalg, (double)lg.nf * lg.nf * kpad, 8.0 * (lg.nf * kpad + 0.5 * lg.nf * (lg.nf + 1)));
-            }
-            pl->grandSegs.upload(gsegs);
-            std::vector<GemmProb> gp(lg.nodes.size());
-            for (size_t sidx = 0; sidx < lg.nodes.size(); ++sidx) {
-                GemmProb g{};
-                g.C = lg.F.p + sidx * (size_t)lg.nf * lg.nf; g.ldc = lg.nf; g.M = lg.nf; g.N = lg.nf; g.lower = 1;
-                g.segs = pl->grandSegs.p + gwhere[sidx].first; g.nseg = gwhere[sidx].second; g.diag_one = lg.cw;
-                if (g.nseg == 0) { g.K = 0; g.A = g.B = pl->W.p; }
-                gp[sidx] = g;
-            }
-            pl->gGrandSyrk.upload(gp);
-            // k_syrk_blk keeps the K steps of a problem as a table in LDS: SB_MAXST segments / 16-column steps at most
-            pl->grand_syrk_blk_ok = pl->grand_syrk_dma_ok = (lg.nf % 16) == 0;
-            for (size_t sidx = 0; sidx < lg.nodes.size() && pl->grand_syrk_blk_ok; ++sidx) {
-                long steps = 0;
-                for (int k = 0; k < gwhere[sidx].second; ++k) steps += gsegs[gwhere[sidx].first + k].K / 16;
-                if (gwhere[sidx].second == 0 || gwhere[sidx].second > SB_MAXST || steps > SB_MAXST) pl->grand_syrk_blk_ok = false;
-                if (gwhere[sidx].second == 0 || gwhere[sidx].second > SD_MAXST || steps > SD_MAXST) pl->grand_syrk_dma_ok = false;
-            }
-        }
-        {
-            std::vector<FrontProb> pf(lv.nodes.size());
-            for (size_t sidx = 0; sidx < lv.nodes.size(); ++sidx)
-                pf[sidx] = FrontProb{lv.F.p + sidx * (size_t)lv.nf * lv.ldf, lv.invF.p + sidx * (size_t)lv.cwt * 256, lv.nf, lv.cwt,
-                                     lv.nodes[sidx], (int)where[sidx].first, where[sidx].second};
-            pl->gParentFront.upload(pf);
-            const long nt = lv.nf / 16, ntiles = nt * (nt + 1) / 2;
-            const long npanel = lv.cwt * nt - lv.cwt * (lv.cwt - 1) / 2;
-            pl->parent_front_lds = (size_t)(2 * lv.nf * PF_LD + (npanel + lv.cwt) * FT_SZ) * sizeof(double);
-            pl->parent_front_nacc = ntiles <= 16 ? 2 : (ntiles <= 32 ? 4 : (ntiles <= 64 ? 8 : (ntiles <= 96 ? 12 : 0)));
-            if (pl->parent_front_lds > 160 * 1024 || lv.panel_only) pl->parent_front_nacc = 0;
-        }
+        gwhere[sidx] = {first, (int)(gsegs.size() - first)};
+        pl->fl_grand_syrk += Work(nft * nft * kalg, (double)lg.nf * lg.nf * kpad, 8.0 * (lg.nf * kpad + 0.5 * lg.nf * (lg.nf + 1)));
     }
-    tr.mark("parent / grandparent descriptors");
-    pl->hLeafResid = gr; pl->leaf_nobs_host = nobs;
-    pl->gLeafResidLik.upload(grl);
-    pl->gLeaf.upload(lp); pl->gLeafResid.upload(gr); pl->gLeafSyrk.upload(gs); pl->gLeafUpdate.upload(gu);
-    pl->gLeafCholFull.upload(pf); pl->gLeafCholLik.upload(pk); pl->gLeafCholC.upload(pc);
-    {
-        // the same problems with the matrices of at most 8 tiles first (k_chol_tiles<8> at three workgroups per CU, then the few larger ones)
-        std::vector<PanelProb> ps;
-        for (int pass = 0; pass < 2; ++pass)
-            for (const PanelProb& p : pc) if ((p.ne <= 8) == (pass == 0)) ps.push_back(p);
-        pl->n_chol_small = 0;
-        for (const PanelProb& p : pc) if (p.ne <= 8) ++pl->n_chol_small;
-        pl->gLeafCholSorted.upload(ps);
+    pl->grandSegs.upload(gsegs);
+    std::vector<GemmProb> gp(lg.nodes.size());
+    for (size_t sidx = 0; sidx < lg.nodes.size(); ++sidx) {
+        GemmProb g{};
+        g.C = lg.F_of(sidx); g.ldc = lg.nf; g.M = lg.nf; g.N = lg.nf; g.lower = 1;
+        g.segs = pl->grandSegs.p + gwhere[sidx].first; g.nseg = gwhere[sidx].second; g.diag_one = lg.cw;
+        if (g.nseg == 0) { g.K = 0; g.A = g.B = pl->W.p; }
+        gp[sidx] = g;
     }
+    pl->gGrandSyrk.upload(gp);
+    // k_syrk_blk keeps the K steps of a problem as a table in LDS: SB_MAXST segments / 16-column steps at most
+    pl->grand_syrk_blk_ok = pl->grand_syrk_dma_ok = (lg.nf % 16) == 0;
+    for (size_t sidx = 0; sidx < lg.nodes.size() && pl->grand_syrk_blk_ok; ++sidx) {
+        long steps = 0;
+        for (int k = 0; k < gwhere[sidx].second; ++k) steps += gsegs[gwhere[sidx].first + k].K / 16;
+        if (gwhere[sidx].second == 0 || gwhere[sidx].second > SB_MAXST || steps > SB_MAXST) pl->grand_syrk_blk_ok = false;
+        if (gwhere[sidx].second == 0 || gwhere[sidx].second > SD_MAXST || steps > SD_MAXST) pl->grand_syrk_dma_ok = false;
+    }
+}
+
+// the parents' fronts for k_parent_front (SYRK + factorisation in one launch), where the front fits its registers and LDS
+static void build_parent_front(mra_plan* pl, const SegRanges& where) {
+    const LevelData& lv = pl->lev[pl->NL - 1];
+    std::vector<FrontProb> fr(lv.nodes.size());
+    for (size_t sidx = 0; sidx < lv.nodes.size(); ++sidx)
+        fr[sidx] = FrontProb{lv.F_of(sidx), lv.invF_of(sidx), lv.nf, lv.cwt, lv.nodes[sidx], (int)where[sidx].first, where[sidx].second};
+    pl->gParentFront.upload(fr);
+    const long nt = lv.nf / 16, ntiles = nt * (nt + 1) / 2;
+    const long npanel = lv.cwt * nt - lv.cwt * (lv.cwt - 1) / 2;
+    pl->parent_front_lds = (size_t)(2 * lv.nf * PF_LD + (npanel + lv.cwt) * FT_SZ) * sizeof(double);
+    pl->parent_front_nacc = ntiles <= 16 ? 2 : (ntiles <= 32 ? 4 : (ntiles <= 64 ? 8 : (ntiles <= 96 ? 12 : 0)));
+    if (pl->parent_front_lds > 160 * 1024 || lv.panel_only) pl->parent_front_nacc = 0;
+}
+
+// shape-regular trees: the segmented products of the leaves' parents and, with lowrank_parent, of the grandparents
+static void build_parent_products(mra_plan* pl, const LeafDescs& d) {
+    pl->parent_syrk = false;
+    if (!pl->shape_regular || pl->NL < 1) return;
+    std::vector<GemmSeg> segs;
+    SegRanges where;
+    build_parent_syrk(pl, segs, where);
+    pl->fl_parent_panel = pl->fl_grand_syrk = Work();
+    if (pl->lowrank_parent && pl->NL >= 2) {
+        build_parent_panels(pl, d, segs, where);
+        build_grand_syrk(pl, d);
+    }
+    build_parent_front(pl, where);
+}
+
+// leaves with more than 192 observations: right-looking blocked factorisation, 64 columns per step (mra_plan::gBigPanel)
+static void build_big_panels(mra_plan* pl, const LeafDescs& d) {
+    const size_t nl = pl->leaf_nodes.size();
     for (int v = 0; v < 2; ++v) { pl->gBigPanel[v].clear(); pl->gBigTrail[v].clear(); pl->bigM[v].clear(); pl->bigN[v].clear(); }
-    if (pl->leaf_max_nop / 16 > LEAF_MAX_TILES) {
-        const int NBT = 4;                                        // column tiles per step
-        const int nsteps = (pl->leaf_max_nop / 16 + NBT - 1) / NBT;
-        for (int v = 0; v < 2; ++v) {
-            pl->gBigPanel[v].resize(nsteps); pl->gBigTrail[v].resize(nsteps);
-            pl->bigM[v].assign(nsteps, 0); pl->bigN[v].assign(nsteps, 0);
-            for (int st = 0; st < nsteps; ++st) {
-                std::vector<PanelProb> pp(nl);
-                std::vector<GemmProb> gg(nl);
-                for (size_t t = 0; t < nl; ++t) {
-                    const PanelProb& full = v == 0 ? pf[t] : pk[t];
-                    const int ntl = full.ne, c0 = st * NBT;               // column tiles of this leaf, first tile of the step
-                    const int ne = std::max(0, std::min(NBT, ntl - c0));
-                    const long nop = full.ld;
-                    PanelProb q = full;
-                    q.P = full.P + (size_t)c0 * 16 * nop + (size_t)c0 * 16;
-                    q.invd = full.invd + (size_t)c0 * 256;
-                    q.ht = ne > 0 ? full.ht - c0 : 0;
-                    q.ne = ne;
-                    pp[t] = q;
-                    GemmProb g{};
-                    const int c1 = c0 + ne;
-                    g.M = ne > 0 ? (full.ht - c1) * 16 : 0;
-                    g.N = ne > 0 ? (ntl - c1) * 16 : 0;
-                    if (g.N <= 0 || g.M <= 0) { g.M = 0; g.N = 0; }
-                    g.K = ne * 16;
-                    g.A = full.P + (size_t)c1 * 16 * nop + (size_t)c0 * 16; g.lda = nop;
-                    g.B = g.A; g.ldb = nop;
-                    g.C = full.P + (size_t)c1 * 16 * nop + (size_t)c1 * 16; g.ldc = nop;
-                    gg[t] = g;
-                    pl->bigM[v][st] = std::max<long>(pl->bigM[v][st], g.M);
-                    pl->bigN[v][st] = std::max<long>(pl->bigN[v][st], g.N);
-                }
-                pl->gBigPanel[v][st].upload(pp);
-                pl->gBigTrail[v][st].upload(gg);
+    if (pl->leaf_max_nop / 16 <= LEAF_MAX_TILES) return;
+    const int NBT = 4;                                        // column tiles per step
+    const int nsteps = (pl->leaf_max_nop / 16 + NBT - 1) / NBT;
+    for (int v = 0; v < 2; ++v) {
+        pl->gBigPanel[v].resize(nsteps); pl->gBigTrail[v].resize(nsteps);
+        pl->bigM[v].assign(nsteps, 0); pl->bigN[v].assign(nsteps, 0);
+        for (int st = 0; st < nsteps; ++st) {
+            std::vector<PanelProb> pp(nl);
+            std::vector<GemmProb> gg(nl);
+            for (size_t t = 0; t < nl; ++t) {
+                const PanelProb& full = v == 0 ? d.chol_full[t] : d.chol_lik[t];
+                const int ntl = full.ne, c0 = st * NBT;               // column tiles of this leaf, first tile of the step
+                const int ne = std::max(0, std::min(NBT, ntl - c0));
+                const long nop = full.ld;
+                PanelProb q = full;
+                q.P = full.P + (size_t)c0 * 16 * nop + (size_t)c0 * 16;
+                q.invd = full.invd + (size_t)c0 * 256;
+                q.ht = ne > 0 ? full.ht - c0 : 0;
+                q.ne = ne;
+                pp[t] = q;
+                GemmProb g{};
+                const int c1 = c0 + ne;
+                g.M = ne > 0 ? (full.ht - c1) * 16 : 0;
+                g.N = ne > 0 ? (ntl - c1) * 16 : 0;
+                if (g.N <= 0 || g.M <= 0) { g.M = 0; g.N = 0; }
+                g.K = ne * 16;
+                g.A = full.P + (size_t)c1 * 16 * nop + (size_t)c0 * 16; g.lda = nop;
+                g.B = g.A; g.ldb = nop;
+                g.C = full.P + (size_t)c1 * 16 * nop + (size_t)c1 * 16; g.ldc = nop;
+                gg[t] = g;
+                pl->bigM[v][st] = std::max<long>(pl->bigM[v][st], g.M);
+                pl->bigN[v][st] = std::max<long>(pl->bigN[v][st], g.N);
             }
+            pl->gBigPanel[v][st].upload(pp);
+            pl->gBigTrail[v][st].upload(gg);
         }
     }
-    pl->gLeafTrsmFull.upload(tf); pl->gLeafTrsmLik.upload(tk);
-    const std::vector<Trsm2Prob> tfg = tf, tkg = tk;          // with the Ut gather
+}
+
+// The stable small-first order of the leaves: those with at most LEAF_SMALL_TILES observation tiles (their count: the return value),
+// then the others, leaf order within each group.  EVERY small-first list is this one permutation - gLeafCholSorted, the *Plain*
+// row-solve lists, gLeafSolve, gLeafUpdatePlain: the kernels index one list with a position taken from another, and run_all steps
+// into each by the number of small leaves.
+static size_t order_small_first(const mra_plan* pl, std::vector<size_t>& order) {
+    const size_t nl = pl->leaf_nop.size();
+    order.clear();
+    order.reserve(nl);
+    for (int pass = 0; pass < 2; ++pass)
+        for (size_t t = 0; t < nl; ++t) if ((pl->leaf_nop[t] / 16 <= LEAF_SMALL_TILES) == (pass == 0)) order.push_back(t);
+    size_t n_small = 0;
+    while (n_small < nl && pl->leaf_nop[order[n_small]] / 16 <= LEAF_SMALL_TILES) ++n_small;
+    return n_small;
+}
+template <class T>
+static std::vector<T> in_order(const std::vector<T>& v, const std::vector<size_t>& order) {
+    std::vector<T> out(order.size());
+    for (size_t k = 0; k < order.size(); ++k) out[k] = v[order[k]];
+    return out;
+}
+
+// the per-leaf descriptors to the device, in leaf order (and the C-only factorisations small first as well)
+static void upload_leaf_descriptors(mra_plan* pl, const LeafDescs& d, const std::vector<size_t>& order) {
+    pl->hLeafResid = d.resid; pl->leaf_nobs_host = d.nobs;
+    pl->gLeafResidLik.upload(d.resid_lik);
+    pl->gLeaf.upload(d.lp); pl->gLeafResid.upload(d.resid); pl->gLeafSyrk.upload(d.syrk); pl->gLeafUpdate.upload(d.upd);
+    pl->gLeafCholFull.upload(d.chol_full); pl->gLeafCholLik.upload(d.chol_lik); pl->gLeafCholC.upload(d.chol_c);
+    // (k_chol_tiles<8, 4> at three workgroups per CU for the small matrices, then the few larger ones)
+    pl->gLeafCholSorted.upload(in_order(d.chol_c, order));
+}
+
+// The row solves: in leaf order (level-by-level path), and small first for the fused path - most leaves are small and get the
+// LEAF_SMALL_TILES instance (fewer registers, two workgroups per CU), the few larger ones the TRSM2_MAX_NT instance.  "G": the Ut rows
+// gathered from W by the row solve itself; plain: scattered there by the row cascade.
+static void build_leaf_row_solves(mra_plan* pl, const LeafDescs& d, const std::vector<size_t>& order, size_t n_small) {
+    pl->gLeafTrsmFull.upload(d.trsm_full); pl->gLeafTrsmLik.upload(d.trsm_lik);
+    const std::vector<Trsm2Prob> tfg = in_order(d.trsm_full, order), tkg = in_order(d.trsm_lik, order);
+    std::vector<Trsm2Prob> tf = tfg, tk = tkg;
     for (auto& e : tf) e.gtiles = 0;
     for (auto& e : tk) e.gtiles = 0;
-    {
-        // most leaves need at most 8 column tiles: they get the 8-tile instance (fewer registers, two
-        // workgroups per CU), the few larger ones the 12-tile instance
-        std::vector<Trsm2Prob> tf2, tk2;
-        pl->trsm_small_nt = pl->trsm_small_tiles_full = pl->trsm_small_tiles_lik = 0;
-        for (int pass = 0; pass < 2; ++pass)
-            for (size_t t = 0; t < nl; ++t) {
-                const bool small = tf[t].nt <= 8;
-                if (small != (pass == 0)) continue;
-                tf2.push_back(tf[t]); tk2.push_back(tk[t]);
-                if (small) {
-                    pl->trsm_small_nt = std::max(pl->trsm_small_nt, tf[t].nt);
-                    pl->trsm_small_tiles_full = std::max(pl->trsm_small_tiles_full, tf[t].ntiles);
-                    pl->trsm_small_tiles_lik = std::max(pl->trsm_small_tiles_lik, tk[t].ntiles);
-                }
-            }
-        pl->n_trsm_small = 0;
-        for (size_t t = 0; t < nl; ++t) if (tf[t].nt <= 8) ++pl->n_trsm_small;
-        pl->gLeafTrsmFullPlain.upload(tf2); pl->gLeafTrsmLikPlain.upload(tk2);
-        {
-            std::vector<Trsm2Prob> tf2g, tk2g;                 // same order, Ut gathered from W by the row solve itself
-            for (int pass = 0; pass < 2; ++pass)
-                for (size_t t = 0; t < nl; ++t)
-                    if ((tf[t].nt <= 8) == (pass == 0)) { tf2g.push_back(tfg[t]); tk2g.push_back(tkg[t]); }
-            pl->gLeafTrsmFullPlainG.upload(tf2g); pl->gLeafTrsmLikPlainG.upload(tk2g);
-        }
-        {
-            // fused row solve + update (k_leaf_solve_update) for the leaves with at most 8 observation tiles, in the same order
-            std::vector<LeafSolveProb> sp;
-            std::vector<GemmProb> up;
-            int nat_max = 0;
-            for (int pass = 0; pass < 2; ++pass)
-                for (size_t t = 0; t < nl; ++t) {
-                    const bool small = tf[t].nt <= 8;
-                    if (small != (pass == 0)) continue;
-                    const int i = pl->leaf_nodes[t];
-                    const int m = pl->node_level[i];
-                    const int na = pl->na[m], a0 = pl->asuf[m], nop = pl->leaf_nop[t];
-                    const long r0 = pl->row0[i], nr = pl->row1[i] - r0;
-                    double* Pn = pl->panel.p + pl->leaf_poff[t];
-                    LeafSolveProb q{};
-                    q.L = Pn; q.invd = pl->leafInv.p + pl->leaf_ioff[t];
-                    q.V = Pn + (size_t)(nop + na) * nop; q.Ut = Pn + (size_t)nop * nop;
-                    q.Wr = pl->W.p + r0 * pl->ldw + a0; q.var = pl->var.p + r0;
-                    q.ldL = nop; q.ldx = nop; q.ldw = pl->ldw;
-                    q.nt = nop / 16; q.nrt = (int)(nr / 16); q.nat = na / 16; q.zt = (na - MRA_YB) / 16;
-                    sp.push_back(q);
-                    up.push_back(gu[t]);
-                    if (small) nat_max = std::max(nat_max, q.nat);
-                }
-            pl->gLeafSolve.upload(sp);
-            pl->gLeafUpdatePlain.upload(up);
-            {
-                std::vector<LeafSolveProb> half;
-                for (size_t k = 0; k < pl->n_trsm_small && k < sp.size(); ++k) {
-                    const LeafSolveProb& q = sp[k];
-                    const int h0 = (q.nrt + 1) / 2;
-                    for (int part = 0; part < 2; ++part) {
-                        LeafSolveProb h = q;
-                        const int t0 = part ? h0 : 0, t1 = part ? q.nrt : h0;
-                        if (t1 <= t0) continue;
-                        h.V = q.V + (size_t)t0 * 16 * q.ldx; h.Wr = q.Wr + (size_t)t0 * 16 * q.ldw; h.var = q.var + (size_t)t0 * 16; h.nrt = t1 - t0;
-                        half.push_back(h);
-                    }
-                }
-                pl->n_leaf_solve_half = half.size();
-                pl->gLeafSolveHalf.upload(half);
-            }
-            {
-                std::vector<long> lr0(nl);
-                std::vector<unsigned char> lup(nl);
-                for (size_t t = 0; t < nl; ++t) { lr0[t] = pl->row0[pl->leaf_nodes[t]]; lup[t] = tf[t].nt <= 8 ? 1 : 0; }
-                pl->leaf_row0_dev.upload(lr0); pl->leaf_upd_dev.upload(lup);
-            }
-            const int nts = pl->trsm_small_nt;
-            pl->leaf_solve_lds = (size_t)((nts * (nts - 1) / 2 + nts) * FT_SZ + 2 * nat_max * 16 * LG_LD) * sizeof(double);
-            pl->leaf_solve_ok = pl->n_trsm_small > 0 && nat_max <= 13 && nat_max > 0 && pl->leaf_solve_lds <= 160 * 1024 && pl->leaf_max_rows >= 128;
+    pl->trsm_small_nt = pl->trsm_small_tiles_full = pl->trsm_small_tiles_lik = 0;
+    for (size_t k = 0; k < n_small; ++k) {
+        pl->trsm_small_nt = std::max(pl->trsm_small_nt, tf[k].nt);
+        pl->trsm_small_tiles_full = std::max(pl->trsm_small_tiles_full, tf[k].ntiles);
+        pl->trsm_small_tiles_lik = std::max(pl->trsm_small_tiles_lik, tk[k].ntiles);
+    }
+    pl->gLeafTrsmFullPlain.upload(tf); pl->gLeafTrsmLikPlain.upload(tk);
+    pl->gLeafTrsmFullPlainG.upload(tfg); pl->gLeafTrsmLikPlainG.upload(tkg);
+}
+
+// fused row solve + update (k_leaf_solve_update) for the small leaves, whole and in two halves, and the plain update of the others,
+// all small first; per leaf in leaf order, its first row and whether that kernel takes it
+static void build_leaf_solve_lists(mra_plan* pl, const LeafDescs& d, const std::vector<size_t>& order, size_t n_small) {
+    const size_t nl = order.size();
+    std::vector<LeafSolveProb> sp(nl);
+    int nat_max = 0;
+    for (size_t k = 0; k < nl; ++k) {
+        const size_t t = order[k];
+        const int i = pl->leaf_nodes[t];
+        const int m = pl->node_level[i];
+        const int na = pl->na[m], a0 = pl->asuf[m], nop = pl->leaf_nop[t];
+        const long r0 = pl->row0[i], nr = pl->row1[i] - r0;
+        LeafSolveProb q{};
+        q.L = leaf_C(pl, t); q.invd = pl->leafInv.p + pl->leaf_ioff[t];
+        q.V = leaf_V(pl, t); q.Ut = leaf_Ut(pl, t);
+        q.Wr = pl->W.p + r0 * pl->ldw + a0; q.var = pl->var.p + r0;
+        q.ldL = nop; q.ldx = nop; q.ldw = pl->ldw;
+        q.nt = nop / 16; q.nrt = (int)(nr / 16); q.nat = na / 16; q.zt = (na - MRA_YB) / 16;
+        sp[k] = q;
+        if (k < n_small) nat_max = std::max(nat_max, q.nat);
+    }
+    pl->gLeafSolve.upload(sp);
+    pl->gLeafUpdatePlain.upload(in_order(d.upd, order));
+    std::vector<LeafSolveProb> half;
+    for (size_t k = 0; k < n_small; ++k) {
+        const LeafSolveProb& q = sp[k];
+        const int h0 = (q.nrt + 1) / 2;
+        for (int part = 0; part < 2; ++part) {
+            LeafSolveProb h = q;
+            const int t0 = part ? h0 : 0, t1 = part ? q.nrt : h0;
+            if (t1 <= t0) continue;
+            h.V = q.V + (size_t)t0 * 16 * q.ldx; h.Wr = q.Wr + (size_t)t0 * 16 * q.ldw; h.var = q.var + (size_t)t0 * 16; h.nrt = t1 - t0;
+            half.push_back(h);
         }
     }
+    pl->n_leaf_solve_half = half.size();
+    pl->gLeafSolveHalf.upload(half);
+    std::vector<long> lr0(nl);
+    std::vector<unsigned char> lup(nl, 0);
+    for (size_t t = 0; t < nl; ++t) lr0[t] = pl->row0[pl->leaf_nodes[t]];
+    for (size_t k = 0; k < n_small; ++k) lup[order[k]] = 1;
+    pl->leaf_row0_dev.upload(lr0); pl->leaf_upd_dev.upload(lup);
+    const int nts = pl->trsm_small_nt;
+    pl->leaf_solve_lds = (size_t)((nts * (nts - 1) / 2 + nts) * FT_SZ + 2 * nat_max * 16 * LG_LD) * sizeof(double);
+    pl->leaf_solve_ok = n_small > 0 && nat_max <= 13 && nat_max > 0 && pl->leaf_solve_lds <= 160 * 1024 && pl->leaf_max_rows >= 128;
+}
+
+static void build_leaf(mra_plan* pl, const double* y) {
+    PlanTrace tr("build_leaf");
+    ArenaScope arena(&pl->arena);
+    pl->cphantom_valid = false;
+    pl->slv.valid = false; pl->slv.built = false;      // mra_solve's descriptors point into the leaves' panels
+    LeafDescs d;
+    build_obs_lists(pl, y, d);
+    tr.mark("observation lists");
+    pl->panel.alloc(std::max<long>(pl->leaf_poff.back(), 1));
+    pl->leafInv.alloc(std::max<long>(pl->leaf_ioff.back(), 1));
+    tr.mark("panel allocation");
+    build_leaf_descriptors(pl, d);
+    tr.mark("leaf descriptors (host)");
+    upload_leaf_ut_and_clear_panels(pl);
+    tr.mark("panel memset");
+    pl->hLeafSyrk = d.syrk;
+    build_parent_products(pl, d);
+    tr.mark("parent / grandparent descriptors");
+    std::vector<size_t> order;
+    const size_t n_small = order_small_first(pl, order);
+    pl->n_chol_small = pl->n_trsm_small = n_small;      // (PanelProb::ne and Trsm2Prob::nt of a leaf are both its observation tiles)
+    upload_leaf_descriptors(pl, d, order);
+    build_big_panels(pl, d);
+    build_leaf_row_solves(pl, d, order, n_small);
+    build_leaf_solve_lists(pl, d, order, n_small);
     arena.finish();
     tr.mark("descriptor arena to the device");
 }
@@ -1184,7 +1259,7 @@ static void launch_panel(mra_plan* pl, const PanelProb* probs, size_t nprob, int
 static bool launch_trsm2(mra_plan* pl, const Trsm2Prob* probs, size_t nprob, int nt, long max_tiles, int tiles_per_wg) {
     if (!pl->prepare_only && (!nprob || max_tiles <= 0 || nt <= 0)) return true;
     if (nt > TRSM2_MAX_NT) return false;
-    ensure_big_lds(pl, {(const void*)k_trsm_rows2<2>, (const void*)k_trsm_rows2<4>, (const void*)k_trsm_rows2<8>, (const void*)k_trsm_rows2<TRSM2_MAX_NT>});
+    ensure_big_lds(pl, {(const void*)k_trsm_rows2<2>, (const void*)k_trsm_rows2<4>, (const void*)k_trsm_rows2<LEAF_SMALL_TILES>, (const void*)k_trsm_rows2<TRSM2_MAX_NT>});
     if (pl->prepare_only) return true;
     const size_t lds = (size_t)(nt * (nt - 1) / 2 + nt) * 2048 + (size_t)nt * 16 * sizeof(int);      // L image + the Ut gather list
     const unsigned gx = (unsigned)((max_tiles + tiles_per_wg - 1) / tiles_per_wg);
@@ -1204,7 +1279,7 @@ static bool launch_trsm2(mra_plan* pl, const Trsm2Prob* probs, size_t nprob, int
         dim3 grid(gx, (unsigned)std::min<size_t>(65535, nprob - off));
         if (nt <= 2) hipLaunchKernelGGL((k_trsm_rows2<2>), grid, dim3(tb), lds, pl->stream, probs + off, tiles_per_wg MRA_TSTAMP_VAL);
         else if (nt <= 4) hipLaunchKernelGGL((k_trsm_rows2<4>), grid, dim3(tb), lds, pl->stream, probs + off, tiles_per_wg MRA_TSTAMP_VAL);
-        else if (nt <= 8) hipLaunchKernelGGL((k_trsm_rows2<8>), grid, dim3(tb), lds, pl->stream, probs + off, tiles_per_wg MRA_TSTAMP_VAL);
+        else if (nt <= LEAF_SMALL_TILES) hipLaunchKernelGGL((k_trsm_rows2<LEAF_SMALL_TILES>), grid, dim3(tb), lds, pl->stream, probs + off, tiles_per_wg MRA_TSTAMP_VAL);
         else hipLaunchKernelGGL((k_trsm_rows2<TRSM2_MAX_NT>), grid, dim3(tb), lds, pl->stream, probs + off, tiles_per_wg MRA_TSTAMP_VAL);
     }
     return true;
@@ -1225,8 +1300,8 @@ static void ensure_lik_tiles(mra_plan* pl) {
         const int i = pl->leaf_nodes[t];
         const long nt = (pl->obs_off_host[t + 1] - pl->obs_off_host[t]) / 16;
         if (!nt) continue;
-        int ch[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        for (int a = pl->parent[i]; a >= 0; a = pl->parent[a]) ch[pl->node_level[a]] = pl->node_slot[a];
+        int ch[8];
+        chain_of(pl, i, ch);
         // the kernel stages the chain of a workgroup's FIRST tile for all of its tiles: join only a workgroup with this very chain (leaf
         // t - 1 may own no tile, and the last workgroup then belongs to another family)
         const bool join = pl->cascade_group_siblings && !wg0.empty() && wg0.back() + wgn.back() == pl->obs_off_host[t] / 16 &&
@@ -1295,7 +1370,7 @@ static bool ensure_lik_general(mra_plan* pl) {
                 g.XA = pl->X.p; g.XB = pl->X.p;
                 g.M = (int)std::min(blk, o1 - b0); g.N = lv.cw; g.K = Kanc; g.lower = 0;
                 g.idxA = pl->need_idx.p + b0;
-                g.solveL = lv.Lp.p + s * (size_t)lv.cw * lv.cw; g.solveI = lv.invP.p + s * (size_t)lv.cwt * 256; g.var = pl->var.p;
+                g.solveL = lv.Lp_of(s); g.solveI = lv.invP_of(s); g.var = pl->var.p;
                 fz.push_back(g);
             }
         }
@@ -1894,7 +1969,7 @@ static void run_all(mra_plan* pl, uint32_t flags, bool full_rows = false) {
             const int ntl = pl->leaf_max_nop / 16;
             if (r.chol != LeafChol::BigPanels) {
                 // k_chol_tiles: one workgroup per matrix, tiles in registers, next diagonal block factorised beside the trailing update
-                const size_t ns = pl->n_chol_small;
+                const size_t ns = pl->n_chol_small;      // (gLeafCholSorted: the leaves of at most LEAF_SMALL_TILES tiles first)
                 if (r.chol == LeafChol::TilesSplit) {
                     if (ns) hipLaunchKernelGGL((k_chol_tiles<8, 4>), dim3((unsigned)ns), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p, pl->dnode.p, pl->errflag.p);
                     if (nl > ns) hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)(nl - ns)), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p + ns, pl->dnode.p, pl->errflag.p);
@@ -1906,7 +1981,7 @@ static void run_all(mra_plan* pl, uint32_t flags, bool full_rows = false) {
                     const size_t nts = pl->n_trsm_small;
                     const int mts = (pred && !r.solve_fused) ? pl->trsm_small_tiles_full : pl->trsm_small_tiles_lik;
                     if (nts) launch_trsm2(pl, r.trsm_small, nts, pl->trsm_small_nt, mts, mts);
-                    // the few leaves with more than 128 observations: several workgroups per leaf when they are few
+                    // the few leaves with more than LEAF_SMALL_TILES observation tiles: several workgroups per leaf when they are few
                     // (one leaf per workgroup would put a single 65 us workgroup on the critical path)
                     if (nl > nts) launch_trsm2(pl, r.trsm_all + nts, nl - nts, ntl, mt, (nl - nts) < 512 ? 4 : mt);
                 }
@@ -1950,14 +2025,14 @@ static void run_all(mra_plan* pl, uint32_t flags, bool full_rows = false) {
                                    pl->host_cov ? pl->covdiag.p : (const double*)nullptr, pl->P);
             }
             if (r.update == LeafUpdate::InCascade) {          // (InPredictHi: nothing to launch here)
-                // the small leaves (<= 8 observation tiles) take their update inside the predictive cascade; the few larger ones here
+                // the small leaves (<= LEAF_SMALL_TILES observation tiles) take their update inside the predictive cascade; the few larger ones here
                 const size_t ns = pl->n_trsm_small;
                 if (nl > ns) {
                     KTimer kt(pl, KF_LEAF_UPDATE, 0);
                     launch_gemm<EPI_SUB>(pl, pl->gLeafUpdatePlain.p + ns, nl - ns, pl->leaf_max_rows, pl->leaf_max_na);
                 }
             } else if (r.update == LeafUpdate::SolveWhole || r.update == LeafUpdate::SolveHalves) {
-                // Tt = V Lc^-T, var -= |Tt|^2 and W -= Tt Ut^T in one launch for the leaves with <= 8 observation tiles; the few
+                // Tt = V Lc^-T, var -= |Tt|^2 and W -= Tt Ut^T in one launch for the leaves with <= LEAF_SMALL_TILES observation tiles; the few
                 // larger ones went through the full row solve above and take the plain update product
                 ensure_big_lds(pl, {(const void*)k_leaf_solve_update<8, 13, true>});
                 KTimer kt(pl, KF_LEAF_UPDATE, pl->fl_leaf_update);
@@ -2815,18 +2890,18 @@ int mra_get_node_block(mra_plan* pl, int32_t node, int what, double* out, int64_
             if (pl->leaf[node]) throw MraError(MRA_ERR_INVALID, "block exists for non-leaf nodes only");
             const LevelData& lv = pl->lev[m];
             const size_t sl = (size_t)pl->node_slot[node];
-            if (what == MRA_BLOCK_LPRIOR) { rows = cols = ld = lv.cw; src = lv.Lp.p + sl * (size_t)lv.cw * lv.cw; }
+            if (what == MRA_BLOCK_LPRIOR) { rows = cols = ld = lv.cw; src = lv.Lp_of(sl); }
             else {
                 if (lv.panel_only) throw MraError(MRA_ERR_STATE, "the fronts of this level are kept as their panel columns only (large fronts of the leaves' parents); "
                                                                   "set MRA_NO_LOWRANK_PARENT=1 before creating the plan to get whole fronts");
-                rows = cols = ld = lv.nf; src = lv.F.p + sl * (size_t)lv.nf * lv.nf;
+                rows = cols = ld = lv.nf; src = lv.F_of(sl);
             }
         } else if (what == MRA_BLOCK_LEAF) {
             if (!pl->leaf[node]) throw MraError(MRA_ERR_INVALID, "block exists for leaves only");
             const int t = pl->leaf_slot[node];
             const int nop = pl->leaf_nop[t];
             rows = nop + pl->na[m] + (pl->row1[node] - pl->row0[node]); cols = ld = nop;
-            src = pl->panel.p + pl->leaf_poff[t];
+            src = leaf_C(pl, t);
         } else throw MraError(MRA_ERR_INVALID, "unknown block id");
         *n_rows = rows; *n_cols = cols;
         const int64_t n = std::min<int64_t>(cap, rows * cols);

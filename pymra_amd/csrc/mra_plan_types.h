@@ -23,7 +23,7 @@
 // ---- host dry run (test instrumentation, never a compute path) ------------------------------------------------------
 // With MRA_HOST_DRYRUN=1 in the environment the plan is built entirely in host memory: every "device" buffer is a
 // malloc, uploads are memcpy, no stream / event / kernel is ever created and mra_run refuses to run.  The point is
-// to push the ~1500 lines of index arithmetic of plan construction (build_static, build_leaf, the host-cov block
+// to push the ~1500 lines of index arithmetic of plan construction (the steps of build_static and build_leaf, the host-cov block
 // bookkeeping) and the native tree replay through AddressSanitizer / UBSan on a machine without a GPU
 // (`make asan`, tests/test_asan_host.py).  Nothing is computed in this mode.
 static const bool g_dry = []() { const char* e = getenv("MRA_HOST_DRYRUN"); return e && e[0] == '1'; }();
@@ -240,6 +240,12 @@ struct LevelData {
     int front_mode = 0;               // 0: separate launches, 1: k_front<PANEL>, 2: k_front<FULL> (whole front in LDS)
     size_t front_lds = 0;
     Work fl_resid, fl_pchol, fl_trsm, fl_fchol, fl_schur, fl_update;
+    // the buffers' layout, per node slot s: the prior factor (cw x cw), the front (nf rows of stride ldf, [Lt ; Zt] in its first cw
+    // columns), and the inverted 16 x 16 diagonal blocks of either factor (cwt of them)
+    double* Lp_of(size_t s) const { return Lp.p + s * (size_t)cw * cw; }
+    double* F_of(size_t s) const { return F.p + s * (size_t)nf * ldf; }
+    double* invP_of(size_t s) const { return invP.p + s * (size_t)cwt * 256; }
+    double* invF_of(size_t s) const { return invF.p + s * (size_t)cwt * 256; }
 };
 
 // ---- the route of a pass: WHICH launch sequence it runs, decided once by route_for (mra_plan.hip) from the tree's shape, the run
@@ -247,6 +253,10 @@ struct LevelData {
 constexpr int LEAF_MAX_TILES = 12;  // widest leaf observation block, in 16-row tiles, of k_chol_wave<LEAF_MAX_TILES> and the LDS row solve behind it
 constexpr int TRSM2_MAX_NT = 12;    // widest block of launch_trsm2 (k_trsm_rows2<TRSM2_MAX_NT>); wider levels take k_trsm_rows
 static_assert(LEAF_MAX_TILES <= TRSM2_MAX_NT, "the leaves' row solve goes through launch_trsm2 without a fall-back");
+// a "small" leaf: at most this many observation tiles.  The tile count of the instances k_chol_tiles<8, 4>, k_trsm_rows2<8> and
+// k_leaf_solve_update<8, 13, true> that take the small leaves; order_small_first (mra_plan.hip) puts them first in every ordered list
+constexpr int LEAF_SMALL_TILES = 8;
+static_assert(LEAF_SMALL_TILES <= LEAF_MAX_TILES, "the small leaves are a subset of those the LDS row solve takes");
 // (the integer values are the MRA_ROUTE_* numbers of include/mra_hip.h: mra_get_route reports them)
 enum class PassPath { Fused = MRA_ROUTE_PATH_FUSED, Hi = MRA_ROUTE_PATH_HI, Levels = MRA_ROUTE_PATH_LEVELS };      // one-kernel cascades of a regular tree / level-by-level with k_predict_hi (deep 64-wide trees) / level-by-level
 // no observations / the gathered COV product wrote all of C / k_leaf_cphantom / k_leaf_fill
@@ -328,7 +338,7 @@ struct mra_plan {
     std::vector<DevVec<GemmProb>> gBigTrail[2];
     std::vector<long> bigM[2], bigN[2];
     DevVec<Trsm2Prob> gLeafTrsmFull, gLeafTrsmLik, gLeafTrsmFullPlain, gLeafTrsmLikPlain, gLeafTrsmFullPlainG, gLeafTrsmLikPlainG;
-    DevVec<LeafSolveProb> gLeafSolve;     // k_leaf_solve_update, same order as the *Plain arrays (leaves with nt <= 8 first)
+    DevVec<LeafSolveProb> gLeafSolve;     // k_leaf_solve_update, same order as the *Plain arrays (order_small_first)
     DevVec<LeafSolveProb> gLeafSolveHalf; // the small leaves again, two workgroups each (row tiles split in two): shorter workgroups on the
     size_t n_leaf_solve_half = 0;         // side stream free their CUs sooner for the high-priority front chain (MRA_OPT_LEAF_SOLVE_SPLIT)
     int leaf_solve_split = 2;             // measured on an eighth of C3: 1.086 -> 1.066 ms
@@ -350,7 +360,7 @@ struct mra_plan {
     DevVec<unsigned char> leaf_upd_dev;
     size_t leaf_solve_lds = 0;
     int leaf_solve_mode = 2;              // MRA_OPT_LEAF_SOLVE: 0 off, 1 always, 2 (default) when the leaves are few per CU
-    size_t n_trsm_small = 0;            // the *Plain arrays are ordered: leaves with nt <= 8 first
+    size_t n_trsm_small = 0;            // = n_chol_small: the small leaves, first in the *Plain arrays and in gLeafCholSorted (order_small_first)
     int trsm_small_nt = 0, trsm_small_tiles_full = 0, trsm_small_tiles_lik = 0;
     DevVec<GemmProb> gParentSyrk;        // fused path: fronts of the leaves' parents straight from the children's Ut
     DevVec<GemmSeg> parentSegs;
@@ -492,6 +502,15 @@ struct mra_plan {
     std::set<const void*> big_lds_done;
     bool prepare_only = false;           // mra_plan_prepare: the launch helpers set their attributes and return
 };
+
+// The panel of leaf t, row stride nop = leaf_nop[t]: [C ; Ut ; V] = the observation block (nop rows; factorised in place: Lc), the
+// ancestor columns and the y block (na rows), one row per row of the leaf (V, then Tt).  Sized in build_leaf (leaf_poff).
+static inline double* leaf_C(const mra_plan* pl, size_t t) { return pl->panel.p + pl->leaf_poff[t]; }
+static inline double* leaf_Ut(const mra_plan* pl, size_t t) { const size_t nop = pl->leaf_nop[t]; return leaf_C(pl, t) + nop * nop; }
+static inline double* leaf_V(const mra_plan* pl, size_t t) {
+    const size_t nop = pl->leaf_nop[t], na = pl->na[pl->node_level[pl->leaf_nodes[t]]];
+    return leaf_C(pl, t) + (nop + na) * nop;
+}
 
 // Dynamic LDS above 64 KiB has to be requested per kernel and per DEVICE.  The record is kept per plan (a plan lives on one
 // device; mra_plan_prepare reports its size) AND per (device, kernel) for the process, so that the second plan of a process - the

@@ -59,7 +59,7 @@ for name in ["kat1", "kat2", "kat3", "c1", "t201", "t1000", "kat4", "u3", "g32",
                 except (ValueError, NotImplementedError):
                     continue
                 build(lt, cs["locs"], cs["y_obs"], cs["c"]["R"])
-# failed constructions return -1 and release the half-built plan: one inside build_static (a cw that is not a multiple of 16),
+# failed constructions return -1 and release the half-built plan: one inside build_static's first step, static_layout_and_checks (a cw that is not a multiple of 16),
 # one in the topology copy with a library exception (knot_ptr[n_nodes] = -1: std::length_error from the knot_rows copy before it
 # reads anything; 2**60 would overflow the pointer arithmetic, itself a UBSan report)
 import copy
