@@ -1255,6 +1255,23 @@ static void launch_panel(mra_plan* pl, const PanelProb* probs, size_t nprob, int
     hipLaunchKernelGGL(k_panel_chol, dim3((unsigned)nprob), dim3(256), 0, pl->stream, probs, pl->dnode.p, pl->errflag.p, accumulate);
 }
 
+// -DMRA_STAMPS (the tools/stamps_*.py builds): some kernels take one more argument, a buffer of per-workgroup clock stamps.  The
+// argument lists below end in one of these macros; a default build compiles them to nothing.
+#ifdef MRA_STAMPS
+// at least n stamps: grown when too small, and then zeroed with the device idle before the kernel that writes it starts
+static unsigned long long* stamp_buffer(DevVec<double>& b, size_t n) {
+    if (b.n < n) { b.alloc(n); HIP_TRY(mraMemset(b.p, 0, b.n * sizeof(double))); HIP_TRY(hipDeviceSynchronize()); }
+    return (unsigned long long*)b.p;
+}
+#define MRA_TSTAMP_VAL , tst                                            // launch_trsm2
+#define MRA_LSTAMP_VAL , (unsigned long long*)pl->kstamps2.p            // k_leaf_solve_update, two workgroups per leaf
+#define MRA_LSTAMP_NUL , (unsigned long long*)nullptr                   // ... one per leaf: no stamps
+#else
+#define MRA_TSTAMP_VAL
+#define MRA_LSTAMP_VAL
+#define MRA_LSTAMP_NUL
+#endif
+
 // row-tile triangular solve with L in LDS; returns false when nt is too large for the LDS path
 static bool launch_trsm2(mra_plan* pl, const Trsm2Prob* probs, size_t nprob, int nt, long max_tiles, int tiles_per_wg) {
     if (!pl->prepare_only && (!nprob || max_tiles <= 0 || nt <= 0)) return true;
@@ -1266,14 +1283,7 @@ static bool launch_trsm2(mra_plan* pl, const Trsm2Prob* probs, size_t nprob, int
     const unsigned tb = 512;
 #ifdef MRA_STAMPS
     // the last big launch wins the buffer (tools/stamps_trsm.py reads it after a pass)
-    unsigned long long* tst = nullptr;
-    if (nprob >= 1024 && max_tiles <= 64) {
-        if (pl->tstamps.n < nprob * 64 * 8) { pl->tstamps.alloc(nprob * 64 * 8); HIP_TRY(mraMemset(pl->tstamps.p, 0, pl->tstamps.n * sizeof(double))); HIP_TRY(hipDeviceSynchronize()); }
-        tst = (unsigned long long*)pl->tstamps.p;
-    }
-#define MRA_TSTAMP_VAL , tst
-#else
-#define MRA_TSTAMP_VAL
+    unsigned long long* tst = (nprob >= 1024 && max_tiles <= 64) ? stamp_buffer(pl->tstamps, nprob * 64 * 8) : nullptr;
 #endif
     for (size_t off = 0; off < nprob; off += 65535) {
         dim3 grid(gx, (unsigned)std::min<size_t>(65535, nprob - off));
@@ -1285,8 +1295,40 @@ static bool launch_trsm2(mra_plan* pl, const Trsm2Prob* probs, size_t nprob, int
     return true;
 }
 
-// whole prior of a regular tree: per level a tiny knot pass (knot rows cascade -> kInv -> Cholesky),
-// then ONE cascade over all leaf row tiles that writes W once
+// row solve of all rows of level m's nodes: launch_trsm2, or k_trsm_rows where the level's block is too wide for it.  The prior and the
+// posterior solve differ in their descriptor lists and in var (the posterior one subtracts the solved rows' squares from it)
+static void launch_level_row_solve(mra_plan* pl, int m, const Trsm2Prob* probs2, const TrsmNode* nodes, double* var) {
+    LevelData& lv = pl->lev[m];
+    if (launch_trsm2(pl, probs2, lv.nodes.size(), lv.cwt, lv.max_tiles, 32)) return;
+    ensure_tile_lists(pl, m);
+    hipLaunchKernelGGL(k_trsm_rows, dim3((unsigned)((lv.ntiles + 3) / 4)), dim3(256), 0, pl->stream, nodes, lv.tile_node.p, lv.tile_row0.p,
+                       lv.ntiles, pl->W.p, (long)pl->ldw, lv.c0, var);
+}
+
+// k_parent_front<nacc>, one workgroup per front (nacc: 2, 4, 8, anything else 12)
+static void launch_parent_front(mra_plan* pl, int nacc, size_t nprob, size_t lds, const FrontProb* probs) {
+    ensure_big_lds(pl, {(const void*)k_parent_front<2>, (const void*)k_parent_front<4>, (const void*)k_parent_front<8>, (const void*)k_parent_front<12>});
+    const dim3 grid((unsigned)nprob);
+    switch (nacc) {
+        case 2: hipLaunchKernelGGL(k_parent_front<2>, grid, dim3(512), lds, pl->stream, probs, pl->parentSegs.p, pl->dnode.p, pl->errflag.p); break;
+        case 4: hipLaunchKernelGGL(k_parent_front<4>, grid, dim3(512), lds, pl->stream, probs, pl->parentSegs.p, pl->dnode.p, pl->errflag.p); break;
+        case 8: hipLaunchKernelGGL(k_parent_front<8>, grid, dim3(512), lds, pl->stream, probs, pl->parentSegs.p, pl->dnode.p, pl->errflag.p); break;
+        default: hipLaunchKernelGGL(k_parent_front<12>, grid, dim3(512), lds, pl->stream, probs, pl->parentSegs.p, pl->dnode.p, pl->errflag.p); break;
+    }
+}
+
+// Cholesky of the nl leaves' C blocks where every one fits (LeafChol but BigPanels).  k_chol_tiles: one workgroup per matrix, tiles in
+// registers, next diagonal block factorised beside the trailing update; k_chol_wave: one wave per matrix
+static void launch_leaf_chol(mra_plan* pl, const PassRoute& r, size_t nl) {
+    const size_t ns = pl->n_chol_small;      // (gLeafCholSorted: the leaves of at most LEAF_SMALL_TILES tiles first)
+    if (r.chol == LeafChol::TilesSplit) {
+        if (ns) hipLaunchKernelGGL((k_chol_tiles<8, 4>), dim3((unsigned)ns), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p, pl->dnode.p, pl->errflag.p);
+        if (nl > ns) hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)(nl - ns)), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p + ns, pl->dnode.p, pl->errflag.p);
+    }
+    else if (r.chol == LeafChol::TilesOne) hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)nl), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p, pl->dnode.p, pl->errflag.p);
+    else hipLaunchKernelGGL((k_chol_wave<LEAF_MAX_TILES>), dim3((unsigned)((nl + 3) / 4)), dim3(256), 0, pl->stream, pl->gLeafCholC.p, (int)nl, pl->dnode.p, pl->errflag.p);
+}
+
 static double kernel_cov0(const mra_plan* pl) { return pl->kp.amp; }   // C(x,x) of every stationary kernel: amp * 1
 
 // tiles of the likelihood-only row cascade: 16 observed rows each (obs_idx, padded with -1), with their leaf's ancestor chain; one
@@ -1404,7 +1446,7 @@ static PassRoute route_for(const mra_plan* pl, uint32_t flags, bool full_rows) {
     // likelihood-only passes never need V[S,o]: just C = v_m(o,o) + R I from a small gathered product (the row solve gathers Ut itself, or
     // the row cascade has scattered it), and W at the rows they need only.  Fused: the row cascade walks gathered tiles of OBSERVED rows
     // (the knots had their own pass; 7 of a leaf's 16 tiles at C3).  Level-by-level: the one-launch prior levels walk the observed rows
-    // and the knots when every level takes that path (ensure_lik_general's verdict; one not yet known counts as yes: run_all then has
+    // and the knots when every level takes that path (ensure_lik_general's verdict; one not yet known counts as yes: open_pass then has
     // the list built and asks again).
     r.c_only = !pred && !pl->host_cov && pl->gemm_lds && fit && obs;
     const bool rows = r.c_only && !full_rows && pl->use_lik_rows;
@@ -1459,9 +1501,10 @@ static PassRoute route_for(const mra_plan* pl, uint32_t flags, bool full_rows) {
     return r;
 }
 
-static void run_prior_fused(mra_plan* pl) {
-    const PassRoute& r = pl->route;
-    const int cw = pl->cw[0];
+// ---- prior of a regular tree (PassPath::Fused): per level a tiny knot pass (knot rows cascade -> kInv -> Cholesky), then ONE cascade
+// over all leaf row tiles that writes W once ----------------------------------------------------------------------------------------
+// what every launch of the fused prior takes: the levels' knots and factors, X and W
+static CascadeArgs prior_cascade_base(const mra_plan* pl) {
     CascadeArgs base{};
     base.ycol = -1;
     for (int m = 0; m < pl->NL; ++m) {
@@ -1470,7 +1513,12 @@ static void run_prior_fused(mra_plan* pl) {
         base.coff[m] = pl->coff[m];
     }
     base.X = pl->X.p; base.W = pl->W.p; base.ldw = pl->ldw;
-    const int n_chain = r.n_chain;
+    return base;
+}
+
+// leaves every level's Wk, prior factor Lp and inverted diagonal blocks: levels [0, n_chain) in one k_knot_chain launch, one launch each below
+static void run_prior_fused_knots(mra_plan* pl, const CascadeArgs& base) {
+    const int n_chain = pl->route.n_chain;
     if (n_chain) {
         Work fl;
         for (int m = 0; m < n_chain; ++m) fl += pl->lev[m].fl_pchol;
@@ -1482,11 +1530,7 @@ static void run_prior_fused(mra_plan* pl) {
         }
         ka.chain = pl->kc_chain.p; ka.ownmask = pl->kc_ownmask.p; ka.knots = pl->kc_knots.p; ka.nl = n_chain; ka.err = pl->errflag.p;
 #ifdef MRA_STAMPS
-        {
-            const size_t need = pl->lev[n_chain - 1].nodes.size() * 64;
-            if (pl->kstamps.n < need) { pl->kstamps.alloc(need); HIP_TRY(mraMemset(pl->kstamps.p, 0, need * sizeof(double))); HIP_TRY(hipDeviceSynchronize()); }
-            ka.stamps = (unsigned long long*)pl->kstamps.p;
-        }
+        ka.stamps = stamp_buffer(pl->kstamps, pl->lev[n_chain - 1].nodes.size() * 64);
 #endif
         launch_knot_chain(pl, ka);
     }
@@ -1503,43 +1547,51 @@ static void run_prior_fused(mra_plan* pl) {
         ar.node_base = (int)pl->level_ptr[m];            // regular trees: slot s of level m is node level_ptr[m] + s
         launch_cascade_any(pl, ar);
     }
-    {
-        Work fl;
-        for (int m = 0; m < pl->NL; ++m) fl += pl->lev[m].fl_resid + pl->lev[m].fl_trsm;
-        // one pass: coordinates and y in, W (all levels + y block) and the prior variance out, observed rows once more into Ut
-        fl.bytes = 8.0 * pl->P * (pl->d + 1 + pl->ldw + 1) + pl->by_leaf_ut;
-        // a likelihood needs W at the OBSERVED rows only (Ut and the leaves' C = v(o,o) + R I are built from them)
-        if (r.lik_rows) {
-            ensure_lik_tiles(pl);
-            const double share = 16.0 * (double)pl->n_lik_tiles / (double)std::max<long>(pl->P, 1);
-            fl.alg *= share; fl.exec *= share; fl.bytes = share * 8.0 * pl->P * (pl->d + 1 + pl->ldw) + pl->by_leaf_ut;
-        }
-        KTimer kt(pl, KF_PRIOR_TRSM, fl);
-        CascadeArgs ar = base;
-        ar.knot_mode = 0; ar.mlast = pl->NL - 1; ar.dbg = pl->dbg;
-#ifdef MRA_STAMPS
-        if (!pl->stamps.p) { pl->stamps.alloc((size_t)pl->n_ftiles * 16); HIP_TRY(mraMemset(pl->stamps.p, 0, pl->stamps.n * sizeof(double))); }
-        ar.stamps = (unsigned long long*)pl->stamps.p;
-#endif
-        ar.var_out = pl->var.p; ar.cov0 = kernel_cov0(pl);
-        ar.ycol = pl->Ka; ar.y = pl->y.p;
-        if (r.scatter_ut) {
-            ar.obs_pos = pl->obs_pos.p; ar.tile_leaf = pl->ft_leaf.p; ar.leaf_ut = pl->leaf_ut.p; ar.leaf_nop = pl->leaf_nop_dev.p;
-            ar.y = pl->y.p;
-            // Ut rows follow W's ancestor columns of a last-level leaf: a = column - asuf[NL]
-            for (int m = 0; m < pl->NL; ++m) ar.ut_off[m] = pl->coff[m] - pl->asuf[pl->NL];
-            ar.ut_yrow = pl->Ka - pl->asuf[pl->NL];
-        }
-        if (pl->cascade_stage_all) { ar.n_wg = pl->n_fwg_leaf; ar.wg_tile0 = pl->ft_wg0_leaf.p; ar.wg_ntiles = pl->ft_wgn_leaf.p; }
-        else { ar.n_wg = pl->n_fwg; ar.wg_tile0 = pl->ft_wg0.p; ar.wg_ntiles = pl->ft_wgn.p; }
-        ar.tile_row0 = pl->ft_row0.p; ar.tile_chain = pl->ft_chain.p;
-        if (r.lik_rows) {
-            ar.row_gather = pl->obs_idx.p; ar.tile_chain = pl->lik_chain.p; ar.tile_leaf = pl->lik_leaf.p;
-            ar.n_wg = pl->n_lik_wg; ar.wg_tile0 = pl->lik_wg0.p; ar.wg_ntiles = pl->lik_wgn.p;
-            ar.var_out = nullptr;                          // the prior variance is the predictive pass's (the y block stays: Ut's y row is gathered from it)
-        }
-        launch_cascade_any(pl, ar);
+}
+
+// leaves W (all levels and the y block) at every row - lik_rows: at the observed rows - the prior variance, and with scatter_ut the leaves' Ut
+static void run_prior_fused_rows(mra_plan* pl, const CascadeArgs& base) {
+    const PassRoute& r = pl->route;
+    Work fl;
+    for (int m = 0; m < pl->NL; ++m) fl += pl->lev[m].fl_resid + pl->lev[m].fl_trsm;
+    // one pass: coordinates and y in, W (all levels + y block) and the prior variance out, observed rows once more into Ut
+    fl.bytes = 8.0 * pl->P * (pl->d + 1 + pl->ldw + 1) + pl->by_leaf_ut;
+    // a likelihood needs W at the OBSERVED rows only (Ut and the leaves' C = v(o,o) + R I are built from them)
+    if (r.lik_rows) {
+        ensure_lik_tiles(pl);
+        const double share = 16.0 * (double)pl->n_lik_tiles / (double)std::max<long>(pl->P, 1);
+        fl.alg *= share; fl.exec *= share; fl.bytes = share * 8.0 * pl->P * (pl->d + 1 + pl->ldw) + pl->by_leaf_ut;
     }
+    KTimer kt(pl, KF_PRIOR_TRSM, fl);
+    CascadeArgs ar = base;
+    ar.knot_mode = 0; ar.mlast = pl->NL - 1; ar.dbg = pl->dbg;
+#ifdef MRA_STAMPS
+    ar.stamps = stamp_buffer(pl->stamps, (size_t)pl->n_ftiles * 16);
+#endif
+    ar.var_out = pl->var.p; ar.cov0 = kernel_cov0(pl);
+    ar.ycol = pl->Ka; ar.y = pl->y.p;
+    if (r.scatter_ut) {
+        ar.obs_pos = pl->obs_pos.p; ar.tile_leaf = pl->ft_leaf.p; ar.leaf_ut = pl->leaf_ut.p; ar.leaf_nop = pl->leaf_nop_dev.p;
+        ar.y = pl->y.p;
+        // Ut rows follow W's ancestor columns of a last-level leaf: a = column - asuf[NL]
+        for (int m = 0; m < pl->NL; ++m) ar.ut_off[m] = pl->coff[m] - pl->asuf[pl->NL];
+        ar.ut_yrow = pl->Ka - pl->asuf[pl->NL];
+    }
+    if (pl->cascade_stage_all) { ar.n_wg = pl->n_fwg_leaf; ar.wg_tile0 = pl->ft_wg0_leaf.p; ar.wg_ntiles = pl->ft_wgn_leaf.p; }
+    else { ar.n_wg = pl->n_fwg; ar.wg_tile0 = pl->ft_wg0.p; ar.wg_ntiles = pl->ft_wgn.p; }
+    ar.tile_row0 = pl->ft_row0.p; ar.tile_chain = pl->ft_chain.p;
+    if (r.lik_rows) {
+        ar.row_gather = pl->obs_idx.p; ar.tile_chain = pl->lik_chain.p; ar.tile_leaf = pl->lik_leaf.p;
+        ar.n_wg = pl->n_lik_wg; ar.wg_tile0 = pl->lik_wg0.p; ar.wg_ntiles = pl->lik_wgn.p;
+        ar.var_out = nullptr;                          // the prior variance is the predictive pass's (the y block stays: Ut's y row is gathered from it)
+    }
+    launch_cascade_any(pl, ar);
+}
+
+static void run_prior_fused(mra_plan* pl) {
+    const CascadeArgs base = prior_cascade_base(pl);
+    run_prior_fused_knots(pl, base);
+    run_prior_fused_rows(pl, base);
 }
 
 // predictive pass of a deep 64-wide tree (regular_hi): W holds the whitened basis after the leaf update
@@ -1608,18 +1660,268 @@ static void run_predict_fused(mra_plan* pl) {
         fl += Work(pl->fl_leaf_update.alg, pl->fl_leaf_update.exec, pl->by_leaf_tt + pl->by_leaf_ut);    // Tt and Ut in, nothing out
     }
 #ifdef MRA_STAMPS
-    if (!pl->pstamps.p) { pl->pstamps.alloc((size_t)pl->n_ftiles * 16); HIP_TRY(mraMemset(pl->pstamps.p, 0, pl->pstamps.n * sizeof(double))); }
-    ar.stamps = (unsigned long long*)pl->pstamps.p;
+    ar.stamps = stamp_buffer(pl->pstamps, (size_t)pl->n_ftiles * 16);
 #endif
     KTimer kt(pl, KF_PRED_UPDATE, fl);
     if (ar.n_wg <= 0) return;
     launch_predict_any(pl, ar, lds);
 }
 
+// ---- the executor: a pass in stages ("the executor").  Every stage reads pl->route, launches on pl->stream and leaves what
+// its comment says for the next one; run_all and run_fronts_and_predict are the two drivers ----------------------------------------
 // events 0 and 5 bracket every pass; the four inner phase boundaries are recorded only with kernel timing on
 // (each hipEventRecord between dependent launches leaves a ~6 us gap on the stream)
 static void phase_mark(mra_plan* pl, int k) { if (k == 0 || k == 5 || pl->ktiming) hipEventRecord(pl->ev[k], pl->stream); }
 
+// allocate the per-leaf Schur blocks the first time a run needs them and point the descriptors at them
+static void ensure_gt(mra_plan* pl) {
+    if (pl->Gt.p || pl->leaf_goff.back() == 0) return;
+    pl->Gt.alloc(pl->leaf_goff.back());
+    for (size_t k = 0; k < pl->hKids.size(); ++k)
+        if (pl->kid_leaf[k] >= 0) pl->hKids[k].G = pl->Gt.p + pl->leaf_goff[pl->kid_leaf[k]];
+    pl->asmKids.upload(pl->hKids);
+    for (size_t t = 0; t < pl->hLeafSyrk.size(); ++t) pl->hLeafSyrk[t].C = pl->Gt.p + pl->leaf_goff[t];
+    pl->gLeafSyrk.upload(pl->hLeafSyrk);
+}
+
+// leaves an open pass: both streams idle of any abandoned pass, the pass state and the kernel statistics reset, pl->route fixed
+static const PassRoute& open_pass(mra_plan* pl, uint32_t flags, bool full_rows) {
+    if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
+    if (!(pl->have_locs && pl->have_obs && pl->have_kernel))
+        throw MraError(MRA_ERR_STATE, "mra_run needs set_locs, set_obs and set_kernel first");
+    HIP_TRY(mraSetDevice(pl->device));
+    if (pl->pass_open) {
+        // the previous pass never reached finish_run (an error was thrown, or a split run was abandoned before
+        // mra_run_resume): wait for whatever it left on the two streams, and clear the device error flag that
+        // only the last kernel of a pass resets
+        pl->cphantom_valid = false;
+        if (pl->side_pending) HIP_TRY(hipStreamWaitEvent(pl->stream, pl->ev_join, 0));
+        HIP_TRY(hipStreamSynchronize(pl->stream));
+        HIP_TRY(hipStreamSynchronize(pl->stream2));
+        HIP_TRY(hipMemsetAsync(pl->errflag.p, 0, sizeof(int), pl->stream));
+        for (auto& e : pl->kev) { hipEventDestroy(e.second.first); hipEventDestroy(e.second.second); }
+        pl->kev.clear();
+    }
+    pl->side_pending = false;
+    pl->split_pending = false;
+    pl->pass_open = true;
+    pl->run_flags = flags;
+    pl->slv.valid = false;               // whatever runs a pass rewrites the factors (mra_solve sets the mark again after its own)
+    for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = mra_plan::KStat();
+    if (!pl->lik_general_valid && route_for(pl, flags, full_rows).lik_general) ensure_lik_general(pl);      // (once; route_for reads the verdict)
+    pl->route = route_for(pl, flags, full_rows);
+    pl->route_set = true;
+    return pl->route;
+}
+
+// leaves W's y block holding y at every row and, with acc_var, var holding the prior variance C(x,x) for the row solves to subtract from
+static void run_init_yblock(mra_plan* pl, const PassRoute& r) {
+    KTimer kt(pl, KF_MISC, 0);
+    const long n = pl->P * MRA_YB;
+    hipLaunchKernelGGL(k_init_yblock, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, pl->stream, pl->W.p,
+                       (long)pl->ldw, pl->Ka, pl->y.p, pl->P, r.acc_var ? pl->var.p : (double*)nullptr, pl->host_cov ? 0.0 : kernel_cov0(pl),
+                       pl->host_cov ? pl->covdiag.p : (const double*)nullptr);
+}
+
+// ---- prior, level by level (PassPath::Hi and Levels; run_prior_fused is the Fused form).  Either form of a level leaves its prior
+// factor Lp with inverted diagonal blocks and W's columns of the level at every row below its nodes (lik_general: at the needed rows)
+// knots' residual block -> Lp (both sides gathered), its Cholesky, then residual + kernel + row solve of every row in one launch: the
+// residual never visits HBM
+static void run_prior_level_one_launch(mra_plan* pl, const PassRoute& r, LevelData& lv) {
+    const size_t nn = lv.nodes.size();
+    { KTimer kt(pl, KF_PRIOR_CHOL, lv.fl_knot_resid); launch_gemm<EPI_COV>(pl, lv.gKnotResid.p, nn, lv.cw, lv.cw); }
+    { KTimer kt(pl, KF_PRIOR_CHOL, lv.fl_pchol); launch_panel(pl, lv.gPriorChol.p, nn); }
+    if (r.lik_general) {
+        Work w = lv.fl_resid + lv.fl_trsm.with_bytes(0.0);
+        w.alg *= lv.lik_share; w.exec *= lv.lik_share; w.bytes *= lv.lik_share;
+        KTimer kt(pl, KF_PRIOR_RESID, w);
+        mra_launch_prior_level(pl, lv.gResidLik.p, lv.gResidLik.n);
+    } else {
+        KTimer kt(pl, KF_PRIOR_RESID, lv.fl_resid + lv.fl_trsm.with_bytes(0.0));
+        mra_launch_prior_level(pl, lv.gResidFused.p, lv.gResidFused.n);
+    }
+}
+
+// residual of every row into W, the knots' block gathered out of it, its Cholesky, the row solve
+static void run_prior_level_four_launches(mra_plan* pl, int m) {
+    LevelData& lv = pl->lev[m];
+    const size_t nn = lv.nodes.size();
+    {
+        KTimer kt(pl, KF_PRIOR_RESID, lv.fl_resid);
+        if (pl->host_cov) launch_gemm<EPI_HOSTCOV>(pl, lv.gResid.p, nn, lv.max_rows, lv.cw);
+        else launch_gemm<EPI_COV>(pl, lv.gResid.p, nn, lv.max_rows, lv.cw);
+    }
+    {
+        KTimer kt(pl, KF_MISC, 0);
+        dim3 grid((unsigned)((lv.cw * lv.cw + 255) / 256), (unsigned)nn);
+        hipLaunchKernelGGL(k_gather_kinv, grid, dim3(256), 0, pl->stream, lv.gKinv.p, pl->W.p, (long)pl->ldw, lv.c0);
+    }
+    { KTimer kt(pl, KF_PRIOR_CHOL, lv.fl_pchol); launch_panel(pl, lv.gPriorChol.p, nn); }
+    { KTimer kt(pl, KF_PRIOR_TRSM, lv.fl_trsm); launch_level_row_solve(pl, m, lv.gTrsm2Prior.p, lv.gTrsmPrior.p, nullptr); }
+}
+
+static void run_prior_levels(mra_plan* pl, const PassRoute& r) {
+    for (int m = 0; m < pl->n_levels; ++m) {
+        LevelData& lv = pl->lev[m];
+        if (lv.nodes.empty()) continue;
+        if (r.prior_level && lv.prior_level_ok) run_prior_level_one_launch(pl, r, lv);
+        else run_prior_level_four_launches(pl, m);
+    }
+}
+
+// ---- leaves (nl of them, nl > 0).  A leaf's panel is [C ; Ut ; V] (leaf_C / leaf_Ut / leaf_V) ------------------------------------
+// leaves every leaf's V[S,o] residual with C = v(o,o) + R I on top of it, or with c_only nothing but C
+static void run_leaf_product(mra_plan* pl, const PassRoute& r, size_t nl) {
+    KTimer kt(pl, KF_LEAF_RESID, r.c_only ? pl->fl_leaf_c_only : pl->fl_leaf_resid);
+    if (pl->host_cov) {
+        if (r.leaf_resident) launch_leaf_gemm<EPI_HOSTCOV>(pl, pl->gLeafResid.p, nl);
+        else launch_gemm<EPI_HOSTCOV>(pl, pl->gLeafResid.p, nl, pl->leaf_max_rows, pl->leaf_max_nop);
+    }
+    else if (r.c_only) launch_gemm<EPI_COV>(pl, pl->gLeafResidLik.p, nl, pl->leaf_max_nop, pl->leaf_max_nop);
+    else if (r.leaf_resident) launch_leaf_gemm<EPI_COV>(pl, pl->gLeafResid.p, nl);
+    else launch_gemm<EPI_COV>(pl, pl->gLeafResid.p, nl, pl->leaf_max_rows, pl->leaf_max_nop);
+}
+
+// leaves C whole, identity rows at its phantom observations (the padding to 16) included; Fill: all of C gathered out of V, and Ut out of W
+static void run_leaf_c_fix(mra_plan* pl, const PassRoute& r, size_t nl) {
+    if (r.c_fix == LeafCFix::None) return;
+    KTimer kt(pl, KF_MISC, 0);
+    // (InProduct: nothing to do, the gathered COV product wrote the whole C block including phantom identities)
+    if (r.c_fix == LeafCFix::Phantom) {
+        // C comes from the COV epilogue, Ut from the gather inside k_trsm_rows2: only the phantom rows remain
+        // ... once: an identity row stays an identity row under the in-place factorisation (L[p][j] = 0, L[p][p] = 1 exactly) and
+        // no epilogue writes there, so later passes find them in place.  (A failed pass - NaN times 0 - a new observation pattern
+        // or a change of options bring the launch back.)
+        if (!pl->cphantom_valid) {
+            hipLaunchKernelGGL(k_leaf_cphantom, dim3((unsigned)nl), dim3(256), 0, pl->stream, pl->gLeaf.p, pl->leaf_nobs.p);
+            pl->cphantom_valid = true;
+        }
+    } else if (r.c_fix == LeafCFix::Fill) {
+        const long total = (long)(pl->leaf_max_nop + pl->leaf_max_na) * pl->leaf_max_nop;
+        dim3 grid((unsigned)std::min<long>((total + 255) / 256, 64), (unsigned)nl);
+        hipLaunchKernelGGL(k_leaf_fill, grid, dim3(256), 0, pl->stream, pl->gLeaf.p, pl->W.p, (long)pl->ldw, pl->R);
+    }
+}
+
+// every leaf's C fits k_chol_tiles / k_chol_wave: the Cholesky, then the LDS row solve of the rows below C
+static void run_leaf_chol_and_solve(mra_plan* pl, const PassRoute& r, size_t nl) {
+    launch_leaf_chol(pl, r, nl);
+    const int obs_tiles = pl->leaf_max_nop / 16;                                              // the widest C, in 16-row tiles
+    const int row_tiles = r.predict ? pl->leaf_max_tiles_full : pl->leaf_max_tiles_lik;       // the most row tiles below one leaf's C
+    if (r.path != PassPath::Fused) { launch_trsm2(pl, r.trsm_all, nl, obs_tiles, row_tiles, row_tiles); return; }
+    // Fused: the small leaves (the first n_trsm_small of every list) on k_trsm_rows2<LEAF_SMALL_TILES>, one workgroup each
+    const size_t n_small = pl->n_trsm_small;
+    const int small_row_tiles = (r.predict && !r.solve_fused) ? pl->trsm_small_tiles_full : pl->trsm_small_tiles_lik;
+    if (n_small) launch_trsm2(pl, r.trsm_small, n_small, pl->trsm_small_nt, small_row_tiles, small_row_tiles);
+    // the few leaves with more than LEAF_SMALL_TILES observation tiles: several workgroups per leaf when they are few
+    // (one leaf per workgroup would put a single 65 us workgroup on the critical path)
+    if (nl > n_small) launch_trsm2(pl, r.trsm_all + n_small, nl - n_small, obs_tiles, row_tiles, (nl - n_small) < 512 ? 4 : row_tiles);
+}
+
+// LeafChol::BigPanels.  Right-looking, 64 columns per step: the panel (factor + solve of ALL rows below, Ut and Tt included) on one
+// workgroup per leaf, the rank-64 update of everything to its right as a batched GEMM over the whole GPU
+// (a single workgroup factorising an 8560 x 8560 block column by column took 15 s: README example 1)
+static void run_leaf_big_panels(mra_plan* pl, const PassRoute& r, size_t nl) {
+    const int v = r.predict ? 0 : 1;
+    for (size_t st = 0; st < pl->gBigPanel[v].size(); ++st) {
+        launch_panel(pl, pl->gBigPanel[v][st].p, nl, st > 0 ? 1 : 0);
+        if (pl->bigM[v][st] > 0 && pl->bigN[v][st] > 0)
+            launch_gemm<EPI_SUB>(pl, pl->gBigTrail[v][st].p, nl, pl->bigM[v][st], pl->bigN[v][st]);
+    }
+}
+
+// leaves C = Lc Lc^T factorised in place (log-determinants in dnode) and Ut = Lc^-1 Ut; where the route's row-solve lists hold them
+// (every predict pass but the small leaves under solve_fused) the rows of V solved too: Tt
+static void run_leaf_factor(mra_plan* pl, const PassRoute& r, size_t nl) {
+    KTimer kt(pl, KF_LEAF_CHOL, r.predict ? pl->fl_leaf_chol : pl->fl_leaf_chol_lik);
+    if (r.chol != LeafChol::BigPanels) run_leaf_chol_and_solve(pl, r, nl);
+    else run_leaf_big_panels(pl, r, nl);
+}
+
+// (!direct_parent) leaves every leaf's Schur block Gt = Ut Ut^T for its parent's assembly
+static void run_leaf_syrk(mra_plan* pl, size_t nl) {
+    ensure_gt(pl);
+    KTimer kt(pl, KF_LEAF_SYRK, pl->fl_leaf_syrk);
+    launch_gemm<EPI_SET>(pl, pl->gLeafSyrk.p, nl, pl->leaf_max_na, pl->leaf_max_na, false, true);
+}
+
+// leaves var = max(C(x,x) - |W_anc[x]|^2 - |Tt[x]|^2, 0) and the y column of the leaves' rows reset (LeafVar::None: the fused kernels' own work)
+static void run_leaf_var(mra_plan* pl, const PassRoute& r) {
+    if (r.var == LeafVar::None) return;
+    KTimer kt(pl, KF_MISC, 0);
+    ensure_row_leaf(pl);
+    if (r.var == LeafVar::FinishVar)
+        hipLaunchKernelGGL(k_leaf_finish_var, dim3((unsigned)((pl->P + 255) / 256)), dim3(256), 0, pl->stream, pl->row_leaf.p, pl->W.p,
+                           (long)pl->ldw, pl->Ka, pl->var.p, pl->P);
+    else
+        hipLaunchKernelGGL(k_leaf_moments, dim3((unsigned)((pl->P + 3) / 4)), dim3(256), 0, pl->stream, pl->gLeaf.p,
+                           pl->row_leaf.p, pl->W.p, (long)pl->ldw, pl->Ka, pl->var.p, pl->host_cov ? 0.0 : kernel_cov0(pl),
+                           pl->host_cov ? pl->covdiag.p : (const double*)nullptr, pl->P);
+}
+
+// LeafUpdate::SolveWhole / SolveHalves.  Tt = V Lc^-T, var -= |Tt|^2 and W -= Tt Ut^T in one launch for the leaves with
+// <= LEAF_SMALL_TILES observation tiles; the few larger ones went through the full row solve and take the plain update product
+static void run_leaf_solve_update(mra_plan* pl, const PassRoute& r, size_t nl) {
+    ensure_big_lds(pl, {(const void*)k_leaf_solve_update<8, 13, true>});
+    KTimer kt(pl, KF_LEAF_UPDATE, pl->fl_leaf_update);
+    const size_t n_small = pl->n_trsm_small;
+#ifdef MRA_STAMPS
+    stamp_buffer(pl->kstamps2, pl->n_leaf_solve_half * 8);
+#endif
+    if (r.update == LeafUpdate::SolveHalves)
+        hipLaunchKernelGGL((k_leaf_solve_update<8, 13, true>), dim3((unsigned)pl->n_leaf_solve_half), dim3(512), pl->leaf_solve_lds, pl->stream, pl->gLeafSolveHalf.p MRA_LSTAMP_VAL);
+    else
+        hipLaunchKernelGGL((k_leaf_solve_update<8, 13, true>), dim3((unsigned)n_small), dim3(512), pl->leaf_solve_lds, pl->stream, pl->gLeafSolve.p MRA_LSTAMP_NUL);
+    if (nl > n_small) launch_gemm<EPI_SUB>(pl, pl->gLeafUpdatePlain.p + n_small, nl - n_small, pl->leaf_max_rows, pl->leaf_max_na);
+}
+
+// leaves W[S,anc] -= Tt Ut^T at every leaf that does not take its update inside the predictive kernel (LeafUpdate)
+static void run_leaf_update(mra_plan* pl, const PassRoute& r, size_t nl) {
+    switch (r.update) {
+        case LeafUpdate::None: case LeafUpdate::InPredictHi: return;           // (InPredictHi: nothing to launch here)
+        case LeafUpdate::InCascade: {
+            // the small leaves (<= LEAF_SMALL_TILES observation tiles) take their update inside the predictive cascade; the few larger ones here
+            const size_t n_small = pl->n_trsm_small;
+            if (nl <= n_small) return;
+            KTimer kt(pl, KF_LEAF_UPDATE, 0);
+            launch_gemm<EPI_SUB>(pl, pl->gLeafUpdatePlain.p + n_small, nl - n_small, pl->leaf_max_rows, pl->leaf_max_na);
+            return;
+        }
+        case LeafUpdate::SolveWhole: case LeafUpdate::SolveHalves: run_leaf_solve_update(pl, r, nl); return;
+        case LeafUpdate::LeafGemm: { KTimer kt(pl, KF_LEAF_UPDATE, pl->fl_leaf_update); launch_leaf_gemm<EPI_SUB>(pl, pl->gLeafUpdate.p, nl); return; }
+        case LeafUpdate::Gemm: { KTimer kt(pl, KF_LEAF_UPDATE, pl->fl_leaf_update); launch_gemm<EPI_SUB>(pl, pl->gLeafUpdate.p, nl, pl->leaf_max_rows, pl->leaf_max_na); return; }
+    }
+}
+
+// The fork of the leaf work that only feeds the predictive pass.  With `side` the launch helpers (they use pl->stream) go to the side
+// stream between the constructor and join(); without it nothing moves.  A throw in between restores pl->stream (later launches must
+// not land on the side stream) and records no join event.
+struct SideFork {
+    mra_plan* pl; hipStream_t main_stream; bool side;
+    SideFork(mra_plan* p, bool on) : pl(p), main_stream(p->stream), side(on) {
+        if (!side) return;
+        HIP_TRY(hipEventRecord(pl->ev_fork, main_stream));
+        HIP_TRY(hipStreamWaitEvent(pl->stream2, pl->ev_fork, 0));
+        pl->stream = pl->stream2;
+    }
+    void join() {
+        if (!side) return;
+        pl->stream = main_stream;
+        HIP_TRY(hipEventRecord(pl->ev_join, pl->stream2));
+        pl->side_pending = true;            // join_side_stream makes the main stream wait, just before the predictive pass
+    }
+    ~SideFork() { pl->stream = main_stream; }
+};
+
+// (predict) leaves var and W ready for the predictive pass, on the side stream (side_pending) where the route forks
+static void run_leaf_predict_work(mra_plan* pl, const PassRoute& r, size_t nl) {
+    SideFork fork(pl, r.side);
+    run_leaf_var(pl, r);
+    run_leaf_update(pl, r, nl);
+    fork.join();
+}
+
+// ---- fronts, bottom-up ------------------------------------------------------------------------------------------------------------
 // factorise the fronts of level m (already assembled in global memory unless do_assemble): fused kernel when the
 // front (or at least its panel) fits in LDS, else panel Cholesky + Schur GEMM as separate launches
 static bool run_front_fused(mra_plan* pl, int m, bool do_assemble, bool add_identity) {
@@ -1666,161 +1968,172 @@ static void run_add_identity(mra_plan* pl, int m) {
     hipLaunchKernelGGL(k_add_identity, dim3((unsigned)((lv.cw + 63) / 64), (unsigned)nn), dim3(64), 0, pl->stream, lv.gAsm.p);
 }
 
-static void finish_run(mra_plan* pl);
+// What happens to the fronts of level m, first match wins (direct_parent already excludes reduce_level == NL-1):
+//   step          when                                                  form_front launches                              afterwards
+//   Resumed       mra_run_resume's first level                          nothing: the caller summed the fronts, which      factor; the identity is missing
+//                                                                       sit in HBM as the Reduce step left them           iff this is the reduce level
+//   ParentFront   direct_parent, m == NL-1, parent_front                k_parent_front<nacc>: children's Ut -> front ->   level done
+//                                                                       Lt, Zt, Schur block, never in HBM unfactorised
+//   ParentPanels  direct_parent, m == NL-1, the level is panel_only     k_parent_front<2|4> on the own block, the panel   level done
+//                                                                       GEMM, the LDS row solve (throws if too wide)
+//   ParentSyrk    direct_parent, m == NL-1 otherwise                    the gParentSyrk GEMM: the front complete in HBM   factor
+//   GrandSyrk     direct_parent, m == NL-2, level NL-1 is panel_only    k_syrk_blk or the GEMM (throws if this is the     factor
+//                                                                       reduce level): the front complete in HBM
+//   Reduce        m == reduce_level                                     k_assemble without identity + the log-det sum of  reduce_front (split: the pass is
+//                                                                       everything below (k_sum_dnode if no assembly ran) suspended), factor, identity missing
+//   Children      otherwise                                             nothing                                           factor, assembling on the way
+enum class FrontStep { Resumed, ParentFront, ParentPanels, ParentSyrk, GrandSyrk, Reduce, Children };
 
-static void run_fronts_and_predict(mra_plan* pl, int m_from, bool resume) {
-    const PassRoute& r = pl->route;
-    pl->slv.valid = false;
-    for (int m = m_from; m >= 0; --m) {
-        const bool is_red = (m == pl->reduce_level);
-        bool red_summed = false;             // the reduce level's log-det sum was written by its assembly launch
-        bool need_identity = false;          // front sits in global memory without its identity block
-        bool assembled = true;
-        if (!(resume && m == m_from)) {
-            if (r.direct_parent && m == pl->NL - 1) {
-                const LevelData& lvp = pl->lev[m];
-                if (r.parent_front) {
-                    // children's Ut -> front -> Lt, Zt, Schur block, all in one launch (the front never visits HBM unfactorised)
-                    ensure_big_lds(pl, {(const void*)k_parent_front<2>, (const void*)k_parent_front<4>, (const void*)k_parent_front<8>, (const void*)k_parent_front<12>});
-                    KTimer kt(pl, KF_LEAF_SYRK, (pl->fl_leaf_syrk + lvp.fl_fchol + lvp.fl_schur).with_bytes(pl->by_leaf_ut + 8.0 * lvp.nodes.size() * (0.5 * lvp.nf * (lvp.nf + 1))));
-                    const dim3 grid((unsigned)lvp.nodes.size());
-                    const size_t lds = pl->parent_front_lds;
-                    switch (pl->parent_front_nacc) {
-                        case 2: hipLaunchKernelGGL(k_parent_front<2>, grid, dim3(512), lds, pl->stream, pl->gParentFront.p, pl->parentSegs.p, pl->dnode.p, pl->errflag.p); break;
-                        case 4: hipLaunchKernelGGL(k_parent_front<4>, grid, dim3(512), lds, pl->stream, pl->gParentFront.p, pl->parentSegs.p, pl->dnode.p, pl->errflag.p); break;
-                        case 8: hipLaunchKernelGGL(k_parent_front<8>, grid, dim3(512), lds, pl->stream, pl->gParentFront.p, pl->parentSegs.p, pl->dnode.p, pl->errflag.p); break;
-                        default: hipLaunchKernelGGL(k_parent_front<12>, grid, dim3(512), lds, pl->stream, pl->gParentFront.p, pl->parentSegs.p, pl->dnode.p, pl->errflag.p); break;
-                    }
-                    continue;
-                }
-                if (lvp.panel_only) {
-                    // only the panel columns of these fronts exist: build them, factorise them, done with the level
-                    const size_t nnp = lvp.nodes.size();
-                    ensure_big_lds(pl, {(const void*)k_parent_front<2>, (const void*)k_parent_front<4>});
-                    {
-                        KTimer kt(pl, KF_LEAF_SYRK, pl->fl_parent_panel);
-                        if (lvp.cwt <= 4) hipLaunchKernelGGL(k_parent_front<2>, dim3((unsigned)nnp), dim3(512), pl->parent_own_lds, pl->stream, pl->gParentOwn.p, pl->parentSegs.p, pl->dnode.p, pl->errflag.p);
-                        else hipLaunchKernelGGL(k_parent_front<4>, dim3((unsigned)nnp), dim3(512), pl->parent_own_lds, pl->stream, pl->gParentOwn.p, pl->parentSegs.p, pl->dnode.p, pl->errflag.p);
-                        launch_gemm<EPI_SET>(pl, pl->gParentPanel.p, nnp, lvp.na, lvp.cw, pl->seg_gemm_lds && pl->parent_panel_lds_ok, false);
-                    }
-                    {
-                        KTimer kt(pl, KF_FRONT_CHOL, pl->lev[m].fl_fchol.with_bytes(8.0 * 2 * nnp * (double)lvp.na * lvp.cw));
-                        if (!launch_trsm2(pl, pl->gParentZt.p, nnp, lvp.cwt, lvp.na / 16, lvp.na / 16))
-                            throw MraError(MRA_ERR_STATE, "panel row solve: block too wide for the LDS row solve");
-                    }
-                    continue;
-                }
-                KTimer kt(pl, KF_LEAF_SYRK, pl->fl_leaf_syrk);
-                launch_gemm<EPI_SET>(pl, pl->gParentSyrk.p, lvp.nodes.size(), lvp.nf, lvp.nf, false, true);
-            } else if (r.direct_parent && m == pl->NL - 2 && pl->lev[pl->NL - 1].panel_only) {
-                if (is_red) throw MraError(MRA_ERR_STATE, "the reduce level cannot be the level above panel-only fronts");
-                const LevelData& lg = pl->lev[m];
-                KTimer kt(pl, KF_FRONT_SCHUR, pl->fl_grand_syrk);
-                if (r.syrk_blk) mra_launch_syrk_blk(pl, pl->gGrandSyrk.p, lg.nodes.size(), lg.nf, r.syrk_dma);
-                else launch_gemm<EPI_SET>(pl, pl->gGrandSyrk.p, lg.nodes.size(), lg.nf, lg.nf, false, true);      // (64 x 64 LDS-tiled: 24.2 vs 23.7 ms at config 5)
-            } else if (is_red) {
-                // (the rank-local log-det sum of everything below rides in the same launch, see the reduce block)
-                LevelData& lvr = pl->lev[m];
-                const int lo_r = (int)pl->level_ptr[m + 1];
-                red_summed = run_assemble_level(pl, m, false, pl->dnode.p + lo_r, pl->n_nodes - lo_r, lvr.F.p + (lvr.F.n - 16));
-                need_identity = true;
-            } else {
-                assembled = false;               // the fused front kernel assembles in LDS when the whole front fits
-            }
-            if (is_red) {
-                // the reduce level's fronts are summed over ranks WITHOUT their identity blocks; the
-                // 16-double tail of the buffer carries the rank-local log-det sum of everything below
-                LevelData& lv = pl->lev[m];
-                const int lo = (int)pl->level_ptr[m + 1];
-                if (!red_summed) {
-                    KTimer kt(pl, KF_MISC, 0);
-                    hipLaunchKernelGGL(k_sum_dnode, dim3(1), dim3(256), 0, pl->stream, pl->dnode.p + lo, pl->n_nodes - lo,
-                                       lv.F.p + (lv.F.n - 16));
-                }
-                if (pl->run_flags & MRA_RUN_SPLIT) { pl->split_pending = true; return; }
-                // a reduce level without a transport would silently build the likelihood from this rank's partial fronts
-                if (!pl->comm || !pl->allreduce)
-                    throw MraError(MRA_ERR_STATE, "reduce level set but neither a communicator (mra_comm_init) nor MRA_RUN_SPLIT: "
-                                                  "the fronts of the reduce level would not be summed over ranks");
-                if (pl->allreduce(lv.F.p, lv.F.p, lv.F.n, ncclDouble, ncclSum, pl->comm, pl->stream) != ncclSuccess)
-                    throw MraError(MRA_ERR_COMM, "ncclAllReduce failed");
-            }
-        } else {
-            need_identity = is_red;
-        }
-        if (!assembled) {
-            if (run_front_fused(pl, m, true, true)) continue;
-            run_assemble_level(pl, m, true);
-        }
-        if (run_front_fused(pl, m, false, need_identity)) continue;
-        if (need_identity) run_add_identity(pl, m);
-        run_front_level(pl, m);
-    }
-    phase_mark(pl, 3);
-    if (pl->side_pending) {                                 // join: the leaf update on the side stream
-        HIP_TRY(hipStreamWaitEvent(pl->stream, pl->ev_join, 0));
-        pl->side_pending = false;
-    }
-    if (r.predict && r.path == PassPath::Fused) run_predict_fused(pl);
-    if (r.predict && r.path == PassPath::Hi) run_predict_hi(pl);         // (sharded plans too: the fronts above the reduce level are complete by now)
-    if (r.predict && r.path == PassPath::Levels) {
-        for (int m = pl->n_levels - 1; m >= 0; --m) {
-            LevelData& lv = pl->lev[m];
-            const size_t nn = lv.nodes.size();
-            if (!nn) continue;
-            {
-                KTimer kt(pl, KF_PRED_TRSM, lv.fl_trsm);
-                if (!launch_trsm2(pl, lv.gTrsm2Post.p, nn, lv.cwt, lv.max_tiles, 32)) {
-                    ensure_tile_lists(pl, m);
-                    hipLaunchKernelGGL(k_trsm_rows, dim3((unsigned)((lv.ntiles + 3) / 4)), dim3(256), 0, pl->stream,
-                                       lv.gTrsmPost.p, lv.tile_node.p, lv.tile_row0.p, lv.ntiles, pl->W.p, (long)pl->ldw,
-                                       lv.c0, pl->var.p);
-                }
-            }
-            { KTimer kt(pl, KF_PRED_UPDATE, lv.fl_update); launch_gemm<EPI_SUB>(pl, lv.gUpdate.p, nn, lv.max_rows, lv.na); }
-        }
-    }
-    phase_mark(pl, 4);
-    finish_run(pl);
+// Pure, like route_for: reads the plan and the route, touches nothing.  resumed_here: mra_run_resume re-enters the loop at this level
+static FrontStep front_step_for(const mra_plan* pl, const PassRoute& r, int m, bool resumed_here) {
+    if (resumed_here) return FrontStep::Resumed;
+    if (r.direct_parent && m == pl->NL - 1)
+        return r.parent_front ? FrontStep::ParentFront : pl->lev[m].panel_only ? FrontStep::ParentPanels : FrontStep::ParentSyrk;
+    if (r.direct_parent && m == pl->NL - 2 && pl->lev[pl->NL - 1].panel_only) return FrontStep::GrandSyrk;
+    return m == pl->reduce_level ? FrontStep::Reduce : FrontStep::Children;
 }
 
-static void finish_run(mra_plan* pl) {
+// FrontStep::ParentPanels.  Only the panel columns of these fronts exist: build them, factorise them, done with the level
+static void run_parent_panels(mra_plan* pl, int m) {
+    const LevelData& lv = pl->lev[m];
+    const size_t nn = lv.nodes.size();
     {
-        KTimer kt(pl, KF_MISC, 0);
-        const int nsum = pl->reduce_level >= 0 ? (int)pl->level_ptr[pl->reduce_level + 1] : pl->n_nodes;
-        const double* up;
-        if (pl->leaf[0]) up = pl->Gt.p + pl->leaf_goff[pl->leaf_slot[0]] + (size_t)(pl->na[0] - MRA_YB) * pl->na[0] + (pl->na[0] - MRA_YB);
-        else {
-            const LevelData& l0 = pl->lev[0];
-            up = l0.F.p + (size_t)(l0.nf - MRA_YB) * l0.nf + (l0.nf - MRA_YB);
-        }
-        const double* below = nullptr;
-        if (pl->reduce_level >= 0) {
-            const LevelData& lr = pl->lev[pl->reduce_level];
-            if (lr.F.n) below = lr.F.p + (lr.F.n - 16);
-        }
-        // the 32-byte record {d, u, log-det carried by the reduce level, error flag} is written by the kernel straight
-        // into pinned host memory (no copy command, no gap after the last launch)
-        if (!pl->host_res) {
-            HIP_TRY(hipHostMalloc((void**)&pl->host_res, 4 * sizeof(double), hipHostMallocMapped));
-            HIP_TRY(hipHostGetDevicePointer((void**)&pl->host_res_dev, pl->host_res, 0));
-        }
-        hipLaunchKernelGGL(k_sum_dnode, dim3(1), dim3(256), 0, pl->stream, pl->dnode.p, nsum, pl->host_res_dev, up, below, pl->errflag.p);
-        if (pl->route.extract_mean)
-            hipLaunchKernelGGL(k_extract_mean, dim3((unsigned)((pl->P + 255) / 256)), dim3(256), 0, pl->stream,
-                               pl->W.p, (long)pl->ldw, pl->Ka, pl->mean.p, pl->P);
+        KTimer kt(pl, KF_LEAF_SYRK, pl->fl_parent_panel);
+        launch_parent_front(pl, lv.cwt <= 4 ? 2 : 4, nn, pl->parent_own_lds, pl->gParentOwn.p);
+        launch_gemm<EPI_SET>(pl, pl->gParentPanel.p, nn, lv.na, lv.cw, pl->seg_gemm_lds && pl->parent_panel_lds_ok, false);
     }
-    phase_mark(pl, 5);
-    HIP_TRY(hipStreamSynchronize(pl->stream));
-    HIP_TRY(hipGetLastError());
-    const int errv = (int)pl->host_res[3];
-    const double dsum = pl->host_res[0] + pl->host_res[2], u = pl->host_res[1];
-    pl->res_d = dsum; pl->res_u = u;
+    KTimer kt(pl, KF_FRONT_CHOL, lv.fl_fchol.with_bytes(8.0 * 2 * nn * (double)lv.na * lv.cw));
+    if (!launch_trsm2(pl, pl->gParentZt.p, nn, lv.cwt, lv.na / 16, lv.na / 16))
+        throw MraError(MRA_ERR_STATE, "panel row solve: block too wide for the LDS row solve");
+}
+
+// FrontStep::Reduce.  The reduce level's fronts are summed over ranks WITHOUT their identity blocks; the 16-double tail of the buffer
+// carries the rank-local log-det sum of everything below (in the assembly's launch; on its own where the level holds no node)
+static void run_assemble_reduce_level(mra_plan* pl, int m) {
+    LevelData& lv = pl->lev[m];
+    const int lo = (int)pl->level_ptr[m + 1];
+    double* tail = lv.F.p + (lv.F.n - 16);
+    if (run_assemble_level(pl, m, false, pl->dnode.p + lo, pl->n_nodes - lo, tail)) return;
+    KTimer kt(pl, KF_MISC, 0);
+    hipLaunchKernelGGL(k_sum_dnode, dim3(1), dim3(256), 0, pl->stream, pl->dnode.p + lo, pl->n_nodes - lo, tail);
+}
+
+// form: leaves level m's fronts as the table's row says - factorised (ParentFront, ParentPanels), in HBM, or still in their children
+static void form_front(mra_plan* pl, const PassRoute& r, FrontStep step, int m) {
+    const LevelData& lv = pl->lev[m];
+    switch (step) {
+        case FrontStep::Resumed: case FrontStep::Children: return;
+        case FrontStep::ParentFront: {
+            KTimer kt(pl, KF_LEAF_SYRK, (pl->fl_leaf_syrk + lv.fl_fchol + lv.fl_schur).with_bytes(pl->by_leaf_ut + 8.0 * lv.nodes.size() * (0.5 * lv.nf * (lv.nf + 1))));
+            launch_parent_front(pl, pl->parent_front_nacc, lv.nodes.size(), pl->parent_front_lds, pl->gParentFront.p);
+            return;
+        }
+        case FrontStep::ParentPanels: run_parent_panels(pl, m); return;
+        case FrontStep::ParentSyrk: {
+            KTimer kt(pl, KF_LEAF_SYRK, pl->fl_leaf_syrk);
+            launch_gemm<EPI_SET>(pl, pl->gParentSyrk.p, lv.nodes.size(), lv.nf, lv.nf, false, true);
+            return;
+        }
+        case FrontStep::GrandSyrk: {
+            if (m == pl->reduce_level) throw MraError(MRA_ERR_STATE, "the reduce level cannot be the level above panel-only fronts");
+            KTimer kt(pl, KF_FRONT_SCHUR, pl->fl_grand_syrk);
+            if (r.syrk_blk) mra_launch_syrk_blk(pl, pl->gGrandSyrk.p, lv.nodes.size(), lv.nf, r.syrk_dma);
+            else launch_gemm<EPI_SET>(pl, pl->gGrandSyrk.p, lv.nodes.size(), lv.nf, lv.nf, false, true);      // (64 x 64 LDS-tiled: 24.2 vs 23.7 ms at config 5)
+            return;
+        }
+        case FrontStep::Reduce: run_assemble_reduce_level(pl, m); return;
+    }
+}
+
+// reduce: leaves the reduce level's fronts summed over all ranks.  Returns false where that is the caller's job (MRA_RUN_SPLIT): the
+// pass is suspended until mra_run_resume
+static bool reduce_front(mra_plan* pl, int m) {
+    LevelData& lv = pl->lev[m];
+    if (pl->run_flags & MRA_RUN_SPLIT) { pl->split_pending = true; return false; }
+    // a reduce level without a transport would silently build the likelihood from this rank's partial fronts
+    if (!pl->comm || !pl->allreduce)
+        throw MraError(MRA_ERR_STATE, "reduce level set but neither a communicator (mra_comm_init) nor MRA_RUN_SPLIT: "
+                                      "the fronts of the reduce level would not be summed over ranks");
+    if (pl->allreduce(lv.F.p, lv.F.p, lv.F.n, ncclDouble, ncclSum, pl->comm, pl->stream) != ncclSuccess)
+        throw MraError(MRA_ERR_COMM, "ncclAllReduce failed");
+    return true;
+}
+
+// factor: leaves level m's fronts factorised ([Lt ; Zt], inverted diagonal blocks, log-determinants) and their Schur blocks ready for
+// the parents.  in_hbm: the fronts are assembled in global memory (else k_front<true> assembles them in LDS where the whole front fits,
+// k_assemble where not; either adds the identity); needs_identity: ... but without their identity blocks
+static void factor_front(mra_plan* pl, int m, bool in_hbm, bool needs_identity) {
+    if (!in_hbm) {
+        if (run_front_fused(pl, m, true, true)) return;
+        run_assemble_level(pl, m, true);
+    }
+    if (run_front_fused(pl, m, false, needs_identity)) return;
+    if (needs_identity) run_add_identity(pl, m);
+    run_front_level(pl, m);
+}
+
+// ---- predictive pass --------------------------------------------------------------------------------------------------------------
+// leaves the main stream waiting for the predict-only leaf work that run_leaf_predict_work put on the side stream
+static void join_side_stream(mra_plan* pl) {
+    if (!pl->side_pending) return;
+    HIP_TRY(hipStreamWaitEvent(pl->stream, pl->ev_join, 0));
+    pl->side_pending = false;
+}
+
+// PassPath::Levels: per level, bottom-up, the posterior row solve (var -= the solved rows' squares) and the update of the columns above
+static void run_predict_levels(mra_plan* pl) {
+    for (int m = pl->n_levels - 1; m >= 0; --m) {
+        LevelData& lv = pl->lev[m];
+        const size_t nn = lv.nodes.size();
+        if (!nn) continue;
+        { KTimer kt(pl, KF_PRED_TRSM, lv.fl_trsm); launch_level_row_solve(pl, m, lv.gTrsm2Post.p, lv.gTrsmPost.p, pl->var.p); }
+        { KTimer kt(pl, KF_PRED_UPDATE, lv.fl_update); launch_gemm<EPI_SUB>(pl, lv.gUpdate.p, nn, lv.max_rows, lv.na); }
+    }
+}
+
+// leaves the predictive variance in var and the mean in `mean` (Levels: in W's y block, for k_extract_mean)
+static void run_predict(mra_plan* pl) {
+    if (!pl->route.predict) return;
+    switch (pl->route.path) {
+        case PassPath::Fused: run_predict_fused(pl); return;
+        case PassPath::Hi: run_predict_hi(pl); return;          // (sharded plans too: the fronts above the reduce level are complete by now)
+        case PassPath::Levels: run_predict_levels(pl); return;
+    }
+}
+
+// ---- the end of a pass ------------------------------------------------------------------------------------------------------------
+// leaves the 32-byte record {d, u, log-det carried by the reduce level, error flag} in pinned host memory - written by the kernel
+// straight into it: no copy command, no gap after the last launch - and with extract_mean the mean out of W's y block
+static void launch_result(mra_plan* pl) {
+    KTimer kt(pl, KF_MISC, 0);
+    const int nsum = pl->reduce_level >= 0 ? (int)pl->level_ptr[pl->reduce_level + 1] : pl->n_nodes;
+    const double* up;
+    if (pl->leaf[0]) up = pl->Gt.p + pl->leaf_goff[pl->leaf_slot[0]] + (size_t)(pl->na[0] - MRA_YB) * pl->na[0] + (pl->na[0] - MRA_YB);
+    else {
+        const LevelData& l0 = pl->lev[0];
+        up = l0.F.p + (size_t)(l0.nf - MRA_YB) * l0.nf + (l0.nf - MRA_YB);
+    }
+    const double* below = nullptr;
+    if (pl->reduce_level >= 0) {
+        const LevelData& lr = pl->lev[pl->reduce_level];
+        if (lr.F.n) below = lr.F.p + (lr.F.n - 16);
+    }
+    if (!pl->host_res) {
+        HIP_TRY(hipHostMalloc((void**)&pl->host_res, 4 * sizeof(double), hipHostMallocMapped));
+        HIP_TRY(hipHostGetDevicePointer((void**)&pl->host_res_dev, pl->host_res, 0));
+    }
+    hipLaunchKernelGGL(k_sum_dnode, dim3(1), dim3(256), 0, pl->stream, pl->dnode.p, nsum, pl->host_res_dev, up, below, pl->errflag.p);
+    if (pl->route.extract_mean)
+        hipLaunchKernelGGL(k_extract_mean, dim3((unsigned)((pl->P + 255) / 256)), dim3(256), 0, pl->stream,
+                           pl->W.p, (long)pl->ldw, pl->Ka, pl->mean.p, pl->P);
+}
+
+// the finished pass's phase times (the inner four only with kernel timing on) and per-kernel times into the plan; drops the kernel events
+static void harvest_timers(mra_plan* pl) {
     float ms;
     for (int k = 0; k < 4; ++k) {
-        static const int a[4] = {0, 1, 2, 3}, b[4] = {1, 2, 3, 4};
         ms = 0.f;
-        if (pl->ktiming) hipEventElapsedTime(&ms, pl->ev[a[k]], pl->ev[b[k]]);
+        if (pl->ktiming) hipEventElapsedTime(&ms, pl->ev[k], pl->ev[k + 1]);
         pl->phase_ms[k] = ms;
     }
     hipEventElapsedTime(&ms, pl->ev[0], pl->ev[5]);
@@ -1831,236 +2144,75 @@ static void finish_run(mra_plan* pl) {
         hipEventDestroy(e.second.first); hipEventDestroy(e.second.second);
     }
     pl->kev.clear();
+}
+
+// the pass is over, whatever it found: errv is the record's error flag (0, or 1 + the node whose Cholesky failed)
+static void close_pass(mra_plan* pl, int errv) {
     pl->ran = true;
     pl->split_pending = false;
     pl->pass_open = false;
-    if (errv) pl->cphantom_valid = false;
-    if (errv) {
-        char b[160];
-        snprintf(b, sizeof b, "matrix not positive definite in node %d (Cholesky pivot <= 0 or NaN)", errv - 1);
-        throw MraError(MRA_ERR_NOT_SPD, b);
-    }
+    if (!errv) return;
+    pl->cphantom_valid = false;
+    char b[160];
+    snprintf(b, sizeof b, "matrix not positive definite in node %d (Cholesky pivot <= 0 or NaN)", errv - 1);
+    throw MraError(MRA_ERR_NOT_SPD, b);
 }
 
-// allocate the per-leaf Schur blocks the first time a run needs them and point the descriptors at them
-static void ensure_gt(mra_plan* pl) {
-    if (pl->Gt.p || pl->leaf_goff.back() == 0) return;
-    pl->Gt.alloc(pl->leaf_goff.back());
-    for (size_t k = 0; k < pl->hKids.size(); ++k)
-        if (pl->kid_leaf[k] >= 0) pl->hKids[k].G = pl->Gt.p + pl->leaf_goff[pl->kid_leaf[k]];
-    pl->asmKids.upload(pl->hKids);
-    for (size_t t = 0; t < pl->hLeafSyrk.size(); ++t) pl->hLeafSyrk[t].C = pl->Gt.p + pl->leaf_goff[t];
-    pl->gLeafSyrk.upload(pl->hLeafSyrk);
+static void finish_run(mra_plan* pl) {
+    launch_result(pl);
+    phase_mark(pl, 5);
+    HIP_TRY(hipStreamSynchronize(pl->stream));
+    HIP_TRY(hipGetLastError());
+    const int errv = (int)pl->host_res[3];
+    pl->res_d = pl->host_res[0] + pl->host_res[2]; pl->res_u = pl->host_res[1];
+    harvest_timers(pl);
+    close_pass(pl, errv);
+}
+
+// ---- the two drivers --------------------------------------------------------------------------------------------------------------
+// fronts bottom-up from level m_from, then the predictive pass and the result.  resume: mra_run_resume, after the caller has summed the
+// reduce level's fronts over the ranks
+static void run_fronts_and_predict(mra_plan* pl, int m_from, bool resume) {
+    const PassRoute& r = pl->route;
+    pl->slv.valid = false;
+    for (int m = m_from; m >= 0; --m) {
+        const FrontStep step = front_step_for(pl, r, m, resume && m == m_from);
+        form_front(pl, r, step, m);
+        switch (step) {
+            case FrontStep::ParentFront: case FrontStep::ParentPanels: break;                                // formed and factorised in one
+            case FrontStep::ParentSyrk: case FrontStep::GrandSyrk: factor_front(pl, m, true, false); break;
+            case FrontStep::Resumed: factor_front(pl, m, true, m == pl->reduce_level); break;
+            case FrontStep::Reduce:
+                if (!reduce_front(pl, m)) return;                                                            // suspended: mra_run_resume goes on
+                factor_front(pl, m, true, true);
+                break;
+            case FrontStep::Children: factor_front(pl, m, false, false); break;
+        }
+    }
+    phase_mark(pl, 3);
+    join_side_stream(pl);
+    run_predict(pl);
+    phase_mark(pl, 4);
+    finish_run(pl);
 }
 
 // full_rows: the caller reads W at every row afterwards (sampler_prior); a likelihood-only pass then walks all rows
 static void run_all(mra_plan* pl, uint32_t flags, bool full_rows = false) {
-    if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
-    if (!(pl->have_locs && pl->have_obs && pl->have_kernel))
-        throw MraError(MRA_ERR_STATE, "mra_run needs set_locs, set_obs and set_kernel first");
-    HIP_TRY(mraSetDevice(pl->device));
-    if (pl->pass_open) {
-        // the previous pass never reached finish_run (an error was thrown, or a split run was abandoned before
-        // mra_run_resume): wait for whatever it left on the two streams, and clear the device error flag that
-        // only the last kernel of a pass resets
-        pl->cphantom_valid = false;
-        if (pl->side_pending) HIP_TRY(hipStreamWaitEvent(pl->stream, pl->ev_join, 0));
-        HIP_TRY(hipStreamSynchronize(pl->stream));
-        HIP_TRY(hipStreamSynchronize(pl->stream2));
-        HIP_TRY(hipMemsetAsync(pl->errflag.p, 0, sizeof(int), pl->stream));
-        for (auto& e : pl->kev) { hipEventDestroy(e.second.first); hipEventDestroy(e.second.second); }
-        pl->kev.clear();
-    }
-    pl->side_pending = false;
-    pl->split_pending = false;
-    pl->pass_open = true;
-    pl->run_flags = flags;
-    pl->slv.valid = false;               // whatever runs a pass rewrites the factors (mra_solve sets the mark again after its own)
-    for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = mra_plan::KStat();
-    if (!pl->lik_general_valid && route_for(pl, flags, full_rows).lik_general) ensure_lik_general(pl);      // (once; route_for reads the verdict)
-    const PassRoute& r = pl->route = route_for(pl, flags, full_rows);
-    pl->route_set = true;
-    const bool pred = r.predict, fused = r.path == PassPath::Fused;
+    const PassRoute& r = open_pass(pl, flags, full_rows);
     phase_mark(pl, 0);
-    if (r.init_yblock) {
-        KTimer kt(pl, KF_MISC, 0);
-        const long n = pl->P * MRA_YB;
-        hipLaunchKernelGGL(k_init_yblock, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, pl->stream, pl->W.p,
-                           (long)pl->ldw, pl->Ka, pl->y.p, pl->P, r.acc_var ? pl->var.p : (double*)nullptr, pl->host_cov ? 0.0 : kernel_cov0(pl),
-                           pl->host_cov ? pl->covdiag.p : (const double*)nullptr);
-    }
+    if (r.init_yblock) run_init_yblock(pl, r);
     // ---- 1. prior, top-down
-    if (fused) run_prior_fused(pl);
-    for (int m = 0; m < pl->n_levels && !fused; ++m) {
-        LevelData& lv = pl->lev[m];
-        const size_t nn = lv.nodes.size();
-        if (!nn) continue;
-        if (r.prior_level && lv.prior_level_ok) {
-            // knots' residual block -> Lp (both sides gathered), its Cholesky, then residual + kernel + row solve of every row in one
-            // launch: the residual never visits HBM
-            { KTimer kt(pl, KF_PRIOR_CHOL, lv.fl_knot_resid); launch_gemm<EPI_COV>(pl, lv.gKnotResid.p, nn, lv.cw, lv.cw); }
-            { KTimer kt(pl, KF_PRIOR_CHOL, lv.fl_pchol); launch_panel(pl, lv.gPriorChol.p, nn); }
-            if (r.lik_general) {
-                Work w = lv.fl_resid + lv.fl_trsm.with_bytes(0.0);
-                w.alg *= lv.lik_share; w.exec *= lv.lik_share; w.bytes *= lv.lik_share;
-                KTimer kt(pl, KF_PRIOR_RESID, w);
-                mra_launch_prior_level(pl, lv.gResidLik.p, lv.gResidLik.n);
-            } else {
-                KTimer kt(pl, KF_PRIOR_RESID, lv.fl_resid + lv.fl_trsm.with_bytes(0.0));
-                mra_launch_prior_level(pl, lv.gResidFused.p, lv.gResidFused.n);
-            }
-            continue;
-        }
-        {
-            KTimer kt(pl, KF_PRIOR_RESID, lv.fl_resid);
-            if (pl->host_cov) launch_gemm<EPI_HOSTCOV>(pl, lv.gResid.p, nn, lv.max_rows, lv.cw);
-            else launch_gemm<EPI_COV>(pl, lv.gResid.p, nn, lv.max_rows, lv.cw);
-        }
-        {
-            KTimer kt(pl, KF_MISC, 0);
-            dim3 grid((unsigned)((lv.cw * lv.cw + 255) / 256), (unsigned)nn);
-            hipLaunchKernelGGL(k_gather_kinv, grid, dim3(256), 0, pl->stream, lv.gKinv.p, pl->W.p, (long)pl->ldw, lv.c0);
-        }
-        { KTimer kt(pl, KF_PRIOR_CHOL, lv.fl_pchol); launch_panel(pl, lv.gPriorChol.p, nn); }
-        {
-            KTimer kt(pl, KF_PRIOR_TRSM, lv.fl_trsm);
-            if (!launch_trsm2(pl, lv.gTrsm2Prior.p, nn, lv.cwt, lv.max_tiles, 32)) {
-                ensure_tile_lists(pl, m);
-                hipLaunchKernelGGL(k_trsm_rows, dim3((unsigned)((lv.ntiles + 3) / 4)), dim3(256), 0, pl->stream,
-                                   lv.gTrsmPrior.p, lv.tile_node.p, lv.tile_row0.p, lv.ntiles, pl->W.p, (long)pl->ldw, lv.c0,
-                                   (double*)nullptr);
-            }
-        }
-    }
+    if (r.path == PassPath::Fused) run_prior_fused(pl);
+    else run_prior_levels(pl, r);
     phase_mark(pl, 1);
     // ---- 2. leaves
     const size_t nl = pl->leaf_nodes.size();
     if (nl) {
-        {
-            KTimer kt(pl, KF_LEAF_RESID, r.c_only ? pl->fl_leaf_c_only : pl->fl_leaf_resid);
-            if (pl->host_cov) {
-                if (r.leaf_resident) launch_leaf_gemm<EPI_HOSTCOV>(pl, pl->gLeafResid.p, nl);
-                else launch_gemm<EPI_HOSTCOV>(pl, pl->gLeafResid.p, nl, pl->leaf_max_rows, pl->leaf_max_nop);
-            }
-            else if (r.c_only) launch_gemm<EPI_COV>(pl, pl->gLeafResidLik.p, nl, pl->leaf_max_nop, pl->leaf_max_nop);
-            else if (r.leaf_resident) launch_leaf_gemm<EPI_COV>(pl, pl->gLeafResid.p, nl);
-            else launch_gemm<EPI_COV>(pl, pl->gLeafResid.p, nl, pl->leaf_max_rows, pl->leaf_max_nop);
-        }
-        if (r.c_fix != LeafCFix::None) {
-            KTimer kt(pl, KF_MISC, 0);
-            // (InProduct: nothing to do, the gathered COV product wrote the whole C block including phantom identities)
-            if (r.c_fix == LeafCFix::Phantom) {
-                // C comes from the COV epilogue, Ut from the gather inside k_trsm_rows2: only the phantom rows remain
-                // ... once: an identity row stays an identity row under the in-place factorisation (L[p][j] = 0, L[p][p] = 1 exactly) and
-                // no epilogue writes there, so later passes find them in place.  (A failed pass - NaN times 0 - a new observation pattern
-                // or a change of options bring the launch back.)
-                if (!pl->cphantom_valid) {
-                    hipLaunchKernelGGL(k_leaf_cphantom, dim3((unsigned)nl), dim3(256), 0, pl->stream, pl->gLeaf.p, pl->leaf_nobs.p);
-                    pl->cphantom_valid = true;
-                }
-            } else if (r.c_fix == LeafCFix::Fill) {
-                const long total = (long)(pl->leaf_max_nop + pl->leaf_max_na) * pl->leaf_max_nop;
-                dim3 grid((unsigned)std::min<long>((total + 255) / 256, 64), (unsigned)nl);
-                hipLaunchKernelGGL(k_leaf_fill, grid, dim3(256), 0, pl->stream, pl->gLeaf.p, pl->W.p, (long)pl->ldw, pl->R);
-            }
-        }
-        {
-            KTimer kt(pl, KF_LEAF_CHOL, pred ? pl->fl_leaf_chol : pl->fl_leaf_chol_lik);
-            const int ntl = pl->leaf_max_nop / 16;
-            if (r.chol != LeafChol::BigPanels) {
-                // k_chol_tiles: one workgroup per matrix, tiles in registers, next diagonal block factorised beside the trailing update
-                const size_t ns = pl->n_chol_small;      // (gLeafCholSorted: the leaves of at most LEAF_SMALL_TILES tiles first)
-                if (r.chol == LeafChol::TilesSplit) {
-                    if (ns) hipLaunchKernelGGL((k_chol_tiles<8, 4>), dim3((unsigned)ns), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p, pl->dnode.p, pl->errflag.p);
-                    if (nl > ns) hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)(nl - ns)), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p + ns, pl->dnode.p, pl->errflag.p);
-                }
-                else if (r.chol == LeafChol::TilesOne) hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)nl), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p, pl->dnode.p, pl->errflag.p);
-                else hipLaunchKernelGGL((k_chol_wave<LEAF_MAX_TILES>), dim3((unsigned)((nl + 3) / 4)), dim3(256), 0, pl->stream, pl->gLeafCholC.p, (int)nl, pl->dnode.p, pl->errflag.p);
-                const int mt = pred ? pl->leaf_max_tiles_full : pl->leaf_max_tiles_lik;
-                if (fused) {
-                    const size_t nts = pl->n_trsm_small;
-                    const int mts = (pred && !r.solve_fused) ? pl->trsm_small_tiles_full : pl->trsm_small_tiles_lik;
-                    if (nts) launch_trsm2(pl, r.trsm_small, nts, pl->trsm_small_nt, mts, mts);
-                    // the few leaves with more than LEAF_SMALL_TILES observation tiles: several workgroups per leaf when they are few
-                    // (one leaf per workgroup would put a single 65 us workgroup on the critical path)
-                    if (nl > nts) launch_trsm2(pl, r.trsm_all + nts, nl - nts, ntl, mt, (nl - nts) < 512 ? 4 : mt);
-                }
-                else launch_trsm2(pl, r.trsm_all, nl, ntl, mt, mt);
-            } else {
-                // right-looking, 64 columns per step: the panel (factor + solve of ALL rows below, Ut and Tt included) on one
-                // workgroup per leaf, the rank-64 update of everything to its right as a batched GEMM over the whole GPU
-                // (a single workgroup factorising an 8560 x 8560 block column by column took 15 s: README example 1)
-                const int v = pred ? 0 : 1;
-                for (size_t st = 0; st < pl->gBigPanel[v].size(); ++st) {
-                    launch_panel(pl, pl->gBigPanel[v][st].p, nl, st > 0 ? 1 : 0);
-                    if (pl->bigM[v][st] > 0 && pl->bigN[v][st] > 0)
-                        launch_gemm<EPI_SUB>(pl, pl->gBigTrail[v][st].p, nl, pl->bigM[v][st], pl->bigN[v][st]);
-                }
-            }
-        }
-        if (!r.direct_parent) { ensure_gt(pl); KTimer kt(pl, KF_LEAF_SYRK, pl->fl_leaf_syrk); launch_gemm<EPI_SET>(pl, pl->gLeafSyrk.p, nl, pl->leaf_max_na, pl->leaf_max_na, false, true); }
-        if (pred) {
-            // fork: everything below only feeds the predictive pass (r.side: on the side stream)
-            hipStream_t main_stream = pl->stream;
-            struct StreamGuard {                                   // a throw below must not leave later launches on the side stream
-                mra_plan* p; hipStream_t s;
-                ~StreamGuard() { p->stream = s; }
-            } guard{pl, main_stream};
-            if (r.side) {
-                HIP_TRY(hipEventRecord(pl->ev_fork, main_stream));
-                HIP_TRY(hipStreamWaitEvent(pl->stream2, pl->ev_fork, 0));
-                pl->stream = pl->stream2;                    // the launch helpers below use pl->stream
-            }
-            if (r.var == LeafVar::FinishVar) {
-                KTimer kt(pl, KF_MISC, 0);
-                ensure_row_leaf(pl);
-                hipLaunchKernelGGL(k_leaf_finish_var, dim3((unsigned)((pl->P + 255) / 256)), dim3(256), 0, pl->stream, pl->row_leaf.p, pl->W.p,
-                                   (long)pl->ldw, pl->Ka, pl->var.p, pl->P);
-            } else if (r.var == LeafVar::Moments) {
-                KTimer kt(pl, KF_MISC, 0);
-                const double cov0 = pl->host_cov ? 0.0 : kernel_cov0(pl);
-                ensure_row_leaf(pl);
-                hipLaunchKernelGGL(k_leaf_moments, dim3((unsigned)((pl->P + 3) / 4)), dim3(256), 0, pl->stream, pl->gLeaf.p,
-                                   pl->row_leaf.p, pl->W.p, (long)pl->ldw, pl->Ka, pl->var.p, cov0,
-                                   pl->host_cov ? pl->covdiag.p : (const double*)nullptr, pl->P);
-            }
-            if (r.update == LeafUpdate::InCascade) {          // (InPredictHi: nothing to launch here)
-                // the small leaves (<= LEAF_SMALL_TILES observation tiles) take their update inside the predictive cascade; the few larger ones here
-                const size_t ns = pl->n_trsm_small;
-                if (nl > ns) {
-                    KTimer kt(pl, KF_LEAF_UPDATE, 0);
-                    launch_gemm<EPI_SUB>(pl, pl->gLeafUpdatePlain.p + ns, nl - ns, pl->leaf_max_rows, pl->leaf_max_na);
-                }
-            } else if (r.update == LeafUpdate::SolveWhole || r.update == LeafUpdate::SolveHalves) {
-                // Tt = V Lc^-T, var -= |Tt|^2 and W -= Tt Ut^T in one launch for the leaves with <= LEAF_SMALL_TILES observation tiles; the few
-                // larger ones went through the full row solve above and take the plain update product
-                ensure_big_lds(pl, {(const void*)k_leaf_solve_update<8, 13, true>});
-                KTimer kt(pl, KF_LEAF_UPDATE, pl->fl_leaf_update);
-                const size_t ns = pl->n_trsm_small;
-#ifdef MRA_STAMPS
-                if (pl->kstamps2.n < pl->n_leaf_solve_half * 8) { pl->kstamps2.alloc(pl->n_leaf_solve_half * 8); HIP_TRY(mraMemset(pl->kstamps2.p, 0, pl->kstamps2.n * sizeof(double))); HIP_TRY(hipDeviceSynchronize()); }
-#define MRA_LSTAMP_VAL , (unsigned long long*)pl->kstamps2.p
-#define MRA_LSTAMP_NUL , (unsigned long long*)nullptr
-#else
-#define MRA_LSTAMP_VAL
-#define MRA_LSTAMP_NUL
-#endif
-                if (r.update == LeafUpdate::SolveHalves)
-                    hipLaunchKernelGGL((k_leaf_solve_update<8, 13, true>), dim3((unsigned)pl->n_leaf_solve_half), dim3(512), pl->leaf_solve_lds, pl->stream, pl->gLeafSolveHalf.p MRA_LSTAMP_VAL);
-                else
-                    hipLaunchKernelGGL((k_leaf_solve_update<8, 13, true>), dim3((unsigned)ns), dim3(512), pl->leaf_solve_lds, pl->stream, pl->gLeafSolve.p MRA_LSTAMP_NUL);
-                if (nl > ns) launch_gemm<EPI_SUB>(pl, pl->gLeafUpdatePlain.p + ns, nl - ns, pl->leaf_max_rows, pl->leaf_max_na);
-            } else if (r.update != LeafUpdate::InPredictHi) {
-                KTimer kt(pl, KF_LEAF_UPDATE, pl->fl_leaf_update);
-                if (r.update == LeafUpdate::LeafGemm) launch_leaf_gemm<EPI_SUB>(pl, pl->gLeafUpdate.p, nl);
-                else launch_gemm<EPI_SUB>(pl, pl->gLeafUpdate.p, nl, pl->leaf_max_rows, pl->leaf_max_na);
-            }
-            if (r.side) {
-                pl->stream = main_stream;
-                HIP_TRY(hipEventRecord(pl->ev_join, pl->stream2));
-                pl->side_pending = true;
-            }
-        }
+        run_leaf_product(pl, r, nl);
+        run_leaf_c_fix(pl, r, nl);
+        run_leaf_factor(pl, r, nl);
+        if (!r.direct_parent) run_leaf_syrk(pl, nl);
+        if (r.predict) run_leaf_predict_work(pl, r, nl);
     }
     phase_mark(pl, 2);
     // ---- 3./4. fronts bottom-up, then predictive moments
