@@ -166,6 +166,28 @@ int mra_sample(mra_plan *plan, uint32_t flags, int64_t n_samples, uint64_t seed,
  * non-finite Y at an observed row.  Work buffers are allocated on the first call.  Blocking. */
 int mra_solve(mra_plan *plan, uint32_t flags, int64_t n_cols, const double *Y, double *mean, double *quad);
 
+/* The MRA covariance as an operator (no counterpart in the reference, which can only draw from it, pyMRA/MRATools.py:395-484): the
+ * prior covariance of the latent field at the reported rows (real rows inside a leaf) is
+ *     Sigma = sum over non-leaf j of W_j W_j^T + sum over leaves l of v_M(K_l, K_l),   v_M(S, S) = C(S, S) - W_anc[S] W_anc[S]^T,
+ * W_j = W[rows of j, block of j's level], K_l the knot rows of leaf l - the Sigma mra_sample draws from.  For n_cols vectors A
+ * (n_cols x P, row-major: vector k at A + k P, padded leaf order, read at the REPORTED rows only; values elsewhere are ignored)
+ *     out  (n_cols x P, or NULL): out[k] = Sigma A[k]; with MRA_COV_POSTERIOR out[k] = Sigma_post A[k],
+ *                                 Sigma_post = Sigma - Sigma[:, o] (Sigma[o, o] + R I)^-1 Sigma[o, :] on the mask of the last set_obs, whose
+ *                                 diagonal is the var of mra_get_predict; unreported rows (phantoms, rows a 1-D split drops) are exactly 0
+ *     gram (n_cols x n_cols, or NULL): A Sigma A^T (A Sigma_post A^T), the covariance matrix of the functionals a_k^T x
+ * Columns are processed in blocks of 16 (the N of v_mfma_f64_16x16x4_f64).  gram is returned BLOCK-DIAGONAL as quad of mra_solve is:
+ * entries whose row and column lie in the same block of 16 columns are computed, all others are set to NaN.  It is summed over a fixed
+ * number of partial sums in a fixed order (the same bits on every call) and returned symmetric.
+ * The call shares the factors mra_solve keeps: the first call (and the first after mra_run, mra_run_resume, mra_sample or any set_*)
+ * runs one likelihood pass with W at every row; later calls - and a later mra_solve, as this call after an mra_solve - launch no
+ * factorisation.  Afterwards y, every option and what mra_get_likelihood / mra_get_predict return are as the caller left them
+ * (mra_get_timers / mra_get_kernel_stats describe the call's own pass; all zero when none ran).
+ * MRA_ERR_STATE before set_locs / set_obs / set_kernel; MRA_ERR_INVALID for unknown flags, MRA_KERNEL_HOST plans, sharded plans,
+ * n_cols < 0, a NULL A with n_cols > 0 and a non-finite A at a reported row (checked on the host before anything is launched).
+ * n_cols == 0 returns MRA_OK.  Work buffers are allocated on the first call.  Blocking. */
+#define MRA_COV_POSTERIOR 1u
+int mra_cov_apply(mra_plan *plan, uint32_t flags, int64_t n_cols, const double *A, double *out, double *gram);
+
 /* Diagnostics for tests (the reference exposes these as attributes of Node objects):
  * what = 0: whitened basis W (P x ldw, row-major) ; 1: per-node log-det terms (n_nodes);
  * copies min(capacity, available) doubles into out, returns the available count in *n_avail.

@@ -199,6 +199,50 @@ class MRATree(object):
         mean[t.perm[rows], :] = m[:, rows].T
         return mean, quad
 
+    def _cov_apply(self, A, distr):
+        """Sigma A (or Sigma_post A) for A (N, c) in the caller's row order -> (A at the reported rows else 0 (N, c), out (N, c))."""
+        if distr not in ("prior", "posterior"):
+            raise ValueError('distr must be "prior" or "posterior"')
+        if self.kernel is None:
+            raise NotImplementedError("covariance needs a device kernel: trees built from an opaque callable or a dense matrix cannot apply it")
+        t = self.topology
+        rows = (t.perm >= 0) & np.asarray(t.in_leaf, dtype=bool)
+        Ap = np.zeros((A.shape[1], t.P))
+        Ap[:, rows] = A[t.perm[rows], :].T
+        o, _ = self.plan.cov_apply(Ap, posterior=(distr == "posterior"), want_gram=False)
+        Arep, out = np.zeros(A.shape), np.zeros(A.shape)
+        Arep[t.perm[rows], :] = A[t.perm[rows], :]
+        out[t.perm[rows], :] = o[:, rows].T
+        return Arep, out
+
+    def covariance(self, rows, distr="prior"):
+        """(N, len(rows)) columns Sigma[:, rows] of the MRA covariance of the latent field, in the caller's row order: the prior
+        (distr="prior": what simulate() draws from, and how well the MRA approximates the kernel) or the posterior given this
+        tree's observations (distr="posterior": its diagonal is predict()'s variance).  Rows outside every leaf are 0, as a
+        column and as an entry.  getLikelihood() and predict() are unchanged afterwards."""
+        rows = np.atleast_1d(np.asarray(rows, dtype=np.int64))
+        N = len(self.locs)
+        if rows.ndim != 1 or np.any(rows < 0) or np.any(rows >= N):
+            raise ValueError("rows must be indices into the %d locations" % N)
+        A = np.zeros((N, len(rows)))
+        A[rows, np.arange(len(rows))] = 1.0
+        return self._cov_apply(A, distr)[1]
+
+    def functionalCovariance(self, A, distr="prior"):
+        """(c, c) covariance matrix of the linear functionals A[:, k]^T x of the latent field (a regional mean, a contrast between
+        two areas): A^T Sigma A under the prior or the posterior.  A: (N,) or (N, c) in the caller's row order; rows outside every
+        leaf do not enter.  The full matrix for any c (the product with Sigma A is formed on the host)."""
+        A = np.asarray(A, dtype=np.float64)
+        if A.ndim == 1:
+            A = A.reshape(-1, 1)
+        if A.ndim != 2 or A.shape[0] != len(self.locs):
+            raise ValueError("A must have shape (N,) or (N, c) with N = %d" % len(self.locs))
+        if not np.all(np.isfinite(A)):
+            raise ValueError("A must be finite")
+        Arep, out = self._cov_apply(A, distr)
+        G = Arep.T @ out
+        return 0.5 * (G + G.T)
+
     def getLikelihoods(self, Y):
         """(c,) likelihoods d + u_k of the columns of Y on this tree's observation mask (getLikelihood() per column; the
         log-determinant d is shared)."""

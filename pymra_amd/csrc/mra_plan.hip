@@ -1173,6 +1173,7 @@ static void build_leaf(mra_plan* pl, const double* y) {
     ArenaScope arena(&pl->arena);
     pl->cphantom_valid = false;
     pl->slv.valid = false; pl->slv.built = false;      // mra_solve's descriptors point into the leaves' panels
+    pl->cov.built = false;                             // mra_cov_apply's read the solver's maps
     LeafDescs d;
     build_obs_lists(pl, y, d);
     tr.mark("observation lists");
@@ -2480,6 +2481,59 @@ static void solve_all(mra_plan* pl, uint32_t flags, int64_t n, const double* Y, 
     }
 }
 
+// ---- covariance operator (mra_cov_apply) ------------------------------------------------------------------
+static void cov_all(mra_plan* pl, uint32_t flags, int64_t n, const double* A, double* out, double* gram) {
+    if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
+    if (flags & ~MRA_COV_POSTERIOR) throw MraError(MRA_ERR_INVALID, "unknown mra_cov_apply flags");
+    if (!(pl->have_locs && pl->have_kernel)) throw MraError(MRA_ERR_STATE, "mra_cov_apply needs set_locs and set_kernel first");
+    if (!pl->have_obs) throw MraError(MRA_ERR_STATE, "mra_cov_apply needs set_obs first");
+    if (pl->host_cov || pl->kp.kind == MRA_KERNEL_HOST) throw MraError(MRA_ERR_INVALID, "mra_cov_apply: MRA_KERNEL_HOST plans cannot apply the covariance (C(S, S) is evaluated on the device)");
+    if (pl->reduce_level >= 0 || pl->comm || pl->n_ranks > 1) throw MraError(MRA_ERR_INVALID, "mra_cov_apply: sharded plans cannot apply the covariance");
+    if (n < 0) throw MraError(MRA_ERR_INVALID, "n_cols < 0");
+    if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
+    if (n == 0) return;
+    if (!A) throw MraError(MRA_ERR_INVALID, "A is NULL");
+    const bool post = flags & MRA_COV_POSTERIOR;
+    const long P = pl->P;
+    HIP_TRY(mraSetDevice(pl->device));
+    mra_solver_build(pl);
+    mra_cov_build(pl);
+    mra_plan::Solver& S = pl->slv;
+    mra_plan::Cov& V = pl->cov;
+    for (int64_t k = 0; k < n; ++k)
+        for (long p = 0; p < P; ++p)
+            if (V.rep_host[p] && !std::isfinite(A[k * P + p])) {
+                char m[128];
+                snprintf(m, sizeof m, "mra_cov_apply: A is not finite at a reported row (column %lld, padded row %ld)", (long long)k, p);
+                throw MraError(MRA_ERR_INVALID, m);
+            }
+    if (!S.valid) {
+        // W at every row and, for the posterior, the factors: the pass mra_solve runs and keeps (solve_all)
+        KeepResults keep(pl, nullptr, S.msave.p, S.vsave.p);
+        sampler_prior(pl);
+        HIP_TRY(hipStreamSynchronize(pl->stream));
+        HIP_TRY(hipGetLastError());
+        S.valid = true;
+    } else {
+        for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = mra_plan::KStat();      // the kernel statistics describe this call: no pass ran
+    }
+    if (gram) for (int64_t e = 0; e < n * n; ++e) gram[e] = std::nan("");
+    for (int64_t c0 = 0; c0 < n; c0 += 16) {
+        const int nc = (int)std::min<int64_t>(16, n - c0);
+        HIP_TRY(hipMemcpyAsync(V.ab.p, A + c0 * P, (size_t)nc * P * sizeof(double), hipMemcpyHostToDevice, pl->stream));
+        if (nc < 16) HIP_TRY(hipMemsetAsync(V.ab.p + (size_t)nc * P, 0, (size_t)(16 - nc) * P * sizeof(double), pl->stream));
+        mra_cov_block(pl, post, gram != nullptr);
+        if (out) HIP_TRY(hipMemcpyAsync(out + c0 * P, V.out.p, (size_t)nc * P * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
+        double gb[256];
+        if (gram) HIP_TRY(hipMemcpyAsync(gb, V.gram.p, sizeof gb, hipMemcpyDeviceToHost, pl->stream));
+        HIP_TRY(hipStreamSynchronize(pl->stream));
+        HIP_TRY(hipGetLastError());
+        if (gram)
+            for (int i = 0; i < nc; ++i)
+                for (int j = 0; j < nc; ++j) gram[(c0 + i) * n + c0 + j] = gb[i * 16 + j];
+    }
+}
+
 // ---- caller-order variants: the permutation work of an end-to-end MRATree(...) call done inside the library -----------------
 // A process-wide pinned staging area (grow-only): gathers land in it, the H2D / D2H copies run at the pinned rate (a pageable
 // 16 MB copy costs ~5 ms, a pinned one ~0.7 ms), and a second plan in the same process does not pay for the allocation again.
@@ -2992,6 +3046,9 @@ int mra_sample(mra_plan* pl, uint32_t flags, int64_t n_samples, uint64_t seed, i
 
 int mra_solve(mra_plan* pl, uint32_t flags, int64_t n_cols, const double* Y, double* mean, double* quad) {
     return guarded(pl, [&] { require(pl, "mra_solve: plan is NULL"); solve_all(pl, flags, n_cols, Y, mean, quad); return MRA_OK; });
+}
+int mra_cov_apply(mra_plan* pl, uint32_t flags, int64_t n_cols, const double* A, double* out, double* gram) {
+    return guarded(pl, [&] { require(pl, "mra_cov_apply: plan is NULL"); cov_all(pl, flags, n_cols, A, out, gram); return MRA_OK; });
 }
 
 int mra_get_likelihood(mra_plan* pl, double* d, double* u) {

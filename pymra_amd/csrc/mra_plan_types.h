@@ -211,6 +211,16 @@ struct SolveFront {             // one non-leaf node
 };
 struct SolveSeg { const double* p; int n; int sign; };      // rows of the quadratic form: sign * sum_rows v v^T
 
+// ---- mra_cov_apply: descriptors of the covariance kernels (mra_cov_kernels.h, launched from mra_launch_cov.hip).
+// The fronts go through SolveFront with buffers of the cov path's own (F is not read: nullptr).
+struct CovLeaf {                // one leaf
+    double* t;                  // anc x16: W[S, anc]^T (rep o A)[S], what the leaf hands up to its parent
+    double* tp;                 // anc x16: W[S, anc]^T (knot o rep o A)[S]
+    const double* chain;        // anc x16: the parent's [tau ; tau_chain] (nullptr when anc == 0)
+    long row0;
+    int nrows, anc, a0;         // a0: first ancestor column in W
+};
+
 struct LevelData {
     std::vector<int> nodes;          // non-leaf nodes of this level
     int cw = 0, cwt = 0, c0 = 0, a0 = 0, nf = 0, na = 0;
@@ -492,6 +502,18 @@ struct mra_plan {
         DevVec<double> yb, out, uy, nb, qpart, quad, msave, vsave;      // 16 x P in / out blocks; U_y / s / q; node buffers; Q
         size_t work_bytes = 0;
     } slv;
+    // covariance operator (mra_cov_apply): reads W of the pass mra_solve keeps (slv.valid), the solver's tile_leaf / rep maps and,
+    // for the posterior, its sweeps.  Built on the first call and again whenever the solver's descriptors are.
+    struct Cov {
+        bool built = false;
+        DevVec<CovLeaf> leaves;
+        DevVec<SolveFront> fronts;                // by level, then slot (the solver's lev_off)
+        DevVec<const double*> kids;
+        DevVec<unsigned char> knot;               // [P] knot row of its own leaf
+        std::vector<unsigned char> rep_host;      // [P] reported row (the rows A is read and checked at)
+        DevVec<double> ab, out, nb, gpart, gram;  // 16 x P in / out blocks; node buffers; gram partial sums; 16 x 16
+        size_t work_bytes = 0;
+    } cov;
     // comm
     void* rccl = nullptr;
     ncclComm_t comm = nullptr;
@@ -545,3 +567,7 @@ void mra_solver_build(mra_plan* pl);
 void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad);
 void mra_solver_pseudo(mra_plan* pl, const double* y, const double* x, const SampleZ& zs, long slot0);
 void mra_solver_addmean(mra_plan* pl, double* x, int ns);
+// mra_launch_cov.hip: descriptors + work buffers of mra_cov_apply; one block of <= 16 columns (cov.ab -> cov.out, cov.gram; launches
+// only, on pl->stream; the posterior goes through slv.yb, mra_solver_block and slv.out)
+void mra_cov_build(mra_plan* pl);
+void mra_cov_block(mra_plan* pl, bool posterior, bool want_gram);

@@ -38,6 +38,7 @@ MRA_OPT_CASCADE_GROUP = 18
 MRA_OPT_SAMPLE_GRAM_BYTES = 19
 MRA_OPT_SAMPLE_SOLVE = 20
 MRA_SAMPLE_CONDITIONAL = 1
+MRA_COV_POSTERIOR = 1
 MRA_BLOCK_W_ROWS, MRA_BLOCK_LPRIOR, MRA_BLOCK_FRONT, MRA_BLOCK_LEAF = 0, 1, 2, 3
 
 # mra_get_route (include/mra_hip.h): the fields in the order the library writes them, and the members of the four enums by value
@@ -60,7 +61,7 @@ ERR_NAMES = {-1: "MRA_ERR_INVALID", -2: "MRA_ERR_HIP", -3: "MRA_ERR_NOT_SPD", -4
 EXPORTS = [
     "mra_device_count", "mra_release_cached_memory", "mra_plan_create", "mra_plan_destroy", "mra_plan_set_locs", "mra_plan_set_obs",
     "mra_plan_set_kernel", "mra_plan_set_locs_rows", "mra_plan_set_obs_rows", "mra_get_predict_rows", "mra_get_predict_rows_sd", "mra_eval_kernel", "mra_plan_set_cov_block", "mra_run", "mra_get_likelihood", "mra_get_predict",
-    "mra_sample_slots", "mra_sample", "mra_solve", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
+    "mra_sample_slots", "mra_sample", "mra_solve", "mra_cov_apply", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
     "mra_get_kernel_stats", "mra_get_kernel_work", "mra_get_route", "mra_device_synchronize", "mra_plan_info", "mra_comm_unique_id", "mra_comm_init",
     "mra_plan_set_reduce_level", "mra_reduce_size", "mra_reduce_export", "mra_reduce_import",
     "mra_run_resume", "mra_last_error", "mra_version",
@@ -123,6 +124,7 @@ def load_library():
         "mra_sample_slots": (C.c_int, [vp, C.POINTER(i64)]),
         "mra_sample": (C.c_int, [vp, u32, i64, C.c_uint64, i64, vp, vp]),
         "mra_solve": (C.c_int, [vp, u32, i64, vp, vp, vp]),
+        "mra_cov_apply": (C.c_int, [vp, u32, i64, vp, vp, vp]),
         "mra_get_buffer": (C.c_int, [vp, C.c_int, vp, i64, C.POINTER(i64)]),
         "mra_get_node_block": (C.c_int, [vp, i32, C.c_int, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
         "mra_get_timers": (C.c_int, [vp, vp, C.c_int]),
@@ -360,6 +362,21 @@ class HipPlan:
         quad = np.empty((c, c)) if want_quad else None
         self._check(self.lib.mra_solve(self._h, 0, c, _ptr(Y), None if mean is None else _ptr(mean), None if quad is None else _ptr(quad)))
         return mean, quad
+
+    def cov_apply(self, A, posterior=False, want_out=True, want_gram=True):
+        """The MRA covariance applied to vectors (include/mra_hip.h, mra_cov_apply).  A: (c, P) in padded leaf order, read at the
+        reported rows only.  -> (out (c, P) or None, gram (c, c) or None): out[k] = Sigma A[k] (posterior=True: Sigma_post A[k];
+        unreported rows 0), gram = A Sigma A^T, BLOCK-DIAGONAL in blocks of 16 columns (NaN elsewhere).  The factorisation is shared
+        with solve() and kept between calls; y, the options and likelihood() / predict() are unchanged afterwards."""
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        if A.ndim != 2 or A.shape[1] != self.topo.P:
+            raise ValueError("A must have shape (c, P) = (c, %d)" % self.topo.P)
+        c = A.shape[0]
+        out = np.empty((c, self.topo.P)) if want_out else None
+        gram = np.empty((c, c)) if want_gram else None
+        flags = MRA_COV_POSTERIOR if posterior else 0
+        self._check(self.lib.mra_cov_apply(self._h, flags, c, _ptr(A), None if out is None else _ptr(out), None if gram is None else _ptr(gram)))
+        return out, gram
 
     def buffer(self, what):
         n = C.c_int64()
