@@ -188,8 +188,34 @@ int mra_solve(mra_plan *plan, uint32_t flags, int64_t n_cols, const double *Y, d
 #define MRA_COV_POSTERIOR 1u
 int mra_cov_apply(mra_plan *plan, uint32_t flags, int64_t n_cols, const double *A, double *out, double *gram);
 
+/* Prediction at locations that are not rows of the tree (no counterpart in the reference, where a prediction location has to be a row
+ * of `locs` with a NaN observation - which changes the knots and so the model, pyMRA/MRANode.py:36-45): the MRA is a process on the
+ * whole domain, x(s) = sum_{m < lev(l)} a_m(s)^T eta_m + delta_l(s) for a site s assigned to leaf l, and the state mra_solve keeps
+ * evaluates its posterior mean and variance anywhere:
+ *     sites (n_sites x d, row-major, the caller's order) and leaf (the NODE index of the leaf each site is assigned to; any assignment
+ *           gives a valid process, pymra_amd.MRATree.locate takes the leaf of the nearest tree location)
+ *     Y     (n_cols x P as for mra_solve, read at the plan's OBSERVED rows only), or NULL: the plan's own observations, n_cols == 1
+ *     mean  (n_cols x n_sites, or NULL): mean[k][i] = E[x(s_i) | Y[k] at the observed rows]
+ *     var   (n_sites, or NULL): the posterior variance of the latent field at s_i (add R for a new observation); it does not depend on Y
+ * At a site that is a tree location, assigned to that row's leaf, these are the mean and var of mra_get_predict.  Inside the library the
+ * sites are grouped by leaf, each group is padded to tiles of 16 sites (the N of v_mfma_f64_16x16x4_f64) and the tiles are processed in
+ * chunks of bounded work memory (MRA_OPT_SITES_CHUNK_BYTES); the result for a site is a pure function of (site, leaf, plan state) -
+ * the same bits whatever else is in the call and however it is chunked.  Columns are processed in blocks of 16.
+ * The call shares the factors mra_solve keeps: the first call (and the first after mra_run, mra_run_resume, mra_sample or any set_*)
+ * runs one likelihood pass with W at every row; later calls - and calls after an mra_solve or mra_cov_apply - launch no factorisation.
+ * Afterwards y, every option and what mra_get_likelihood / mra_get_predict return are as the caller left them (mra_get_timers /
+ * mra_get_kernel_stats describe the call's own pass; all zero when none ran).  flags: 0.
+ * MRA_ERR_STATE before set_locs / set_obs / set_kernel; MRA_ERR_INVALID for unknown flags, MRA_KERNEL_HOST plans, sharded plans,
+ * n_sites < 0, n_cols < 0, a NULL sites or leaf with n_sites > 0, a leaf entry that is out of range or not a leaf node, a non-finite
+ * site coordinate, a non-finite Y at an observed row and a NULL Y with n_cols != 1 (all checked on the host before anything is
+ * launched).  n_sites == 0 returns MRA_OK.  Work buffers are allocated on the first call.  Blocking. */
+int mra_predict_sites(mra_plan *plan, uint32_t flags, int64_t n_sites, const double *sites, const int32_t *leaf, int64_t n_cols,
+                      const double *Y, double *mean, double *var);
+
 /* Diagnostics for tests (the reference exposes these as attributes of Node objects):
  * what = 0: whitened basis W (P x ldw, row-major) ; 1: per-node log-det terms (n_nodes);
+ * 7: stream milliseconds of the last mra_predict_sites, measured while MRA_OPT_KERNEL_TIMING is on (7 values: the basis, leaf, chain
+ * and mean kernels, the solver's sweeps, the uploads of sites and the downloads of results);
  * copies min(capacity, available) doubles into out, returns the available count in *n_avail.
  * (W after a likelihood-only run is complete only with MRA_OPT_LIK_ROWS off: by default such a run computes W at the rows a
  * likelihood needs - the observed rows, and the knots on the level-by-level path - and leaves the others as they were.) */
@@ -315,6 +341,8 @@ int mra_get_timers(mra_plan *plan, double *out_ms, int capacity);
 #define MRA_OPT_SAMPLE_SOLVE   20  /* mra_sample with MRA_SAMPLE_CONDITIONAL: 0 (default): one likelihood + predict pass per draw; 1: the pseudo-data of
                                       a block of up to 16 draws are 16 right-hand sides of mra_solve's sweeps over the factors of the
                                       block's prior pass (one pass per block instead of 1 + 16) */
+#define MRA_OPT_SITES_CHUNK_BYTES 21 /* mra_predict_sites: bytes of site work buffers (a, b, t, sites, results) per chunk of tiles, at least one tile
+                                      per chunk; 0 (default): 256 MiB.  The results do not depend on it; setting it keeps mra_solve's factors */
 int mra_plan_set_option(mra_plan *plan, int option, int64_t value);
 /* current value of an option (so that a caller can change one temporarily and put it back) */
 int mra_plan_get_option(mra_plan *plan, int option, int64_t *value);

@@ -27,6 +27,7 @@ a level, and multi-GPU sharding lives in pymra_amd.sharding.
 from __future__ import annotations
 
 import logging
+import os
 
 import numpy as np
 
@@ -198,6 +199,64 @@ class MRATree(object):
         mean = np.zeros((len(self.locs), Y.shape[1]))
         mean[t.perm[rows], :] = m[:, rows].T
         return mean, quad
+
+    def _sites(self, sites):
+        X = np.asarray(sites, dtype=np.float64)
+        if X.ndim == 1 and self.d == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise ValueError("sites must have shape (n, %d)" % self.d)
+        if not np.all(np.isfinite(X)):
+            raise ValueError("sites must be finite")
+        return X
+
+    def locate(self, sites):
+        """int32[n]: for each site the leaf (node index) of the nearest tree location that the tree reports - locations a 1-D split
+        drops never win; on a circular 1-D kernel the distance wraps at 1.  The rule serves every partition of the tree replay
+        (quadrants, terciles, knot boundaries, KMeans) and sends a site that coincides with a tree location to that location's leaf.
+        Any assignment of sites to leaves gives a valid process: predictAt(leaf=...) overrides this one."""
+        from scipy.spatial import cKDTree
+        X = self._sites(sites)
+        t = self.topology
+        if getattr(self, "_locator", None) is None:
+            rows = np.nonzero((t.perm >= 0) & np.asarray(t.in_leaf, dtype=bool))[0]
+            leaf_of = np.full(t.P, -1, dtype=np.int32)
+            for i in np.nonzero(np.asarray(t.node_leaf, dtype=bool))[0]:
+                leaf_of[int(t.node_row0[i]):int(t.node_row1[i])] = i
+            pts = np.asarray(self.locs, dtype=np.float64).reshape(len(self.locs), -1)[t.perm[rows]]
+            wrap = self.kernel is not None and self.kernel.circular
+            self._locator = (cKDTree(np.mod(pts, 1.0) if wrap else pts, boxsize=1.0 if wrap else None), leaf_of[rows], wrap)
+        kd, leaves, wrap = self._locator
+        workers = min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
+        return leaves[kd.query(np.mod(X, 1.0) if wrap else X, workers=workers)[1]].astype(np.int32)
+
+    def predictAt(self, sites, Y=None, leaf=None):
+        """Posterior mean and standard deviation of the latent field at locations that need not be rows of `locs`, from this tree's
+        factors - the tree (its knots, its likelihood) stays the one that was fitted.  sites: (n, d); Y: None (this tree's
+        observations) or (N,) / (N, c) observation vectors in the caller's row order on this tree's mask, as for solve(); leaf: None
+        (locate(sites)) or int32[n] leaf node indices.  -> (mean (n, c), sd (n,)); add R to sd ** 2 for a new observation.  At a
+        location of the tree, in that location's leaf, these are predict()'s values.  getLikelihood() and predict() are unchanged."""
+        if self.kernel is None:
+            raise NotImplementedError("predictAt needs a device kernel: trees built from an opaque callable or a dense matrix cannot predict at new sites")
+        X = self._sites(sites)
+        if leaf is None:
+            leaf = self.locate(X)
+        leaf = np.asarray(leaf)
+        if leaf.shape != (len(X),):
+            raise ValueError("leaf must have shape (n,) = (%d,)" % len(X))
+        Yp = None
+        if Y is not None:
+            Y = np.asarray(Y, dtype=np.float64)
+            if Y.ndim == 1:
+                Y = Y.reshape(-1, 1)
+            if Y.ndim != 2 or Y.shape[0] != len(self.locs):
+                raise ValueError("Y must have shape (N,) or (N, c) with N = %d" % len(self.locs))
+            t = self.topology
+            real = t.perm >= 0
+            Yp = np.zeros((Y.shape[1], t.P))
+            Yp[:, real] = Y[t.perm[real], :].T
+        mean, var = self.plan.predict_sites(X, leaf, Yp)
+        return np.ascontiguousarray(mean.T), np.sqrt(var)
 
     def _cov_apply(self, A, distr):
         """Sigma A (or Sigma_post A) for A (N, c) in the caller's row order -> (A at the reported rows else 0 (N, c), out (N, c))."""

@@ -1,0 +1,132 @@
+// mra_launch_sites.hip - mra_predict_sites: descriptors, work buffers and the launches of one chunk of site tiles
+// over the state a likelihood pass left in the plan.  A translation unit of its own: the kernels of the pass keep their object code.
+#define MRA_KERNELS_TEMPLATES_ONLY
+#include "mra_site_kernels.h"
+
+void mra_sites_build(mra_plan* pl) {
+    mra_plan::Sites& T = pl->sit;
+    if (T.built) return;
+    mra_solver_build(pl);                       // the leaves' descriptors, and the checks of the column layout
+    const size_t nl = pl->leaf_nodes.size();
+    std::vector<SiteNode> nv((size_t)pl->n_nodes);
+    for (int m = 0; m < pl->n_levels; ++m) {
+        const LevelData& lvl = pl->lev[m];
+        for (size_t s = 0; s < lvl.nodes.size(); ++s) {
+            const int i = lvl.nodes[s];
+            SiteNode N{};
+            N.Lp = lvl.Lp_of(s); N.F = lvl.F_of(s);
+            N.knots = pl->knot_idx.p + pl->knot_idx_off[i];
+            N.ld = lvl.ldf; N.cw = lvl.cw; N.c0 = pl->coff[m]; N.anc = pl->Ka - pl->asuf[m];
+            nv[i] = N;
+        }
+    }
+    std::vector<int> chain, chain_ptr(nl + 1, 0);
+    T.anc_max = 0; T.nop_max = 0;
+    for (size_t t = 0; t < nl; ++t) {
+        const int i = pl->leaf_nodes[t];
+        std::vector<int> up;
+        int width = 0;
+        for (int p = pl->parent[i]; p >= 0; p = pl->parent[p]) { up.push_back(p); width += pl->cw[pl->node_level[p]]; }
+        const int anc = pl->Ka - pl->asuf[pl->node_level[i]];
+        if (width != anc) throw MraError(MRA_ERR_STATE, "mra_predict_sites: a leaf's ancestor blocks do not fill its ancestor columns");
+        chain.insert(chain.end(), up.rbegin(), up.rend());      // root first
+        chain_ptr[t + 1] = (int)chain.size();
+        T.anc_max = std::max(T.anc_max, anc);
+        T.nop_max = std::max(T.nop_max, pl->leaf_nop[t]);
+    }
+    if (chain.empty()) chain.push_back(0);
+    T.nodes.upload(nv); T.chain.upload(chain); T.chain_ptr.upload(chain_ptr);
+    T.cap_tiles = 0;                            // the strides of the work buffers follow anc_max / nop_max
+    T.built = true;
+}
+
+// a and b (anc_max x16 each), t (nop_max x16), the sites, the leaf slot, 16 variances and a 16 x 16 block of means
+size_t mra_sites_tile_bytes(const mra_plan* pl) {
+    const mra_plan::Sites& T = pl->sit;
+    return sizeof(double) * 16 * ((size_t)2 * T.anc_max + T.nop_max + pl->d + 1 + 16) + sizeof(int);
+}
+
+void mra_sites_reserve(mra_plan* pl, long n) {
+    mra_plan::Sites& T = pl->sit;
+    if (n <= T.cap_tiles) return;
+    T.cap_tiles = 0;
+    T.tleaf.alloc((size_t)n);
+    T.xs.alloc((size_t)n * 16 * pl->d);
+    T.a.alloc(std::max<size_t>((size_t)n * T.anc_max * 16, 1)); T.b.alloc(std::max<size_t>((size_t)n * T.anc_max * 16, 1));
+    T.t.alloc(std::max<size_t>((size_t)n * T.nop_max * 16, 1));
+    T.var.alloc((size_t)n * 16); T.mean.alloc((size_t)n * 256);
+    T.cap_tiles = n;
+}
+
+void mra_sites_timed(mra_plan* pl, int which, const std::function<void()>& work) {
+    if (!pl->ktiming) { work(); return; }
+    hipEvent_t e0, e1;
+    HIP_TRY(hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { hipEventDestroy(e0); throw MraError(MRA_ERR_HIP, "hipEventCreate failed"); }
+    struct Pair { hipEvent_t a, b; ~Pair() { hipEventDestroy(a); hipEventDestroy(b); } } pair{e0, e1};
+    HIP_TRY(hipEventRecord(e0, pl->stream));
+    work();
+    HIP_TRY(hipEventRecord(e1, pl->stream));
+    HIP_TRY(hipEventSynchronize(e1));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
+    pl->sit.ms[which] += ms;
+}
+static void timed(mra_plan* pl, int which, const std::function<void()>& work) { mra_sites_timed(pl, which, work); }
+
+template <int DIM, int MODE>
+static void launch_basis(mra_plan* pl, long n) {
+    mra_plan::Sites& T = pl->sit;
+    hipLaunchKernelGGL((k_site_basis<DIM, MODE>), dim3((unsigned)n), dim3(64), 0, pl->stream, pl->slv.leaves.p, T.nodes.p, T.chain_ptr.p, T.chain.p,
+                       T.tleaf.p, T.xs.p, pl->W.p, (long)pl->ldw, pl->X.p, pl->kp, T.a.p, (long)T.anc_max * 16);
+}
+template <int DIM, int MODE>
+static void launch_leaf(mra_plan* pl, long n) {
+    mra_plan::Sites& T = pl->sit;
+    hipLaunchKernelGGL((k_site_leaf<DIM, MODE>), dim3((unsigned)n), dim3(64), 0, pl->stream, pl->slv.leaves.p, T.tleaf.p, T.xs.p, pl->X.p, pl->kp,
+                       T.a.p, T.b.p, (long)T.anc_max * 16, T.t.p, (long)T.nop_max * 16, T.var.p);
+}
+template <int DIM, int MODE>
+static void launch_mean(mra_plan* pl, long n, int nc) {
+    mra_plan::Sites& T = pl->sit;
+    hipLaunchKernelGGL((k_site_mean<DIM, MODE>), dim3((unsigned)n), dim3(64), 0, pl->stream, pl->slv.leaves.p, T.tleaf.p, T.xs.p, pl->X.p, pl->kp,
+                       T.a.p, (long)T.anc_max * 16, nc, T.mean.p, n * 16);
+}
+
+// the <DIM, MODE> instance of the plan's dimension and kernel, as the solver's row kernel is chosen
+#define MRA_SITES_DISPATCH(FN, ...)                                                                                  \
+    do {                                                                                                             \
+        if (pl->d != 1 && pl->d != 2) throw MraError(MRA_ERR_INVALID, "mra_predict_sites: 1-D and 2-D locations only"); \
+        const int md_ = pl->kp.mode < 0 || pl->kp.mode > 3 ? 3 : pl->kp.mode;                                        \
+        switch ((pl->d - 1) * 4 + md_) {                                                                             \
+            case 0: FN<1, 0>(__VA_ARGS__); break; case 1: FN<1, 1>(__VA_ARGS__); break;                              \
+            case 2: FN<1, 2>(__VA_ARGS__); break; case 3: FN<1, 3>(__VA_ARGS__); break;                              \
+            case 4: FN<2, 0>(__VA_ARGS__); break; case 5: FN<2, 1>(__VA_ARGS__); break;                              \
+            case 6: FN<2, 2>(__VA_ARGS__); break; default: FN<2, 3>(__VA_ARGS__); break;                             \
+        }                                                                                                            \
+    } while (0)
+
+static void check_chunk(const mra_plan* pl, long n) {
+    if (n <= 0 || n > pl->sit.cap_tiles) throw MraError(MRA_ERR_STATE, "mra_predict_sites: chunk larger than its work buffers");
+}
+
+void mra_sites_basis(mra_plan* pl, long n) {
+    check_chunk(pl, n);
+    timed(pl, 0, [&] { MRA_SITES_DISPATCH(launch_basis, pl, n); });
+}
+
+void mra_sites_var(mra_plan* pl, long n) {
+    check_chunk(pl, n);
+    mra_plan::Sites& T = pl->sit;
+    timed(pl, 1, [&] { MRA_SITES_DISPATCH(launch_leaf, pl, n); });
+    timed(pl, 2, [&] {
+        hipLaunchKernelGGL(k_site_chain, dim3((unsigned)n), dim3(64), 0, pl->stream, pl->slv.leaves.p, T.nodes.p, T.chain_ptr.p, T.chain.p, T.tleaf.p,
+                           T.b.p, (long)T.anc_max * 16, T.var.p);
+    });
+}
+
+void mra_sites_mean(mra_plan* pl, long n, int nc) {
+    check_chunk(pl, n);
+    if (nc < 1 || nc > 16) throw MraError(MRA_ERR_STATE, "mra_predict_sites: a column block has 1 to 16 columns");
+    timed(pl, 3, [&] { MRA_SITES_DISPATCH(launch_mean, pl, n, nc); });
+}

@@ -112,7 +112,7 @@ static void launch_rows(mra_plan* pl) {
 #undef MRA_SOLVE_ROWS
 }
 
-void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad) {
+void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad, bool want_rows) {
     mra_plan::Solver& S = pl->slv;
     const unsigned nl = (unsigned)pl->leaf_nodes.size();
     if (pl->d != 1 && pl->d != 2) throw MraError(MRA_ERR_INVALID, "mra_solve: 1-D and 2-D locations only");
@@ -144,6 +144,7 @@ void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad) {
         hipLaunchKernelGGL(k_solve_leaf_sbeta, dim3(nl), dim3(256), 0, pl->stream, S.leaves.p);
         hipLaunchKernelGGL(k_solve_leaf_trsm<true>, dim3(nl), dim3(64), 0, pl->stream, S.leaves.p, S.yb.p, pl->P);
     }
+    if (!want_rows) return;          // mra_predict_sites: beta and q are read from the leaves' gb / uy
     if (pl->d == 1) launch_rows<1>(pl); else launch_rows<2>(pl);
 }
 

@@ -1174,6 +1174,7 @@ static void build_leaf(mra_plan* pl, const double* y) {
     pl->cphantom_valid = false;
     pl->slv.valid = false; pl->slv.built = false;      // mra_solve's descriptors point into the leaves' panels
     pl->cov.built = false;                             // mra_cov_apply's read the solver's maps
+    pl->sit.built = false;                             // mra_predict_sites' read the solver's leaf descriptors
     LeafDescs d;
     build_obs_lists(pl, y, d);
     tr.mark("observation lists");
@@ -2534,6 +2535,133 @@ static void cov_all(mra_plan* pl, uint32_t flags, int64_t n, const double* A, do
     }
 }
 
+// ---- prediction at new sites (mra_predict_sites) ----------------------------------------------------------------
+// The tiles of a call: the sites grouped by leaf (stable: a leaf's sites keep the caller's order), each group padded to a multiple of 16
+// with copies of its first site.  slot[tile * 16 + k] = the caller's site of that column, -1 for padding.  Plain host code.
+static void sites_tiles(const std::vector<int>& slot_of_leaf_site, int64_t n, size_t nl, std::vector<int64_t>& slot, std::vector<int>& tile_leaf) {
+    std::vector<int64_t> cnt(nl + 1, 0), order((size_t)n);
+    for (int64_t i = 0; i < n; ++i) ++cnt[(size_t)slot_of_leaf_site[i] + 1];
+    for (size_t t = 0; t < nl; ++t) cnt[t + 1] += cnt[t];
+    {
+        std::vector<int64_t> at(cnt.begin(), cnt.end() - 1);
+        for (int64_t i = 0; i < n; ++i) order[(size_t)at[(size_t)slot_of_leaf_site[i]]++] = i;      // counting sort: stable
+    }
+    slot.clear(); tile_leaf.clear();
+    for (size_t t = 0; t < nl; ++t) {
+        const int64_t g0 = cnt[t], g1 = cnt[t + 1];
+        if (g1 == g0) continue;
+        for (int64_t g = g0; g < g1; g += 16) {
+            tile_leaf.push_back((int)t);
+            for (int64_t k = 0; k < 16; ++k) slot.push_back(g + k < g1 ? order[(size_t)(g + k)] : -1);
+        }
+    }
+}
+
+static void predict_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const double* sites, const int32_t* leaf, int64_t nc,
+                              const double* Y, double* mean, double* var) {
+    if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
+    if (flags) throw MraError(MRA_ERR_INVALID, "unknown mra_predict_sites flags");
+    if (!(pl->have_locs && pl->have_kernel)) throw MraError(MRA_ERR_STATE, "mra_predict_sites needs set_locs and set_kernel first");
+    if (!pl->have_obs) throw MraError(MRA_ERR_STATE, "mra_predict_sites needs set_obs first");
+    if (pl->host_cov || pl->kp.kind == MRA_KERNEL_HOST) throw MraError(MRA_ERR_INVALID, "mra_predict_sites: MRA_KERNEL_HOST plans cannot predict at new sites (C(Q, s) is evaluated on the device)");
+    if (pl->reduce_level >= 0 || pl->comm || pl->n_ranks > 1) throw MraError(MRA_ERR_INVALID, "mra_predict_sites: sharded plans cannot predict at new sites");
+    if (n < 0) throw MraError(MRA_ERR_INVALID, "n_sites < 0");
+    if (nc < 0) throw MraError(MRA_ERR_INVALID, "n_cols < 0");
+    if (!Y && nc != 1) throw MraError(MRA_ERR_INVALID, "Y is NULL (the plan's own observations): n_cols must be 1");
+    if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
+    if (n > 0 && (!sites || !leaf)) throw MraError(MRA_ERR_INVALID, "sites or leaf is NULL");
+    const long P = pl->P;
+    const int d = pl->d;
+    std::vector<int> lslot((size_t)n);
+    for (int64_t i = 0; i < n; ++i) {
+        char m[128];
+        if (leaf[i] < 0 || leaf[i] >= pl->n_nodes || !pl->leaf[leaf[i]] || pl->leaf_slot[leaf[i]] < 0) {
+            snprintf(m, sizeof m, "mra_predict_sites: leaf[%lld] = %d is not a leaf node", (long long)i, (int)leaf[i]);
+            throw MraError(MRA_ERR_INVALID, m);
+        }
+        lslot[(size_t)i] = pl->leaf_slot[leaf[i]];
+        for (int e = 0; e < d; ++e)
+            if (!std::isfinite(sites[i * d + e])) {
+                snprintf(m, sizeof m, "mra_predict_sites: site %lld has a non-finite coordinate", (long long)i);
+                throw MraError(MRA_ERR_INVALID, m);
+            }
+    }
+    const bool want_mean = mean != nullptr && nc > 0;
+    if (Y)
+        for (int64_t k = 0; k < nc; ++k)
+            for (long p = 0; p < P; ++p)
+                if (pl->y_finite_host[p] && !std::isfinite(Y[k * P + p])) {
+                    char m[128];
+                    snprintf(m, sizeof m, "mra_predict_sites: Y is not finite at an observed row (column %lld, padded row %ld)", (long long)k, p);
+                    throw MraError(MRA_ERR_INVALID, m);
+                }
+    if (n == 0) return;
+    HIP_TRY(mraSetDevice(pl->device));
+    mra_sites_build(pl);
+    mra_plan::Solver& S = pl->slv;
+    mra_plan::Sites& T = pl->sit;
+    if (!S.valid) {
+        // W at every row and the factors: the pass mra_solve runs and keeps (solve_all)
+        KeepResults keep(pl, nullptr, S.msave.p, S.vsave.p);
+        sampler_prior(pl);
+        HIP_TRY(hipStreamSynchronize(pl->stream));
+        HIP_TRY(hipGetLastError());
+        S.valid = true;
+    } else {
+        for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = mra_plan::KStat();      // the kernel statistics describe this call: no pass ran
+    }
+    for (double& v : T.ms) v = 0.0;
+    std::vector<int64_t> slot;
+    std::vector<int> tile_leaf;
+    sites_tiles(lslot, n, pl->leaf_nodes.size(), slot, tile_leaf);
+    const long n_tiles = (long)tile_leaf.size();
+    const size_t budget = T.chunk_bytes ? T.chunk_bytes : SITES_CHUNK_BYTES;
+    const long per_chunk = std::min<long>(n_tiles, std::max<long>(1, (long)(budget / mra_sites_tile_bytes(pl))));
+    mra_sites_reserve(pl, per_chunk);
+    std::vector<double> xs((size_t)per_chunk * 16 * d), vh((size_t)per_chunk * 16), mh(want_mean ? (size_t)per_chunk * 256 : 0);
+    const int64_t n_blocks = want_mean ? (nc + 15) / 16 : (var ? 1 : 0);
+    for (int64_t cb = 0; cb < n_blocks; ++cb) {
+        const int ncb = want_mean ? (int)std::min<int64_t>(16, nc - cb * 16) : 0;
+        if (want_mean) {
+            // the block's beta (leaves' gb) and q (leaves' uy): the solver's sweeps without its row step
+            if (Y) HIP_TRY(hipMemcpyAsync(S.yb.p, Y + cb * 16 * P, (size_t)ncb * P * sizeof(double), hipMemcpyHostToDevice, pl->stream));
+            else HIP_TRY(hipMemcpyAsync(S.yb.p, pl->y.p, (size_t)P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+            if (ncb < 16) HIP_TRY(hipMemsetAsync(S.yb.p + (size_t)ncb * P, 0, (size_t)(16 - ncb) * P * sizeof(double), pl->stream));
+            mra_sites_timed(pl, 4, [&] { mra_solver_block(pl, true, false, false); });
+        }
+        for (long t0 = 0; t0 < n_tiles; t0 += per_chunk) {
+            const long nt = std::min(per_chunk, n_tiles - t0);
+            for (long e = 0; e < nt * 16; ++e) {
+                const int64_t src = slot[(size_t)(t0 * 16 + e)];
+                const int64_t i = src >= 0 ? src : slot[(size_t)((t0 * 16 + e) & ~(int64_t)15)];      // padding: the tile's first site
+                for (int k = 0; k < d; ++k) xs[(size_t)e * d + k] = sites[i * d + k];
+            }
+            mra_sites_timed(pl, 5, [&] {
+                HIP_TRY(hipMemcpyAsync(T.xs.p, xs.data(), (size_t)nt * 16 * d * sizeof(double), hipMemcpyHostToDevice, pl->stream));
+                HIP_TRY(hipMemcpyAsync(T.tleaf.p, tile_leaf.data() + t0, (size_t)nt * sizeof(int), hipMemcpyHostToDevice, pl->stream));
+            });
+            mra_sites_basis(pl, nt);
+            const bool do_var = var && cb == 0;
+            if (do_var) {
+                mra_sites_var(pl, nt);
+                mra_sites_timed(pl, 6, [&] { HIP_TRY(hipMemcpyAsync(vh.data(), T.var.p, (size_t)nt * 16 * sizeof(double), hipMemcpyDeviceToHost, pl->stream)); });
+            }
+            if (want_mean) {
+                mra_sites_mean(pl, nt, ncb);
+                mra_sites_timed(pl, 6, [&] { HIP_TRY(hipMemcpyAsync(mh.data(), T.mean.p, (size_t)ncb * nt * 16 * sizeof(double), hipMemcpyDeviceToHost, pl->stream)); });
+            }
+            HIP_TRY(hipStreamSynchronize(pl->stream));
+            HIP_TRY(hipGetLastError());
+            for (long e = 0; e < nt * 16; ++e) {
+                const int64_t i = slot[(size_t)(t0 * 16 + e)];
+                if (i < 0) continue;
+                if (do_var) var[i] = vh[(size_t)e];
+                for (int c = 0; c < ncb; ++c) mean[(cb * 16 + c) * n + i] = mh[(size_t)c * nt * 16 + e];
+            }
+        }
+    }
+}
+
 // ---- caller-order variants: the permutation work of an end-to-end MRATree(...) call done inside the library -----------------
 // A process-wide pinned staging area (grow-only): gathers land in it, the H2D / D2H copies run at the pinned rate (a pageable
 // 16 MB copy costs ~5 ms, a pinned one ~0.7 ms), and a second plan in the same process does not pay for the allocation again.
@@ -3051,6 +3179,11 @@ int mra_cov_apply(mra_plan* pl, uint32_t flags, int64_t n_cols, const double* A,
     return guarded(pl, [&] { require(pl, "mra_cov_apply: plan is NULL"); cov_all(pl, flags, n_cols, A, out, gram); return MRA_OK; });
 }
 
+int mra_predict_sites(mra_plan* pl, uint32_t flags, int64_t n_sites, const double* sites, const int32_t* leaf, int64_t n_cols, const double* Y,
+                      double* mean, double* var) {
+    return guarded(pl, [&] { require(pl, "mra_predict_sites: plan is NULL"); predict_sites_all(pl, flags, n_sites, sites, leaf, n_cols, Y, mean, var); return MRA_OK; });
+}
+
 int mra_get_likelihood(mra_plan* pl, double* d, double* u) {
     return guarded(pl, [&] {
         require(pl && d && u, "mra_get_likelihood: plan, d or u is NULL");
@@ -3069,6 +3202,11 @@ int mra_get_buffer(mra_plan* pl, int what, double* out, int64_t cap, int64_t* n_
         require(pl && n_avail, "mra_get_buffer: plan or n_avail is NULL");
         HIP_TRY(mraSetDevice(pl->device));
         const double* src = nullptr; int64_t n = 0;
+        if (what == 7) {             // host record: stream ms of the last mra_predict_sites by kernel (MRA_OPT_KERNEL_TIMING)
+            *n_avail = 7;
+            if (out && cap > 0) memcpy(out, pl->sit.ms, (size_t)std::min<int64_t>(cap, 7) * sizeof(double));
+            return MRA_OK;
+        }
         if (what == 0) { src = pl->W.p; n = (int64_t)pl->W.n; }
         else if (what == 1) { src = pl->dnode.p; n = (int64_t)pl->dnode.n; }
         else if (what == 2) { src = pl->stamps.p; n = (int64_t)pl->stamps.n; }     // -DMRA_STAMPS builds: raw 64-bit clock stamps
@@ -3135,7 +3273,7 @@ int mra_plan_set_option(mra_plan* pl, int option, int64_t value) {
         // options that change which kernel produces or factorises the leaves' C blocks bring the phantom-row launch back; the others
         // (timing, front / knot / solve / update variants) never touch C
         if (option == MRA_OPT_FUSED || option == MRA_OPT_GEMM_LDS || option == MRA_OPT_LEAF_GEMM || option == MRA_OPT_CHOL_TILES) pl->cphantom_valid = false;
-        if (option != MRA_OPT_KERNEL_TIMING && option != MRA_OPT_SAMPLE_SOLVE) pl->slv.valid = false;     // the next pass may run other kernels: mra_solve factorises again
+        if (option != MRA_OPT_KERNEL_TIMING && option != MRA_OPT_SAMPLE_SOLVE && option != MRA_OPT_SITES_CHUNK_BYTES) pl->slv.valid = false;     // the next pass may run other kernels: mra_solve factorises again
         switch (option) {
         case MRA_OPT_KERNEL_TIMING: pl->ktiming = value != 0; return MRA_OK;
         case MRA_OPT_FUSED: pl->use_fused = value != 0; return MRA_OK;
@@ -3160,6 +3298,10 @@ int mra_plan_set_option(mra_plan* pl, int option, int64_t value) {
         case MRA_OPT_SAMPLE_SOLVE:
             if (value != 0 && value != 1) throw MraError(MRA_ERR_INVALID, "option 20: 0 or 1");
             pl->slv.in_sampler = (int)value;
+            return MRA_OK;
+        case MRA_OPT_SITES_CHUNK_BYTES:
+            if (value < 0) throw MraError(MRA_ERR_INVALID, "option 21: the site chunk budget is a byte count >= 0");
+            pl->sit.chunk_bytes = (size_t)value;
             return MRA_OK;
         case MRA_OPT_CASCADE_GROUP:
             if (!pl->regular) return MRA_OK;          // (no fused cascade: nothing is grouped, the decision stays 0)
@@ -3205,6 +3347,7 @@ int mra_plan_get_option(mra_plan* pl, int option, int64_t* value) {
             case MRA_OPT_CASCADE_GROUP: *value = pl->cascade_group_siblings; break;
             case MRA_OPT_SAMPLE_GRAM_BYTES: *value = (int64_t)pl->smp.gram_bytes; break;
             case MRA_OPT_SAMPLE_SOLVE: *value = pl->slv.in_sampler; break;
+            case MRA_OPT_SITES_CHUNK_BYTES: *value = (int64_t)pl->sit.chunk_bytes; break;
             case OPT_KERNEL_SHAPE: *value = pl->dbg; break;
             default: throw MraError(MRA_ERR_INVALID, "unknown option");
         }

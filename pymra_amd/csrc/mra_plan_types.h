@@ -11,6 +11,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <dlfcn.h>
+#include <functional>
 #include <initializer_list>
 #include <rccl/rccl.h>      // types and enum values only: the library itself is loaded with dlopen at run time
 #include <set>
@@ -219,6 +220,15 @@ struct CovLeaf {                // one leaf
     const double* chain;        // anc x16: the parent's [tau ; tau_chain] (nullptr when anc == 0)
     long row0;
     int nrows, anc, a0;         // a0: first ancestor column in W
+};
+
+// ---- mra_predict_sites: descriptors of the site kernels (mra_site_kernels.h, launched from mra_launch_sites.hip).
+// The leaves go through the solver's SolveLeaf (Lc, Ut, obs; beta in gb and q in uy after the backward sweep).
+struct SiteNode {               // one non-leaf node, as an ancestor of a site
+    const double* Lp;           // cw x cw (ld cw): the prior factor L_j (identity rows at phantom knots)
+    const double* F;            // Lt in rows [0, cw), Zt in rows [cw, cw + anc) (its y block below is not read); row stride ld
+    const int* knots;           // cw padded rows of the node's knots (-1: phantom)
+    int ld, cw, c0, anc;        // c0: first column of the node's own block in W; its ancestors' columns are [c0 + cw, c0 + cw + anc)
 };
 
 struct LevelData {
@@ -514,6 +524,20 @@ struct mra_plan {
         DevVec<double> ab, out, nb, gpart, gram;  // 16 x P in / out blocks; node buffers; gram partial sums; 16 x 16
         size_t work_bytes = 0;
     } cov;
+    // prediction at new sites (mra_predict_sites): reads W, the prior factors and the fronts of the pass mra_solve keeps (slv.valid), the
+    // solver's leaf descriptors and, for the mean, its sweeps.  Descriptors are built on the first call and again whenever the solver's
+    // are; the work buffers hold one chunk of site tiles (MRA_OPT_SITES_CHUNK_BYTES) and grow on demand.
+    struct Sites {
+        bool built = false;
+        DevVec<SiteNode> nodes;                   // [n_nodes] (leaves: unused)
+        DevVec<int> chain, chain_ptr;             // a leaf's ancestors, root first: chain[chain_ptr[t] .. chain_ptr[t + 1])
+        int anc_max = 0, nop_max = 0;             // widest ancestor chain / observation block among the leaves
+        size_t chunk_bytes = 0;                   // MRA_OPT_SITES_CHUNK_BYTES (0: SITES_CHUNK_BYTES)
+        long cap_tiles = 0;                       // tiles the work buffers hold
+        DevVec<int> tleaf;                        // [tile] leaf slot
+        DevVec<double> xs, a, b, t, var, mean;    // [tile]: 16 x d sites; a, b (anc_max x16); t (nop_max x16); 16 variances; 16 x 16 means
+        double ms[7] = {0, 0, 0, 0, 0, 0, 0};     // stream ms of the last call with MRA_OPT_KERNEL_TIMING: basis, leaf, chain, mean, the solver's sweeps, uploads, downloads
+    } sit;
     // comm
     void* rccl = nullptr;
     ncclComm_t comm = nullptr;
@@ -564,10 +588,21 @@ void launch_predict_hi(mra_plan* pl, const PredHiArgs& hi, const PredArgs& low, 
 // mra_launch_solve.hip: descriptors + work buffers of mra_solve; one block of <= 16 columns (slv.yb -> slv.out, slv.quad; launches
 // only, on pl->stream); the 16-column glue of the sampler's MRA_OPT_SAMPLE_SOLVE path
 void mra_solver_build(mra_plan* pl);
-void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad);
+void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad, bool want_rows = true);      // want_rows false: stop before step 6 (beta and q stay in the leaves' gb / uy)
 void mra_solver_pseudo(mra_plan* pl, const double* y, const double* x, const SampleZ& zs, long slot0);
 void mra_solver_addmean(mra_plan* pl, double* x, int ns);
 // mra_launch_cov.hip: descriptors + work buffers of mra_cov_apply; one block of <= 16 columns (cov.ab -> cov.out, cov.gram; launches
 // only, on pl->stream; the posterior goes through slv.yb, mra_solver_block and slv.out)
 void mra_cov_build(mra_plan* pl);
 void mra_cov_block(mra_plan* pl, bool posterior, bool want_gram);
+// mra_launch_sites.hip: descriptors + work buffers of mra_predict_sites; the kernels of one chunk of n_tiles site tiles (sit.xs, sit.tleaf
+// -> sit.var, sit.mean; launches only, on pl->stream).  mra_sites_tile_bytes: work memory of one tile.
+constexpr size_t SITES_CHUNK_BYTES = (size_t)256 << 20;
+void mra_sites_build(mra_plan* pl);
+size_t mra_sites_tile_bytes(const mra_plan* pl);
+void mra_sites_reserve(mra_plan* pl, long n_tiles);
+void mra_sites_basis(mra_plan* pl, long n_tiles);
+void mra_sites_var(mra_plan* pl, long n_tiles);
+void mra_sites_mean(mra_plan* pl, long n_tiles, int n_cols);
+// with MRA_OPT_KERNEL_TIMING: `work` between two events on pl->stream, the time added to sit.ms[which] (one synchronisation each: a measuring mode)
+void mra_sites_timed(mra_plan* pl, int which, const std::function<void()>& work);

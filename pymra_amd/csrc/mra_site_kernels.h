@@ -1,0 +1,269 @@
+// mra_site_kernels.h - kernels of mra_predict_sites: the posterior mean and variance of the MRA process at
+// locations that are not rows of the tree, from the state one likelihood pass leaves in the plan (the prior W and factors L_j, the
+// leaves' L_c and Ut, the fronts' Lt and Zt) and, for the mean, the beta / q of the solver's backward sweep.  Included by
+// mra_launch_sites.hip only, so that the other translation units keep their object code.
+//
+// A tile is 16 sites of ONE leaf; the 16 sites are the 16 columns (N) of v_mfma_f64_16x16x4_f64 throughout, so a^T, t, b and p_j are
+// k x16 arrays in the solver's "x16" layout: element (row, site) at row * 16 + site.  Every column of an MFMA product, of a
+// substitution and of a column sum depends on that column's operands alone and is summed in an order that depends on the plan alone:
+// the result for a site is a pure function of (site, leaf, plan state), whatever shares its tile.
+// One wave per tile (workgroups of 64): the tiles of a leaf are neighbours in the grid, so L_c and Ut are served by the caches after
+// the first of them.  MFMA conventions as in mra_solve_kernels.h: lane (r, q) = (lane & 15, lane >> 4); mfma16(a, b, acc) over k-step
+// s takes a = A[r][q + 4 s], b = B[q + 4 s][r] and leaves D[q + 4 j][r] in acc[j].
+#pragma once
+#include "mra_plan_types.h"      // SolveLeaf, SiteNode; mra_kernels.h
+
+template <int MODE>
+__device__ __forceinline__ double site_cov(const KernelParams& kp, double D2) {
+    if (MODE == 3) {             // the Kanter taper through sinpi / cospi (no range-reduction table on the stack), as k_solve_rows
+        const double D = fmin(sqrt_pos(D2) * kp.c_inv_l, 2.0);
+        const double p2 = 6.283185307179586 * D;
+        const double v = (1.0 - D) * sinpi(2.0 * D) / p2 + 0.3183098861837907 * (1.0 - cospi(2.0 * D)) / p2;
+        return kp.amp * ((D == 0.0) ? 1.0 : ((D > 1.0) ? 0.0 : v));
+    }
+    return cov_of_dist2<MODE>(kp, D2);
+}
+
+// x <- L^-1 rhs for a lower-triangular L (n = 16 nt rows, row stride ld; only its lower triangle is read) and 16 columns, x in the
+// x16 layout.  rhs(I) gives rows I * 16 + q + 4 j of column r in element j; it may read x's own tile I (in-place solve).  Off-diagonal
+// tiles on the MFMA, the 16 x 16 diagonal block by substitution across the wave (the block in LDS, the solved row broadcast with one
+// shuffle per step) - k_solve_leaf_trsm<false>.  Ld: 256 doubles of LDS.  Ends with x visible to the whole wave.
+template <class RHS>
+__device__ __forceinline__ void site_trsm(const double* __restrict__ L, int ld, int nt, double* __restrict__ x, double* Ld, RHS rhs) {
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    for (int I = 0; I < nt; ++I) {
+        d4 acc = rhs(I);
+        for (int J = 0; J < I; ++J) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int k = J * 16 + q + 4 * s;
+                acc = mfma16(-gld(L + (long)(I * 16 + r) * ld + k), gld(x + (long)k * 16 + r), acc);
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int j = 0; j < 4; ++j) Ld[lane + 64 * j] = gld(L + (long)(I * 16 + q + 4 * j) * ld + I * 16 + r);
+        __syncthreads();
+        // Ld[i * 16 + k] = L_II[i][k]; lane (r, q) holds rows q + 4 j of column r
+#pragma unroll
+        for (int k = 0; k < 16; ++k) {
+            const double xk = __shfl(acc[k >> 2], r + 16 * (k & 3), 64) / Ld[k * 17];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int row = q + 4 * j;
+                if (row > k) acc[j] = __builtin_fma(-Ld[row * 16 + k], xk, acc[j]);
+                if (row == k) acc[j] = xk;
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gst(x + (long)(I * 16 + q + 4 * j) * 16 + r, acc[j]);
+        __syncthreads();             // the tile is read back by every lane of the wave in the next steps
+    }
+}
+
+// sum over the n rows of an x16 array of the squares, per column: the lane's quarter of the rows (k = q mod 4, ascending), then the
+// four quarters in a fixed order.  Every lane of column r gets the sum.
+__device__ __forceinline__ double site_colsq(const double* __restrict__ x, int n, int r, int q) {
+    double s = 0.0;
+    for (int k = q; k < n; k += 4) { const double v = gld(x + (long)k * 16 + r); s = __builtin_fma(v, v, s); }
+    s += __shfl_xor(s, 16, 64);
+    s += __shfl_xor(s, 32, 64);
+    return s;
+}
+
+// ---- 1. basis: a(s), top-down along the leaf's chain ---------------------------------------------------------------------------------
+// a_k = L_k^-1 (C(Q_k, s) - W[Q_k, ancestors of k] a_{<k}), the row recursion of the prior for a location that is not a row: knot
+// coordinates and W rows are gathered through the node's knot list; a phantom knot gives 0.  The covariance value is computed by the
+// lane that holds the element (knot q + 4 j of the tile, site r).
+template <int DIM, int MODE>
+__global__ __launch_bounds__(64, 4) void k_site_basis(const SolveLeaf* __restrict__ lv, const SiteNode* __restrict__ nodes,
+                                                      const int* __restrict__ chain_ptr, const int* __restrict__ chain,
+                                                      const int* __restrict__ tile_leaf, const double* __restrict__ xs,
+                                                      const double* __restrict__ W, long ldw, const double* __restrict__ X,
+                                                      KernelParams kp, double* __restrict__ a_buf, long a_stride) {
+    __shared__ double Ld[256];
+    const long tile = blockIdx.x;
+    const int t = tile_leaf[tile];
+    const SolveLeaf L = lv[t];
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    double* a = a_buf + tile * a_stride;
+    double xr[DIM];
+#pragma unroll
+    for (int e = 0; e < DIM; ++e) xr[e] = gld(xs + (tile * 16 + r) * DIM + e);
+    const int c0 = chain_ptr[t], c1 = chain_ptr[t + 1];
+    for (int c = c0; c < c1; ++c) {
+        const SiteNode N = nodes[chain[c]];
+        const int own = N.c0 - L.a0, up = own + N.cw;          // the node's own block and its ancestors' blocks in a
+        const double* Wup = W + N.c0 + N.cw;
+        site_trsm(N.Lp, N.cw, N.cw >> 4, a + (long)own * 16, Ld, [&](int I) {
+            d4 acc;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int kn = gldi(N.knots + I * 16 + q + 4 * j);
+                double xk[DIM];
+#pragma unroll
+                for (int e = 0; e < DIM; ++e) xk[e] = gld(X + (long)(kn >= 0 ? kn : 0) * DIM + e);
+                const double cv = site_cov<MODE>(kp, pair_dist2<DIM>(xk, xr, kp.circular));
+                acc[j] = kn >= 0 ? cv : 0.0;
+            }
+            const int kr = gldi(N.knots + I * 16 + r);
+            const double* wrow = Wup + (long)(kr >= 0 ? kr : 0) * ldw;
+            for (int k0 = 0; k0 < N.anc; k0 += 16) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int k = k0 + q + 4 * s;
+                    const double w = gld(wrow + k);
+                    acc = mfma16(kr >= 0 ? -w : 0.0, gld(a + (long)(up + k) * 16 + r), acc);
+                }
+            }
+            return acc;
+        });
+    }
+}
+
+// ---- 2. leaf: t = L_c^-1 C(o, s) - Ut_anc^T a, b = a - Ut_anc t, v = max(C(s, s) - |a|^2 - |t|^2, 0) ---------------------------------
+// The substitution is k_solve_leaf_trsm<false>'s, the two Ut products are k_solve_leaf_sbeta's.  Phantom observations contribute 0.
+template <int DIM, int MODE>
+__global__ __launch_bounds__(64, 4) void k_site_leaf(const SolveLeaf* __restrict__ lv, const int* __restrict__ tile_leaf,
+                                                     const double* __restrict__ xs, const double* __restrict__ X, KernelParams kp,
+                                                     const double* __restrict__ a_buf, double* __restrict__ b_buf, long a_stride,
+                                                     double* __restrict__ t_buf, long t_stride, double* __restrict__ var) {
+    __shared__ double Ld[256];
+    const long tile = blockIdx.x;
+    const SolveLeaf L = lv[tile_leaf[tile]];
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4, nop = L.nop, anc = L.anc;
+    const double* a = a_buf + tile * a_stride;
+    double* b = b_buf + tile * a_stride;
+    double* tt = t_buf + tile * t_stride;
+    double xr[DIM];
+#pragma unroll
+    for (int e = 0; e < DIM; ++e) xr[e] = gld(xs + (tile * 16 + r) * DIM + e);
+    site_trsm(L.Lc, nop, nop >> 4, tt, Ld, [&](int I) {
+        d4 acc;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int o = gldi(L.obs + I * 16 + q + 4 * j);
+            double xo[DIM];
+#pragma unroll
+            for (int e = 0; e < DIM; ++e) xo[e] = gld(X + (long)(o >= 0 ? o : 0) * DIM + e);
+            const double cv = site_cov<MODE>(kp, pair_dist2<DIM>(xo, xr, kp.circular));
+            acc[j] = o >= 0 ? cv : 0.0;
+        }
+        return acc;
+    });
+    for (int ot = 0; ot < (nop >> 4); ++ot) {
+        d4 acc;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = gld(tt + (long)(ot * 16 + q + 4 * j) * 16 + r);
+        for (int a0 = 0; a0 < anc; a0 += 16) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const int k = a0 + q + 4 * s;
+                acc = mfma16(-gld(L.Ut + (long)k * nop + ot * 16 + r), gld(a + (long)k * 16 + r), acc);
+            }
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int k = ot * 16 + q + 4 * j;
+            gst(tt + (long)k * 16 + r, gldi(L.obs + k) >= 0 ? acc[j] : 0.0);
+        }
+    }
+    __syncthreads();
+    for (int at = 0; at < (anc >> 4); ++at) {
+        d4 acc;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = gld(a + (long)(at * 16 + q + 4 * j) * 16 + r);
+        for (int o0 = 0; o0 < nop; o0 += 16) {
+            const d4 u = load_rowlane(L.Ut + (long)at * 16 * nop + o0, nop, r, q);
+#pragma unroll
+            for (int s = 0; s < 4; ++s) acc = mfma16(-u[s], gld(tt + (long)(o0 + q + 4 * s) * 16 + r), acc);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gst(b + (long)(at * 16 + q + 4 * j) * 16 + r, acc[j]);
+    }
+    const double v = site_cov<MODE>(kp, 0.0) - site_colsq(a, anc, r, q) - site_colsq(tt, nop, r, q);
+    if (q == 0) gst(var + tile * 16 + r, fmax(v, 0.0));
+}
+
+// ---- 3. chain: parent up to root, p_j = Lt_j^-1 b[own], b[ancestors of j] -= Zt_j p_j, var += |p_j|^2 --------------------------------
+// The solver's forward sweep (k_solve_front_fwd) on one chain, in place in b.
+__global__ __launch_bounds__(64, 4) void k_site_chain(const SolveLeaf* __restrict__ lv, const SiteNode* __restrict__ nodes,
+                                                      const int* __restrict__ chain_ptr, const int* __restrict__ chain,
+                                                      const int* __restrict__ tile_leaf, double* __restrict__ b_buf, long a_stride,
+                                                      double* __restrict__ var) {
+    __shared__ double Ld[256];
+    const long tile = blockIdx.x;
+    const int t = tile_leaf[tile];
+    const SolveLeaf L = lv[t];
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    double* b = b_buf + tile * a_stride;
+    double v = 0.0;
+    const int c0 = chain_ptr[t], c1 = chain_ptr[t + 1];
+    for (int c = c1 - 1; c >= c0; --c) {
+        const SiteNode N = nodes[chain[c]];
+        double* p = b + (long)(N.c0 - L.a0) * 16;
+        double* up = p + (long)N.cw * 16;
+        site_trsm(N.F, N.ld, N.cw >> 4, p, Ld, [&](int I) {
+            d4 acc;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = gld(p + (long)(I * 16 + q + 4 * j) * 16 + r);
+            return acc;
+        });
+        for (int at = 0; at < (N.anc >> 4); ++at) {
+            d4 acc;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) acc[j] = gld(up + (long)(at * 16 + q + 4 * j) * 16 + r);
+            for (int k0 = 0; k0 < N.cw; k0 += 16) {
+                const d4 z = load_rowlane(N.F + (long)(N.cw + at * 16) * N.ld + k0, N.ld, r, q);
+#pragma unroll
+                for (int s = 0; s < 4; ++s) acc = mfma16(-z[s], gld(p + (long)(k0 + q + 4 * s) * 16 + r), acc);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) gst(up + (long)(at * 16 + q + 4 * j) * 16 + r, acc[j]);
+        }
+        __syncthreads();
+        v += site_colsq(p, N.cw, r, q);
+    }
+    if (q == 0) gst(var + tile * 16 + r, gld(var + tile * 16 + r) + v);
+}
+
+// ---- 4. mean: mean[site, 0:16] = a(site)^T beta + C(site, o) q ------------------------------------------------------------------------
+// k_solve_rows with a(s) in place of a row of W: the 16 sites are the M side here, the 16 observation vectors the N side.  Columns
+// < n_cols are written: out[c * ldo + tile * 16 + site].
+template <int DIM, int MODE>
+__global__ __launch_bounds__(64, 4) void k_site_mean(const SolveLeaf* __restrict__ lv, const int* __restrict__ tile_leaf,
+                                                     const double* __restrict__ xs, const double* __restrict__ X, KernelParams kp,
+                                                     const double* __restrict__ a_buf, long a_stride, int n_cols,
+                                                     double* __restrict__ out, long ldo) {
+    const long tile = blockIdx.x;
+    const SolveLeaf L = lv[tile_leaf[tile]];
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    const double* a = a_buf + tile * a_stride;
+    d4 acc = {0, 0, 0, 0};
+    for (int k0 = 0; k0 < L.anc; k0 += 16) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int k = k0 + q + 4 * s;
+            acc = mfma16(gld(a + (long)k * 16 + r), gld(L.gb + (long)k * 16 + r), acc);
+        }
+    }
+    double xr[DIM];
+#pragma unroll
+    for (int e = 0; e < DIM; ++e) xr[e] = gld(xs + (tile * 16 + r) * DIM + e);
+    for (int o0 = 0; o0 < L.nop; o0 += 16) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int k = o0 + q + 4 * s;
+            const int o = gldi(L.obs + k);
+            double xo[DIM];
+#pragma unroll
+            for (int e = 0; e < DIM; ++e) xo[e] = gld(X + (long)(o >= 0 ? o : 0) * DIM + e);
+            const double cv = site_cov<MODE>(kp, pair_dist2<DIM>(xr, xo, kp.circular));
+            acc = mfma16(o >= 0 ? cv : 0.0, gld(L.uy + (long)k * 16 + r), acc);
+        }
+    }
+    if (r < n_cols) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) gst(out + (long)r * ldo + tile * 16 + q + 4 * j, acc[j]);
+    }
+}
