@@ -343,6 +343,13 @@ int mra_get_timers(mra_plan *plan, double *out_ms, int capacity);
                                       block's prior pass (one pass per block instead of 1 + 16) */
 #define MRA_OPT_SITES_CHUNK_BYTES 21 /* mra_predict_sites: bytes of site work buffers (a, b, t, sites, results) per chunk of tiles, at least one tile
                                       per chunk; 0 (default): 256 MiB.  The results do not depend on it; setting it keeps mra_solve's factors */
+#define MRA_OPT_LEAF_ORDER     22  /* scheduling of the per-leaf launches of the fused path; the results do not depend on it, bit for bit.
+                                      1 (default): (a) where the leaf Cholesky is split in two launches, the few leaves of more than 8 observation
+                                      tiles factorise, solve and (predict) update on the side stream beside the small ones; (b) inside the small
+                                      leaves and inside the others, every ordered leaf list takes the leaves of most tiles first.  0: leaf order,
+                                      serial launches.  For A/B runs: 2: (a) alone, 3: (b) alone, 4: 1 with the residual product's problems in
+                                      that order as well.  (a) is read when a pass opens; (b) when the leaf lists are built: it takes effect
+                                      with the next mra_plan_set_obs.  mra_get_route does not report it */
 int mra_plan_set_option(mra_plan *plan, int option, int64_t value);
 /* current value of an option (so that a caller can change one temporarily and put it back) */
 int mra_plan_get_option(mra_plan *plan, int option, int64_t *value);

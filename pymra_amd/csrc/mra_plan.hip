@@ -1071,16 +1071,27 @@ static void build_big_panels(mra_plan* pl, const LeafDescs& d) {
     }
 }
 
-// The stable small-first order of the leaves: those with at most LEAF_SMALL_TILES observation tiles (their count: the return value),
-// then the others, leaf order within each group.  EVERY small-first list is this one permutation - gLeafCholSorted, the *Plain*
-// row-solve lists, gLeafSolve, gLeafUpdatePlain: the kernels index one list with a position taken from another, and run_all steps
-// into each by the number of small leaves.
+// Does a leaf of ta observation tiles go before one of tb in the small-first order?  The small ones (at most LEAF_SMALL_TILES tiles)
+// before the others; longest_first: inside either part the one with more tiles - a leaf's Cholesky, row solve and residual product all
+// take time in proportion to its tiles, and a launch that hands out its longest workgroups first ends with the shortest tail.
+// False both ways for leaves that tie: a stable sort keeps them in leaf order.
+static inline bool leaf_goes_before(int ta, int tb, bool longest_first) {
+    const bool sa = ta <= LEAF_SMALL_TILES, sb = tb <= LEAF_SMALL_TILES;
+    if (sa != sb) return sa;
+    return longest_first && ta > tb;
+}
+
+// The small-first order of the leaves: those with at most LEAF_SMALL_TILES observation tiles (their count: the return value), then
+// the others; inside each group by decreasing tile count (MRA_OPT_LEAF_ORDER, read here: it takes effect with the next
+// mra_plan_set_obs), leaf order among equals - without the option leaf order throughout.  EVERY small-first list is this one
+// permutation - gLeafCholSorted, the *Plain* row-solve lists, gLeafSolve, gLeafSolveHalf, gLeafUpdatePlain: the kernels index one list
+// with a position taken from another, and run_all steps into each by the number of small leaves.  (leaf_upd_dev is indexed by leaf.)
 static size_t order_small_first(const mra_plan* pl, std::vector<size_t>& order) {
     const size_t nl = pl->leaf_nop.size();
-    order.clear();
-    order.reserve(nl);
-    for (int pass = 0; pass < 2; ++pass)
-        for (size_t t = 0; t < nl; ++t) if ((pl->leaf_nop[t] / 16 <= LEAF_SMALL_TILES) == (pass == 0)) order.push_back(t);
+    order.resize(nl);
+    for (size_t t = 0; t < nl; ++t) order[t] = t;
+    const bool longest_first = pl->leaf_longest_first;
+    std::stable_sort(order.begin(), order.end(), [&](size_t a, size_t b) { return leaf_goes_before(pl->leaf_nop[a] / 16, pl->leaf_nop[b] / 16, longest_first); });
     size_t n_small = 0;
     while (n_small < nl && pl->leaf_nop[order[n_small]] / 16 <= LEAF_SMALL_TILES) ++n_small;
     return n_small;
@@ -1092,10 +1103,13 @@ static std::vector<T> in_order(const std::vector<T>& v, const std::vector<size_t
     return out;
 }
 
-// the per-leaf descriptors to the device, in leaf order (and the C-only factorisations small first as well)
+// the per-leaf descriptors to the device, in leaf order (and the C-only factorisations small first as well; with resid_longest_first
+// the residual products of the device kernels too: every problem carries all its operands, so the list may be dealt in any order)
 static void upload_leaf_descriptors(mra_plan* pl, const LeafDescs& d, const std::vector<size_t>& order) {
     pl->hLeafResid = d.resid; pl->leaf_nobs_host = d.nobs;
     pl->gLeafResidLik.upload(d.resid_lik);
+    pl->gLeafResidSorted.upload(pl->resid_longest_first ? in_order(d.resid, order) : std::vector<GemmProb>());
+    pl->gLeafResidLikSorted.upload(pl->resid_longest_first ? in_order(d.resid_lik, order) : std::vector<GemmProb>());
     pl->gLeaf.upload(d.lp); pl->gLeafResid.upload(d.resid); pl->gLeafSyrk.upload(d.syrk); pl->gLeafUpdate.upload(d.upd);
     pl->gLeafCholFull.upload(d.chol_full); pl->gLeafCholLik.upload(d.chol_lik); pl->gLeafCholC.upload(d.chol_c);
     // (k_chol_tiles<8, 4> at three workgroups per CU for the small matrices, then the few larger ones)
@@ -1321,11 +1335,13 @@ static void launch_parent_front(mra_plan* pl, int nacc, size_t nprob, size_t lds
 
 // Cholesky of the nl leaves' C blocks where every one fits (LeafChol but BigPanels).  k_chol_tiles: one workgroup per matrix, tiles in
 // registers, next diagonal block factorised beside the trailing update; k_chol_wave: one wave per matrix
-static void launch_leaf_chol(mra_plan* pl, const PassRoute& r, size_t nl) {
+// (TilesSplit is two launches: `part` picks the small leaves', the others', or both)
+enum class LeafPart { All, Small, Rest };
+static void launch_leaf_chol(mra_plan* pl, const PassRoute& r, size_t nl, LeafPart part = LeafPart::All) {
     const size_t ns = pl->n_chol_small;      // (gLeafCholSorted: the leaves of at most LEAF_SMALL_TILES tiles first)
     if (r.chol == LeafChol::TilesSplit) {
-        if (ns) hipLaunchKernelGGL((k_chol_tiles<8, 4>), dim3((unsigned)ns), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p, pl->dnode.p, pl->errflag.p);
-        if (nl > ns) hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)(nl - ns)), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p + ns, pl->dnode.p, pl->errflag.p);
+        if (ns && part != LeafPart::Rest) hipLaunchKernelGGL((k_chol_tiles<8, 4>), dim3((unsigned)ns), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p, pl->dnode.p, pl->errflag.p);
+        if (nl > ns && part != LeafPart::Small) hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)(nl - ns)), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p + ns, pl->dnode.p, pl->errflag.p);
     }
     else if (r.chol == LeafChol::TilesOne) hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)nl), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p, pl->dnode.p, pl->errflag.p);
     else hipLaunchKernelGGL((k_chol_wave<LEAF_MAX_TILES>), dim3((unsigned)((nl + 3) / 4)), dim3(256), 0, pl->stream, pl->gLeafCholC.p, (int)nl, pl->dnode.p, pl->errflag.p);
@@ -1694,8 +1710,8 @@ static const PassRoute& open_pass(mra_plan* pl, uint32_t flags, bool full_rows) 
     HIP_TRY(mraSetDevice(pl->device));
     if (pl->pass_open) {
         // the previous pass never reached finish_run (an error was thrown, or a split run was abandoned before
-        // mra_run_resume): wait for whatever it left on the two streams, and clear the device error flag that
-        // only the last kernel of a pass resets
+        // mra_run_resume): wait for whatever it left on the two streams (every fork's work is on one of them, whether its join
+        // was recorded or not), and clear the device error flag that only the last kernel of a pass resets
         pl->cphantom_valid = false;
         if (pl->side_pending) HIP_TRY(hipStreamWaitEvent(pl->stream, pl->ev_join, 0));
         HIP_TRY(hipStreamSynchronize(pl->stream));
@@ -1713,6 +1729,11 @@ static const PassRoute& open_pass(mra_plan* pl, uint32_t flags, bool full_rows) 
     if (!pl->lik_general_valid && route_for(pl, flags, full_rows).lik_general) ensure_lik_general(pl);      // (once; route_for reads the verdict)
     pl->route = route_for(pl, flags, full_rows);
     pl->route_set = true;
+    // MRA_OPT_LEAF_ORDER's fork (pass state, not part of the route read-back): there is a split to overlap - two launches per stage
+    // (TilesSplit; TilesOne has one launch for all leaves) and leaves on either side of it
+    const PassRoute& r = pl->route;
+    pl->leaf_fork = pl->use_leaf_fork && r.path == PassPath::Fused && r.chol == LeafChol::TilesSplit &&
+                    0 < pl->n_trsm_small && pl->n_trsm_small < pl->leaf_nodes.size();
     return pl->route;
 }
 
@@ -1779,8 +1800,8 @@ static void run_leaf_product(mra_plan* pl, const PassRoute& r, size_t nl) {
         if (r.leaf_resident) launch_leaf_gemm<EPI_HOSTCOV>(pl, pl->gLeafResid.p, nl);
         else launch_gemm<EPI_HOSTCOV>(pl, pl->gLeafResid.p, nl, pl->leaf_max_rows, pl->leaf_max_nop);
     }
-    else if (r.c_only) launch_gemm<EPI_COV>(pl, pl->gLeafResidLik.p, nl, pl->leaf_max_nop, pl->leaf_max_nop);
-    else if (r.leaf_resident) launch_leaf_gemm<EPI_COV>(pl, pl->gLeafResid.p, nl);
+    else if (r.c_only) launch_gemm<EPI_COV>(pl, pl->gLeafResidLikSorted.n ? pl->gLeafResidLikSorted.p : pl->gLeafResidLik.p, nl, pl->leaf_max_nop, pl->leaf_max_nop);
+    else if (r.leaf_resident) launch_leaf_gemm<EPI_COV>(pl, pl->gLeafResidSorted.n ? pl->gLeafResidSorted.p : pl->gLeafResid.p, nl);
     else launch_gemm<EPI_COV>(pl, pl->gLeafResid.p, nl, pl->leaf_max_rows, pl->leaf_max_nop);
 }
 
@@ -1805,19 +1826,54 @@ static void run_leaf_c_fix(mra_plan* pl, const PassRoute& r, size_t nl) {
     }
 }
 
-// every leaf's C fits k_chol_tiles / k_chol_wave: the Cholesky, then the LDS row solve of the rows below C
+// A fork to the side stream.  With `on` the launch helpers (they use pl->stream) go to stream2 between the constructor and join();
+// without it nothing moves.  after: the event that orders stream2 behind what the main stream holds now (nullptr: stream2 is already
+// behind everything the forked work reads); joined: recorded on stream2 by join(), for the main stream to wait for.  The leaves' fork
+// has events of its own, so that no wait can be lost to a later record of the predict-only fork's.  A throw in
+// between restores pl->stream (later launches must not land on the side stream) and records no join event; open_pass then waits for
+// both streams.  Nothing meant for the main stream may be launched while a fork is open.
+struct SideFork {
+    mra_plan* pl; hipStream_t main_stream; bool side; hipEvent_t joined;
+    SideFork(mra_plan* p, bool on, hipEvent_t after, hipEvent_t joined_) : pl(p), main_stream(p->stream), side(on), joined(joined_) {
+        if (!side) return;
+        if (after) {
+            HIP_TRY(hipEventRecord(after, main_stream));
+            HIP_TRY(hipStreamWaitEvent(pl->stream2, after, 0));
+        }
+        pl->stream = pl->stream2;
+    }
+    void join() {
+        if (!side) return;
+        pl->stream = main_stream;
+        HIP_TRY(hipEventRecord(joined, pl->stream2));
+    }
+    ~SideFork() { pl->stream = main_stream; }
+};
+
+// every leaf's C fits k_chol_tiles / k_chol_wave: the Cholesky, then the LDS row solve of the rows below C.  leaf_fork: the few leaves
+// of more than LEAF_SMALL_TILES tiles do both on the side stream meanwhile (two short launches of a handful of workgroups, which
+// would otherwise hold the whole GPU in turn); the main stream waits for them here, behind its own row solve - before any consumer
+// of a leaf's Ut, before mra_run_resume's part of a split pass, and inside the KF_LEAF_CHOL bracket of run_leaf_factor
 static void run_leaf_chol_and_solve(mra_plan* pl, const PassRoute& r, size_t nl) {
-    launch_leaf_chol(pl, r, nl);
     const int obs_tiles = pl->leaf_max_nop / 16;                                              // the widest C, in 16-row tiles
     const int row_tiles = r.predict ? pl->leaf_max_tiles_full : pl->leaf_max_tiles_lik;       // the most row tiles below one leaf's C
-    if (r.path != PassPath::Fused) { launch_trsm2(pl, r.trsm_all, nl, obs_tiles, row_tiles, row_tiles); return; }
+    if (r.path != PassPath::Fused) { launch_leaf_chol(pl, r, nl); launch_trsm2(pl, r.trsm_all, nl, obs_tiles, row_tiles, row_tiles); return; }
     // Fused: the small leaves (the first n_trsm_small of every list) on k_trsm_rows2<LEAF_SMALL_TILES>, one workgroup each
     const size_t n_small = pl->n_trsm_small;
     const int small_row_tiles = (r.predict && !r.solve_fused) ? pl->trsm_small_tiles_full : pl->trsm_small_tiles_lik;
-    if (n_small) launch_trsm2(pl, r.trsm_small, n_small, pl->trsm_small_nt, small_row_tiles, small_row_tiles);
     // the few leaves with more than LEAF_SMALL_TILES observation tiles: several workgroups per leaf when they are few
     // (one leaf per workgroup would put a single 65 us workgroup on the critical path)
-    if (nl > n_small) launch_trsm2(pl, r.trsm_all + n_small, nl - n_small, obs_tiles, row_tiles, (nl - n_small) < 512 ? 4 : row_tiles);
+    auto solve_rest = [&] { launch_trsm2(pl, r.trsm_all + n_small, nl - n_small, obs_tiles, row_tiles, (nl - n_small) < 512 ? 4 : row_tiles); };
+    if (pl->leaf_fork) {
+        SideFork fork(pl, true, pl->ev_leaf_fork, pl->ev_leaf_join);
+        launch_leaf_chol(pl, r, nl, LeafPart::Rest);
+        solve_rest();
+        fork.join();
+    }
+    launch_leaf_chol(pl, r, nl, pl->leaf_fork ? LeafPart::Small : LeafPart::All);
+    if (n_small) launch_trsm2(pl, r.trsm_small, n_small, pl->trsm_small_nt, small_row_tiles, small_row_tiles);
+    if (pl->leaf_fork) HIP_TRY(hipStreamWaitEvent(pl->stream, pl->ev_leaf_join, 0));
+    else if (nl > n_small) solve_rest();
 }
 
 // LeafChol::BigPanels.  Right-looking, 64 columns per step: the panel (factor + solve of ALL rows below, Ut and Tt included) on one
@@ -1883,10 +1939,17 @@ static void run_leaf_update(mra_plan* pl, const PassRoute& r, size_t nl) {
         case LeafUpdate::None: case LeafUpdate::InPredictHi: return;           // (InPredictHi: nothing to launch here)
         case LeafUpdate::InCascade: {
             // the small leaves (<= LEAF_SMALL_TILES observation tiles) take their update inside the predictive cascade; the few larger ones here
+            // (leaf_fork: on the side stream, behind those leaves' row solve, unless the route has put this whole stage there already)
             const size_t n_small = pl->n_trsm_small;
             if (nl <= n_small) return;
-            KTimer kt(pl, KF_LEAF_UPDATE, 0);
-            launch_gemm<EPI_SUB>(pl, pl->gLeafUpdatePlain.p + n_small, nl - n_small, pl->leaf_max_rows, pl->leaf_max_na);
+            const bool to_side = pl->leaf_fork && pl->stream != pl->stream2;
+            SideFork fork(pl, to_side, nullptr, pl->ev_join);
+            {
+                KTimer kt(pl, KF_LEAF_UPDATE, 0);
+                launch_gemm<EPI_SUB>(pl, pl->gLeafUpdatePlain.p + n_small, nl - n_small, pl->leaf_max_rows, pl->leaf_max_na);
+            }
+            fork.join();
+            if (to_side) pl->side_pending = true;       // join_side_stream makes the main stream wait, just before the predictive pass
             return;
         }
         case LeafUpdate::SolveWhole: case LeafUpdate::SolveHalves: run_leaf_solve_update(pl, r, nl); return;
@@ -1895,32 +1958,13 @@ static void run_leaf_update(mra_plan* pl, const PassRoute& r, size_t nl) {
     }
 }
 
-// The fork of the leaf work that only feeds the predictive pass.  With `side` the launch helpers (they use pl->stream) go to the side
-// stream between the constructor and join(); without it nothing moves.  A throw in between restores pl->stream (later launches must
-// not land on the side stream) and records no join event.
-struct SideFork {
-    mra_plan* pl; hipStream_t main_stream; bool side;
-    SideFork(mra_plan* p, bool on) : pl(p), main_stream(p->stream), side(on) {
-        if (!side) return;
-        HIP_TRY(hipEventRecord(pl->ev_fork, main_stream));
-        HIP_TRY(hipStreamWaitEvent(pl->stream2, pl->ev_fork, 0));
-        pl->stream = pl->stream2;
-    }
-    void join() {
-        if (!side) return;
-        pl->stream = main_stream;
-        HIP_TRY(hipEventRecord(pl->ev_join, pl->stream2));
-        pl->side_pending = true;            // join_side_stream makes the main stream wait, just before the predictive pass
-    }
-    ~SideFork() { pl->stream = main_stream; }
-};
-
 // (predict) leaves var and W ready for the predictive pass, on the side stream (side_pending) where the route forks
 static void run_leaf_predict_work(mra_plan* pl, const PassRoute& r, size_t nl) {
-    SideFork fork(pl, r.side);
+    SideFork fork(pl, r.side, pl->ev_fork, pl->ev_join);
     run_leaf_var(pl, r);
     run_leaf_update(pl, r, nl);
     fork.join();
+    if (r.side) pl->side_pending = true;            // join_side_stream makes the main stream wait, just before the predictive pass
 }
 
 // ---- fronts, bottom-up ------------------------------------------------------------------------------------------------------------
@@ -2739,8 +2783,7 @@ static void destroy_plan(mra_plan* pl) {
     for (int k = 0; k < 6; ++k) if (pl->ev[k]) hipEventDestroy(pl->ev[k]);
     drop_arena(pl);
     return_streams(pl);                              // (with the pinned result record and the arena's pinned mirror)
-    if (pl->ev_fork) hipEventDestroy(pl->ev_fork);
-    if (pl->ev_join) hipEventDestroy(pl->ev_join);
+    for (hipEvent_t e : {pl->ev_fork, pl->ev_join, pl->ev_leaf_fork, pl->ev_leaf_join}) if (e) hipEventDestroy(e);
     delete pl;
 }
 struct PlanDeleter { void operator()(mra_plan* pl) const { destroy_plan(pl); } };
@@ -2763,8 +2806,8 @@ static PlanPtr new_plan(int device) {
         // latency-bound chain never wait behind the update.  (On one GPU the update keeps every SIMD's register file
         // full and the pass time does not change; the point is the sharded run.)
         acquire_streams(pl.get());
-        HIP_TRY(hipEventCreateWithFlags(&pl->ev_fork, hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&pl->ev_join, hipEventDisableTiming));
+        for (hipEvent_t* e : {&pl->ev_fork, &pl->ev_join, &pl->ev_leaf_fork, &pl->ev_leaf_join})
+            HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
         for (int k = 0; k < 6; ++k) HIP_TRY(hipEventCreate(&pl->ev[k]));
     }
     init_arena(pl.get());
@@ -3291,6 +3334,12 @@ int mra_plan_set_option(mra_plan* pl, int option, int64_t value) {
         case MRA_OPT_HI_FOLD: pl->use_hi_fold = (int)value; return MRA_OK;
         case MRA_OPT_LIK_ROWS: pl->use_lik_rows = value != 0; return MRA_OK;
         case MRA_OPT_UT_GATHER: pl->ut_gather = value != 0; return MRA_OK;
+        case MRA_OPT_LEAF_ORDER:
+            if (value < 0 || value > 4) throw MraError(MRA_ERR_INVALID, "option 22: 0, 1, 2 (the fork alone), 3 (the order alone) or 4 (1 and the residual product in that order)");
+            pl->use_leaf_fork = value == 1 || value == 2 || value == 4;
+            pl->leaf_longest_first = value == 1 || value == 3 || value == 4;
+            pl->resid_longest_first = value == 4;
+            return MRA_OK;
         case MRA_OPT_SAMPLE_GRAM_BYTES:
             if (value < 0) throw MraError(MRA_ERR_INVALID, "option 19: the Gram batch budget is a byte count >= 0");
             if ((size_t)value != pl->smp.gram_bytes) { pl->smp.gram_bytes = (size_t)value; pl->smp.built = false; }
@@ -3344,6 +3393,7 @@ int mra_plan_get_option(mra_plan* pl, int option, int64_t* value) {
             case MRA_OPT_HI_FOLD: *value = pl->use_hi_fold; break;
             case MRA_OPT_LIK_ROWS: *value = pl->use_lik_rows; break;
             case MRA_OPT_UT_GATHER: *value = pl->ut_gather; break;
+            case MRA_OPT_LEAF_ORDER: *value = pl->resid_longest_first ? 4 : pl->use_leaf_fork ? (pl->leaf_longest_first ? 1 : 2) : (pl->leaf_longest_first ? 3 : 0); break;
             case MRA_OPT_CASCADE_GROUP: *value = pl->cascade_group_siblings; break;
             case MRA_OPT_SAMPLE_GRAM_BYTES: *value = (int64_t)pl->smp.gram_bytes; break;
             case MRA_OPT_SAMPLE_SOLVE: *value = pl->slv.in_sampler; break;

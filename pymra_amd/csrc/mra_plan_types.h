@@ -275,6 +275,7 @@ constexpr int TRSM2_MAX_NT = 12;    // widest block of launch_trsm2 (k_trsm_rows
 static_assert(LEAF_MAX_TILES <= TRSM2_MAX_NT, "the leaves' row solve goes through launch_trsm2 without a fall-back");
 // a "small" leaf: at most this many observation tiles.  The tile count of the instances k_chol_tiles<8, 4>, k_trsm_rows2<8> and
 // k_leaf_solve_update<8, 13, true> that take the small leaves; order_small_first (mra_plan.hip) puts them first in every ordered list
+// and, with MRA_OPT_LEAF_ORDER, the leaves of most tiles first inside either part
 constexpr int LEAF_SMALL_TILES = 8;
 static_assert(LEAF_SMALL_TILES <= LEAF_MAX_TILES, "the small leaves are a subset of those the LDS row solve takes");
 // (the integer values are the MRA_ROUTE_* numbers of include/mra_hip.h: mra_get_route reports them)
@@ -312,6 +313,13 @@ struct mra_plan {
     hipStream_t stream2 = nullptr;       // side stream: the leaf update runs here, beside the front chain / all-reduce (low priority)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     bool side_pending = false;           // work on stream2 that the predictive pass has to wait for
+    // MRA_OPT_LEAF_ORDER (1, the default: the fork and the order; 0: neither; 2, 3, 4 for A/B runs: the fork alone, the order alone, 1 with
+    // the residual product in that order as well)
+    bool use_leaf_fork = true;           // read by open_pass: leaf_fork below
+    bool leaf_longest_first = true;      // read by build_leaf: order_small_first sorts each of its two parts by decreasing tile count
+    bool resid_longest_first = false;    // read by build_leaf: the residual product's problems in that order too (else leaf order)
+    bool leaf_fork = false;              // this pass: the leaves of more than LEAF_SMALL_TILES tiles factorise, solve and update on stream2 beside the small ones
+    hipEvent_t ev_leaf_fork = nullptr, ev_leaf_join = nullptr;      // the events of that fork (SideFork)
     std::string err;
     // topology (host)
     long P = 0;
@@ -349,6 +357,7 @@ struct mra_plan {
     DevVec<double*> leaf_ut;
     DevVec<LeafProb> gLeaf;
     DevVec<GemmProb> gLeafResid, gLeafSyrk, gLeafUpdate, gLeafResidLik;
+    DevVec<GemmProb> gLeafResidSorted, gLeafResidLikSorted;      // resid_longest_first: those of the device kernels once more, in the order of order_small_first (else empty); gLeafResid stays leaf-indexed (MRA_KERNEL_HOST points its problems at the host blocks by leaf)
     std::vector<GemmProb> hLeafResid;
     std::vector<int> leaf_nobs_host;
     DevVec<PanelProb> gLeafCholFull, gLeafCholLik, gLeafCholC, gLeafCholSorted;

@@ -38,6 +38,7 @@ MRA_OPT_CASCADE_GROUP = 18
 MRA_OPT_SAMPLE_GRAM_BYTES = 19
 MRA_OPT_SAMPLE_SOLVE = 20
 MRA_OPT_SITES_CHUNK_BYTES = 21
+MRA_OPT_LEAF_ORDER = 22
 MRA_SAMPLE_CONDITIONAL = 1
 MRA_COV_POSTERIOR = 1
 MRA_BLOCK_W_ROWS, MRA_BLOCK_LPRIOR, MRA_BLOCK_FRONT, MRA_BLOCK_LEAF = 0, 1, 2, 3

@@ -1,5 +1,6 @@
-"""A/B timing of a plan option on config c3 (or rank 0 of an N-way shard): interleaved rounds in one process.
-usage: python tools/ab_option.py <option id> [world]"""
+"""A/B timing of a plan option on config c3 (or rank 0 of an N-way shard): interleaved rounds in one process.  The observations are
+set again after every switch, for the options that are read when the leaf lists are built (MRA_OPT_LEAF_ORDER).
+usage: python tools/ab_option.py <option id> [world [value,value,...]]"""
 import sys, os, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -24,6 +25,7 @@ lik = {}
 for rnd in range(6):
     for v in VALS:
         pl.set_option(opt, v)
+        pl.set_obs(y_obs, c["R"])
         for _ in range(3): step()
         t0 = time.perf_counter()
         for _ in range(20): step()
