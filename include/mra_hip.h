@@ -212,10 +212,35 @@ int mra_cov_apply(mra_plan *plan, uint32_t flags, int64_t n_cols, const double *
 int mra_predict_sites(mra_plan *plan, uint32_t flags, int64_t n_sites, const double *sites, const int32_t *leaf, int64_t n_cols,
                       const double *Y, double *mean, double *var);
 
+/* The joint covariance of the latent MRA process at locations that are not rows of the tree (no counterpart in the reference; DESIGN.md
+ * section 13): what mra_predict_sites gives the diagonal of.  With a_j(s), t(s) and p_j(s) of section 12 and l(u) the leaf of site u,
+ *     prior      Sigma(u, w)      = C(s_u, s_w) if l(u) == l(w), else sum over the common ancestors j of a_j(u)^T a_j(w)
+ *     posterior  Sigma_post(u, w) = sum over the common ancestors j of p_j(u)^T p_j(w)
+ *                                   + [l(u) == l(w)] (C(s_u, s_w) - a(u)^T a(w) - t(u)^T t(w))
+ *     sites, leaf as for mra_predict_sites; flags: 0 (prior) or MRA_COV_POSTERIOR (on the mask of the last set_obs)
+ *     out   (n_sites x n_sites, row-major, the caller's order).  No entry is clamped: the posterior diagonal is mra_predict_sites' var
+ *           without its max(., 0) on the leaf term, and the matrix is positive semi-definite down to roundoff only.
+ * out is symmetric to the bit.  Entry (u, w) is a pure function of (site u, leaf u, site w, leaf w, plan state): the same bits whatever
+ * else is in the call, in whatever order, and whatever MRA_OPT_SITES_CHUNK_BYTES says; duplicated sites give duplicated rows.  At sites
+ * that are tree locations assigned to their own leaf the matrix is the corresponding block of mra_cov_apply's Sigma or Sigma_post, and
+ * the posterior diagonal is the var of mra_get_predict up to rounding.  Inside the library the sites are tiled as for mra_predict_sites,
+ * the work arrays of ALL tiles stay on the device for the call, and the matrix is produced in row panels of whole tiles (at least one;
+ * MRA_OPT_SITES_CHUNK_BYTES bounds the device panel), each 16 x 16 block on or above the diagonal computed once and mirrored.
+ * The state is mra_predict_sites': the first call (and the first after mra_run, mra_run_resume, mra_sample or any set_*) runs one
+ * likelihood pass with W at every row; later calls - and calls after an mra_solve, mra_cov_apply or mra_predict_sites - launch no
+ * factorisation.  Afterwards y, every option and what mra_get_likelihood / mra_get_predict return are as the caller left them.
+ * MRA_ERR_STATE before set_locs / set_obs / set_kernel; MRA_ERR_INVALID for unknown flags, MRA_KERNEL_HOST plans, sharded plans,
+ * n_sites < 0, n_sites > MRA_SITES_COV_MAX (the result is dense: 2 GiB at the cap), a NULL sites, leaf or out with n_sites > 0, a leaf
+ * entry that is out of range or not a leaf node and a non-finite site coordinate (all checked on the host before anything is launched
+ * or allocated).  n_sites == 0 returns MRA_OK.  Blocking. */
+#define MRA_SITES_COV_MAX 16384
+int mra_sites_cov(mra_plan *plan, uint32_t flags, int64_t n_sites, const double *sites, const int32_t *leaf, double *out);
+
 /* Diagnostics for tests (the reference exposes these as attributes of Node objects):
  * what = 0: whitened basis W (P x ldw, row-major) ; 1: per-node log-det terms (n_nodes);
  * 7: stream milliseconds of the last mra_predict_sites, measured while MRA_OPT_KERNEL_TIMING is on (7 values: the basis, leaf, chain
  * and mean kernels, the solver's sweeps, the uploads of sites and the downloads of results);
+ * 8: the same for the last mra_sites_cov (6 values: the basis, leaf, chain and gram kernels, the uploads and the downloads);
  * copies min(capacity, available) doubles into out, returns the available count in *n_avail.
  * (W after a likelihood-only run is complete only with MRA_OPT_LIK_ROWS off: by default such a run computes W at the rows a
  * likelihood needs - the observed rows, and the knots on the level-by-level path - and leaves the others as they were.) */
@@ -342,7 +367,8 @@ int mra_get_timers(mra_plan *plan, double *out_ms, int capacity);
                                       a block of up to 16 draws are 16 right-hand sides of mra_solve's sweeps over the factors of the
                                       block's prior pass (one pass per block instead of 1 + 16) */
 #define MRA_OPT_SITES_CHUNK_BYTES 21 /* mra_predict_sites: bytes of site work buffers (a, b, t, sites, results) per chunk of tiles, at least one tile
-                                      per chunk; 0 (default): 256 MiB.  The results do not depend on it; setting it keeps mra_solve's factors */
+                                      per chunk; mra_sites_cov: bytes of the device row panel of its result, at least one tile row per panel.
+                                      0 (default): 256 MiB.  The results do not depend on it; setting it keeps mra_solve's factors */
 #define MRA_OPT_LEAF_ORDER     22  /* scheduling of the per-leaf launches of the fused path; the results do not depend on it, bit for bit.
                                       1 (default): (a) where the leaf Cholesky is split in two launches, the few leaves of more than 8 observation
                                       tiles factorise, solve and (predict) update on the side stream beside the small ones; (b) inside the small

@@ -258,6 +258,48 @@ class MRATree(object):
         mean, var = self.plan.predict_sites(X, leaf, Yp)
         return np.ascontiguousarray(mean.T), np.sqrt(var)
 
+    def covarianceAt(self, sites, distr="posterior", leaf=None):
+        """(n, n) joint covariance of the latent field at locations that need not be rows of `locs`, from this tree's factors:
+        the posterior given this tree's observations (distr="posterior": its diagonal is predictAt's sd ** 2) or the prior
+        (distr="prior").  sites: (n, d); leaf: None (locate(sites)) or int32[n] leaf node indices.  Symmetric to the bit; positive
+        semi-definite down to roundoff only (duplicated sites and the Iden kernel make it singular).  w @ covarianceAt(grid) @ w is
+        the variance of the functional w . x over a prediction grid.  getLikelihood() and predict() are unchanged."""
+        if distr not in ("prior", "posterior"):
+            raise ValueError('distr must be "prior" or "posterior"')
+        if self.kernel is None:
+            raise NotImplementedError("covarianceAt needs a device kernel: trees built from an opaque callable or a dense matrix cannot evaluate it at new sites")
+        X = self._sites(sites)
+        if leaf is None:
+            leaf = self.locate(X)
+        leaf = np.asarray(leaf)
+        if leaf.shape != (len(X),):
+            raise ValueError("leaf must have shape (n,) = (%d,)" % len(X))
+        return self.plan.sites_cov(X, leaf, posterior=(distr == "posterior"))
+
+    def simulateAt(self, sites, nsim, distr="posterior", seed=None, leaf=None, z=None):
+        """(n, nsim) draws of the latent field at locations that need not be rows of `locs`: mean + F z, with mean predictAt's for
+        this tree's observations (0 for distr="prior"), F the symmetric square root of covarianceAt(sites, distr, leaf) (numpy.linalg.eigh,
+        eigenvalues below 0 set to 0) and z (n, nsim) given, or standard normals from numpy.random.default_rng(seed)."""
+        if self.kernel is None:
+            raise NotImplementedError("simulateAt needs a device kernel: trees built from an opaque callable or a dense matrix cannot simulate at new sites")
+        X = self._sites(sites)
+        if leaf is None:
+            leaf = self.locate(X)
+        S = self.covarianceAt(X, distr=distr, leaf=leaf)
+        n = len(X)
+        nsim = int(nsim)
+        if z is None:
+            z = np.random.default_rng(seed).standard_normal((n, nsim))
+        z = np.asarray(z, dtype=np.float64)
+        if z.shape != (n, nsim):
+            raise ValueError("z must have shape (n, nsim) = (%d, %d)" % (n, nsim))
+        lam, Q = np.linalg.eigh(S)
+        F = (Q * np.sqrt(np.maximum(lam, 0.0))) @ Q.T
+        x = F @ z
+        if distr == "posterior" and n:
+            x += self.predictAt(X, leaf=leaf)[0]
+        return x
+
     def _cov_apply(self, A, distr):
         """Sigma A (or Sigma_post A) for A (N, c) in the caller's row order -> (A at the reported rows else 0 (N, c), out (N, c))."""
         if distr not in ("prior", "posterior"):

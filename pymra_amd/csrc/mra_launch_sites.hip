@@ -1,5 +1,6 @@
 // mra_launch_sites.hip - mra_predict_sites: descriptors, work buffers and the launches of one chunk of site tiles
-// over the state a likelihood pass left in the plan.  A translation unit of its own: the kernels of the pass keep their object code.
+// over the state a likelihood pass left in the plan, and the Gram launch of mra_sites_cov (section 13) over the same buffers.  A
+// translation unit of its own: the kernels of the pass keep their object code.
 #define MRA_KERNELS_TEMPLATES_ONLY
 #include "mra_site_kernels.h"
 
@@ -70,7 +71,7 @@ void mra_sites_timed(mra_plan* pl, int which, const std::function<void()>& work)
     HIP_TRY(hipEventSynchronize(e1));
     float ms = 0.f;
     HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
-    pl->sit.ms[which] += ms;
+    (pl->sit.ms_sink ? pl->sit.ms_sink : pl->sit.ms)[which] += ms;
 }
 static void timed(mra_plan* pl, int which, const std::function<void()>& work) { mra_sites_timed(pl, which, work); }
 
@@ -91,6 +92,18 @@ static void launch_mean(mra_plan* pl, long n, int nc) {
     mra_plan::Sites& T = pl->sit;
     hipLaunchKernelGGL((k_site_mean<DIM, MODE>), dim3((unsigned)n), dim3(64), 0, pl->stream, pl->slv.leaves.p, T.tleaf.p, T.xs.p, pl->X.p, pl->kp,
                        T.a.p, (long)T.anc_max * 16, nc, T.mean.p, n * 16);
+}
+
+template <int DIM, int MODE>
+static void launch_gram(mra_plan* pl, long n, long tile0, long rows, bool post) {
+    mra_plan::Sites& T = pl->sit;
+    const dim3 grid((unsigned)n, (unsigned)rows);
+    if (post)
+        hipLaunchKernelGGL((k_site_gram<DIM, MODE, true>), grid, dim3(64), 0, pl->stream, pl->slv.leaves.p, T.nodes.p, T.chain_ptr.p, T.chain.p, T.tleaf.p,
+                           T.xs.p, pl->kp, T.a.p, T.b.p, (long)T.anc_max * 16, T.t.p, (long)T.nop_max * 16, tile0, T.gram.p, n * 16);
+    else
+        hipLaunchKernelGGL((k_site_gram<DIM, MODE, false>), grid, dim3(64), 0, pl->stream, pl->slv.leaves.p, T.nodes.p, T.chain_ptr.p, T.chain.p, T.tleaf.p,
+                           T.xs.p, pl->kp, T.a.p, T.b.p, (long)T.anc_max * 16, T.t.p, (long)T.nop_max * 16, tile0, T.gram.p, n * 16);
 }
 
 // the <DIM, MODE> instance of the plan's dimension and kernel, as the solver's row kernel is chosen
@@ -129,4 +142,11 @@ void mra_sites_mean(mra_plan* pl, long n, int nc) {
     check_chunk(pl, n);
     if (nc < 1 || nc > 16) throw MraError(MRA_ERR_STATE, "mra_predict_sites: a column block has 1 to 16 columns");
     timed(pl, 3, [&] { MRA_SITES_DISPATCH(launch_mean, pl, n, nc); });
+}
+
+void mra_sites_gram(mra_plan* pl, long n, long tile0, long rows, bool posterior) {
+    check_chunk(pl, n);
+    if (tile0 < 0 || rows < 1 || rows > 65535 || tile0 + rows > n || (size_t)rows * 16 * (size_t)n * 16 > pl->sit.gram.n)
+        throw MraError(MRA_ERR_STATE, "mra_sites_cov: row panel outside its tiles or larger than its buffer");
+    timed(pl, 3, [&] { MRA_SITES_DISPATCH(launch_gram, pl, n, tile0, rows, posterior); });
 }

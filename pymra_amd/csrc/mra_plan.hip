@@ -2601,35 +2601,79 @@ static void sites_tiles(const std::vector<int>& slot_of_leaf_site, int64_t n, si
     }
 }
 
-static void predict_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const double* sites, const int32_t* leaf, int64_t nc,
-                              const double* Y, double* mean, double* var) {
+// What mra_predict_sites and mra_sites_cov check before anything is launched, in this order: the plan (sites_check_plan), then the call's
+// own arguments, then the sites (sites_check_sites, which also gives each site's leaf slot).  `who` names the export in the messages.
+static void sites_check_plan(const mra_plan* pl, const char* who, bool unknown_flags, int64_t n) {
+    char m[200];
     if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
-    if (flags) throw MraError(MRA_ERR_INVALID, "unknown mra_predict_sites flags");
-    if (!(pl->have_locs && pl->have_kernel)) throw MraError(MRA_ERR_STATE, "mra_predict_sites needs set_locs and set_kernel first");
-    if (!pl->have_obs) throw MraError(MRA_ERR_STATE, "mra_predict_sites needs set_obs first");
-    if (pl->host_cov || pl->kp.kind == MRA_KERNEL_HOST) throw MraError(MRA_ERR_INVALID, "mra_predict_sites: MRA_KERNEL_HOST plans cannot predict at new sites (C(Q, s) is evaluated on the device)");
-    if (pl->reduce_level >= 0 || pl->comm || pl->n_ranks > 1) throw MraError(MRA_ERR_INVALID, "mra_predict_sites: sharded plans cannot predict at new sites");
+    if (unknown_flags) { snprintf(m, sizeof m, "unknown %s flags", who); throw MraError(MRA_ERR_INVALID, m); }
+    if (!(pl->have_locs && pl->have_kernel)) { snprintf(m, sizeof m, "%s needs set_locs and set_kernel first", who); throw MraError(MRA_ERR_STATE, m); }
+    if (!pl->have_obs) { snprintf(m, sizeof m, "%s needs set_obs first", who); throw MraError(MRA_ERR_STATE, m); }
+    if (pl->host_cov || pl->kp.kind == MRA_KERNEL_HOST) {
+        snprintf(m, sizeof m, "%s: MRA_KERNEL_HOST plans cannot predict at new sites (C(Q, s) is evaluated on the device)", who);
+        throw MraError(MRA_ERR_INVALID, m);
+    }
+    if (pl->reduce_level >= 0 || pl->comm || pl->n_ranks > 1) {
+        snprintf(m, sizeof m, "%s: sharded plans cannot predict at new sites", who);
+        throw MraError(MRA_ERR_INVALID, m);
+    }
     if (n < 0) throw MraError(MRA_ERR_INVALID, "n_sites < 0");
-    if (nc < 0) throw MraError(MRA_ERR_INVALID, "n_cols < 0");
-    if (!Y && nc != 1) throw MraError(MRA_ERR_INVALID, "Y is NULL (the plan's own observations): n_cols must be 1");
+}
+
+static std::vector<int> sites_check_sites(const mra_plan* pl, const char* who, int64_t n, const double* sites, const int32_t* leaf) {
     if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
     if (n > 0 && (!sites || !leaf)) throw MraError(MRA_ERR_INVALID, "sites or leaf is NULL");
-    const long P = pl->P;
     const int d = pl->d;
     std::vector<int> lslot((size_t)n);
     for (int64_t i = 0; i < n; ++i) {
         char m[128];
         if (leaf[i] < 0 || leaf[i] >= pl->n_nodes || !pl->leaf[leaf[i]] || pl->leaf_slot[leaf[i]] < 0) {
-            snprintf(m, sizeof m, "mra_predict_sites: leaf[%lld] = %d is not a leaf node", (long long)i, (int)leaf[i]);
+            snprintf(m, sizeof m, "%s: leaf[%lld] = %d is not a leaf node", who, (long long)i, (int)leaf[i]);
             throw MraError(MRA_ERR_INVALID, m);
         }
         lslot[(size_t)i] = pl->leaf_slot[leaf[i]];
         for (int e = 0; e < d; ++e)
             if (!std::isfinite(sites[i * d + e])) {
-                snprintf(m, sizeof m, "mra_predict_sites: site %lld has a non-finite coordinate", (long long)i);
+                snprintf(m, sizeof m, "%s: site %lld has a non-finite coordinate", who, (long long)i);
                 throw MraError(MRA_ERR_INVALID, m);
             }
     }
+    return lslot;
+}
+
+// The state both calls run on: the site descriptors, and W at every row and the factors - the pass mra_solve runs and keeps (solve_all).
+static void sites_ensure_state(mra_plan* pl) {
+    HIP_TRY(mraSetDevice(pl->device));
+    mra_sites_build(pl);
+    mra_plan::Solver& S = pl->slv;
+    if (!S.valid) {
+        KeepResults keep(pl, nullptr, S.msave.p, S.vsave.p);
+        sampler_prior(pl);
+        HIP_TRY(hipStreamSynchronize(pl->stream));
+        HIP_TRY(hipGetLastError());
+        S.valid = true;
+    } else {
+        for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = mra_plan::KStat();      // the kernel statistics describe this call: no pass ran
+    }
+}
+
+// the coordinates of tiles [t0, t0 + nt) for the device: padding columns repeat their tile's first site
+static void sites_gather(const std::vector<int64_t>& slot, long t0, long nt, int d, const double* sites, double* xs) {
+    for (long e = 0; e < nt * 16; ++e) {
+        const int64_t src = slot[(size_t)(t0 * 16 + e)];
+        const int64_t i = src >= 0 ? src : slot[(size_t)((t0 * 16 + e) & ~(int64_t)15)];
+        for (int k = 0; k < d; ++k) xs[(size_t)e * d + k] = sites[i * d + k];
+    }
+}
+
+static void predict_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const double* sites, const int32_t* leaf, int64_t nc,
+                              const double* Y, double* mean, double* var) {
+    sites_check_plan(pl, "mra_predict_sites", flags != 0, n);
+    if (nc < 0) throw MraError(MRA_ERR_INVALID, "n_cols < 0");
+    if (!Y && nc != 1) throw MraError(MRA_ERR_INVALID, "Y is NULL (the plan's own observations): n_cols must be 1");
+    const std::vector<int> lslot = sites_check_sites(pl, "mra_predict_sites", n, sites, leaf);
+    const long P = pl->P;
+    const int d = pl->d;
     const bool want_mean = mean != nullptr && nc > 0;
     if (Y)
         for (int64_t k = 0; k < nc; ++k)
@@ -2640,20 +2684,9 @@ static void predict_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const dou
                     throw MraError(MRA_ERR_INVALID, m);
                 }
     if (n == 0) return;
-    HIP_TRY(mraSetDevice(pl->device));
-    mra_sites_build(pl);
+    sites_ensure_state(pl);
     mra_plan::Solver& S = pl->slv;
     mra_plan::Sites& T = pl->sit;
-    if (!S.valid) {
-        // W at every row and the factors: the pass mra_solve runs and keeps (solve_all)
-        KeepResults keep(pl, nullptr, S.msave.p, S.vsave.p);
-        sampler_prior(pl);
-        HIP_TRY(hipStreamSynchronize(pl->stream));
-        HIP_TRY(hipGetLastError());
-        S.valid = true;
-    } else {
-        for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = mra_plan::KStat();      // the kernel statistics describe this call: no pass ran
-    }
     for (double& v : T.ms) v = 0.0;
     std::vector<int64_t> slot;
     std::vector<int> tile_leaf;
@@ -2675,11 +2708,7 @@ static void predict_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const dou
         }
         for (long t0 = 0; t0 < n_tiles; t0 += per_chunk) {
             const long nt = std::min(per_chunk, n_tiles - t0);
-            for (long e = 0; e < nt * 16; ++e) {
-                const int64_t src = slot[(size_t)(t0 * 16 + e)];
-                const int64_t i = src >= 0 ? src : slot[(size_t)((t0 * 16 + e) & ~(int64_t)15)];      // padding: the tile's first site
-                for (int k = 0; k < d; ++k) xs[(size_t)e * d + k] = sites[i * d + k];
-            }
+            sites_gather(slot, t0, nt, d, sites, xs.data());
             mra_sites_timed(pl, 5, [&] {
                 HIP_TRY(hipMemcpyAsync(T.xs.p, xs.data(), (size_t)nt * 16 * d * sizeof(double), hipMemcpyHostToDevice, pl->stream));
                 HIP_TRY(hipMemcpyAsync(T.tleaf.p, tile_leaf.data() + t0, (size_t)nt * sizeof(int), hipMemcpyHostToDevice, pl->stream));
@@ -2703,6 +2732,71 @@ static void predict_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const dou
                 for (int c = 0; c < ncb; ++c) mean[(cb * 16 + c) * n + i] = mh[(size_t)c * nt * 16 + e];
             }
         }
+    }
+}
+
+// ---- joint covariance of new sites (mra_sites_cov) ---------------------------------------------------------------
+// Every tile's a (prior) or a, t, b (posterior) stays on the device for the call; the matrix comes back in row panels of whole tiles,
+// each block at or after the diagonal computed once and written to both triangles here: `out` is symmetric by construction.
+static void sites_cov_all(mra_plan* pl, uint32_t flags, int64_t n, const double* sites, const int32_t* leaf, double* out) {
+    sites_check_plan(pl, "mra_sites_cov", (flags & ~MRA_COV_POSTERIOR) != 0, n);
+    if (n > MRA_SITES_COV_MAX) {
+        char m[200];
+        snprintf(m, sizeof m, "mra_sites_cov: n_sites = %lld is above MRA_SITES_COV_MAX = %d (the result is a dense matrix, 2 GiB at the cap)", (long long)n, MRA_SITES_COV_MAX);
+        throw MraError(MRA_ERR_INVALID, m);
+    }
+    if (n > 0 && !out) throw MraError(MRA_ERR_INVALID, "out is NULL");
+    const std::vector<int> lslot = sites_check_sites(pl, "mra_sites_cov", n, sites, leaf);
+    if (n == 0) return;
+    const bool post = (flags & MRA_COV_POSTERIOR) != 0;
+    const int d = pl->d;
+    sites_ensure_state(pl);
+    mra_plan::Sites& T = pl->sit;
+    for (double& v : T.cov_ms) v = 0.0;
+    struct Sink { mra_plan::Sites& T; ~Sink() { T.ms_sink = nullptr; } } sink{T};
+    T.ms_sink = T.cov_ms;
+    std::vector<int64_t> slot;
+    std::vector<int> tile_leaf;
+    sites_tiles(lslot, n, pl->leaf_nodes.size(), slot, tile_leaf);
+    const long n_tiles = (long)tile_leaf.size(), ld = n_tiles * 16;
+    const size_t budget = T.chunk_bytes ? T.chunk_bytes : SITES_CHUNK_BYTES;
+    const long rows = std::min<long>(std::min<long>(n_tiles, 65535), std::max<long>(1, (long)(budget / ((size_t)16 * ld * sizeof(double)))));
+    mra_sites_reserve(pl, n_tiles);
+    if (T.gram.n < (size_t)rows * 16 * ld) T.gram.alloc((size_t)rows * 16 * ld);
+    {
+        std::vector<double> xs((size_t)n_tiles * 16 * d);
+        sites_gather(slot, 0, n_tiles, d, sites, xs.data());
+        mra_sites_timed(pl, 4, [&] {
+            HIP_TRY(hipMemcpyAsync(T.xs.p, xs.data(), xs.size() * sizeof(double), hipMemcpyHostToDevice, pl->stream));
+            HIP_TRY(hipMemcpyAsync(T.tleaf.p, tile_leaf.data(), (size_t)n_tiles * sizeof(int), hipMemcpyHostToDevice, pl->stream));
+        });
+        mra_sites_basis(pl, n_tiles);
+        if (post) mra_sites_var(pl, n_tiles);
+        HIP_TRY(hipStreamSynchronize(pl->stream));       // xs is read by the copy until here
+        HIP_TRY(hipGetLastError());
+    }
+    std::vector<double> panel((size_t)rows * 16 * ld);
+    for (long t0 = 0; t0 < n_tiles; t0 += rows) {
+        const long nr = std::min(rows, n_tiles - t0);
+        mra_sites_gram(pl, n_tiles, t0, nr, post);
+        // the panel from its first diagonal block on: what lies before it in the first row is never written
+        const size_t first = (size_t)t0 * 16, count = (size_t)nr * 16 * ld - first;
+        mra_sites_timed(pl, 5, [&] { HIP_TRY(hipMemcpyAsync(panel.data() + first, T.gram.p + first, count * sizeof(double), hipMemcpyDeviceToHost, pl->stream)); });
+        HIP_TRY(hipStreamSynchronize(pl->stream));
+        HIP_TRY(hipGetLastError());
+        for (long I = t0; I < t0 + nr; ++I)
+            for (long J = I; J < n_tiles; ++J)
+                for (int a = 0; a < 16; ++a) {
+                    const int64_t u = slot[(size_t)(I * 16 + a)];
+                    if (u < 0) continue;
+                    const double* row = panel.data() + ((size_t)(I - t0) * 16 + a) * ld + J * 16;
+                    for (int b = (I == J ? a : 0); b < 16; ++b) {
+                        const int64_t w = slot[(size_t)(J * 16 + b)];
+                        if (w < 0) continue;
+                        out[u * n + w] = row[b];
+                        out[w * n + u] = row[b];
+                    }
+                }
     }
 }
 
@@ -3227,6 +3321,10 @@ int mra_predict_sites(mra_plan* pl, uint32_t flags, int64_t n_sites, const doubl
     return guarded(pl, [&] { require(pl, "mra_predict_sites: plan is NULL"); predict_sites_all(pl, flags, n_sites, sites, leaf, n_cols, Y, mean, var); return MRA_OK; });
 }
 
+int mra_sites_cov(mra_plan* pl, uint32_t flags, int64_t n_sites, const double* sites, const int32_t* leaf, double* out) {
+    return guarded(pl, [&] { require(pl, "mra_sites_cov: plan is NULL"); sites_cov_all(pl, flags, n_sites, sites, leaf, out); return MRA_OK; });
+}
+
 int mra_get_likelihood(mra_plan* pl, double* d, double* u) {
     return guarded(pl, [&] {
         require(pl && d && u, "mra_get_likelihood: plan, d or u is NULL");
@@ -3248,6 +3346,11 @@ int mra_get_buffer(mra_plan* pl, int what, double* out, int64_t cap, int64_t* n_
         if (what == 7) {             // host record: stream ms of the last mra_predict_sites by kernel (MRA_OPT_KERNEL_TIMING)
             *n_avail = 7;
             if (out && cap > 0) memcpy(out, pl->sit.ms, (size_t)std::min<int64_t>(cap, 7) * sizeof(double));
+            return MRA_OK;
+        }
+        if (what == 8) {             // host record: stream ms of the last mra_sites_cov
+            *n_avail = 6;
+            if (out && cap > 0) memcpy(out, pl->sit.cov_ms, (size_t)std::min<int64_t>(cap, 6) * sizeof(double));
             return MRA_OK;
         }
         if (what == 0) { src = pl->W.p; n = (int64_t)pl->W.n; }

@@ -546,6 +546,10 @@ struct mra_plan {
         DevVec<int> tleaf;                        // [tile] leaf slot
         DevVec<double> xs, a, b, t, var, mean;    // [tile]: 16 x d sites; a, b (anc_max x16); t (nop_max x16); 16 variances; 16 x 16 means
         double ms[7] = {0, 0, 0, 0, 0, 0, 0};     // stream ms of the last call with MRA_OPT_KERNEL_TIMING: basis, leaf, chain, mean, the solver's sweeps, uploads, downloads
+        // mra_sites_cov: every tile's a, b, t stay in the buffers above for the call; one row panel of the result
+        DevVec<double> gram;                      // rows of whole tiles x the padded site count
+        double cov_ms[6] = {0, 0, 0, 0, 0, 0};    // stream ms of the last mra_sites_cov: basis, leaf, chain, gram, uploads, downloads
+        double* ms_sink = nullptr;                // where mra_sites_timed adds (nullptr: ms); mra_sites_cov points it at cov_ms for its call
     } sit;
     // comm
     void* rccl = nullptr;
@@ -613,5 +617,8 @@ void mra_sites_reserve(mra_plan* pl, long n_tiles);
 void mra_sites_basis(mra_plan* pl, long n_tiles);
 void mra_sites_var(mra_plan* pl, long n_tiles);
 void mra_sites_mean(mra_plan* pl, long n_tiles, int n_cols);
-// with MRA_OPT_KERNEL_TIMING: `work` between two events on pl->stream, the time added to sit.ms[which] (one synchronisation each: a measuring mode)
+// mra_sites_cov: one row panel of the joint covariance of the n_tiles resident tiles - tile rows [tile0, tile0 + n_rows) against every
+// tile at or after them, into sit.gram with row stride n_tiles * 16 (blocks before the diagonal are not written: the caller mirrors)
+void mra_sites_gram(mra_plan* pl, long n_tiles, long tile0, long n_rows, bool posterior);
+// with MRA_OPT_KERNEL_TIMING: `work` between two events on pl->stream, the time added to sit.ms[which] (sit.ms_sink[which] when set; one synchronisation each: a measuring mode)
 void mra_sites_timed(mra_plan* pl, int which, const std::function<void()>& work);

@@ -1,7 +1,8 @@
 // mra_site_kernels.h - kernels of mra_predict_sites: the posterior mean and variance of the MRA process at
 // locations that are not rows of the tree, from the state one likelihood pass leaves in the plan (the prior W and factors L_j, the
 // leaves' L_c and Ut, the fronts' Lt and Zt) and, for the mean, the beta / q of the solver's backward sweep.  Included by
-// mra_launch_sites.hip only, so that the other translation units keep their object code.
+// mra_launch_sites.hip only, so that the other translation units keep their object code.  The last kernel, k_site_gram, is
+// mra_sites_cov's (section 13): the joint covariance of the sites of two tiles from the arrays the first three leave behind.
 //
 // A tile is 16 sites of ONE leaf; the 16 sites are the 16 columns (N) of v_mfma_f64_16x16x4_f64 throughout, so a^T, t, b and p_j are
 // k x16 arrays in the solver's "x16" layout: element (row, site) at row * 16 + site.  Every column of an MFMA product, of a
@@ -266,4 +267,88 @@ __global__ __launch_bounds__(64, 4) void k_site_mean(const SolveLeaf* __restrict
 #pragma unroll
         for (int j = 0; j < 4; ++j) gst(out + (long)r * ldo + tile * 16 + q + 4 * j, acc[j]);
     }
+}
+
+// ---- 5. gram: the joint covariance of the sites of two tiles (mra_sites_cov) -------------------------------------
+// One wave per 16 x 16 block (tile I = blockIdx.y + tile0, tile J = blockIdx.x; blocks with J < I are the caller's to mirror and are
+// not computed): the 16 sites of I are M, those of J are N.  W's columns run deepest block first and end at Ka for every leaf, so the
+// blocks of the two leaves' common ancestors are the trailing w = cw + anc rows (of the lowest common ancestor's SiteNode) of both
+// tiles' arrays, and the cross term is one product over a contiguous K range, ascending:
+//     prior      different leaves: sum_k a_I[k] a_J[k]           same leaf: C(s_u, s_w)
+//     posterior  different leaves: sum_k p_I[k] p_J[k]           same leaf: sum_k p p - sum_k a a (anc) - sum_k t t (nop) + C(s_u, s_w)
+// (p: k_site_chain's b).  Both operands of a k-step are rows of x16 arrays, so element (u, w) is the same chain of fused
+// multiply-adds whichever of the two sites is on the M side: the block of (J, I) is the transpose of this one to the bit.
+// Lane (r, q) leaves elements (q + 4 j, r); out has row stride ldo, row 0 = site 0 of tile tile0.
+template <int DIM, int MODE, bool POST>
+__global__ __launch_bounds__(64, 4) void k_site_gram(const SolveLeaf* __restrict__ lv, const SiteNode* __restrict__ nodes,
+                                                     const int* __restrict__ chain_ptr, const int* __restrict__ chain,
+                                                     const int* __restrict__ tile_leaf, const double* __restrict__ xs, KernelParams kp,
+                                                     const double* __restrict__ a_buf, const double* __restrict__ b_buf, long a_stride,
+                                                     const double* __restrict__ t_buf, long t_stride, long tile0,
+                                                     double* __restrict__ out, long ldo) {
+    const long I = tile0 + blockIdx.y, J = blockIdx.x;
+    if (J < I) return;
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    const int tI = tile_leaf[I], tJ = tile_leaf[J];
+    const int ancI = lv[tI].anc, ancJ = lv[tJ].anc;
+    const bool same = tI == tJ;
+    d4 acc = {0, 0, 0, 0};
+    if (POST || !same) {
+        // the lowest common ancestor: the last node of the common prefix of the two root-first chains
+        const int cI = chain_ptr[tI], cJ = chain_ptr[tJ];
+        const int nc = min(chain_ptr[tI + 1] - cI, chain_ptr[tJ + 1] - cJ);
+        int lca = -1;
+        for (int c = 0; c < nc; ++c) {
+            const int i = chain[cI + c];
+            if (i != chain[cJ + c]) break;
+            lca = i;
+        }
+        int w = 0;
+        if (lca >= 0) { const SiteNode N = nodes[lca]; w = N.cw + N.anc; }
+        const double* xI = (POST ? b_buf : a_buf) + I * a_stride + (long)(ancI - w) * 16;
+        const double* xJ = (POST ? b_buf : a_buf) + J * a_stride + (long)(ancJ - w) * 16;
+        for (int k0 = 0; k0 < w; k0 += 16) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const long k = k0 + q + 4 * s;
+                acc = mfma16(gld(xI + k * 16 + r), gld(xJ + k * 16 + r), acc);
+            }
+        }
+    }
+    if (same) {
+        if (POST) {
+            const double* aI = a_buf + I * a_stride;
+            const double* aJ = a_buf + J * a_stride;
+            for (int k0 = 0; k0 < ancI; k0 += 16) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const long k = k0 + q + 4 * s;
+                    acc = mfma16(-gld(aI + k * 16 + r), gld(aJ + k * 16 + r), acc);
+                }
+            }
+            const int nop = lv[tI].nop;
+            const double* uI = t_buf + I * t_stride;
+            const double* uJ = t_buf + J * t_stride;
+            for (int k0 = 0; k0 < nop; k0 += 16) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const long k = k0 + q + 4 * s;
+                    acc = mfma16(-gld(uI + k * 16 + r), gld(uJ + k * 16 + r), acc);
+                }
+            }
+        }
+        double xw[DIM];
+#pragma unroll
+        for (int e = 0; e < DIM; ++e) xw[e] = gld(xs + (J * 16 + r) * DIM + e);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            double xu[DIM];
+#pragma unroll
+            for (int e = 0; e < DIM; ++e) xu[e] = gld(xs + (I * 16 + q + 4 * j) * DIM + e);
+            acc[j] += site_cov<MODE>(kp, pair_dist2<DIM>(xu, xw, kp.circular));
+        }
+    }
+    double* o = out + (long)blockIdx.y * 16 * ldo + J * 16 + r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) gst(o + (long)(q + 4 * j) * ldo, acc[j]);
 }

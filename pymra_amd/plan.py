@@ -41,6 +41,7 @@ MRA_OPT_SITES_CHUNK_BYTES = 21
 MRA_OPT_LEAF_ORDER = 22
 MRA_SAMPLE_CONDITIONAL = 1
 MRA_COV_POSTERIOR = 1
+MRA_SITES_COV_MAX = 16384
 MRA_BLOCK_W_ROWS, MRA_BLOCK_LPRIOR, MRA_BLOCK_FRONT, MRA_BLOCK_LEAF = 0, 1, 2, 3
 
 # mra_get_route (include/mra_hip.h): the fields in the order the library writes them, and the members of the four enums by value
@@ -63,7 +64,7 @@ ERR_NAMES = {-1: "MRA_ERR_INVALID", -2: "MRA_ERR_HIP", -3: "MRA_ERR_NOT_SPD", -4
 EXPORTS = [
     "mra_device_count", "mra_release_cached_memory", "mra_plan_create", "mra_plan_destroy", "mra_plan_set_locs", "mra_plan_set_obs",
     "mra_plan_set_kernel", "mra_plan_set_locs_rows", "mra_plan_set_obs_rows", "mra_get_predict_rows", "mra_get_predict_rows_sd", "mra_eval_kernel", "mra_plan_set_cov_block", "mra_run", "mra_get_likelihood", "mra_get_predict",
-    "mra_sample_slots", "mra_sample", "mra_solve", "mra_cov_apply", "mra_predict_sites", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
+    "mra_sample_slots", "mra_sample", "mra_solve", "mra_cov_apply", "mra_predict_sites", "mra_sites_cov", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
     "mra_get_kernel_stats", "mra_get_kernel_work", "mra_get_route", "mra_device_synchronize", "mra_plan_info", "mra_comm_unique_id", "mra_comm_init",
     "mra_plan_set_reduce_level", "mra_reduce_size", "mra_reduce_export", "mra_reduce_import",
     "mra_run_resume", "mra_last_error", "mra_version",
@@ -128,6 +129,7 @@ def load_library():
         "mra_solve": (C.c_int, [vp, u32, i64, vp, vp, vp]),
         "mra_cov_apply": (C.c_int, [vp, u32, i64, vp, vp, vp]),
         "mra_predict_sites": (C.c_int, [vp, u32, i64, vp, vp, i64, vp, vp, vp]),
+        "mra_sites_cov": (C.c_int, [vp, u32, i64, vp, vp, vp]),
         "mra_get_buffer": (C.c_int, [vp, C.c_int, vp, i64, C.POINTER(i64)]),
         "mra_get_node_block": (C.c_int, [vp, i32, C.c_int, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
         "mra_get_timers": (C.c_int, [vp, vp, C.c_int]),
@@ -406,6 +408,25 @@ class HipPlan:
         var = np.empty(n) if want_var else None
         self._check(self.lib.mra_predict_sites(self._h, 0, n, _ptr(X), _ptr(lf), c, Yp, _ptr(mean), None if var is None else _ptr(var)))
         return mean, var
+
+    def sites_cov(self, sites, leaf, posterior=False):
+        """The joint covariance of the latent MRA process at locations that need not be rows of the tree (include/mra_hip.h,
+        mra_sites_cov).  sites: (n, d) (or (n,) in 1-D); leaf: (n,) NODE indices of the leaf each site is assigned to.  -> (n, n): the
+        prior covariance, or with posterior=True the posterior one on the plan's observation mask; symmetric to the bit, no entry
+        clamped, its posterior diagonal predict_sites' var up to rounding.  The factorisation is shared with solve() / cov_apply() /
+        predict_sites() and kept between calls; y, the options and likelihood() / predict() are unchanged."""
+        X = np.ascontiguousarray(sites, dtype=np.float64)
+        if X.ndim == 1 and self.d == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise ValueError("sites must have shape (n, d) = (n, %d)" % self.d)
+        n = X.shape[0]
+        lf = np.ascontiguousarray(leaf, dtype=np.int32)
+        if lf.shape != (n,):
+            raise ValueError("leaf must have shape (n,) = (%d,)" % n)
+        out = np.empty((n, n)) if n <= MRA_SITES_COV_MAX else None       # above the cap the library refuses before it reads `out`
+        self._check(self.lib.mra_sites_cov(self._h, MRA_COV_POSTERIOR if posterior else 0, n, _ptr(X), _ptr(lf), None if out is None else _ptr(out)))
+        return out
 
     def buffer(self, what):
         n = C.c_int64()

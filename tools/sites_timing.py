@@ -7,6 +7,15 @@ locs + sites with NaN observations at the sites, end to end (construction, likel
 Prints one JSON line per configuration (profiles/sites_timing.txt).
 
     python tools/sites_timing.py [c3]
+
+`cov` mode: mra_sites_cov at the same configuration, 4096 and 16384 sites of the shifted grid taken in WHOLE leaves - one family of four
+siblings, a cousin family and leaves spread over the rest of the domain, so that tile pairs with every depth of lowest common ancestor
+occur -, prior and posterior, medians of three with the factors valid; with MRA_OPT_KERNEL_TIMING the stream times of
+mra_get_buffer(what = 8).  Against it the only way to the same numbers without the entry point: a second MRATree on locs + sites and
+covariance(rows) in n / 16 sweeps - a DIFFERENT model (other knots), timed at 4096 sites.  One JSON line per site count
+(profiles/sitecov_timing.txt).
+
+    python tools/sites_timing.py cov [c3]
 """
 import json
 import os
@@ -84,5 +93,69 @@ def main(cfgs):
         pl.close()
 
 
+COV_PARTS = ("basis", "leaf", "chain", "gram", "upload", "download")
+
+
+def whole_leaves(t, leaf, count):
+    """indices of `count` sites in whole leaves: the first family, a cousin family, then leaves spread evenly over the leaf list"""
+    leaves = np.nonzero(np.asarray(t.node_leaf, dtype=bool))[0]
+    par = np.asarray(t.node_parent)
+    fam = [j for j in leaves if par[j] == par[leaves[0]]]
+    cousins = [j for j in leaves if par[j] != par[leaves[0]] and par[par[j]] == par[par[leaves[0]]]]
+    cousins = [j for j in cousins if par[j] == par[cousins[0]]]
+    per = max(1, int(np.bincount(leaf).max()))
+    rest = [j for j in leaves[np.linspace(0, len(leaves) - 1, max(2, 2 * count // per)).astype(int)] if j not in fam and j not in cousins]
+    idx = np.concatenate([np.nonzero(leaf == j)[0] for j in fam + cousins + rest])
+    assert len(idx) >= count
+    return idx[:count]
+
+
+def main_cov(cfgs):
+    import make_golden as mg
+    for cfg in cfgs:
+        c = mg.CASES[cfg]
+        locs, y_obs, _ = mg.make_inputs(c)
+        cov = lambda a, b=np.array([]): mt.Matern32(a, b, l=c["l"], sig=c["sig"])      # noqa: E731
+        tree = MRATree(locs, c["r"], cov, y_obs, c["R"], M=c["M"], J=c["J"], verbose=False)
+        pl = tree.plan
+        n = int(round(np.sqrt(len(locs))))
+        grid = locs + 0.5 * (locs.max(0) - locs.min(0)) / (n - 1)
+        leaf_all = tree.locate(grid)
+        info = pl.info()
+        for count in (4096, 16384):
+            idx = whole_leaves(tree.topology, leaf_all, count)
+            sites, leaf = np.ascontiguousarray(grid[idx]), np.ascontiguousarray(leaf_all[idx])
+            n_tiles = int(sum((k + 15) // 16 for k in np.bincount(leaf)))
+            out = {"config": cfg, "P": info["P"], "Ka": info["Ka"], "n_sites": count, "n_leaves": int(len(np.unique(leaf))), "n_tiles": n_tiles,
+                   "result_bytes": 8 * count * count}
+            for kind, post in (("prior", False), ("posterior", True)):
+                first_ms, _ = timed(lambda: pl.sites_cov(sites, leaf, posterior=post))      # the very first call factorises and allocates
+                wall = sorted(timed(lambda: pl.sites_cov(sites, leaf, posterior=post))[0] for _ in range(3))[1]
+                pl.set_option(P.MRA_OPT_KERNEL_TIMING, 1)
+                parts = []
+                for _ in range(3):
+                    S = pl.sites_cov(sites, leaf, posterior=post)
+                    parts.append(pl.buffer(8))
+                pl.set_option(P.MRA_OPT_KERNEL_TIMING, 0)
+                parts = np.median(np.array(parts), axis=0)
+                out[kind] = {"first_call_ms": round(first_ms, 1), "wall_ms": round(wall, 1),
+                             "stream_ms": {k: round(float(v), 2) for k, v in zip(COV_PARTS, parts)},
+                             "symmetric": bool(np.array_equal(S, S.T)), "finite": bool(np.isfinite(S).all())}
+            if count == 4096:
+                both = np.vstack([locs, sites])
+                y_both = np.vstack([np.asarray(y_obs, float).reshape(-1, 1), np.full((count, 1), np.nan)])
+                rows = np.arange(len(locs), len(both))
+
+                def rebuild():
+                    t2 = MRATree(both, c["r"], cov, y_both, c["R"], M=c["M"], J=c["J"], verbose=False)
+                    return np.vstack([t2.covariance(rows[k:k + 16], distr="posterior")[rows] for k in range(0, count, 16)])
+                out["second_tree_covariance_in_sweeps_ms"] = round(timed(rebuild)[0], 1)
+            print(json.dumps(out), flush=True)
+        pl.close()
+
+
 if __name__ == "__main__":
-    main(sys.argv[1:] or ["c3"])
+    if sys.argv[1:2] == ["cov"]:
+        main_cov(sys.argv[2:] or ["c3"])
+    else:
+        main(sys.argv[1:] or ["c3"])
