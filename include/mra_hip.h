@@ -376,6 +376,11 @@ int mra_get_timers(mra_plan *plan, double *out_ms, int capacity);
                                       serial launches.  For A/B runs: 2: (a) alone, 3: (b) alone, 4: 1 with the residual product's problems in
                                       that order as well.  (a) is read when a pass opens; (b) when the leaf lists are built: it takes effect
                                       with the next mra_plan_set_obs.  mra_get_route does not report it */
+#define MRA_OPT_PARENT_PAIR    23  /* which kernel factorises the fronts of the leaves' parents (k_parent_front's step of a pass); the results do
+                                      not depend on it, bit for bit.  1 (default): k_parent_front_pair - four-wave workgroups, two to a CU - where
+                                      the fronts fit it (at most 92 tiles, 64 KB of LDS) and the level has more fronts than the device has CUs;
+                                      0: always k_parent_front (eight waves, one workgroup per CU); 2: the pair kernel wherever the fronts fit
+                                      (tests, A/B runs).  Read at every launch.  mra_get_route does not report it */
 int mra_plan_set_option(mra_plan *plan, int option, int64_t value);
 /* current value of an option (so that a caller can change one temporarily and put it back) */
 int mra_plan_get_option(mra_plan *plan, int option, int64_t *value);

@@ -4305,6 +4305,226 @@ __global__ __launch_bounds__(512, 1) void k_parent_front(const FrontProb* __rest
     if (threadIdx.x == 64 * (nwave - 1)) dnode[pp->node] = 2.0 * logacc;
 }
 
+// ------------------------------------------------------------------------------------------------
+//  k_parent_front in four-wave workgroups that fit a CU two at a time: the same front, the same arithmetic per tile (k order,
+//  panel factorisation, Schur expression), so the same bits.  Two independent fronts share a CU and drift out of phase - one's
+//  diagonal blocks, stores and prologue run under the other's K loop, which k_parent_front (one workgroup per CU) leaves idle.
+//  What makes two fit:
+//    LDS <= 64 KB, one region used twice: in the K loop two UNPADDED stages of nf x 16 doubles and the flat table of 16-column
+//        steps (built once: no segment walk in the loop); after the loop the panel tiles and inverted diagonal blocks in k_front's
+//        PANEL layout over the same bytes.  The barrier that ends the last step separates the two uses.
+//    no staging registers: the stage is filled by LDS DMA as in k_syrk_dma (lane-linear, so the 16-byte chunks of a row are
+//        XOR-swizzled on the source address; a fragment is read as two 16-byte halves).  The swizzle is not k_syrk_dma's: chunk c of
+//        row p sits at position c ^ pp_swz(p), which makes every ds_read_b128 of the K loop conflict-free in the lane groups the LDS
+//        serves such a read in ({0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}, the same + 32), for rows r and for rows pi16(r);
+//        c ^ (p & 7) is 3-way conflicted there.  The next stage is requested BEFORE the fragment reads of the current one.
+//    fixed slots: accumulator slots n < NPAN of every wave hold panel tiles (column block < cwt), which are dead once they are in
+//        LDS; the other slots hold the trailing tiles (and what panel tiles did not fit the first 4 NPAN places), the only
+//        accumulators alive across the diagonal-block routine.
+//  pp_pair_nacc (host) says which instantiation takes a front, if any.
+// ------------------------------------------------------------------------------------------------
+#define PP_MAXPC 7        /* 1 KB pieces (8 staged rows) a wave requests per step: fronts of at most 14 row tiles */
+struct PpStep { const double* A; int lda; int k0; };
+__host__ __device__ constexpr int pp_npan(int nacc) { return (nacc + 3) / 4; }
+// XOR mask of the chunk positions of row p of a stage (a function of p & 15: of the row in its 1 KB piece and of the piece's parity)
+__device__ __forceinline__ int pp_swz(int p) { return ((p >> 1) & 1) ^ (((p >> 2) & 1) * 4) ^ (((p >> 3) & 1) * 6); }
+// tile of slot n of wave w.  Slots n < NPAN: panel tile p = w + 4 n; the others, u = w + 4 (n - NPAN): the panel tiles from 4 NPAN on,
+// then the trailing tiles row-major over their lower triangle.  Panel tiles are numbered as they lie in LDS (k_front's PANEL layout).
+template <int NPAN>
+__device__ __forceinline__ bool pp_tile(int n, int w, int nt, int cwt, int& i, int& j) {
+    const int npanel = cwt * nt - cwt * (cwt - 1) / 2;
+    const int nover = max(0, npanel - 4 * NPAN);
+    int p;
+    if (n < NPAN) p = w + 4 * n;
+    else {
+        const int u = w + 4 * (n - NPAN);
+        if (u >= nover) {
+            const int t = u - nover, ntr = nt - cwt;
+            int ii = 0;
+            while ((ii + 1) * (ii + 2) / 2 <= t) ++ii;
+            i = cwt + ii; j = cwt + t - ii * (ii + 1) / 2;
+            return t < ntr * (ntr + 1) / 2;
+        }
+        p = 4 * NPAN + u;
+    }
+    int jj = 0, base = 0;
+    while (jj + 1 < cwt && p >= base + (nt - jj)) { base += nt - jj; ++jj; }
+    i = jj + (p - base); j = jj;
+    return p < npanel;
+}
+
+template <int NACC>
+__global__ __launch_bounds__(256, 2) void k_parent_front_pair(const FrontProb* __restrict__ probs, const GemmSeg* __restrict__ segs_all,
+                                                               double* __restrict__ dnode, int* __restrict__ err) {
+    constexpr int NPAN = pp_npan(NACC);
+    extern __shared__ __attribute__((aligned(16))) double lds[];
+    const FrontProb* __restrict__ pp = probs + blockIdx.x;
+    double* const F = pp->F;
+    const int nf = pp->nf, cwt = pp->cwt, nt = nf >> 4;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    const int prow = pi16(r);
+    const d4 zero = {0, 0, 0, 0};
+    const int npanel = cwt * nt - cwt * (cwt - 1) / 2;
+    // LDS, K loop: two stages of nf rows x 128 bytes, then the step table.  Afterwards: panel tiles + inverted diagonal blocks
+    char* const stage = (char*)lds;
+    const int stage_bytes = nf * 128;
+    PpStep* const tab = (PpStep*)(stage + 2 * stage_bytes);
+    double* const pan = lds;
+    double* const inv = pan + (long)npanel * FT_SZ;
+    auto tix = [&](int i, int j) -> int { return j * nt - j * (j - 1) / 2 + (i - j); };
+    // ---- the step table: one entry per 16 columns of every child, in segment order
+    const GemmSeg* segs = segs_all + pp->child0;
+    const int nseg = pp->nchild;
+    int nk = 0;
+    for (int sg = 0; sg < nseg; ++sg) nk += (segs[sg].K + 15) >> 4;
+    for (int sg = threadIdx.x; sg < nseg; sg += 256) {
+        int start = 0;
+        for (int s = 0; s < sg; ++s) start += (segs[s].K + 15) >> 4;
+        const int cnt = (segs[sg].K + 15) >> 4;
+        const double* A = segs[sg].A;
+        const int lda = (int)segs[sg].lda;
+        for (int t = 0; t < cnt; ++t) tab[start + t] = PpStep{A, lda, 16 * t};
+    }
+    // this wave's tiles: byte offsets of the two operands' row blocks in a stage (A side: column block j, low half; B side: row block
+    // i, high half).  An empty slot (one of 92 at C3) runs tile (0, 0) once more and is never stored: no branch in the K loop
+    int code[NACC];
+#pragma unroll
+    for (int n = 0; n < NACC; ++n) {
+        int i, j;
+        const bool ok = pp_tile<NPAN>(n, wave, nt, cwt, i, j);
+        code[n] = ok ? ((j * 2048) | ((i * 2048) << 16)) : 0;
+    }
+    d4 acc[NACC];
+#pragma unroll
+    for (int n = 0; n < NACC; ++n) acc[n] = zero;
+    // staging role: wave w requests the 1 KB pieces w, w + 4, ... (8 rows each; all of one parity); lane l: row l >> 3 of the piece,
+    // position l & 7, which holds chunk (l & 7) ^ pp_swz(row)
+    const int npieces = nf >> 3;
+    const int schunk = ((lane & 7) ^ pp_swz((wave & 1) * 8 + (lane >> 3))) * 2;
+    auto request = [&](int step, int buf) {
+        const PpStep e = tab[step];
+        const double* src = e.A + (long)(wave * 8 + (lane >> 3)) * e.lda + e.k0 + schunk;
+        const long pstep = 32L * e.lda;
+        char* const db = stage + buf * stage_bytes + wave * 1024;
+#pragma unroll
+        for (int i = 0; i < PP_MAXPC; ++i)
+            if (wave + 4 * i < npieces) gld_lds16(src + i * pstep, db + i * 4096);
+    };
+    // fragment of lane (r, q): row prow (A side) or r (B side) of a 16-row block, doubles 4 q .. 4 q + 3 = chunks 2 q, 2 q + 1
+    const int fa0 = prow * 128 + (((2 * q) ^ pp_swz(prow)) << 4), fa1 = prow * 128 + (((2 * q + 1) ^ pp_swz(prow)) << 4);
+    const int fb0 = r * 128 + (((2 * q) ^ pp_swz(r)) << 4), fb1 = r * 128 + (((2 * q + 1) ^ pp_swz(r)) << 4);
+    __syncthreads();
+    if (nk > 0) request(0, 0);
+    mra_wait_vm0();
+    __syncthreads();
+    for (int ks = 0; ks < nk; ++ks) {
+        const int cur = ks & 1;
+        if (ks + 1 < nk) request(ks + 1, cur ^ 1);           // (that stage was read in step ks - 1: everybody has passed a barrier since)
+        const char* st = stage + cur * stage_bytes;
+        // the fragments of tile n + 1 are requested before the MFMAs of tile n
+        d2 a0 = *(const d2*)(st + (code[0] & 0xffff) + fa0), a1 = *(const d2*)(st + (code[0] & 0xffff) + fa1);
+        d2 b0 = *(const d2*)(st + (code[0] >> 16) + fb0), b1 = *(const d2*)(st + (code[0] >> 16) + fb1);
+#pragma unroll
+        for (int n = 0; n < NACC; ++n) {
+            d2 na0 = a0, na1 = a1, nb0 = b0, nb1 = b1;
+            if (n + 1 < NACC) {
+                const char* sa = st + (code[n + 1] & 0xffff);
+                const char* sb = st + (code[n + 1] >> 16);
+                na0 = *(const d2*)(sa + fa0); na1 = *(const d2*)(sa + fa1);
+                nb0 = *(const d2*)(sb + fb0); nb1 = *(const d2*)(sb + fb1);
+            }
+            __builtin_amdgcn_sched_barrier(0);            // (left to itself the scheduler sinks the reads below the MFMAs and waits for them at once)
+            acc[n] = mfma16(a0[0], b0[0], acc[n]);
+            acc[n] = mfma16(a0[1], b0[1], acc[n]);
+            acc[n] = mfma16(a1[0], b1[0], acc[n]);
+            acc[n] = mfma16(a1[1], b1[1], acc[n]);
+            __builtin_amdgcn_sched_barrier(0);
+            a0 = na0; a1 = na1; b0 = nb0; b1 = nb1;
+        }
+        mra_wait_vm0();
+        __syncthreads();
+    }
+    // ---- identity on the own block, panel tiles to LDS (over the stages: the barrier above was the last read of them).  The tile
+    // coordinates are worked out again from an opaque copy of the wave number, here and before the Schur update (see k_parent_front):
+    // kept from the top of the kernel they would sit in registers through the K loop and the factorisation
+    int wv = wave;
+    asm volatile("" : "+s"(wv));
+#pragma unroll
+    for (int n = 0; n < NACC; ++n) {
+        int i, j;
+        if (pp_tile<NPAN>(n, wv, nt, cwt, i, j) && j < cwt) {
+            d4 v = acc[n];
+            if (i == j) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) v[e] += (r == 4 * q + e) ? 1.0 : 0.0;
+            }
+            *(d4*)(pan + (long)tix(i, j) * FT_SZ + r * FT_LD + 4 * q) = v;
+        }
+    }
+    __syncthreads();
+    // ---- partial Cholesky of the panel (k_front, phase B; k_parent_front's with four waves)
+    double logacc = 0.0;
+    const int nwave = 4;
+    for (int jb = 0; jb < cwt; ++jb) {
+        if (jb > 0) {
+            for (int ib = jb + wave; ib < nt; ib += nwave) {
+                d4 u0 = zero, u1 = zero;
+                for (int kb = 0; kb < jb; ++kb) {
+                    const d4 a = *(const d4*)(pan + (long)tix(jb, kb) * FT_SZ + prow * FT_LD + 4 * q);
+                    const d4 b = *(const d4*)(pan + (long)tix(ib, kb) * FT_SZ + r * FT_LD + 4 * q);
+                    u0 = mfma16(a[0], b[0], u0); u1 = mfma16(a[1], b[1], u1);
+                    u0 = mfma16(a[2], b[2], u0); u1 = mfma16(a[3], b[3], u1);
+                }
+                d4* tp = (d4*)(pan + (long)tix(ib, jb) * FT_SZ + r * FT_LD + 4 * q);
+                *tp = *tp - (u0 + u1);
+            }
+            __syncthreads();
+        }
+        if (wave == nwave - 1) {
+            double* dt = pan + (long)tix(jb, jb) * FT_SZ;
+            bool bad = false;
+            logacc += chol16_ldl(dt, FT_LD, dt, FT_LD, inv + jb * FT_SZ, FT_LD, lane, bad, nullptr, 0, pp->invd + (long)jb * 256);
+            if (bad && lane == 0) atomicMax(err, pp->node + 1);
+        }
+        __syncthreads();
+        {
+            const d4 ia = *(const d4*)(inv + jb * FT_SZ + prow * FT_LD + 4 * q);
+            for (int ib = jb + 1 + wave; ib < nt; ib += nwave) {
+                d4* tp = (d4*)(pan + (long)tix(ib, jb) * FT_SZ + r * FT_LD + 4 * q);
+                const d4 b = *tp;
+                d4 x0 = mfma16(ia[0], b[0], zero), x1 = mfma16(ia[1], b[1], zero);
+                x0 = mfma16(ia[2], b[2], x0); x1 = mfma16(ia[3], b[3], x1);
+                *tp = x0 + x1;
+            }
+        }
+        __syncthreads();
+    }
+    // ---- Schur update of the trailing tiles in registers, then the panel columns, Lt and Zt, from LDS
+    asm volatile("" : "+s"(wv));
+#pragma unroll
+    for (int n = NPAN; n < NACC; ++n) {
+        int i, j;
+        if (pp_tile<NPAN>(n, wv, nt, cwt, i, j) && j >= cwt) {
+            d4 u0 = zero, u1 = zero;
+            for (int kb = 0; kb < cwt; ++kb) {
+                const d4 a = *(const d4*)(pan + (long)tix(j, kb) * FT_SZ + prow * FT_LD + 4 * q);
+                const d4 b = *(const d4*)(pan + (long)tix(i, kb) * FT_SZ + r * FT_LD + 4 * q);
+                u0 = mfma16(a[0], b[0], u0); u1 = mfma16(a[1], b[1], u1);
+                u0 = mfma16(a[2], b[2], u0); u1 = mfma16(a[3], b[3], u1);
+            }
+            gst4(F + (long)(i * 16 + r) * nf + j * 16 + 4 * q, acc[n] - (u0 + u1));
+        }
+    }
+    for (int t = wave; t < npanel; t += nwave) {
+        int j = 0, base = 0;
+        while (j + 1 < cwt && t >= base + (nt - j)) { base += nt - j; ++j; }
+        const int i = j + (t - base);
+        gst4(F + (long)(i * 16 + r) * nf + j * 16 + 4 * q, *(const d4*)(pan + (long)t * FT_SZ + r * FT_LD + 4 * q));
+    }
+    if (threadIdx.x == 64 * (nwave - 1)) dnode[pp->node] = 2.0 * logacc;
+}
+
 // mean = -W[:, Ka]
 #ifndef MRA_KERNELS_TEMPLATES_ONLY      /* non-template kernel: defined once, in the translation unit of mra_plan.hip */
 __global__ void k_extract_mean(const double* __restrict__ W, long ldw, int Ka, double* __restrict__ mean, long P) {

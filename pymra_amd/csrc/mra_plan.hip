@@ -999,8 +999,29 @@ static void build_grand_syrk(mra_plan* pl, const LeafDescs& d) {
     }
 }
 
+// LDS of k_parent_front_pair: the larger of its two uses of one region - two unpadded stages and the table of max_steps 16-column
+// steps in the K loop, the panel tiles and inverted diagonal blocks afterwards
+static size_t parent_pair_lds(long nf, long cwt, long max_steps) {
+    const long nt = nf / 16, npanel = cwt * nt - cwt * (cwt - 1) / 2;
+    const size_t kloop = (size_t)(2 * nf * 128) + (size_t)max_steps * sizeof(PpStep);
+    const size_t fact = (size_t)(npanel + cwt) * FT_SZ * sizeof(double);
+    return std::max(kloop, fact);
+}
+
+// the instantiation of k_parent_front_pair whose slots hold a front of nt row tiles with cwt panel columns (pp_tile's deal: 4 NPAN
+// places for panel tiles, the other slots for the rest), 0 if neither does
+static int parent_pair_nacc(long nt, long cwt) {
+    const long ntiles = nt * (nt + 1) / 2, npanel = cwt * nt - cwt * (cwt - 1) / 2;
+    if (nt > 2 * PP_MAXPC || ntiles > 92) return 0;
+    for (int nacc : {17, 23}) {
+        const long npan = pp_npan(nacc);
+        if (ntiles - std::min(npanel, 4 * npan) <= 4 * (nacc - npan)) return nacc;
+    }
+    return 0;
+}
+
 // the parents' fronts for k_parent_front (SYRK + factorisation in one launch), where the front fits its registers and LDS
-static void build_parent_front(mra_plan* pl, const SegRanges& where) {
+static void build_parent_front(mra_plan* pl, const std::vector<GemmSeg>& segs, const SegRanges& where) {
     const LevelData& lv = pl->lev[pl->NL - 1];
     std::vector<FrontProb> fr(lv.nodes.size());
     for (size_t sidx = 0; sidx < lv.nodes.size(); ++sidx)
@@ -1011,6 +1032,18 @@ static void build_parent_front(mra_plan* pl, const SegRanges& where) {
     pl->parent_front_lds = (size_t)(2 * lv.nf * PF_LD + (npanel + lv.cwt) * FT_SZ) * sizeof(double);
     pl->parent_front_nacc = ntiles <= 16 ? 2 : (ntiles <= 32 ? 4 : (ntiles <= 64 ? 8 : (ntiles <= 96 ? 12 : 0)));
     if (pl->parent_front_lds > 160 * 1024 || lv.panel_only) pl->parent_front_nacc = 0;
+    // parent_pair_ok: the same fronts in four-wave workgroups, two to a CU (at most 64 KB of LDS each)
+    long max_steps = 0, all_steps = 0;
+    for (size_t sidx = 0; sidx < lv.nodes.size(); ++sidx) {
+        long steps = 0;
+        for (int k = 0; k < where[sidx].second; ++k) steps += (segs[where[sidx].first + k].K + 15) / 16;
+        max_steps = std::max(max_steps, steps);
+        all_steps += steps;
+    }
+    pl->parent_pair_lds = parent_pair_lds(lv.nf, lv.cwt, max_steps);
+    pl->parent_pair_nacc = (lv.panel_only || pl->parent_pair_lds > 64 * 1024) ? 0 : parent_pair_nacc(nt, lv.cwt);
+    // its empty accumulator slots run one more tile per K step (four 16 x 16 x 4 MFMAs): executed, not algorithmic, work
+    pl->parent_pair_idle_exec = !pl->parent_pair_nacc ? 0.0 : (double)all_steps * (double)(4 * pl->parent_pair_nacc - ntiles) * 4.0 * (2.0 * 16 * 16 * 4);
 }
 
 // shape-regular trees: the segmented products of the leaves' parents and, with lowrank_parent, of the grandparents
@@ -1025,7 +1058,7 @@ static void build_parent_products(mra_plan* pl, const LeafDescs& d) {
         build_parent_panels(pl, d, segs, where);
         build_grand_syrk(pl, d);
     }
-    build_parent_front(pl, where);
+    build_parent_front(pl, segs, where);
 }
 
 // leaves with more than 192 observations: right-looking blocked factorisation, 64 columns per step (mra_plan::gBigPanel)
@@ -1321,10 +1354,17 @@ static void launch_level_row_solve(mra_plan* pl, int m, const Trsm2Prob* probs2,
                        lv.ntiles, pl->W.p, (long)pl->ldw, lv.c0, var);
 }
 
-// k_parent_front<nacc>, one workgroup per front (nacc: 2, 4, 8, anything else 12)
-static void launch_parent_front(mra_plan* pl, int nacc, size_t nprob, size_t lds, const FrontProb* probs) {
-    ensure_big_lds(pl, {(const void*)k_parent_front<2>, (const void*)k_parent_front<4>, (const void*)k_parent_front<8>, (const void*)k_parent_front<12>});
+// k_parent_front<nacc>, one workgroup per front (nacc: 2, 4, 8, anything else 12); pair: k_parent_front_pair<17|23> on the same
+// descriptors, 256 threads, lds = parent_pair_lds
+static void launch_parent_front(mra_plan* pl, int nacc, size_t nprob, size_t lds, const FrontProb* probs, bool pair = false) {
+    ensure_big_lds(pl, {(const void*)k_parent_front<2>, (const void*)k_parent_front<4>, (const void*)k_parent_front<8>, (const void*)k_parent_front<12>,
+                        (const void*)k_parent_front_pair<17>, (const void*)k_parent_front_pair<23>});
     const dim3 grid((unsigned)nprob);
+    if (pair) {
+        if (nacc == 17) hipLaunchKernelGGL(k_parent_front_pair<17>, grid, dim3(256), lds, pl->stream, probs, pl->parentSegs.p, pl->dnode.p, pl->errflag.p);
+        else hipLaunchKernelGGL(k_parent_front_pair<23>, grid, dim3(256), lds, pl->stream, probs, pl->parentSegs.p, pl->dnode.p, pl->errflag.p);
+        return;
+    }
     switch (nacc) {
         case 2: hipLaunchKernelGGL(k_parent_front<2>, grid, dim3(512), lds, pl->stream, probs, pl->parentSegs.p, pl->dnode.p, pl->errflag.p); break;
         case 4: hipLaunchKernelGGL(k_parent_front<4>, grid, dim3(512), lds, pl->stream, probs, pl->parentSegs.p, pl->dnode.p, pl->errflag.p); break;
@@ -2071,7 +2111,14 @@ static void form_front(mra_plan* pl, const PassRoute& r, FrontStep step, int m) 
         case FrontStep::Resumed: case FrontStep::Children: return;
         case FrontStep::ParentFront: {
             KTimer kt(pl, KF_LEAF_SYRK, (pl->fl_leaf_syrk + lv.fl_fchol + lv.fl_schur).with_bytes(pl->by_leaf_ut + 8.0 * lv.nodes.size() * (0.5 * lv.nf * (lv.nf + 1))));
-            launch_parent_front(pl, pl->parent_front_nacc, lv.nodes.size(), pl->parent_front_lds, pl->gParentFront.p);
+            // MRA_OPT_PARENT_PAIR (pass state, not part of the route): two four-wave workgroups per CU where a CU gets more than one
+            // front; with at most one front per CU (an 8-way shard) a front finishes sooner on eight waves
+            const bool pair = pl->parent_pair_nacc > 0 && (pl->use_parent_pair == 2 || (pl->use_parent_pair == 1 && lv.nodes.size() > (size_t)pl->n_cu));
+            if (pair) {
+                pl->kstat[KF_LEAF_SYRK].flops_exec += pl->parent_pair_idle_exec;
+                launch_parent_front(pl, pl->parent_pair_nacc, lv.nodes.size(), pl->parent_pair_lds, pl->gParentFront.p, true);
+            }
+            else launch_parent_front(pl, pl->parent_front_nacc, lv.nodes.size(), pl->parent_front_lds, pl->gParentFront.p);
             return;
         }
         case FrontStep::ParentPanels: run_parent_panels(pl, m); return;
@@ -3443,6 +3490,10 @@ int mra_plan_set_option(mra_plan* pl, int option, int64_t value) {
             pl->leaf_longest_first = value == 1 || value == 3 || value == 4;
             pl->resid_longest_first = value == 4;
             return MRA_OK;
+        case MRA_OPT_PARENT_PAIR:
+            if (value < 0 || value > 2) throw MraError(MRA_ERR_INVALID, "option 23: 0, 1 (where a CU gets more than one front) or 2 (wherever the fronts fit)");
+            pl->use_parent_pair = (int)value;
+            return MRA_OK;
         case MRA_OPT_SAMPLE_GRAM_BYTES:
             if (value < 0) throw MraError(MRA_ERR_INVALID, "option 19: the Gram batch budget is a byte count >= 0");
             if ((size_t)value != pl->smp.gram_bytes) { pl->smp.gram_bytes = (size_t)value; pl->smp.built = false; }
@@ -3497,6 +3548,7 @@ int mra_plan_get_option(mra_plan* pl, int option, int64_t* value) {
             case MRA_OPT_LIK_ROWS: *value = pl->use_lik_rows; break;
             case MRA_OPT_UT_GATHER: *value = pl->ut_gather; break;
             case MRA_OPT_LEAF_ORDER: *value = pl->resid_longest_first ? 4 : pl->use_leaf_fork ? (pl->leaf_longest_first ? 1 : 2) : (pl->leaf_longest_first ? 3 : 0); break;
+            case MRA_OPT_PARENT_PAIR: *value = pl->use_parent_pair; break;
             case MRA_OPT_CASCADE_GROUP: *value = pl->cascade_group_siblings; break;
             case MRA_OPT_SAMPLE_GRAM_BYTES: *value = (int64_t)pl->smp.gram_bytes; break;
             case MRA_OPT_SAMPLE_SOLVE: *value = pl->slv.in_sampler; break;
@@ -3518,7 +3570,8 @@ int mra_plan_prepare(mra_plan* pl, int64_t* n_kernels) {
         struct Guard { mra_plan* p; ~Guard() { p->prepare_only = false; } } guard{pl};
         launch_trsm2(pl, nullptr, 0, 1, 0, 1);
         ensure_big_lds(pl, {(const void*)k_front<true>, (const void*)k_front<false>, (const void*)k_parent_front<2>, (const void*)k_parent_front<4>,
-                            (const void*)k_parent_front<8>, (const void*)k_parent_front<12>, (const void*)k_leaf_solve_update<8, 13, true>});
+                            (const void*)k_parent_front<8>, (const void*)k_parent_front<12>, (const void*)k_parent_front_pair<17>,
+                            (const void*)k_parent_front_pair<23>, (const void*)k_leaf_solve_update<8, 13, true>});
         if (pl->regular) {
             CascadeArgs ar{};
             ar.n_wg = 1;

@@ -396,6 +396,10 @@ struct mra_plan {
     DevVec<FrontProb> gParentFront;      // the same nodes for k_parent_front (SYRK + factorisation in one launch)
     int parent_front_nacc = 0;           // 0: not available (front too large for the register-resident SYRK)
     size_t parent_front_lds = 0;
+    int parent_pair_nacc = 0;            // k_parent_front_pair<17|23> can take these fronts (parent_pair_ok); 0: it cannot
+    size_t parent_pair_lds = 0;
+    double parent_pair_idle_exec = 0;    // flops its empty accumulator slots execute in a pass (they repeat tile (0, 0))
+    int use_parent_pair = 1;             // MRA_OPT_PARENT_PAIR, read at launch: 0 never, 1 where a CU gets more than one front, 2 wherever it can
     bool parent_syrk = false;
     // Large fronts at the level of the leaves' parents (config 5: 528^2 per node, 36 GB in all) are never formed: F = I + U U^T with
     // U = the children's Ut blocks side by side has rank <= sum(n_obs), so only its panel columns [F_oo ; F_ao] = U U_o^T (+ I) are

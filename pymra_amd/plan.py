@@ -39,6 +39,7 @@ MRA_OPT_SAMPLE_GRAM_BYTES = 19
 MRA_OPT_SAMPLE_SOLVE = 20
 MRA_OPT_SITES_CHUNK_BYTES = 21
 MRA_OPT_LEAF_ORDER = 22
+MRA_OPT_PARENT_PAIR = 23
 MRA_SAMPLE_CONDITIONAL = 1
 MRA_COV_POSTERIOR = 1
 MRA_SITES_COV_MAX = 16384
