@@ -236,11 +236,49 @@ int mra_predict_sites(mra_plan *plan, uint32_t flags, int64_t n_sites, const dou
 #define MRA_SITES_COV_MAX 16384
 int mra_sites_cov(mra_plan *plan, uint32_t flags, int64_t n_sites, const double *sites, const int32_t *leaf, double *out);
 
+/* Draws of the latent MRA process at locations that are not rows of the tree (no counterpart in the reference, which can only draw at
+ * the rows of `locs`, pyMRA/MRATools.py:395-484).  Section 13's two covariance formulas are a factorisation
+ * Sigma = F F^T with a sparse, tree-shaped F: with a_j(s), t(s), p_j(s) of section 12 and l(u) the leaf of site u,
+ *     prior      x(s_u) =              sum over the chain j of l(u) of a_j(u)^T xi_j + (L_l zeta_l)_u,   L_l L_l^T = C(S_l, S_l) - a^T a
+ *     posterior  x(s_u) = mean(s_u) +  sum over the chain j of l(u) of p_j(u)^T xi_j + (L_l zeta_l)_u,   L_l L_l^T = C - a^T a - t^T t
+ * xi_j ~ N(0, I) one vector per non-leaf node, shared by every site below it; zeta_l ~ N(0, I) one entry per site of leaf l; S_l the
+ * call's sites assigned to leaf l, in the caller's order (the order of the Cholesky); mean = mra_predict_sites' for the plan's own
+ * observations.  The posterior draw needs no kriging pass: one basis / leaf / chain pass, one Cholesky per leaf that has sites, two
+ * MFMA products per block of 16 samples.
+ *     sites, leaf as for mra_predict_sites; flags: 0 (prior) or MRA_COV_POSTERIOR (on the mask of the last set_obs, mean included)
+ *     out   (n_samples x n_sites, row-major, the caller's site order)
+ *     latent slots [0, Kn): the non-leaf nodes, numbered exactly as mra_sample numbers them (node order, cw[level] each, knot-column
+ *           order; phantom columns are inert: a and p are 0 there); [Kn, Kn + n_sites): the leaf term of site u, by the caller's index.
+ *           mra_sample_sites_slots gives Kn + n_sites.
+ *     z     NULL: Philox exactly as mra_sample draws (counter (slot, sample0 + s), key seed); else n_samples x n_slots, row-major
+ * Samples go in blocks of 16 (the N of v_mfma_f64_16x16x4_f64).  Exact duplicates (same leaf, equal coordinates) are collapsed on the
+ * host to their first occurrence: they receive its draw bit for bit, do not count towards MRA_SAMPLE_SITES_LEAF_MAX, and their own
+ * leaf slots are not read.  A site with G_uu <= 2^-40 C(s_u, s_u) - it lies on a knot of an ancestor, its leaf term is structurally
+ * zero - is inert: its row and column of G_l become the identity and its zeta is not used.
+ * The coarse term and the mean of a site are a pure function of (site, leaf, plan state, seed, sample); the leaf term depends on the
+ * call's sites in that leaf and their order and on nothing else in the call: the bits of out do not depend on
+ * MRA_OPT_SITES_CHUNK_BYTES (which bounds a batch of whole leaves: work arrays + blocks, at least one leaf) nor on which other leaves
+ * have sites.  Near-duplicate sites that make a pivot <= 0 give MRA_ERR_NOT_SPD naming the leaf; no jitter is added.
+ * The state is mra_predict_sites': the first call (and the first after mra_run, mra_run_resume, mra_sample or any set_*) runs one
+ * likelihood pass with W at every row; later calls - and calls after an mra_solve, mra_cov_apply, mra_predict_sites or mra_sites_cov -
+ * launch no factorisation.  Afterwards y, every option and what mra_get_likelihood / mra_get_predict return are as the caller left them.
+ * MRA_ERR_STATE before set_locs / set_obs / set_kernel; MRA_ERR_INVALID for unknown flags, MRA_KERNEL_HOST plans, sharded plans,
+ * n_sites < 0, n_samples < 0, sample0 < 0 or a sample number past 2^63 - 1, a NULL out when there is something to write, a NULL sites
+ * or leaf with n_sites > 0, a leaf entry that is out of range or not a leaf node, a non-finite site coordinate and a leaf that receives
+ * more than MRA_SAMPLE_SITES_LEAF_MAX distinct sites (all checked on the host before anything is launched or allocated).
+ * n_sites == 0 or n_samples == 0 returns MRA_OK.  Blocking. */
+#define MRA_SAMPLE_SITES_LEAF_MAX 4096   /* distinct sites one leaf may receive in a call: its block is dense, 128 MiB at the cap */
+int mra_sample_sites_slots(mra_plan *plan, int64_t n_sites, int64_t *n_slots);       /* Kn + n_sites */
+int mra_sample_sites(mra_plan *plan, uint32_t flags, int64_t n_sites, const double *sites, const int32_t *leaf,
+                     int64_t n_samples, uint64_t seed, int64_t sample0, const double *z, double *out);
+
 /* Diagnostics for tests (the reference exposes these as attributes of Node objects):
  * what = 0: whitened basis W (P x ldw, row-major) ; 1: per-node log-det terms (n_nodes);
  * 7: stream milliseconds of the last mra_predict_sites, measured while MRA_OPT_KERNEL_TIMING is on (7 values: the basis, leaf, chain
  * and mean kernels, the solver's sweeps, the uploads of sites and the downloads of results);
  * 8: the same for the last mra_sites_cov (6 values: the basis, leaf, chain and gram kernels, the uploads and the downloads);
+ * 9: the same for the last mra_sample_sites (9 values: basis, leaf, chain, leaf Gram, leaf Cholesky, draw, mean with the solver's
+ * sweeps, uploads, downloads);
  * copies min(capacity, available) doubles into out, returns the available count in *n_avail.
  * (W after a likelihood-only run is complete only with MRA_OPT_LIK_ROWS off: by default such a run computes W at the rows a
  * likelihood needs - the observed rows, and the knots on the level-by-level path - and leaves the others as they were.) */

@@ -300,6 +300,36 @@ class MRATree(object):
             x += self.predictAt(X, leaf=leaf)[0]
         return x
 
+    def sampleAt(self, sites, nsim, distr="posterior", seed=None, leaf=None, z=None):
+        """(n, nsim) draws of the latent field at locations that need not be rows of `locs`, at any number of sites: the scalable
+        counterpart of simulateAt (no dense n x n matrix; a leaf may receive up to plan.MRA_SAMPLE_SITES_LEAF_MAX distinct sites).
+        distr="posterior": draws given this tree's observations, predictAt's mean included; distr="prior": mean 0.  Their covariance
+        is covarianceAt(sites, distr, leaf).  seed=None takes a 64-bit seed from NumPy's global RNG, as simulate() does; z: None
+        (Philox draws on the device, a pure function of the seed) or (plan.sample_sites_slots(n), nsim) latent draws - the non-leaf
+        nodes' slots first, shared with simulate(), then one per site.  leaf: None (locate(sites)) or int32[n] leaf node indices.
+        getLikelihood() and predict() are unchanged."""
+        if distr not in ("prior", "posterior"):
+            raise ValueError('distr must be "prior" or "posterior"')
+        if self.kernel is None:
+            raise NotImplementedError("sampleAt needs a device kernel: trees built from an opaque callable or a dense matrix cannot simulate at new sites")
+        X = self._sites(sites)
+        if leaf is None:
+            leaf = self.locate(X)
+        leaf = np.asarray(leaf)
+        if leaf.shape != (len(X),):
+            raise ValueError("leaf must have shape (n,) = (%d,)" % len(X))
+        nsim = int(nsim)
+        if z is not None:
+            z = np.asarray(z, dtype=np.float64)
+            slots = self.plan.sample_sites_slots(len(X))
+            if z.shape != (slots, nsim):
+                raise ValueError("z must have shape (sample_sites_slots(n), nsim) = (%d, %d)" % (slots, nsim))
+            z = np.ascontiguousarray(z.T)
+        elif seed is None:
+            seed = int(np.random.randint(0, 2 ** 63 - 1, dtype=np.int64)) * 2 + int(np.random.randint(0, 2))
+        x = self.plan.sample_sites(X, leaf, nsim, seed=seed or 0, z=z, posterior=(distr == "posterior"))
+        return np.ascontiguousarray(x.T)
+
     def _cov_apply(self, A, distr):
         """Sigma A (or Sigma_post A) for A (N, c) in the caller's row order -> (A at the reported rows else 0 (N, c), out (N, c))."""
         if distr not in ("prior", "posterior"):

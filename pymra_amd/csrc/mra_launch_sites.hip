@@ -1,6 +1,7 @@
 // mra_launch_sites.hip - mra_predict_sites: descriptors, work buffers and the launches of one chunk of site tiles
 // over the state a likelihood pass left in the plan, and the Gram launch of mra_sites_cov (section 13) over the same buffers.  A
-// translation unit of its own: the kernels of the pass keep their object code.
+// translation unit of its own: the kernels of the pass keep their object code.  The inert, leaf Gram, zeta and draw launches of
+// mra_sample_sites (section 14) run over the same buffers, a batch of whole leaves at a time.
 #define MRA_KERNELS_TEMPLATES_ONLY
 #include "mra_site_kernels.h"
 
@@ -138,10 +139,10 @@ void mra_sites_var(mra_plan* pl, long n) {
     });
 }
 
-void mra_sites_mean(mra_plan* pl, long n, int nc) {
+void mra_sites_mean(mra_plan* pl, long n, int nc, int which) {
     check_chunk(pl, n);
     if (nc < 1 || nc > 16) throw MraError(MRA_ERR_STATE, "mra_predict_sites: a column block has 1 to 16 columns");
-    timed(pl, 3, [&] { MRA_SITES_DISPATCH(launch_mean, pl, n, nc); });
+    timed(pl, which, [&] { MRA_SITES_DISPATCH(launch_mean, pl, n, nc); });
 }
 
 void mra_sites_gram(mra_plan* pl, long n, long tile0, long rows, bool posterior) {
@@ -149,4 +150,66 @@ void mra_sites_gram(mra_plan* pl, long n, long tile0, long rows, bool posterior)
     if (tile0 < 0 || rows < 1 || rows > 65535 || tile0 + rows > n || (size_t)rows * 16 * (size_t)n * 16 > pl->sit.gram.n)
         throw MraError(MRA_ERR_STATE, "mra_sites_cov: row panel outside its tiles or larger than its buffer");
     timed(pl, 3, [&] { MRA_SITES_DISPATCH(launch_gram, pl, n, tile0, rows, posterior); });
+}
+
+// ---- mra_sample_sites ------------------------------------------------------------------------------------------
+void mra_sites_draw_reserve(mra_plan* pl, long n, size_t g_doubles, long n_leaves) {
+    mra_plan::Sites& T = pl->sit;
+    mra_sites_reserve(pl, n);
+    if (T.dtile.n < (size_t)n) T.dtile.alloc((size_t)n);
+    if (T.sslot.n < (size_t)n * 16) { T.sslot.alloc((size_t)n * 16); T.live.alloc((size_t)n * 16); }
+    if (T.zl.n < (size_t)n * 256) { T.zl.alloc((size_t)n * 256); T.dout.alloc((size_t)n * 256); }
+    if (T.G.n < g_doubles) T.G.alloc(g_doubles);
+    if (T.invd.n < (size_t)n * 256) T.invd.alloc((size_t)n * 256);
+    if (T.dprob.n < (size_t)n_leaves) { T.dprob.alloc((size_t)n_leaves); T.dn.alloc((size_t)n_leaves); }
+    if (!T.derr.n) T.derr.alloc(1);
+}
+
+template <int DIM, int MODE>
+static void launch_leaf_gram(mra_plan* pl, long n, int nt_max, bool post) {
+    mra_plan::Sites& T = pl->sit;
+    const dim3 grid((unsigned)n, (unsigned)nt_max);
+    const long as = (long)T.anc_max * 16, ts = (long)T.nop_max * 16;
+    if (post) {
+        hipLaunchKernelGGL((k_site_inert<MODE, true>), dim3((unsigned)n), dim3(64), 0, pl->stream, pl->slv.leaves.p, T.tleaf.p, pl->kp, T.a.p, as, T.t.p, ts,
+                           T.sslot.p, T.live.p);
+        hipLaunchKernelGGL((k_site_leaf_gram<DIM, MODE, true>), grid, dim3(64), 0, pl->stream, pl->slv.leaves.p, T.tleaf.p, T.dtile.p, T.xs.p, pl->kp,
+                           T.a.p, as, T.t.p, ts, T.live.p, T.G.p);
+    } else {
+        hipLaunchKernelGGL((k_site_inert<MODE, false>), dim3((unsigned)n), dim3(64), 0, pl->stream, pl->slv.leaves.p, T.tleaf.p, pl->kp, T.a.p, as, T.t.p, ts,
+                           T.sslot.p, T.live.p);
+        hipLaunchKernelGGL((k_site_leaf_gram<DIM, MODE, false>), grid, dim3(64), 0, pl->stream, pl->slv.leaves.p, T.tleaf.p, T.dtile.p, T.xs.p, pl->kp,
+                           T.a.p, as, T.t.p, ts, T.live.p, T.G.p);
+    }
+}
+
+static void check_batch(const mra_plan* pl, long n) {
+    const mra_plan::Sites& T = pl->sit;
+    if (n <= 0 || n > T.cap_tiles || (size_t)n > T.dtile.n || (size_t)n * 16 > T.sslot.n || (size_t)n * 256 > T.zl.n)
+        throw MraError(MRA_ERR_STATE, "mra_sample_sites: batch larger than its work buffers");
+}
+
+void mra_sites_leaf_gram(mra_plan* pl, long n, int nt_max, bool posterior) {
+    check_batch(pl, n);
+    if (nt_max < 1 || nt_max > 65535) throw MraError(MRA_ERR_STATE, "mra_sample_sites: a leaf of the batch has no tile or too many");
+    timed(pl, 3, [&] { MRA_SITES_DISPATCH(launch_leaf_gram, pl, n, nt_max, posterior); });
+}
+
+void mra_sites_zeta(mra_plan* pl, long n, const SampleZ& zs, long n_coarse, bool from_caller) {
+    check_batch(pl, n);
+    mra_plan::Sites& T = pl->sit;
+    if (from_caller && T.zin.n < (size_t)n * 256) throw MraError(MRA_ERR_STATE, "mra_sample_sites: the caller's leaf draws are not staged");
+    timed(pl, 5, [&] {
+        hipLaunchKernelGGL(k_site_zeta, dim3((unsigned)((n * 256 + 255) / 256)), dim3(256), 0, pl->stream, zs, n_coarse, T.sslot.p, T.live.p,
+                           from_caller ? T.zin.p : nullptr, n * 16, T.zl.p);
+    });
+}
+
+void mra_sites_draw(mra_plan* pl, long n, bool posterior) {
+    check_batch(pl, n);
+    mra_plan::Sites& T = pl->sit;
+    timed(pl, 5, [&] {
+        hipLaunchKernelGGL(k_site_draw, dim3((unsigned)n), dim3(64), 0, pl->stream, T.tleaf.p, T.dtile.p, T.dchain_ptr.p, T.dchain.p, posterior ? T.b.p : T.a.p,
+                           (long)T.anc_max * 16, T.zc.p, T.G.p, T.zl.p, posterior ? T.mean.p : nullptr, T.dout.p, n * 16);
+    });
 }

@@ -2318,15 +2318,20 @@ static void run_all(mra_plan* pl, uint32_t flags, bool full_rows = false) {
 static const size_t SAMPLE_GRAM_BUDGET = (size_t)1536 << 20;   // default bytes of leaf Gram blocks + inverted diagonal blocks per batch
 static const size_t SAMPLE_LEAF_GRID = 65535;                  // leaves per launch of the kernels that take the leaf from blockIdx.y
 
+// latent slots of the non-leaf nodes: node order, cw[level] each.  zoff (may be nullptr): per node its first slot (-1: leaf)
+static long coarse_slots(const mra_plan* pl, std::vector<long>* zoff) {
+    long kn = 0;
+    if (zoff) zoff->assign((size_t)pl->n_nodes, -1);
+    for (int i = 0; i < pl->n_nodes; ++i)
+        if (!pl->leaf[i]) { if (zoff) (*zoff)[(size_t)i] = kn; kn += pl->cw[pl->node_level[i]]; }
+    return kn;
+}
+
 static void sampler_build(mra_plan* pl) {
     mra_plan::Sampler& S = pl->smp;
     if (S.built) return;
     const long P = pl->P;
-    S.zoff.assign(pl->n_nodes, -1);
-    long kn = 0;
-    for (int i = 0; i < pl->n_nodes; ++i)
-        if (!pl->leaf[i]) { S.zoff[i] = kn; kn += pl->cw[pl->node_level[i]]; }
-    S.n_coarse = kn;
+    S.n_coarse = coarse_slots(pl, &S.zoff);
     std::vector<unsigned char> is_knot(P, 0), knot(P, 0), rep(P, 0);
     for (int i = 0; i < pl->n_nodes; ++i)
         for (long k = pl->knot_ptr[i]; k < pl->knot_ptr[i + 1]; ++k) {
@@ -2847,6 +2852,209 @@ static void sites_cov_all(mra_plan* pl, uint32_t flags, int64_t n, const double*
     }
 }
 
+// ---- draws at new sites (mra_sample_sites) -----------------------------------------------------------------------
+static void sample_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const double* sites, const int32_t* leaf, int64_t ns_all, uint64_t seed,
+                             int64_t sample0, const double* z, double* out) {
+    sites_check_plan(pl, "mra_sample_sites", (flags & ~MRA_COV_POSTERIOR) != 0, n);
+    if (ns_all < 0) throw MraError(MRA_ERR_INVALID, "n_samples < 0");
+    if (sample0 < 0 || (ns_all > 0 && sample0 > INT64_MAX - (ns_all - 1))) throw MraError(MRA_ERR_INVALID, "sample0 < 0, or a sample number past 2^63 - 1");
+    if (n > 0 && ns_all > 0 && !out) throw MraError(MRA_ERR_INVALID, "out is NULL");
+    const std::vector<int> lslot = sites_check_sites(pl, "mra_sample_sites", n, sites, leaf);
+    const int d = pl->d;
+    const size_t nl = pl->leaf_nodes.size();
+    // exact duplicates (same leaf, equal coordinates) collapse to their first occurrence: first[i] = the caller's index of it
+    std::vector<int64_t> first((size_t)n), distinct;
+    {
+        // a stable counting sort by leaf (as sites_tiles), then each leaf's sites by coordinates: equal sites become neighbours, first index first
+        std::vector<int64_t> order((size_t)n), cnt(nl + 1, 0);
+        for (int64_t i = 0; i < n; ++i) ++cnt[(size_t)lslot[(size_t)i] + 1];
+        for (size_t t = 0; t < nl; ++t) cnt[t + 1] += cnt[t];
+        {
+            std::vector<int64_t> at(cnt.begin(), cnt.end() - 1);
+            for (int64_t i = 0; i < n; ++i) order[(size_t)at[(size_t)lslot[(size_t)i]]++] = i;
+        }
+        auto less = [&](int64_t x, int64_t y) {
+            for (int e = 0; e < d; ++e)
+                if (sites[x * d + e] != sites[y * d + e]) return sites[x * d + e] < sites[y * d + e];
+            return x < y;
+        };
+        for (size_t t = 0; t < nl; ++t) std::sort(order.begin() + cnt[t], order.begin() + cnt[t + 1], less);
+        for (int64_t k = 0; k < n; ++k) {
+            const int64_t i = order[(size_t)k], h = k ? first[(size_t)order[(size_t)(k - 1)]] : -1;
+            bool same = k > 0 && lslot[(size_t)i] == lslot[(size_t)h];
+            for (int e = 0; same && e < d; ++e) same = sites[i * d + e] == sites[h * d + e];
+            first[(size_t)i] = same ? h : i;
+        }
+        std::vector<int64_t> per_leaf(nl, 0);
+        for (int64_t i = 0; i < n; ++i)
+            if (first[(size_t)i] == i) {
+                distinct.push_back(i);
+                if (++per_leaf[(size_t)lslot[(size_t)i]] == (int64_t)MRA_SAMPLE_SITES_LEAF_MAX + 1) {
+                    char m[200];
+                    snprintf(m, sizeof m, "mra_sample_sites: leaf %d receives more than MRA_SAMPLE_SITES_LEAF_MAX = %d distinct sites (its block is dense, 128 MiB at the cap)",
+                             pl->leaf_nodes[(size_t)lslot[(size_t)i]], MRA_SAMPLE_SITES_LEAF_MAX);
+                    throw MraError(MRA_ERR_INVALID, m);
+                }
+            }
+    }
+    if (n == 0 || ns_all == 0) return;
+    const bool post = (flags & MRA_COV_POSTERIOR) != 0;
+    sites_ensure_state(pl);
+    mra_plan::Solver& S = pl->slv;
+    mra_plan::Sites& T = pl->sit;
+    for (double& v : T.draw_ms) v = 0.0;
+    struct Sink { mra_plan::Sites& T; ~Sink() { T.ms_sink = nullptr; } } sink{T};
+    T.ms_sink = T.draw_ms;
+    // the tiles of the distinct sites; slot[] then holds the caller's index of each column
+    const int64_t nd = (int64_t)distinct.size();
+    std::vector<int64_t> slot;
+    std::vector<int> tile_leaf;
+    {
+        std::vector<int> ls((size_t)nd);
+        for (int64_t k = 0; k < nd; ++k) ls[(size_t)k] = lslot[(size_t)distinct[(size_t)k]];
+        sites_tiles(ls, nd, nl, slot, tile_leaf);
+        for (int64_t& v : slot) if (v >= 0) v = distinct[(size_t)v];
+    }
+    const long n_tiles = (long)tile_leaf.size();
+    // a leaf's chain for the coarse term: first row in a / p, first latent slot, width - root first, as mra_sites_build's chain
+    std::vector<long> zoff;
+    const long Kn = coarse_slots(pl, &zoff), n_slots = Kn + n;
+    {
+        std::vector<SiteDrawChain> ch;
+        std::vector<int> ptr(nl + 1, 0);
+        for (size_t t = 0; t < nl; ++t) {
+            const int i = pl->leaf_nodes[t], a0 = pl->asuf[pl->node_level[i]];
+            std::vector<SiteDrawChain> up;
+            for (int p = pl->parent[i]; p >= 0; p = pl->parent[p]) {
+                const int k = pl->node_level[p];
+                if (pl->cw[k]) up.push_back(SiteDrawChain{pl->coff[k] - a0, (int)zoff[(size_t)p], pl->cw[k], 0});
+            }
+            ch.insert(ch.end(), up.rbegin(), up.rend());
+            ptr[t + 1] = (int)ch.size();
+        }
+        if (ch.empty()) ch.push_back(SiteDrawChain{0, 0, 0, 0});
+        T.dchain.upload(ch); T.dchain_ptr.upload(ptr);
+    }
+    // batches of whole leaves: work arrays of the tiles + the leaf's block, its inverted diagonal blocks, its draws and results
+    const size_t budget = T.chunk_bytes ? T.chunk_bytes : SITES_CHUNK_BYTES;
+    const size_t tile_bytes = mra_sites_tile_bytes(pl) + sizeof(SiteDrawTile) + 16 * (sizeof(long) + sizeof(int)) + 3 * 256 * sizeof(double);
+    struct Batch { long t0, nt, n_leaves; size_t g; int nt_max; };
+    std::vector<Batch> bat;
+    {
+        Batch cur{0, 0, 0, 0, 0};
+        size_t bytes = 0;
+        for (long t0 = 0; t0 < n_tiles;) {
+            long t1 = t0;
+            while (t1 < n_tiles && tile_leaf[(size_t)t1] == tile_leaf[(size_t)t0]) ++t1;
+            const long nt = t1 - t0;
+            const size_t g = (size_t)(16 * nt) * (size_t)(16 * nt), need = (size_t)nt * tile_bytes + g * sizeof(double);
+            if (cur.nt && bytes + need > budget) { bat.push_back(cur); cur = Batch{t0, 0, 0, 0, 0}; bytes = 0; }
+            cur.nt += nt; ++cur.n_leaves; cur.g += g; cur.nt_max = std::max(cur.nt_max, (int)nt); bytes += need;
+            t0 = t1;
+        }
+        bat.push_back(cur);
+    }
+    long cap_t = 0, cap_l = 0;
+    size_t cap_g = 0;
+    for (const Batch& b : bat) { cap_t = std::max(cap_t, b.nt); cap_l = std::max(cap_l, b.n_leaves); cap_g = std::max(cap_g, b.g); }
+    mra_sites_draw_reserve(pl, cap_t, cap_g, cap_l);
+    if (T.zc.n < (size_t)std::max<long>(Kn, 1) * 16) T.zc.alloc((size_t)std::max<long>(Kn, 1) * 16);
+    if (z) {
+        if (T.zcin.n < (size_t)std::max<long>(Kn, 1) * 16) T.zcin.alloc((size_t)std::max<long>(Kn, 1) * 16);
+        if (T.zin.n < (size_t)cap_t * 256) T.zin.alloc((size_t)cap_t * 256);
+    }
+    if (post) {
+        // beta (leaves' gb) and q (leaves' uy) of the plan's own observations: the solver's sweeps without its row step, once per call
+        HIP_TRY(hipMemcpyAsync(S.yb.p, pl->y.p, (size_t)pl->P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+        HIP_TRY(hipMemsetAsync(S.yb.p + (size_t)pl->P, 0, (size_t)15 * pl->P * sizeof(double), pl->stream));
+        mra_sites_timed(pl, 6, [&] { mra_solver_block(pl, true, false, false); });
+    }
+    std::vector<double> xs((size_t)cap_t * 16 * d), oh((size_t)cap_t * 256), zch(z ? (size_t)std::max<long>(Kn, 1) * 16 : 0), zlh(z ? (size_t)cap_t * 256 : 0);
+    std::vector<SiteDrawTile> dt((size_t)cap_t);
+    std::vector<PanelProb> pp((size_t)cap_l);
+    std::vector<int> leaf_of_prob((size_t)cap_l);
+    for (const Batch& b : bat) {
+        sites_gather(slot, b.t0, b.nt, d, sites, xs.data());
+        size_t goff = 0;
+        long nlb = 0;
+        for (long t = 0; t < b.nt;) {
+            long t1 = t;
+            while (t1 < b.nt && tile_leaf[(size_t)(b.t0 + t1)] == tile_leaf[(size_t)(b.t0 + t)]) ++t1;
+            const long nt = t1 - t;
+            for (long k = t; k < t1; ++k) dt[(size_t)k] = SiteDrawTile{(long)goff, (int)t, (int)nt};
+            pp[(size_t)nlb] = PanelProb{T.G.p + goff, T.invd.p + (size_t)t * 256, 16 * nt, (int)nt, (int)nt, (int)nlb};
+            leaf_of_prob[(size_t)nlb] = pl->leaf_nodes[(size_t)tile_leaf[(size_t)(b.t0 + t)]];
+            goff += (size_t)(16 * nt) * (size_t)(16 * nt);
+            ++nlb; t = t1;
+        }
+        mra_sites_timed(pl, 7, [&] {
+            HIP_TRY(hipMemcpyAsync(T.xs.p, xs.data(), (size_t)b.nt * 16 * d * sizeof(double), hipMemcpyHostToDevice, pl->stream));
+            HIP_TRY(hipMemcpyAsync(T.tleaf.p, tile_leaf.data() + b.t0, (size_t)b.nt * sizeof(int), hipMemcpyHostToDevice, pl->stream));
+            HIP_TRY(hipMemcpyAsync(T.dtile.p, dt.data(), (size_t)b.nt * sizeof(SiteDrawTile), hipMemcpyHostToDevice, pl->stream));
+            HIP_TRY(hipMemcpyAsync(T.sslot.p, slot.data() + b.t0 * 16, (size_t)b.nt * 16 * sizeof(long), hipMemcpyHostToDevice, pl->stream));
+            HIP_TRY(hipMemcpyAsync(T.dprob.p, pp.data(), (size_t)nlb * sizeof(PanelProb), hipMemcpyHostToDevice, pl->stream));
+        });
+        mra_sites_basis(pl, b.nt);
+        if (post) {
+            mra_sites_var(pl, b.nt);
+            mra_sites_mean(pl, b.nt, 1, 6);
+        }
+        mra_sites_leaf_gram(pl, b.nt, b.nt_max, post);
+        int e = 0;
+        mra_sites_timed(pl, 4, [&] {
+            HIP_TRY(hipMemsetAsync(T.derr.p, 0, sizeof(int), pl->stream));
+            hipLaunchKernelGGL(k_panel_chol, dim3((unsigned)nlb), dim3(256), 0, pl->stream, T.dprob.p, T.dn.p, T.derr.p, 0);
+        });
+        HIP_TRY(hipMemcpyAsync(&e, T.derr.p, sizeof(int), hipMemcpyDeviceToHost, pl->stream));
+        HIP_TRY(hipStreamSynchronize(pl->stream));
+        HIP_TRY(hipGetLastError());
+        if (e) {
+            char m[200];
+            snprintf(m, sizeof m, "mra_sample_sites: leaf %d: the covariance of its sites' leaf terms is not positive definite (Cholesky pivot <= 0 or NaN; near-duplicate sites?)",
+                     leaf_of_prob[(size_t)(e - 1)]);
+            throw MraError(MRA_ERR_NOT_SPD, m);
+        }
+        for (int64_t s0 = 0; s0 < ns_all; s0 += 16) {
+            const int ns = (int)std::min<int64_t>(16, ns_all - s0);
+            SampleZ zs{nullptr, n_slots, (unsigned long long)seed, (long)(sample0 + s0), ns};
+            if (z) {
+                // the block's draws in the layouts the kernels read: the non-leaf slots sample-major (ldz = Kn), the leaf slots [site][16]
+                for (int s = 0; s < ns; ++s) {
+                    const double* zr = z + (s0 + s) * n_slots;
+                    for (long k = 0; k < Kn; ++k) zch[(size_t)s * Kn + k] = zr[k];
+                    for (long u = 0; u < b.nt * 16; ++u) {
+                        const int64_t i = slot[(size_t)(b.t0 * 16 + u)];
+                        zlh[(size_t)u * 16 + s] = i >= 0 ? zr[Kn + i] : 0.0;
+                    }
+                }
+                for (int s = ns; s < 16; ++s)
+                    for (long u = 0; u < b.nt * 16; ++u) zlh[(size_t)u * 16 + s] = 0.0;
+                mra_sites_timed(pl, 7, [&] {
+                    if (Kn) HIP_TRY(hipMemcpyAsync(T.zcin.p, zch.data(), (size_t)ns * Kn * sizeof(double), hipMemcpyHostToDevice, pl->stream));
+                    HIP_TRY(hipMemcpyAsync(T.zin.p, zlh.data(), (size_t)b.nt * 256 * sizeof(double), hipMemcpyHostToDevice, pl->stream));
+                });
+                zs.z = T.zcin.p; zs.ldz = Kn;
+            }
+            // the non-leaf draws of the block, slot-major (k_sample_draw is this translation unit's)
+            if (Kn) mra_sites_timed(pl, 5, [&] { hipLaunchKernelGGL(k_sample_draw, dim3((unsigned)((Kn * 16 + 255) / 256)), dim3(256), 0, pl->stream, zs, Kn, T.zc.p); });
+            mra_sites_zeta(pl, b.nt, zs, Kn, z != nullptr);
+            mra_sites_draw(pl, b.nt, post);
+            mra_sites_timed(pl, 8, [&] { HIP_TRY(hipMemcpyAsync(oh.data(), T.dout.p, (size_t)ns * b.nt * 16 * sizeof(double), hipMemcpyDeviceToHost, pl->stream)); });
+            HIP_TRY(hipStreamSynchronize(pl->stream));
+            HIP_TRY(hipGetLastError());
+            for (int s = 0; s < ns; ++s)
+                for (long u = 0; u < b.nt * 16; ++u) {
+                    const int64_t i = slot[(size_t)(b.t0 * 16 + u)];
+                    if (i >= 0) out[(s0 + s) * n + i] = oh[(size_t)s * b.nt * 16 + u];
+                }
+        }
+    }
+    if (nd < n)
+        for (int64_t s = 0; s < ns_all; ++s)
+            for (int64_t i = 0; i < n; ++i)
+                if (first[(size_t)i] != i) out[s * n + i] = out[s * n + first[(size_t)i]];
+}
+
 // ---- caller-order variants: the permutation work of an end-to-end MRATree(...) call done inside the library -----------------
 // A process-wide pinned staging area (grow-only): gathers land in it, the H2D / D2H copies run at the pinned rate (a pageable
 // 16 MB copy costs ~5 ms, a pinned one ~0.7 ms), and a second plan in the same process does not pay for the allocation again.
@@ -3344,10 +3552,7 @@ int mra_run_resume(mra_plan* pl) {
 int mra_sample_slots(mra_plan* pl, int64_t* n_slots) {
     return guarded(pl, [&] {
         require(pl && n_slots, "mra_sample_slots: plan or n_slots is NULL");
-        long kn = 0;
-        for (int i = 0; i < pl->n_nodes; ++i)
-            if (!pl->leaf[i]) kn += pl->cw[pl->node_level[i]];
-        *n_slots = kn + 2 * pl->P;
+        *n_slots = coarse_slots(pl, nullptr) + 2 * pl->P;
         return MRA_OK;
     });
 }
@@ -3370,6 +3575,24 @@ int mra_predict_sites(mra_plan* pl, uint32_t flags, int64_t n_sites, const doubl
 
 int mra_sites_cov(mra_plan* pl, uint32_t flags, int64_t n_sites, const double* sites, const int32_t* leaf, double* out) {
     return guarded(pl, [&] { require(pl, "mra_sites_cov: plan is NULL"); sites_cov_all(pl, flags, n_sites, sites, leaf, out); return MRA_OK; });
+}
+
+int mra_sample_sites_slots(mra_plan* pl, int64_t n_sites, int64_t* n_slots) {
+    return guarded(pl, [&] {
+        require(pl && n_slots, "mra_sample_sites_slots: plan or n_slots is NULL");
+        if (n_sites < 0) throw MraError(MRA_ERR_INVALID, "n_sites < 0");
+        *n_slots = coarse_slots(pl, nullptr) + n_sites;
+        return MRA_OK;
+    });
+}
+
+int mra_sample_sites(mra_plan* pl, uint32_t flags, int64_t n_sites, const double* sites, const int32_t* leaf, int64_t n_samples, uint64_t seed,
+                     int64_t sample0, const double* z, double* out) {
+    return guarded(pl, [&] {
+        require(pl, "mra_sample_sites: plan is NULL");
+        sample_sites_all(pl, flags, n_sites, sites, leaf, n_samples, seed, sample0, z, out);
+        return MRA_OK;
+    });
 }
 
 int mra_get_likelihood(mra_plan* pl, double* d, double* u) {
@@ -3398,6 +3621,11 @@ int mra_get_buffer(mra_plan* pl, int what, double* out, int64_t cap, int64_t* n_
         if (what == 8) {             // host record: stream ms of the last mra_sites_cov
             *n_avail = 6;
             if (out && cap > 0) memcpy(out, pl->sit.cov_ms, (size_t)std::min<int64_t>(cap, 6) * sizeof(double));
+            return MRA_OK;
+        }
+        if (what == 9) {             // host record: stream ms of the last mra_sample_sites
+            *n_avail = 9;
+            if (out && cap > 0) memcpy(out, pl->sit.draw_ms, (size_t)std::min<int64_t>(cap, 9) * sizeof(double));
             return MRA_OK;
         }
         if (what == 0) { src = pl->W.p; n = (int64_t)pl->W.n; }

@@ -231,6 +231,13 @@ struct SiteNode {               // one non-leaf node, as an ancestor of a site
     int ld, cw, c0, anc;        // c0: first column of the node's own block in W; its ancestors' columns are [c0 + cw, c0 + cw + anc)
 };
 
+// ---- mra_sample_sites: descriptors of the draw kernels (mra_site_kernels.h)
+struct SiteDrawTile {           // one tile of a batch of whole leaves
+    long goff;                  // its leaf's block G_l in the batch's block buffer ((16 nt)^2 doubles, row stride 16 nt)
+    int first, nt;              // the leaf's first tile in the batch and its tile count
+};
+struct SiteDrawChain { int row, zoff, width, pad; };      // one ancestor of a leaf: its first row in a / p, its first latent slot, its width
+
 struct LevelData {
     std::vector<int> nodes;          // non-leaf nodes of this level
     int cw = 0, cwt = 0, c0 = 0, a0 = 0, nf = 0, na = 0;
@@ -554,6 +561,16 @@ struct mra_plan {
         DevVec<double> gram;                      // rows of whole tiles x the padded site count
         double cov_ms[6] = {0, 0, 0, 0, 0, 0};    // stream ms of the last mra_sites_cov: basis, leaf, chain, gram, uploads, downloads
         double* ms_sink = nullptr;                // where mra_sites_timed adds (nullptr: ms); mra_sites_cov points it at cov_ms for its call
+        // mra_sample_sites: one batch of whole leaves at a time - their tiles' a, b, t in the buffers above, their
+        // blocks G_l (factorised in place), and one block of 16 samples
+        DevVec<SiteDrawTile> dtile;               // [tile of the batch]
+        DevVec<SiteDrawChain> dchain;             // a leaf's ancestors, root first: dchain[dchain_ptr[t] .. dchain_ptr[t + 1])
+        DevVec<int> dchain_ptr, live, derr;       // [n_leaves + 1]; [tile][16] 1: the site has a leaf term (not padding, not inert); Cholesky error slot
+        DevVec<long> sslot;                       // [tile][16] the caller's index of the site (-1: padding)
+        DevVec<PanelProb> dprob;                  // [leaf of the batch]
+        DevVec<double> G, invd, dn;               // the batch's blocks; their inverted diagonal blocks; log-determinants (not read)
+        DevVec<double> zc, zcin, zl, zin, dout;   // Kn x16 non-leaf draws (and the caller's, 16 x Kn); [tile][16] x16 leaf draws (and the caller's); 16 x [tile][16] results
+        double draw_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // stream ms of the last mra_sample_sites: basis, leaf, chain, leaf Gram, leaf Cholesky, draw, mean (+ sweeps), uploads, downloads
     } sit;
     // comm
     void* rccl = nullptr;
@@ -620,9 +637,17 @@ size_t mra_sites_tile_bytes(const mra_plan* pl);
 void mra_sites_reserve(mra_plan* pl, long n_tiles);
 void mra_sites_basis(mra_plan* pl, long n_tiles);
 void mra_sites_var(mra_plan* pl, long n_tiles);
-void mra_sites_mean(mra_plan* pl, long n_tiles, int n_cols);
+void mra_sites_mean(mra_plan* pl, long n_tiles, int n_cols, int which = 3);      // which: the timing entry of the launch
 // mra_sites_cov: one row panel of the joint covariance of the n_tiles resident tiles - tile rows [tile0, tile0 + n_rows) against every
 // tile at or after them, into sit.gram with row stride n_tiles * 16 (blocks before the diagonal are not written: the caller mirrors)
 void mra_sites_gram(mra_plan* pl, long n_tiles, long tile0, long n_rows, bool posterior);
+// mra_sample_sites: the kernels of one batch of whole leaves whose n_tiles tiles are resident (sit.dtile, sit.sslot uploaded).
+// mra_sites_leaf_gram: sit.live and the leaves' blocks G_l into sit.G (nt_max: tiles of the batch's largest leaf); mra_sites_zeta: the
+// leaf draws of one block of samples into sit.zl (from sit.zin when from_caller, else Philox at slot n_coarse + the caller's index);
+// mra_sites_draw: coarse term (sit.zc) + leaf term (sit.G factorised, sit.zl) [+ sit.mean] -> sit.dout, 16 x (n_tiles * 16)
+void mra_sites_draw_reserve(mra_plan* pl, long n_tiles, size_t g_doubles, long n_leaves);
+void mra_sites_leaf_gram(mra_plan* pl, long n_tiles, int nt_max, bool posterior);
+void mra_sites_zeta(mra_plan* pl, long n_tiles, const SampleZ& zs, long n_coarse, bool from_caller);
+void mra_sites_draw(mra_plan* pl, long n_tiles, bool posterior);
 // with MRA_OPT_KERNEL_TIMING: `work` between two events on pl->stream, the time added to sit.ms[which] (sit.ms_sink[which] when set; one synchronisation each: a measuring mode)
 void mra_sites_timed(mra_plan* pl, int which, const std::function<void()>& work);

@@ -2,7 +2,8 @@
 // locations that are not rows of the tree, from the state one likelihood pass leaves in the plan (the prior W and factors L_j, the
 // leaves' L_c and Ut, the fronts' Lt and Zt) and, for the mean, the beta / q of the solver's backward sweep.  Included by
 // mra_launch_sites.hip only, so that the other translation units keep their object code.  The last kernel, k_site_gram, is
-// mra_sites_cov's (section 13): the joint covariance of the sites of two tiles from the arrays the first three leave behind.
+// mra_sites_cov's (section 13): the joint covariance of the sites of two tiles from the arrays the first three leave behind.  After it,
+// the kernels of mra_sample_sites (section 14): the inert flags, the leaves' blocks G_l, the staged leaf draws and the draw itself.
 //
 // A tile is 16 sites of ONE leaf; the 16 sites are the 16 columns (N) of v_mfma_f64_16x16x4_f64 throughout, so a^T, t, b and p_j are
 // k x16 arrays in the solver's "x16" layout: element (row, site) at row * 16 + site.  Every column of an MFMA product, of a
@@ -351,4 +352,151 @@ __global__ __launch_bounds__(64, 4) void k_site_gram(const SolveLeaf* __restrict
     double* o = out + (long)blockIdx.y * 16 * ldo + J * 16 + r;
 #pragma unroll
     for (int j = 0; j < 4; ++j) gst(o + (long)(q + 4 * j) * ldo, acc[j]);
+}
+
+// ---- 6. draws at new sites (mra_sample_sites) --------------------------------------------------------------------
+// Section 13's covariance is F F^T with a tree-shaped F: x(s_u) = sum over the chain of X_j(u)^T xi_j + (L_l zeta_l)_u, X = a (prior) or
+// p (posterior: k_site_chain's b), L_l L_l^T = G_l = C(S_l, S_l) - a^T a [- t^T t] over the call's sites S_l of leaf l, in the caller's
+// order.  A batch holds whole leaves; SiteDrawTile gives a tile its leaf's block and its place in it.
+//
+// A site whose leaf term is structurally zero (it lies on an ancestor's knot, so a(s) reproduces C(s, s)) is INERT: G_uu <= 2^-40 C(s, s).
+// Its row and column of G_l become the identity and its zeta is not used, as k_sample_mask does for non-knot rows.  On the CPU twin
+// (g32, c1, kat3, u3; 40 off-row sites and every reported row) the sites on ancestor knots had |G_uu| / C(s, s) <= 4.4e-16, the
+// smallest genuine relative diagonal was 1.4e-8 and the smallest relative Cholesky pivot 1.4e-9 (c1): 2^-40 = 9.1e-13 lies between.
+constexpr double SITE_INERT_REL = 0x1p-40;
+
+// live[site] = 1 when the site is no padding column and not inert: G_uu = C(s, s) - |a|^2 [- |t|^2] in site_colsq's fixed order
+template <int MODE, bool POST>
+__global__ __launch_bounds__(64, 4) void k_site_inert(const SolveLeaf* __restrict__ lv, const int* __restrict__ tile_leaf, KernelParams kp,
+                                                      const double* __restrict__ a_buf, long a_stride, const double* __restrict__ t_buf,
+                                                      long t_stride, const long* __restrict__ sslot, int* __restrict__ live) {
+    const long tile = blockIdx.x;
+    const int t = tile_leaf[tile];
+    const int anc = lv[t].anc, nop = lv[t].nop;
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    const double c = site_cov<MODE>(kp, 0.0);
+    double g = c - site_colsq(a_buf + tile * a_stride, anc, r, q);
+    if (POST) g -= site_colsq(t_buf + tile * t_stride, nop, r, q);
+    if (q == 0) live[tile * 16 + r] = (sslot[tile * 16 + r] >= 0 && g > SITE_INERT_REL * c) ? 1 : 0;
+}
+
+// One wave per 16 x 16 block on or below the diagonal of a leaf's G_l: tile I = blockIdx.x of the batch (M), tile J = the leaf's
+// blockIdx.y-th (N).  k_site_gram's same-leaf operand pattern without p^T p (that part is the coarse term): both operands are rows of
+// x16 arrays, a over anc and t over nop with the A operand negated, C(s_u, s_w) added by the lane that holds the element.  Rows and
+// columns of padding and inert sites become the identity; the diagonal block is written in full.
+template <int DIM, int MODE, bool POST>
+__global__ __launch_bounds__(64, 4) void k_site_leaf_gram(const SolveLeaf* __restrict__ lv, const int* __restrict__ tile_leaf,
+                                                          const SiteDrawTile* __restrict__ dt, const double* __restrict__ xs, KernelParams kp,
+                                                          const double* __restrict__ a_buf, long a_stride, const double* __restrict__ t_buf,
+                                                          long t_stride, const int* __restrict__ live, double* __restrict__ G) {
+    const long I = blockIdx.x;
+    const SiteDrawTile D = dt[I];
+    const int il = (int)(I - D.first), jl = blockIdx.y;
+    if (jl > il) return;
+    const long J = (long)D.first + jl;
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    const int t = tile_leaf[I];
+    const int anc = lv[t].anc;
+    d4 acc = {0, 0, 0, 0};
+    const double* aI = a_buf + I * a_stride;
+    const double* aJ = a_buf + J * a_stride;
+    for (int k0 = 0; k0 < anc; k0 += 16) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const long k = k0 + q + 4 * s;
+            acc = mfma16(-gld(aI + k * 16 + r), gld(aJ + k * 16 + r), acc);
+        }
+    }
+    if (POST) {
+        const int nop = lv[t].nop;
+        const double* uI = t_buf + I * t_stride;
+        const double* uJ = t_buf + J * t_stride;
+        for (int k0 = 0; k0 < nop; k0 += 16) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const long k = k0 + q + 4 * s;
+                acc = mfma16(-gld(uI + k * 16 + r), gld(uJ + k * 16 + r), acc);
+            }
+        }
+    }
+    double xw[DIM];
+#pragma unroll
+    for (int e = 0; e < DIM; ++e) xw[e] = gld(xs + (J * 16 + r) * DIM + e);
+    const int lw = live[J * 16 + r];
+    const long ld = 16L * D.nt;
+    double* o = G + D.goff + (long)il * 16 * ld + jl * 16 + r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double xu[DIM];
+#pragma unroll
+        for (int e = 0; e < DIM; ++e) xu[e] = gld(xs + (I * 16 + q + 4 * j) * DIM + e);
+        const double v = acc[j] + site_cov<MODE>(kp, pair_dist2<DIM>(xu, xw, kp.circular));
+        const bool both = lw && live[I * 16 + q + 4 * j];
+        gst(o + (long)(q + 4 * j) * ld, both ? v : ((il == jl && q + 4 * j == r) ? 1.0 : 0.0));
+    }
+}
+
+// the leaf draws of a block of 16 samples, staged once per leaf: zl[site * 16 + s] = zeta of the site's own slot n_coarse + (the
+// caller's index of the site) - Philox exactly as k_sample_draw, or the caller's value (zin, same layout) - and 0 for padding sites,
+// inert sites and samples past the block's count
+__global__ __launch_bounds__(256) void k_site_zeta(SampleZ zs, long n_coarse, const long* __restrict__ sslot, const int* __restrict__ live,
+                                                   const double* __restrict__ zin, long n_sites, double* __restrict__ zl) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_sites * 16) return;
+    const long u = i >> 4;
+    const int s = (int)(i & 15);
+    double v = 0.0;
+    if (live[u] && s < zs.ns)
+        v = zin ? gld(zin + i) : philox_normal(zs.seed, (unsigned long long)(n_coarse + sslot[u]), (unsigned long long)(zs.sample0 + s));
+    zl[i] = v;
+}
+
+// One wave per (tile, block of 16 samples): the 16 sites are M, the samples N; lane (r, q) leaves (site q + 4 j, sample r).
+//   coarse term  over the leaf's chain: X[rows of block j]^T zc[slots of j] - X in x16 form (the A operand of k-step s is row k of X at
+//                lane r), zc slot-major as k_sample_coarse reads it
+//   leaf term    L_l[tile rows, 0 .. tile end] zeta_l: L_l row-major in the leaf's block, the entries above the diagonal inside the
+//                diagonal tile masked (k_panel_chol leaves that part of the block as it was)
+//   mean         the posterior mean of the plan's own observations (k_site_mean's column 0), added last; nullptr: none
+// out[sample * ldo + tile * 16 + site].
+__global__ __launch_bounds__(64, 4) void k_site_draw(const int* __restrict__ tile_leaf, const SiteDrawTile* __restrict__ dt,
+                                                     const int* __restrict__ dchain_ptr, const SiteDrawChain* __restrict__ dchain,
+                                                     const double* __restrict__ x_buf, long a_stride, const double* __restrict__ zc,
+                                                     const double* __restrict__ G, const double* __restrict__ zl,
+                                                     const double* __restrict__ mean, double* __restrict__ out, long ldo) {
+    const long tile = blockIdx.x;
+    const int t = tile_leaf[tile];
+    const SiteDrawTile D = dt[tile];
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    d4 acc = {0, 0, 0, 0};
+    const double* X = x_buf + tile * a_stride;
+    const int e1 = dchain_ptr[t + 1];
+    for (int e = dchain_ptr[t]; e < e1; ++e) {
+        const SiteDrawChain c = dchain[e];
+        const double* xp = X + (long)c.row * 16 + r;
+        const double* zp = zc + (long)c.zoff * 16 + r;
+        for (int k0 = 0; k0 < c.width; k0 += 16) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const long k = k0 + q + 4 * s;
+                acc = mfma16(gld(xp + k * 16), gld(zp + k * 16), acc);
+            }
+        }
+    }
+    const int il = (int)(tile - D.first);
+    const long ld = 16L * D.nt;
+    const double* Lrow = G + D.goff + ((long)il * 16 + r) * ld;
+    const double* zt = zl + (long)D.first * 256 + r;
+    for (int J = 0; J <= il; ++J) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const int k = q + 4 * s;
+            const double l = gld(Lrow + J * 16 + k);
+            acc = mfma16((J == il && k > r) ? 0.0 : l, gld(zt + (long)(J * 16 + k) * 16), acc);
+        }
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long u = tile * 16 + q + 4 * j;
+        gst(out + (long)r * ldo + u, mean ? acc[j] + gld(mean + u) : acc[j]);
+    }
 }

@@ -43,6 +43,7 @@ MRA_OPT_PARENT_PAIR = 23
 MRA_SAMPLE_CONDITIONAL = 1
 MRA_COV_POSTERIOR = 1
 MRA_SITES_COV_MAX = 16384
+MRA_SAMPLE_SITES_LEAF_MAX = 4096
 MRA_BLOCK_W_ROWS, MRA_BLOCK_LPRIOR, MRA_BLOCK_FRONT, MRA_BLOCK_LEAF = 0, 1, 2, 3
 
 # mra_get_route (include/mra_hip.h): the fields in the order the library writes them, and the members of the four enums by value
@@ -65,7 +66,7 @@ ERR_NAMES = {-1: "MRA_ERR_INVALID", -2: "MRA_ERR_HIP", -3: "MRA_ERR_NOT_SPD", -4
 EXPORTS = [
     "mra_device_count", "mra_release_cached_memory", "mra_plan_create", "mra_plan_destroy", "mra_plan_set_locs", "mra_plan_set_obs",
     "mra_plan_set_kernel", "mra_plan_set_locs_rows", "mra_plan_set_obs_rows", "mra_get_predict_rows", "mra_get_predict_rows_sd", "mra_eval_kernel", "mra_plan_set_cov_block", "mra_run", "mra_get_likelihood", "mra_get_predict",
-    "mra_sample_slots", "mra_sample", "mra_solve", "mra_cov_apply", "mra_predict_sites", "mra_sites_cov", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
+    "mra_sample_slots", "mra_sample", "mra_solve", "mra_cov_apply", "mra_predict_sites", "mra_sites_cov", "mra_sample_sites_slots", "mra_sample_sites", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
     "mra_get_kernel_stats", "mra_get_kernel_work", "mra_get_route", "mra_device_synchronize", "mra_plan_info", "mra_comm_unique_id", "mra_comm_init",
     "mra_plan_set_reduce_level", "mra_reduce_size", "mra_reduce_export", "mra_reduce_import",
     "mra_run_resume", "mra_last_error", "mra_version",
@@ -131,6 +132,8 @@ def load_library():
         "mra_cov_apply": (C.c_int, [vp, u32, i64, vp, vp, vp]),
         "mra_predict_sites": (C.c_int, [vp, u32, i64, vp, vp, i64, vp, vp, vp]),
         "mra_sites_cov": (C.c_int, [vp, u32, i64, vp, vp, vp]),
+        "mra_sample_sites_slots": (C.c_int, [vp, i64, C.POINTER(i64)]),
+        "mra_sample_sites": (C.c_int, [vp, u32, i64, vp, vp, i64, C.c_uint64, i64, vp, vp]),
         "mra_get_buffer": (C.c_int, [vp, C.c_int, vp, i64, C.POINTER(i64)]),
         "mra_get_node_block": (C.c_int, [vp, i32, C.c_int, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
         "mra_get_timers": (C.c_int, [vp, vp, C.c_int]),
@@ -427,6 +430,43 @@ class HipPlan:
             raise ValueError("leaf must have shape (n,) = (%d,)" % n)
         out = np.empty((n, n)) if n <= MRA_SITES_COV_MAX else None       # above the cap the library refuses before it reads `out`
         self._check(self.lib.mra_sites_cov(self._h, MRA_COV_POSTERIOR if posterior else 0, n, _ptr(X), _ptr(lf), None if out is None else _ptr(out)))
+        return out
+
+    def sample_sites_slots(self, n_sites):
+        """Number of latent slots of one draw at n_sites sites (include/mra_hip.h: the non-leaf nodes as sample() numbers them, then
+        one leaf slot per site in the caller's order)."""
+        n = C.c_int64()
+        self._check(self.lib.mra_sample_sites_slots(self._h, int(n_sites), C.byref(n)))
+        return int(n.value)
+
+    def sample_sites(self, sites, leaf, n, seed=0, z=None, posterior=False, sample0=0):
+        """(n, n_sites) draws of the latent MRA process at locations that need not be rows of the tree (include/mra_hip.h,
+        mra_sample_sites): from the prior, or with posterior=True from the posterior on the plan's observation mask, the mean for the
+        plan's own observations included.  sites: (n_sites, d) (or (n_sites,) in 1-D); leaf: (n_sites,) NODE indices of the leaf each
+        site is assigned to.  z: None = Philox draws on the device, a pure function of (seed, slot, sample0 + s); else an
+        (n, sample_sites_slots(n_sites)) array of latent draws.  The factorisation is shared with solve() / cov_apply() /
+        predict_sites() / sites_cov() and kept between calls; y, the options and likelihood() / predict() are unchanged."""
+        X = np.ascontiguousarray(sites, dtype=np.float64)
+        if X.ndim == 1 and self.d == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2 or X.shape[1] != self.d:
+            raise ValueError("sites must have shape (n, d) = (n, %d)" % self.d)
+        ns = X.shape[0]
+        lf = np.ascontiguousarray(leaf, dtype=np.int32)
+        if lf.shape != (ns,):
+            raise ValueError("leaf must have shape (n,) = (%d,)" % ns)
+        n = int(n)
+        if n < 0:
+            raise ValueError("n must be >= 0")
+        zp = None
+        if z is not None:
+            z = np.ascontiguousarray(z, dtype=np.float64)
+            if z.shape != (n, self.sample_sites_slots(ns)):
+                raise ValueError("z must have shape (n, sample_sites_slots(n_sites)) = (%d, %d)" % (n, self.sample_sites_slots(ns)))
+            zp = _ptr(z)
+        out = np.empty((n, ns))
+        self._check(self.lib.mra_sample_sites(self._h, MRA_COV_POSTERIOR if posterior else 0, ns, _ptr(X), _ptr(lf), n,
+                                              int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample0), zp, _ptr(out)))
         return out
 
     def buffer(self, what):

@@ -16,6 +16,16 @@ covariance(rows) in n / 16 sweeps - a DIFFERENT model (other knots), timed at 40
 (profiles/sitecov_timing.txt).
 
     python tools/sites_timing.py cov [c3]
+
+`draw` mode: mra_sample_sites at the same configuration, 16 prior and 16 posterior draws from a seed with the factors valid, medians of
+three, wall and - with MRA_OPT_KERNEL_TIMING - the stream times of mra_get_buffer(what = 9): (a) the 2^20 sites of the shifted grid, 256
+sites = 16 tiles in every leaf; (b) a 4 x 4 refinement of 64 leaves, 4096 sites = 256 tiles per leaf (MRA_SAMPLE_SITES_LEAF_MAX: a
+block of 128 MiB each), once with all 64 leaves in one batch (MRA_OPT_SITES_CHUNK_BYTES = 12 GiB) and once, a single run, with the
+default 256 MiB (one leaf per batch: the 64 Cholesky factorisations run one after the other on one compute unit each).  Last, the parent
+commit's way at its cap: MRATree.simulateAt on 16384 sites (dense matrix + numpy.linalg.eigh on the host).  One JSON line each
+(profiles/sitedraw_timing.txt).
+
+    python tools/sites_timing.py draw [c3]
 """
 import json
 import os
@@ -154,8 +164,85 @@ def main_cov(cfgs):
         pl.close()
 
 
+DRAW_PARTS = ("basis", "leaf", "chain", "leaf_gram", "leaf_cholesky", "draw", "mean_and_sweeps", "upload", "download")
+
+
+def draw_case(pl, sites, leaf, reps, timed_reps):
+    out = {}
+    for kind, post in (("prior", False), ("posterior", True)):
+        first_ms, x = timed(lambda: pl.sample_sites(sites, leaf, 16, seed=1, posterior=post))
+        rec = {"first_call_ms": round(first_ms, 1), "finite": bool(np.isfinite(x).all())}
+        if reps:
+            rec["wall_ms"] = round(sorted(timed(lambda: pl.sample_sites(sites, leaf, 16, seed=1, posterior=post))[0] for _ in range(reps))[reps // 2], 1)
+        pl.set_option(P.MRA_OPT_KERNEL_TIMING, 1)
+        parts = []
+        for _ in range(timed_reps):
+            pl.sample_sites(sites, leaf, 16, seed=1, posterior=post)
+            parts.append(pl.buffer(9))
+        pl.set_option(P.MRA_OPT_KERNEL_TIMING, 0)
+        parts = np.median(np.array(parts), axis=0)
+        rec["stream_ms"] = {k: round(float(v), 2) for k, v in zip(DRAW_PARTS, parts)}
+        rec["stream_ms_kernels"] = round(float(parts[:7].sum()), 2)
+        out[kind] = rec
+    return out
+
+
+def main_draw(cfgs):
+    import make_golden as mg
+    for cfg in cfgs:
+        c = mg.CASES[cfg]
+        locs, y_obs, _ = mg.make_inputs(c)
+        cov = lambda a, b=np.array([]): mt.Matern32(a, b, l=c["l"], sig=c["sig"])      # noqa: E731
+        tree = MRATree(locs, c["r"], cov, y_obs, c["R"], M=c["M"], J=c["J"], verbose=False)
+        pl = tree.plan
+        n = int(round(np.sqrt(len(locs))))
+        cell = (locs.max(0) - locs.min(0)) / (n - 1)
+        grid = locs + 0.5 * cell
+        leaf_all = tree.locate(grid)
+        info = pl.info()
+        pl.predict_sites(grid[:16], leaf_all[:16])            # the factors: one likelihood pass, not part of any figure below
+        # (a) the whole shifted grid
+        out = {"config": cfg, "case": "shifted grid", "P": info["P"], "Ka": info["Ka"], "n_sites": len(grid), "n_leaves": int(len(np.unique(leaf_all))),
+               "sites_per_leaf_max": int(np.bincount(leaf_all).max()), "n_samples": 16, "chunk_bytes": "default (256 MiB)"}
+        out.update(draw_case(pl, grid, leaf_all, 3, 3))
+        print(json.dumps(out), flush=True)
+        # (b) 64 leaves refined 4 x 4
+        t = tree.topology
+        leaves = np.nonzero(np.asarray(t.node_leaf, dtype=bool))[0]
+        some = leaves[np.linspace(0, len(leaves) - 1, 64).astype(int)]
+        off = np.stack(np.meshgrid((np.arange(4) + 0.5) / 4 - 0.5, (np.arange(4) + 0.5) / 4 - 0.5, indexing="ij"), -1).reshape(-1, 2) * cell
+        sites, leaf = [], []
+        for i in some:
+            p = t.perm[int(t.node_row0[i]):int(t.node_row1[i])]
+            own = locs[p[p >= 0]]
+            sites.append((own[:, None, :] + off[None, :, :]).reshape(-1, 2))
+            leaf.append(np.full(len(own) * 16, i, dtype=np.int32))
+        sites, leaf = np.ascontiguousarray(np.vstack(sites)), np.concatenate(leaf)
+        base = {"config": cfg, "case": "4 x 4 refinement of 64 leaves", "n_sites": len(sites), "n_leaves": 64, "sites_per_leaf_max": int(np.bincount(leaf).max()),
+                "n_samples": 16, "block_bytes_per_leaf": 8 * int(np.bincount(leaf).max()) ** 2}
+        pl.set_option(P.MRA_OPT_SITES_CHUNK_BYTES, 12 << 30)
+        out = dict(base, chunk_bytes="12 GiB (one batch)")
+        out.update(draw_case(pl, sites, leaf, 3, 3))
+        print(json.dumps(out), flush=True)
+        pl.set_option(P.MRA_OPT_SITES_CHUNK_BYTES, 0)
+        out = dict(base, chunk_bytes="default (256 MiB: one leaf per batch)", runs="single")
+        out.update(draw_case(pl, sites, leaf, 0, 1))
+        print(json.dumps(out), flush=True)
+        # the parent commit's way, at its cap
+        idx = whole_leaves(t, leaf_all, P.MRA_SITES_COV_MAX)
+        s16, l16 = np.ascontiguousarray(grid[idx]), np.ascontiguousarray(leaf_all[idx])
+        ms, x = timed(lambda: tree.simulateAt(s16, 16, distr="posterior", seed=1, leaf=l16))
+        ms2, x2 = timed(lambda: tree.sampleAt(s16, 16, distr="posterior", seed=1, leaf=l16))
+        print(json.dumps({"config": cfg, "case": "simulateAt (dense matrix + eigh on the host) at its cap", "n_sites": len(idx), "n_samples": 16,
+                          "simulateAt_wall_ms": round(ms, 1), "sampleAt_same_sites_wall_ms": round(ms2, 1),
+                          "finite": bool(np.isfinite(x).all() and np.isfinite(x2).all())}), flush=True)
+        pl.close()
+
+
 if __name__ == "__main__":
-    if sys.argv[1:2] == ["cov"]:
+    if sys.argv[1:2] == ["draw"]:
+        main_draw(sys.argv[2:] or ["c3"])
+    elif sys.argv[1:2] == ["cov"]:
         main_cov(sys.argv[2:] or ["c3"])
     else:
         main(sys.argv[1:] or ["c3"])
