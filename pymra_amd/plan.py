@@ -174,6 +174,46 @@ def _ptr(a):
     return a.ctypes.data_as(C.c_void_p)
 
 
+def host_cov_blocks(topo, cov, locs, obs):
+    """The blocks mra_plan_set_cov_block wants from an opaque ``cov`` (callable on location arrays, or a dense N x N matrix), node by
+    node as (node, C, diag): non-leaf nodes C(S_j, Q_j) (rows node_row0 .. node_row1, one column per knot), diag None; leaves
+    C(S_j, O_j) with one column per observed row in ascending padded-row order (none: 0 columns) and diag = C(x,x) of every row of
+    the leaf, phantom rows (at their ``src`` location) included.  Host arithmetic only: no plan, no device."""
+    t = topo
+    X = np.asarray(locs, dtype=np.float64)
+    if X.ndim == 1:
+        X = X.reshape(-1, 1)
+    y = np.asarray(obs, dtype=np.float64).reshape(-1)
+    dense = None if callable(cov) else np.asarray(cov, dtype=np.float64)
+    if dense is not None and dense.shape != (t.N, t.N):
+        raise ValueError("a dense cov must be N x N")
+
+    def block(ra, rb):
+        if dense is not None:
+            return dense[np.ix_(ra, rb)]
+        return np.asarray(cov(X[ra], X[rb]), dtype=np.float64)
+
+    def blocks():
+        for i in range(t.n_nodes):
+            rows = np.arange(t.node_row0[i], t.node_row1[i])
+            ra = t.src[rows]
+            if t.node_leaf[i]:
+                real = t.perm[rows] >= 0
+                obs_rows = rows[real & np.isfinite(np.where(real, y[ra], np.nan))]
+                rb = t.src[obs_rows]
+                C = block(ra, rb) if len(rb) else np.zeros((len(ra), 0))
+                if dense is not None:
+                    dg = np.diag(dense)[ra]
+                else:
+                    dg = np.diag(block(ra, ra))
+                yield i, C, dg
+            else:
+                kq = t.knot_rows[t.knot_ptr[i]:t.knot_ptr[i + 1]]
+                yield i, block(ra, t.src[kq]), None
+
+    return blocks()
+
+
 class HipPlan:
     """One MRA tree on one GPU.  Thin, stateful wrapper of the C ABI."""
 
@@ -263,37 +303,10 @@ class HipPlan:
         """Evaluate an opaque ``cov`` (callable on location arrays, or a dense N x N matrix) block by block
         on the host - C(S_j, Q_j) for non-leaf nodes (pyMRA/MRANode.py:384), C(S_j, O_j) and C(x,x) for
         leaves - and hand the blocks to the library."""
-        t = self.topo
-        X = np.asarray(locs, dtype=np.float64)
-        if X.ndim == 1:
-            X = X.reshape(-1, 1)
-        y = np.asarray(obs, dtype=np.float64).reshape(-1)
-        dense = None if callable(cov) else np.asarray(cov, dtype=np.float64)
-        if dense is not None and dense.shape != (t.N, t.N):
-            raise ValueError("a dense cov must be N x N")
-
-        def block(ra, rb):
-            if dense is not None:
-                return dense[np.ix_(ra, rb)]
-            return np.asarray(cov(X[ra], X[rb]), dtype=np.float64)
-
+        blocks = host_cov_blocks(self.topo, cov, locs, obs)      # (validates its arguments before the plan changes state)
         self.set_kernel_host()
-        for i in range(t.n_nodes):
-            rows = np.arange(t.node_row0[i], t.node_row1[i])
-            ra = t.src[rows]
-            if t.node_leaf[i]:
-                real = t.perm[rows] >= 0
-                obs_rows = rows[real & np.isfinite(np.where(real, y[ra], np.nan))]
-                rb = t.src[obs_rows]
-                C = block(ra, rb) if len(rb) else np.zeros((len(ra), 0))
-                if dense is not None:
-                    dg = np.diag(dense)[ra]
-                else:
-                    dg = np.diag(block(ra, ra))
-                self.set_cov_block(i, C, dg)
-            else:
-                kq = t.knot_rows[t.knot_ptr[i]:t.knot_ptr[i + 1]]
-                self.set_cov_block(i, block(ra, t.src[kq]))
+        for i, C, dg in blocks:
+            self.set_cov_block(i, C, dg)
 
     def set_option(self, option, value):
         self._check(self.lib.mra_plan_set_option(self._h, int(option), int(value)))
