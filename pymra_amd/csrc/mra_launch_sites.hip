@@ -26,12 +26,12 @@ void mra_sites_build(mra_plan* pl) {
     T.anc_max = 0; T.nop_max = 0;
     for (size_t t = 0; t < nl; ++t) {
         const int i = pl->leaf_nodes[t];
-        std::vector<int> up;
+        const std::vector<int> up = leaf_ancestors(pl, i);      // root first, zero-width levels included
         int width = 0;
-        for (int p = pl->parent[i]; p >= 0; p = pl->parent[p]) { up.push_back(p); width += pl->cw[pl->node_level[p]]; }
+        for (int p : up) width += pl->cw[pl->node_level[p]];
         const int anc = pl->Ka - pl->asuf[pl->node_level[i]];
         if (width != anc) throw MraError(MRA_ERR_STATE, "mra_predict_sites: a leaf's ancestor blocks do not fill its ancestor columns");
-        chain.insert(chain.end(), up.rbegin(), up.rend());      // root first
+        chain.insert(chain.end(), up.begin(), up.end());
         chain_ptr[t + 1] = (int)chain.size();
         T.anc_max = std::max(T.anc_max, anc);
         T.nop_max = std::max(T.nop_max, pl->leaf_nop[t]);

@@ -6,6 +6,46 @@
 
 static const int SOLVE_QUAD_BLOCKS = 512;
 
+NodeLayout mra_node_layout(mra_plan* pl, int leaf_blocks, bool with_F, DevVec<double>& nb, DevVec<SolveFront>& fronts, DevVec<const double*>& kids) {
+    const int nn = pl->n_nodes;
+    NodeLayout Y;
+    Y.noff.assign(nn + 1, 0); Y.anc.assign(nn, 0);
+    for (int i = 0; i < nn; ++i) {
+        const int m = pl->node_level[i];
+        Y.anc[i] = pl->Ka - pl->asuf[m];
+        Y.noff[i + 1] = Y.noff[i] + (pl->leaf[i] ? (long)leaf_blocks * Y.anc[i] : (long)pl->cw[m] + Y.anc[i]) * 16;
+    }
+    nb.alloc((size_t)std::max<long>(Y.noff[nn], 1));
+    std::vector<const double*> kv;
+    Y.lev_off.assign(pl->n_levels + 1, 0);
+    for (int m = 0; m < pl->n_levels; ++m) {
+        const LevelData& lvl = pl->lev[m];
+        Y.lev_off[m] = Y.fronts.size();
+        for (size_t s = 0; s < lvl.nodes.size(); ++s) {
+            const int i = lvl.nodes[s];
+            const int p = pl->parent[i];
+            SolveFront N{};
+            N.F = with_F ? lvl.F_of(s) : nullptr;
+            N.buf = nb.p + Y.noff[i];
+            N.chain = p >= 0 ? nb.p + Y.noff[p] : nullptr;
+            N.ld = with_F ? lvl.ldf : 0; N.cw = lvl.cw; N.anc = Y.anc[i];
+            N.kid0 = (int)kv.size();
+            for (int k = pl->child_ptr[i]; k < pl->child_ptr[i + 1]; ++k) {
+                const int ch = pl->child_list[k];
+                // a leaf hands up its first block (cw + anc rows), a front the ancestor part of its buffer
+                kv.push_back(nb.p + Y.noff[ch] + (pl->leaf[ch] ? 0 : (long)pl->cw[pl->node_level[ch]] * 16));
+            }
+            N.nkid = (int)kv.size() - N.kid0;
+            Y.fronts.push_back(N);
+        }
+    }
+    Y.lev_off[pl->n_levels] = Y.fronts.size();
+    if (kv.empty()) kv.push_back(nullptr);
+    fronts.upload(Y.fronts.empty() ? std::vector<SolveFront>(1) : Y.fronts);
+    kids.upload(kv);
+    return Y;
+}
+
 void mra_solver_build(mra_plan* pl) {
     mra_plan::Solver& S = pl->slv;
     if (S.built) return;
@@ -13,21 +53,23 @@ void mra_solver_build(mra_plan* pl) {
     const long P = pl->P;
     const size_t nl = pl->leaf_nodes.size();
     const int nn = pl->n_nodes;
-    // node buffers: a leaf's g / beta (anc x16), a front's [z ; g] / [alpha ; chain] ((cw + anc) x16)
-    std::vector<long> noff(nn + 1, 0);
-    std::vector<int> anc(nn, 0);
+    // the column layout the sweeps assume, checked here for every call on the retained factors
     for (int i = 0; i < nn; ++i) {
-        const int m = pl->node_level[i];
-        anc[i] = pl->Ka - pl->asuf[m];
-        const int own = pl->leaf[i] ? 0 : pl->cw[m];
-        if (!pl->leaf[i] && pl->lev[m].nf != own + anc[i] + MRA_YB) throw MraError(MRA_ERR_STATE, "mra_solve: front size does not match the column layout");
-        const int p = pl->parent[i];
-        if (p >= 0 && anc[i] != pl->cw[pl->node_level[p]] + anc[p]) throw MraError(MRA_ERR_STATE, "mra_solve: ancestor chain does not match the column layout");
-        if (p < 0 && anc[i] != 0) throw MraError(MRA_ERR_STATE, "mra_solve: the root has ancestor columns");
-        noff[i + 1] = noff[i] + (long)(own + anc[i]) * 16;
+        const int m = pl->node_level[i], p = pl->parent[i], anc = pl->Ka - pl->asuf[m];
+        if (!pl->leaf[i] && pl->lev[m].nf != pl->cw[m] + anc + MRA_YB) throw MraError(MRA_ERR_STATE, "mra_solve: front size does not match the column layout");
+        if (p >= 0 && anc != pl->cw[pl->node_level[p]] + pl->Ka - pl->asuf[pl->node_level[p]]) throw MraError(MRA_ERR_STATE, "mra_solve: ancestor chain does not match the column layout");
+        if (p < 0 && anc != 0) throw MraError(MRA_ERR_STATE, "mra_solve: the root has ancestor columns");
     }
+    for (int m = 0; m < pl->n_levels; ++m)
+        for (size_t s = 0; s < pl->lev[m].nodes.size(); ++s)
+            if (pl->node_slot[pl->lev[m].nodes[s]] != (int)s) throw MraError(MRA_ERR_STATE, "mra_solve: node slot order");
+    mra_row_maps(pl);
+    // node buffers: a leaf's g / beta (anc x16), a front's [z ; g] / [alpha ; chain] ((cw + anc) x16)
+    const NodeLayout lay = mra_node_layout(pl, 1, true, S.nb, S.fronts, S.kids);
+    const std::vector<long>& noff = lay.noff;
+    const std::vector<int>& anc = lay.anc;
+    S.lev_off = lay.lev_off;
     const long n_uy = pl->obs_off_host.empty() ? 0 : pl->obs_off_host.back() * 16;
-    S.nb.alloc((size_t)std::max<long>(noff[nn], 1));
     S.uy.alloc((size_t)std::max<long>(n_uy, 1));
     S.yb.alloc((size_t)16 * P); S.out.alloc((size_t)16 * P);
     S.qpart.alloc((size_t)SOLVE_QUAD_BLOCKS * 256); S.quad.alloc(256);
@@ -35,14 +77,6 @@ void mra_solver_build(mra_plan* pl) {
     S.work_bytes = sizeof(double) * ((size_t)noff[nn] + (size_t)n_uy + (size_t)34 * P + (size_t)SOLVE_QUAD_BLOCKS * 256 + 256);
     std::vector<SolveLeaf> lv(nl);
     std::vector<SolveSeg> segs;
-    std::vector<int> tile_leaf((size_t)(P / 16), -1);
-    std::vector<unsigned char> is_knot(P, 0), rep(P, 0);
-    for (int i = 0; i < nn; ++i)
-        for (long k = pl->knot_ptr[i]; k < pl->knot_ptr[i + 1]; ++k) {
-            const long row = pl->knot_rows[k];
-            if (row < 0 || row >= P) throw MraError(MRA_ERR_INVALID, "knot row out of range");
-            is_knot[row] = 1;
-        }
     for (size_t t = 0; t < nl; ++t) {
         const int i = pl->leaf_nodes[t];
         const int m = pl->node_level[i], nop = pl->leaf_nop[t], p = pl->parent[i];
@@ -56,44 +90,17 @@ void mra_solver_build(mra_plan* pl) {
         L.nop = nop; L.anc = anc[i]; L.a0 = pl->asuf[m];
         lv[t] = L;
         if (nop) segs.push_back(SolveSeg{L.uy, nop, 1});
-        for (long r = pl->row0[i]; r < pl->row1[i]; ++r) rep[r] = is_knot[r];
-        for (long tl = pl->row0[i] / 16; tl < pl->row1[i] / 16; ++tl) tile_leaf[tl] = (int)t;
     }
-    std::vector<SolveFront> fv;
-    std::vector<const double*> kids;
-    S.lev_off.assign(pl->n_levels + 1, 0);
+    for (const SolveFront& N : lay.fronts) segs.push_back(SolveSeg{N.buf, N.cw, -1});
     S.lev_lds.assign(pl->n_levels, 0);
     for (int m = 0; m < pl->n_levels; ++m) {
-        const LevelData& lvl = pl->lev[m];
-        S.lev_off[m] = fv.size();
-        for (size_t s = 0; s < lvl.nodes.size(); ++s) {
-            const int i = lvl.nodes[s];
-            if (pl->node_slot[i] != (int)s) throw MraError(MRA_ERR_STATE, "mra_solve: node slot order");
-            const int p = pl->parent[i];
-            SolveFront N{};
-            N.F = lvl.F_of(s);
-            N.buf = S.nb.p + noff[i];
-            N.chain = p >= 0 ? S.nb.p + noff[p] : nullptr;
-            N.ld = lvl.ldf; N.cw = lvl.cw; N.anc = anc[i];
-            N.kid0 = (int)kids.size();
-            for (int k = pl->child_ptr[i]; k < pl->child_ptr[i + 1]; ++k) {
-                const int ch = pl->child_list[k];
-                kids.push_back(S.nb.p + noff[ch] + (pl->leaf[ch] ? 0 : (long)pl->cw[pl->node_level[ch]] * 16));
-            }
-            N.nkid = (int)kids.size() - N.kid0;
-            fv.push_back(N);
-            segs.push_back(SolveSeg{N.buf, lvl.cw, -1});
-        }
-        S.lev_lds[m] = sizeof(double) * ((size_t)lvl.cw * 16 + (lvl.cw <= SOLVE_FRONT_STAGE ? (size_t)lvl.cw * lvl.cw : 0));
+        const int cw = pl->lev[m].cw;
+        S.lev_lds[m] = sizeof(double) * ((size_t)cw * 16 + (cw <= SOLVE_FRONT_STAGE ? (size_t)cw * cw : 0));
         if (S.lev_lds[m] > 64 * 1024) throw MraError(MRA_ERR_INVALID, "mra_solve: blocks wider than 512 columns are not supported");
     }
-    S.lev_off[pl->n_levels] = fv.size();
-    if (kids.empty()) kids.push_back(nullptr);
     if (segs.empty()) segs.push_back(SolveSeg{nullptr, 0, 1});
-    if (fv.empty()) fv.push_back(SolveFront{});
     if (nl) S.leaves.upload(lv);
-    S.fronts.upload(fv); S.kids.upload(kids); S.segs.upload(segs);
-    S.tile_leaf.upload(tile_leaf); S.rep.upload(rep);
+    S.segs.upload(segs);
     S.built = true;
 }
 
@@ -101,8 +108,8 @@ template <int DIM>
 static void launch_rows(mra_plan* pl) {
     mra_plan::Solver& S = pl->slv;
     const dim3 grid((unsigned)((pl->P / 16 + 3) / 4)), block(256);
-#define MRA_SOLVE_ROWS(MD) hipLaunchKernelGGL((k_solve_rows<DIM, MD>), grid, block, 0, pl->stream, S.leaves.p, S.tile_leaf.p, pl->W.p, (long)pl->ldw, \
-                                              pl->X.p, S.rep.p, pl->kp, S.out.p, pl->P)
+#define MRA_SOLVE_ROWS(MD) hipLaunchKernelGGL((k_solve_rows<DIM, MD>), grid, block, 0, pl->stream, S.leaves.p, pl->maps.tile_leaf.p, pl->W.p, (long)pl->ldw, \
+                                              pl->X.p, pl->maps.rep.p, pl->kp, S.out.p, pl->P)
     switch (pl->kp.mode) {
         case 0: MRA_SOLVE_ROWS(0); break;
         case 1: MRA_SOLVE_ROWS(1); break;

@@ -1220,7 +1220,7 @@ static void build_leaf(mra_plan* pl, const double* y) {
     ArenaScope arena(&pl->arena);
     pl->cphantom_valid = false;
     pl->slv.valid = false; pl->slv.built = false;      // mra_solve's descriptors point into the leaves' panels
-    pl->cov.built = false;                             // mra_cov_apply's read the solver's maps
+    pl->cov.built = false;                             // mra_cov_apply's read the solver's level offsets
     pl->sit.built = false;                             // mra_predict_sites' read the solver's leaf descriptors
     LeafDescs d;
     build_obs_lists(pl, y, d);
@@ -2327,29 +2327,46 @@ static long coarse_slots(const mra_plan* pl, std::vector<long>* zoff) {
     return kn;
 }
 
-static void sampler_build(mra_plan* pl) {
-    mra_plan::Sampler& S = pl->smp;
-    if (S.built) return;
+// ---- what the calls on the retained factors share ------------------------------------------------------------
+// The plan's row maps: rep = a leaf's row that is a knot of some node, knot = a knot of its own leaf, tile_leaf = the leaf of a row tile.
+const mra_plan::RowMaps& mra_row_maps(mra_plan* pl) {
+    mra_plan::RowMaps& R = pl->maps;
+    if (R.built) return R;
     const long P = pl->P;
-    S.n_coarse = coarse_slots(pl, &S.zoff);
-    std::vector<unsigned char> is_knot(P, 0), knot(P, 0), rep(P, 0);
+    std::vector<unsigned char> is_knot(P, 0);
+    R.knot_host.assign(P, 0); R.rep_host.assign(P, 0);
     for (int i = 0; i < pl->n_nodes; ++i)
         for (long k = pl->knot_ptr[i]; k < pl->knot_ptr[i + 1]; ++k) {
             const long row = pl->knot_rows[k];
             if (row < 0 || row >= P) throw MraError(MRA_ERR_INVALID, "knot row out of range");
             is_knot[row] = 1;
-            if (pl->leaf[i]) knot[row] = 1;
+            if (pl->leaf[i]) R.knot_host[row] = 1;
         }
+    std::vector<int> tile_leaf((size_t)(P / 16), -1);
+    for (size_t t = 0; t < pl->leaf_nodes.size(); ++t) {
+        const int i = pl->leaf_nodes[t];
+        for (long r = pl->row0[i]; r < pl->row1[i]; ++r) R.rep_host[r] = is_knot[r];
+        for (long tl = pl->row0[i] / 16; tl < pl->row1[i] / 16; ++tl) tile_leaf[tl] = (int)t;
+    }
+    R.rep.upload(R.rep_host); R.knot.upload(R.knot_host); R.tile_leaf.upload(tile_leaf);
+    R.built = true;
+    return R;
+}
+
+static void sampler_build(mra_plan* pl) {
+    mra_plan::Sampler& S = pl->smp;
+    if (S.built) return;
+    const long P = pl->P;
+    mra_row_maps(pl);
+    S.n_coarse = coarse_slots(pl, &S.zoff);
     const size_t nl = pl->leaf_nodes.size();
-    std::vector<int> tile_leaf((size_t)(P / 16), -1), chain_ptr(nl + 1, 0);
+    std::vector<int> chain_ptr(nl + 1, 0);
     std::vector<SampleChain> chain;
     for (size_t t = 0; t < nl; ++t) {
-        const int i = pl->leaf_nodes[t];
-        for (long r = pl->row0[i]; r < pl->row1[i]; ++r) rep[r] = is_knot[r];
-        for (long tl = pl->row0[i] / 16; tl < pl->row1[i] / 16; ++tl) tile_leaf[tl] = (int)t;
-        for (int p = pl->parent[i]; p >= 0; p = pl->parent[p]) {
-            const int k = pl->node_level[p];
-            if (pl->cw[k]) chain.push_back(SampleChain{pl->coff[k], (int)S.zoff[p], pl->cw[k], 0});
+        const std::vector<int> up = leaf_ancestors(pl, pl->leaf_nodes[t]);
+        for (auto p = up.rbegin(); p != up.rend(); ++p) {      // leaf to root: the order k_sample_coarse sums in
+            const int k = pl->node_level[*p];
+            if (pl->cw[k]) chain.push_back(SampleChain{pl->coff[k], (int)S.zoff[*p], pl->cw[k], 0});
         }
         chain_ptr[t + 1] = (int)chain.size();
     }
@@ -2394,7 +2411,7 @@ static void sampler_build(mra_plan* pl) {
             gp[t] = g;
             cp[t] = PanelProb{G, S.invd.p + ioff[t], nr, (int)(nr / 16), (int)(nr / 16), (int)(t - S.bat[b])};
         }
-    S.rep.upload(rep); S.knot.upload(knot); S.tile_leaf.upload(tile_leaf); S.chain_ptr.upload(chain_ptr);
+    S.chain_ptr.upload(chain_ptr);
     if (chain.empty()) chain.push_back(SampleChain{0, 0, 0, 0});
     S.chain.upload(chain);
     if (nl) { S.leaves.upload(lv); S.gram.upload(gp); S.chol.upload(cp); }
@@ -2411,7 +2428,7 @@ static void sampler_factor(mra_plan* pl, size_t b) {
     launch_gemm<EPI_COV>(pl, S.gram.p + t0, n, rmax, rmax);
     for (size_t off = 0; off < n; off += SAMPLE_LEAF_GRID)
         hipLaunchKernelGGL(k_sample_mask, dim3((unsigned)std::min<long>((rmax * rmax + 255) / 256, 64), (unsigned)std::min(SAMPLE_LEAF_GRID, n - off)),
-                           dim3(256), 0, pl->stream, S.leaves.p + t0 + off, S.knot.p);
+                           dim3(256), 0, pl->stream, S.leaves.p + t0 + off, pl->maps.knot.p);
     HIP_TRY(hipMemsetAsync(S.err.p, 0, sizeof(int), pl->stream));
     hipLaunchKernelGGL(k_panel_chol, dim3((unsigned)n), dim3(256), 0, pl->stream, S.chol.p + t0, S.dn.p, S.err.p, 0);
     int e = 0;
@@ -2451,17 +2468,88 @@ struct KeepResults {
 // the likelihood pass with W at every row: the prior basis the sampler reads (option 17 is overridden by the route, not through the option)
 static void sampler_prior(mra_plan* pl) { run_all(pl, MRA_RUN_LIKELIHOOD, true); }
 
-static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, int64_t sample0, const double* z, double* out) {
+// What every call on the retained factors refuses before it looks at its own arguments, in this order.  `who` names the export;
+// host_cannot / sharded_cannot finish "<who>: MRA_KERNEL_HOST plans ..." and "<who>: sharded plans ...".
+// (the prior basis is computed by the plan's likelihood pass, which reads the observation layout: set_obs comes first for every call)
+static void retained_check_plan(const mra_plan* pl, const char* who, uint32_t flags, uint32_t accepted, const char* host_cannot, const char* sharded_cannot) {
+    char m[200];
     if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
-    const bool cond = flags & MRA_SAMPLE_CONDITIONAL;
-    if (flags & ~MRA_SAMPLE_CONDITIONAL) throw MraError(MRA_ERR_INVALID, "unknown mra_sample flags");
-    if (!(pl->have_locs && pl->have_kernel)) throw MraError(MRA_ERR_STATE, "mra_sample needs set_locs and set_kernel first");
-    // (the prior basis is computed by the plan's likelihood pass, which reads the observation layout: set_obs comes first either way)
-    if (!pl->have_obs) throw MraError(MRA_ERR_STATE, "mra_sample needs set_obs first");
-    if (pl->host_cov || pl->kp.kind == MRA_KERNEL_HOST) throw MraError(MRA_ERR_INVALID, "mra_sample: MRA_KERNEL_HOST plans cannot sample (leaf C(S, S) is not available)");
-    if (pl->reduce_level >= 0 || pl->comm || pl->n_ranks > 1) throw MraError(MRA_ERR_INVALID, "mra_sample: sharded plans cannot sample");
-    if (n < 0) throw MraError(MRA_ERR_INVALID, "n_samples < 0");
+    if (flags & ~accepted) { snprintf(m, sizeof m, "unknown %s flags", who); throw MraError(MRA_ERR_INVALID, m); }
+    if (!(pl->have_locs && pl->have_kernel)) { snprintf(m, sizeof m, "%s needs set_locs and set_kernel first", who); throw MraError(MRA_ERR_STATE, m); }
+    if (!pl->have_obs) { snprintf(m, sizeof m, "%s needs set_obs first", who); throw MraError(MRA_ERR_STATE, m); }
+    if (pl->host_cov || pl->kp.kind == MRA_KERNEL_HOST) { snprintf(m, sizeof m, "%s: MRA_KERNEL_HOST plans %s", who, host_cannot); throw MraError(MRA_ERR_INVALID, m); }
+    if (pl->reduce_level >= 0 || pl->comm || pl->n_ranks > 1) { snprintf(m, sizeof m, "%s: sharded plans %s", who, sharded_cannot); throw MraError(MRA_ERR_INVALID, m); }
+}
+
+static void check_sample0(int64_t sample0, int64_t n) {      // the n sample numbers from sample0 on
     if (sample0 < 0 || (n > 0 && sample0 > INT64_MAX - (n - 1))) throw MraError(MRA_ERR_INVALID, "sample0 < 0, or a sample number past 2^63 - 1");
+}
+
+// "<who>: <noun> is not finite at <where> (column, padded row)": the n columns of M (P each) at the rows of the mask
+static void check_finite_rows(const mra_plan* pl, const char* who, const char* noun, const char* where, const std::vector<unsigned char>& mask,
+                              const double* M, int64_t n) {
+    const long P = pl->P;
+    for (int64_t k = 0; k < n; ++k)
+        for (long p = 0; p < P; ++p)
+            if (mask[p] && !std::isfinite(M[k * P + p])) {
+                char m[128];
+                snprintf(m, sizeof m, "%s: %s is not finite at %s (column %lld, padded row %ld)", who, noun, where, (long long)k, p);
+                throw MraError(MRA_ERR_INVALID, m);
+            }
+}
+
+// W at every row and the factors, valid: one likelihood pass (as sample_all's prior pass) unless the last one still stands.  What the
+// caller reads back afterwards - the last mra_run's likelihood, mean and var - is put back; y and the options are not touched.  After
+// mra_solver_build (msave / vsave).
+static void ensure_factors(mra_plan* pl) {
+    mra_plan::Solver& S = pl->slv;
+    if (S.valid) {
+        for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = mra_plan::KStat();      // the kernel statistics describe this call: no pass ran
+        return;
+    }
+    KeepResults keep(pl, nullptr, S.msave.p, S.vsave.p);
+    sampler_prior(pl);
+    HIP_TRY(hipStreamSynchronize(pl->stream));
+    HIP_TRY(hipGetLastError());
+    S.valid = true;
+}
+
+// nc <= 16 columns of src (P each) into a 16 x P block on the device, the tail zeroed
+static void stage_columns(mra_plan* pl, const double* src, int nc, double* dev, hipMemcpyKind kind = hipMemcpyHostToDevice) {
+    const size_t P = (size_t)pl->P;
+    HIP_TRY(hipMemcpyAsync(dev, src, (size_t)nc * P * sizeof(double), kind, pl->stream));
+    if (nc < 16) HIP_TRY(hipMemsetAsync(dev + (size_t)nc * P, 0, (size_t)(16 - nc) * P * sizeof(double), pl->stream));
+}
+
+// The n columns of `in`, 16 at a time: staged into in_dev, run_block(), then the block's rows (rows_dev -> rows, when rows is given) and
+// its 16 x 16 tile (tile_dev -> the diagonal block of the n x n matrix `tile`, NaN elsewhere, when tile is given) brought back.
+static void column_blocks(mra_plan* pl, int64_t n, const double* in, double* in_dev, double* rows, const double* rows_dev, double* tile,
+                          const double* tile_dev, const std::function<void()>& run_block) {
+    const long P = pl->P;
+    if (tile) for (int64_t e = 0; e < n * n; ++e) tile[e] = std::nan("");
+    for (int64_t c0 = 0; c0 < n; c0 += 16) {
+        const int nc = (int)std::min<int64_t>(16, n - c0);
+        stage_columns(pl, in + c0 * P, nc, in_dev);
+        run_block();
+        if (rows) HIP_TRY(hipMemcpyAsync(rows + c0 * P, rows_dev, (size_t)nc * P * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
+        double tb[256];
+        if (tile) HIP_TRY(hipMemcpyAsync(tb, tile_dev, sizeof tb, hipMemcpyDeviceToHost, pl->stream));
+        HIP_TRY(hipStreamSynchronize(pl->stream));
+        HIP_TRY(hipGetLastError());
+        if (tile)
+            for (int i = 0; i < nc; ++i)
+                for (int j = 0; j < nc; ++j) tile[(c0 + i) * n + c0 + j] = tb[i * 16 + j];
+    }
+}
+
+// room for the Kn x16 non-leaf draws of a block of samples (grow-only)
+static void reserve_coarse(DevVec<double>& v, long Kn) { if (v.n < (size_t)std::max<long>(Kn, 1) * 16) v.alloc((size_t)std::max<long>(Kn, 1) * 16); }
+
+static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, int64_t sample0, const double* z, double* out) {
+    retained_check_plan(pl, "mra_sample", flags, MRA_SAMPLE_CONDITIONAL, "cannot sample (leaf C(S, S) is not available)", "cannot sample");
+    const bool cond = flags & MRA_SAMPLE_CONDITIONAL;
+    if (n < 0) throw MraError(MRA_ERR_INVALID, "n_samples < 0");
+    check_sample0(sample0, n);
     if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
     if (n == 0) return;
     if (!out) throw MraError(MRA_ERR_INVALID, "out is NULL");
@@ -2474,7 +2562,7 @@ static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, i
     const size_t nb = S.bat.size() - 1;
     // caller-given draws are staged a block of samples at a time (at most 512 MB of them)
     const int nsb = z ? (int)std::max<long>(1, std::min<long>(16, ((long)512 << 20) / (8 * n_slots))) : 16;
-    if (S.zc.n < (size_t)std::max<long>(Kn, 1) * 16) S.zc.alloc((size_t)std::max<long>(Kn, 1) * 16);
+    reserve_coarse(S.zc, Kn);
     if (S.out.n < (size_t)16 * P) S.out.alloc((size_t)16 * P);
     if (z && S.zh.n < (size_t)nsb * n_slots) S.zh.alloc((size_t)nsb * n_slots);
     {
@@ -2492,14 +2580,14 @@ static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, i
             // coarse term: all non-leaf draws of the block, then one wave per row tile
             if (Kn) hipLaunchKernelGGL(k_sample_draw, dim3((unsigned)((Kn * 16 + 255) / 256)), dim3(256), 0, pl->stream, zs, Kn, S.zc.p);
             hipLaunchKernelGGL(k_sample_coarse, dim3((unsigned)((P / 16 + 3) / 4)), dim3(256), 0, pl->stream, pl->W.p, (long)pl->ldw,
-                               S.tile_leaf.p, S.chain_ptr.p, S.chain.p, S.zc.p, S.rep.p, S.out.p, P);
+                               pl->maps.tile_leaf.p, S.chain_ptr.p, S.chain.p, S.zc.p, pl->maps.rep.p, S.out.p, P);
             // leaf term, batch by batch (a single batch is factorised once per call)
             for (size_t b = 0; b < nb; ++b) {
                 if (S.factored != (int)b) sampler_factor(pl, b);
                 const size_t t0 = S.bat[b], cnt = S.bat[b + 1] - t0;
                 for (size_t off = 0; off < cnt; off += SAMPLE_LEAF_GRID)
                     hipLaunchKernelGGL(k_sample_leaf, dim3((unsigned)((S.bat_rows[b] + 15) / 16), (unsigned)std::min(SAMPLE_LEAF_GRID, cnt - off)),
-                                       dim3(256), 0, pl->stream, S.leaves.p + t0 + off, S.knot.p, S.rep.p, zs, Kn, S.out.p, P);
+                                       dim3(256), 0, pl->stream, S.leaves.p + t0 + off, pl->maps.knot.p, pl->maps.rep.p, zs, Kn, S.out.p, P);
             }
             if (cond && S.use_solve) {
                 // conditioning by kriging, all draws of the block at once: the factors of the prior pass above are those of the
@@ -2514,7 +2602,7 @@ static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, i
                     hipLaunchKernelGGL(k_sample_pseudo, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, pl->stream, S.ysave.p, xs, zs, s,
                                        Kn + P, std::sqrt(pl->R), pl->y.p, P);
                     run_all(pl, MRA_RUN_LIKELIHOOD | MRA_RUN_PREDICT);
-                    hipLaunchKernelGGL(k_sample_addmean, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, pl->stream, xs, pl->mean.p, S.rep.p, P);
+                    hipLaunchKernelGGL(k_sample_addmean, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, pl->stream, xs, pl->mean.p, pl->maps.rep.p, P);
                 }
                 w_prior = false;              // the predict passes rewrote W
             }
@@ -2529,119 +2617,52 @@ static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, i
 
 // ---- solver (mra_solve) ------------------------------------------------------------------------------------
 static void solve_all(mra_plan* pl, uint32_t flags, int64_t n, const double* Y, double* mean, double* quad) {
-    if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
-    if (flags) throw MraError(MRA_ERR_INVALID, "unknown mra_solve flags");
-    if (!(pl->have_locs && pl->have_kernel)) throw MraError(MRA_ERR_STATE, "mra_solve needs set_locs and set_kernel first");
-    if (!pl->have_obs) throw MraError(MRA_ERR_STATE, "mra_solve needs set_obs first");
-    if (pl->host_cov || pl->kp.kind == MRA_KERNEL_HOST) throw MraError(MRA_ERR_INVALID, "mra_solve: MRA_KERNEL_HOST plans cannot solve (C(S, o) is evaluated on the device)");
-    if (pl->reduce_level >= 0 || pl->comm || pl->n_ranks > 1) throw MraError(MRA_ERR_INVALID, "mra_solve: sharded plans cannot solve");
+    retained_check_plan(pl, "mra_solve", flags, 0, "cannot solve (C(S, o) is evaluated on the device)", "cannot solve");
     if (n < 0) throw MraError(MRA_ERR_INVALID, "n_cols < 0");
     if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
     if (n == 0) return;
     if (!Y) throw MraError(MRA_ERR_INVALID, "Y is NULL");
-    const long P = pl->P;
-    for (int64_t k = 0; k < n; ++k)
-        for (long p = 0; p < P; ++p)
-            if (pl->y_finite_host[p] && !std::isfinite(Y[k * P + p])) {
-                char m[128];
-                snprintf(m, sizeof m, "mra_solve: Y is not finite at an observed row (column %lld, padded row %ld)", (long long)k, p);
-                throw MraError(MRA_ERR_INVALID, m);
-            }
+    check_finite_rows(pl, "mra_solve", "Y", "an observed row", pl->y_finite_host, Y, n);
     HIP_TRY(mraSetDevice(pl->device));
     mra_solver_build(pl);
+    ensure_factors(pl);
     mra_plan::Solver& S = pl->slv;
-    if (!S.valid) {
-        // the factors: one likelihood pass with W at every row (as sample_all's prior pass); what the caller reads back afterwards -
-        // the last mra_run's likelihood, mean and var - is put back.  y and the options are not touched.
-        KeepResults keep(pl, nullptr, S.msave.p, S.vsave.p);
-        sampler_prior(pl);
-        HIP_TRY(hipStreamSynchronize(pl->stream));
-        HIP_TRY(hipGetLastError());
-        S.valid = true;
-    } else {
-        for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = mra_plan::KStat();      // the kernel statistics describe this call: no pass ran
-    }
-    if (quad) for (int64_t e = 0; e < n * n; ++e) quad[e] = std::nan("");
-    for (int64_t c0 = 0; c0 < n; c0 += 16) {
-        const int nc = (int)std::min<int64_t>(16, n - c0);
-        HIP_TRY(hipMemcpyAsync(S.yb.p, Y + c0 * P, (size_t)nc * P * sizeof(double), hipMemcpyHostToDevice, pl->stream));
-        if (nc < 16) HIP_TRY(hipMemsetAsync(S.yb.p + (size_t)nc * P, 0, (size_t)(16 - nc) * P * sizeof(double), pl->stream));
-        mra_solver_block(pl, mean != nullptr, quad != nullptr);
-        if (mean) HIP_TRY(hipMemcpyAsync(mean + c0 * P, S.out.p, (size_t)nc * P * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
-        double qb[256];
-        if (quad) HIP_TRY(hipMemcpyAsync(qb, S.quad.p, sizeof qb, hipMemcpyDeviceToHost, pl->stream));
-        HIP_TRY(hipStreamSynchronize(pl->stream));
-        HIP_TRY(hipGetLastError());
-        if (quad)
-            for (int i = 0; i < nc; ++i)
-                for (int j = 0; j < nc; ++j) quad[(c0 + i) * n + c0 + j] = qb[i * 16 + j];
-    }
+    column_blocks(pl, n, Y, S.yb.p, mean, S.out.p, quad, S.quad.p, [&] { mra_solver_block(pl, mean != nullptr, quad != nullptr); });
 }
 
 // ---- covariance operator (mra_cov_apply) ------------------------------------------------------------------
 static void cov_all(mra_plan* pl, uint32_t flags, int64_t n, const double* A, double* out, double* gram) {
-    if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
-    if (flags & ~MRA_COV_POSTERIOR) throw MraError(MRA_ERR_INVALID, "unknown mra_cov_apply flags");
-    if (!(pl->have_locs && pl->have_kernel)) throw MraError(MRA_ERR_STATE, "mra_cov_apply needs set_locs and set_kernel first");
-    if (!pl->have_obs) throw MraError(MRA_ERR_STATE, "mra_cov_apply needs set_obs first");
-    if (pl->host_cov || pl->kp.kind == MRA_KERNEL_HOST) throw MraError(MRA_ERR_INVALID, "mra_cov_apply: MRA_KERNEL_HOST plans cannot apply the covariance (C(S, S) is evaluated on the device)");
-    if (pl->reduce_level >= 0 || pl->comm || pl->n_ranks > 1) throw MraError(MRA_ERR_INVALID, "mra_cov_apply: sharded plans cannot apply the covariance");
+    retained_check_plan(pl, "mra_cov_apply", flags, MRA_COV_POSTERIOR, "cannot apply the covariance (C(S, S) is evaluated on the device)",
+                        "cannot apply the covariance");
     if (n < 0) throw MraError(MRA_ERR_INVALID, "n_cols < 0");
     if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
     if (n == 0) return;
     if (!A) throw MraError(MRA_ERR_INVALID, "A is NULL");
     const bool post = flags & MRA_COV_POSTERIOR;
-    const long P = pl->P;
     HIP_TRY(mraSetDevice(pl->device));
     mra_solver_build(pl);
     mra_cov_build(pl);
-    mra_plan::Solver& S = pl->slv;
+    check_finite_rows(pl, "mra_cov_apply", "A", "a reported row", mra_row_maps(pl).rep_host, A, n);
+    ensure_factors(pl);      // W at every row and, for the posterior, the factors
     mra_plan::Cov& V = pl->cov;
-    for (int64_t k = 0; k < n; ++k)
-        for (long p = 0; p < P; ++p)
-            if (V.rep_host[p] && !std::isfinite(A[k * P + p])) {
-                char m[128];
-                snprintf(m, sizeof m, "mra_cov_apply: A is not finite at a reported row (column %lld, padded row %ld)", (long long)k, p);
-                throw MraError(MRA_ERR_INVALID, m);
-            }
-    if (!S.valid) {
-        // W at every row and, for the posterior, the factors: the pass mra_solve runs and keeps (solve_all)
-        KeepResults keep(pl, nullptr, S.msave.p, S.vsave.p);
-        sampler_prior(pl);
-        HIP_TRY(hipStreamSynchronize(pl->stream));
-        HIP_TRY(hipGetLastError());
-        S.valid = true;
-    } else {
-        for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = mra_plan::KStat();      // the kernel statistics describe this call: no pass ran
-    }
-    if (gram) for (int64_t e = 0; e < n * n; ++e) gram[e] = std::nan("");
-    for (int64_t c0 = 0; c0 < n; c0 += 16) {
-        const int nc = (int)std::min<int64_t>(16, n - c0);
-        HIP_TRY(hipMemcpyAsync(V.ab.p, A + c0 * P, (size_t)nc * P * sizeof(double), hipMemcpyHostToDevice, pl->stream));
-        if (nc < 16) HIP_TRY(hipMemsetAsync(V.ab.p + (size_t)nc * P, 0, (size_t)(16 - nc) * P * sizeof(double), pl->stream));
-        mra_cov_block(pl, post, gram != nullptr);
-        if (out) HIP_TRY(hipMemcpyAsync(out + c0 * P, V.out.p, (size_t)nc * P * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
-        double gb[256];
-        if (gram) HIP_TRY(hipMemcpyAsync(gb, V.gram.p, sizeof gb, hipMemcpyDeviceToHost, pl->stream));
-        HIP_TRY(hipStreamSynchronize(pl->stream));
-        HIP_TRY(hipGetLastError());
-        if (gram)
-            for (int i = 0; i < nc; ++i)
-                for (int j = 0; j < nc; ++j) gram[(c0 + i) * n + c0 + j] = gb[i * 16 + j];
-    }
+    column_blocks(pl, n, A, V.ab.p, out, V.out.p, gram, V.gram.p, [&] { mra_cov_block(pl, post, gram != nullptr); });
 }
 
 // ---- prediction at new sites (mra_predict_sites) ----------------------------------------------------------------
 // The tiles of a call: the sites grouped by leaf (stable: a leaf's sites keep the caller's order), each group padded to a multiple of 16
 // with copies of its first site.  slot[tile * 16 + k] = the caller's site of that column, -1 for padding.  Plain host code.
-static void sites_tiles(const std::vector<int>& slot_of_leaf_site, int64_t n, size_t nl, std::vector<int64_t>& slot, std::vector<int>& tile_leaf) {
-    std::vector<int64_t> cnt(nl + 1, 0), order((size_t)n);
-    for (int64_t i = 0; i < n; ++i) ++cnt[(size_t)slot_of_leaf_site[i] + 1];
+// sites 0 .. n-1 grouped by leaf slot, a stable counting sort: leaf t's sites are order[cnt[t] .. cnt[t + 1]), in the caller's order
+static void group_by_leaf(const std::vector<int>& lslot, int64_t n, size_t nl, std::vector<int64_t>& cnt, std::vector<int64_t>& order) {
+    cnt.assign(nl + 1, 0); order.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) ++cnt[(size_t)lslot[(size_t)i] + 1];
     for (size_t t = 0; t < nl; ++t) cnt[t + 1] += cnt[t];
-    {
-        std::vector<int64_t> at(cnt.begin(), cnt.end() - 1);
-        for (int64_t i = 0; i < n; ++i) order[(size_t)at[(size_t)slot_of_leaf_site[i]]++] = i;      // counting sort: stable
-    }
+    std::vector<int64_t> at(cnt.begin(), cnt.end() - 1);
+    for (int64_t i = 0; i < n; ++i) order[(size_t)at[(size_t)lslot[(size_t)i]]++] = i;
+}
+
+static void sites_tiles(const std::vector<int>& slot_of_leaf_site, int64_t n, size_t nl, std::vector<int64_t>& slot, std::vector<int>& tile_leaf) {
+    std::vector<int64_t> cnt, order;
+    group_by_leaf(slot_of_leaf_site, n, nl, cnt, order);
     slot.clear(); tile_leaf.clear();
     for (size_t t = 0; t < nl; ++t) {
         const int64_t g0 = cnt[t], g1 = cnt[t + 1];
@@ -2653,22 +2674,10 @@ static void sites_tiles(const std::vector<int>& slot_of_leaf_site, int64_t n, si
     }
 }
 
-// What mra_predict_sites and mra_sites_cov check before anything is launched, in this order: the plan (sites_check_plan), then the call's
-// own arguments, then the sites (sites_check_sites, which also gives each site's leaf slot).  `who` names the export in the messages.
-static void sites_check_plan(const mra_plan* pl, const char* who, bool unknown_flags, int64_t n) {
-    char m[200];
-    if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
-    if (unknown_flags) { snprintf(m, sizeof m, "unknown %s flags", who); throw MraError(MRA_ERR_INVALID, m); }
-    if (!(pl->have_locs && pl->have_kernel)) { snprintf(m, sizeof m, "%s needs set_locs and set_kernel first", who); throw MraError(MRA_ERR_STATE, m); }
-    if (!pl->have_obs) { snprintf(m, sizeof m, "%s needs set_obs first", who); throw MraError(MRA_ERR_STATE, m); }
-    if (pl->host_cov || pl->kp.kind == MRA_KERNEL_HOST) {
-        snprintf(m, sizeof m, "%s: MRA_KERNEL_HOST plans cannot predict at new sites (C(Q, s) is evaluated on the device)", who);
-        throw MraError(MRA_ERR_INVALID, m);
-    }
-    if (pl->reduce_level >= 0 || pl->comm || pl->n_ranks > 1) {
-        snprintf(m, sizeof m, "%s: sharded plans cannot predict at new sites", who);
-        throw MraError(MRA_ERR_INVALID, m);
-    }
+// What the three site calls check before anything is launched, in this order: the plan (sites_check_plan), then the call's own
+// arguments, then the sites (sites_check_sites, which also gives each site's leaf slot).  `who` names the export in the messages.
+static void sites_check_plan(const mra_plan* pl, const char* who, uint32_t flags, uint32_t accepted, int64_t n) {
+    retained_check_plan(pl, who, flags, accepted, "cannot predict at new sites (C(Q, s) is evaluated on the device)", "cannot predict at new sites");
     if (n < 0) throw MraError(MRA_ERR_INVALID, "n_sites < 0");
 }
 
@@ -2693,21 +2702,15 @@ static std::vector<int> sites_check_sites(const mra_plan* pl, const char* who, i
     return lslot;
 }
 
-// The state both calls run on: the site descriptors, and W at every row and the factors - the pass mra_solve runs and keeps (solve_all).
+// The state the site calls run on: the site descriptors, and W at every row and the factors
 static void sites_ensure_state(mra_plan* pl) {
     HIP_TRY(mraSetDevice(pl->device));
     mra_sites_build(pl);
-    mra_plan::Solver& S = pl->slv;
-    if (!S.valid) {
-        KeepResults keep(pl, nullptr, S.msave.p, S.vsave.p);
-        sampler_prior(pl);
-        HIP_TRY(hipStreamSynchronize(pl->stream));
-        HIP_TRY(hipGetLastError());
-        S.valid = true;
-    } else {
-        for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = mra_plan::KStat();      // the kernel statistics describe this call: no pass ran
-    }
+    ensure_factors(pl);
 }
+
+// mra_sites_timed adds to `ms` instead of sit.ms while this lives
+struct SitesSink { mra_plan::Sites& T; SitesSink(mra_plan::Sites& t, double* ms) : T(t) { T.ms_sink = ms; } ~SitesSink() { T.ms_sink = nullptr; } };
 
 // the coordinates of tiles [t0, t0 + nt) for the device: padding columns repeat their tile's first site
 static void sites_gather(const std::vector<int64_t>& slot, long t0, long nt, int d, const double* sites, double* xs) {
@@ -2720,21 +2723,14 @@ static void sites_gather(const std::vector<int64_t>& slot, long t0, long nt, int
 
 static void predict_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const double* sites, const int32_t* leaf, int64_t nc,
                               const double* Y, double* mean, double* var) {
-    sites_check_plan(pl, "mra_predict_sites", flags != 0, n);
+    sites_check_plan(pl, "mra_predict_sites", flags, 0, n);
     if (nc < 0) throw MraError(MRA_ERR_INVALID, "n_cols < 0");
     if (!Y && nc != 1) throw MraError(MRA_ERR_INVALID, "Y is NULL (the plan's own observations): n_cols must be 1");
     const std::vector<int> lslot = sites_check_sites(pl, "mra_predict_sites", n, sites, leaf);
     const long P = pl->P;
     const int d = pl->d;
     const bool want_mean = mean != nullptr && nc > 0;
-    if (Y)
-        for (int64_t k = 0; k < nc; ++k)
-            for (long p = 0; p < P; ++p)
-                if (pl->y_finite_host[p] && !std::isfinite(Y[k * P + p])) {
-                    char m[128];
-                    snprintf(m, sizeof m, "mra_predict_sites: Y is not finite at an observed row (column %lld, padded row %ld)", (long long)k, p);
-                    throw MraError(MRA_ERR_INVALID, m);
-                }
+    if (Y) check_finite_rows(pl, "mra_predict_sites", "Y", "an observed row", pl->y_finite_host, Y, nc);
     if (n == 0) return;
     sites_ensure_state(pl);
     mra_plan::Solver& S = pl->slv;
@@ -2753,9 +2749,8 @@ static void predict_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const dou
         const int ncb = want_mean ? (int)std::min<int64_t>(16, nc - cb * 16) : 0;
         if (want_mean) {
             // the block's beta (leaves' gb) and q (leaves' uy): the solver's sweeps without its row step
-            if (Y) HIP_TRY(hipMemcpyAsync(S.yb.p, Y + cb * 16 * P, (size_t)ncb * P * sizeof(double), hipMemcpyHostToDevice, pl->stream));
-            else HIP_TRY(hipMemcpyAsync(S.yb.p, pl->y.p, (size_t)P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
-            if (ncb < 16) HIP_TRY(hipMemsetAsync(S.yb.p + (size_t)ncb * P, 0, (size_t)(16 - ncb) * P * sizeof(double), pl->stream));
+            if (Y) stage_columns(pl, Y + cb * 16 * P, ncb, S.yb.p);
+            else stage_columns(pl, pl->y.p, 1, S.yb.p, hipMemcpyDeviceToDevice);      // (n_cols is 1)
             mra_sites_timed(pl, 4, [&] { mra_solver_block(pl, true, false, false); });
         }
         for (long t0 = 0; t0 < n_tiles; t0 += per_chunk) {
@@ -2791,7 +2786,7 @@ static void predict_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const dou
 // Every tile's a (prior) or a, t, b (posterior) stays on the device for the call; the matrix comes back in row panels of whole tiles,
 // each block at or after the diagonal computed once and written to both triangles here: `out` is symmetric by construction.
 static void sites_cov_all(mra_plan* pl, uint32_t flags, int64_t n, const double* sites, const int32_t* leaf, double* out) {
-    sites_check_plan(pl, "mra_sites_cov", (flags & ~MRA_COV_POSTERIOR) != 0, n);
+    sites_check_plan(pl, "mra_sites_cov", flags, MRA_COV_POSTERIOR, n);
     if (n > MRA_SITES_COV_MAX) {
         char m[200];
         snprintf(m, sizeof m, "mra_sites_cov: n_sites = %lld is above MRA_SITES_COV_MAX = %d (the result is a dense matrix, 2 GiB at the cap)", (long long)n, MRA_SITES_COV_MAX);
@@ -2805,8 +2800,7 @@ static void sites_cov_all(mra_plan* pl, uint32_t flags, int64_t n, const double*
     sites_ensure_state(pl);
     mra_plan::Sites& T = pl->sit;
     for (double& v : T.cov_ms) v = 0.0;
-    struct Sink { mra_plan::Sites& T; ~Sink() { T.ms_sink = nullptr; } } sink{T};
-    T.ms_sink = T.cov_ms;
+    SitesSink sink(T, T.cov_ms);
     std::vector<int64_t> slot;
     std::vector<int> tile_leaf;
     sites_tiles(lslot, n, pl->leaf_nodes.size(), slot, tile_leaf);
@@ -2855,9 +2849,9 @@ static void sites_cov_all(mra_plan* pl, uint32_t flags, int64_t n, const double*
 // ---- draws at new sites (mra_sample_sites) -----------------------------------------------------------------------
 static void sample_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const double* sites, const int32_t* leaf, int64_t ns_all, uint64_t seed,
                              int64_t sample0, const double* z, double* out) {
-    sites_check_plan(pl, "mra_sample_sites", (flags & ~MRA_COV_POSTERIOR) != 0, n);
+    sites_check_plan(pl, "mra_sample_sites", flags, MRA_COV_POSTERIOR, n);
     if (ns_all < 0) throw MraError(MRA_ERR_INVALID, "n_samples < 0");
-    if (sample0 < 0 || (ns_all > 0 && sample0 > INT64_MAX - (ns_all - 1))) throw MraError(MRA_ERR_INVALID, "sample0 < 0, or a sample number past 2^63 - 1");
+    check_sample0(sample0, ns_all);
     if (n > 0 && ns_all > 0 && !out) throw MraError(MRA_ERR_INVALID, "out is NULL");
     const std::vector<int> lslot = sites_check_sites(pl, "mra_sample_sites", n, sites, leaf);
     const int d = pl->d;
@@ -2865,14 +2859,9 @@ static void sample_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const doub
     // exact duplicates (same leaf, equal coordinates) collapse to their first occurrence: first[i] = the caller's index of it
     std::vector<int64_t> first((size_t)n), distinct;
     {
-        // a stable counting sort by leaf (as sites_tiles), then each leaf's sites by coordinates: equal sites become neighbours, first index first
-        std::vector<int64_t> order((size_t)n), cnt(nl + 1, 0);
-        for (int64_t i = 0; i < n; ++i) ++cnt[(size_t)lslot[(size_t)i] + 1];
-        for (size_t t = 0; t < nl; ++t) cnt[t + 1] += cnt[t];
-        {
-            std::vector<int64_t> at(cnt.begin(), cnt.end() - 1);
-            for (int64_t i = 0; i < n; ++i) order[(size_t)at[(size_t)lslot[(size_t)i]]++] = i;
-        }
+        // grouped by leaf, then each leaf's sites by coordinates: equal sites become neighbours, first index first
+        std::vector<int64_t> order, cnt;
+        group_by_leaf(lslot, n, nl, cnt, order);
         auto less = [&](int64_t x, int64_t y) {
             for (int e = 0; e < d; ++e)
                 if (sites[x * d + e] != sites[y * d + e]) return sites[x * d + e] < sites[y * d + e];
@@ -2903,8 +2892,7 @@ static void sample_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const doub
     mra_plan::Solver& S = pl->slv;
     mra_plan::Sites& T = pl->sit;
     for (double& v : T.draw_ms) v = 0.0;
-    struct Sink { mra_plan::Sites& T; ~Sink() { T.ms_sink = nullptr; } } sink{T};
-    T.ms_sink = T.draw_ms;
+    SitesSink sink(T, T.draw_ms);
     // the tiles of the distinct sites; slot[] then holds the caller's index of each column
     const int64_t nd = (int64_t)distinct.size();
     std::vector<int64_t> slot;
@@ -2924,12 +2912,10 @@ static void sample_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const doub
         std::vector<int> ptr(nl + 1, 0);
         for (size_t t = 0; t < nl; ++t) {
             const int i = pl->leaf_nodes[t], a0 = pl->asuf[pl->node_level[i]];
-            std::vector<SiteDrawChain> up;
-            for (int p = pl->parent[i]; p >= 0; p = pl->parent[p]) {
+            for (int p : leaf_ancestors(pl, i)) {
                 const int k = pl->node_level[p];
-                if (pl->cw[k]) up.push_back(SiteDrawChain{pl->coff[k] - a0, (int)zoff[(size_t)p], pl->cw[k], 0});
+                if (pl->cw[k]) ch.push_back(SiteDrawChain{pl->coff[k] - a0, (int)zoff[(size_t)p], pl->cw[k], 0});
             }
-            ch.insert(ch.end(), up.rbegin(), up.rend());
             ptr[t + 1] = (int)ch.size();
         }
         if (ch.empty()) ch.push_back(SiteDrawChain{0, 0, 0, 0});
@@ -2958,15 +2944,14 @@ static void sample_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const doub
     size_t cap_g = 0;
     for (const Batch& b : bat) { cap_t = std::max(cap_t, b.nt); cap_l = std::max(cap_l, b.n_leaves); cap_g = std::max(cap_g, b.g); }
     mra_sites_draw_reserve(pl, cap_t, cap_g, cap_l);
-    if (T.zc.n < (size_t)std::max<long>(Kn, 1) * 16) T.zc.alloc((size_t)std::max<long>(Kn, 1) * 16);
+    reserve_coarse(T.zc, Kn);
     if (z) {
-        if (T.zcin.n < (size_t)std::max<long>(Kn, 1) * 16) T.zcin.alloc((size_t)std::max<long>(Kn, 1) * 16);
+        reserve_coarse(T.zcin, Kn);
         if (T.zin.n < (size_t)cap_t * 256) T.zin.alloc((size_t)cap_t * 256);
     }
     if (post) {
         // beta (leaves' gb) and q (leaves' uy) of the plan's own observations: the solver's sweeps without its row step, once per call
-        HIP_TRY(hipMemcpyAsync(S.yb.p, pl->y.p, (size_t)pl->P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
-        HIP_TRY(hipMemsetAsync(S.yb.p + (size_t)pl->P, 0, (size_t)15 * pl->P * sizeof(double), pl->stream));
+        stage_columns(pl, pl->y.p, 1, S.yb.p, hipMemcpyDeviceToDevice);
         mra_sites_timed(pl, 6, [&] { mra_solver_block(pl, true, false, false); });
     }
     std::vector<double> xs((size_t)cap_t * 16 * d), oh((size_t)cap_t * 256), zch(z ? (size_t)std::max<long>(Kn, 1) * 16 : 0), zlh(z ? (size_t)cap_t * 256 : 0);

@@ -495,15 +495,24 @@ struct mra_plan {
     bool ktiming = false;
     struct KStat { int launches = 0; double ms = 0, flops = 0, flops_exec = 0, bytes = 0; } kstat[KF_COUNT];
     std::vector<std::pair<int, std::pair<hipEvent_t, hipEvent_t>>> kev;
-    // sampler (mra_sample): index maps built and device buffers allocated on the first call, so that a plan that never samples keeps
+    // The row maps of the calls on the retained factors ("What the calls on the retained factors share").  They
+    // follow from the topology and the knot rows alone: built once per plan, by the first call that reads them (mra_row_maps), and
+    // reset by no set_* and no option.
+    struct RowMaps {
+        bool built = false;
+        std::vector<unsigned char> rep_host, knot_host;      // [P] reported row (a leaf's row that is a knot of some node); knot row of its own leaf
+        DevVec<unsigned char> rep, knot;          // the same two on the device
+        DevVec<int> tile_leaf;                    // [P / 16] leaf of a row tile (-1: none)
+    } maps;
+    // sampler (mra_sample): chains built and device buffers allocated on the first call, so that a plan that never samples keeps
     // its footprint.  Leaves go through their Gram / factor stage in batches of bounded size (batch b = leaves [bat[b], bat[b+1])).
+    // The row maps are the plan's (maps).
     struct Sampler {
         bool built = false;
         long n_coarse = 0;                        // latent slots of the non-leaf nodes
         std::vector<long> zoff;                   // per node: its first latent slot (-1: leaf)
-        DevVec<unsigned char> rep, knot;          // [P] reported row; knot row of its leaf
-        DevVec<int> tile_leaf, chain_ptr;         // [P / 16] leaf of a row tile (-1: none); [n_leaves + 1] into chain
-        DevVec<SampleChain> chain;
+        DevVec<int> chain_ptr;                    // [n_leaves + 1] into chain
+        DevVec<SampleChain> chain;                // a leaf's ancestors of non-zero width, leaf to root
         DevVec<SampleLeaf> leaves;                // every leaf, G pointing into the batch buffer
         DevVec<GemmProb> gram;
         DevVec<PanelProb> chol;
@@ -515,8 +524,9 @@ struct mra_plan {
         bool use_solve = false;                   // this call conditions its draws through mra_solve's sweeps (MRA_OPT_SAMPLE_SOLVE)
         size_t gram_bytes = 0;                    // MRA_OPT_SAMPLE_GRAM_BYTES (0: SAMPLE_GRAM_BUDGET); a change rebuilds the batches
     } smp;
-    // solver (mra_solve): the factors of a likelihood pass with W at every row, kept for any number of right-hand sides.  Index maps,
-    // descriptors and work buffers are built on the first call (and again after new observations: the leaves' panels move).
+    // solver (mra_solve): the factors of a likelihood pass with W at every row, kept for any number of right-hand sides.  Descriptors
+    // and work buffers are built on the first call (and again after new observations: the leaves' panels move); the node buffers are
+    // laid out by mra_node_layout, the row maps are the plan's (maps).
     struct Solver {
         bool built = false;
         bool valid = false;                       // "factors valid, W complete": set by mra_solve's own pass, cleared by mra_run,
@@ -527,20 +537,17 @@ struct mra_plan {
         std::vector<size_t> lev_off, lev_lds;     // [level]: first front of the level in `fronts`; dynamic LDS of its launches
         DevVec<const double*> kids;
         DevVec<SolveSeg> segs;
-        DevVec<int> tile_leaf;                    // [P / 16] leaf of a row tile (-1: none)
-        DevVec<unsigned char> rep;                // [P] reported row
         DevVec<double> yb, out, uy, nb, qpart, quad, msave, vsave;      // 16 x P in / out blocks; U_y / s / q; node buffers; Q
         size_t work_bytes = 0;
     } slv;
-    // covariance operator (mra_cov_apply): reads W of the pass mra_solve keeps (slv.valid), the solver's tile_leaf / rep maps and,
-    // for the posterior, its sweeps.  Built on the first call and again whenever the solver's descriptors are.
+    // covariance operator (mra_cov_apply): reads W of the pass mra_solve keeps (slv.valid), the plan's row maps (maps), the solver's
+    // level offsets and, for the posterior, its sweeps.  Its node buffers are its own, laid out by mra_node_layout as the solver's are.
+    // Built on the first call and again whenever the solver's descriptors are.
     struct Cov {
         bool built = false;
         DevVec<CovLeaf> leaves;
         DevVec<SolveFront> fronts;                // by level, then slot (the solver's lev_off)
         DevVec<const double*> kids;
-        DevVec<unsigned char> knot;               // [P] knot row of its own leaf
-        std::vector<unsigned char> rep_host;      // [P] reported row (the rows A is read and checked at)
         DevVec<double> ab, out, nb, gpart, gram;  // 16 x P in / out blocks; node buffers; gram partial sums; 16 x 16
         size_t work_bytes = 0;
     } cov;
@@ -592,6 +599,14 @@ static inline double* leaf_V(const mra_plan* pl, size_t t) {
     return leaf_C(pl, t) + (nop + na) * nop;
 }
 
+// The non-leaf ancestors of a node, root first (levels of zero width included: the caller skips them where its chain has no use for them)
+static inline std::vector<int> leaf_ancestors(const mra_plan* pl, int node) {
+    std::vector<int> up;
+    for (int p = pl->parent[node]; p >= 0; p = pl->parent[p]) up.push_back(p);
+    std::reverse(up.begin(), up.end());
+    return up;
+}
+
 // Dynamic LDS above 64 KiB has to be requested per kernel and per DEVICE.  The record is kept per plan (a plan lives on one
 // device; mra_plan_prepare reports its size) AND per (device, kernel) for the process, so that the second plan of a process - the
 // reference's MLE pattern builds a new MRATree per objective call - does not pay ~20 us per kernel again in its first pass.
@@ -619,6 +634,18 @@ static inline void launch_cascade_any(mra_plan* pl, const CascadeArgs& ar) { if 
 static inline void launch_knot_chain(mra_plan* pl, const KnotChainArgs& ka) { if (pl->d == 1) launch_knot_chain_d1(pl, ka); else launch_knot_chain_d2(pl, ka); }
 void launch_predict_any(mra_plan* pl, const PredArgs& ar, size_t lds);
 void launch_predict_hi(mra_plan* pl, const PredHiArgs& hi, const PredArgs& low, size_t lds_low, bool upd);
+// mra_plan.hip: the plan's row maps (mra_plan::RowMaps), built on the first call; holds the one "knot row out of range" check
+const mra_plan::RowMaps& mra_row_maps(mra_plan* pl);
+// mra_launch_solve.hip: the node buffers of a sweep over the tree and the fronts that point into them.  A leaf's buffer holds leaf_blocks
+// blocks of anc x16, a front's (cw + anc) x16; nb is allocated here, fronts (by level, then slot) and kids are uploaded.  with_F: the
+// fronts read their factor (F_of / ldf; the solver), else nullptr / 0 (the covariance path).
+struct NodeLayout {
+    std::vector<long> noff;                   // [n_nodes + 1] a node's first double in nb
+    std::vector<int> anc;                     // [n_nodes] ancestor columns
+    std::vector<size_t> lev_off;              // [n_levels + 1] first front of a level
+    std::vector<SolveFront> fronts;           // the host copy of what was uploaded
+};
+NodeLayout mra_node_layout(mra_plan* pl, int leaf_blocks, bool with_F, DevVec<double>& nb, DevVec<SolveFront>& fronts, DevVec<const double*>& kids);
 // mra_launch_solve.hip: descriptors + work buffers of mra_solve; one block of <= 16 columns (slv.yb -> slv.out, slv.quad; launches
 // only, on pl->stream); the 16-column glue of the sampler's MRA_OPT_SAMPLE_SOLVE path
 void mra_solver_build(mra_plan* pl);
