@@ -93,6 +93,23 @@ int mra_plan_set_locs(mra_plan *plan, const double *locs_perm);
  * R: scalar nugget variance (the reference requires a Python float, pyMRA/MRANode.py:85-88). */
 int mra_plan_set_obs(mra_plan *plan, const double *y_perm, double R);
 
+/* Replaces: the non-float `R` of the reference, a matrix that Node.__init__ slices per child (pyMRA/MRANode.py:85-88) and that its
+ * leaves then cannot use (R*np.eye, (1/R)*H.T*H, :415-430) - here its diagonal: per-observation noise variances,
+ * y_p = x(s_p) + eps_p, eps_p ~ N(0, r_p).  Every leaf factorises C = v_M(o,o) + diag(r_o); the likelihood, the predictions, mra_solve,
+ * mra_cov_apply, mra_predict_sites, mra_sites_cov, mra_sample_sites and sharded passes are what they are with that C, and conditional
+ * draws of mra_sample use sqrt(r_p) eps_p as the noise of row p (same noise slots).  With r_p = R at every observed row every result is
+ * bit for bit the scalar one: the leaves' C is written as v + 0 and the diagonal then takes r in one rounding, as v + R does.
+ * r_perm: P values, padded leaf order, read only at the rows the plan observes (finite y); values elsewhere, NaN included, are ignored.
+ * NULL returns to the scalar R of the last mra_plan_set_obs.  Call it after mra_plan_set_obs (MRA_ERR_STATE before); a later
+ * mra_plan_set_obs* drops the vector (its scalar holds again: the mask may have changed).  MRA_ERR_INVALID for a value that is negative
+ * or not finite at an observed row, checked on the host before anything changes.  y, the mask, the leaf lists and every option stay;
+ * the retained factors do not (as after any set_*, the next call on them factorises once).  Allowed on sharded plans (the rows are the
+ * rank's own) and on MRA_KERNEL_HOST plans.  A pass with a vector set launches one more kernel (k_leaf_noise); a pass without one is
+ * unchanged.  mra_plan_set_noise_rows: r in the CALLER's row order (N values), gathered through the topology's src[P] as
+ * mra_plan_set_locs_rows gathers the locations. */
+int mra_plan_set_noise(mra_plan *plan, const double *r_perm);
+int mra_plan_set_noise_rows(mra_plan *plan, const double *r, const int64_t *src);
+
 /* Replaces: the `cov` callable when it is one of pyMRA's stationary kernels
  * (pyMRA/MRATools.py:256-301).  params = {l, sig, scale[, circular]}; value = scale * k(D; l, sig);
  * circular != 0 (1-D only): D = min(|a-b|, 1-|a-b|), the torus branch of dist() (MRATools.py:232-239).
@@ -126,7 +143,7 @@ int mra_get_predict(mra_plan *plan, double *mean_perm, double *var_perm);
 
 /* Simulation from the model (the reference's dense-Cholesky simulate1D / simulateGRF, pyMRA/MRATools.py:395-484, at any size):
  * exact draws from the MRA prior covariance Sigma = sum_j B_j k_j B_j^T of the reported rows, or, with MRA_SAMPLE_CONDITIONAL,
- * from the posterior given the plan's observations and nugget R ("conditioning by kriging": x + mean_MRA(y - x_o - sqrt(R) eps),
+ * from the posterior given the plan's observations and noise r ("conditioning by kriging": x + mean_MRA(y - x_o - sqrt(r_o) eps), r_o = R or the vector of mra_plan_set_noise,
  * one likelihood + predict pass per conditional draw).  A prior draw is
  *     x = sum_{non-leaf j} W^m(j)[rows_j] z_j + sum_{leaf j} L_j zeta_j,   L_j L_j^T = v_M(K_j, K_j)  (K_j: the leaf's knot rows)
  * Latent slots (mra_sample_slots gives their number, Kn + 2 P):
@@ -153,7 +170,7 @@ int mra_sample(mra_plan *plan, uint32_t flags, int64_t n_samples, uint64_t seed,
  * vector k at Y + k P, padded leaf order, read at the plan's OBSERVED rows only - the mask of the last set_obs)
  *     mean (n_cols x P, or NULL): mean[k] = E[x | Y[k] at the observed rows] = the mean mra_run + mra_get_predict give for y = Y[k];
  *                                 unreported rows (phantoms, rows a 1-D split drops) are exactly 0
- *     quad (n_cols x n_cols, or NULL): Y_o^T (Sigma_MRA[o, o] + R I)^-1 Y_o, so that quad[k][k] is the u of mra_get_likelihood for
+ *     quad (n_cols x n_cols, or NULL): Y_o^T (Sigma_MRA[o, o] + D)^-1 Y_o, D = R I or diag(r_o) of mra_plan_set_noise, so that quad[k][k] is the u of mra_get_likelihood for
  *                                 y = Y[k] (the log-determinant d does not depend on y)
  * Columns are processed in blocks of 16 (the N of v_mfma_f64_16x16x4_f64).  quad is returned BLOCK-DIAGONAL: entries whose row and
  * column lie in the same block of 16 columns (k / 16 equal) are computed, all others are set to NaN - a cross-block entry needs the
@@ -172,7 +189,7 @@ int mra_solve(mra_plan *plan, uint32_t flags, int64_t n_cols, const double *Y, d
  * W_j = W[rows of j, block of j's level], K_l the knot rows of leaf l - the Sigma mra_sample draws from.  For n_cols vectors A
  * (n_cols x P, row-major: vector k at A + k P, padded leaf order, read at the REPORTED rows only; values elsewhere are ignored)
  *     out  (n_cols x P, or NULL): out[k] = Sigma A[k]; with MRA_COV_POSTERIOR out[k] = Sigma_post A[k],
- *                                 Sigma_post = Sigma - Sigma[:, o] (Sigma[o, o] + R I)^-1 Sigma[o, :] on the mask of the last set_obs, whose
+ *                                 Sigma_post = Sigma - Sigma[:, o] (Sigma[o, o] + D)^-1 Sigma[o, :] (D as in mra_solve) on the mask of the last set_obs, whose
  *                                 diagonal is the var of mra_get_predict; unreported rows (phantoms, rows a 1-D split drops) are exactly 0
  *     gram (n_cols x n_cols, or NULL): A Sigma A^T (A Sigma_post A^T), the covariance matrix of the functionals a_k^T x
  * Columns are processed in blocks of 16 (the N of v_mfma_f64_16x16x4_f64).  gram is returned BLOCK-DIAGONAL as quad of mra_solve is:
@@ -279,6 +296,8 @@ int mra_sample_sites(mra_plan *plan, uint32_t flags, int64_t n_sites, const doub
  * 8: the same for the last mra_sites_cov (6 values: the basis, leaf, chain and gram kernels, the uploads and the downloads);
  * 9: the same for the last mra_sample_sites (9 values: basis, leaf, chain, leaf Gram, leaf Cholesky, draw, mean with the solver's
  * sweeps, uploads, downloads);
+ * 10: the noise variance by padded row (P values): the vector of mra_plan_set_noise at observed rows and 0 elsewhere, or the scalar R
+ * at every row when no vector is set;
  * copies min(capacity, available) doubles into out, returns the available count in *n_avail.
  * (W after a likelihood-only run is complete only with MRA_OPT_LIK_ROWS off: by default such a run computes W at the rows a
  * likelihood needs - the observed rows, and the knots on the level-by-level path - and leaves the others as they were.) */
@@ -332,7 +351,7 @@ int mra_get_route(mra_plan *plan, int32_t *out, int capacity);
  *   MRA_BLOCK_LPRIOR  non-leaf: L_j, cw x cw lower Cholesky factor of kInv_j (padded with the identity)
  *   MRA_BLOCK_FRONT   non-leaf: the factorised front, nf x nf (lower triangle): Lt_j (cw x cw), Zt_j below it
  *                     (na x cw), the Schur block Gt_j (na x na) - whitened ATil / omgTil / u (last block = y)
- *   MRA_BLOCK_LEAF    leaf: the panel [C = v_m(o,o) + R I -> Lc ; Ut ; Tt], (nop + na + N_j) x nop
+ *   MRA_BLOCK_LEAF    leaf: the panel [C = v_m(o,o) + R I (diag(r_o) with mra_plan_set_noise) -> Lc ; Ut ; Tt], (nop + na + N_j) x nop
  * out receives min(capacity, rows*cols) doubles row-major; *n_rows, *n_cols the block shape. */
 #define MRA_BLOCK_W_ROWS   0
 #define MRA_BLOCK_LPRIOR   1

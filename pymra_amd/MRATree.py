@@ -3,6 +3,8 @@
 Mirrors the public surface of pyMRA/MRATree.py:
 
 * ``MRATree(locs, r, cov, obs, R, M=-1, J=-1, critDepth=-1, verbose=True)``   MRATree.py:23
+  (``R``: a Python float, or a 1-D float array of N per-observation noise variances - the diagonal of the matrix ``R`` that
+  MRANode.py:85-88 slices per child; ``setNoise`` re-sets it on the same tree)
 * ``getLikelihood()`` -> 1x1 ``np.matrix`` (root.d + root.u)                  MRATree.py:82-84
 * ``predict()`` -> (N x 1 ``np.matrix`` mean, (N,) ``ndarray`` sd)            MRATree.py:90-94
 * attributes ``locs, d, r, J, M, obs_inds, root`` with ``root.d, root.u, root.mean, root.var``
@@ -90,6 +92,22 @@ def probe_cov(cov, d, locs=None):
     return out if isinstance(out, mt.KernelSpec) else None
 
 
+def _check_noise(R, N):
+    """The `R` argument: a Python float (scalar nugget) -> (R, False); a 1-D float array of N per-observation variances, the
+    diagonal of the reference's matrix R (pyMRA/MRANode.py:85-88) -> (float64 array, True)."""
+    if isinstance(R, float):
+        return R, False
+    if isinstance(R, np.ndarray) and R.dtype.kind == "f":
+        if R.ndim != 1:
+            raise ValueError("R must be a float or a 1-D array of per-observation variances: only a diagonal R is supported, "
+                             "not a %d-D array (correlated noise)" % R.ndim)
+        if len(R) != N:
+            raise ValueError("a noise vector R must have one entry per location (%d), got %d" % (N, len(R)))
+        return np.ascontiguousarray(R, dtype=np.float64), True
+    # the reference indexes a non-float R as a matrix (MRANode.py:85-88) and fails on an int
+    raise TypeError("R must be a Python float (scalar nugget variance) or a 1-D float array (per-observation variances); got %r" % type(R))
+
+
 class MRATree(object):
 
     def __init__(self, locs, r, cov, obs, R, M=-1, J=-1, critDepth=-1, verbose=True, device=0,
@@ -102,12 +120,16 @@ class MRATree(object):
         if critDepth < 0:
             critDepth = self.M + 1
         self.critDepth = critDepth
-        if not isinstance(R, float):
-            # the reference indexes a non-float R as a matrix (MRANode.py:85-88) and fails on an int
-            raise TypeError("R must be a Python float (scalar nugget variance); got %r" % type(R))
+        R_in = R
+        R, noise_vector = _check_noise(R, N)
         obs_arr = np.asarray(obs, dtype=np.float64)
         self._obs_inds = None                   # (the reference's obs_inds, MRATree.py:62: computed when somebody reads it)
-        self.obs, self.R = obs_arr, R
+        self.obs, self.R = obs_arr, R_in
+        if noise_vector:
+            # checked before anything is built; the scalar that the one-call constructor takes is only a placeholder
+            ro = R[np.isfinite(obs_arr.reshape(-1))] if obs_arr.size == N else R
+            if not (np.all(np.isfinite(ro)) and np.all(ro >= 0.0)):
+                raise ValueError("the noise variance of an observed location is negative or not finite")
 
         spec = probe_cov(cov, self.d, np.asarray(locs, dtype=np.float64))
         if spec is not None and spec.circular and self.d != 1:
@@ -119,9 +141,12 @@ class MRATree(object):
         logger.debug('r: %d, \tJ: %d,\tM: %d' % (self.r, self.J, self.M))
         # large 2-D trees: tree replay, plan construction and the uploads in one library call (the plan is built beside the
         # sequential knot draws); everything else - 1-D, small nodes, KMeans rules - the general path
-        both = create_with_replay(locs, r, self.M, self.J, obs_arr, R, device) if self.d == 2 else None
+        R_scalar = (float(ro.mean()) if ro.size and ro.mean() > 0.0 else 1.0) if noise_vector else R
+        both = create_with_replay(locs, r, self.M, self.J, obs_arr, R_scalar, device) if self.d == 2 else None
         if both is not None:
             self.plan, self.topology = both
+            if noise_vector:
+                self.plan.set_noise(R)          # (the one-call constructor takes a scalar: the vector goes in before the first run)
         else:
             self.topology = build_topology(np.asarray(locs, dtype=np.float64), r, self.M, self.J)
             self.plan = HipPlan(self.topology, device=device)
@@ -417,4 +442,20 @@ class MRATree(object):
         d, u = self.plan.likelihood()
         mean, var, self._sd = self.plan.predict(with_sd=True) if want_predict else (None, None, None)
         self.root = RootView(d, u, mean, var, len(self.locs), self.topology, np.asarray(self.locs, dtype=np.float64), spec)
+        return self.getLikelihood()
+
+    def setNoise(self, R, want_predict=False):
+        """Re-set the observation noise on the same tree (a Python float, or a 1-D array of N per-observation variances), run a
+        pass and return the likelihood - the counterpart of ``reevaluate`` for the noise."""
+        R, vector = _check_noise(R, len(self.locs))
+        if vector:
+            self.plan.set_noise(R)
+        else:
+            self.plan.set_noise(np.full(len(self.locs), R))
+        self.R = R
+        self._node_blocks = {}
+        self.plan.run(likelihood=True, predict=want_predict)
+        d, u = self.plan.likelihood()
+        mean, var, self._sd = self.plan.predict(with_sd=True) if want_predict else (None, None, None)
+        self.root = RootView(d, u, mean, var, len(self.locs), self.topology, np.asarray(self.locs, dtype=np.float64), self.kernel)
         return self.getLikelihood()

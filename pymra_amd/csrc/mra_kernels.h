@@ -3830,6 +3830,23 @@ __global__ void k_leaf_cphantom(const LeafProb* __restrict__ probs, const int* _
 }
 #endif
 
+// per-observation noise (mra_plan_set_noise): C[k][k] += r[obs[k]] at a leaf's real observations, on top of the C = v_M(o,o) + 0 that the
+// residual product (or k_leaf_fill) left; r by padded row.  The phantom rows behind them keep their identity.  Four leaves per workgroup,
+// one wave each.
+#ifndef MRA_KERNELS_TEMPLATES_ONLY      /* non-template kernel: defined once, in the translation unit of mra_plan.hip */
+__global__ __launch_bounds__(256) void k_leaf_noise(const LeafProb* __restrict__ probs, const int* __restrict__ n_obs,
+                                                     const double* __restrict__ r, int n_leaves) {
+    const int lf = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (lf >= n_leaves) return;
+    const LeafProb pb = probs[lf];
+    const int no = n_obs[lf];
+    for (int k = threadIdx.x & 63; k < no; k += 64) {
+        double* c = pb.Pn + (long)k * pb.ld + k;
+        *c += r[pb.obs[k]];
+    }
+}
+#endif
+
 // leaf moments: var = max(C(x,x) - |W_anc[x]|^2 - |Tt[x]|^2, 0); y column of W reset to 0.
 // One wave per row.
 #ifndef MRA_KERNELS_TEMPLATES_ONLY      /* non-template kernel: defined once, in the translation unit of mra_plan.hip */
@@ -4679,6 +4696,14 @@ __global__ __launch_bounds__(256) void k_sample_pseudo(const double* __restrict_
     if (i >= P) return;
     const double yo = y_in[i];
     y_out[i] = (yo == yo) ? yo - x[i] - sqrtR * sample_z(zs, noise0 + i, s) : yo;
+}
+// the same with a noise vector: sd[i] = sqrt(r_i) by padded row
+__global__ __launch_bounds__(256) void k_sample_pseudo_rows(const double* __restrict__ y_in, const double* __restrict__ x, SampleZ zs, int s,
+                                                            long noise0, const double* __restrict__ sd, double* __restrict__ y_out, long P) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    const double yo = y_in[i];
+    y_out[i] = (yo == yo) ? yo - x[i] - sd[i] * sample_z(zs, noise0 + i, s) : yo;
 }
 __global__ __launch_bounds__(256) void k_sample_addmean(double* __restrict__ x, const double* __restrict__ mean,
                                                         const unsigned char* __restrict__ rep, long P) {

@@ -156,6 +156,11 @@ void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad, bool want_ro
 }
 
 void mra_solver_pseudo(mra_plan* pl, const double* y, const double* x, const SampleZ& zs, long slot0) {
+    if (pl->noise_on) {
+        hipLaunchKernelGGL(k_solve_pseudo_rows, dim3((unsigned)((pl->P + 255) / 256)), dim3(256), 0, pl->stream, y, x, zs, slot0, pl->noise_sd.p,
+                           pl->slv.yb.p, pl->P);
+        return;
+    }
     hipLaunchKernelGGL(k_solve_pseudo, dim3((unsigned)((pl->P + 255) / 256)), dim3(256), 0, pl->stream, y, x, zs, slot0, std::sqrt(pl->R),
                        pl->slv.yb.p, pl->P);
 }

@@ -832,7 +832,7 @@ static void build_leaf_descriptors(mra_plan* pl, LeafDescs& d) {
         g.rowmap = pl->obs_pos.p + r0; g.C2 = Pn; g.diag_add = pl->R;
         d.resid[t] = g;
         {
-            // likelihood-only runs need just C = v_m(o,o) + R I: both sides gathered through the observation list
+            // likelihood-only runs need just C = v_m(o,o) + R I (diag_add 0 while a noise vector is set: run_leaf_noise): both sides gathered through the observation list
             GemmProb c{};
             c.A = pl->W.p + a0; c.lda = pl->ldw; c.idxA = q.obs; c.B = c.A; c.ldb = pl->ldw; c.idxB = q.obs;
             c.C = Pn; c.ldc = nop; c.XA = pl->X.p; c.XB = pl->X.p;
@@ -1139,7 +1139,7 @@ static std::vector<T> in_order(const std::vector<T>& v, const std::vector<size_t
 // the per-leaf descriptors to the device, in leaf order (and the C-only factorisations small first as well; with resid_longest_first
 // the residual products of the device kernels too: every problem carries all its operands, so the list may be dealt in any order)
 static void upload_leaf_descriptors(mra_plan* pl, const LeafDescs& d, const std::vector<size_t>& order) {
-    pl->hLeafResid = d.resid; pl->leaf_nobs_host = d.nobs;
+    pl->hLeafResid = d.resid; pl->hLeafResidLik = d.resid_lik; pl->leaf_order = order; pl->leaf_nobs_host = d.nobs;
     pl->gLeafResidLik.upload(d.resid_lik);
     pl->gLeafResidSorted.upload(pl->resid_longest_first ? in_order(d.resid, order) : std::vector<GemmProb>());
     pl->gLeafResidLikSorted.upload(pl->resid_longest_first ? in_order(d.resid_lik, order) : std::vector<GemmProb>());
@@ -1833,7 +1833,7 @@ static void run_prior_levels(mra_plan* pl, const PassRoute& r) {
 }
 
 // ---- leaves (nl of them, nl > 0).  A leaf's panel is [C ; Ut ; V] (leaf_C / leaf_Ut / leaf_V) ------------------------------------
-// leaves every leaf's V[S,o] residual with C = v(o,o) + R I on top of it, or with c_only nothing but C
+// leaves every leaf's V[S,o] residual with C = v(o,o) + R I (+ 0 while a noise vector is set) on top of it, or with c_only nothing but C
 static void run_leaf_product(mra_plan* pl, const PassRoute& r, size_t nl) {
     KTimer kt(pl, KF_LEAF_RESID, r.c_only ? pl->fl_leaf_c_only : pl->fl_leaf_resid);
     if (pl->host_cov) {
@@ -1862,8 +1862,16 @@ static void run_leaf_c_fix(mra_plan* pl, const PassRoute& r, size_t nl) {
     } else if (r.c_fix == LeafCFix::Fill) {
         const long total = (long)(pl->leaf_max_nop + pl->leaf_max_na) * pl->leaf_max_nop;
         dim3 grid((unsigned)std::min<long>((total + 255) / 256, 64), (unsigned)nl);
-        hipLaunchKernelGGL(k_leaf_fill, grid, dim3(256), 0, pl->stream, pl->gLeaf.p, pl->W.p, (long)pl->ldw, pl->R);
+        hipLaunchKernelGGL(k_leaf_fill, grid, dim3(256), 0, pl->stream, pl->gLeaf.p, pl->W.p, (long)pl->ldw, pl->noise_on ? 0.0 : pl->R);
     }
+}
+
+// (a noise vector is set) leaves C = v(o,o) + diag(r_o): the stages above wrote v(o,o) + 0, exactly v(o,o), so the diagonal takes the one
+// rounding of the scalar path's v + R.  On the main stream, before the leaves' fork; every route and both kinds of pass come through here
+static void run_leaf_noise(mra_plan* pl, size_t nl) {
+    if (!pl->noise_on) return;
+    KTimer kt(pl, KF_MISC, 0);
+    hipLaunchKernelGGL(k_leaf_noise, dim3((unsigned)((nl + 3) / 4)), dim3(256), 0, pl->stream, pl->gLeaf.p, pl->leaf_nobs.p, pl->noise.p, (int)nl);
 }
 
 // A fork to the side stream.  With `on` the launch helpers (they use pl->stream) go to stream2 between the constructor and join();
@@ -2303,6 +2311,7 @@ static void run_all(mra_plan* pl, uint32_t flags, bool full_rows = false) {
     if (nl) {
         run_leaf_product(pl, r, nl);
         run_leaf_c_fix(pl, r, nl);
+        run_leaf_noise(pl, nl);
         run_leaf_factor(pl, r, nl);
         if (!r.direct_parent) run_leaf_syrk(pl, nl);
         if (r.predict) run_leaf_predict_work(pl, r, nl);
@@ -2596,11 +2605,15 @@ static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, i
                 mra_solver_block(pl, true, false);
                 mra_solver_addmean(pl, S.out.p, ns);
             } else if (cond) {
-                // conditioning by kriging: x + mean_MRA(y - x_o - sqrt(R) eps), one likelihood + predict pass per sample
+                // conditioning by kriging: x + mean_MRA(y - x_o - sqrt(r_o) eps), one likelihood + predict pass per sample
                 for (int s = 0; s < ns; ++s) {
                     double* xs = S.out.p + (long)s * P;
-                    hipLaunchKernelGGL(k_sample_pseudo, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, pl->stream, S.ysave.p, xs, zs, s,
-                                       Kn + P, std::sqrt(pl->R), pl->y.p, P);
+                    if (pl->noise_on)
+                        hipLaunchKernelGGL(k_sample_pseudo_rows, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, pl->stream, S.ysave.p, xs, zs, s,
+                                           Kn + P, pl->noise_sd.p, pl->y.p, P);
+                    else
+                        hipLaunchKernelGGL(k_sample_pseudo, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, pl->stream, S.ysave.p, xs, zs, s,
+                                           Kn + P, std::sqrt(pl->R), pl->y.p, P);
                     run_all(pl, MRA_RUN_LIKELIHOOD | MRA_RUN_PREDICT);
                     hipLaunchKernelGGL(k_sample_addmean, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, pl->stream, xs, pl->mean.p, pl->maps.rep.p, P);
                 }
@@ -3178,6 +3191,7 @@ static void set_obs(mra_plan* pl, const double* y, double R) {
     HIP_TRY(mraSetDevice(pl->device));
     HIP_TRY(mraMemcpy(pl->y.p, y, (size_t)pl->P * sizeof(double), hipMemcpyHostToDevice));
     pl->R = R;
+    pl->noise_on = false;               // a noise vector belongs to the mask it was checked against: the scalar holds again
     if (pl->host_cov) {
         // host-evaluated covariance blocks are per observed row: a new observation pattern invalidates them (and
         // build_leaf rebuilds the leaf descriptors without their Csrc pointers).  The caller has to select
@@ -3194,6 +3208,51 @@ static void set_obs(mra_plan* pl, const double* y, double R) {
     }
     build_leaf(pl, y);
     pl->have_obs = true;
+}
+
+// the diag_add of every leaf residual problem, in place: gLeafResid (the host-covariance problems included), gLeafResidLik and their
+// sorted copies
+static void set_leaf_diag_add(mra_plan* pl, double v) {
+    for (auto& g : pl->hLeafResid) g.diag_add = v;
+    for (auto& g : pl->hLeafResidLik) g.diag_add = v;
+    pl->gLeafResid.fill(pl->hLeafResid); pl->gLeafResidLik.fill(pl->hLeafResidLik);
+    if (pl->gLeafResidSorted.n) pl->gLeafResidSorted.fill(in_order(pl->hLeafResid, pl->leaf_order));
+    if (pl->gLeafResidLikSorted.n) pl->gLeafResidLikSorted.fill(in_order(pl->hLeafResidLik, pl->leaf_order));
+}
+
+// r: P noise variances by padded row, read at observed rows only (nullptr: back to the scalar of the last set_obs).  Every value is
+// checked before anything changes.  y, the mask, the leaf lists and the options stay; the retained factors do not.
+static void set_noise(mra_plan* pl, const double* r) {
+    if (!pl->have_obs) throw MraError(MRA_ERR_STATE, "mra_plan_set_noise needs mra_plan_set_obs first (the noise is read at the observed rows)");
+    const long P = pl->P;
+    // observed: a finite y inside a leaf (rows outside every leaf - dropped by a 1-D split, orphan knot rows of a shard - are nobody's)
+    std::vector<unsigned char> seen((size_t)P, 0);
+    if (r) {
+        for (size_t t = 0; t < pl->leaf_nodes.size(); ++t)
+            for (long p = pl->row0[pl->leaf_nodes[t]]; p < pl->row1[pl->leaf_nodes[t]]; ++p) seen[p] = pl->y_finite_host[p];
+        for (long p = 0; p < P; ++p)
+            if (seen[p] && !(std::isfinite(r[p]) && r[p] >= 0.0))
+                throw MraError(MRA_ERR_INVALID, "mra_plan_set_noise: the noise variance of an observed row is negative or not finite");
+    }
+    HIP_TRY(mraSetDevice(pl->device));
+    pl->slv.valid = false;
+    if (!r) {
+        if (pl->noise_on) { set_leaf_diag_add(pl, pl->R); pl->noise_on = false; }
+        return;
+    }
+    std::vector<double> sd((size_t)P);
+    pl->noise_host.assign((size_t)P, 0.0);
+    parallel_rows(P, [&](int64_t a, int64_t b) {
+        for (int64_t p = a; p < b; ++p) {
+            if (seen[p]) pl->noise_host[p] = r[p];
+            sd[p] = std::sqrt(pl->noise_host[p]);
+        }
+    });
+    if (pl->noise.n != (size_t)P) { pl->noise.alloc((size_t)P); pl->noise_sd.alloc((size_t)P); }
+    HIP_TRY(mraMemcpy(pl->noise.p, pl->noise_host.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice));
+    HIP_TRY(mraMemcpy(pl->noise_sd.p, sd.data(), (size_t)P * sizeof(double), hipMemcpyHostToDevice));
+    if (!pl->noise_on) set_leaf_diag_add(pl, 0.0);
+    pl->noise_on = true;
 }
 
 static void get_predict(mra_plan* pl, double* mean, double* var) {
@@ -3437,6 +3496,21 @@ int mra_plan_set_obs(mra_plan* pl, const double* y, double R) {
     return guarded(pl, [&] { require(pl && y, "mra_plan_set_obs: plan or y is NULL"); set_obs(pl, y, R); return MRA_OK; });
 }
 
+int mra_plan_set_noise(mra_plan* pl, const double* r_perm) {
+    return guarded(pl, [&] { require(pl, "mra_plan_set_noise: plan is NULL"); set_noise(pl, r_perm); return MRA_OK; });
+}
+
+int mra_plan_set_noise_rows(mra_plan* pl, const double* r, const int64_t* src) {
+    return guarded(pl, [&] {
+        require(pl && r && src, "mra_plan_set_noise_rows: plan, r or src is NULL");
+        std::lock_guard<std::mutex> lock(g_stage_mutex);
+        double* rp = stage_buffer((size_t)pl->P);
+        parallel_rows(pl->P, [&](int64_t a, int64_t b) { for (int64_t p = a; p < b; ++p) rp[p] = r[src[p]]; });
+        set_noise(pl, rp);
+        return MRA_OK;
+    });
+}
+
 int mra_plan_set_kernel(mra_plan* pl, int kind, const double* params, int n) {
     return guarded(pl, [&] {
         require(pl, "mra_plan_set_kernel: plan is NULL");
@@ -3611,6 +3685,15 @@ int mra_get_buffer(mra_plan* pl, int what, double* out, int64_t cap, int64_t* n_
         if (what == 9) {             // host record: stream ms of the last mra_sample_sites
             *n_avail = 9;
             if (out && cap > 0) memcpy(out, pl->sit.draw_ms, (size_t)std::min<int64_t>(cap, 9) * sizeof(double));
+            return MRA_OK;
+        }
+        if (what == 10) {            // host record: the noise variance by padded row (the scalar R everywhere when no vector is set)
+            *n_avail = pl->P;
+            const int64_t m = std::min<int64_t>(cap, pl->P);
+            if (out && m > 0) {
+                if (pl->noise_on) memcpy(out, pl->noise_host.data(), (size_t)m * sizeof(double));
+                else std::fill(out, out + m, pl->R);
+            }
             return MRA_OK;
         }
         if (what == 0) { src = pl->W.p; n = (int64_t)pl->W.n; }

@@ -344,6 +344,12 @@ struct mra_plan {
     KernelParams kp{};
     bool host_cov = false;
     double R = 0.0;
+    // per-observation noise variances (mra_plan_set_noise): while noise_on the leaves' C = v_M(o,o) + diag(r_o) - the leaf descriptors
+    // carry diag_add = 0 and run_leaf_noise adds r on the diagonal; noise_sd = sqrt(r) for the pseudo-data of conditional draws.
+    // By padded row, 0 at rows the plan does not observe.  Dropped by the next mra_plan_set_obs (pl->R holds again).
+    bool noise_on = false;
+    DevVec<double> noise, noise_sd;
+    std::vector<double> noise_host;
     int reduce_level = -1;
     // device data
     DevVec<double> X, y, W, var, mean, dnode, scal, covsrc, covdiag, stamps, pstamps, tstamps, kstamps, kstamps2;
@@ -365,7 +371,8 @@ struct mra_plan {
     DevVec<LeafProb> gLeaf;
     DevVec<GemmProb> gLeafResid, gLeafSyrk, gLeafUpdate, gLeafResidLik;
     DevVec<GemmProb> gLeafResidSorted, gLeafResidLikSorted;      // resid_longest_first: those of the device kernels once more, in the order of order_small_first (else empty); gLeafResid stays leaf-indexed (MRA_KERNEL_HOST points its problems at the host blocks by leaf)
-    std::vector<GemmProb> hLeafResid;
+    std::vector<GemmProb> hLeafResid, hLeafResidLik;      // host copies: MRA_KERNEL_HOST and mra_plan_set_noise patch them and send them again
+    std::vector<size_t> leaf_order;                       // order_small_first, the order of the *Sorted lists
     std::vector<int> leaf_nobs_host;
     DevVec<PanelProb> gLeafCholFull, gLeafCholLik, gLeafCholC, gLeafCholSorted;
     // leaves with more than 192 observations: right-looking blocked factorisation, 64 columns per step (one panel launch +

@@ -273,6 +273,17 @@ __global__ __launch_bounds__(256) void k_solve_pseudo(const double* __restrict__
     for (int s = 0; s < 16; ++s)
         Yb[(long)s * P + p] = (ob && s < zs.ns) ? yp - x[(long)s * P + p] - sqrtR * sample_z(zs, slot0 + p, s) : 0.0;
 }
+// the same with a noise vector: sd[p] = sqrt(r_p) by padded row
+__global__ __launch_bounds__(256) void k_solve_pseudo_rows(const double* __restrict__ y, const double* __restrict__ x, SampleZ zs, long slot0,
+                                                           const double* __restrict__ sd, double* __restrict__ Yb, long P) {
+    const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    const double yp = y[p];
+    const bool ob = yp == yp && fabs(yp) != __builtin_inf();
+    const double sdp = sd[p];
+    for (int s = 0; s < 16; ++s)
+        Yb[(long)s * P + p] = (ob && s < zs.ns) ? yp - x[(long)s * P + p] - sdp * sample_z(zs, slot0 + p, s) : 0.0;
+}
 __global__ __launch_bounds__(256) void k_solve_addmean(double* __restrict__ x, const double* __restrict__ mean, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) x[i] += mean[i];

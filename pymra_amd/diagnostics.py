@@ -67,7 +67,8 @@ def collect_node_blocks(tree, posterior: bool = True) -> List[NodeBlocks]:
     if locs.ndim == 1:
         locs = locs.reshape(-1, 1)
     yv = np.asarray(tree.obs, dtype=np.float64).reshape(-1)
-    R = float(tree.R)
+    # the noise by caller row: a scalar nugget, or per-observation variances (then the leaves use diag(1 / r_o) for 1 / R)
+    R = np.broadcast_to(np.asarray(tree.R, dtype=np.float64), (len(yv),))
     n = topo.n_nodes
     # ---- pass 1: prior basis of EVERY row (a likelihood-only pass computes it at the observed rows only unless told otherwise)
     was_lik_rows = pl.get_option(P.MRA_OPT_LIK_ROWS)
@@ -186,12 +187,20 @@ def collect_node_blocks(tree, posterior: bool = True) -> List[NodeBlocks]:
                     ma, ra = int(topo.node_level[a]), topo.rank(a)
                     Bk.append(Wp[pr, coff[ma]:coff[ma] + ra] @ Lp[a][:ra, :ra].T)
                 Bk.append(nb.B)
-                nb.A = [[Bk[k][o].T @ Bk[l][o] / R for l in range(m + 1)] for k in range(m + 1)]
-                nb.omg = [Bk[k][o].T @ yo[o] / R for k in range(m + 1)]
+                if np.ndim(tree.R) == 0:
+                    R0 = float(tree.R)
+                    nb.A = [[Bk[k][o].T @ Bk[l][o] / R0 for l in range(m + 1)] for k in range(m + 1)]
+                    nb.omg = [Bk[k][o].T @ yo[o] / R0 for k in range(m + 1)]
+                    yRy = yo[o] @ yo[o] / R0
+                else:
+                    wo = 1.0 / R[topo.perm[pr][o]]                             # diag(r_o)^-1 in the place of 1 / R
+                    nb.A = [[(Bk[k][o].T * wo) @ Bk[l][o] for l in range(m + 1)] for k in range(m + 1)]
+                    nb.omg = [(Bk[k][o].T * wo) @ yo[o] for k in range(m + 1)]
+                    yRy = (yo[o] * wo) @ yo[o]
                 Amm = nb.A[m][m]
                 nb.kTil = np.linalg.inv(nb.kInv + Amm)
                 nb.BTil = nb.B
-                nb.u = float(-nb.omg[m] @ nb.kTil @ nb.omg[m] + yo[o] @ yo[o] / R)
+                nb.u = float(-nb.omg[m] @ nb.kTil @ nb.omg[m] + yRy)
             ev, V = np.linalg.eigh(0.5 * (nb.kTil + nb.kTil.T))            # MRANode.py:504-507
             nb.kTilC = V @ np.diag(np.sqrt(np.abs(ev)))
             nb.d = float(sub_d[i])

@@ -65,6 +65,7 @@ ERR_NAMES = {-1: "MRA_ERR_INVALID", -2: "MRA_ERR_HIP", -3: "MRA_ERR_NOT_SPD", -4
 # every symbol include/mra_hip.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "mra_device_count", "mra_release_cached_memory", "mra_plan_create", "mra_plan_destroy", "mra_plan_set_locs", "mra_plan_set_obs",
+    "mra_plan_set_noise", "mra_plan_set_noise_rows",
     "mra_plan_set_kernel", "mra_plan_set_locs_rows", "mra_plan_set_obs_rows", "mra_get_predict_rows", "mra_get_predict_rows_sd", "mra_eval_kernel", "mra_plan_set_cov_block", "mra_run", "mra_get_likelihood", "mra_get_predict",
     "mra_sample_slots", "mra_sample", "mra_solve", "mra_cov_apply", "mra_predict_sites", "mra_sites_cov", "mra_sample_sites_slots", "mra_sample_sites", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
     "mra_get_kernel_stats", "mra_get_kernel_work", "mra_get_route", "mra_device_synchronize", "mra_plan_info", "mra_comm_unique_id", "mra_comm_init",
@@ -115,6 +116,8 @@ def load_library():
         "mra_plan_destroy": (C.c_int, [vp]),
         "mra_plan_set_locs": (C.c_int, [vp, vp]),
         "mra_plan_set_obs": (C.c_int, [vp, vp, dbl]),
+        "mra_plan_set_noise": (C.c_int, [vp, vp]),
+        "mra_plan_set_noise_rows": (C.c_int, [vp, vp, vp]),
         "mra_plan_set_locs_rows": (C.c_int, [vp, vp, vp]),
         "mra_plan_set_obs_rows": (C.c_int, [vp, vp, vp, vp, dbl]),
         "mra_get_predict_rows": (C.c_int, [vp, vp, vp, i64, vp, vp]),
@@ -278,12 +281,43 @@ class HipPlan:
         src, _, _ = self._row_maps()
         self._check(self.lib.mra_plan_set_locs_rows(self._h, _ptr(X), _ptr(src)))
 
+    def _noise_rows(self, R):
+        r = np.ascontiguousarray(np.asarray(R, dtype=np.float64))
+        if r.ndim != 1:
+            raise ValueError("a noise array must be 1-D: only a diagonal R (per-observation variances) is supported")
+        if len(r) != self.topo.N:
+            raise ValueError("a noise vector must have N entries")
+        return r
+
     def set_obs(self, obs, R):
+        """obs: the caller's N values (NaN = missing).  R: the scalar nugget, or N per-observation noise variances in the caller's
+        order (read where obs is finite) - then the scalar that ``set_noise(None)`` returns to is their mean over the observed rows."""
         y = np.ascontiguousarray(np.asarray(obs, dtype=np.float64).reshape(-1))
         if len(y) != self.topo.N:
             raise ValueError("obs must have N entries")
         src, perm, _ = self._row_maps()
-        self._check(self.lib.mra_plan_set_obs_rows(self._h, _ptr(y), _ptr(src), _ptr(perm), float(R)))
+        if np.ndim(R) == 0:
+            self._check(self.lib.mra_plan_set_obs_rows(self._h, _ptr(y), _ptr(src), _ptr(perm), float(R)))
+            return
+        r = self._noise_rows(R)
+        in_leaf = np.zeros(len(y), dtype=bool)
+        in_leaf[perm[(perm >= 0) & (self._row_maps()[2] != 0)]] = True
+        ro = r[np.isfinite(y) & in_leaf]                                # the rows the plan observes
+        if not (np.all(np.isfinite(ro)) and np.all(ro >= 0.0)):          # before the plan changes
+            raise ValueError("the noise variance of an observed row is negative or not finite")
+        scalar = float(ro.mean()) if ro.size and ro.mean() > 0.0 else 1.0
+        self._check(self.lib.mra_plan_set_obs_rows(self._h, _ptr(y), _ptr(src), _ptr(perm), scalar))
+        self._check(self.lib.mra_plan_set_noise_rows(self._h, _ptr(r), _ptr(src)))
+
+    def set_noise(self, R):
+        """Per-observation noise variances (mra_plan_set_noise): N values in the caller's order, read at the observed rows of the
+        last ``set_obs``; None returns to that call's scalar.  y, the mask and the options stay."""
+        if R is None:
+            self._check(self.lib.mra_plan_set_noise(self._h, None))
+            return
+        r = self._noise_rows(R)
+        src, _, _ = self._row_maps()
+        self._check(self.lib.mra_plan_set_noise_rows(self._h, _ptr(r), _ptr(src)))
 
     def set_kernel(self, kind, l, sig=1.0, scale=1.0, circular=False):
         par = np.array([l, sig, scale, 1.0 if circular else 0.0], dtype=np.float64)
