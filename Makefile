@@ -3,8 +3,8 @@
 # and the dispatchers of the heavily templated kernels (mra_launch_*.hip), so that `make -j8 lib` takes ~1 min instead of 2.5.
 HIPCC ?= /opt/rocm/bin/hipcc
 CSRC   = pymra_amd/csrc
-UNITS  = mra_plan mra_launch_gemm mra_launch_pred mra_launch_prior_row1 mra_launch_prior_row2 mra_launch_prior_knot1 mra_launch_prior_knot2 mra_launch_solve mra_launch_cov mra_launch_sites
-HDRS   = $(CSRC)/mra_kernels.h $(CSRC)/mra_plan_types.h $(CSRC)/mra_launch_prior.inc $(CSRC)/mra_solve_kernels.h $(CSRC)/mra_cov_kernels.h $(CSRC)/mra_site_kernels.h include/mra_hip.h
+UNITS  = mra_plan mra_launch_gemm mra_launch_pred mra_launch_prior_row1 mra_launch_prior_row2 mra_launch_prior_knot1 mra_launch_prior_knot2 mra_launch_solve mra_launch_cov mra_launch_sites mra_launch_laplace
+HDRS   = $(CSRC)/mra_kernels.h $(CSRC)/mra_plan_types.h $(CSRC)/mra_launch_prior.inc $(CSRC)/mra_solve_kernels.h $(CSRC)/mra_cov_kernels.h $(CSRC)/mra_site_kernels.h $(CSRC)/mra_laplace_kernels.h include/mra_hip.h
 CFLAGS = --offload-arch=gfx950 -std=c++17 -fPIC -Wno-unused-value -Wno-unused-result -Wno-pass-failed
 B      = build
 

@@ -110,6 +110,35 @@ int mra_plan_set_obs(mra_plan *plan, const double *y_perm, double R);
 int mra_plan_set_noise(mra_plan *plan, const double *r_perm);
 int mra_plan_set_noise_rows(mra_plan *plan, const double *r, const int64_t *src);
 
+/* Non-Gaussian data by a Laplace approximation (no counterpart in the reference, whose observations are Gaussian): the posterior
+ * mode of x given z_p ~ p(. | eta_p), eta_p = x(s_p) + offset_p at the rows the plan observes, found by Newton / IRLS on the device.
+ *   MRA_FAMILY_GAUSSIAN  N(eta, aux):              g = (z - eta) / aux,  D = 1 / aux,        start x0 = z - offset
+ *   MRA_FAMILY_POISSON   Poisson(e^eta):           g = z - e^eta,        D = e^eta,          start x0 = log(z + 1/2) - offset
+ *   MRA_FAMILY_BINOMIAL  Bin(aux, logistic(eta)):  g = z - aux p,        D = aux p (1 - p),  start x0 = log((z + 1/2) / (aux - z + 1/2)) - offset
+ * (g = d log p / d eta, D = -d2 log p / d eta2, floored at 2^-40).  One iteration from x: t_p = x_p + g_p / D_p and r_p = 1 / D_p go
+ * into the plan's y and noise at the observed rows (one launch), one likelihood + predict pass gives x^ = its mean there, and
+ * step = max |x^ - x| (two launches, a fixed number of partial results in a fixed order: the same inputs give the same bits).  The
+ * call stops after the pass with step <= tol * max(1, max |x^|), or after max_iter passes (MRA_OK, info[7] = 0).  Plain Newton: no
+ * damping, no step control.  The Gaussian family's t = z - offset and r = aux do not depend on x: its second pass repeats the first.
+ * z_perm, aux_perm, offset_perm, x0_perm: P values each, padded leaf order.  z must be finite exactly where the plan observes (the mask
+ * is that of the last mra_plan_set_obs: the call builds no leaf lists and keeps every option; rows outside every leaf are nobody's and
+ * are not read).  aux_perm may be NULL for Poisson; offset_perm NULL: 0; x0_perm NULL: the start of the table.
+ * info[8]: [0] d = log|Sigma + D^-1| and [1] u = t^T (Sigma + D^-1)^-1 t of the last pass; [2] -2 sum log p(z_p | eta^_p), every
+ * normalising constant included; [3] sum log D_p; [4] sum D_p (t_p - x^_p)^2 ([3], [4]: D and t of the last pass); [5] passes run;
+ * [6] the last step; [7] converged, 1 or 0.  -2 log q(z) of the Laplace approximation is [0] + [1] + [2] + [3] - [4].
+ * MRA_ERR_STATE without set_locs, set_obs and set_kernel.  MRA_ERR_INVALID, checked on the host in this order before anything
+ * changes: an unknown family; a mask that differs from the plan's; at an observed row z < 0 (the two count families), (binomial) aux < z or aux <= 0,
+ * (Gaussian) aux <= 0, a non-finite aux, offset or x0 where one is read; max_iter < 1; tol not > 0; NULL z or info; a sharded plan.
+ * A pass's MRA_ERR_NOT_SPD propagates.  Afterwards the plan is a plan after mra_plan_set_obs(t) + mra_plan_set_noise(r) +
+ * mra_run(LIKELIHOOD | PREDICT): mra_get_likelihood / mra_get_predict give the last pass, mra_get_buffer(10) gives r, and the calls on
+ * the retained factors serve the Laplace posterior N(x^, (Sigma^-1 + D)^-1) (they factorise once first).  The next mra_plan_set_obs
+ * returns the plan to the Gaussian model.  Works on MRA_KERNEL_HOST plans. */
+#define MRA_FAMILY_GAUSSIAN 0
+#define MRA_FAMILY_POISSON  1
+#define MRA_FAMILY_BINOMIAL 2
+int mra_plan_fit_laplace(mra_plan *plan, int family, const double *z_perm, const double *aux_perm, const double *offset_perm,
+                         const double *x0_perm, int max_iter, double tol, double *info);
+
 /* Replaces: the `cov` callable when it is one of pyMRA's stationary kernels
  * (pyMRA/MRATools.py:256-301).  params = {l, sig, scale[, circular]}; value = scale * k(D; l, sig);
  * circular != 0 (1-D only): D = min(|a-b|, 1-|a-b|), the torus branch of dist() (MRATools.py:232-239).
@@ -298,6 +327,8 @@ int mra_sample_sites(mra_plan *plan, uint32_t flags, int64_t n_sites, const doub
  * sweeps, uploads, downloads);
  * 10: the noise variance by padded row (P values): the vector of mra_plan_set_noise at observed rows and 0 elsewhere, or the scalar R
  * at every row when no vector is set;
+ * 11: the observations y by padded row as the device holds them (P values, NaN where nothing is observed): what the last
+ * mra_plan_set_obs uploaded, or the pseudo-observations t of the last pass of mra_plan_fit_laplace;
  * copies min(capacity, available) doubles into out, returns the available count in *n_avail.
  * (W after a likelihood-only run is complete only with MRA_OPT_LIK_ROWS off: by default such a run computes W at the rows a
  * likelihood needs - the observed rows, and the knots on the level-by-level path - and leaves the others as they were.) */

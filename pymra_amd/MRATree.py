@@ -459,3 +459,28 @@ class MRATree(object):
         mean, var, self._sd = self.plan.predict(with_sd=True) if want_predict else (None, None, None)
         self.root = RootView(d, u, mean, var, len(self.locs), self.topology, np.asarray(self.locs, dtype=np.float64), self.kernel)
         return self.getLikelihood()
+
+    def fitLaplace(self, family, aux=None, offset=None, z=None, x0=None, cov=None, max_iter=50, tol=1e-10):
+        """Fit non-Gaussian data on this tree by a Laplace approximation (``HipPlan.fit_laplace``): family "gaussian" (variance
+        ``aux``), "poisson" (``offset`` = log exposure) or "binomial" (``aux`` trials), eta = x + offset.  z: N values, finite
+        exactly where this tree observes (default: the tree's ``obs``).  cov: other parameters of a device kernel, set without a
+        pass of its own (MLE loops).  x0: the start; default the mean of the previous fit when there is one (a warm start), else the
+        data-based start.  Updates ``root`` and ``predict()`` to the Laplace posterior N(x^, (Sigma^-1 + D)^-1), keeps the numbers
+        of the fit in ``self.laplace`` and returns -2 log q(z); ``getLikelihood()`` keeps its meaning, d + u of the last pass."""
+        if cov is not None:
+            spec = probe_cov(cov, self.d, np.asarray(self.locs, dtype=np.float64))
+            if spec is None:
+                raise NotImplementedError("cov must be a device kernel")
+            self.kernel = spec
+            self.plan.set_kernel(spec.kind, spec.l, spec.sig, spec.scale, spec.circular)
+        if z is None:
+            z = self.obs
+        if x0 is None:
+            x0 = getattr(self, "_laplace_mean", None)
+        self._node_blocks = {}
+        res = self.plan.fit_laplace(family, z, aux=aux, offset=offset, x0=x0, max_iter=max_iter, tol=tol)
+        mean, var, self._sd = self.plan.predict(with_sd=True)
+        self._laplace_mean = mean.copy() if res["converged"] else None      # (a fit that did not converge is no start for the next)
+        self.laplace = res
+        self.root = RootView(res["d"], res["u"], mean, var, len(self.locs), self.topology, np.asarray(self.locs, dtype=np.float64), self.kernel)
+        return res["lik"]

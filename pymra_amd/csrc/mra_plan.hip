@@ -2203,7 +2203,8 @@ static void run_predict(mra_plan* pl) {
 }
 
 // ---- the end of a pass ------------------------------------------------------------------------------------------------------------
-// leaves the 32-byte record {d, u, log-det carried by the reduce level, error flag} in pinned host memory - written by the kernel
+// leaves the record {d, u, log-det carried by the reduce level, error flag} in pinned host memory (MRA_HOST_RES_DOUBLES doubles: the
+// reduction of mra_plan_fit_laplace writes its five behind them) - written by the kernel
 // straight into it: no copy command, no gap after the last launch - and with extract_mean the mean out of W's y block
 static void launch_result(mra_plan* pl) {
     KTimer kt(pl, KF_MISC, 0);
@@ -2220,7 +2221,7 @@ static void launch_result(mra_plan* pl) {
         if (lr.F.n) below = lr.F.p + (lr.F.n - 16);
     }
     if (!pl->host_res) {
-        HIP_TRY(hipHostMalloc((void**)&pl->host_res, 4 * sizeof(double), hipHostMallocMapped));
+        HIP_TRY(hipHostMalloc((void**)&pl->host_res, MRA_HOST_RES_DOUBLES * sizeof(double), hipHostMallocMapped));
         HIP_TRY(hipHostGetDevicePointer((void**)&pl->host_res_dev, pl->host_res, 0));
     }
     hipLaunchKernelGGL(k_sum_dnode, dim3(1), dim3(256), 0, pl->stream, pl->dnode.p, nsum, pl->host_res_dev, up, below, pl->errflag.p);
@@ -2262,6 +2263,7 @@ static void close_pass(mra_plan* pl, int errv) {
 static void finish_run(mra_plan* pl) {
     launch_result(pl);
     phase_mark(pl, 5);
+    if (pl->pass_tail) pl->pass_tail();      // (mra_plan_fit_laplace's reduction: behind the pass's last kernel, under its one synchronisation)
     HIP_TRY(hipStreamSynchronize(pl->stream));
     HIP_TRY(hipGetLastError());
     const int errv = (int)pl->host_res[3];
@@ -3255,6 +3257,117 @@ static void set_noise(mra_plan* pl, const double* r) {
     pl->noise_on = true;
 }
 
+// ---- Laplace fit (mra_plan_fit_laplace) ---------------------------------------------------------------------
+// Newton / IRLS for the mode of x given non-Gaussian data: every iteration is one likelihood + predict pass on the pseudo-observations
+// t = x + g / D with noise r = 1 / D, which one launch writes into the plan's y / noise / noise_sd; the step and the sums of the
+// result come from one reduction (two launches) after the pass.  Every argument is checked before anything changes.
+static inline double lgamma_of(double v) { int sign; return lgamma_r(v, &sign); }      // (std::lgamma writes the global signgam: not for threads)
+static void fit_laplace(mra_plan* pl, int family, const double* z, const double* aux, const double* off, const double* x0, int max_iter,
+                        double tol, double* info) {
+    const char* who = "mra_plan_fit_laplace";
+    char m[200];
+    auto invalid = [&](const char* what, long p) {
+        if (p >= 0) snprintf(m, sizeof m, "%s: %s (padded row %ld)", who, what, p); else snprintf(m, sizeof m, "%s: %s", who, what);
+        throw MraError(MRA_ERR_INVALID, m);
+    };
+    if (!(pl->have_locs && pl->have_obs && pl->have_kernel)) { snprintf(m, sizeof m, "%s needs set_locs, set_obs and set_kernel first", who); throw MraError(MRA_ERR_STATE, m); }
+    if (family != MRA_FAMILY_GAUSSIAN && family != MRA_FAMILY_POISSON && family != MRA_FAMILY_BINOMIAL) invalid("unknown family", -1);
+    const long P = pl->P;
+    const bool need_aux = family != MRA_FAMILY_POISSON;
+    const bool readable = z && info && (aux || !need_aux);
+    // observed: a finite y inside a leaf, as mra_plan_set_noise reads it (rows outside every leaf are nobody's)
+    std::vector<unsigned char> seen((size_t)P, 0);
+    for (size_t t = 0; t < pl->leaf_nodes.size(); ++t)
+        for (long p = pl->row0[pl->leaf_nodes[t]]; p < pl->row1[pl->leaf_nodes[t]]; ++p) seen[p] = pl->y_finite_host[p];
+    if (readable) {
+        for (size_t t = 0; t < pl->leaf_nodes.size(); ++t)
+            for (long p = pl->row0[pl->leaf_nodes[t]]; p < pl->row1[pl->leaf_nodes[t]]; ++p)
+                if ((std::isfinite(z[p]) ? 1 : 0) != seen[p]) invalid("z is not finite exactly where the plan observes: the mask is that of the last mra_plan_set_obs", p);
+        if (family != MRA_FAMILY_GAUSSIAN)
+            for (long p = 0; p < P; ++p) if (seen[p] && z[p] < 0.0) invalid("z < 0 at an observed row (a count)", p);
+        if (family == MRA_FAMILY_BINOMIAL)
+            for (long p = 0; p < P; ++p) if (seen[p] && (aux[p] < z[p] || aux[p] <= 0.0)) invalid("binomial trials aux < z or aux <= 0 at an observed row", p);
+        if (family == MRA_FAMILY_GAUSSIAN)
+            for (long p = 0; p < P; ++p) if (seen[p] && aux[p] <= 0.0) invalid("Gaussian variance aux <= 0 at an observed row", p);
+        for (long p = 0; p < P; ++p) {
+            if (!seen[p]) continue;
+            if (need_aux && !std::isfinite(aux[p])) invalid("aux is not finite at an observed row", p);
+            if (off && !std::isfinite(off[p])) invalid("offset is not finite at an observed row", p);
+            if (x0 && !std::isfinite(x0[p])) invalid("x0 is not finite at an observed row", p);
+        }
+    }
+    if (max_iter < 1) invalid("max_iter < 1", -1);
+    if (!(tol > 0.0)) invalid("tol must be greater than 0", -1);
+    if (!readable) invalid(!z || !info ? "z or info is NULL" : "aux is NULL (only the Poisson family reads none)", -1);
+    if (pl->reduce_level >= 0 || pl->comm || pl->n_ranks > 1) invalid("sharded plans cannot iterate (the mean of a pass lives on its rank)", -1);
+    if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
+
+    // the data by padded row (z: NaN where the plan does not observe), the start, and the constants of -2 log p that do not depend on x
+    std::vector<double> zh((size_t)P, std::nan("")), ah((size_t)P, 1.0), oh((size_t)P, 0.0), xh((size_t)P, 0.0);
+    // (chunks of 65536 rows over a few host threads; the chunks' sums are added in chunk order, whatever the number of threads)
+    const long CH = 65536, nch = (P + CH - 1) / CH;
+    std::vector<double> kpart((size_t)nch, 0.0);
+    parallel_rows(nch, [&](int64_t c0, int64_t c1) {
+        for (int64_t c = c0; c < c1; ++c) {
+            double k = 0.0;
+            for (long p = c * CH; p < std::min<long>(P, (c + 1) * CH); ++p) {
+                if (!seen[p]) continue;
+                const double zp = z[p], a = need_aux ? aux[p] : 1.0, o = off ? off[p] : 0.0;
+                zh[p] = zp; ah[p] = a; oh[p] = o;
+                if (family == MRA_FAMILY_POISSON) {
+                    k += 2.0 * lgamma_of(zp + 1.0);
+                    xh[p] = std::log(zp + 0.5) - o;
+                } else if (family == MRA_FAMILY_BINOMIAL) {
+                    k -= 2.0 * (lgamma_of(a + 1.0) - lgamma_of(zp + 1.0) - lgamma_of(a - zp + 1.0));
+                    xh[p] = std::log((zp + 0.5) / (a - zp + 0.5)) - o;
+                } else {
+                    k += std::log(6.283185307179586 * a);
+                    xh[p] = zp - o;
+                }
+                if (x0) xh[p] = x0[p];
+            }
+            kpart[(size_t)c] = k;
+        }
+    }, 1);
+    double konst = 0.0;
+    for (long c = 0; c < nch; ++c) konst += kpart[(size_t)c];
+    HIP_TRY(mraSetDevice(pl->device));
+    mra_laplace_reserve(pl);
+    mra_plan::Laplace& L = pl->lap;
+    const size_t bytes = (size_t)P * sizeof(double);
+    HIP_TRY(mraMemcpy(L.z.p, zh.data(), bytes, hipMemcpyHostToDevice));
+    HIP_TRY(mraMemcpy(L.aux.p, ah.data(), bytes, hipMemcpyHostToDevice));
+    HIP_TRY(mraMemcpy(L.off.p, oh.data(), bytes, hipMemcpyHostToDevice));
+    HIP_TRY(mraMemcpy(L.x.p, xh.data(), bytes, hipMemcpyHostToDevice));
+    pl->slv.valid = false;
+    if (!pl->noise_on) set_leaf_diag_add(pl, 0.0);      // the noise vector goes on as in mra_plan_set_noise; every pass below rewrites it
+    pl->noise_on = true;
+    pl->noise_host.assign((size_t)P, 0.0);
+
+    double res[MRA_LAPLACE_NRES] = {0, 0, 0, 0, 0};
+    int passes = 0;
+    bool converged = false;
+    // the host mirror of the noise follows the device, whatever ends the loop (a pass that fails leaves its own r in the plan)
+    auto mirror = [&] { return mraMemcpy(pl->noise_host.data(), pl->noise.p, bytes, hipMemcpyDeviceToHost); };
+    // the reduction rides behind every pass's last kernel (finish_run), so that an iteration synchronises once
+    struct TailGuard { mra_plan* pl; ~TailGuard() { pl->pass_tail = nullptr; } } guard{pl};
+    pl->pass_tail = [&] { KTimer kt(pl, KF_MISC, 0); mra_laplace_reduce(pl, family, pl->host_res_dev + MRA_HOST_RES_LAPLACE); };
+    try {
+        for (int it = 0; it < max_iter && !converged; ++it) {
+            { KTimer kt(pl, KF_MISC, 0); mra_laplace_linearise(pl, family, it ? pl->mean.p : L.x.p); }
+            run_all(pl, MRA_RUN_LIKELIHOOD | MRA_RUN_PREDICT);
+            ++passes;
+            std::copy(pl->host_res + MRA_HOST_RES_LAPLACE, pl->host_res + MRA_HOST_RES_LAPLACE + MRA_LAPLACE_NRES, res);
+            converged = res[0] <= tol * std::max(1.0, res[1]);
+        }
+    } catch (...) { hipStreamSynchronize(pl->stream); mirror(); throw; }
+    HIP_TRY(mirror());
+    info[0] = pl->res_d; info[1] = pl->res_u;
+    info[2] = -2.0 * res[4] + konst;
+    info[3] = res[2]; info[4] = res[3];
+    info[5] = passes; info[6] = res[0]; info[7] = converged ? 1.0 : 0.0;
+}
+
 static void get_predict(mra_plan* pl, double* mean, double* var) {
     if (!pl->ran || !(pl->run_flags & MRA_RUN_PREDICT)) throw MraError(MRA_ERR_STATE, "mra_run with MRA_RUN_PREDICT has not completed");
     HIP_TRY(mraSetDevice(pl->device));
@@ -3511,6 +3624,15 @@ int mra_plan_set_noise_rows(mra_plan* pl, const double* r, const int64_t* src) {
     });
 }
 
+int mra_plan_fit_laplace(mra_plan* pl, int family, const double* z_perm, const double* aux_perm, const double* offset_perm, const double* x0_perm,
+                         int max_iter, double tol, double* info) {
+    return guarded(pl, [&] {
+        require(pl, "mra_plan_fit_laplace: plan is NULL");
+        fit_laplace(pl, family, z_perm, aux_perm, offset_perm, x0_perm, max_iter, tol, info);
+        return MRA_OK;
+    });
+}
+
 int mra_plan_set_kernel(mra_plan* pl, int kind, const double* params, int n) {
     return guarded(pl, [&] {
         require(pl, "mra_plan_set_kernel: plan is NULL");
@@ -3703,6 +3825,7 @@ int mra_get_buffer(mra_plan* pl, int what, double* out, int64_t cap, int64_t* n_
         else if (what == 5) { src = pl->kstamps.p; n = (int64_t)pl->kstamps.n; }   // same, knot chain
         else if (what == 6) { src = pl->kstamps2.p; n = (int64_t)pl->kstamps2.n; } // same, fused leaf solve + update
         else if (what == 4) { src = pl->tstamps.p; n = (int64_t)pl->tstamps.n; }   // same, leaf row solves   // same, predictive cascade
+        else if (what == 11) { src = pl->y.p; n = pl->P; }                         // the observations as the device holds them (the pseudo-observations t after mra_plan_fit_laplace)
         else throw MraError(MRA_ERR_INVALID, "unknown buffer id");
         *n_avail = n;
         if (out && cap > 0) HIP_TRY(mraMemcpy(out, src, (size_t)std::min(cap, n) * sizeof(double), hipMemcpyDeviceToHost));

@@ -353,7 +353,7 @@ struct mra_plan {
     int reduce_level = -1;
     // device data
     DevVec<double> X, y, W, var, mean, dnode, scal, covsrc, covdiag, stamps, pstamps, tstamps, kstamps, kstamps2;
-    double* host_res = nullptr;      // pinned, device-mapped {d, u, below, err} record of the last pass
+    double* host_res = nullptr;      // pinned, device-mapped {d, u, below, err} record of the last pass; from MRA_HOST_RES_LAPLACE on the reduction of mra_plan_fit_laplace
     double* host_res_dev = nullptr;  // the same memory as the device sees it
     DevVec<int> errflag, knot_idx, row_leaf;
     DevVec<long> knots_dev;
@@ -586,11 +586,17 @@ struct mra_plan {
         DevVec<double> zc, zcin, zl, zin, dout;   // Kn x16 non-leaf draws (and the caller's, 16 x Kn); [tile][16] x16 leaf draws (and the caller's); 16 x [tile][16] results
         double draw_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // stream ms of the last mra_sample_sites: basis, leaf, chain, leaf Gram, leaf Cholesky, draw, mean (+ sweeps), uploads, downloads
     } sit;
+    // Laplace fit (mra_plan_fit_laplace): the data of the call by padded row (z: NaN at rows the plan does not
+    // observe), the linearisation point of the running pass, and the reduction's partial results.  Allocated by the first call.
+    struct Laplace {
+        DevVec<double> z, aux, off, x, part;
+    } lap;
     // comm
     void* rccl = nullptr;
     ncclComm_t comm = nullptr;
     ncclResult_t (*allreduce)(const void*, void*, size_t, ncclDataType_t, ncclRedOp_t, ncclComm_t, hipStream_t) = nullptr;
     int n_ranks = 1, rank = 0;
+    std::function<void()> pass_tail;     // launches behind the last kernel of a pass, before its one synchronisation (set by mra_plan_fit_laplace for its call)
     bool pass_open = false;              // a pass was started and has not reached finish_run (error or abandoned split)
     // kernels whose dynamic-LDS limit was raised for THIS plan's device (the attribute is per device, a plan lives on one)
     std::set<const void*> big_lds_done;
@@ -683,5 +689,14 @@ void mra_sites_draw_reserve(mra_plan* pl, long n_tiles, size_t g_doubles, long n
 void mra_sites_leaf_gram(mra_plan* pl, long n_tiles, int nt_max, bool posterior);
 void mra_sites_zeta(mra_plan* pl, long n_tiles, const SampleZ& zs, long n_coarse, bool from_caller);
 void mra_sites_draw(mra_plan* pl, long n_tiles, bool posterior);
+// mra_launch_laplace.hip: the work buffers of mra_plan_fit_laplace (and the plan's noise / noise_sd); one linearisation at x_in (lap.x
+// itself, or the mean of the last pass) -> y, noise, noise_sd, lap.x; the reduction after a pass -> res[MRA_LAPLACE_NRES] = {step,
+// max |x^|, sum log D, sum D (t - x^)^2, sum of the x-dependent part of log p}, res a device-visible pointer (the plan's pinned record).
+// Launches only, on pl->stream.
+constexpr int MRA_LAPLACE_NRES = 5;
+constexpr int MRA_HOST_RES_DOUBLES = 16, MRA_HOST_RES_LAPLACE = 8;      // the pinned result record of a pass (mra_plan::host_res)
+void mra_laplace_reserve(mra_plan* pl);
+void mra_laplace_linearise(mra_plan* pl, int family, const double* x_in);
+void mra_laplace_reduce(mra_plan* pl, int family, double* res);
 // with MRA_OPT_KERNEL_TIMING: `work` between two events on pl->stream, the time added to sit.ms[which] (sit.ms_sink[which] when set; one synchronisation each: a measuring mode)
 void mra_sites_timed(mra_plan* pl, int which, const std::function<void()>& work);

@@ -40,6 +40,9 @@ MRA_OPT_SAMPLE_SOLVE = 20
 MRA_OPT_SITES_CHUNK_BYTES = 21
 MRA_OPT_LEAF_ORDER = 22
 MRA_OPT_PARENT_PAIR = 23
+MRA_FAMILY_GAUSSIAN, MRA_FAMILY_POISSON, MRA_FAMILY_BINOMIAL = 0, 1, 2
+LAPLACE_FAMILIES = {"gaussian": MRA_FAMILY_GAUSSIAN, "poisson": MRA_FAMILY_POISSON, "binomial": MRA_FAMILY_BINOMIAL}
+LAPLACE_INFO = ("d", "u", "neg2logp", "sum_log_D", "sum_D_res2", "passes", "step", "converged")      # info[8] of mra_plan_fit_laplace
 MRA_SAMPLE_CONDITIONAL = 1
 MRA_COV_POSTERIOR = 1
 MRA_SITES_COV_MAX = 16384
@@ -65,7 +68,7 @@ ERR_NAMES = {-1: "MRA_ERR_INVALID", -2: "MRA_ERR_HIP", -3: "MRA_ERR_NOT_SPD", -4
 # every symbol include/mra_hip.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "mra_device_count", "mra_release_cached_memory", "mra_plan_create", "mra_plan_destroy", "mra_plan_set_locs", "mra_plan_set_obs",
-    "mra_plan_set_noise", "mra_plan_set_noise_rows",
+    "mra_plan_set_noise", "mra_plan_set_noise_rows", "mra_plan_fit_laplace",
     "mra_plan_set_kernel", "mra_plan_set_locs_rows", "mra_plan_set_obs_rows", "mra_get_predict_rows", "mra_get_predict_rows_sd", "mra_eval_kernel", "mra_plan_set_cov_block", "mra_run", "mra_get_likelihood", "mra_get_predict",
     "mra_sample_slots", "mra_sample", "mra_solve", "mra_cov_apply", "mra_predict_sites", "mra_sites_cov", "mra_sample_sites_slots", "mra_sample_sites", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
     "mra_get_kernel_stats", "mra_get_kernel_work", "mra_get_route", "mra_device_synchronize", "mra_plan_info", "mra_comm_unique_id", "mra_comm_init",
@@ -118,6 +121,7 @@ def load_library():
         "mra_plan_set_obs": (C.c_int, [vp, vp, dbl]),
         "mra_plan_set_noise": (C.c_int, [vp, vp]),
         "mra_plan_set_noise_rows": (C.c_int, [vp, vp, vp]),
+        "mra_plan_fit_laplace": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, dbl, vp]),
         "mra_plan_set_locs_rows": (C.c_int, [vp, vp, vp]),
         "mra_plan_set_obs_rows": (C.c_int, [vp, vp, vp, vp, dbl]),
         "mra_get_predict_rows": (C.c_int, [vp, vp, vp, i64, vp, vp]),
@@ -318,6 +322,37 @@ class HipPlan:
         r = self._noise_rows(R)
         src, _, _ = self._row_maps()
         self._check(self.lib.mra_plan_set_noise_rows(self._h, _ptr(r), _ptr(src)))
+
+    def _padded(self, a, name):
+        """The caller's N values in padded leaf order (NaN at the padding rows), or None."""
+        if a is None:
+            return None
+        v = np.asarray(a, dtype=np.float64).reshape(-1)
+        if len(v) != self.topo.N:
+            raise ValueError("%s must have N entries" % name)
+        src, perm, _ = self._row_maps()
+        return np.ascontiguousarray(np.where(perm >= 0, v[src], np.nan))
+
+    def fit_laplace(self, family, z, aux=None, offset=None, x0=None, max_iter=50, tol=1e-10):
+        """Non-Gaussian data by a Laplace approximation (include/mra_hip.h, mra_plan_fit_laplace): Newton / IRLS on the device for the
+        mode of x given z ~ ``family`` ("gaussian": N(eta, aux); "poisson": Poisson(e^eta); "binomial": Bin(aux, logistic eta)),
+        eta = x + offset.  z, aux, offset, x0: the caller's N values; z finite exactly where the last ``set_obs`` observes (the mask
+        is the plan's).  A scalar aux or offset holds at every row.  -> dict with d, u, neg2logp, sum_log_D, sum_D_res2, passes,
+        step, converged and lik = -2 log q(z) = d + u + neg2logp + sum_log_D - sum_D_res2.  Afterwards the plan holds y = t and
+        noise = 1 / D of the last pass: likelihood(), predict() and the calls on the retained factors serve the Laplace posterior."""
+        fam = LAPLACE_FAMILIES.get(family, family) if isinstance(family, str) else family
+        if isinstance(fam, str):
+            raise ValueError("family must be one of %s" % sorted(LAPLACE_FAMILIES))
+        full = lambda a: None if a is None else (np.full(self.topo.N, float(a)) if np.ndim(a) == 0 else a)
+        zp, ap, op, xp = (self._padded(z, "z"), self._padded(full(aux), "aux"), self._padded(full(offset), "offset"), self._padded(x0, "x0"))
+        info = np.zeros(8)
+        opt = lambda a: None if a is None else _ptr(a)
+        self._check(self.lib.mra_plan_fit_laplace(self._h, int(fam), opt(zp), opt(ap), opt(op), opt(xp), int(max_iter), float(tol), _ptr(info)))
+        res = dict(zip(LAPLACE_INFO, info.tolist()))
+        res["passes"], res["converged"] = int(res["passes"]), bool(res["converged"])
+        res["info"] = info
+        res["lik"] = info[0] + info[1] + info[2] + info[3] - info[4]
+        return res
 
     def set_kernel(self, kind, l, sig=1.0, scale=1.0, circular=False):
         par = np.array([l, sig, scale, 1.0 if circular else 0.0], dtype=np.float64)
