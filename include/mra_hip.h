@@ -129,7 +129,12 @@ int mra_plan_set_noise_rows(mra_plan *plan, const double *r, const int64_t *src)
  * MRA_ERR_STATE without set_locs, set_obs and set_kernel.  MRA_ERR_INVALID, checked on the host in this order before anything
  * changes: an unknown family; a mask that differs from the plan's; at an observed row z < 0 (the two count families), (binomial) aux < z or aux <= 0,
  * (Gaussian) aux <= 0, a non-finite aux, offset or x0 where one is read; max_iter < 1; tol not > 0; NULL z or info; a sharded plan.
- * A pass's MRA_ERR_NOT_SPD propagates.  Afterwards the plan is a plan after mra_plan_set_obs(t) + mra_plan_set_noise(r) +
+ * A pass's MRA_ERR_NOT_SPD propagates, with that pass's r in the plan.  An iterate that leaves the doubles (e^eta = inf: t = NaN,
+ * r = 0; undamped Newton from a poor start on counts in the thousands gets there) never comes back as converged: a pass reads a NaN y
+ * as 0, and r = 0 at a row that is a knot of a node above the leaves has no positive pivot, so such a pass is as a rule refused
+ * MRA_ERR_NOT_SPD - the same holds for any r below the rounding of that pivot, about 1e-16 of the prior variance (a Poisson mean
+ * near 1e16) - and a pass that does come back with a step that is NaN or inf ends the call: MRA_OK, info[5] = the passes including
+ * it, info[6] = that step, info[7] = 0.  Afterwards the plan is a plan after mra_plan_set_obs(t) + mra_plan_set_noise(r) +
  * mra_run(LIKELIHOOD | PREDICT): mra_get_likelihood / mra_get_predict give the last pass, mra_get_buffer(10) gives r, and the calls on
  * the retained factors serve the Laplace posterior N(x^, (Sigma^-1 + D)^-1) (they factorise once first).  The next mra_plan_set_obs
  * returns the plan to the Gaussian model.  Works on MRA_KERNEL_HOST plans. */

@@ -12,6 +12,9 @@ static const int LAPLACE_NRES = 5;          // step, max |x^|, sum log D, sum D 
 
 struct LaplaceTerm { double g, D, logp; };
 
+// max(a, b) over values >= 0 that keeps a NaN from either side (fmax drops it): a NaN step must reach the host, which stops on it
+__device__ __forceinline__ double laplace_max(double a, double b) { return (b > a || b != b) ? b : a; }
+
 // g, D (floored) and the part of log p(z | eta) that depends on eta.  Gaussian: -(z - eta)^2 / (2 aux); Poisson: z eta - e^eta;
 // binomial: z eta - aux log(1 + e^eta), with p and 1 - p from e^-|eta| so that neither saturates.
 __device__ __forceinline__ LaplaceTerm laplace_term(int family, double z, double aux, double eta) {
@@ -59,7 +62,8 @@ __global__ __launch_bounds__(256) void k_laplace_linearise(int family, const dou
 
 // After the pass: with x^ = mean at the observed rows, per workgroup {max |x^ - x|, max |x^|, sum log D, sum D (t - x^)^2, sum of the
 // x-dependent part of log p(z | x^ + offset)}, D = 1 / noise and t = y of the pass.  A thread walks its rows in order, the workgroup
-// folds its 256 values in a fixed tree: the same inputs give the same bits.
+// folds its 256 values in a fixed tree: the same inputs give the same bits.  The two maxima keep a NaN (laplace_max): a mean that is
+// not finite at an observed row gives a step that is not finite.
 __global__ __launch_bounds__(256) void k_laplace_part(int family, const double* __restrict__ z, const double* __restrict__ aux,
                                                       const double* __restrict__ off, const double* __restrict__ x_keep,
                                                       const double* __restrict__ mean, const double* __restrict__ y,
@@ -70,8 +74,8 @@ __global__ __launch_bounds__(256) void k_laplace_part(int family, const double* 
         const double zp = z[p];
         if (!(fabs(zp) < __builtin_inf())) continue;
         const double xh = mean[p], D = 1.0 / noise[p], dt = y[p] - xh;
-        v[0] = fmax(v[0], fabs(xh - x_keep[p]));
-        v[1] = fmax(v[1], fabs(xh));
+        v[0] = laplace_max(v[0], fabs(xh - x_keep[p]));
+        v[1] = laplace_max(v[1], fabs(xh));
         v[2] += log(D);
         v[3] += D * dt * dt;
         v[4] += laplace_term(family, zp, aux[p], xh + off[p]).logp;
@@ -84,7 +88,7 @@ __global__ __launch_bounds__(256) void k_laplace_part(int family, const double* 
 #pragma unroll
             for (int k = 0; k < LAPLACE_NRES; ++k) {
                 const double a = sh[k][threadIdx.x], b = sh[k][threadIdx.x + w];
-                sh[k][threadIdx.x] = k < 2 ? fmax(a, b) : a + b;
+                sh[k][threadIdx.x] = k < 2 ? laplace_max(a, b) : a + b;
             }
         }
         __syncthreads();
@@ -99,14 +103,14 @@ __global__ __launch_bounds__(64 * LAPLACE_NRES) void k_laplace_sum(const double*
     double acc = 0.0;
     for (int b = lane; b < nblk; b += 64) {
         const double a = part[(long)b * LAPLACE_NRES + k];
-        acc = k < 2 ? fmax(acc, a) : acc + a;
+        acc = k < 2 ? laplace_max(acc, a) : acc + a;
     }
     sh[k][lane] = acc;
     __syncthreads();
     for (int w = 32; w > 0; w >>= 1) {
         if (lane < w) {
             const double a = sh[k][lane], b = sh[k][lane + w];
-            sh[k][lane] = k < 2 ? fmax(a, b) : a + b;
+            sh[k][lane] = k < 2 ? laplace_max(a, b) : a + b;
         }
         __syncthreads();
     }

@@ -3304,24 +3304,27 @@ static void fit_laplace(mra_plan* pl, int family, const double* z, const double*
 
     // the data by padded row (z: NaN where the plan does not observe), the start, and the constants of -2 log p that do not depend on x
     std::vector<double> zh((size_t)P, std::nan("")), ah((size_t)P, 1.0), oh((size_t)P, 0.0), xh((size_t)P, 0.0);
-    // (chunks of 65536 rows over a few host threads; the chunks' sums are added in chunk order, whatever the number of threads)
+    // (chunks of 65536 rows over a few host threads; a chunk's sum is compensated (Kahan) - a plain serial sum of 26 000 constants loses
+    // 1e-13 of it, a hundred times what the device's tree of partial sums loses - and the chunks' sums are added in chunk order,
+    // whatever the number of threads)
     const long CH = 65536, nch = (P + CH - 1) / CH;
     std::vector<double> kpart((size_t)nch, 0.0);
     parallel_rows(nch, [&](int64_t c0, int64_t c1) {
         for (int64_t c = c0; c < c1; ++c) {
-            double k = 0.0;
+            double k = 0.0, lost = 0.0;
+            auto add = [&](double v) { const double y = v - lost, t = k + y; lost = (t - k) - y; k = t; };
             for (long p = c * CH; p < std::min<long>(P, (c + 1) * CH); ++p) {
                 if (!seen[p]) continue;
                 const double zp = z[p], a = need_aux ? aux[p] : 1.0, o = off ? off[p] : 0.0;
                 zh[p] = zp; ah[p] = a; oh[p] = o;
                 if (family == MRA_FAMILY_POISSON) {
-                    k += 2.0 * lgamma_of(zp + 1.0);
+                    add(2.0 * lgamma_of(zp + 1.0));
                     xh[p] = std::log(zp + 0.5) - o;
                 } else if (family == MRA_FAMILY_BINOMIAL) {
-                    k -= 2.0 * (lgamma_of(a + 1.0) - lgamma_of(zp + 1.0) - lgamma_of(a - zp + 1.0));
+                    add(-2.0 * (lgamma_of(a + 1.0) - lgamma_of(zp + 1.0) - lgamma_of(a - zp + 1.0)));
                     xh[p] = std::log((zp + 0.5) / (a - zp + 0.5)) - o;
                 } else {
-                    k += std::log(6.283185307179586 * a);
+                    add(std::log(6.283185307179586 * a));
                     xh[p] = zp - o;
                 }
                 if (x0) xh[p] = x0[p];
@@ -3358,6 +3361,10 @@ static void fit_laplace(mra_plan* pl, int family, const double* z, const double*
             run_all(pl, MRA_RUN_LIKELIHOOD | MRA_RUN_PREDICT);
             ++passes;
             std::copy(pl->host_res + MRA_HOST_RES_LAPLACE, pl->host_res + MRA_HOST_RES_LAPLACE + MRA_LAPLACE_NRES, res);
+            // a step that is not finite (the reduction keeps a NaN or inf of the mean): the iterate has left the doubles.  The fit ends
+            // here, not converged, with that step in info[6].  (A guard: a pass whose t is NaN is as a rule refused before it has a
+            // mean - r = 0 at an upper node's knot row has no positive pivot - DESIGN.md section 16.)
+            if (!std::isfinite(res[0])) break;
             converged = res[0] <= tol * std::max(1.0, res[1]);
         }
     } catch (...) { hipStreamSynchronize(pl->stream); mirror(); throw; }

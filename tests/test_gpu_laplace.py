@@ -4,7 +4,9 @@
 2. the Gaussian family is set_obs(z - offset, aux), bit for bit; 3. one cell each of the Fused, level-by-level and Hi routes and
 a leaf of 193 observations: the fixed point and a fresh plan given (t, r); 4. the 1-D tree t201, whose partition drops rows;
 5. an opaque callable (MRA_KERNEL_HOST); 6. a warm start; 7. the calls on the retained factors after a fit; 8. refusals;
-9. MRATree.fitLaplace.
+9. MRATree.fitLaplace; 10. laplace_term from eta = -700 to 700 against 50 digits; 11. the floor on D and saturated probabilities
+against the dense twin; 12. an iterate that leaves the doubles is refused, never converged.  3. and 4. run the Poisson and the
+binomial family, and one more pass from the converged mean whose info[2..4] and step are recomputed from arrays.
 
 Trees, masks and expected routes are those of tests/_route_cells.py; bars are ORACLE_BARS and ROUTE_BARS of
 tests/test_gpu_routes.py (Newton's map has zero derivative at its fixed point, so a pass's error is not amplified), and for the calls
@@ -122,7 +124,7 @@ def test_gaussian_family_is_set_obs_bit_for_bit(hip):
 
 
 # ---- 3. / 4. routes, a leaf of 193 observations, a 1-D tree with dropped rows ---------------------------------------------------------
-def _fixed_point_and_fresh_plan(hip, pl, topo, locs, spec, z, offset, res, tag):
+def _fixed_point_and_fresh_plan(hip, pl, topo, locs, spec, family, z, aux, offset, res, tag):
     """the checks without a dense oracle: convergence, t = x^ + g(eta^) / D(eta^) at the observed rows, and a fresh plan given (t, r)"""
     print("%s: passes %d, step %.2e" % (tag, res["passes"], res["step"]))
     assert res["info"][7] == 1.0, tag
@@ -130,7 +132,7 @@ def _fixed_point_and_fresh_plan(hip, pl, topo, locs, spec, z, offset, res, tag):
     got = _state(pl)
     xh = got[1][seen]
     t, r = _caller(topo, pl.buffer(11)), _caller(topo, pl.buffer(10))
-    g, D, _ = LP.terms(LP.POISSON, z[seen], 1.0, xh + offset[seen])
+    g, D, _ = LP.terms(family, z[seen], 1.0 if aux is None else aux[seen], xh + (0.0 if offset is None else offset[seen]))
     e_t = np.abs(t[seen] - (xh + g / D)) / np.maximum(1.0, np.abs(xh))
     print("%s: fixed point %.2e" % (tag, e_t.max()))
     assert e_t.max() <= 10 * TOL, tag
@@ -142,52 +144,95 @@ def _fixed_point_and_fresh_plan(hip, pl, topo, locs, spec, z, offset, res, tag):
     return got, fresh
 
 
-@pytest.mark.parametrize("key,recipe,opts", [("A", RC.CLOUD, ()), ("A", RC.CLOUD, LEVELS), ("H", RC.CLOUD, ()), ("A", RC.E193, ())],
-                         ids=["A-fused", "A-levels", "H-hi", "A-193"])
-def test_routes_fixed_point_and_fresh_plan(hip, key, recipe, opts):
+def _info_of_one_more_pass(pl, topo, family, z, aux, offset, x0, tag):
+    """One pass from a copy of the converged mean: only here is the linearisation point known outside the library, so only here
+    can info[2..4] and the step be recomputed from arrays (LP.recompute_info).  Bars: INFO_ULPS eps x the sum of the absolute
+    values of a sum's terms - a term passes through at most 34 roundings on its way into a sum (tests/test_gpu_fullsize.py has the
+    count), and exp, log and lgamma are good to a few ulp; the step is a maximum and has no rounding."""
+    res = _fit(pl, family, z, aux, offset, x0=x0, max_iter=1)
+    seen = _seen(topo, z)
+    mean = pl.predict()[0]
+    rc = LP.recompute_info(family, z, aux, offset, x0, mean, _caller(topo, pl.buffer(11)), _caller(topo, pl.buffer(10)), seen)
+    for k, key in ((2, "info2"), (3, "info3"), (4, "info4")):
+        e = abs(res["info"][k] - rc[key]) / (LP.EPS * rc["S"][k - 2])
+        print("%s: info[%d] %.10f recomputed %.10f: %.2f eps x sum |term|" % (tag, k, res["info"][k], rc[key], e))
+        assert e <= INFO_ULPS, "%s: info[%d]" % (tag, k)
+    assert res["passes"] == 1 and res["info"][6] == rc["step"], tag
+    assert res["info"][7] == float(rc["step"] <= TOL * max(1.0, rc["max_xhat"])), tag
+    return res
+
+
+INFO_ULPS = 128
+ROUTE_CELLS = [("A", RC.CLOUD, ()), ("A", RC.CLOUD, LEVELS), ("H", RC.CLOUD, ()), ("A", RC.E193, ())]
+ROUTE_IDS = ["A-fused", "A-levels", "H-hi", "A-193"]
+
+
+def _route_cell(hip, key, recipe, opts, family):
     topo, locs = TR._tree(key)
     obs = RC.make_obs(topo, locs, recipe)
     if recipe == RC.E193:
         assert MK.leaf_counts(topo, obs)[0] == 0                      # an empty first leaf
-    z, _, offset = LP.inputs(locs, obs, LP.POISSON)
-    tag = "%s %s %s" % (key, recipe, opts)
+    z, aux, offset = LP.inputs(locs, obs, family)
+    tag = "%s %s %s %s" % (key, recipe, opts, LP.NAMES[family])
     pl = MK._plan(hip, topo, locs, _y_mask(z))
     TR._set(pl, opts)
-    res = _fit(pl, LP.POISSON, z, None, offset, max_iter=30)
+    res = _fit(pl, family, z, aux, offset, max_iter=30)
     expect = _expect(key, recipe, opts)
     TR._check_route(pl, expect, tag)
-    got, fresh = _fixed_point_and_fresh_plan(hip, pl, topo, locs, MK._spec(), z, offset, res, tag)
+    got, fresh = _fixed_point_and_fresh_plan(hip, pl, topo, locs, MK._spec(), family, z, aux, offset, res, tag)
     TR._set(fresh, opts)
     want = TR._predict(fresh)
     TR._check_route(fresh, expect, tag + " fresh plan")
     assert (res["d"], res["u"]) == fresh.likelihood(), tag
     _same(got, want, tag + " vs a fresh plan given (t, r)")
+    _info_of_one_more_pass(pl, topo, family, z, aux, offset, got[1].copy(), tag)
+    TR._check_route(pl, expect, tag + " one more pass")
     fresh.close(); pl.close()
 
 
-def test_1d_tree_with_dropped_rows(hip):
+@pytest.mark.parametrize("key,recipe,opts", ROUTE_CELLS, ids=ROUTE_IDS)
+def test_routes_fixed_point_and_fresh_plan(hip, key, recipe, opts):
+    _route_cell(hip, key, recipe, opts, LP.POISSON)
+
+
+@pytest.mark.parametrize("key,recipe,opts", ROUTE_CELLS, ids=ROUTE_IDS)
+def test_routes_fixed_point_and_fresh_plan_binomial(hip, key, recipe, opts):
+    _route_cell(hip, key, recipe, opts, LP.BINOMIAL)
+
+
+def _t201(hip, family):
     cs = K.load_case("t201")
     topo, locs, y, spec, R1 = cs["topo"], cs["locs"], cs["y_obs"], cs["spec"], float(cs["c"]["R"])
     rep = NZ.reported(topo)
     obs = np.isfinite(np.asarray(y).ravel())
     assert not rep.all() and (obs & ~rep).any()                       # data at rows outside every leaf: ignored
-    z, _, offset = LP.inputs(locs, obs, LP.POISSON)
+    z, aux, offset = LP.inputs(locs, obs, family)
+    tag = "t201 " + LP.NAMES[family]
     pl = hip.HipPlan(topo, 0)
     pl.set_locs(locs); pl.set_obs(y, R1); pl.set_kernel(spec.kind, spec.l, spec.sig, spec.scale, spec.circular)
-    res = _fit(pl, LP.POISSON, z, None, offset, max_iter=30)
-    got, fresh = _fixed_point_and_fresh_plan(hip, pl, topo, locs, spec, z, offset, res, "t201")
+    res = _fit(pl, family, z, aux, offset, max_iter=30)
+    got, fresh = _fixed_point_and_fresh_plan(hip, pl, topo, locs, spec, family, z, aux, offset, res, tag)
     fresh.set_kernel(spec.kind, spec.l, spec.sig, spec.scale, spec.circular)
     want = TR._predict(fresh)
     assert (res["d"], res["u"]) == fresh.likelihood()
-    _same(got, want, "t201 vs a fresh plan given (t, r)")
+    _same(got, want, tag + " vs a fresh plan given (t, r)")
     assert np.all(got[1][~rep] == 0.0)
     # the data at the dropped rows are nobody's: other values there, the same bits
     z2 = z.copy()
     z2[obs & ~rep] += 5.0
-    res2 = _fit(pl, LP.POISSON, z2, None, offset, max_iter=30)
+    res2 = _fit(pl, family, z2, aux, offset, max_iter=30)                # (binomial: aux < z2 there, and nobody looks)
     assert np.array_equal(res2["info"], res["info"])
-    _same(_state(pl), got, "t201 with other data at the dropped rows")
+    _same(_state(pl), got, tag + " with other data at the dropped rows")
+    _info_of_one_more_pass(pl, topo, family, z, aux, offset, got[1].copy(), tag)
     fresh.close(); pl.close()
+
+
+def test_1d_tree_with_dropped_rows(hip):
+    _t201(hip, LP.POISSON)
+
+
+def test_1d_tree_with_dropped_rows_binomial(hip):
+    _t201(hip, LP.BINOMIAL)
 
 
 # ---- 5. / 6. an opaque callable; a warm start ------------------------------------------------------------------------------------------
@@ -383,3 +428,121 @@ def test_mratree_fit_laplace(hip):
         tree.fitLaplace("poisson", offset=offset, cov=lambda a, b: np.exp(-np.abs(a - b.T)))
     with pytest.raises(ValueError):
         tree.fitLaplace("gamma")
+
+
+# ---- 10. laplace_term across the range -----------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("family", [LP.GAUSSIAN, LP.POISSON, LP.BINOMIAL], ids=["gaussian", "poisson", "binomial"])
+def test_laplace_term_across_the_range(hip, family):
+    """One linearisation at x0 = a grid of eta over T16's observed rows (LP.term_cases: +-0, +-2^-60, the edge of the floor, +-700,
+    z = 0, z at its upper end and z ~ its mean), t and r against 50 digits.  r relatively; t in units of |x| + (|z| + m) / D, the
+    terms that cancel in it.  Bar: four times the error of the float64 statement on the same grid (tests/test_laplace_cpu.py
+    asserts that one), and not below 8 eps.  The step of the pass is a maximum and is compared exactly."""
+    topo, locs, obs, y, counts, Sigma, o = LP.t16()
+    e = LP.term_errors(family, int(o.sum()), LP.t16_upper_knots())
+    zN, auxN, xN = np.full(topo.N, np.nan), np.ones(topo.N), np.zeros(topo.N)
+    zN[o], auxN[o], xN[o] = e["z"], e["aux"], e["x"]
+    pl = MK._plan(hip, topo, locs, y)
+    res = _fit(pl, family, zN, auxN, None, x0=xN, max_iter=1)
+    t, r = _caller(topo, pl.buffer(11)), _caller(topo, pl.buffer(10))
+    e_t, e_r = LP.err_mp(t[o], e["t"], e["unit"]), LP.err_mp(r[o], e["r"], e["r"])
+    bar_t, bar_r = max(8 * LP.EPS, 4 * e["e_t"]), max(8 * LP.EPS, 4 * e["e_r"])
+    print("%s: t %.2f eps (float64 %.2f, bar %.2f), r %.2f eps (float64 %.2f, bar %.2f)"
+          % (LP.NAMES[family], e_t / LP.EPS, e["e_t"] / LP.EPS, bar_t / LP.EPS, e_r / LP.EPS, e["e_r"] / LP.EPS, bar_r / LP.EPS))
+    assert e_t <= bar_t and e_r <= bar_r
+    assert np.all(r[~o] == 0.0) and (r[o] == 2.0 ** 40).sum() >= 100
+    mean = pl.predict()[0]
+    assert np.all(np.isfinite(mean))
+    assert res["passes"] == 1 and res["info"][6] == np.abs(mean[o] - xN[o]).max()
+    pl.close()
+
+
+# ---- 11. the floor on D and saturated probabilities against the dense twin -------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["tiny_exposure", "saturated", "gauss_floor"])
+def test_floor_and_saturation_against_the_dense_twin(hip, name):
+    topo, locs, obs, y, counts, Sigma, o = LP.t16()
+    family, z, aux, offset = LP.edge_inputs(name)
+    ref = LP.edge_fit(name)
+    pl = MK._plan(hip, topo, locs, y)
+    res = _fit(pl, family, z, aux, offset)
+    got = _state(pl)
+    r = _caller(topo, pl.buffer(10))
+    print("%s: passes %d (dense %d), step %.2e, %d rows at r = 2^40" % (name, res["passes"], ref["info"][5], res["step"], (r[o] == 2.0 ** 40).sum()))
+    TR._against(topo, counts, got, (ref["info"][0] + ref["info"][1], ref["mean"], ref["sd"]), TR.ORACLE_BARS, "T16 %s vs dense" % name)
+    for k in range(5):
+        e = abs(res["info"][k] - ref["info"][k]) / abs(ref["info"][k])
+        print("info[%d]: %.10f vs %.10f, rel %.2e" % (k, res["info"][k], ref["info"][k], e))
+        assert e <= TR.ORACLE_BARS[0], "info[%d] rel err %.3e" % (k, e)
+    assert abs(res["lik"] - ref["lik"]) <= TR.ORACLE_BARS[0] * abs(ref["lik"])
+    assert res["info"][7] == 1.0 and res["converged"] is True
+    assert res["passes"] == int(ref["info"][5])
+    if name == "saturated":
+        assert r[o].max() > 1e3 and np.abs(got[1][o]).max() > 5.0
+    else:
+        assert (r[o] == 2.0 ** 40).sum() >= 100                       # otherwise this does not test the floor
+        assert np.array_equal(r[o] == 2.0 ** 40, ref["r"][o] == 2.0 ** 40)
+    if name == "gauss_floor":
+        fresh = hip.HipPlan(topo, 0)
+        s = MK._spec()
+        fresh.set_locs(locs); fresh.set_obs((z - offset).reshape(-1, 1), np.minimum(aux, 2.0 ** 40)); fresh.set_kernel(s.kind, s.l, s.sig, s.scale)
+        want = TR._predict(fresh)
+        assert (res["d"], res["u"]) == fresh.likelihood()
+        _same(got, want, "gauss_floor vs set_obs(z - offset, min(aux, 2^40))")
+        fresh.close()
+    pl.close()
+
+
+# ---- 12. an iterate that leaves the doubles --------------------------------------------------------------------------------------------------
+NOT_SPD = -3
+
+
+def test_non_finite_iterate_is_refused_never_converged(hip):
+    """Poisson counts in the thousands from x0 = 0: pass 1 overshoots to max |x^| = 5139, pass 2 linearises at e^eta = inf, which
+    gives t = NaN and r = 1 / inf = 0.  The dense twin ends there, not converged (tests/test_laplace_cpu.py).  The device pass does
+    not get as far as a mean: r = 0 at a row that is an upper node's knot leaves that leaf no positive pivot, and the pass is
+    refused MRA_ERR_NOT_SPD with the r of that pass in the plan: the call never returns converged with
+    a mean that is not finite."""
+    topo, locs, obs, y, counts, Sigma, o = LP.t16()
+    family, z, aux, offset = LP.edge_inputs("big_counts")
+    twin = LP.edge_fit("big_counts", True, 10)
+    assert twin["info"][5] == 2 and twin["info"][7] == 0.0 and np.isnan(twin["info"][6])
+    knot = np.zeros(int(o.sum()), dtype=bool)
+    knot[list(LP.t16_upper_knots())] = True
+    assert (np.isnan(twin["t"][o]) & (twin["r"][o] == 0.0) & knot).any()          # the rows the refusal comes from
+    pl = MK._plan(hip, topo, locs, y)
+    with pytest.raises(hip.MraError) as ei:
+        _fit(pl, family, z, aux, offset, x0=np.zeros(topo.N), max_iter=10)
+    print("big_counts from 0: %s" % ei.value)
+    assert ei.value.code == NOT_SPD and "not positive definite" in str(ei.value)
+    r = _caller(topo, pl.buffer(10))
+    assert np.array_equal(r[o] == 0.0, twin["r"][o] == 0.0) and (r[o] == 0.0).any()          # pass 2's r, as the twin has it
+    # the plan is not poisoned: the data-based start on the same data converges as the twin does
+    ref = LP.edge_fit("big_counts")
+    res = _fit(pl, family, z, aux, offset)
+    assert res["converged"] and res["passes"] == int(ref["info"][5]) == 4
+    TR._against(topo, counts, _state(pl), (ref["info"][0] + ref["info"][1], ref["mean"], ref["sd"]), TR.ORACLE_BARS, "T16 big_counts vs dense")
+    assert abs(res["lik"] - ref["lik"]) <= TR.ORACLE_BARS[0] * abs(ref["lik"])
+    pl.close()
+
+
+def test_mratree_keeps_no_mode_of_a_fit_that_left_the_doubles(hip):
+    import pymra_amd
+    import pymra_amd.MRATools as mt
+    n, r0, M = RC.TREES["T16"]
+    topo, locs, obs, y, counts, Sigma, o = LP.t16()
+    family, z, aux, offset = LP.edge_inputs("big_counts")
+    s = MK._spec()
+    cov = lambda a, b: mt.Matern32(a, b, l=s.l, sig=s.sig)           # noqa: E731
+    np.random.seed(7)                                                 # as MK._tree does: the same knots
+    mt.genLocations2d(Nx=n, Ny=n)
+    tree = pymra_amd.MRATree(locs, r0, cov, z.reshape(-1, 1), MK.R, M=M, J=4)
+    assert np.array_equal(tree.topology.knot_rows, topo.knot_rows)
+    lik = tree.fitLaplace("poisson")
+    mode = tree._laplace_mean.copy()
+    assert tree.laplace["converged"] and tree.laplace["passes"] == 4
+    with pytest.raises(pymra_amd.plan.MraError) as ei:
+        tree.fitLaplace("poisson", x0=np.zeros(topo.N), max_iter=10)
+    assert ei.value.code == NOT_SPD
+    assert np.array_equal(tree._laplace_mean, mode)                   # the mode of the last converged fit, not of the refused one
+    warm = tree.fitLaplace("poisson")                                 # started from that mode
+    assert tree.laplace["converged"] and tree.laplace["passes"] <= 4 and np.all(np.isfinite(tree._laplace_mean))
+    assert abs(warm - lik) <= TR.ROUTE_BARS[0] * abs(lik)
