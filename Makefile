@@ -3,7 +3,7 @@
 # and the dispatchers of the heavily templated kernels (mra_launch_*.hip), so that `make -j8 lib` takes ~1 min instead of 2.5.
 HIPCC ?= /opt/rocm/bin/hipcc
 CSRC   = pymra_amd/csrc
-UNITS  = mra_plan mra_launch_gemm mra_launch_pred mra_launch_prior_row1 mra_launch_prior_row2 mra_launch_prior_knot1 mra_launch_prior_knot2 mra_launch_solve mra_launch_cov mra_launch_sites mra_launch_laplace
+UNITS  = mra_plan mra_launch_gemm mra_launch_pred mra_launch_prior_row1 mra_launch_prior_row2 mra_launch_prior_row3 mra_launch_prior_knot1 mra_launch_prior_knot2 mra_launch_prior_knot3 mra_launch_solve mra_launch_cov mra_launch_sites mra_launch_laplace
 HDRS   = $(CSRC)/mra_kernels.h $(CSRC)/mra_plan_types.h $(CSRC)/mra_launch_prior.inc $(CSRC)/mra_solve_kernels.h $(CSRC)/mra_cov_kernels.h $(CSRC)/mra_site_kernels.h $(CSRC)/mra_laplace_kernels.h include/mra_hip.h
 CFLAGS = --offload-arch=gfx950 -std=c++17 -fPIC -Wno-unused-value -Wno-unused-result -Wno-pass-failed
 B      = build
@@ -28,6 +28,14 @@ $(B)/asan/%.o: $(CSRC)/%.hip $(HDRS)
 pymra_amd/libmra_hip_asan.so: $(UNITS:%=$(B)/asan/%.o)
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC $(SAN) -o $@ $^ -ldl
 
+# Stand-alone host program on the sanitizer build (its own main, the sanitizer runtime linked in: no preload): the host side of
+# d = 3 plans - replay on (lon, lat), plan with mra_topology.d = 3, xyz gather, knot coordinates - in MRA_HOST_DRYRUN mode.
+HOSTCXX ?= /opt/rocm/lib/llvm/bin/clang++
+tools/asan_plan3d: tools/asan_plan3d.cpp include/mra_hip.h pymra_amd/libmra_hip_asan.so
+	$(HOSTCXX) -std=c++17 -O1 -g -fsanitize=address -fsanitize=undefined -fno-omit-frame-pointer -fno-sanitize-recover=undefined -Iinclude $< -o $@ pymra_amd/libmra_hip_asan.so -Wl,-rpath,'$$ORIGIN/../pymra_amd'
+asan3d: tools/asan_plan3d
+	MRA_HOST_DRYRUN=1 ASAN_OPTIONS=detect_leaks=0:halt_on_error=1 UBSAN_OPTIONS=halt_on_error=1:print_stacktrace=1 tools/asan_plan3d
+
 # Diagnostic build with in-kernel clock stamps in the prior row cascade (tools/stamps_cascade.py); never the product.
 stamps: pymra_amd/libmra_hip_stamps.so
 $(B)/stamps/%.o: $(CSRC)/%.hip $(HDRS)
@@ -46,5 +54,5 @@ pymra_amd/libmra_hip_whatif.so: $(UNITS:%=$(B)/whatif/%.o)
 	$(HIPCC) --offload-arch=gfx950 -shared -fPIC -o $@ $^ -ldl
 
 clean:
-	rm -rf $(B) pymra_amd/libmra_hip.so pymra_amd/libmra_hip_asan.so pymra_amd/libmra_hip_stamps.so pymra_amd/libmra_hip_whatif.so pymra_amd/libmra_hip.resource_usage.txt
-.PHONY: lib asan stamps whatif clean
+	rm -rf $(B) pymra_amd/libmra_hip.so pymra_amd/libmra_hip_asan.so pymra_amd/libmra_hip_stamps.so pymra_amd/libmra_hip_whatif.so pymra_amd/libmra_hip.resource_usage.txt tools/asan_plan3d
+.PHONY: lib asan asan3d stamps whatif clean

@@ -61,7 +61,9 @@ typedef struct mra_plan mra_plan;
  */
 typedef struct {
     int64_t        P;            /* padded rows                                    */
-    int32_t        d;            /* spatial dimension, 1 or 2                      */
+    int32_t        d;            /* dimension of the coordinates the covariance is evaluated on: 1, 2 or 3 (3: chordal distance on a
+                                  * sphere, or 3-D Euclidean).  The tree arrays below do not depend on it: the partition may
+                                  * have been built on other coordinates (lon/lat for points on a sphere)            */
     int32_t        n_levels;
     int32_t        n_nodes;
     const int64_t *level_ptr;    /* [n_levels + 1]                                 */

@@ -97,6 +97,31 @@ def genLocations2d(Nx, lbx=0, ubx=1, Ny=0, lby=0, uby=1):
     return np.hstack((gx.reshape(Nx * Ny, 1), gy.reshape(Nx * Ny, 1)))
 
 
+# ---- points on a sphere: the covariance is evaluated on the chordal distance, the Euclidean distance of the points' 3-D
+# coordinates (every stationary kernel here stays positive definite on it); the tree is still partitioned on (lon, lat)
+def lonlat_to_xyz(lonlat, radius=1.0, degrees=True):
+    """(n, 2) longitude / latitude -> (n, 3) Cartesian coordinates on the sphere of the given radius."""
+    ll = np.asarray(lonlat, dtype=np.float64)
+    if ll.ndim != 2 or ll.shape[1] != 2:
+        raise ValueError("lonlat must have shape (n, 2)")
+    if degrees:
+        ll = np.deg2rad(ll)
+    lon, lat = ll[:, 0], ll[:, 1]
+    cl = np.cos(lat)
+    return float(radius) * np.column_stack((cl * np.cos(lon), cl * np.sin(lon), np.sin(lat)))
+
+
+def chord_of_arc(theta, radius=1.0):
+    """Chord length of a great-circle distance theta (a length on the sphere of the given radius): 2 R sin(theta / 2R).  States a
+    range parameter given as a great-circle distance in the chordal metric the kernels are evaluated on."""
+    return 2.0 * radius * np.sin(np.asarray(theta, dtype=np.float64) / (2.0 * radius))
+
+
+def arc_of_chord(c, radius=1.0):
+    """Great-circle distance of a chord length c: 2 R asin(c / 2R), the inverse of chord_of_arc."""
+    return 2.0 * radius * np.arcsin(np.clip(np.asarray(c, dtype=np.float64) / (2.0 * radius), -1.0, 1.0))
+
+
 def dist(locs, locs2=np.array([]), circular=False):
     locs = locs if np.ndim(locs) == 2 else np.reshape(locs, [len(locs), 1])
     if circular:

@@ -8,6 +8,8 @@ Mirrors the public surface of pyMRA/MRATree.py:
 * ``getLikelihood()`` -> 1x1 ``np.matrix`` (root.d + root.u)                  MRATree.py:82-84
 * ``predict()`` -> (N x 1 ``np.matrix`` mean, (N,) ``ndarray`` sd)            MRATree.py:90-94
 * attributes ``locs, d, r, J, M, obs_inds, root`` with ``root.d, root.u, root.mean, root.var``
+* beyond pyMRA: ``cov_locs`` / ``metric="chordal"`` - the covariance is evaluated on other coordinates (N x k, k <= 3) than the
+  ones the tree is partitioned on: points on a sphere keep a (lon, lat) tree and get chordal distances from their xyz
 
 As in the reference all the work happens in the constructor - here it is: replay the tree on
 the host (pymra_amd.topology), hand the flat tree + locations + observations to libmra_hip.so
@@ -111,10 +113,36 @@ def _check_noise(R, N):
 class MRATree(object):
 
     def __init__(self, locs, r, cov, obs, R, M=-1, J=-1, critDepth=-1, verbose=True, device=0,
-                 want_predict=True):
+                 want_predict=True, cov_locs=None, metric="euclidean", radius=1.0):
+        """cov_locs: N x k (k <= 3) coordinates the covariance is evaluated on, when they are not ``locs``; ``locs`` still builds
+        the tree.  metric="chordal": ``locs`` are (lon, lat) in degrees on a sphere of the given radius and the covariance sees
+        their chordal distances (cov_locs = mt.lonlat_to_xyz(locs, radius)); the sites of predictAt and its siblings are (lon, lat)
+        too.  Under an explicit cov_locs the sites are given in covariance coordinates (n x k)."""
         self.locs = locs
         self.d = np.shape(self.locs)[1]
         N = len(locs)
+        if metric not in ("euclidean", "chordal"):
+            raise ValueError('metric must be "euclidean" or "chordal"')
+        self.metric, self.radius = metric, float(radius)
+        if metric == "chordal":
+            if cov_locs is not None:
+                raise ValueError('metric="chordal" derives the covariance coordinates from locs: do not pass cov_locs as well')
+            if np.ndim(locs) != 2 or self.d != 2:
+                raise ValueError('metric="chordal" needs locs of shape (N, 2): longitude and latitude in degrees')
+            cov_locs = mt.lonlat_to_xyz(locs, self.radius)
+        self._split_coords = cov_locs is not None           # the covariance has coordinates of its own
+        if self._split_coords:
+            cov_locs = np.ascontiguousarray(np.asarray(cov_locs, dtype=np.float64))
+            if cov_locs.ndim == 1:
+                cov_locs = cov_locs.reshape(-1, 1)
+            if cov_locs.ndim != 2 or len(cov_locs) != N or not 1 <= cov_locs.shape[1] <= 3:
+                raise ValueError("cov_locs must have shape (N, k) with N = %d and k <= 3" % N)
+            if not np.all(np.isfinite(cov_locs)):
+                raise ValueError("cov_locs must be finite")
+            self.cov_locs = cov_locs
+        else:
+            self.cov_locs = np.asarray(locs, dtype=np.float64)
+        self.cov_d = self.cov_locs.shape[1] if self.cov_locs.ndim == 2 else 1      # dimension the covariance is evaluated in
         self.r = r
         self.M, self.J = resolve_tree_shape(N, self.d, r, M, J)
         if critDepth < 0:
@@ -131,8 +159,8 @@ class MRATree(object):
             if not (np.all(np.isfinite(ro)) and np.all(ro >= 0.0)):
                 raise ValueError("the noise variance of an observed location is negative or not finite")
 
-        spec = probe_cov(cov, self.d, np.asarray(locs, dtype=np.float64))
-        if spec is not None and spec.circular and self.d != 1:
+        spec = probe_cov(cov, self.cov_d, self.cov_locs)
+        if spec is not None and spec.circular and self.cov_d != 1:
             raise ValueError("circular distances are defined for 1-D locations only")
         if spec is None and not callable(cov) and not isinstance(cov, np.ndarray):
             raise TypeError("cov must be a callable cov(locs1, locs2) or a dense N x N matrix")
@@ -142,29 +170,31 @@ class MRATree(object):
         # large 2-D trees: tree replay, plan construction and the uploads in one library call (the plan is built beside the
         # sequential knot draws); everything else - 1-D, small nodes, KMeans rules - the general path
         R_scalar = (float(ro.mean()) if ro.size and ro.mean() > 0.0 else 1.0) if noise_vector else R
-        both = create_with_replay(locs, r, self.M, self.J, obs_arr, R_scalar, device) if self.d == 2 else None
+        # (covariance coordinates of their own: the general path - the native 2-D replay still builds the tree)
+        both = create_with_replay(locs, r, self.M, self.J, obs_arr, R_scalar, device) if self.d == 2 and not self._split_coords else None
         if both is not None:
             self.plan, self.topology = both
             if noise_vector:
                 self.plan.set_noise(R)          # (the one-call constructor takes a scalar: the vector goes in before the first run)
         else:
-            self.topology = build_topology(np.asarray(locs, dtype=np.float64), r, self.M, self.J)
+            self.topology = build_topology(np.asarray(locs, dtype=np.float64), r, self.M, self.J,
+                                           coord_dim=self.cov_d if self._split_coords else None)
             self.plan = HipPlan(self.topology, device=device)
-            self.plan.set_locs(locs)
+            self.plan.set_locs(self.cov_locs if self._split_coords else locs)
             self.plan.set_obs(obs_arr, R)
         if spec is not None:
             self.plan.set_kernel(spec.kind, spec.l, spec.sig, spec.scale, spec.circular)
         else:
             # cov-callable plug-in for anything the device cannot evaluate itself (pyMRA/MRANode.py:73-80,
             # 381-384): the host evaluates the raw covariance blocks, the GPU does everything else
-            self.plan.upload_host_cov(cov, locs, obs_arr)
+            self.plan.upload_host_cov(cov, self.cov_locs if self._split_coords else locs, obs_arr)     # (the callable sees the covariance coordinates)
         self.plan.run(likelihood=True, predict=want_predict)
         d, u = self.plan.likelihood()
         if want_predict:
             mean, var, self._sd = self.plan.predict(with_sd=True)      # (sd beside var: predict() returns it, as the reference's np.sqrt(root.var))
         else:
             mean, var, self._sd = None, None, None
-        self.root = RootView(d, u, mean, var, N, self.topology, np.asarray(locs, dtype=np.float64), spec)
+        self.root = RootView(d, u, mean, var, N, self.topology, self.cov_locs, spec)
         self._node_blocks = {}
 
     @property
@@ -226,13 +256,19 @@ class MRATree(object):
         return mean, quad
 
     def _sites(self, sites):
+        """The caller's sites, checked, in covariance coordinates: (lon, lat) degrees -> xyz under metric="chordal", else as given
+        (n x k under an explicit cov_locs, n x d otherwise).  The public calls convert once and hand the result to the private
+        _locate / _predict_at / _covariance_at, which take covariance coordinates."""
         X = np.asarray(sites, dtype=np.float64)
-        if X.ndim == 1 and self.d == 1:
+        din = 2 if self.metric == "chordal" else self.cov_d
+        if X.ndim == 1 and din == 1:
             X = X.reshape(-1, 1)
-        if X.ndim != 2 or X.shape[1] != self.d:
-            raise ValueError("sites must have shape (n, %d)" % self.d)
+        if X.ndim != 2 or X.shape[1] != din:
+            raise ValueError("sites must have shape (n, %d)" % din)
         if not np.all(np.isfinite(X)):
             raise ValueError("sites must be finite")
+        if self.metric == "chordal":
+            X = mt.lonlat_to_xyz(X, self.radius)
         return X
 
     def locate(self, sites):
@@ -240,15 +276,18 @@ class MRATree(object):
         drops never win; on a circular 1-D kernel the distance wraps at 1.  The rule serves every partition of the tree replay
         (quadrants, terciles, knot boundaries, KMeans) and sends a site that coincides with a tree location to that location's leaf.
         Any assignment of sites to leaves gives a valid process: predictAt(leaf=...) overrides this one."""
+        return self._locate(self._sites(sites))
+
+    def _locate(self, X):
         from scipy.spatial import cKDTree
-        X = self._sites(sites)
         t = self.topology
         if getattr(self, "_locator", None) is None:
             rows = np.nonzero((t.perm >= 0) & np.asarray(t.in_leaf, dtype=bool))[0]
             leaf_of = np.full(t.P, -1, dtype=np.int32)
             for i in np.nonzero(np.asarray(t.node_leaf, dtype=bool))[0]:
                 leaf_of[int(t.node_row0[i]):int(t.node_row1[i])] = i
-            pts = np.asarray(self.locs, dtype=np.float64).reshape(len(self.locs), -1)[t.perm[rows]]
+            # (nearest in covariance coordinates: by chord is by great circle, so the date line needs no special case)
+            pts = np.asarray(self.cov_locs, dtype=np.float64).reshape(len(self.locs), -1)[t.perm[rows]]
             wrap = self.kernel is not None and self.kernel.circular
             self._locator = (cKDTree(np.mod(pts, 1.0) if wrap else pts, boxsize=1.0 if wrap else None), leaf_of[rows], wrap)
         kd, leaves, wrap = self._locator
@@ -257,15 +296,18 @@ class MRATree(object):
 
     def predictAt(self, sites, Y=None, leaf=None):
         """Posterior mean and standard deviation of the latent field at locations that need not be rows of `locs`, from this tree's
-        factors - the tree (its knots, its likelihood) stays the one that was fitted.  sites: (n, d); Y: None (this tree's
-        observations) or (N,) / (N, c) observation vectors in the caller's row order on this tree's mask, as for solve(); leaf: None
-        (locate(sites)) or int32[n] leaf node indices.  -> (mean (n, c), sd (n,)); add R to sd ** 2 for a new observation.  At a
+        factors - the tree (its knots, its likelihood) stays the one that was fitted.  sites: (n, d) - under metric="chordal" (n, 2)
+        longitude / latitude in degrees, under an explicit cov_locs (n, k) in the covariance coordinates, here and in locate,
+        covarianceAt, simulateAt and sampleAt; Y: None (this tree's observations) or (N,) / (N, c) observation vectors in the
+        caller's row order on this tree's mask, as for solve(); leaf: None (locate(sites)) or int32[n] leaf node indices.  -> (mean (n, c), sd (n,)); add R to sd ** 2 for a new observation.  At a
         location of the tree, in that location's leaf, these are predict()'s values.  getLikelihood() and predict() are unchanged."""
         if self.kernel is None:
             raise NotImplementedError("predictAt needs a device kernel: trees built from an opaque callable or a dense matrix cannot predict at new sites")
-        X = self._sites(sites)
+        return self._predict_at(self._sites(sites), Y, leaf)
+
+    def _predict_at(self, X, Y=None, leaf=None):
         if leaf is None:
-            leaf = self.locate(X)
+            leaf = self._locate(X)
         leaf = np.asarray(leaf)
         if leaf.shape != (len(X),):
             raise ValueError("leaf must have shape (n,) = (%d,)" % len(X))
@@ -286,16 +328,19 @@ class MRATree(object):
     def covarianceAt(self, sites, distr="posterior", leaf=None):
         """(n, n) joint covariance of the latent field at locations that need not be rows of `locs`, from this tree's factors:
         the posterior given this tree's observations (distr="posterior": its diagonal is predictAt's sd ** 2) or the prior
-        (distr="prior").  sites: (n, d); leaf: None (locate(sites)) or int32[n] leaf node indices.  Symmetric to the bit; positive
+        (distr="prior").  sites: (n, d), (lon, lat) or covariance coordinates as for predictAt; leaf: None (locate(sites)) or
+        int32[n] leaf node indices.  Symmetric to the bit; positive
         semi-definite down to roundoff only (duplicated sites and the Iden kernel make it singular).  w @ covarianceAt(grid) @ w is
         the variance of the functional w . x over a prediction grid.  getLikelihood() and predict() are unchanged."""
         if distr not in ("prior", "posterior"):
             raise ValueError('distr must be "prior" or "posterior"')
         if self.kernel is None:
             raise NotImplementedError("covarianceAt needs a device kernel: trees built from an opaque callable or a dense matrix cannot evaluate it at new sites")
-        X = self._sites(sites)
+        return self._covariance_at(self._sites(sites), distr, leaf)
+
+    def _covariance_at(self, X, distr, leaf):
         if leaf is None:
-            leaf = self.locate(X)
+            leaf = self._locate(X)
         leaf = np.asarray(leaf)
         if leaf.shape != (len(X),):
             raise ValueError("leaf must have shape (n,) = (%d,)" % len(X))
@@ -307,10 +352,12 @@ class MRATree(object):
         eigenvalues below 0 set to 0) and z (n, nsim) given, or standard normals from numpy.random.default_rng(seed)."""
         if self.kernel is None:
             raise NotImplementedError("simulateAt needs a device kernel: trees built from an opaque callable or a dense matrix cannot simulate at new sites")
+        if distr not in ("prior", "posterior"):
+            raise ValueError('distr must be "prior" or "posterior"')
         X = self._sites(sites)
         if leaf is None:
-            leaf = self.locate(X)
-        S = self.covarianceAt(X, distr=distr, leaf=leaf)
+            leaf = self._locate(X)
+        S = self._covariance_at(X, distr, leaf)
         n = len(X)
         nsim = int(nsim)
         if z is None:
@@ -322,7 +369,7 @@ class MRATree(object):
         F = (Q * np.sqrt(np.maximum(lam, 0.0))) @ Q.T
         x = F @ z
         if distr == "posterior" and n:
-            x += self.predictAt(X, leaf=leaf)[0]
+            x += self._predict_at(X, leaf=leaf)[0]
         return x
 
     def sampleAt(self, sites, nsim, distr="posterior", seed=None, leaf=None, z=None):
@@ -339,7 +386,7 @@ class MRATree(object):
             raise NotImplementedError("sampleAt needs a device kernel: trees built from an opaque callable or a dense matrix cannot simulate at new sites")
         X = self._sites(sites)
         if leaf is None:
-            leaf = self.locate(X)
+            leaf = self._locate(X)
         leaf = np.asarray(leaf)
         if leaf.shape != (len(X),):
             raise ValueError("leaf must have shape (n,) = (%d,)" % len(X))
@@ -432,7 +479,7 @@ class MRATree(object):
     # re-evaluate with other kernel parameters on the same tree (plan reuse for MLE loops,
     # README.md:96-104 builds a new MRATree per objective call)
     def reevaluate(self, cov, want_predict=False):
-        spec = probe_cov(cov, self.d, np.asarray(self.locs, dtype=np.float64))
+        spec = probe_cov(cov, self.cov_d, self.cov_locs)
         if spec is None:
             raise NotImplementedError("cov must be a device kernel")
         self.kernel = spec
@@ -441,7 +488,7 @@ class MRATree(object):
         self.plan.run(likelihood=True, predict=want_predict)
         d, u = self.plan.likelihood()
         mean, var, self._sd = self.plan.predict(with_sd=True) if want_predict else (None, None, None)
-        self.root = RootView(d, u, mean, var, len(self.locs), self.topology, np.asarray(self.locs, dtype=np.float64), spec)
+        self.root = RootView(d, u, mean, var, len(self.locs), self.topology, self.cov_locs, spec)
         return self.getLikelihood()
 
     def setNoise(self, R, want_predict=False):
@@ -457,7 +504,7 @@ class MRATree(object):
         self.plan.run(likelihood=True, predict=want_predict)
         d, u = self.plan.likelihood()
         mean, var, self._sd = self.plan.predict(with_sd=True) if want_predict else (None, None, None)
-        self.root = RootView(d, u, mean, var, len(self.locs), self.topology, np.asarray(self.locs, dtype=np.float64), self.kernel)
+        self.root = RootView(d, u, mean, var, len(self.locs), self.topology, self.cov_locs, self.kernel)
         return self.getLikelihood()
 
     def fitLaplace(self, family, aux=None, offset=None, z=None, x0=None, cov=None, max_iter=50, tol=1e-10):
@@ -468,7 +515,7 @@ class MRATree(object):
         data-based start.  Updates ``root`` and ``predict()`` to the Laplace posterior N(x^, (Sigma^-1 + D)^-1), keeps the numbers
         of the fit in ``self.laplace`` and returns -2 log q(z); ``getLikelihood()`` keeps its meaning, d + u of the last pass."""
         if cov is not None:
-            spec = probe_cov(cov, self.d, np.asarray(self.locs, dtype=np.float64))
+            spec = probe_cov(cov, self.cov_d, self.cov_locs)
             if spec is None:
                 raise NotImplementedError("cov must be a device kernel")
             self.kernel = spec
@@ -482,5 +529,5 @@ class MRATree(object):
         mean, var, self._sd = self.plan.predict(with_sd=True)
         self._laplace_mean = mean.copy() if res["converged"] else None      # (a fit that did not converge is no start for the next)
         self.laplace = res
-        self.root = RootView(res["d"], res["u"], mean, var, len(self.locs), self.topology, np.asarray(self.locs, dtype=np.float64), self.kernel)
+        self.root = RootView(res["d"], res["u"], mean, var, len(self.locs), self.topology, self.cov_locs, self.kernel)
         return res["lik"]

@@ -226,6 +226,10 @@ __device__ __forceinline__ double pair_dist2(const double* __restrict__ xa, cons
         if (circular) dx = fmin(dx, fabs(1.0 - dx));
         return dx * dx;
     }
+    if (DIM == 3) {                                  // chordal distance on a sphere, or plain 3-D Euclidean
+        const double dx = xa[0] - xb[0], dy = xa[1] - xb[1], dz = xa[2] - xb[2];
+        return dx * dx + dy * dy + dz * dz;
+    }
     const double dx = xa[0] - xb[0], dy = xa[1] - xb[1];
     return dx * dx + dy * dy;
 }
@@ -1194,7 +1198,9 @@ __global__ __launch_bounds__(NTHR, WPE) void k_leaf_gemm(const GemmProb* __restr
             }
             __syncthreads();                                     // previous pass is done with sB / sXB / sIB
             if (EPI == EPI_COV || EPI == EPI_HOSTCOV) {
-                for (int t = threadIdx.x; t < nc * 16; t += blockDim.x) {
+                int ts = threadIdx.x;
+                if (EPI == EPI_COV && DIM == 3) asm volatile("" : "+v"(ts));   // opaque: no 64-bit idxB pointer carried (and spilled) across the passes
+                for (int t = ts; t < nc * 16; t += blockDim.x) {
                     const int col = j0 * 16 + t;
                     const int ib = col < N ? (idxB ? gldi(idxB + col) : col) : -1;
                     sIB[t] = ib;
@@ -2545,11 +2551,16 @@ __device__ __forceinline__ void cascade_compute_level_kx(const double* __restric
         if (LAT && cvp) res = cvp[jb] - acc;
         else {
             double kc[4 * DIM];                     // coordinates of this lane's 4 knots (phantoms: far away)
-            const double* kp4 = kx + (long)(jb * 16 + 4 * q) * DIM;
+            int qk = q;
+            if (DIM == 3 && !LAT) asm volatile("" : "+v"(qk));   // opaque: the knots' lane address is rebuilt per level, not hoisted out of the tile loop and spilled
+            const double* kp4 = kx + (long)(jb * 16 + 4 * qk) * DIM;
 #pragma unroll
             for (int e = 0; e < 4 * DIM; e += 4) *(d4*)(kc + e) = *(const d4*)(kp4 + e);
 #pragma unroll
-            for (int j = 0; j < 4; ++j) res[j] = (MRA_WHATIF_BIT(dbg, 4) ? kc[j * DIM] * 1e-3 : cov_of_dist2<MODE>(kp, pair_dist2<DIM>(xr, kc + j * DIM, kp.circular))) - acc[j];
+            for (int j = 0; j < 4; ++j) {
+                res[j] = (MRA_WHATIF_BIT(dbg, 4) ? kc[j * DIM] * 1e-3 : cov_of_dist2<MODE>(kp, pair_dist2<DIM>(xr, kc + j * DIM, kp.circular))) - acc[j];
+                if (DIM == 3 && MODE == 3 && !LAT) __builtin_amdgcn_sched_barrier(0);   // Kanter in 3-D: one sin/cos at a time, or four sets of temporaries spill
+            }
         }
         d4 upd = zero, upd1 = zero;
 #pragma unroll
@@ -2596,7 +2607,9 @@ __device__ __forceinline__ void cascade_cov_tiles(const double* __restrict__ kx,
     }
 }
 
-template <int CWT, int NLMAX>
+// ZLATE: the zeros of the y block's store are made where they are stored (behind an opaque copy), not kept in four registers
+// across the level loop - the 3-D stage-all cascade has none to spare
+template <int CWT, int NLMAX, bool ZLATE = false>
 __device__ __forceinline__ void cascade_outputs(const CascadeArgs& ar, const int* chain, long t, long myrow, bool phantom_row,
                                                 d4 (&w)[NLMAX][CWT], int r, int q, double ssq) {
     constexpr int CW = CWT * 16;
@@ -2630,6 +2643,12 @@ __device__ __forceinline__ void cascade_outputs(const CascadeArgs& ar, const int
         const d4 yt = {(q == 0 && isfinite(yy)) ? yy : 0.0, 0.0, 0.0, 0.0};
         int qo = q;
         asm volatile("" : "+v"(qo));     // opaque: the lane part of the address is rebuilt here, not hoisted out of the tile loop and spilled
+        if constexpr (ZLATE) {
+            double z0 = 0.0;
+            asm volatile("" : "+v"(z0));
+            const d4 yz = {(q == 0 && isfinite(yy)) ? yy : z0, z0, z0, z0};
+            *(d4*)(ar.W + myrow * ar.ldw + ar.ycol + 4 * qo) = yz;
+        } else
         *(d4*)(ar.W + myrow * ar.ldw + ar.ycol + 4 * qo) = yt;
     }
     if (ar.obs_pos && !phantom_row) {
@@ -2729,7 +2748,7 @@ __global__ __launch_bounds__(512) void k_prior_cascade(CascadeArgs ar, KernelPar
                     if (!ar.knot_mode) ssq += cascade_output_level<CWT, NLMAX>(ar, m, t, myrow, op, w, q);
                     MRA_STAMP(3 + 2 * m);
                 }
-            cascade_outputs<CWT, NLMAX>(ar, chain, t, myrow, ar.knot_mode ? phantom_row : op == -2, w, r, q, ssq);
+            cascade_outputs<CWT, NLMAX, DIM == 3>(ar, chain, t, myrow, ar.knot_mode ? phantom_row : op == -2, w, r, q, ssq);
             MRA_STAMP(15);
         }
     } else {
@@ -2772,6 +2791,11 @@ __global__ __launch_bounds__(512) void k_prior_cascade(CascadeArgs ar, KernelPar
         const int Kw = mo * CW;
         const int nnode = nt_wg / CWT;
         const d4 zero = {0, 0, 0, 0};
+        // DIM == 3: the lane's coordinates are derived afresh from the hardware lane count, so that r, q and prow need not
+        // survive the row loop above in registers it cannot spare (DIM <= 2: the values from the top of the kernel)
+        const int lane_t = DIM == 3 ? (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) : lane;
+        const int r = DIM == 3 ? (lane_t & 15) : (lane & 15), q = DIM == 3 ? (lane_t >> 4) : (lane >> 4);
+        const int prow = pi16(r);
         __syncthreads();                                  // every wave's Wk rows are in global memory
         for (int w = wave; w < nnode * NT2; w += nwave) {
             const int ni = w / NT2, idx = w - ni * NT2;
@@ -2806,8 +2830,8 @@ __global__ __launch_bounds__(512) void k_prior_cascade(CascadeArgs ar, KernelPar
             double* s_sd = lds + wave * 576;
             double* s_si = s_sd + 288;
             bool bad = false;
-            chol_wave_body(ar.Lp_out + (long)slotk * CW * CW, CW, CWT, ar.invd_out + (long)slotk * CWT * 256, s_sd, s_si, lane, bad);
-            if (bad && lane == 0) atomicMax(ar.err, ar.node_base + slotk + 1);
+            chol_wave_body(ar.Lp_out + (long)slotk * CW * CW, CW, CWT, ar.invd_out + (long)slotk * CWT * 256, s_sd, s_si, lane_t, bad);
+            if (bad && lane_t == 0) atomicMax(ar.err, ar.node_base + slotk + 1);
         }
     }
 }

@@ -59,7 +59,7 @@ void mra_cov_block(mra_plan* pl, bool posterior, bool want_gram) {
     mra_plan::Solver& S = pl->slv;
     const long P = pl->P;
     const unsigned nl = (unsigned)pl->leaf_nodes.size();
-    if (pl->d != 1 && pl->d != 2) throw MraError(MRA_ERR_INVALID, "mra_cov_apply: 1-D and 2-D locations only");
+    if (pl->d < 1 || pl->d > 3) throw MraError(MRA_ERR_INVALID, "mra_cov_apply: 1-, 2- or 3-D locations only");
     // 1. leaves; 2. fronts bottom-up; 3. fronts top-down (a single-leaf tree has no ancestors: none of the three reads anything)
     if (nl)
         hipLaunchKernelGGL(k_cov_leaf_proj, dim3(nl), dim3(256), 0, pl->stream, V.leaves.p, pl->W.p, (long)pl->ldw, V.ab.p, pl->maps.rep.p, pl->maps.knot.p, P);
@@ -72,7 +72,7 @@ void mra_cov_block(mra_plan* pl, bool posterior, bool want_gram) {
         if (n) hipLaunchKernelGGL(k_cov_down, dim3(n), dim3(256), 0, pl->stream, V.fronts.p + S.lev_off[m]);
     }
     // 4. rows
-    if (pl->d == 1) launch_cov_rows<1>(pl); else launch_cov_rows<2>(pl);
+    if (pl->d == 1) launch_cov_rows<1>(pl); else if (pl->d == 2) launch_cov_rows<2>(pl); else launch_cov_rows<3>(pl);
     // 5. posterior: out -= mean_MRA(out at the observed rows)
     if (posterior) {
         const long n = 16 * P;

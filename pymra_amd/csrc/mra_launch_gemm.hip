@@ -15,6 +15,7 @@ static void launch_gemm(mra_plan* pl, const GemmProb* probs, size_t nprob, long 
     const bool lds = pl->gemm_lds && allow_lds;
     const unsigned gx = lds ? (unsigned)(((maxM + 63) / 64) * ((maxN + 63) / 64)) : gemm_grid_x(maxM, maxN, lower_tri);
     const int mode = (EPI == EPI_COV) ? pl->kp.mode : 0;
+    // (DIM only matters to the covariance epilogue: the other epilogues of a 3-D plan run the DIM = 2 instances)
     // 1-D grid, XCD-aware (xcd_problem_tile): gx workgroups per problem, problems rounded up to 8
     const size_t chunk = (size_t)std::max<long>(8, ((0x7fffffffL / (long)gx) / 8) * 8);
     for (size_t off = 0; off < nprob; off += chunk) {
@@ -29,9 +30,11 @@ static void launch_gemm(mra_plan* pl, const GemmProb* probs, size_t nprob, long 
         dim3 grid(gxs * (((gy + 7u) / 8u) * 8u));
 #define MRA_GEMM_LAUNCH(KERN, D, MD) hipLaunchKernelGGL((KERN<EPI, D, (EPI == EPI_COV ? MD : 0)>), grid, dim3(256), 0, pl->stream, probs + off, pl->kp, gxs, gy, S)
         if (lds) {
+            if constexpr (EPI == EPI_COV) { if (pl->d == 3) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 2); else MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 3); continue; } }
             if (pl->d == 1) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 2); else MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 3); }
             else { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 2); else MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 3); }
         } else {
+            if constexpr (EPI == EPI_COV) { if (pl->d == 3) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 2); else MRA_GEMM_LAUNCH(k_gemm_nt, 3, 3); continue; } }
             if (pl->d == 1) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 2); else MRA_GEMM_LAUNCH(k_gemm_nt, 1, 3); }
             else { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 2); else MRA_GEMM_LAUNCH(k_gemm_nt, 2, 3); }
         }
@@ -54,6 +57,7 @@ static void launch_leaf_gemm(mra_plan* pl, const GemmProb* probs, size_t nprob) 
         if (wide) hipLaunchKernelGGL((k_leaf_gemm<EPI, D, (EPI == EPI_COV ? MD : 0), 1, 8, 512, (MD == 3 ? 2 : 4)>), grid, dim3(512), 0, pl->stream, probs, pl->kp); \
         else hipLaunchKernelGGL((k_leaf_gemm<EPI, D, (EPI == EPI_COV ? MD : 0), (EPI == EPI_SUB ? 1 : 2), CT, 256, 2>), grid, dim3(256), 0, pl->stream, probs, pl->kp); \
     } while (0)
+    if constexpr (EPI == EPI_COV) { if (pl->d == 3) { if (mode == 0) MRA_LG_LAUNCH(3, 0); else if (mode == 1) MRA_LG_LAUNCH(3, 1); else if (mode == 2) MRA_LG_LAUNCH(3, 2); else MRA_LG_LAUNCH(3, 3); return; } }
     if (pl->d == 1) { if (mode == 0) MRA_LG_LAUNCH(1, 0); else if (mode == 1) MRA_LG_LAUNCH(1, 1); else if (mode == 2) MRA_LG_LAUNCH(1, 2); else MRA_LG_LAUNCH(1, 3); }
     else { if (mode == 0) MRA_LG_LAUNCH(2, 0); else if (mode == 1) MRA_LG_LAUNCH(2, 1); else if (mode == 2) MRA_LG_LAUNCH(2, 2); else MRA_LG_LAUNCH(2, 3); }
 #undef MRA_LG_LAUNCH
@@ -89,8 +93,11 @@ void mra_launch_prior_level(mra_plan* pl, const GemmProb* probs, size_t nprob) {
     if (!nprob) return;
     const int mode = pl->kp.mode;
     const dim3 grid((unsigned)nprob);
-#define MRA_PL_LAUNCH(D, MD) hipLaunchKernelGGL((k_leaf_gemm<EPI_COV, D, MD, 2, 4, 256, (MD == 3 ? 2 : MRA_PL_WPE), 1>), grid, dim3(256), 0, pl->stream, probs, pl->kp)
+    // (D == 3: two workgroups per CU, 192 registers - at three the third coordinate takes the 168-register shape's parked epilogue
+    // addresses from 60 to 76 bytes of scratch per lane; two cost the 2-D kernel 3 % at config 5)
+#define MRA_PL_LAUNCH(D, MD) hipLaunchKernelGGL((k_leaf_gemm<EPI_COV, D, MD, 2, 4, 256, (MD == 3 || D == 3 ? 2 : MRA_PL_WPE), 1>), grid, dim3(256), 0, pl->stream, probs, pl->kp)
     if (pl->d == 1) { if (mode == 0) MRA_PL_LAUNCH(1, 0); else if (mode == 1) MRA_PL_LAUNCH(1, 1); else if (mode == 2) MRA_PL_LAUNCH(1, 2); else MRA_PL_LAUNCH(1, 3); }
+    else if (pl->d == 3) { if (mode == 0) MRA_PL_LAUNCH(3, 0); else if (mode == 1) MRA_PL_LAUNCH(3, 1); else if (mode == 2) MRA_PL_LAUNCH(3, 2); else MRA_PL_LAUNCH(3, 3); }
     else { if (mode == 0) MRA_PL_LAUNCH(2, 0); else if (mode == 1) MRA_PL_LAUNCH(2, 1); else if (mode == 2) MRA_PL_LAUNCH(2, 2); else MRA_PL_LAUNCH(2, 3); }
 #undef MRA_PL_LAUNCH
 }

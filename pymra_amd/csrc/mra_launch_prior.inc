@@ -1,7 +1,7 @@
 // mra_launch_prior.inc - dispatch of the prior cascade kernels over block width, depth and covariance family for ONE spatial
 // dimension (MRA_TU_DIM) and one kernel (MRA_TU_KNOT: k_knot_chain, else k_prior_cascade in row and knot mode).  Included by
-// the four mra_launch_prior_*.hip translation units: the 72 instantiations are most of the library's compile time, split
-// four ways they build in parallel.
+// the six mra_launch_prior_*.hip translation units: the 108 instantiations are most of the library's compile time, split
+// six ways they build in parallel.
 #define MRA_KERNELS_TEMPLATES_ONLY
 #include "mra_plan_types.h"
 

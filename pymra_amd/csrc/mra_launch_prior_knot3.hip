@@ -1,0 +1,4 @@
+#define MRA_TU_DIM 3
+#define MRA_TU_KNOT
+#define MRA_TU_NAME launch_knot_chain_d3
+#include "mra_launch_prior.inc"

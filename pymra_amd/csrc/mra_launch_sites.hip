@@ -110,13 +110,15 @@ static void launch_gram(mra_plan* pl, long n, long tile0, long rows, bool post) 
 // the <DIM, MODE> instance of the plan's dimension and kernel, as the solver's row kernel is chosen
 #define MRA_SITES_DISPATCH(FN, ...)                                                                                  \
     do {                                                                                                             \
-        if (pl->d != 1 && pl->d != 2) throw MraError(MRA_ERR_INVALID, "mra_predict_sites: 1-D and 2-D locations only"); \
+        if (pl->d < 1 || pl->d > 3) throw MraError(MRA_ERR_INVALID, "mra_predict_sites: 1-, 2- or 3-D locations only"); \
         const int md_ = pl->kp.mode < 0 || pl->kp.mode > 3 ? 3 : pl->kp.mode;                                        \
         switch ((pl->d - 1) * 4 + md_) {                                                                             \
             case 0: FN<1, 0>(__VA_ARGS__); break; case 1: FN<1, 1>(__VA_ARGS__); break;                              \
             case 2: FN<1, 2>(__VA_ARGS__); break; case 3: FN<1, 3>(__VA_ARGS__); break;                              \
             case 4: FN<2, 0>(__VA_ARGS__); break; case 5: FN<2, 1>(__VA_ARGS__); break;                              \
-            case 6: FN<2, 2>(__VA_ARGS__); break; default: FN<2, 3>(__VA_ARGS__); break;                             \
+            case 6: FN<2, 2>(__VA_ARGS__); break; case 7: FN<2, 3>(__VA_ARGS__); break;                              \
+            case 8: FN<3, 0>(__VA_ARGS__); break; case 9: FN<3, 1>(__VA_ARGS__); break;                              \
+            case 10: FN<3, 2>(__VA_ARGS__); break; default: FN<3, 3>(__VA_ARGS__); break;                            \
         }                                                                                                            \
     } while (0)
 

@@ -122,7 +122,7 @@ static void launch_rows(mra_plan* pl) {
 void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad, bool want_rows) {
     mra_plan::Solver& S = pl->slv;
     const unsigned nl = (unsigned)pl->leaf_nodes.size();
-    if (pl->d != 1 && pl->d != 2) throw MraError(MRA_ERR_INVALID, "mra_solve: 1-D and 2-D locations only");
+    if (pl->d < 1 || pl->d > 3) throw MraError(MRA_ERR_INVALID, "mra_solve: 1-, 2- or 3-D locations only");
     // 1. forward, leaves
     if (nl) {
         hipLaunchKernelGGL(k_solve_leaf_trsm<false>, dim3(nl), dim3(64), 0, pl->stream, S.leaves.p, S.yb.p, pl->P);
@@ -152,7 +152,7 @@ void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad, bool want_ro
         hipLaunchKernelGGL(k_solve_leaf_trsm<true>, dim3(nl), dim3(64), 0, pl->stream, S.leaves.p, S.yb.p, pl->P);
     }
     if (!want_rows) return;          // mra_predict_sites: beta and q are read from the leaves' gb / uy
-    if (pl->d == 1) launch_rows<1>(pl); else launch_rows<2>(pl);
+    if (pl->d == 1) launch_rows<1>(pl); else if (pl->d == 2) launch_rows<2>(pl); else launch_rows<3>(pl);
 }
 
 void mra_solver_pseudo(mra_plan* pl, const double* y, const double* x, const SampleZ& zs, long slot0) {

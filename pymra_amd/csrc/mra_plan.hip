@@ -3512,7 +3512,7 @@ int mra_plan_create(mra_plan** out, const mra_topology* t, int device) {
     return guarded(nullptr, [&] {
         require(out && t, "mra_plan_create: out or topology is NULL");
         *out = nullptr;
-        if (t->P <= 0 || (t->d != 1 && t->d != 2) || t->n_levels <= 0 || t->n_nodes <= 0)
+        if (t->P <= 0 || t->d < 1 || t->d > 3 || t->n_levels <= 0 || t->n_nodes <= 0)
             throw MraError(MRA_ERR_INVALID, "bad topology header");
         PlanTrace tr("mra_plan_create");
         PlanPtr pl = new_plan(device);
@@ -3572,7 +3572,8 @@ int mra_plan_set_locs_rows(mra_plan* pl, const double* locs, const int64_t* src)
         tr.mark("staging buffer");
         parallel_rows(pl->P, [&](int64_t a, int64_t b) {
             if (d == 2) for (int64_t p = a; p < b; ++p) { const int64_t q = src[p]; xp[2 * p] = locs[2 * q]; xp[2 * p + 1] = locs[2 * q + 1]; }
-            else for (int64_t p = a; p < b; ++p) xp[p] = locs[src[p]];
+            else if (d == 1) for (int64_t p = a; p < b; ++p) xp[p] = locs[src[p]];
+            else for (int64_t p = a; p < b; ++p) { const int64_t q = src[p]; for (int e = 0; e < d; ++e) xp[d * p + e] = locs[d * q + e]; }
         });
         tr.mark("gather into leaf order");
         set_locs(pl, xp);

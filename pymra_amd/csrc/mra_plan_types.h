@@ -641,10 +641,12 @@ void mra_launch_syrk_blk(mra_plan* pl, const GemmProb* probs, size_t nprob, long
 void mra_launch_prior_level(mra_plan* pl, const GemmProb* probs, size_t nprob);
 void launch_cascade_d1(mra_plan* pl, const CascadeArgs& ar);       // one translation unit per spatial dimension
 void launch_cascade_d2(mra_plan* pl, const CascadeArgs& ar);
+void launch_cascade_d3(mra_plan* pl, const CascadeArgs& ar);
 void launch_knot_chain_d1(mra_plan* pl, const KnotChainArgs& ka);
 void launch_knot_chain_d2(mra_plan* pl, const KnotChainArgs& ka);
-static inline void launch_cascade_any(mra_plan* pl, const CascadeArgs& ar) { if (pl->d == 1) launch_cascade_d1(pl, ar); else launch_cascade_d2(pl, ar); }
-static inline void launch_knot_chain(mra_plan* pl, const KnotChainArgs& ka) { if (pl->d == 1) launch_knot_chain_d1(pl, ka); else launch_knot_chain_d2(pl, ka); }
+void launch_knot_chain_d3(mra_plan* pl, const KnotChainArgs& ka);
+static inline void launch_cascade_any(mra_plan* pl, const CascadeArgs& ar) { if (pl->d == 1) launch_cascade_d1(pl, ar); else if (pl->d == 2) launch_cascade_d2(pl, ar); else launch_cascade_d3(pl, ar); }
+static inline void launch_knot_chain(mra_plan* pl, const KnotChainArgs& ka) { if (pl->d == 1) launch_knot_chain_d1(pl, ka); else if (pl->d == 2) launch_knot_chain_d2(pl, ka); else launch_knot_chain_d3(pl, ka); }
 void launch_predict_any(mra_plan* pl, const PredArgs& ar, size_t lds);
 void launch_predict_hi(mra_plan* pl, const PredHiArgs& hi, const PredArgs& low, size_t lds_low, bool upd);
 // mra_plan.hip: the plan's row maps (mra_plan::RowMaps), built on the first call; holds the one "knot row out of range" check

@@ -63,7 +63,7 @@ def collect_node_blocks(tree, posterior: bool = True) -> List[NodeBlocks]:
     if spec is None:
         raise NotImplementedError("node blocks need a device kernel (KernelSpec); opaque cov callables are not supported here")
     cw, coff, Ka, ldw = _layout(topo)
-    locs = np.asarray(tree.locs, dtype=np.float64)
+    locs = np.asarray(getattr(tree, "cov_locs", tree.locs), dtype=np.float64)     # the coordinates the covariance is evaluated on
     if locs.ndim == 1:
         locs = locs.reshape(-1, 1)
     yv = np.asarray(tree.obs, dtype=np.float64).reshape(-1)

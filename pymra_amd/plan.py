@@ -246,11 +246,14 @@ class HipPlan:
             knot_rows=np.ascontiguousarray(topo.knot_rows, dtype=np.int64),
             cw=np.ascontiguousarray(topo.cw, dtype=np.int32),
         )
-        st = MraTopologyStruct(P=int(topo.P), d=int(topo.d), n_levels=int(topo.n_levels), n_nodes=int(topo.n_nodes),
+        # the struct's d is the dimension of the coordinates the covariance is evaluated on (set_locs, sites): the topology's
+        # coord_dim where it differs from the dimension the tree was partitioned on (lon/lat tree, xyz covariance)
+        cd = int(getattr(topo, "coord_dim", 0) or topo.d)
+        st = MraTopologyStruct(P=int(topo.P), d=cd, n_levels=int(topo.n_levels), n_nodes=int(topo.n_nodes),
                                **{k: _ptr(v) for k, v in arrs.items()})
         _check(self.lib, self.lib.mra_plan_create(C.byref(self._h), C.byref(st), int(device)))
         self.P = int(topo.P)
-        self.d = int(topo.d)
+        self.d = cd
 
     # -- helpers -------------------------------------------------------------------------------
     def _check(self, rc):

@@ -244,6 +244,8 @@ class Topology:
     cw: np.ndarray              # int32[n_levels] knot-block width of the NON-LEAF nodes of a level,
                                 #                 padded to COL_ALIGN (0 if the level has none)
     order_preorder: np.ndarray  # int32[n] node numbers in the reference's construction order
+    coord_dim: int = 0          # columns of the coordinates the COVARIANCE is evaluated on (1, 2 or 3); 0: the same as d, the
+                                # dimension the tree was partitioned on (lon/lat partition, xyz covariance: d = 2, coord_dim = 3)
 
     def rank(self, i: int) -> int:
         return int(self.knot_ptr[i + 1] - self.knot_ptr[i])
@@ -343,12 +345,25 @@ def topology_from_tree(lib, handle, N, r, M, J, perm, src, in_leaf, knot_rows) -
                     node_ident=idents, cw=a["cw"], order_preorder=a["pre"])
 
 
-def build_topology(locs: np.ndarray, r: int, M: int, J: int, native: bool = True) -> Topology:
+def build_topology(locs: np.ndarray, r: int, M: int, J: int, native: bool = True, coord_dim: Optional[int] = None) -> Topology:
     """Replay the reference's tree construction for ``locs`` (N x d, d in {1,2}).
 
     M and J must already be resolved (``resolve_tree_shape``).  Consumes the global NumPy
     RNG exactly like the reference does (one ``np.random.choice`` per 2-D node with more
-    than 100 candidates, depth-first pre-order)."""
+    than 100 candidates, depth-first pre-order).
+
+    coord_dim: the number of columns (1, 2 or 3) of the coordinates the covariance will be evaluated on, when they are not
+    ``locs`` themselves - a tree partitioned on (lon, lat) whose kernels see the points' xyz has coord_dim = 3.  The tree does
+    not depend on it: every array equals the coord_dim=None tree's; only ``Topology.coord_dim`` is set."""
+    if coord_dim is not None and int(coord_dim) not in (1, 2, 3):
+        raise ValueError("coord_dim must be 1, 2 or 3")
+    topo = _build_topology(locs, r, M, J, native)
+    if coord_dim is not None:
+        topo.coord_dim = int(coord_dim)
+    return topo
+
+
+def _build_topology(locs: np.ndarray, r: int, M: int, J: int, native: bool) -> Topology:
     coords = np.ascontiguousarray(np.asarray(locs, dtype=np.float64))
     if coords.ndim == 1:
         coords = coords.reshape(-1, 1)
