@@ -41,10 +41,18 @@ def _solve_lower(L, B):
 def _kernel(spec, a, b):
     a = np.asarray(a, dtype=LD)
     b = np.asarray(b, dtype=LD)
-    D2 = np.zeros((len(a), len(b)), dtype=LD)
-    for c in range(a.shape[1]):
-        D2 += (a[:, c:c + 1] - b[:, c:c + 1].T) ** 2
-    D = np.sqrt(D2)
+    if getattr(spec, "circular", False):
+        # the 1-D torus [0, 1) of pymra_amd.MRATools.dist: the shorter way round
+        if a.shape[1] != 1:
+            raise ValueError("a circular kernel takes 1-D locations")
+        D = np.abs(a - b.T)
+        D = np.minimum(D, 1 - D)
+        D2 = D * D
+    else:
+        D2 = np.zeros((len(a), len(b)), dtype=LD)
+        for c in range(a.shape[1]):
+            D2 += (a[:, c:c + 1] - b[:, c:c + 1].T) ** 2
+        D = np.sqrt(D2)
     l, sig, scale = LD(spec.l), LD(spec.sig), LD(spec.scale)
     if spec.kind == 0:
         v = np.exp(-D / l)
@@ -56,8 +64,17 @@ def _kernel(spec, a, b):
         v = sig * (1 + t + (LD(5) / 3) * (D / l) ** 2) * np.exp(-t)
     elif spec.kind == 3:
         v = sig * np.exp(-D2 / (2 * l * l))
-    else:
+    elif spec.kind == 4:
         v = (D == 0).astype(LD)
+    elif spec.kind == 5:
+        # Kanter's taper of radius l (pymra_amd.MRATools._kanter): 1 at 0, 0 beyond the radius
+        t = D / l
+        p2 = 8 * np.arctan(LD(1)) * t                 # 2 pi t with pi in extended precision
+        safe = np.where(p2 > 0, p2, LD(1))
+        v = (1 - t) * np.sin(safe) / safe + (1 - np.cos(safe)) / (4 * np.arctan(LD(1)) * safe)
+        v = np.where(t > 1, LD(0), np.where(t == 0, LD(1), v))
+    else:
+        raise ValueError("unknown kernel kind %r" % (spec.kind,))
     return scale * v
 
 

@@ -169,11 +169,12 @@ def _relerr(a, b):
     return abs(a - b) / max(abs(b), 1.0)
 
 
-def check_fused(hip, topo, locs, y, tag, ref=None, gathered=True):
+def check_fused(hip, topo, locs, y, tag, ref=None, gathered=True, make_plan=None):
     """Likelihood-only passes of one mask on one plan, sibling grouping forced on and off: each bit-identical to the pass over all
     rows (option 17 = 0) and to each other, equal to the predictive pass's likelihood (1e-12) and to ``ref`` (1e-11).  The
-    gathered path must have run (fewer prior-row flops than the pass over all rows) - or, with ``gathered`` False, not."""
-    pl = _plan(hip, topo, locs, y)
+    gathered path must have run (fewer prior-row flops than the pass over all rows) - or, with ``gathered`` False, not.
+    ``make_plan``: builds the plan instead of ``_plan`` (another kernel or noise variance; ``ref`` is then the caller's)."""
+    pl = (make_plan or _plan)(hip, topo, locs, y)
     pl.set_option(hip.MRA_OPT_KERNEL_TIMING, 1)
     liks = {}
     for grp in (1, 0):
