@@ -476,6 +476,13 @@ int mra_get_timers(mra_plan *plan, double *out_ms, int capacity);
                                       the fronts fit it (at most 92 tiles, 64 KB of LDS) and the level has more fronts than the device has CUs;
                                       0: always k_parent_front (eight waves, one workgroup per CU); 2: the pair kernel wherever the fronts fit
                                       (tests, A/B runs).  Read at every launch.  mra_get_route does not report it */
+#define MRA_OPT_PRIOR_REUSE    24  /* fused path: a pass that follows one with the same kernel, locations and knots keeps that pass's prior - the
+                                      levels' factors and, where they were written at the rows it needs, the rows of W and the prior variance -
+                                      and launches neither prior kernel: it writes W's y block again, puts the prior variance back and re-runs the
+                                      row cascade on the few leaves whose rows the last update rewrote.  The results do not depend on it, bit for
+                                      bit.  1 (default); 0: every pass computes its prior, the launches are those of a plan's first pass.  Every
+                                      mra_plan_set_kernel / set_locs / set_cov_block / set_reduce_level, every option but 1, 20 and 21, and a pass
+                                      that fails drop what is kept; mra_plan_set_obs and set_noise do not.  mra_get_route does not report it */
 int mra_plan_set_option(mra_plan *plan, int option, int64_t value);
 /* current value of an option (so that a caller can change one temporarily and put it back) */
 int mra_plan_get_option(mra_plan *plan, int option, int64_t *value);

@@ -3783,6 +3783,24 @@ __global__ void k_init_yblock(double* __restrict__ W, long ldw, int Ka, const do
     }
     W[p * ldw + Ka + c] = v;
 }
+// What a fused pass that keeps the last pass's prior rows (MRA_OPT_PRIOR_REUSE) runs in place of the row cascade: the y block of every
+// row of the leaves' tiles exactly as cascade_outputs stores it - y in its first column (0 where y is not finite), zeros in the other
+// fifteen - and, with var, the prior variance put back from the copy the last full row pass left.  One thread per row and quarter block.
+__global__ void k_refresh_yblock(double* __restrict__ W, long ldw, int Ka, const double* __restrict__ y, const long* __restrict__ tile_row0,
+                                 long ntiles, double* __restrict__ var, const double* __restrict__ var_prior) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= ntiles * 64) return;
+    const long p = tile_row0[i >> 6] + ((i >> 2) & 15);
+    const int q = (int)(i & 3);
+    double y0 = 0.0;
+    if (q == 0) {
+        const double yy = y[p];
+        y0 = isfinite(yy) ? yy : 0.0;
+        if (var) var[p] = var_prior[p];
+    }
+    const d4 v = {y0, 0.0, 0.0, 0.0};
+    *(d4*)(W + p * ldw + Ka + 4 * q) = v;
+}
 // what is left of k_leaf_moments when the row solves have accumulated the variance: clamp at 0, reset the y column of the leaves' rows
 __global__ void k_leaf_finish_var(const int* __restrict__ row_leaf, double* __restrict__ W, long ldw, int Ka, double* __restrict__ var, long P) {
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;

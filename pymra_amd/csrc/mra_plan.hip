@@ -1215,6 +1215,31 @@ static void build_leaf_solve_lists(mra_plan* pl, const LeafDescs& d, const std::
     pl->leaf_solve_ok = n_small > 0 && nat_max <= 13 && nat_max > 0 && pl->leaf_solve_lds <= 160 * 1024 && pl->leaf_max_rows >= 128;
 }
 
+// The row cascade's workgroups over the tiles of the leaves behind the small ones in `order` (those of more than LEAF_SMALL_TILES
+// observation tiles): what a pass that keeps the last pass's W re-runs, because the plain update beside LeafUpdate::InCascade rewrote
+// those leaves' rows.  One leaf per workgroup run (a workgroup stages ONE chain), as many tiles per workgroup as either form of the
+// cascade walks (stage-all: any number, 8 = one per wave; else one tile per wave of its cascade_wpw).  If the standing dirty mark was
+// set under the old mask its list is put aside (stale) for that re-run.
+static void build_big_leaf_tiles(mra_plan* pl, const std::vector<size_t>& order, size_t n_small) {
+    typedef mra_plan::PriorKeep K;
+    if (pl->keep.dirty == K::Dirty::Oversized && !pl->stale.n_wg) pl->stale.swap(pl->big);
+    pl->big.n_wg = pl->big.n_tiles = 0;
+    if (!pl->regular || n_small >= order.size()) return;
+    const size_t nl = pl->leaf_nodes.size();
+    std::vector<long> first(nl + 1, 0);                      // a leaf's first tile in ft_row0 (build_cascade_tiles: leaves in order)
+    for (size_t t = 0; t < nl; ++t) first[t + 1] = first[t] + (pl->row1[pl->leaf_nodes[t]] - pl->row0[pl->leaf_nodes[t]]) / 16;
+    const long per_wg = pl->cascade_stage_all ? 8 : pl->cascade_wpw;
+    std::vector<long> wg0;
+    std::vector<int> wgn;
+    for (size_t k = n_small; k < order.size(); ++k) {
+        const size_t t = order[k];
+        for (long a = first[t]; a < first[t + 1]; a += per_wg) { wg0.push_back(a); wgn.push_back((int)std::min(per_wg, first[t + 1] - a)); }
+        pl->big.n_tiles += first[t + 1] - first[t];
+    }
+    pl->big.n_wg = (long)wg0.size();
+    pl->big.wg0.upload(wg0); pl->big.wgn.upload(wgn);
+}
+
 static void build_leaf(mra_plan* pl, const double* y) {
     PlanTrace tr("build_leaf");
     ArenaScope arena(&pl->arena);
@@ -1242,6 +1267,7 @@ static void build_leaf(mra_plan* pl, const double* y) {
     build_big_panels(pl, d);
     build_leaf_row_solves(pl, d, order, n_small);
     build_leaf_solve_lists(pl, d, order, n_small);
+    build_big_leaf_tiles(pl, order, n_small);
     arena.finish();
     tr.mark("descriptor arena to the device");
 }
@@ -1559,6 +1585,34 @@ static PassRoute route_for(const mra_plan* pl, uint32_t flags, bool full_rows) {
     return r;
 }
 
+// ---- the prior of the last pass (mra_plan::PriorKeep, MRA_OPT_PRIOR_REUSE) ----------------------------------------------------------
+// The one invalidation: nothing of the last pass's prior stands.  Called by every set_* that changes what the prior depends on (the
+// kernel - on every set_kernel, values are not compared - the locations, the knots, a host covariance block, the reduce level), by every
+// option but the three that spare slv.valid, by a pass that fails or is found open, and by every pass off the fused path (its stages
+// rewrite W in place).  mra_plan_set_obs is narrower (set_obs); set_noise and the Laplace linearisation keep everything.
+static void prior_keep_reset(mra_plan* pl) {
+    pl->keep = mra_plan::PriorKeep();
+    pl->stale.n_wg = pl->stale.n_tiles = 0;
+}
+
+// What the prior stage of a fused pass launches, decided from the plan's record and the route; read at the launch (run_prior_fused).
+// Pure, like route_for and front_step_for, and like leaf_fork no PassRoute field: the route read-back does not show it.
+enum class PriorRows { RunAll, KeepAll, KeepRerunDirty };      // the row cascade in full / nothing but the refresh / the refresh + the dirty leaves' tiles
+struct PriorStep { bool run_knots = true; PriorRows rows = PriorRows::RunAll; };
+static PriorStep prior_step_for(const mra_plan* pl, const PassRoute& r) {
+    typedef mra_plan::PriorKeep K;
+    PriorStep s;
+    const K& k = pl->keep;
+    if (r.path != PassPath::Fused || pl->host_cov || !pl->use_prior_reuse || (pl->dbg & 7) || !k.knots_valid) return s;
+    s.run_knots = false;
+    if (r.scatter_ut) return s;      // (MRA_OPT_UT_GATHER off: the row cascade also scatters the leaves' Ut rows, which every pass factorises in place)
+    // a pass that reads W at every row (predict, full_rows) takes nothing less; a lik_rows pass also what the last one left at its mask's rows
+    const bool have = (k.rows == K::Rows::All && k.var_valid) || (r.lik_rows && k.rows == K::Rows::Observed && k.dirty == K::Dirty::Clean);
+    if (!have || k.dirty == K::Dirty::All) return s;
+    s.rows = k.dirty == K::Dirty::Clean ? PriorRows::KeepAll : PriorRows::KeepRerunDirty;
+    return s;
+}
+
 // ---- prior of a regular tree (PassPath::Fused): per level a tiny knot pass (knot rows cascade -> kInv -> Cholesky), then ONE cascade
 // over all leaf row tiles that writes W once ----------------------------------------------------------------------------------------
 // what every launch of the fused prior takes: the levels' knots and factors, X and W
@@ -1607,15 +1661,20 @@ static void run_prior_fused_knots(mra_plan* pl, const CascadeArgs& base) {
     }
 }
 
-// leaves W (all levels and the y block) at every row - lik_rows: at the observed rows - the prior variance, and with scatter_ut the leaves' Ut
-static void run_prior_fused_rows(mra_plan* pl, const CascadeArgs& base) {
+// leaves W (all levels and the y block) at every row - lik_rows: at the observed rows - the prior variance, and with scatter_ut the leaves' Ut.
+// only: at the rows of these workgroups' tiles alone (whole tiles of ft_row0, never gathered) - the dirty leaves of a pass that keeps the rest
+static void run_prior_fused_rows(mra_plan* pl, const CascadeArgs& base, const mra_plan::LeafTileWgs* only = nullptr) {
     const PassRoute& r = pl->route;
     Work fl;
     for (int m = 0; m < pl->NL; ++m) fl += pl->lev[m].fl_resid + pl->lev[m].fl_trsm;
     // one pass: coordinates and y in, W (all levels + y block) and the prior variance out, observed rows once more into Ut
     fl.bytes = 8.0 * pl->P * (pl->d + 1 + pl->ldw + 1) + pl->by_leaf_ut;
+    if (only) {
+        const double share = 16.0 * (double)only->n_tiles / (double)std::max<long>(pl->P, 1);
+        fl.alg *= share; fl.exec *= share; fl.bytes = share * 8.0 * pl->P * (pl->d + 1 + pl->ldw + 1);
+    }
     // a likelihood needs W at the OBSERVED rows only (Ut and the leaves' C = v(o,o) + R I are built from them)
-    if (r.lik_rows) {
+    else if (r.lik_rows) {
         ensure_lik_tiles(pl);
         const double share = 16.0 * (double)pl->n_lik_tiles / (double)std::max<long>(pl->P, 1);
         fl.alg *= share; fl.exec *= share; fl.bytes = share * 8.0 * pl->P * (pl->d + 1 + pl->ldw) + pl->by_leaf_ut;
@@ -1638,18 +1697,62 @@ static void run_prior_fused_rows(mra_plan* pl, const CascadeArgs& base) {
     if (pl->cascade_stage_all) { ar.n_wg = pl->n_fwg_leaf; ar.wg_tile0 = pl->ft_wg0_leaf.p; ar.wg_ntiles = pl->ft_wgn_leaf.p; }
     else { ar.n_wg = pl->n_fwg; ar.wg_tile0 = pl->ft_wg0.p; ar.wg_ntiles = pl->ft_wgn.p; }
     ar.tile_row0 = pl->ft_row0.p; ar.tile_chain = pl->ft_chain.p;
-    if (r.lik_rows) {
+    if (r.lik_rows) ar.var_out = nullptr;              // the prior variance is the predictive pass's (the y block stays: Ut's y row is gathered from it)
+    if (only) { ar.n_wg = only->n_wg; ar.wg_tile0 = only->wg0.p; ar.wg_ntiles = only->wgn.p; }
+    else if (r.lik_rows) {
         ar.row_gather = pl->obs_idx.p; ar.tile_chain = pl->lik_chain.p; ar.tile_leaf = pl->lik_leaf.p;
         ar.n_wg = pl->n_lik_wg; ar.wg_tile0 = pl->lik_wg0.p; ar.wg_ntiles = pl->lik_wgn.p;
-        ar.var_out = nullptr;                          // the prior variance is the predictive pass's (the y block stays: Ut's y row is gathered from it)
     }
     launch_cascade_any(pl, ar);
 }
 
+// the y block of every row once more and, on a pass that writes the variance, the prior variance put back: what stands in for the row
+// cascade where its W is kept
+static void run_prior_refresh(mra_plan* pl, bool with_var) {
+    KTimer kt(pl, KF_MISC, Work(0.0, 0.0, 8.0 * 16.0 * pl->n_ftiles * (MRA_YB + (with_var ? 3 : 1))));
+    const long n = pl->n_ftiles * 64;
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_refresh_yblock, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, pl->stream, pl->W.p, (long)pl->ldw, pl->Ka, pl->y.p,
+                       pl->ft_row0.p, pl->n_ftiles, with_var ? pl->var.p : (double*)nullptr, pl->var_prior.p);
+}
+
+// the prior variance of a full row pass, kept for the passes that keep its W (one device copy of P doubles)
+static void keep_prior_var(mra_plan* pl) {
+    if (pl->var_prior.n != (size_t)pl->P) pl->var_prior.alloc((size_t)pl->P);
+    KTimer kt(pl, KF_MISC, Work(0.0, 0.0, 16.0 * pl->P));
+    HIP_TRY(hipMemcpyAsync(pl->var_prior.p, pl->var.p, (size_t)pl->P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+}
+
+// prior_step_for decides what runs; the plan's record (pl->keep) follows every launch as it is enqueued
 static void run_prior_fused(mra_plan* pl) {
+    typedef mra_plan::PriorKeep K;
+    const PassRoute& r = pl->route;
+    const PriorStep step = prior_step_for(pl, r);
     const CascadeArgs base = prior_cascade_base(pl);
-    run_prior_fused_knots(pl, base);
-    run_prior_fused_rows(pl, base);
+    K& k = pl->keep;
+    if (step.run_knots) {
+        prior_keep_reset(pl);                // new factors: nothing that was built on the old ones stands
+        run_prior_fused_knots(pl, base);
+        k.knots_valid = true;
+    }
+    switch (step.rows) {
+        case PriorRows::RunAll:
+            run_prior_fused_rows(pl, base);
+            k.rows = r.lik_rows ? K::Rows::Observed : K::Rows::All;
+            k.dirty = K::Dirty::Clean;
+            pl->stale.n_wg = pl->stale.n_tiles = 0;
+            if (!r.lik_rows && pl->use_prior_reuse) { keep_prior_var(pl); k.var_valid = true; }
+            return;
+        case PriorRows::KeepRerunDirty:
+            run_prior_refresh(pl, !r.lik_rows);
+            run_prior_fused_rows(pl, base, pl->stale.n_wg ? &pl->stale : &pl->big);
+            k.dirty = K::Dirty::Clean;
+            pl->stale.n_wg = pl->stale.n_tiles = 0;
+            return;
+        case PriorRows::KeepAll:
+            run_prior_refresh(pl, !r.lik_rows);
+            return;
+    }
 }
 
 // predictive pass of a deep 64-wide tree (regular_hi): W holds the whitened basis after the leaf update
@@ -1753,6 +1856,7 @@ static const PassRoute& open_pass(mra_plan* pl, uint32_t flags, bool full_rows) 
         // mra_run_resume): wait for whatever it left on the two streams (every fork's work is on one of them, whether its join
         // was recorded or not), and clear the device error flag that only the last kernel of a pass resets
         pl->cphantom_valid = false;
+        prior_keep_reset(pl);
         if (pl->side_pending) HIP_TRY(hipStreamWaitEvent(pl->stream, pl->ev_join, 0));
         HIP_TRY(hipStreamSynchronize(pl->stream));
         HIP_TRY(hipStreamSynchronize(pl->stream2));
@@ -1983,13 +2087,17 @@ static void run_leaf_solve_update(mra_plan* pl, const PassRoute& r, size_t nl) {
 
 // leaves W[S,anc] -= Tt Ut^T at every leaf that does not take its update inside the predictive kernel (LeafUpdate)
 static void run_leaf_update(mra_plan* pl, const PassRoute& r, size_t nl) {
+    typedef mra_plan::PriorKeep K;
+    // what the update overwrites of the prior rows is marked here, where it is enqueued: a pass abandoned later must not look clean
     switch (r.update) {
-        case LeafUpdate::None: case LeafUpdate::InPredictHi: return;           // (InPredictHi: nothing to launch here)
+        case LeafUpdate::None: return;
+        case LeafUpdate::InPredictHi: pl->keep.dirty = K::Dirty::All; return;  // (nothing to launch here; k_predict_hi rewrites W)
         case LeafUpdate::InCascade: {
             // the small leaves (<= LEAF_SMALL_TILES observation tiles) take their update inside the predictive cascade; the few larger ones here
             // (leaf_fork: on the side stream, behind those leaves' row solve, unless the route has put this whole stage there already)
             const size_t n_small = pl->n_trsm_small;
             if (nl <= n_small) return;
+            if (pl->keep.dirty == K::Dirty::Clean) pl->keep.dirty = K::Dirty::Oversized;
             const bool to_side = pl->leaf_fork && pl->stream != pl->stream2;
             SideFork fork(pl, to_side, nullptr, pl->ev_join);
             {
@@ -2000,9 +2108,9 @@ static void run_leaf_update(mra_plan* pl, const PassRoute& r, size_t nl) {
             if (to_side) pl->side_pending = true;       // join_side_stream makes the main stream wait, just before the predictive pass
             return;
         }
-        case LeafUpdate::SolveWhole: case LeafUpdate::SolveHalves: run_leaf_solve_update(pl, r, nl); return;
-        case LeafUpdate::LeafGemm: { KTimer kt(pl, KF_LEAF_UPDATE, pl->fl_leaf_update); launch_leaf_gemm<EPI_SUB>(pl, pl->gLeafUpdate.p, nl); return; }
-        case LeafUpdate::Gemm: { KTimer kt(pl, KF_LEAF_UPDATE, pl->fl_leaf_update); launch_gemm<EPI_SUB>(pl, pl->gLeafUpdate.p, nl, pl->leaf_max_rows, pl->leaf_max_na); return; }
+        case LeafUpdate::SolveWhole: case LeafUpdate::SolveHalves: pl->keep.dirty = K::Dirty::All; run_leaf_solve_update(pl, r, nl); return;
+        case LeafUpdate::LeafGemm: { pl->keep.dirty = K::Dirty::All; KTimer kt(pl, KF_LEAF_UPDATE, pl->fl_leaf_update); launch_leaf_gemm<EPI_SUB>(pl, pl->gLeafUpdate.p, nl); return; }
+        case LeafUpdate::Gemm: { pl->keep.dirty = K::Dirty::All; KTimer kt(pl, KF_LEAF_UPDATE, pl->fl_leaf_update); launch_gemm<EPI_SUB>(pl, pl->gLeafUpdate.p, nl, pl->leaf_max_rows, pl->leaf_max_na); return; }
     }
 }
 
@@ -2255,6 +2363,7 @@ static void close_pass(mra_plan* pl, int errv) {
     pl->pass_open = false;
     if (!errv) return;
     pl->cphantom_valid = false;
+    prior_keep_reset(pl);
     char b[160];
     snprintf(b, sizeof b, "matrix not positive definite in node %d (Cholesky pivot <= 0 or NaN)", errv - 1);
     throw MraError(MRA_ERR_NOT_SPD, b);
@@ -2306,7 +2415,7 @@ static void run_all(mra_plan* pl, uint32_t flags, bool full_rows = false) {
     if (r.init_yblock) run_init_yblock(pl, r);
     // ---- 1. prior, top-down
     if (r.path == PassPath::Fused) run_prior_fused(pl);
-    else run_prior_levels(pl, r);
+    else { prior_keep_reset(pl); run_prior_levels(pl, r); }      // (Hi, Levels: their stages rewrite W in place - nothing is kept)
     phase_mark(pl, 1);
     // ---- 2. leaves
     const size_t nl = pl->leaf_nodes.size();
@@ -3079,6 +3188,7 @@ static void set_knot_coords_src(mra_plan* pl, const double* locs, const int64_t*
 static void set_knot_coords(mra_plan* pl, const double* locs) { set_knot_coords_src(pl, locs, nullptr); }
 // (src: locs is the CALLER's N x d array and padded row p holds caller row src[p]; nullptr: locs is already in padded order)
 static void set_knot_coords_src(mra_plan* pl, const double* locs, const int64_t* src) {
+    prior_keep_reset(pl);
     if (!pl->regular) return;
     const int cw = pl->cw[0];
     std::vector<std::vector<double>> kxh(pl->kc_levels);
@@ -3183,6 +3293,7 @@ static void require(bool ok, const char* msg) { if (!ok) throw MraError(MRA_ERR_
 static void set_locs(mra_plan* pl, const double* locs) {
     HIP_TRY(mraSetDevice(pl->device));
     pl->slv.valid = false;
+    prior_keep_reset(pl);
     HIP_TRY(mraMemcpy(pl->X.p, locs, (size_t)pl->P * pl->d * sizeof(double), hipMemcpyHostToDevice));
     if (!pl->knots_pending) set_knot_coords(pl, locs);
     pl->have_locs = true;
@@ -3208,6 +3319,8 @@ static void set_obs(mra_plan* pl, const double* y, double R) {
                 lv.gResid.upload(lv.hResid);
             }
     }
+    // the prior of the last pass stands (it does not depend on y or R), but W "at the observed rows" was at the old mask's
+    if (pl->keep.rows == mra_plan::PriorKeep::Rows::Observed) pl->keep.rows = mra_plan::PriorKeep::Rows::None;
     build_leaf(pl, y);
     pl->have_obs = true;
 }
@@ -3645,6 +3758,7 @@ int mra_plan_set_kernel(mra_plan* pl, int kind, const double* params, int n) {
     return guarded(pl, [&] {
         require(pl, "mra_plan_set_kernel: plan is NULL");
         pl->slv.valid = false;
+        prior_keep_reset(pl);                // on every call: the values are not compared
         if (kind == MRA_KERNEL_HOST) {
             if (!pl->have_obs) throw MraError(MRA_ERR_STATE, "MRA_KERNEL_HOST needs mra_plan_set_obs first (leaf blocks are per observed row)");
             HIP_TRY(mraSetDevice(pl->device));
@@ -3694,6 +3808,7 @@ int mra_plan_set_cov_block(mra_plan* pl, int32_t node, const double* C, int64_t 
     return guarded(pl, [&] {
         require(pl && C, "mra_plan_set_cov_block: plan or C is NULL");
         pl->slv.valid = false;
+        prior_keep_reset(pl);
         if (!pl->host_cov) throw MraError(MRA_ERR_STATE, "select MRA_KERNEL_HOST with mra_plan_set_kernel first");
         if (node < 0 || node >= pl->n_nodes) throw MraError(MRA_ERR_INVALID, "node out of range");
         HIP_TRY(mraSetDevice(pl->device));
@@ -3893,7 +4008,10 @@ int mra_plan_set_option(mra_plan* pl, int option, int64_t value) {
         // options that change which kernel produces or factorises the leaves' C blocks bring the phantom-row launch back; the others
         // (timing, front / knot / solve / update variants) never touch C
         if (option == MRA_OPT_FUSED || option == MRA_OPT_GEMM_LDS || option == MRA_OPT_LEAF_GEMM || option == MRA_OPT_CHOL_TILES) pl->cphantom_valid = false;
-        if (option != MRA_OPT_KERNEL_TIMING && option != MRA_OPT_SAMPLE_SOLVE && option != MRA_OPT_SITES_CHUNK_BYTES) pl->slv.valid = false;     // the next pass may run other kernels: mra_solve factorises again
+        if (option != MRA_OPT_KERNEL_TIMING && option != MRA_OPT_SAMPLE_SOLVE && option != MRA_OPT_SITES_CHUNK_BYTES) {
+            pl->slv.valid = false;     // the next pass may run other kernels: mra_solve factorises again
+            prior_keep_reset(pl);      // ... and its prior stage may leave W, the factors or the variance in another state
+        }
         switch (option) {
         case MRA_OPT_KERNEL_TIMING: pl->ktiming = value != 0; return MRA_OK;
         case MRA_OPT_FUSED: pl->use_fused = value != 0; return MRA_OK;
@@ -3920,6 +4038,10 @@ int mra_plan_set_option(mra_plan* pl, int option, int64_t value) {
         case MRA_OPT_PARENT_PAIR:
             if (value < 0 || value > 2) throw MraError(MRA_ERR_INVALID, "option 23: 0, 1 (where a CU gets more than one front) or 2 (wherever the fronts fit)");
             pl->use_parent_pair = (int)value;
+            return MRA_OK;
+        case MRA_OPT_PRIOR_REUSE:
+            if (value != 0 && value != 1) throw MraError(MRA_ERR_INVALID, "option 24: 0 or 1");
+            pl->use_prior_reuse = value != 0;
             return MRA_OK;
         case MRA_OPT_SAMPLE_GRAM_BYTES:
             if (value < 0) throw MraError(MRA_ERR_INVALID, "option 19: the Gram batch budget is a byte count >= 0");
@@ -3976,6 +4098,7 @@ int mra_plan_get_option(mra_plan* pl, int option, int64_t* value) {
             case MRA_OPT_UT_GATHER: *value = pl->ut_gather; break;
             case MRA_OPT_LEAF_ORDER: *value = pl->resid_longest_first ? 4 : pl->use_leaf_fork ? (pl->leaf_longest_first ? 1 : 2) : (pl->leaf_longest_first ? 3 : 0); break;
             case MRA_OPT_PARENT_PAIR: *value = pl->use_parent_pair; break;
+            case MRA_OPT_PRIOR_REUSE: *value = pl->use_prior_reuse; break;
             case MRA_OPT_CASCADE_GROUP: *value = pl->cascade_group_siblings; break;
             case MRA_OPT_SAMPLE_GRAM_BYTES: *value = (int64_t)pl->smp.gram_bytes; break;
             case MRA_OPT_SAMPLE_SOLVE: *value = pl->slv.in_sampler; break;
@@ -4163,6 +4286,7 @@ int mra_plan_set_reduce_level(mra_plan* pl, int level) {
     return guarded(pl, [&] {
         require(pl, "mra_plan_set_reduce_level: plan is NULL");
         pl->slv.valid = false;
+        prior_keep_reset(pl);
         if (level >= pl->n_levels) throw MraError(MRA_ERR_INVALID, "reduce level out of range");
         if (pl->lowrank_parent && level >= pl->n_levels - 3)
             throw MraError(MRA_ERR_INVALID, "reduce level too deep: the fronts of the leaves' parents are kept as panels on this plan (set MRA_NO_LOWRANK_PARENT=1 before creating it)");

@@ -183,6 +183,7 @@ struct DevVec {
             throw MraError(MRA_ERR_HIP, b);
         }
     }
+    void swap(DevVec& o) { std::swap(p, o.p); std::swap(n, o.n); std::swap(in_arena, o.in_arena); }
     void release() {
         if (p && !in_arena) mraFree(p);
         p = nullptr;
@@ -391,6 +392,29 @@ struct mra_plan {
     size_t n_chol_small = 0;
     bool ut_gather = true;                    // fused path: the leaves' Ut rows gathered from W by the row solve (no scatter in the row cascade: 1.21 -> 1.03 ms there, +0.16 ms in the solve)
     bool cphantom_valid = false;              // the phantom observation rows of the leaves' C blocks hold their identity rows
+    // What the last pass left of its PRIOR for the next one (MRA_OPT_PRIOR_REUSE; DESIGN.md section 4, "the prior of the last pass").  The
+    // prior depends on the locations, the knots and the kernel - not on y, the noise or (where W was written at every row) the mask.
+    // Read by prior_step_for, written where the launches are enqueued, reset by prior_keep_reset (mra_plan.hip) - the one invalidation.
+    struct PriorKeep {
+        enum class Rows { None, Observed, All };      // Observed: at the rows of the mask of the last build_leaf (a lik_rows pass)
+        enum class Dirty { Clean, Oversized, All };   // leaves whose rows of W a later stage of the last pass overwrote (Oversized: those of
+                                                      // more than LEAF_SMALL_TILES observation tiles - the plain update beside InCascade)
+        bool knots_valid = false;                     // Lp / invP / Wk of every level belong to the current kernel and locations
+        Rows rows = Rows::None;                       // W's level columns hold the prior basis at these rows
+        bool var_valid = false;                       // var_prior holds the prior variance of every row
+        Dirty dirty = Dirty::Clean;
+    } keep;
+    bool use_prior_reuse = true;              // MRA_OPT_PRIOR_REUSE
+    DevVec<double> var_prior;                 // [P] the prior variance the row cascade wrote (allocated by the first pass that keeps it)
+    // the row cascade's workgroups over the oversized leaves' tiles (build_leaf): first tile and tile count, one leaf per workgroup run,
+    // tile numbers as in ft_row0.  big: of the current mask - the leaves the next plain update dirties; stale: of the mask under which
+    // the standing keep.dirty == Oversized was set, where a set_obs has come between (n_wg 0: none, the current list is the one)
+    struct LeafTileWgs {
+        DevVec<long> wg0;
+        DevVec<int> wgn;
+        long n_wg = 0, n_tiles = 0;
+        void swap(LeafTileWgs& o) { wg0.swap(o.wg0); wgn.swap(o.wgn); std::swap(n_wg, o.n_wg); std::swap(n_tiles, o.n_tiles); }
+    } big, stale;
     int use_hi_fold = 1;                      // deep 64-wide trees: the leaf update W -= Tt Ut^T inside k_predict_hi instead of a pass over all of W (option 16)
     bool use_prior_level = true;              // levels of the level-by-level prior with blocks <= 64 wide: residual + kernel + row solve in one launch (option 15)
     bool parent_panel_lds_ok = false;         // every parent-panel problem fits the step table of the LDS-tiled segmented product
