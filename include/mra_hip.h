@@ -390,6 +390,8 @@ int mra_get_route(mra_plan *plan, int32_t *out, int capacity);
  *   MRA_BLOCK_FRONT   non-leaf: the factorised front, nf x nf (lower triangle): Lt_j (cw x cw), Zt_j below it
  *                     (na x cw), the Schur block Gt_j (na x na) - whitened ATil / omgTil / u (last block = y)
  *   MRA_BLOCK_LEAF    leaf: the panel [C = v_m(o,o) + R I (diag(r_o) with mra_plan_set_noise) -> Lc ; Ut ; Tt], (nop + na + N_j) x nop
+ *                     (Lc: the lower triangle; what stands above it is not defined - a pass that reads C from the kept
+ *                     residual, MRA_OPT_RESID_REUSE, never writes there)
  * out receives min(capacity, rows*cols) doubles row-major; *n_rows, *n_cols the block shape. */
 #define MRA_BLOCK_W_ROWS   0
 #define MRA_BLOCK_LPRIOR   1
@@ -483,6 +485,13 @@ int mra_get_timers(mra_plan *plan, double *out_ms, int capacity);
                                       bit.  1 (default); 0: every pass computes its prior, the launches are those of a plan's first pass.  Every
                                       mra_plan_set_kernel / set_locs / set_cov_block / set_reduce_level, every option but 1, 20 and 21, and a pass
                                       that fails drop what is kept; mra_plan_set_obs and set_noise do not.  mra_get_route does not report it */
+#define MRA_OPT_RESID_REUSE    25  /* fused path, k_chol_tiles routes with the Ut rows gathered: the leaves' residual V[S,o] and v(o,o) - which
+                                      depend on the kernel, the locations, the knots and the mask, not on y, R or a noise vector - go to a buffer
+                                      of the plan's own beside the panels (sum over the leaves of (n_obs16 + N_j) n_obs16 doubles, 1.35 GB at config
+                                      c3, allocated by the first such pass; a refused allocation only means that nothing is kept).  The Cholesky and
+                                      the row solves read it and store where they always did, so a pass that keeps its prior (option 24) on the
+                                      same mask launches no residual product.  Bit-identical results.  1 (default); 0: the in-place launch list.
+                                      Dropped with the prior, and by a mra_plan_set_obs whose mask differs.  mra_get_route does not report it */
 int mra_plan_set_option(mra_plan *plan, int option, int64_t value);
 /* current value of an option (so that a caller can change one temporarily and put it back) */
 int mra_plan_get_option(mra_plan *plan, int option, int64_t *value);

@@ -1672,6 +1672,12 @@ struct PanelProb {
     int ht;             // row tiles
     int ne;             // column tiles to eliminate
     int node;           // where to put 2*sum(log diag L)
+    // k_chol_tiles alone (null / 0 in every other list): the matrix is READ from src (same ld) - a kept v(o,o) that no pass overwrites,
+    // MRA_OPT_RESID_REUSE - and the noise goes on the diagonal of its first n_obs rows as the tiles are loaded: the kernel's scalar R, or
+    // its vector r at the padded rows obs[k].  L and invd are stored where they are without it.  nullptr: P is factorised in place
+    const double* src;
+    const int* obs;
+    int n_obs;
 };
 
 #ifndef MRA_KERNELS_TEMPLATES_ONLY      /* non-template kernel: defined once, in the translation unit of mra_plan.hip */
@@ -1864,7 +1870,7 @@ __global__ __launch_bounds__(256, 4) void k_chol_wave(const PanelProb* __restric
 // ------------------------------------------------------------------------------------------------
 template <int NT, int NW>
 __global__ __launch_bounds__(NW * 64, NT <= 8 ? 3 : 2) void k_chol_tiles(const PanelProb* __restrict__ probs, double* __restrict__ dnode,
-                                                                      int* __restrict__ err) {
+                                                                      int* __restrict__ err, double R, const double* __restrict__ noise) {
     constexpr int NWK = NW - 1;
     constexpr int NOFF = NT * (NT - 1) / 2;
     constexpr int NSLOT = (NOFF + NWK - 1) / NWK;
@@ -1881,6 +1887,7 @@ __global__ __launch_bounds__(NW * 64, NT <= 8 ? 3 : 2) void k_chol_tiles(const P
         if (threadIdx.x == 0) dnode[pb.node] = 0.0;
         return;
     }
+    const double* src = pb.src ? pb.src : pb.P;                   // every tile is loaded once, before any store
     // ---- diagonal tiles into LDS (16-byte pieces, all loads of a thread in flight before its first write)
     {
         constexpr int PD = (NT * 128 + NTH - 1) / NTH;
@@ -1891,7 +1898,13 @@ __global__ __launch_bounds__(NW * 64, NT <= 8 ? 3 : 2) void k_chol_tiles(const P
             int e = (int)threadIdx.x + i * NTH;
             e = e < total ? e : total - 1;
             const int tile = e >> 7, row = (e >> 3) & 15, c2 = (e & 7) << 1;
-            v[i] = gld2(pb.P + (long)(tile * 16 + row) * pb.ld + tile * 16 + c2);
+            v[i] = gld2(src + (long)(tile * 16 + row) * pb.ld + tile * 16 + c2);
+            // (out of place) the kept block is v(o,o) + 0: the diagonal of a true observation takes its one rounding of v + r here
+            const int k = tile * 16 + row;
+            if (pb.src && k < pb.n_obs && (row & ~1) == c2) {
+                const double add = noise ? gld(noise + gldi(pb.obs + k)) : R;
+                if (row & 1) v[i][1] += add; else v[i][0] += add;
+            }
         }
 #pragma unroll
         for (int i = 0; i < PD; ++i) {
@@ -1959,7 +1972,7 @@ __global__ __launch_bounds__(NW * 64, NT <= 8 ? 3 : 2) void k_chol_tiles(const P
             tib[s] = (t < NOFF && ib < nt) ? ib : 0;            // 0: no such tile in this matrix
             tjc[s] = t - ib * (ib - 1) / 2;
             T[s] = zero;
-            if (tib[s]) T[s] = gld4(pb.P + (long)(tib[s] * 16 + r) * pb.ld + tjc[s] * 16 + 4 * q);
+            if (tib[s]) T[s] = gld4(src + (long)(tib[s] * 16 + r) * pb.ld + tjc[s] * 16 + 4 * q);
         }
         __syncthreads();
 #pragma unroll 1
@@ -2105,6 +2118,10 @@ struct Trsm2Prob {
     const double* gW;
     long gld;
     int gtiles;
+    // (MRA_OPT_RESID_REUSE) the row tiles from gtiles on take their right-hand side from src (row tile t - gtiles, row stride ldsrc) - a
+    // kept V[S,o] that no pass overwrites - and are stored in X as ever; nullptr: solved in place
+    const double* src;
+    long ldsrc;
 };
 
 
@@ -2161,6 +2178,7 @@ __global__ __launch_bounds__(512) void k_trsm_rows2(const Trsm2Prob* __restrict_
 #endif
         MRA_TSTAMP(2);
         double* xp = pb.X + (long)t * 16 * pb.ldx + (long)r * pb.ldx + 4 * q;
+        const double* lp = (pb.src && t >= pb.gtiles) ? pb.src + ((long)(t - pb.gtiles) * 16 + r) * pb.ldsrc + 4 * q : xp;
         d4 x[NTMAX];
         double ssq = 0.0;
         // the whole row of tiles is fetched first (independent loads in flight together); read one
@@ -2175,7 +2193,7 @@ __global__ __launch_bounds__(512) void k_trsm_rows2(const Trsm2Prob* __restrict_
                         x[jb][j] = gi < 0 ? 0.0 : gld(pb.gW + (long)gi * pb.gld + t * 16 + r);
                     }
                 } else {
-                    x[jb] = gld4(xp + jb * 16);
+                    x[jb] = gld4(lp + jb * 16);
                 }
             }
         }

@@ -797,6 +797,7 @@ static void build_obs_lists(mra_plan* pl, const double* y, LeafDescs& d) {
         }
     }, leaves_per_thread);
     pl->obs_idx.upload(obs); pl->obs_pos.upload(opos); pl->leaf_nobs.upload(nobs);
+    pl->obs_list_host.swap(obs);                       // (the mask a kept residual belongs to: set_obs compares)
     pl->obs_off_host = obs_off; pl->lik_tiles_valid = false; pl->lik_general_valid = false;
     pl->y_finite_host.assign(pl->P, 0);
     for (long p2 = 0; p2 < pl->P; ++p2) pl->y_finite_host[p2] = std::isfinite(y[p2]) ? 1 : 0;
@@ -1146,7 +1147,9 @@ static void upload_leaf_descriptors(mra_plan* pl, const LeafDescs& d, const std:
     pl->gLeaf.upload(d.lp); pl->gLeafResid.upload(d.resid); pl->gLeafSyrk.upload(d.syrk); pl->gLeafUpdate.upload(d.upd);
     pl->gLeafCholFull.upload(d.chol_full); pl->gLeafCholLik.upload(d.chol_lik); pl->gLeafCholC.upload(d.chol_c);
     // (k_chol_tiles<8, 4> at three workgroups per CU for the small matrices, then the few larger ones)
-    pl->gLeafCholSorted.upload(in_order(d.chol_c, order));
+    pl->hLeafCholSorted = in_order(d.chol_c, order);
+    pl->gLeafCholSorted.upload(pl->hLeafCholSorted);
+    pl->hLeaf = d.lp;
 }
 
 // The row solves: in leaf order (level-by-level path), and small first for the fused path - most leaves are small and get the
@@ -1166,6 +1169,7 @@ static void build_leaf_row_solves(mra_plan* pl, const LeafDescs& d, const std::v
     }
     pl->gLeafTrsmFullPlain.upload(tf); pl->gLeafTrsmLikPlain.upload(tk);
     pl->gLeafTrsmFullPlainG.upload(tfg); pl->gLeafTrsmLikPlainG.upload(tkg);
+    pl->hLeafTrsmFullPlainG = tfg;
 }
 
 // fused row solve + update (k_leaf_solve_update) for the small leaves, whole and in two halves, and the plain update of the others,
@@ -1192,6 +1196,7 @@ static void build_leaf_solve_lists(mra_plan* pl, const LeafDescs& d, const std::
     pl->gLeafSolve.upload(sp);
     pl->gLeafUpdatePlain.upload(in_order(d.upd, order));
     std::vector<LeafSolveProb> half;
+    pl->hLeafSolveHalfPos.clear();
     for (size_t k = 0; k < n_small; ++k) {
         const LeafSolveProb& q = sp[k];
         const int h0 = (q.nrt + 1) / 2;
@@ -1201,10 +1206,12 @@ static void build_leaf_solve_lists(mra_plan* pl, const LeafDescs& d, const std::
             if (t1 <= t0) continue;
             h.V = q.V + (size_t)t0 * 16 * q.ldx; h.Wr = q.Wr + (size_t)t0 * 16 * q.ldw; h.var = q.var + (size_t)t0 * 16; h.nrt = t1 - t0;
             half.push_back(h);
+            pl->hLeafSolveHalfPos.push_back(k);
         }
     }
     pl->n_leaf_solve_half = half.size();
     pl->gLeafSolveHalf.upload(half);
+    pl->hLeafSolve = sp; pl->hLeafSolveHalf = half;
     std::vector<long> lr0(nl);
     std::vector<unsigned char> lup(nl, 0);
     for (size_t t = 0; t < nl; ++t) lr0[t] = pl->row0[pl->leaf_nodes[t]];
@@ -1244,6 +1251,7 @@ static void build_leaf(mra_plan* pl, const double* y) {
     PlanTrace tr("build_leaf");
     ArenaScope arena(&pl->arena);
     pl->cphantom_valid = false;
+    pl->resid_lists = pl->resid_refused = false;       // the kept residual's descriptors point into the panels as well
     pl->slv.valid = false; pl->slv.built = false;      // mra_solve's descriptors point into the leaves' panels
     pl->cov.built = false;                             // mra_cov_apply's read the solver's level offsets
     pl->sit.built = false;                             // mra_predict_sites' read the solver's leaf descriptors
@@ -1403,13 +1411,18 @@ static void launch_parent_front(mra_plan* pl, int nacc, size_t nprob, size_t lds
 // registers, next diagonal block factorised beside the trailing update; k_chol_wave: one wave per matrix
 // (TilesSplit is two launches: `part` picks the small leaves', the others', or both)
 enum class LeafPart { All, Small, Rest };
+// (out of place - resid_out_of_place - k_chol_tiles reads the kept C0 and puts the noise on its diagonal itself: the scalar, or the vector)
+static bool resid_out_of_place(const mra_plan* pl, const PassRoute& r);
 static void launch_leaf_chol(mra_plan* pl, const PassRoute& r, size_t nl, LeafPart part = LeafPart::All) {
     const size_t ns = pl->n_chol_small;      // (gLeafCholSorted: the leaves of at most LEAF_SMALL_TILES tiles first)
+    const PanelProb* list = resid_out_of_place(pl, r) ? pl->kLeafCholSorted.p : pl->gLeafCholSorted.p;
+    const double R = pl->noise_on ? 0.0 : pl->R;
+    const double* noise = pl->noise_on ? pl->noise.p : nullptr;
     if (r.chol == LeafChol::TilesSplit) {
-        if (ns && part != LeafPart::Rest) hipLaunchKernelGGL((k_chol_tiles<8, 4>), dim3((unsigned)ns), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p, pl->dnode.p, pl->errflag.p);
-        if (nl > ns && part != LeafPart::Small) hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)(nl - ns)), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p + ns, pl->dnode.p, pl->errflag.p);
+        if (ns && part != LeafPart::Rest) hipLaunchKernelGGL((k_chol_tiles<8, 4>), dim3((unsigned)ns), dim3(256), 0, pl->stream, list, pl->dnode.p, pl->errflag.p, R, noise);
+        if (nl > ns && part != LeafPart::Small) hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)(nl - ns)), dim3(256), 0, pl->stream, list + ns, pl->dnode.p, pl->errflag.p, R, noise);
     }
-    else if (r.chol == LeafChol::TilesOne) hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)nl), dim3(256), 0, pl->stream, pl->gLeafCholSorted.p, pl->dnode.p, pl->errflag.p);
+    else if (r.chol == LeafChol::TilesOne) hipLaunchKernelGGL((k_chol_tiles<10, 4>), dim3((unsigned)nl), dim3(256), 0, pl->stream, list, pl->dnode.p, pl->errflag.p, R, noise);
     else hipLaunchKernelGGL((k_chol_wave<LEAF_MAX_TILES>), dim3((unsigned)((nl + 3) / 4)), dim3(256), 0, pl->stream, pl->gLeafCholC.p, (int)nl, pl->dnode.p, pl->errflag.p);
 }
 
@@ -1593,6 +1606,81 @@ static PassRoute route_for(const mra_plan* pl, uint32_t flags, bool full_rows) {
 static void prior_keep_reset(mra_plan* pl) {
     pl->keep = mra_plan::PriorKeep();
     pl->stale.n_wg = pl->stale.n_tiles = 0;
+    pl->rkeep = mra_plan::ResidKeep();       // the leaves' residual is built on the prior
+}
+
+// ---- the leaves' residual of the last pass (mra_plan::ResidKeep, MRA_OPT_RESID_REUSE) ------------------------------------------------
+// Does this route run its leaf stage OUT OF PLACE - product into the kept buffer, Cholesky and solves reading it?  Pure.  The fused
+// path with a device covariance, the Ut rows gathered by the row solve, and k_chol_tiles (either launch form, both halves of the leaf
+// fork) - the one factorisation that loads its matrix whole before it stores.  Every other route (k_chol_wave, the big panels, host
+// covariance, Hi, Levels, a residual product that is neither the gathered C-only one nor k_leaf_gemm) runs the in-place launch list.
+static bool resid_route_eligible(const mra_plan* pl, const PassRoute& r) {
+    if (r.path != PassPath::Fused || pl->host_cov || !pl->use_resid_reuse || (pl->dbg & 7) || pl->resid_refused) return false;
+    if (!pl->ut_gather || r.scatter_ut || pl->leaf_nodes.empty()) return false;
+    if (r.chol != LeafChol::TilesOne && r.chol != LeafChol::TilesSplit) return false;
+    return r.c_only ? r.c_fix == LeafCFix::InProduct : (r.leaf_resident && r.c_fix == LeafCFix::Phantom);
+}
+// ... and has the buffer and its descriptor lists (run_leaf_product asks for them first): what every launch of the leaf stage reads
+static bool resid_out_of_place(const mra_plan* pl, const PassRoute& r) { return pl->resid_lists && resid_route_eligible(pl, r); }
+
+// What the residual product of a pass does, decided from the plan's record and the route; read at the launch (run_leaf_product), where
+// the record is updated too.  Pure, like prior_step_for.  Keep: the record was left by this route's own product form, under this mask,
+// on this prior (a pass whose prior stage ran its knots has reset the record before this is read).
+enum class ResidStep { InPlace, Run, Keep };
+static ResidStep resid_step_for(const mra_plan* pl, const PassRoute& r) {
+    typedef mra_plan::ResidKeep K;
+    if (!resid_out_of_place(pl, r)) return ResidStep::InPlace;
+    const K::Form form = r.c_only ? K::Form::COnly : K::Form::Full;
+    return (pl->keep.knots_valid && pl->rkeep.resid == form) ? ResidStep::Keep : ResidStep::Run;
+}
+
+// The kept buffer [per leaf: C0 ; V0] and the lists that point into it, for the mask of the last build_leaf.  A refused allocation
+// clears the error and marks the plan: its passes run in place until the next mra_plan_set_obs asks again.
+static void ensure_resid_lists(mra_plan* pl) {
+    if (pl->resid_lists || pl->resid_refused) return;
+    const size_t nl = pl->leaf_nodes.size();
+    pl->leaf_koff.assign(nl + 1, 0);
+    for (size_t t = 0; t < nl; ++t) {
+        const long nop = pl->leaf_nop[t], nr = pl->row1[pl->leaf_nodes[t]] - pl->row0[pl->leaf_nodes[t]];
+        pl->leaf_koff[t + 1] = pl->leaf_koff[t] + (nop + nr) * nop;
+    }
+    const size_t need = (size_t)std::max<long>(pl->leaf_koff.back(), 1);
+    if (pl->resid.n != need) {
+        pl->resid.release();
+        pl->rkeep = mra_plan::ResidKeep();
+        double* p = nullptr;
+        if (mraMalloc((void**)&p, need * sizeof(double)) != hipSuccess) { (void)hipGetLastError(); pl->resid_refused = true; return; }
+        pl->resid.p = p; pl->resid.n = need;
+    }
+    auto C0 = [&](size_t t) { return pl->resid.p + pl->leaf_koff[t]; };
+    auto V0 = [&](size_t t) { return C0(t) + (size_t)pl->leaf_nop[t] * pl->leaf_nop[t]; };
+    const std::vector<size_t>& order = pl->leaf_order;
+    std::vector<GemmProb> full = pl->hLeafResid, lik = pl->hLeafResidLik;
+    std::vector<LeafProb> lp = pl->hLeaf;
+    for (size_t t = 0; t < nl; ++t) {
+        full[t].C = V0(t); full[t].C2 = C0(t); full[t].diag_add = 0.0;      // v(o,o) + 0, as while a noise vector is set
+        lik[t].C = C0(t); lik[t].diag_add = 0.0;
+        lp[t].Pn = C0(t);
+    }
+    pl->kLeafResid.upload(pl->gLeafResidSorted.n ? in_order(full, order) : full);
+    pl->kLeafResidLik.upload(pl->gLeafResidLikSorted.n ? in_order(lik, order) : lik);
+    pl->kLeaf.upload(lp);
+    std::vector<PanelProb> ch = pl->hLeafCholSorted;
+    std::vector<Trsm2Prob> ts = pl->hLeafTrsmFullPlainG;
+    std::vector<LeafSolveProb> sp = pl->hLeafSolve, half = pl->hLeafSolveHalf;
+    for (size_t k = 0; k < nl; ++k) {
+        const size_t t = order[k];
+        ch[k].src = C0(t); ch[k].obs = pl->obs_idx.p + pl->obs_off_host[t]; ch[k].n_obs = pl->leaf_nobs_host[t];
+        ts[k].src = V0(t); ts[k].ldsrc = pl->leaf_nop[t];
+        sp[k].V = V0(t);
+    }
+    for (size_t h = 0; h < half.size(); ++h) {
+        const size_t k = pl->hLeafSolveHalfPos[h];
+        half[h].V = sp[k].V + (half[h].V - pl->hLeafSolve[k].V);                // the same row tiles of V0
+    }
+    pl->kLeafCholSorted.upload(ch); pl->kLeafTrsmFullPlainG.upload(ts);
+    pl->kLeafSolve.upload(sp); pl->kLeafSolveHalf.upload(half);
+    pl->resid_lists = true;
 }
 
 // What the prior stage of a fused pass launches, decided from the plan's record and the route; read at the launch (run_prior_fused).
@@ -1938,8 +2026,19 @@ static void run_prior_levels(mra_plan* pl, const PassRoute& r) {
 
 // ---- leaves (nl of them, nl > 0).  A leaf's panel is [C ; Ut ; V] (leaf_C / leaf_Ut / leaf_V) ------------------------------------
 // leaves every leaf's V[S,o] residual with C = v(o,o) + R I (+ 0 while a noise vector is set) on top of it, or with c_only nothing but C
+// (resid_step_for: on an eligible route into the kept buffer, or not at all where the last pass's product stands)
 static void run_leaf_product(mra_plan* pl, const PassRoute& r, size_t nl) {
+    if (resid_route_eligible(pl, r)) ensure_resid_lists(pl);
+    const ResidStep step = resid_step_for(pl, r);
+    if (step == ResidStep::Keep) return;
     KTimer kt(pl, KF_LEAF_RESID, r.c_only ? pl->fl_leaf_c_only : pl->fl_leaf_resid);
+    if (step == ResidStep::Run) {
+        pl->rkeep.resid = mra_plan::ResidKeep::Form::None;      // (until the launch is enqueued)
+        if (r.c_only) launch_gemm<EPI_COV>(pl, pl->kLeafResidLik.p, nl, pl->leaf_max_nop, pl->leaf_max_nop);
+        else launch_leaf_gemm<EPI_COV>(pl, pl->kLeafResid.p, nl);
+        pl->rkeep.resid = r.c_only ? mra_plan::ResidKeep::Form::COnly : mra_plan::ResidKeep::Form::Full;
+        return;
+    }
     if (pl->host_cov) {
         if (r.leaf_resident) launch_leaf_gemm<EPI_HOSTCOV>(pl, pl->gLeafResid.p, nl);
         else launch_gemm<EPI_HOSTCOV>(pl, pl->gLeafResid.p, nl, pl->leaf_max_rows, pl->leaf_max_nop);
@@ -1954,7 +2053,13 @@ static void run_leaf_c_fix(mra_plan* pl, const PassRoute& r, size_t nl) {
     if (r.c_fix == LeafCFix::None) return;
     KTimer kt(pl, KF_MISC, 0);
     // (InProduct: nothing to do, the gathered COV product wrote the whole C block including phantom identities)
-    if (r.c_fix == LeafCFix::Phantom) {
+    if (r.c_fix == LeafCFix::Phantom && resid_out_of_place(pl, r)) {
+        // the kept C0 is never factorised in place and the gathered C-only product writes identity rows there too: once per mask
+        if (!pl->rkeep.phantom) {
+            hipLaunchKernelGGL(k_leaf_cphantom, dim3((unsigned)nl), dim3(256), 0, pl->stream, pl->kLeaf.p, pl->leaf_nobs.p);
+            pl->rkeep.phantom = true;
+        }
+    } else if (r.c_fix == LeafCFix::Phantom) {
         // C comes from the COV epilogue, Ut from the gather inside k_trsm_rows2: only the phantom rows remain
         // ... once: an identity row stays an identity row under the in-place factorisation (L[p][j] = 0, L[p][p] = 1 exactly) and
         // no epilogue writes there, so later passes find them in place.  (A failed pass - NaN times 0 - a new observation pattern
@@ -1972,8 +2077,9 @@ static void run_leaf_c_fix(mra_plan* pl, const PassRoute& r, size_t nl) {
 
 // (a noise vector is set) leaves C = v(o,o) + diag(r_o): the stages above wrote v(o,o) + 0, exactly v(o,o), so the diagonal takes the one
 // rounding of the scalar path's v + R.  On the main stream, before the leaves' fork; every route and both kinds of pass come through here
-static void run_leaf_noise(mra_plan* pl, size_t nl) {
-    if (!pl->noise_on) return;
+// (out of place k_chol_tiles adds it as it loads the diagonal tiles: nothing to launch)
+static void run_leaf_noise(mra_plan* pl, const PassRoute& r, size_t nl) {
+    if (!pl->noise_on || resid_out_of_place(pl, r)) return;
     KTimer kt(pl, KF_MISC, 0);
     hipLaunchKernelGGL(k_leaf_noise, dim3((unsigned)((nl + 3) / 4)), dim3(256), 0, pl->stream, pl->gLeaf.p, pl->leaf_nobs.p, pl->noise.p, (int)nl);
 }
@@ -2015,7 +2121,11 @@ static void run_leaf_chol_and_solve(mra_plan* pl, const PassRoute& r, size_t nl)
     const int small_row_tiles = (r.predict && !r.solve_fused) ? pl->trsm_small_tiles_full : pl->trsm_small_tiles_lik;
     // the few leaves with more than LEAF_SMALL_TILES observation tiles: several workgroups per leaf when they are few
     // (one leaf per workgroup would put a single 65 us workgroup on the critical path)
-    auto solve_rest = [&] { launch_trsm2(pl, r.trsm_all + n_small, nl - n_small, obs_tiles, row_tiles, (nl - n_small) < 512 ? 4 : row_tiles); };
+    // out of place: the predict lists that read the kept V0 (the likelihood-only lists hold the Ut rows alone, gathered from W as ever)
+    const bool oop = resid_out_of_place(pl, r);
+    auto kept = [&](const Trsm2Prob* p) { return (oop && p == pl->gLeafTrsmFullPlainG.p) ? pl->kLeafTrsmFullPlainG.p : p; };
+    const Trsm2Prob *trsm_all = kept(r.trsm_all), *trsm_small = kept(r.trsm_small);
+    auto solve_rest = [&] { launch_trsm2(pl, trsm_all + n_small, nl - n_small, obs_tiles, row_tiles, (nl - n_small) < 512 ? 4 : row_tiles); };
     if (pl->leaf_fork) {
         SideFork fork(pl, true, pl->ev_leaf_fork, pl->ev_leaf_join);
         launch_leaf_chol(pl, r, nl, LeafPart::Rest);
@@ -2023,7 +2133,7 @@ static void run_leaf_chol_and_solve(mra_plan* pl, const PassRoute& r, size_t nl)
         fork.join();
     }
     launch_leaf_chol(pl, r, nl, pl->leaf_fork ? LeafPart::Small : LeafPart::All);
-    if (n_small) launch_trsm2(pl, r.trsm_small, n_small, pl->trsm_small_nt, small_row_tiles, small_row_tiles);
+    if (n_small) launch_trsm2(pl, trsm_small, n_small, pl->trsm_small_nt, small_row_tiles, small_row_tiles);
     if (pl->leaf_fork) HIP_TRY(hipStreamWaitEvent(pl->stream, pl->ev_leaf_join, 0));
     else if (nl > n_small) solve_rest();
 }
@@ -2075,13 +2185,14 @@ static void run_leaf_solve_update(mra_plan* pl, const PassRoute& r, size_t nl) {
     ensure_big_lds(pl, {(const void*)k_leaf_solve_update<8, 13, true>});
     KTimer kt(pl, KF_LEAF_UPDATE, pl->fl_leaf_update);
     const size_t n_small = pl->n_trsm_small;
+    const bool oop = resid_out_of_place(pl, r);          // the small leaves' V from the kept V0
 #ifdef MRA_STAMPS
     stamp_buffer(pl->kstamps2, pl->n_leaf_solve_half * 8);
 #endif
     if (r.update == LeafUpdate::SolveHalves)
-        hipLaunchKernelGGL((k_leaf_solve_update<8, 13, true>), dim3((unsigned)pl->n_leaf_solve_half), dim3(512), pl->leaf_solve_lds, pl->stream, pl->gLeafSolveHalf.p MRA_LSTAMP_VAL);
+        hipLaunchKernelGGL((k_leaf_solve_update<8, 13, true>), dim3((unsigned)pl->n_leaf_solve_half), dim3(512), pl->leaf_solve_lds, pl->stream, oop ? pl->kLeafSolveHalf.p : pl->gLeafSolveHalf.p MRA_LSTAMP_VAL);
     else
-        hipLaunchKernelGGL((k_leaf_solve_update<8, 13, true>), dim3((unsigned)n_small), dim3(512), pl->leaf_solve_lds, pl->stream, pl->gLeafSolve.p MRA_LSTAMP_NUL);
+        hipLaunchKernelGGL((k_leaf_solve_update<8, 13, true>), dim3((unsigned)n_small), dim3(512), pl->leaf_solve_lds, pl->stream, oop ? pl->kLeafSolve.p : pl->gLeafSolve.p MRA_LSTAMP_NUL);
     if (nl > n_small) launch_gemm<EPI_SUB>(pl, pl->gLeafUpdatePlain.p + n_small, nl - n_small, pl->leaf_max_rows, pl->leaf_max_na);
 }
 
@@ -2422,7 +2533,7 @@ static void run_all(mra_plan* pl, uint32_t flags, bool full_rows = false) {
     if (nl) {
         run_leaf_product(pl, r, nl);
         run_leaf_c_fix(pl, r, nl);
-        run_leaf_noise(pl, nl);
+        run_leaf_noise(pl, r, nl);
         run_leaf_factor(pl, r, nl);
         if (!r.direct_parent) run_leaf_syrk(pl, nl);
         if (r.predict) run_leaf_predict_work(pl, r, nl);
@@ -3321,7 +3432,11 @@ static void set_obs(mra_plan* pl, const double* y, double R) {
     }
     // the prior of the last pass stands (it does not depend on y or R), but W "at the observed rows" was at the old mask's
     if (pl->keep.rows == mra_plan::PriorKeep::Rows::Observed) pl->keep.rows = mra_plan::PriorKeep::Rows::None;
+    // ... and the leaves' kept residual stands where the observed-row list does (new y on the old mask)
+    std::vector<int> standing;
+    standing.swap(pl->obs_list_host);
     build_leaf(pl, y);
+    if (standing != pl->obs_list_host) pl->rkeep = mra_plan::ResidKeep();
     pl->have_obs = true;
 }
 
@@ -4007,7 +4122,7 @@ int mra_plan_set_option(mra_plan* pl, int option, int64_t value) {
         require(pl, "mra_plan_set_option: plan is NULL");
         // options that change which kernel produces or factorises the leaves' C blocks bring the phantom-row launch back; the others
         // (timing, front / knot / solve / update variants) never touch C
-        if (option == MRA_OPT_FUSED || option == MRA_OPT_GEMM_LDS || option == MRA_OPT_LEAF_GEMM || option == MRA_OPT_CHOL_TILES) pl->cphantom_valid = false;
+        if (option == MRA_OPT_FUSED || option == MRA_OPT_GEMM_LDS || option == MRA_OPT_LEAF_GEMM || option == MRA_OPT_CHOL_TILES || option == MRA_OPT_RESID_REUSE) pl->cphantom_valid = false;
         if (option != MRA_OPT_KERNEL_TIMING && option != MRA_OPT_SAMPLE_SOLVE && option != MRA_OPT_SITES_CHUNK_BYTES) {
             pl->slv.valid = false;     // the next pass may run other kernels: mra_solve factorises again
             prior_keep_reset(pl);      // ... and its prior stage may leave W, the factors or the variance in another state
@@ -4042,6 +4157,10 @@ int mra_plan_set_option(mra_plan* pl, int option, int64_t value) {
         case MRA_OPT_PRIOR_REUSE:
             if (value != 0 && value != 1) throw MraError(MRA_ERR_INVALID, "option 24: 0 or 1");
             pl->use_prior_reuse = value != 0;
+            return MRA_OK;
+        case MRA_OPT_RESID_REUSE:
+            if (value != 0 && value != 1) throw MraError(MRA_ERR_INVALID, "option 25: 0 or 1");
+            pl->use_resid_reuse = value != 0;
             return MRA_OK;
         case MRA_OPT_SAMPLE_GRAM_BYTES:
             if (value < 0) throw MraError(MRA_ERR_INVALID, "option 19: the Gram batch budget is a byte count >= 0");
@@ -4099,6 +4218,7 @@ int mra_plan_get_option(mra_plan* pl, int option, int64_t* value) {
             case MRA_OPT_LEAF_ORDER: *value = pl->resid_longest_first ? 4 : pl->use_leaf_fork ? (pl->leaf_longest_first ? 1 : 2) : (pl->leaf_longest_first ? 3 : 0); break;
             case MRA_OPT_PARENT_PAIR: *value = pl->use_parent_pair; break;
             case MRA_OPT_PRIOR_REUSE: *value = pl->use_prior_reuse; break;
+            case MRA_OPT_RESID_REUSE: *value = pl->use_resid_reuse; break;
             case MRA_OPT_CASCADE_GROUP: *value = pl->cascade_group_siblings; break;
             case MRA_OPT_SAMPLE_GRAM_BYTES: *value = (int64_t)pl->smp.gram_bytes; break;
             case MRA_OPT_SAMPLE_SOLVE: *value = pl->slv.in_sampler; break;

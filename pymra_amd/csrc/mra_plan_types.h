@@ -404,6 +404,35 @@ struct mra_plan {
         bool var_valid = false;                       // var_prior holds the prior variance of every row
         Dirty dirty = Dirty::Clean;
     } keep;
+    // What the last pass left of the leaves' RESIDUAL (MRA_OPT_RESID_REUSE): V0 = V[S,o] = kernel(x_S, x_o) - W_S W_o^T
+    // and C0 = v(o,o) + 0 depend on what the prior depends on and on the mask - not on y, R or a noise vector.  A pass on an eligible
+    // route (resid_step_for) writes them into `resid` instead of the panel; k_chol_tiles, k_trsm_rows2 and k_leaf_solve_update read them
+    // there and store L, Tt and W where they always did, so the next pass launches no residual product.  Reset with `keep`
+    // (prior_keep_reset) and by a mra_plan_set_obs whose observed-row list differs from the standing one.
+    struct ResidKeep {
+        enum class Form { None, COnly, Full };        // COnly: C0 from the gathered k_gemm_nt_lds product; Full: C0 and V0 from k_leaf_gemm.
+                                                      // The two sum in different orders: a pass never takes the other form's C0
+        Form resid = Form::None;
+        bool phantom = false;                         // C0's phantom observation rows hold their identity rows
+    } rkeep;
+    bool use_resid_reuse = true;              // MRA_OPT_RESID_REUSE
+    // [per leaf: C0 (nop x nop) ; V0 (N_j x nop)], row stride nop, leaves in leaf order: allocated by the first eligible pass (a refused
+    // allocation: resid_refused, no pass keeps until the next mra_plan_set_obs), and the descriptor lists that point into it - the
+    // plan's own lists with C / C2 / src / V redirected and diag_add 0, rebuilt after every build_leaf (resid_lists)
+    DevVec<double> resid;
+    std::vector<long> leaf_koff;              // [leaf + 1] offsets into resid
+    bool resid_lists = false, resid_refused = false;
+    std::vector<int> obs_list_host;           // obs_idx as build_leaf uploaded it: the mask `rkeep` belongs to
+    std::vector<PanelProb> hLeafCholSorted;   // host copies of the lists the kept ones are made from (build_leaf)
+    std::vector<Trsm2Prob> hLeafTrsmFullPlainG;
+    std::vector<LeafSolveProb> hLeafSolve, hLeafSolveHalf;
+    std::vector<size_t> hLeafSolveHalfPos;    // a half's position in hLeafSolve
+    std::vector<LeafProb> hLeaf;
+    DevVec<GemmProb> kLeafResid, kLeafResidLik;       // in the order run_leaf_product launches (sorted when the plan's are)
+    DevVec<PanelProb> kLeafCholSorted;
+    DevVec<Trsm2Prob> kLeafTrsmFullPlainG;
+    DevVec<LeafSolveProb> kLeafSolve, kLeafSolveHalf;
+    DevVec<LeafProb> kLeaf;
     bool use_prior_reuse = true;              // MRA_OPT_PRIOR_REUSE
     DevVec<double> var_prior;                 // [P] the prior variance the row cascade wrote (allocated by the first pass that keeps it)
     // the row cascade's workgroups over the oversized leaves' tiles (build_leaf): first tile and tile count, one leaf per workgroup run,

@@ -41,6 +41,7 @@ MRA_OPT_SITES_CHUNK_BYTES = 21
 MRA_OPT_LEAF_ORDER = 22
 MRA_OPT_PARENT_PAIR = 23
 MRA_OPT_PRIOR_REUSE = 24
+MRA_OPT_RESID_REUSE = 25
 MRA_FAMILY_GAUSSIAN, MRA_FAMILY_POISSON, MRA_FAMILY_BINOMIAL = 0, 1, 2
 LAPLACE_FAMILIES = {"gaussian": MRA_FAMILY_GAUSSIAN, "poisson": MRA_FAMILY_POISSON, "binomial": MRA_FAMILY_BINOMIAL}
 LAPLACE_INFO = ("d", "u", "neg2logp", "sum_log_D", "sum_D_res2", "passes", "step", "converged")      # info[8] of mra_plan_fit_laplace
