@@ -325,6 +325,43 @@ int mra_sample_sites_slots(mra_plan *plan, int64_t n_sites, int64_t *n_slots);  
 int mra_sample_sites(mra_plan *plan, uint32_t flags, int64_t n_sites, const double *sites, const int32_t *leaf,
                      int64_t n_samples, uint64_t seed, int64_t sample0, const double *z, double *out);
 
+/* Cross-validation of the fitted model from the retained factors, without a refit (no counterpart in the reference; DESIGN.md section
+ * 18).  With o the observed rows, D = diag(r_o) the noise (the scalar R or the vector of mra_plan_set_noise), K = Sigma[o, o] + D, m and
+ * Sigma_post the posterior mean and covariance of the latent field given all the data and rho = y - m: K^-1 = D^-1 - D^-1 Sigma_post D^-1
+ * and K^-1 y = D^-1 rho, so for a group G of observed rows and N_G = D_G - Sigma_post[G, G] = L L^T the predictive distribution of y_G
+ * given every observation OUTSIDE G is
+ *     mean mu_G = y_G - D_G N_G^-1 rho_G,   covariance S_G = D_G N_G^-1 D_G (the noise of the new observation included),
+ *     log N(y_G; mu_G, S_G) = -1/2 [2 sum log r_p - log det N_G + |L^-1 rho_G|^2 + |G| log 2 pi].
+ * flags: 0 - leave one out, every observed row its own group: with h_p = v_p / r_p (v the posterior variance) mu_p = y_p -
+ * rho_p / (1 - h_p) and S_pp = r_p / (1 - h_p); MRA_CV_LEAF - the groups are the observed rows of each leaf (spatial block
+ * cross-validation on the tree's own partition), Sigma_post[G, G] by mra_sites_cov's same-leaf formula with the rows as sites.
+ *     mean_perm, var_perm, lpd_perm   (P each, padded leaf order, any may be NULL): mu_p, S_pp - the predictive variance of a new y_p,
+ *           noise included - and the marginal log N(y_p; mu_p, S_pp); NaN at rows the plan does not observe
+ *     group_lpd   (n_nodes, or NULL): by leaf, the joint log predictive density of the group at its leaf's node index; otherwise the sum
+ *           of that leaf's rows' lpd; NaN for non-leaves and for leaves without observations
+ *     info[8]     0: rows scored; 1: groups; 2: the sum over groups of the joint log predictive density (the CV log score); 3: the sum
+ *           over rows of the marginal lpd; 4: the sum of squared standardised residuals (y_p - mu_p)^2 / S_pp; 5: max_p h_p;
+ *           6: tr K^-1 = sum (1 - h_p) / r_p; 7: alpha^T alpha = sum (rho_p / r_p)^2, alpha = K^-1 y.  [6] - [7] is the derivative of
+ *           mra_get_likelihood's d + u with respect to tau for K + tau I at tau = 0: the exact derivative by the nugget.
+ * CONDITIONING: the information sits in r - v, so float64 loses about eps / (1 - h)^2 whatever computes the identity: against
+ * brute-force conditioning (dense, 60 points, groups of 12) the mean is off by 6e-15 max|y| at max h = 0.77, 2.5e-13 at 0.94, 3e-9 at
+ * 0.9994 and 2e-5 at 0.99999 (diag S relatively: 9e-15, 1e-12, 1e-8, 2e-4).  info[5] reports max h so that a caller sees it.
+ * The sums of info are folded over a fixed number of partial results in a fixed order: the same inputs give the same bits.  A row's
+ * results are a pure function of (row, its group, plan state): they do not depend on MRA_OPT_SITES_CHUNK_BYTES (which bounds a batch
+ * of whole leaves, at least one leaf).  A pivot of N_G that is <= 0 or NaN, or 1 - h_p <= 0 or NaN when every row is its own group,
+ * gives MRA_ERR_NOT_SPD naming the leaf or the padded row; no jitter is added.  After mra_plan_fit_laplace the call scores what the plan
+ * holds: the pseudo-observations t with noise 1 / D of the last linearisation (mra_get_buffer 11 and 10), not the counts.
+ * The state is mra_predict_sites': the first call (and the first after mra_run, mra_run_resume, mra_sample or any set_*) runs one
+ * likelihood pass with W at every row; later calls - and calls after an mra_solve, mra_cov_apply, mra_predict_sites, mra_sites_cov or
+ * mra_sample_sites - launch no factorisation.  Afterwards y, every option and what mra_get_likelihood / mra_get_predict return are as
+ * the caller left them.
+ * MRA_ERR_STATE before set_locs / set_obs / set_kernel; MRA_ERR_INVALID for unknown flags, MRA_KERNEL_HOST plans, sharded plans, a NULL
+ * info, a noise variance that is 0 at an observed row and, by leaf, a leaf with more than MRA_SAMPLE_SITES_LEAF_MAX observed rows (all
+ * checked on the host before anything is launched or allocated).  A plan with no observed row returns MRA_OK with info all zero.
+ * Blocking. */
+#define MRA_CV_LEAF 1u   /* groups = the observed rows of each leaf; 0: every observed row its own group */
+int mra_cv(mra_plan *plan, uint32_t flags, double *mean_perm, double *var_perm, double *lpd_perm, double *group_lpd, double *info);
+
 /* Diagnostics for tests (the reference exposes these as attributes of Node objects):
  * what = 0: whitened basis W (P x ldw, row-major) ; 1: per-node log-det terms (n_nodes);
  * 7: stream milliseconds of the last mra_predict_sites, measured while MRA_OPT_KERNEL_TIMING is on (7 values: the basis, leaf, chain
@@ -336,6 +373,8 @@ int mra_sample_sites(mra_plan *plan, uint32_t flags, int64_t n_sites, const doub
  * at every row when no vector is set;
  * 11: the observations y by padded row as the device holds them (P values, NaN where nothing is observed): what the last
  * mra_plan_set_obs uploaded, or the pseudo-observations t of the last pass of mra_plan_fit_laplace;
+ * 12: stream milliseconds of the last mra_cv under MRA_OPT_KERNEL_TIMING (9 values: basis, leaf, chain, mean with the solver's sweeps,
+ * Gram, Cholesky, solve with the reduction, uploads, downloads);
  * copies min(capacity, available) doubles into out, returns the available count in *n_avail.
  * (W after a likelihood-only run is complete only with MRA_OPT_LIK_ROWS off: by default such a run computes W at the rows a
  * likelihood needs - the observed rows, and the knots on the level-by-level path - and leaves the others as they were.) */

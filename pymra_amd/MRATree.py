@@ -42,6 +42,16 @@ from .topology import build_topology, resolve_tree_shape
 logger = logging.getLogger("pyMRA.MRATree")
 
 
+class CVResult:
+    """What ``MRATree.crossValidate`` returns (its docstring lists the fields)."""
+
+    def __init__(self, **fields):
+        self.__dict__.update(fields)
+
+    def __repr__(self):
+        return "CVResult(kind=%r, n=%d, score=%.6g, leverage_max=%.4g)" % (self.kind, self.n, self.score, self.leverage_max)
+
+
 class RootView:
     """The attributes of the reference's root ``Node`` that callers read (pyMRA/MRANode.py:26-45, 378-391,
     444-520).  ``d, u, mean, var`` come from the GPU pass; ``knots, B, kInv, k`` (the root's prior blocks,
@@ -254,6 +264,35 @@ class MRATree(object):
         mean = np.zeros((len(self.locs), Y.shape[1]))
         mean[t.perm[rows], :] = m[:, rows].T
         return mean, quad
+
+    def crossValidate(self, kind="loo"):
+        """Cross-validation of the fitted model without a refit, from the factors this tree's pass left on the device: every observed
+        location left out on its own (kind="loo") or the observed locations of each leaf left out together (kind="leaf": spatial block
+        cross-validation on the tree's own partition).  -> CVResult, per-row fields in the caller's row order and NaN where nothing
+        is observed: mean and sd of the leave-out predictive distribution of a new observation (noise included), z = (y - mean) / sd,
+        lpd = the marginal log predictive density; leaf_lpd {leaf node: log predictive density of its group (kind="leaf": joint)};
+        score = their sum, the CV log score; n rows scored; leverage_max = max v / R (float64 loses about eps / (1 - leverage)^2);
+        dlik_dR = the exact derivative of getLikelihood() with respect to a nugget added to every observed row.  getLikelihood() and
+        predict() are unchanged afterwards."""
+        if kind not in ("loo", "leaf"):
+            raise ValueError('kind must be "loo" or "leaf"')
+        if self.kernel is None:
+            raise NotImplementedError("crossValidate needs a device kernel: trees built from an opaque callable or a dense matrix cannot cross-validate")
+        mean, var, lpd, group, info = self.plan.cv(leaf=(kind == "leaf"))
+        yp = self.plan.buffer(11)
+        t = self.topology
+        rows = t.perm >= 0
+        N = len(self.locs)
+
+        def by_caller(v):
+            out = np.full(N, np.nan)
+            out[t.perm[rows]] = v[rows]
+            return out
+        sd = np.sqrt(var)
+        nodes = np.nonzero(~np.isnan(group))[0]
+        return CVResult(kind=kind, mean=by_caller(mean), sd=by_caller(sd), z=by_caller((yp - mean) / sd), lpd=by_caller(lpd),
+                        leaf_lpd={int(i): float(group[i]) for i in nodes}, score=float(info[2]), n=int(info[0]),
+                        leverage_max=float(info[5]), dlik_dR=float(info[6] - info[7]))
 
     def _sites(self, sites):
         """The caller's sites, checked, in covariance coordinates: (lon, lat) degrees -> xyz under metric="chordal", else as given

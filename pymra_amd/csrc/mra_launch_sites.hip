@@ -1,7 +1,7 @@
 // mra_launch_sites.hip - mra_predict_sites: descriptors, work buffers and the launches of one chunk of site tiles
 // over the state a likelihood pass left in the plan, and the Gram launch of mra_sites_cov (section 13) over the same buffers.  A
 // translation unit of its own: the kernels of the pass keep their object code.  The inert, leaf Gram, zeta and draw launches of
-// mra_sample_sites (section 14) run over the same buffers, a batch of whole leaves at a time.
+// mra_sample_sites (section 14) run over the same buffers, a batch of whole leaves at a time; so do the launches of mra_cv (section 18).
 #define MRA_KERNELS_TEMPLATES_ONLY
 #include "mra_site_kernels.h"
 
@@ -213,5 +213,92 @@ void mra_sites_draw(mra_plan* pl, long n, bool posterior) {
     timed(pl, 5, [&] {
         hipLaunchKernelGGL(k_site_draw, dim3((unsigned)n), dim3(64), 0, pl->stream, T.tleaf.p, T.dtile.p, T.dchain_ptr.p, T.dchain.p, posterior ? T.b.p : T.a.p,
                            (long)T.anc_max * 16, T.zc.p, T.G.p, T.zl.p, posterior ? T.mean.p : nullptr, T.dout.p, n * 16);
+    });
+}
+
+// ---- mra_cv --------------------------------------------------------------------------------------------------------
+// timing entries of a call (sit.cv_ms through the sink): 0 .. 2 the site kernels, 3 mean and sweeps, 4 Gram, 5 Cholesky, 6 solve and
+// reduction, 7 uploads, 8 downloads
+void mra_cv_reserve(mra_plan* pl, long n, size_t g_doubles, long n_leaves) {
+    mra_plan::Sites& T = pl->sit;
+    mra_sites_draw_reserve(pl, n, g_doubles, n_leaves);
+    if (T.cvx.n < g_doubles) T.cvx.alloc(g_doubles);
+    if (T.cvgroup.n < (size_t)n_leaves) T.cvgroup.alloc((size_t)n_leaves);
+    const size_t P = (size_t)pl->P, nn = (size_t)pl->n_nodes, nl = pl->leaf_nodes.size();
+    if (T.cvrow.n != 5 * P) T.cvrow.alloc(5 * P);
+    if (T.cvgl.n != nn) T.cvgl.alloc(nn);
+    if (!T.cvpart.n) { T.cvpart.alloc((size_t)CV_BLOCKS * MRA_CV_NRES); T.cvres.alloc(MRA_CV_NRES); }
+    if (T.cvleaf.n != nl) {
+        std::vector<long> rows(2 * nl);
+        for (size_t t = 0; t < nl; ++t) { rows[2 * t] = pl->row0[pl->leaf_nodes[t]]; rows[2 * t + 1] = pl->row1[pl->leaf_nodes[t]]; }
+        T.cvleaf.upload(pl->leaf_nodes); T.cvleaf_row.upload(rows);
+    }
+    // all-ones bytes are a NaN: rows and nodes that nothing writes stay NaN
+    HIP_TRY(hipMemsetAsync(T.cvrow.p, 0xFF, 5 * P * sizeof(double), pl->stream));
+    HIP_TRY(hipMemsetAsync(T.cvgl.p, 0xFF, nn * sizeof(double), pl->stream));
+}
+
+CvRows mra_cv_rows(const mra_plan* pl) { return CvRows{pl->y.p, pl->noise_on ? pl->noise.p : nullptr, pl->R}; }
+CvOut mra_cv_out(const mra_plan* pl) {
+    double* b = pl->sit.cvrow.p;
+    const long P = pl->P;
+    return CvOut{b, b + P, b + 2 * P, b + 3 * P, b + 4 * P};
+}
+
+static void check_cv_batch(const mra_plan* pl, long n) {
+    const mra_plan::Sites& T = pl->sit;
+    if (n <= 0 || n > T.cap_tiles || (size_t)n > T.dtile.n || (size_t)n * 16 > T.sslot.n || (size_t)n * 256 > T.zl.n || T.cvrow.n != 5 * (size_t)pl->P)
+        throw MraError(MRA_ERR_STATE, "mra_cv: batch larger than its work buffers");
+}
+
+void mra_cv_sites(mra_plan* pl, long n) {
+    check_cv_batch(pl, n);
+    mra_plan::Sites& T = pl->sit;
+    timed(pl, 7, [&] { hipLaunchKernelGGL(k_cv_sites, dim3((unsigned)((n * 16 + 255) / 256)), dim3(256), 0, pl->stream, T.sslot.p, pl->X.p, pl->d, n * 16, T.xs.p); });
+}
+
+void mra_cv_loo(mra_plan* pl, long n) {
+    check_cv_batch(pl, n);
+    mra_plan::Sites& T = pl->sit;
+    timed(pl, 6, [&] {
+        hipLaunchKernelGGL(k_cv_loo, dim3((unsigned)((n * 16 + 255) / 256)), dim3(256), 0, pl->stream, T.sslot.p, n * 16, T.var.p, T.mean.p, mra_cv_rows(pl),
+                           mra_cv_out(pl), T.derr.p);
+    });
+}
+
+template <int DIM, int MODE>
+static void launch_cv_gram(mra_plan* pl, long n, int nt_max) {
+    mra_plan::Sites& T = pl->sit;
+    hipLaunchKernelGGL((k_cv_gram<DIM, MODE>), dim3((unsigned)n, (unsigned)nt_max), dim3(64), 0, pl->stream, pl->slv.leaves.p, T.tleaf.p, T.dtile.p, T.xs.p, pl->kp,
+                       T.a.p, T.b.p, (long)T.anc_max * 16, T.t.p, (long)T.nop_max * 16, T.sslot.p, mra_cv_rows(pl), T.G.p);
+}
+
+void mra_cv_gram(mra_plan* pl, long n, int nt_max) {
+    check_cv_batch(pl, n);
+    if (nt_max < 1 || nt_max > 65535) throw MraError(MRA_ERR_STATE, "mra_cv: a leaf of the batch has no tile or too many");
+    timed(pl, 4, [&] { MRA_SITES_DISPATCH(launch_cv_gram, pl, n, nt_max); });
+}
+
+void mra_cv_solve(mra_plan* pl, long n, long n_groups) {
+    check_cv_batch(pl, n);
+    mra_plan::Sites& T = pl->sit;
+    if (n_groups < 1 || (size_t)n_groups > T.cvgroup.n || (size_t)n_groups > T.dn.n) throw MraError(MRA_ERR_STATE, "mra_cv: more groups than the batch holds");
+    timed(pl, 6, [&] {
+        hipLaunchKernelGGL(k_cv_fwd, dim3((unsigned)n_groups), dim3(64), 0, pl->stream, T.cvgroup.p, T.sslot.p, T.mean.p, mra_cv_rows(pl), T.G.p, T.dn.p, T.zl.p,
+                           T.cvgl.p);
+        hipLaunchKernelGGL(k_cv_solve, dim3((unsigned)n), dim3(64), 0, pl->stream, T.dtile.p, T.sslot.p, T.var.p, T.mean.p, mra_cv_rows(pl), T.G.p, T.zl.p,
+                           T.cvx.p, mra_cv_out(pl));
+    });
+}
+
+void mra_cv_reduce(mra_plan* pl, bool by_leaf) {
+    mra_plan::Sites& T = pl->sit;
+    if (T.cvrow.n != 5 * (size_t)pl->P || !T.cvpart.n) throw MraError(MRA_ERR_STATE, "mra_cv: the row results are not allocated");
+    const int nl = (int)pl->leaf_nodes.size();
+    timed(pl, 6, [&] {
+        if (!by_leaf && nl)
+            hipLaunchKernelGGL(k_cv_leaf_sum, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, pl->stream, T.cvleaf.p, T.cvleaf_row.p, nl, mra_cv_out(pl).lpd, T.cvgl.p);
+        hipLaunchKernelGGL(k_cv_part, dim3(CV_BLOCKS), dim3(256), 0, pl->stream, mra_cv_rows(pl), mra_cv_out(pl), (long)pl->P, T.cvgl.p, pl->n_nodes, T.cvpart.p);
+        hipLaunchKernelGGL(k_cv_sum, dim3(1), dim3(64 * MRA_CV_NRES), 0, pl->stream, T.cvpart.p, CV_BLOCKS, T.cvres.p);
     });
 }

@@ -3275,6 +3275,156 @@ static void sample_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const doub
                 if (first[(size_t)i] != i) out[s * n + i] = out[s * n + first[(size_t)i]];
 }
 
+// ---- cross-validation (mra_cv) -------------------------------------------------------------------------------------
+// The sites are the plan's own observed rows, each in its own leaf: batches of whole leaves as sample_sites_all, the four site kernels
+// with the plan's y as the one column, then the leave-one-out step or, by leaf, N_G, its Cholesky factor and the solves.  The per-row
+// results are scattered by padded row on the device and reduced there after the last batch, so nothing depends on the batches.
+static void cv_all(mra_plan* pl, uint32_t flags, double* mean, double* var, double* lpd, double* group_lpd, double* info) {
+    retained_check_plan(pl, "mra_cv", flags, MRA_CV_LEAF, "cannot cross-validate (C(s, s) is evaluated on the device)", "cannot cross-validate");
+    if (!info) throw MraError(MRA_ERR_INVALID, "mra_cv: info is NULL");
+    if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
+    const bool by_leaf = (flags & MRA_CV_LEAF) != 0;
+    const long P = pl->P;
+    const size_t nl = pl->leaf_nodes.size();
+    char m[200];
+    // the observed rows, leaf by leaf in row order: site i is padded row rows[i]
+    std::vector<int64_t> rows;
+    std::vector<int> lslot;
+    for (size_t t = 0; t < nl; ++t)
+        for (long p = pl->row0[pl->leaf_nodes[t]]; p < pl->row1[pl->leaf_nodes[t]]; ++p) {
+            if (!pl->y_finite_host[p]) continue;
+            if ((pl->noise_on ? pl->noise_host[(size_t)p] : pl->R) == 0.0) {
+                snprintf(m, sizeof m, "mra_cv: the noise variance is 0 at observed padded row %ld (the leave-out distributions divide by it)", p);
+                throw MraError(MRA_ERR_INVALID, m);
+            }
+            rows.push_back(p); lslot.push_back((int)t);
+        }
+    const int64_t n = (int64_t)rows.size();
+    if (by_leaf) {
+        std::vector<int64_t> per_leaf(nl, 0);
+        for (int64_t i = 0; i < n; ++i)
+            if (++per_leaf[(size_t)lslot[(size_t)i]] == (int64_t)MRA_SAMPLE_SITES_LEAF_MAX + 1) {
+                snprintf(m, sizeof m, "mra_cv: leaf %d has more than MRA_SAMPLE_SITES_LEAF_MAX = %d observed rows (its block is dense, 128 MiB at the cap)",
+                         pl->leaf_nodes[(size_t)lslot[(size_t)i]], MRA_SAMPLE_SITES_LEAF_MAX);
+                throw MraError(MRA_ERR_INVALID, m);
+            }
+    }
+    const double nan = std::nan("");
+    for (int k = 0; k < 8; ++k) info[k] = 0.0;
+    for (double* o : {mean, var, lpd})
+        if (o) std::fill(o, o + P, nan);
+    if (group_lpd) std::fill(group_lpd, group_lpd + pl->n_nodes, nan);
+    if (n == 0) return;
+    const int d = pl->d;
+    sites_ensure_state(pl);
+    mra_plan::Solver& S = pl->slv;
+    mra_plan::Sites& T = pl->sit;
+    for (double& v : T.cv_ms) v = 0.0;
+    SitesSink sink(T, T.cv_ms);
+    std::vector<int64_t> slot;
+    std::vector<int> tile_leaf;
+    sites_tiles(lslot, n, nl, slot, tile_leaf);
+    for (int64_t& v : slot) if (v >= 0) v = rows[(size_t)v];
+    const long n_tiles = (long)tile_leaf.size();
+    // batches of whole leaves: work arrays of the tiles + (by leaf) the leaf's block twice, N_G and X
+    const size_t budget = T.chunk_bytes ? T.chunk_bytes : SITES_CHUNK_BYTES;
+    const size_t tile_bytes = mra_sites_tile_bytes(pl) + sizeof(SiteDrawTile) + 16 * (sizeof(long) + sizeof(int)) + 3 * 256 * sizeof(double);
+    struct Batch { long t0, nt, n_leaves; size_t g; int nt_max; };
+    std::vector<Batch> bat;
+    {
+        Batch cur{0, 0, 0, 0, 0};
+        size_t bytes = 0;
+        for (long t0 = 0; t0 < n_tiles;) {
+            long t1 = t0;
+            while (t1 < n_tiles && tile_leaf[(size_t)t1] == tile_leaf[(size_t)t0]) ++t1;
+            const long nt = t1 - t0;
+            const size_t g = by_leaf ? (size_t)(16 * nt) * (size_t)(16 * nt) : 0, need = (size_t)nt * tile_bytes + 2 * g * sizeof(double);
+            if (cur.nt && bytes + need > budget) { bat.push_back(cur); cur = Batch{t0, 0, 0, 0, 0}; bytes = 0; }
+            cur.nt += nt; ++cur.n_leaves; cur.g += g; cur.nt_max = std::max(cur.nt_max, (int)nt); bytes += need;
+            t0 = t1;
+        }
+        bat.push_back(cur);
+    }
+    long cap_t = 0, cap_l = 0;
+    size_t cap_g = 0;
+    for (const Batch& b : bat) { cap_t = std::max(cap_t, b.nt); cap_l = std::max(cap_l, b.n_leaves); cap_g = std::max(cap_g, b.g); }
+    mra_cv_reserve(pl, cap_t, cap_g, cap_l);
+    HIP_TRY(hipMemsetAsync(T.derr.p, 0, sizeof(int), pl->stream));
+    // beta (leaves' gb) and q (leaves' uy) of the plan's own observations: the solver's sweeps without its row step, once per call
+    stage_columns(pl, pl->y.p, 1, S.yb.p, hipMemcpyDeviceToDevice);
+    mra_sites_timed(pl, 3, [&] { mra_solver_block(pl, true, false, false); });
+    std::vector<SiteDrawTile> dt((size_t)cap_t);
+    std::vector<PanelProb> pp((size_t)cap_l);
+    std::vector<CvGroup> gr((size_t)cap_l);
+    for (const Batch& b : bat) {
+        size_t goff = 0;
+        long nlb = 0;
+        for (long t = 0; t < b.nt;) {
+            long t1 = t;
+            while (t1 < b.nt && tile_leaf[(size_t)(b.t0 + t1)] == tile_leaf[(size_t)(b.t0 + t)]) ++t1;
+            const long nt = t1 - t;
+            const int node = pl->leaf_nodes[(size_t)tile_leaf[(size_t)(b.t0 + t)]];
+            for (long k = t; k < t1; ++k) dt[(size_t)k] = SiteDrawTile{(long)goff, (int)t, (int)nt};
+            pp[(size_t)nlb] = PanelProb{T.G.p + goff, T.invd.p + (size_t)t * 256, 16 * nt, (int)nt, (int)nt, (int)nlb};
+            gr[(size_t)nlb] = CvGroup{(long)goff, (int)t, (int)nt, node, 0};
+            if (by_leaf) goff += (size_t)(16 * nt) * (size_t)(16 * nt);
+            ++nlb; t = t1;
+        }
+        mra_sites_timed(pl, 7, [&] {
+            HIP_TRY(hipMemcpyAsync(T.tleaf.p, tile_leaf.data() + b.t0, (size_t)b.nt * sizeof(int), hipMemcpyHostToDevice, pl->stream));
+            HIP_TRY(hipMemcpyAsync(T.sslot.p, slot.data() + b.t0 * 16, (size_t)b.nt * 16 * sizeof(long), hipMemcpyHostToDevice, pl->stream));
+            if (by_leaf) {
+                HIP_TRY(hipMemcpyAsync(T.dtile.p, dt.data(), (size_t)b.nt * sizeof(SiteDrawTile), hipMemcpyHostToDevice, pl->stream));
+                HIP_TRY(hipMemcpyAsync(T.dprob.p, pp.data(), (size_t)nlb * sizeof(PanelProb), hipMemcpyHostToDevice, pl->stream));
+                HIP_TRY(hipMemcpyAsync(T.cvgroup.p, gr.data(), (size_t)nlb * sizeof(CvGroup), hipMemcpyHostToDevice, pl->stream));
+            }
+        });
+        mra_cv_sites(pl, b.nt);
+        mra_sites_basis(pl, b.nt);
+        mra_sites_var(pl, b.nt);
+        mra_sites_mean(pl, b.nt, 1, 3);
+        int e = 0;
+        if (by_leaf) {
+            mra_cv_gram(pl, b.nt, b.nt_max);
+            mra_sites_timed(pl, 5, [&] { hipLaunchKernelGGL(k_panel_chol, dim3((unsigned)nlb), dim3(256), 0, pl->stream, T.dprob.p, T.dn.p, T.derr.p, 0); });
+        } else {
+            mra_cv_loo(pl, b.nt);
+        }
+        // (the host arrays of the uploads above are reused by the next batch: the copy of the error slot waits for them too)
+        HIP_TRY(hipMemcpyAsync(&e, T.derr.p, sizeof(int), hipMemcpyDeviceToHost, pl->stream));
+        HIP_TRY(hipStreamSynchronize(pl->stream));
+        HIP_TRY(hipGetLastError());
+        if (e && by_leaf) {
+            snprintf(m, sizeof m, "mra_cv: leaf %d: D - Sigma_post over its observed rows is not positive definite (Cholesky pivot <= 0 or NaN; no jitter is added)",
+                     gr[(size_t)(e - 1)].node);
+            throw MraError(MRA_ERR_NOT_SPD, m);
+        }
+        if (e) {
+            snprintf(m, sizeof m, "mra_cv: padded row %d: 1 - v / r <= 0 or NaN (the posterior variance reaches the noise variance; no jitter is added)", e - 1);
+            throw MraError(MRA_ERR_NOT_SPD, m);
+        }
+        if (by_leaf) mra_cv_solve(pl, b.nt, nlb);
+    }
+    mra_cv_reduce(pl, by_leaf);
+    double res[MRA_CV_NRES];
+    const CvOut O = mra_cv_out(pl);
+    mra_sites_timed(pl, 8, [&] {
+        HIP_TRY(hipMemcpyAsync(res, T.cvres.p, sizeof res, hipMemcpyDeviceToHost, pl->stream));
+        if (mean) HIP_TRY(hipMemcpyAsync(mean, O.mean, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
+        if (var) HIP_TRY(hipMemcpyAsync(var, O.var, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
+        if (lpd) HIP_TRY(hipMemcpyAsync(lpd, O.lpd, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
+        if (group_lpd) HIP_TRY(hipMemcpyAsync(group_lpd, T.cvgl.p, (size_t)pl->n_nodes * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
+    });
+    HIP_TRY(hipStreamSynchronize(pl->stream));
+    HIP_TRY(hipGetLastError());
+    long n_groups = 0;
+    for (const Batch& b : bat) n_groups += b.n_leaves;
+    info[0] = res[0];
+    info[1] = by_leaf ? (double)n_groups : res[0];
+    info[2] = by_leaf ? res[6] : res[1];      // every row its own group: the groups' joint densities are the rows' marginal ones
+    info[3] = res[1]; info[4] = res[2]; info[5] = res[3]; info[6] = res[4]; info[7] = res[5];
+}
+
 // ---- caller-order variants: the permutation work of an end-to-end MRATree(...) call done inside the library -----------------
 // A process-wide pinned staging area (grow-only): gathers land in it, the H2D / D2H copies run at the pinned rate (a pageable
 // 16 MB copy costs ~5 ms, a pinned one ~0.7 ms), and a second plan in the same process does not pay for the allocation again.
@@ -4014,6 +4164,10 @@ int mra_sample_sites(mra_plan* pl, uint32_t flags, int64_t n_sites, const double
     });
 }
 
+int mra_cv(mra_plan* pl, uint32_t flags, double* mean_perm, double* var_perm, double* lpd_perm, double* group_lpd, double* info) {
+    return guarded(pl, [&] { require(pl, "mra_cv: plan is NULL"); cv_all(pl, flags, mean_perm, var_perm, lpd_perm, group_lpd, info); return MRA_OK; });
+}
+
 int mra_get_likelihood(mra_plan* pl, double* d, double* u) {
     return guarded(pl, [&] {
         require(pl && d && u, "mra_get_likelihood: plan, d or u is NULL");
@@ -4045,6 +4199,11 @@ int mra_get_buffer(mra_plan* pl, int what, double* out, int64_t cap, int64_t* n_
         if (what == 9) {             // host record: stream ms of the last mra_sample_sites
             *n_avail = 9;
             if (out && cap > 0) memcpy(out, pl->sit.draw_ms, (size_t)std::min<int64_t>(cap, 9) * sizeof(double));
+            return MRA_OK;
+        }
+        if (what == 12) {            // host record: stream ms of the last mra_cv
+            *n_avail = 9;
+            if (out && cap > 0) memcpy(out, pl->sit.cv_ms, (size_t)std::min<int64_t>(cap, 9) * sizeof(double));
             return MRA_OK;
         }
         if (what == 10) {            // host record: the noise variance by padded row (the scalar R everywhere when no vector is set)

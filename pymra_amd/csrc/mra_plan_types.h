@@ -239,6 +239,22 @@ struct SiteDrawTile {           // one tile of a batch of whole leaves
 };
 struct SiteDrawChain { int row, zoff, width, pad; };      // one ancestor of a leaf: its first row in a / p, its first latent slot, its width
 
+// ---- mra_cv: descriptors of the cross-validation kernels (mra_site_kernels.h).  The sites are the observed rows.
+struct CvRows {                 // what the plan holds by padded row
+    const double* y;            // the observations
+    const double* noise;        // their noise variances (nullptr: the scalar R everywhere)
+    double R;
+};
+struct CvOut {                  // results by padded row (P each), NaN where nothing is observed
+    double *mean, *var, *lpd;   // mu_p, S_pp, log N(y_p; mu_p, S_pp)
+    double *h, *rho;            // v_p / r_p and y_p - m_p: what the reduction reads
+};
+struct CvGroup {                // one leaf of a batch, as a group
+    long goff;                  // its block N_G in the batch's block buffer (SiteDrawTile::goff of its tiles)
+    int first, nt, node, pad;   // its first tile in the batch, its tile count, its node index
+};
+constexpr int MRA_CV_NRES = 7;  // rows, sum lpd, sum z^2, max h, tr K^-1, alpha^T alpha, sum of the groups' joint lpd
+
 struct LevelData {
     std::vector<int> nodes;          // non-leaf nodes of this level
     int cw = 0, cwt = 0, c0 = 0, a0 = 0, nf = 0, na = 0;
@@ -638,6 +654,14 @@ struct mra_plan {
         DevVec<double> G, invd, dn;               // the batch's blocks; their inverted diagonal blocks; log-determinants (not read)
         DevVec<double> zc, zcin, zl, zin, dout;   // Kn x16 non-leaf draws (and the caller's, 16 x Kn); [tile][16] x16 leaf draws (and the caller's); 16 x [tile][16] results
         double draw_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};      // stream ms of the last mra_sample_sites: basis, leaf, chain, leaf Gram, leaf Cholesky, draw, mean (+ sweeps), uploads, downloads
+        // mra_cv: the sites are the observed rows, a batch of whole leaves at a time over the buffers above (sslot:
+        // padded rows; G: the groups' N_G, factorised in place; zl: w = L^-1 rho) - and the results by padded row for the call
+        DevVec<CvGroup> cvgroup;                  // [leaf of the batch]
+        DevVec<double> cvx;                       // the batch's X = L^-1 column tiles, laid out as G
+        DevVec<double> cvrow, cvgl, cvpart, cvres;      // 5 x P: mean, var, lpd, h, rho; [n_nodes] group values; the reduction's partial and final results
+        DevVec<int> cvleaf;                       // [n_leaves] node index
+        DevVec<long> cvleaf_row;                  // [n_leaves][2] first and one-past-last padded row
+        double cv_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};        // stream ms of the last mra_cv: basis, leaf, chain, mean (+ sweeps), Gram, Cholesky, solve (+ reduction), uploads, downloads
     } sit;
     // Laplace fit (mra_plan_fit_laplace): the data of the call by padded row (z: NaN at rows the plan does not
     // observe), the linearisation point of the running pass, and the reduction's partial results.  Allocated by the first call.
@@ -744,6 +768,17 @@ void mra_sites_draw_reserve(mra_plan* pl, long n_tiles, size_t g_doubles, long n
 void mra_sites_leaf_gram(mra_plan* pl, long n_tiles, int nt_max, bool posterior);
 void mra_sites_zeta(mra_plan* pl, long n_tiles, const SampleZ& zs, long n_coarse, bool from_caller);
 void mra_sites_draw(mra_plan* pl, long n_tiles, bool posterior);
+// ... and of mra_cv (section 18): the call's row results (NaN everywhere) and the batch buffers; the sites of a batch out of the plan's
+// rows; the elementwise leave-one-out step; N_G of a batch's leaves; w, the groups' values and the per-row results; the reduction into
+// res[MRA_CV_NRES] on the device (leaf mode: group_lpd is summed as it stands; otherwise the leaves' sums of lpd are formed first)
+void mra_cv_reserve(mra_plan* pl, long n_tiles, size_t g_doubles, long n_leaves);
+CvRows mra_cv_rows(const mra_plan* pl);
+CvOut mra_cv_out(const mra_plan* pl);
+void mra_cv_sites(mra_plan* pl, long n_tiles);
+void mra_cv_loo(mra_plan* pl, long n_tiles);
+void mra_cv_gram(mra_plan* pl, long n_tiles, int nt_max);
+void mra_cv_solve(mra_plan* pl, long n_tiles, long n_groups);
+void mra_cv_reduce(mra_plan* pl, bool by_leaf);
 // mra_launch_laplace.hip: the work buffers of mra_plan_fit_laplace (and the plan's noise / noise_sd); one linearisation at x_in (lap.x
 // itself, or the mean of the last pass) -> y, noise, noise_sd, lap.x; the reduction after a pass -> res[MRA_LAPLACE_NRES] = {step,
 // max |x^|, sum log D, sum D (t - x^)^2, sum of the x-dependent part of log p}, res a device-visible pointer (the plan's pinned record).

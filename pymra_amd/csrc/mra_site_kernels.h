@@ -4,6 +4,7 @@
 // mra_launch_sites.hip only, so that the other translation units keep their object code.  The last kernel, k_site_gram, is
 // mra_sites_cov's (section 13): the joint covariance of the sites of two tiles from the arrays the first three leave behind.  After it,
 // the kernels of mra_sample_sites (section 14): the inert flags, the leaves' blocks G_l, the staged leaf draws and the draw itself.
+// Last, the kernels of mra_cv (section 18): the observed rows as sites, the groups' blocks N_G, their solves and the reduction.
 //
 // A tile is 16 sites of ONE leaf; the 16 sites are the 16 columns (N) of v_mfma_f64_16x16x4_f64 throughout, so a^T, t, b and p_j are
 // k x16 arrays in the solver's "x16" layout: element (row, site) at row * 16 + site.  Every column of an MFMA product, of a
@@ -499,4 +500,243 @@ __global__ __launch_bounds__(64, 4) void k_site_draw(const int* __restrict__ til
         const long u = tile * 16 + q + 4 * j;
         gst(out + (long)r * ldo + u, mean ? acc[j] + gld(mean + u) : acc[j]);
     }
+}
+
+// ---- 7. cross-validation from the retained factors (mra_cv) -----------------------------------------------------
+// The sites are the plan's own observed rows, tiled by leaf: sslot[tile * 16 + k] = the padded row of the column (-1: padding).  After the
+// four site kernels above a tile holds a, t, p (k_site_chain's b), the posterior variance v and the posterior mean m of its rows.  With
+// D = diag(r) the noise, rho = y - m and N_G = D_G - Sigma_post[G, G] for a group G of observed rows, the predictive distribution of y_G
+// given every observation outside G has mean y_G - D_G N_G^-1 rho_G and covariance D_G N_G^-1 D_G (noise included).  The information sits
+// in r - v: with h = v / r float64 loses about eps / (1 - h)^2, whatever computes it.
+constexpr double CV_LOG_2PI = 1.8378770664093454836;
+static const int CV_BLOCKS = 1024;          // partial results of the reduction: a fixed number, folded in a fixed order (as k_laplace_part)
+
+__device__ __forceinline__ double cv_noise(const CvRows& c, long p) { return c.noise ? c.noise[p] : c.R; }
+
+// the coordinates of a batch's sites out of the plan's rows; padding columns repeat their tile's first site (as sites_gather)
+__global__ __launch_bounds__(256) void k_cv_sites(const long* __restrict__ sslot, const double* __restrict__ X, int d, long n_sites,
+                                                  double* __restrict__ xs) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_sites) return;
+    long p = sslot[i];
+    if (p < 0) p = sslot[i & ~15L];
+    for (int k = 0; k < d; ++k) xs[i * d + k] = X[p * d + k];
+}
+
+// leave one out: every observed row its own group, so N_G = r (1 - h).  1 - h <= 0 or NaN: err = the largest such padded row + 1.
+__global__ __launch_bounds__(256) void k_cv_loo(const long* __restrict__ sslot, long n_sites, const double* __restrict__ v,
+                                                const double* __restrict__ m, CvRows c, CvOut o, int* __restrict__ err) {
+    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_sites) return;
+    const long p = sslot[i];
+    if (p < 0) return;
+    const double r = cv_noise(c, p), y = c.y[p], h = v[i] / r, om = 1.0 - h, rho = y - m[i];
+    if (!(om > 0.0)) atomicMax(err, (int)(p + 1));
+    const double e = rho / om, S = r / om;
+    o.mean[p] = y - e; o.var[p] = S; o.lpd[p] = -0.5 * (CV_LOG_2PI + log(S) + e * e / S);
+    o.h[p] = h; o.rho[p] = rho;
+}
+
+// One wave per 16 x 16 block on or below the diagonal of a leaf's N_G = diag(r) - [p^T p - a^T a - t^T t + C(s_u, s_w)]: tile I =
+// blockIdx.x of the batch (M), tile J = the leaf's blockIdx.y-th (N).  k_site_leaf_gram's operand pattern (both operands rows of x16
+// arrays, the covariance added by the lane that holds the element) plus k_site_gram's p^T p over the whole chain, which is all of anc.
+// Rows and columns of padding become the identity.
+template <int DIM, int MODE>
+__global__ __launch_bounds__(64, 4) void k_cv_gram(const SolveLeaf* __restrict__ lv, const int* __restrict__ tile_leaf,
+                                                   const SiteDrawTile* __restrict__ dt, const double* __restrict__ xs, KernelParams kp,
+                                                   const double* __restrict__ a_buf, const double* __restrict__ b_buf, long a_stride,
+                                                   const double* __restrict__ t_buf, long t_stride, const long* __restrict__ sslot,
+                                                   CvRows c, double* __restrict__ G) {
+    const long I = blockIdx.x;
+    const SiteDrawTile D = dt[I];
+    const int il = (int)(I - D.first), jl = blockIdx.y;
+    if (jl > il) return;
+    const long J = (long)D.first + jl;
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    const int t = tile_leaf[I];
+    const int anc = lv[t].anc, nop = lv[t].nop;
+    d4 acc = {0, 0, 0, 0};
+    const double* pI = b_buf + I * a_stride;
+    const double* pJ = b_buf + J * a_stride;
+    const double* aI = a_buf + I * a_stride;
+    const double* aJ = a_buf + J * a_stride;
+    for (int k0 = 0; k0 < anc; k0 += 16) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const long k = k0 + q + 4 * s;
+            acc = mfma16(-gld(pI + k * 16 + r), gld(pJ + k * 16 + r), acc);
+        }
+    }
+    for (int k0 = 0; k0 < anc; k0 += 16) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const long k = k0 + q + 4 * s;
+            acc = mfma16(gld(aI + k * 16 + r), gld(aJ + k * 16 + r), acc);
+        }
+    }
+    const double* uI = t_buf + I * t_stride;
+    const double* uJ = t_buf + J * t_stride;
+    for (int k0 = 0; k0 < nop; k0 += 16) {
+#pragma unroll
+        for (int s = 0; s < 4; ++s) {
+            const long k = k0 + q + 4 * s;
+            acc = mfma16(gld(uI + k * 16 + r), gld(uJ + k * 16 + r), acc);
+        }
+    }
+    double xw[DIM];
+#pragma unroll
+    for (int e = 0; e < DIM; ++e) xw[e] = gld(xs + (J * 16 + r) * DIM + e);
+    const bool lw = sslot[J * 16 + r] >= 0;
+    const long ld = 16L * D.nt;
+    double* o = G + D.goff + (long)il * 16 * ld + jl * 16 + r;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        double xu[DIM];
+#pragma unroll
+        for (int e = 0; e < DIM; ++e) xu[e] = gld(xs + (I * 16 + q + 4 * j) * DIM + e);
+        const long pu = sslot[I * 16 + q + 4 * j];
+        const bool on_diag = il == jl && q + 4 * j == r;
+        double v = acc[j] - site_cov<MODE>(kp, pair_dist2<DIM>(xu, xw, kp.circular));
+        if (on_diag && pu >= 0) v += cv_noise(c, pu);
+        gst(o + (long)(q + 4 * j) * ld, (lw && pu >= 0) ? v : (on_diag ? 1.0 : 0.0));
+    }
+}
+
+// One wave per group, after k_panel_chol left N_G = L L^T in the group's block: w = L^-1 rho_G in column 0 of an x16 array (the other
+// columns are zero), and the group's joint log predictive density -1/2 [2 sum log r - log det N_G + |w|^2 + |G| log 2 pi] at its node.
+// dn: k_panel_chol's 2 sum log diag L per group of the batch (padding rows are the identity and add 0).
+__global__ __launch_bounds__(64, 4) void k_cv_fwd(const CvGroup* __restrict__ groups, const long* __restrict__ sslot,
+                                                  const double* __restrict__ m, CvRows c, const double* __restrict__ G,
+                                                  const double* __restrict__ dn, double* __restrict__ w_buf, double* __restrict__ group_lpd) {
+    __shared__ double Ld[256];
+    const CvGroup g = groups[blockIdx.x];
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    double* w = w_buf + (long)g.first * 256;
+    site_trsm(G + g.goff, 16 * g.nt, g.nt, w, Ld, [&](int I) {
+        d4 acc;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const long u = ((long)g.first + I) * 16 + q + 4 * j;
+            const long p = sslot[u];
+            acc[j] = (r == 0 && p >= 0) ? c.y[p] - m[u] : 0.0;
+        }
+        return acc;
+    });
+    const double quad = __shfl(site_colsq(w, 16 * g.nt, r, q), 0, 64);
+    double s = 0.0, cnt = 0.0;
+    for (int u = lane; u < 16 * g.nt; u += 64) {
+        const long p = sslot[(long)g.first * 16 + u];
+        if (p >= 0) { s += log(cv_noise(c, p)); cnt += 1.0; }
+    }
+#pragma unroll
+    for (int k = 32; k > 0; k >>= 1) { s += __shfl_xor(s, k, 64); cnt += __shfl_xor(cnt, k, 64); }
+    if (lane == 0) group_lpd[g.node] = -0.5 * (2.0 * s - dn[blockIdx.x] + quad + cnt * CV_LOG_2PI);
+}
+
+// One wave per (group, column tile c): X_c = L^-1 E_c by forward substitution (its rows above tile c are zero and are not computed: the
+// trailing block of L is solved), then for the tile's rows diag(N^-1)_p = the column sums of squares of X_c and (N^-1 rho)_p = X_c[:, p]^T w
+// - N^-1 = L^-T L^-1, so no backward substitution is run.  y_p - mu_p = r_p (N^-1 rho)_p, S_pp = r_p^2 diag(N^-1)_p.
+// x_buf: the batch's second block buffer, tile c of a group using the rows of the group's block from its own first row on.
+__global__ __launch_bounds__(64, 4) void k_cv_solve(const SiteDrawTile* __restrict__ dt, const long* __restrict__ sslot,
+                                                    const double* __restrict__ v, const double* __restrict__ m, CvRows c,
+                                                    const double* __restrict__ G, const double* __restrict__ w_buf,
+                                                    double* __restrict__ x_buf, CvOut o) {
+    __shared__ double Ld[256];
+    const long I = blockIdx.x;
+    const SiteDrawTile D = dt[I];
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    const int cI = (int)(I - D.first), nt = D.nt - cI;
+    const long ld = 16L * D.nt;
+    double* x = x_buf + D.goff + (long)cI * 16 * ld;
+    site_trsm(G + D.goff + (long)cI * 16 * ld + cI * 16, (int)ld, nt, x, Ld, [&](int K) {
+        d4 acc;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[j] = (K == 0 && q + 4 * j == r) ? 1.0 : 0.0;
+        return acc;
+    });
+    const double dg = site_colsq(x, 16 * nt, r, q);
+    const double* w = w_buf + I * 256;
+    double dot = 0.0;
+    for (int k = q; k < 16 * nt; k += 4) dot = __builtin_fma(gld(x + (long)k * 16 + r), gld(w + (long)k * 16), dot);
+    dot += __shfl_xor(dot, 16, 64);
+    dot += __shfl_xor(dot, 32, 64);
+    const long u = I * 16 + r;
+    const long p = sslot[u];
+    if (q == 0 && p >= 0) {
+        const double rr = cv_noise(c, p), y = c.y[p], e = rr * dot, S = rr * rr * dg;
+        o.mean[p] = y - e; o.var[p] = S; o.lpd[p] = -0.5 * (CV_LOG_2PI + log(S) + e * e / S);
+        o.h[p] = v[u] / rr; o.rho[p] = y - m[u];
+    }
+}
+
+// leave one out: a leaf's group value is the sum of its rows' lpd, in row order (one thread per leaf); NaN for a leaf without observations
+__global__ __launch_bounds__(256) void k_cv_leaf_sum(const int* __restrict__ leaf_node, const long* __restrict__ leaf_row, int n_leaves,
+                                                     const double* __restrict__ lpd, double* __restrict__ group_lpd) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= n_leaves) return;
+    double s = 0.0;
+    bool any = false;
+    for (long p = leaf_row[2 * t]; p < leaf_row[2 * t + 1]; ++p) {
+        const double l = lpd[p];
+        if (l == l) { s += l; any = true; }
+    }
+    if (any) group_lpd[leaf_node[t]] = s;
+}
+
+// Per workgroup {rows, sum lpd, sum (y - mu)^2 / S, max h, sum (1 - h) / r, sum (rho / r)^2, sum of the groups' values}: a thread walks
+// its rows (then its nodes) in order, the workgroup folds its 256 values in a fixed tree, as k_laplace_part: the same inputs give the
+// same bits.  A row counts when it was scored (h is not NaN), a node when its group value is not NaN.
+__global__ __launch_bounds__(256) void k_cv_part(CvRows c, CvOut o, long P, const double* __restrict__ group_lpd, int n_nodes,
+                                                 double* __restrict__ part) {
+    __shared__ double sh[MRA_CV_NRES][256];
+    double a[MRA_CV_NRES] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < P; p += (long)gridDim.x * 256) {
+        const double h = o.h[p];
+        if (!(h == h)) continue;
+        const double r = cv_noise(c, p), e = c.y[p] - o.mean[p], al = o.rho[p] / r;
+        a[0] += 1.0;
+        a[1] += o.lpd[p];
+        a[2] += e * e / o.var[p];
+        a[3] = h > a[3] ? h : a[3];
+        a[4] += (1.0 - h) / r;
+        a[5] += al * al;
+    }
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n_nodes; i += gridDim.x * 256) {
+        const double l = group_lpd[i];
+        if (l == l) a[6] += l;
+    }
+#pragma unroll
+    for (int k = 0; k < MRA_CV_NRES; ++k) sh[k][threadIdx.x] = a[k];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+#pragma unroll
+            for (int k = 0; k < MRA_CV_NRES; ++k) {
+                const double x = sh[k][threadIdx.x], y = sh[k][threadIdx.x + w];
+                sh[k][threadIdx.x] = k == 3 ? (y > x ? y : x) : x + y;
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < MRA_CV_NRES) part[(long)blockIdx.x * MRA_CV_NRES + threadIdx.x] = sh[threadIdx.x][0];
+}
+// the workgroups' partial results -> res[MRA_CV_NRES]: one wave per result, as k_laplace_sum
+__global__ __launch_bounds__(64 * MRA_CV_NRES) void k_cv_sum(const double* __restrict__ part, int nblk, double* __restrict__ res) {
+    __shared__ double sh[MRA_CV_NRES][64];
+    const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double acc = 0.0;
+    for (int b = lane; b < nblk; b += 64) {
+        const double a = part[(long)b * MRA_CV_NRES + k];
+        acc = k == 3 ? (a > acc ? a : acc) : acc + a;
+    }
+    sh[k][lane] = acc;
+    __syncthreads();
+    for (int w = 32; w > 0; w >>= 1) {
+        if (lane < w) {
+            const double a = sh[k][lane], b = sh[k][lane + w];
+            sh[k][lane] = k == 3 ? (b > a ? b : a) : a + b;
+        }
+        __syncthreads();
+    }
+    if (lane == 0) res[k] = sh[k][0];
 }

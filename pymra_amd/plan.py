@@ -38,6 +38,7 @@ MRA_OPT_CASCADE_GROUP = 18
 MRA_OPT_SAMPLE_GRAM_BYTES = 19
 MRA_OPT_SAMPLE_SOLVE = 20
 MRA_OPT_SITES_CHUNK_BYTES = 21
+MRA_CV_LEAF = 1
 MRA_OPT_LEAF_ORDER = 22
 MRA_OPT_PARENT_PAIR = 23
 MRA_OPT_PRIOR_REUSE = 24
@@ -72,7 +73,7 @@ EXPORTS = [
     "mra_device_count", "mra_release_cached_memory", "mra_plan_create", "mra_plan_destroy", "mra_plan_set_locs", "mra_plan_set_obs",
     "mra_plan_set_noise", "mra_plan_set_noise_rows", "mra_plan_fit_laplace",
     "mra_plan_set_kernel", "mra_plan_set_locs_rows", "mra_plan_set_obs_rows", "mra_get_predict_rows", "mra_get_predict_rows_sd", "mra_eval_kernel", "mra_plan_set_cov_block", "mra_run", "mra_get_likelihood", "mra_get_predict",
-    "mra_sample_slots", "mra_sample", "mra_solve", "mra_cov_apply", "mra_predict_sites", "mra_sites_cov", "mra_sample_sites_slots", "mra_sample_sites", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
+    "mra_sample_slots", "mra_sample", "mra_solve", "mra_cov_apply", "mra_predict_sites", "mra_sites_cov", "mra_sample_sites_slots", "mra_sample_sites", "mra_cv", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
     "mra_get_kernel_stats", "mra_get_kernel_work", "mra_get_route", "mra_device_synchronize", "mra_plan_info", "mra_comm_unique_id", "mra_comm_init",
     "mra_plan_set_reduce_level", "mra_reduce_size", "mra_reduce_export", "mra_reduce_import",
     "mra_run_resume", "mra_last_error", "mra_version",
@@ -143,6 +144,7 @@ def load_library():
         "mra_sites_cov": (C.c_int, [vp, u32, i64, vp, vp, vp]),
         "mra_sample_sites_slots": (C.c_int, [vp, i64, C.POINTER(i64)]),
         "mra_sample_sites": (C.c_int, [vp, u32, i64, vp, vp, i64, C.c_uint64, i64, vp, vp]),
+        "mra_cv": (C.c_int, [vp, u32, vp, vp, vp, vp, vp]),
         "mra_get_buffer": (C.c_int, [vp, C.c_int, vp, i64, C.POINTER(i64)]),
         "mra_get_node_block": (C.c_int, [vp, i32, C.c_int, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
         "mra_get_timers": (C.c_int, [vp, vp, C.c_int]),
@@ -555,6 +557,20 @@ class HipPlan:
         self._check(self.lib.mra_sample_sites(self._h, MRA_COV_POSTERIOR if posterior else 0, ns, _ptr(X), _ptr(lf), n,
                                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample0), zp, _ptr(out)))
         return out
+
+    def cv(self, leaf=False):
+        """Cross-validation of the fitted model from the retained factors, without a refit (include/mra_hip.h, mra_cv): every observed
+        row left out on its own, or with leaf=True the observed rows of each leaf left out together.  -> (mean, var, lpd, group_lpd,
+        info): the leave-out predictive mean, the predictive variance of a new observation (noise included) and the marginal log
+        predictive density by padded row, NaN where nothing is observed; the groups' log predictive densities by node (NaN for
+        non-leaves and leaves without observations); info[8] as the header lists it (2: the CV log score, 5: max v / r).  The
+        factorisation is shared with the other calls on the retained factors and kept between calls; y, the options and
+        likelihood() / predict() are unchanged."""
+        mean, var, lpd = np.empty(self.P), np.empty(self.P), np.empty(self.P)
+        group = np.empty(self.info()["n_nodes"])
+        info = np.zeros(8)
+        self._check(self.lib.mra_cv(self._h, MRA_CV_LEAF if leaf else 0, _ptr(mean), _ptr(var), _ptr(lpd), _ptr(group), _ptr(info)))
+        return mean, var, lpd, group, info
 
     def buffer(self, what):
         n = C.c_int64()
