@@ -90,6 +90,27 @@ int mra_plan_destroy(mra_plan *plan);
  * locs_perm: P x d row-major, padded leaf order (phantom rows must hold a valid location). */
 int mra_plan_set_locs(mra_plan *plan, const double *locs_perm);
 
+/* Anisotropic and space-time covariances (no counterpart in the reference, whose kernels take dist(locs, locs2), pyMRA/MRATools.py:229-253;
+ * DESIGN.md section 19): every device kernel evaluates value = scale * k(h; l, sig) with h = |A (a - b)|.  Geometric anisotropy (a ratio
+ * and an angle), per-axis ranges and (x, y, t) data with a temporal range of its own are all this.
+ * h = |A (a - b)|: A is d x d row-major (d = the topology's d), NULL = no metric (the identity).
+ * The metric is applied in front of the kernels, once per call: the plan keeps the caller's coordinates x in one more P x d array (allocated
+ * by the first non-NULL call, released by NULL) and hands every kernel t = A x, row i computed as
+ *     acc = A[i][0] * x[0];  for k = 1 .. d-1: acc = fma(A[i][k], x[k], acc)
+ * by one function on the device and on the host (the knot coordinates of regular trees, the sites of the site calls): the same bits
+ * everywhere, and x itself for A = I.  No kernel of a pass changes, and a plan that never sets a metric allocates and launches nothing new.
+ * The metric is a property of the plan, as the kernel is: it survives mra_plan_set_locs* (which then take the caller's coordinates and
+ * transform them again) and mra_plan_set_obs*.  mra_predict_sites, mra_sites_cov and mra_sample_sites take their sites in the caller's
+ * coordinates and transform them the same way (a site that is a tree location still reproduces that row bit for bit; the duplicate
+ * collapse of mra_sample_sites compares the transformed coordinates).  NULL puts the caller's coordinates back bit for bit.
+ * As after mra_plan_set_kernel the retained factors, the kept prior and the kept residual are dropped; y, the mask, the noise vector, the
+ * leaf lists and every option stay.  Allowed on sharded plans: every rank sets the same A (the rows are the rank's own).
+ * MRA_ERR_STATE before mra_plan_set_locs.  MRA_ERR_INVALID, checked on the host before anything changes: an entry of A that is not
+ * finite; a determinant that is 0 or not finite; a non-NULL A while the kernel is circular (and mra_plan_set_kernel with circular != 0
+ * while a metric is set: the torus has period 1 in the raw coordinate); a non-NULL A on an MRA_KERNEL_HOST plan (and selecting
+ * MRA_KERNEL_HOST while a metric is set: those plans never read coordinates).  mra_get_buffer(13) returns the coordinates the kernels read. */
+int mra_plan_set_metric(mra_plan *plan, const double *A);
+
 /* Replaces: the `obs` and `R` arguments of MRATree (pyMRA/MRATree.py:23, 61-62; NaN = missing,
  * pyMRA/MRANode.py:415).  y_perm: P values, padded leaf order, NaN for missing and for phantom rows.
  * R: scalar nugget variance (the reference requires a Python float, pyMRA/MRANode.py:85-88). */
@@ -375,6 +396,8 @@ int mra_cv(mra_plan *plan, uint32_t flags, double *mean_perm, double *var_perm, 
  * mra_plan_set_obs uploaded, or the pseudo-observations t of the last pass of mra_plan_fit_laplace;
  * 12: stream milliseconds of the last mra_cv under MRA_OPT_KERNEL_TIMING (9 values: basis, leaf, chain, mean with the solver's sweeps,
  * Gram, Cholesky, solve with the reduction, uploads, downloads);
+ * 13: the coordinates as the kernels read them (P x d, padded leaf order): what mra_plan_set_locs uploaded, or A x under
+ * mra_plan_set_metric;
  * copies min(capacity, available) doubles into out, returns the available count in *n_avail.
  * (W after a likelihood-only run is complete only with MRA_OPT_LIK_ROWS off: by default such a run computes W at the rows a
  * likelihood needs - the observed rows, and the knots on the level-by-level path - and leaves the others as they were.) */

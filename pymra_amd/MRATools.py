@@ -47,16 +47,43 @@ class SymbolicLocs:
         return 1            # `if len(locs2)` in the reference's dist(): "second set given"
 
 
-class KernelSpec:
-    """kind + (l, sig) + an overall scale; value = scale * k_kind(D; l, sig)."""
-    __slots__ = ("kind", "l", "sig", "scale", "circular")
+def _check_metric(A, circular=False):
+    """The ``metric=`` argument of the kernels: None, or a square float64 matrix A (1 x 1 to 3 x 3; a scalar counts as 1 x 1) -
+    distances are |A (a - b)|.  Its size against the locations is checked where both are known."""
+    if A is None:
+        return None
+    A = np.array(A, dtype=np.float64)
+    if A.ndim == 0:
+        A = A.reshape(1, 1)
+    if A.ndim != 2 or A.shape[0] != A.shape[1] or not 1 <= A.shape[0] <= 3:
+        raise ValueError("metric must be a d x d matrix with d = 1, 2 or 3, got shape %r" % (A.shape,))
+    if circular:
+        raise ValueError("metric= cannot be combined with circular=True: the torus has period 1 in the raw coordinate")
+    return A
 
-    def __init__(self, kind, l=1.0, sig=1.0, scale=1.0, circular=False):
+
+def _in_metric(locs, A):
+    """locs @ A.T: the coordinates distances are taken on under metric=A (None for None or an empty second set)."""
+    if A is None or locs is None or not len(locs):
+        return locs
+    locs = np.asarray(locs, dtype=np.float64)
+    locs = locs if locs.ndim == 2 else locs.reshape(len(locs), 1)
+    if locs.shape[1] != A.shape[0]:
+        raise ValueError("metric is %d x %d but the locations have %d coordinates" % (A.shape[0], A.shape[0], locs.shape[1]))
+    return locs @ A.T
+
+
+class KernelSpec:
+    """kind + (l, sig) + an overall scale; value = scale * k_kind(D; l, sig), D = |a - b| or, with a metric A, |A (a - b)|."""
+    __slots__ = ("kind", "l", "sig", "scale", "circular", "A")
+
+    def __init__(self, kind, l=1.0, sig=1.0, scale=1.0, circular=False, A=None):
         self.kind, self.l, self.sig, self.scale, self.circular = int(kind), float(l), float(sig), float(scale), bool(circular)
+        self.A = _check_metric(A, self.circular)
 
     def __mul__(self, c):
         if isinstance(c, (int, float, np.floating, np.integer)):
-            return KernelSpec(self.kind, self.l, self.sig, self.scale * float(c), self.circular)
+            return KernelSpec(self.kind, self.l, self.sig, self.scale * float(c), self.circular, self.A)
         return NotImplemented
 
     __rmul__ = __mul__
@@ -70,10 +97,12 @@ class KernelSpec:
     def evaluate(self, locs1, locs2):
         """Host evaluation (tests / diagnostics); same arithmetic as the array path below."""
         fn = _HOST_KERNELS[self.kind]
-        return self.scale * np.asarray(fn(np.asarray(locs1), np.asarray(locs2), self.l, self.sig, self.circular))
+        locs1, locs2 = _in_metric(np.asarray(locs1), self.A), _in_metric(np.asarray(locs2), self.A)
+        return self.scale * np.asarray(fn(locs1, locs2, self.l, self.sig, self.circular))
 
     def __repr__(self):
-        return "KernelSpec(kind=%d, l=%g, sig=%g, scale=%g)" % (self.kind, self.l, self.sig, self.scale)
+        base = "KernelSpec(kind=%d, l=%g, sig=%g, scale=%g" % (self.kind, self.l, self.sig, self.scale)
+        return base + (")" if self.A is None else ", A=%s)" % np.array2string(self.A, separator=", ").replace("\n", ""))
 
 
 def _symbolic(*args):
@@ -120,6 +149,25 @@ def chord_of_arc(theta, radius=1.0):
 def arc_of_chord(c, radius=1.0):
     """Great-circle distance of a chord length c: 2 R asin(c / 2R), the inverse of chord_of_arc."""
     return 2.0 * radius * np.arcsin(np.clip(np.asarray(c, dtype=np.float64) / (2.0 * radius), -1.0, 1.0))
+
+
+def aniso2d(ratio, angle, degrees=True):
+    """The 2 x 2 metric of geometric anisotropy: with a kernel of range l, the range is l along the major axis of correlation,
+    which points along ``angle`` (counter-clockwise from the x axis), and l / ratio across it.  A = diag(1, ratio) R(-angle)."""
+    ratio = float(ratio)
+    if not ratio > 0.0:
+        raise ValueError("ratio must be positive")
+    th = np.deg2rad(float(angle)) if degrees else float(angle)
+    c, s = np.cos(th), np.sin(th)
+    return np.array([[c, s], [-ratio * s, ratio * c]])
+
+
+def ard(lengths):
+    """Per-axis ranges: diag(1 / lengths), to be used with l = 1 (space-time data on (x, y, t): ard([lx, ly, lt]))."""
+    lengths = np.atleast_1d(np.asarray(lengths, dtype=np.float64))
+    if lengths.ndim != 1 or not 1 <= len(lengths) <= 3 or not np.all(lengths > 0.0):
+        raise ValueError("lengths must be 1 to 3 positive numbers")
+    return np.diag(1.0 / lengths)
 
 
 def dist(locs, locs2=np.array([]), circular=False):
@@ -201,7 +249,7 @@ def determine_radius(k, h, ndim=2):
     return h * np.sqrt((base + 1) ** 2 + (pick - 1) ** 2) + h * 0.01
 
 
-def KanterCovFun(locs, locs2=np.array([]), radius=1.0, circular=False):
+def KanterCovFun(locs, locs2=np.array([]), radius=1.0, circular=False, metric=None):
     """radius: float = taper radius; int = target number of points in the support (resolved from the grid
     spacing of ``locs`` like the reference does; on the device path from the tree's full location set)."""
     src = locs.data if isinstance(locs, SymbolicLocs) else locs
@@ -211,36 +259,42 @@ def KanterCovFun(locs, locs2=np.array([]), radius=1.0, circular=False):
         xs = np.sort(np.unique(src[:, 0]))
         ndim = len(np.unique(src[:, 1])) if src.shape[1] > 1 else 1
         radius = determine_radius(radius, xs[1] - xs[0], ndim=ndim)
+    metric = _check_metric(metric, circular)
     if _symbolic(locs, locs2):
-        return KernelSpec(KIND_KANTER, radius, 1.0, 1.0, circular)
-    return _kanter(locs, locs2, radius, 1.0, circular)
+        return KernelSpec(KIND_KANTER, radius, 1.0, 1.0, circular, metric)
+    return _kanter(_in_metric(locs, metric), _in_metric(locs2, metric), radius, 1.0, circular)
 
 
-def Iden(locs, locs2=np.array([]), l=1, circular=False):
+def Iden(locs, locs2=np.array([]), l=1, circular=False, metric=None):
+    metric = _check_metric(metric, circular)
     if _symbolic(locs, locs2):
-        return KernelSpec(KIND_IDEN, l, 1.0, 1.0, circular)
-    return _iden(locs, locs2, l, 1.0, circular)
+        return KernelSpec(KIND_IDEN, l, 1.0, 1.0, circular, metric)
+    return _iden(_in_metric(locs, metric), _in_metric(locs2, metric), l, 1.0, circular)
 
 
-def ExpCovFun(locs, locs2=np.array([]), l=1, circular=False):
+def ExpCovFun(locs, locs2=np.array([]), l=1, circular=False, metric=None):
+    metric = _check_metric(metric, circular)
     if _symbolic(locs, locs2):
-        return KernelSpec(KIND_EXP, l, 1.0, 1.0, circular)
-    return _exp(locs, locs2, l, 1.0, circular)
+        return KernelSpec(KIND_EXP, l, 1.0, 1.0, circular, metric)
+    return _exp(_in_metric(locs, metric), _in_metric(locs2, metric), l, 1.0, circular)
 
 
-def Matern52(locs, locs2=np.array([]), l=1, sig=1, circular=False):
+def Matern52(locs, locs2=np.array([]), l=1, sig=1, circular=False, metric=None):
+    metric = _check_metric(metric, circular)
     if _symbolic(locs, locs2):
-        return KernelSpec(KIND_MATERN52, l, sig, 1.0, circular)
-    return np.matrix(_m52(locs, locs2, l, sig, circular))
+        return KernelSpec(KIND_MATERN52, l, sig, 1.0, circular, metric)
+    return np.matrix(_m52(_in_metric(locs, metric), _in_metric(locs2, metric), l, sig, circular))
 
 
-def Matern32(locs, locs2=np.array([]), l=1, sig=1, circular=False):
+def Matern32(locs, locs2=np.array([]), l=1, sig=1, circular=False, metric=None):
+    metric = _check_metric(metric, circular)
     if _symbolic(locs, locs2):
-        return KernelSpec(KIND_MATERN32, l, sig, 1.0, circular)
-    return np.matrix(_m32(locs, locs2, l, sig, circular))
+        return KernelSpec(KIND_MATERN32, l, sig, 1.0, circular, metric)
+    return np.matrix(_m32(_in_metric(locs, metric), _in_metric(locs2, metric), l, sig, circular))
 
 
-def GaussianCovFun(locs, locs2=np.array([]), l=1, sig=1, circular=False):
+def GaussianCovFun(locs, locs2=np.array([]), l=1, sig=1, circular=False, metric=None):
+    metric = _check_metric(metric, circular)
     if _symbolic(locs, locs2):
-        return KernelSpec(KIND_GAUSSIAN, l, sig, 1.0, circular)
-    return np.matrix(_gauss(locs, locs2, l, sig, circular))
+        return KernelSpec(KIND_GAUSSIAN, l, sig, 1.0, circular, metric)
+    return np.matrix(_gauss(_in_metric(locs, metric), _in_metric(locs2, metric), l, sig, circular))

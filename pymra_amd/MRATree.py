@@ -174,6 +174,7 @@ class MRATree(object):
             raise ValueError("circular distances are defined for 1-D locations only")
         if spec is None and not callable(cov) and not isinstance(cov, np.ndarray):
             raise TypeError("cov must be a callable cov(locs1, locs2) or a dense N x N matrix")
+        self._check_spec_metric(spec)
         self.kernel = spec          # None: opaque callable / dense matrix -> values come from the host
 
         logger.debug('r: %d, \tJ: %d,\tM: %d' % (self.r, self.J, self.M))
@@ -193,6 +194,8 @@ class MRATree(object):
             self.plan.set_locs(self.cov_locs if self._split_coords else locs)
             self.plan.set_obs(obs_arr, R)
         if spec is not None:
+            if spec.A is not None:
+                self.plan.set_metric(spec.A)        # (before the kernel, as reevaluate sends it)
             self.plan.set_kernel(spec.kind, spec.l, spec.sig, spec.scale, spec.circular)
         else:
             # cov-callable plug-in for anything the device cannot evaluate itself (pyMRA/MRANode.py:73-80,
@@ -206,6 +209,21 @@ class MRATree(object):
             mean, var, self._sd = None, None, None
         self.root = RootView(d, u, mean, var, N, self.topology, self.cov_locs, spec)
         self._node_blocks = {}
+
+    def _check_spec_metric(self, spec):
+        """A kernel's metric A (``mt.Matern32(..., metric=A)``) lives in the covariance coordinates: cov_d x cov_d (3 x 3 on the xyz
+        coordinates under metric="chordal")."""
+        if spec is not None and spec.A is not None and spec.A.shape != (self.cov_d, self.cov_d):
+            raise ValueError("the kernel's metric must be a %d x %d matrix (the covariance is evaluated on %d coordinates), got shape %r"
+                             % (self.cov_d, self.cov_d, self.cov_d, spec.A.shape))
+
+    def _send_kernel(self, spec):
+        """The kernel of a later pass on the same plan: a changed metric (or its removal) first, then the kernel."""
+        old = self.kernel.A if self.kernel is not None else None
+        if (spec.A is None) != (old is None) or (spec.A is not None and not np.array_equal(spec.A, old)):
+            self.plan.set_metric(spec.A)
+        self.kernel = spec
+        self.plan.set_kernel(spec.kind, spec.l, spec.sig, spec.scale, spec.circular)
 
     @property
     def obs_inds(self):
@@ -521,9 +539,9 @@ class MRATree(object):
         spec = probe_cov(cov, self.cov_d, self.cov_locs)
         if spec is None:
             raise NotImplementedError("cov must be a device kernel")
-        self.kernel = spec
+        self._check_spec_metric(spec)
         self._node_blocks = {}
-        self.plan.set_kernel(spec.kind, spec.l, spec.sig, spec.scale, spec.circular)
+        self._send_kernel(spec)
         self.plan.run(likelihood=True, predict=want_predict)
         d, u = self.plan.likelihood()
         mean, var, self._sd = self.plan.predict(with_sd=True) if want_predict else (None, None, None)
@@ -557,8 +575,8 @@ class MRATree(object):
             spec = probe_cov(cov, self.cov_d, self.cov_locs)
             if spec is None:
                 raise NotImplementedError("cov must be a device kernel")
-            self.kernel = spec
-            self.plan.set_kernel(spec.kind, spec.l, spec.sig, spec.scale, spec.circular)
+            self._check_spec_metric(spec)
+            self._send_kernel(spec)
         if z is None:
             z = self.obs
         if x0 is None:

@@ -2937,6 +2937,15 @@ static std::vector<int> sites_check_sites(const mra_plan* pl, const char* who, i
     return lslot;
 }
 
+// the sites of the three site calls as the kernels read them: the caller's own without a metric, else A s by the metric's one function
+static const double* sites_in_metric(const mra_plan* pl, int64_t n, const double* sites, std::vector<double>& store) {
+    if (!pl->metric_on || n <= 0) return sites;
+    const int d = pl->d;
+    store.resize((size_t)n * d);
+    for (int64_t i = 0; i < n; ++i) mra_metric_row_d(d, pl->metric_A, sites + i * d, store.data() + i * d);
+    return store.data();
+}
+
 // The state the site calls run on: the site descriptors, and W at every row and the factors
 static void sites_ensure_state(mra_plan* pl) {
     HIP_TRY(mraSetDevice(pl->device));
@@ -2962,6 +2971,8 @@ static void predict_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const dou
     if (nc < 0) throw MraError(MRA_ERR_INVALID, "n_cols < 0");
     if (!Y && nc != 1) throw MraError(MRA_ERR_INVALID, "Y is NULL (the plan's own observations): n_cols must be 1");
     const std::vector<int> lslot = sites_check_sites(pl, "mra_predict_sites", n, sites, leaf);
+    std::vector<double> msites;
+    sites = sites_in_metric(pl, n, sites, msites);
     const long P = pl->P;
     const int d = pl->d;
     const bool want_mean = mean != nullptr && nc > 0;
@@ -3029,6 +3040,8 @@ static void sites_cov_all(mra_plan* pl, uint32_t flags, int64_t n, const double*
     }
     if (n > 0 && !out) throw MraError(MRA_ERR_INVALID, "out is NULL");
     const std::vector<int> lslot = sites_check_sites(pl, "mra_sites_cov", n, sites, leaf);
+    std::vector<double> msites;
+    sites = sites_in_metric(pl, n, sites, msites);
     if (n == 0) return;
     const bool post = (flags & MRA_COV_POSTERIOR) != 0;
     const int d = pl->d;
@@ -3089,6 +3102,8 @@ static void sample_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const doub
     check_sample0(sample0, ns_all);
     if (n > 0 && ns_all > 0 && !out) throw MraError(MRA_ERR_INVALID, "out is NULL");
     const std::vector<int> lslot = sites_check_sites(pl, "mra_sample_sites", n, sites, leaf);
+    std::vector<double> msites;
+    sites = sites_in_metric(pl, n, sites, msites);      // (the duplicate collapse below compares what the kernels read)
     const int d = pl->d;
     const size_t nl = pl->leaf_nodes.size();
     // exact duplicates (same leaf, equal coordinates) collapse to their first occurrence: first[i] = the caller's index of it
@@ -3448,11 +3463,14 @@ static double* stage_buffer(size_t n) {               // caller holds g_stage_mu
 static void set_knot_coords_src(mra_plan* pl, const double* locs, const int64_t* src);
 static void set_knot_coords(mra_plan* pl, const double* locs) { set_knot_coords_src(pl, locs, nullptr); }
 // (src: locs is the CALLER's N x d array and padded row p holds caller row src[p]; nullptr: locs is already in padded order)
+static void upload_knot_chain(mra_plan* pl, const std::vector<std::vector<double>>& kxh);
+static void upload_knot_coords(mra_plan* pl);
 static void set_knot_coords_src(mra_plan* pl, const double* locs, const int64_t* src) {
     prior_keep_reset(pl);
     if (!pl->regular) return;
     const int cw = pl->cw[0];
     std::vector<std::vector<double>> kxh(pl->kc_levels);
+    if (pl->metric_on) pl->knot_raw.assign((size_t)pl->NL, std::vector<double>());
     for (int m = 0; m < pl->NL; ++m) {
         const LevelData& lv = pl->lev[m];
         std::vector<double> kx(lv.nodes.size() * (size_t)cw * pl->d);
@@ -3465,9 +3483,17 @@ static void set_knot_coords_src(mra_plan* pl, const double* locs, const int64_t*
                 for (int k = 0; k < pl->d; ++k)
                     kx[(sl * cw + c) * pl->d + k] = locs[(src ? src[pl->knot_rows[pl->knot_ptr[i] + c]] : pl->knot_rows[pl->knot_ptr[i] + c]) * pl->d + k];
         }
+        if (pl->metric_on) { pl->knot_raw[m].swap(kx); continue; }      // (the metric's plans: kept raw, sent transformed below)
         HIP_TRY(mraMemcpy(pl->fl[m].kx.p, kx.data(), kx.size() * sizeof(double), hipMemcpyHostToDevice));
         if (m < pl->kc_levels) kxh[m].swap(kx);
     }
+    if (pl->metric_on) { upload_knot_coords(pl); return; }
+    upload_knot_chain(pl, kxh);
+}
+
+// k_knot_chain's packed records from the knot coordinates of its levels (kxh[m], m < kc_levels, as the kernels read them)
+static void upload_knot_chain(mra_plan* pl, const std::vector<std::vector<double>>& kxh) {
+    const int cw = pl->cw[0];
     // k_knot_chain: every workgroup's knots of all its levels in one record (coordinates, then 1.0 / 0.0 = real / phantom)
     if (pl->kc_levels >= 2 && pl->kc_knots.n) {
         const int nlv = pl->kc_levels, d = pl->d;
@@ -3484,6 +3510,28 @@ static void set_knot_coords_src(mra_plan* pl, const double* locs, const int64_t*
             }
         HIP_TRY(mraMemcpy(pl->kc_knots.p, pk.data(), pk.size() * sizeof(double), hipMemcpyHostToDevice));
     }
+}
+
+// The knot coordinates of a plan that has (or just dropped) a metric, from the raw ones it keeps: real knots through the metric's one
+// function (mra_metric_row), phantom knots as they are - MRA_FAR_AWAY is a distance to stay away by, not a location.
+static void upload_knot_coords(mra_plan* pl) {
+    if (!pl->regular || pl->knot_raw.empty()) return;
+    const int cw = pl->cw[0], d = pl->d;
+    std::vector<std::vector<double>> kxh(pl->kc_levels);
+    for (int m = 0; m < pl->NL; ++m) {
+        const LevelData& lv = pl->lev[m];
+        std::vector<double> kx = pl->knot_raw[m];
+        if (pl->metric_on)
+            for (size_t sl = 0; sl < lv.nodes.size(); ++sl) {
+                const int i = lv.nodes[sl];
+                const long rk = pl->knot_ptr[i + 1] - pl->knot_ptr[i];
+                for (long c = 0; c < rk; ++c)
+                    mra_metric_row_d(d, pl->metric_A, pl->knot_raw[m].data() + (sl * cw + c) * d, kx.data() + (sl * cw + c) * d);
+            }
+        HIP_TRY(mraMemcpy(pl->fl[m].kx.p, kx.data(), kx.size() * sizeof(double), hipMemcpyHostToDevice));
+        if (m < pl->kc_levels) kxh[m].swap(kx);
+    }
+    upload_knot_chain(pl, kxh);
 }
 
 // ---- one plan lifetime ------------------------------------------------------------------------------------------------------
@@ -3551,13 +3599,74 @@ static int guarded(mra_plan* pl, F&& body) {
 static void require(bool ok, const char* msg) { if (!ok) throw MraError(MRA_ERR_INVALID, msg); }
 
 // ---- inputs and results in padded leaf order (the exports, their caller-order variants and the one-call constructor) ----------
+// X = A Xraw on the plan's stream, finished before the call returns (the uploads around it are synchronous copies)
+static void metric_transform_X(mra_plan* pl) {
+    mra_metric_apply(pl);
+    if (!g_dry) { HIP_TRY(hipGetLastError()); HIP_TRY(hipStreamSynchronize(pl->stream)); }
+}
+
+// a device-to-device copy of n doubles ordered with the transform: on the plan's stream, finished before the call returns
+static void metric_copy(mra_plan* pl, double* dst, const double* src, size_t n) {
+    if (g_dry) { memcpy(dst, src, n * sizeof(double)); return; }
+    HIP_TRY(hipMemcpyAsync(dst, src, n * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+    HIP_TRY(hipStreamSynchronize(pl->stream));
+}
+
 static void set_locs(mra_plan* pl, const double* locs) {
     HIP_TRY(mraSetDevice(pl->device));
     pl->slv.valid = false;
     prior_keep_reset(pl);
-    HIP_TRY(mraMemcpy(pl->X.p, locs, (size_t)pl->P * pl->d * sizeof(double), hipMemcpyHostToDevice));
+    // (a plan with a metric keeps the caller's coordinates in Xraw; X and the knot coordinates are A x)
+    HIP_TRY(mraMemcpy(pl->metric_on ? pl->Xraw.p : pl->X.p, locs, (size_t)pl->P * pl->d * sizeof(double), hipMemcpyHostToDevice));
+    if (pl->metric_on) metric_transform_X(pl);
     if (!pl->knots_pending) set_knot_coords(pl, locs);
     pl->have_locs = true;
+}
+
+// mra_plan_set_metric.  A: d x d row-major, nullptr: no metric.  Everything is checked before anything changes.
+static void set_metric(mra_plan* pl, const double* A) {
+    if (!pl->have_locs) throw MraError(MRA_ERR_STATE, "mra_plan_set_metric needs mra_plan_set_locs first (the metric transforms the plan's coordinates)");
+    const int d = pl->d;
+    if (A) {
+        for (int k = 0; k < d * d; ++k)
+            if (!std::isfinite(A[k])) throw MraError(MRA_ERR_INVALID, "mra_plan_set_metric: an entry of A is not finite");
+        const double det = d == 1 ? A[0] : d == 2 ? A[0] * A[3] - A[1] * A[2]
+                         : A[0] * (A[4] * A[8] - A[5] * A[7]) - A[1] * (A[3] * A[8] - A[5] * A[6]) + A[2] * (A[3] * A[7] - A[4] * A[6]);
+        if (!(std::isfinite(det) && det != 0.0)) throw MraError(MRA_ERR_INVALID, "mra_plan_set_metric: A is singular (its determinant is 0 or not finite)");
+        if (pl->host_cov) throw MraError(MRA_ERR_INVALID, "mra_plan_set_metric: MRA_KERNEL_HOST plans never read coordinates (apply the metric in the callable)");
+        if (pl->have_kernel && pl->kp.circular) throw MraError(MRA_ERR_INVALID, "mra_plan_set_metric: the kernel is circular (the torus has period 1 in the raw coordinate)");
+    }
+    HIP_TRY(mraSetDevice(pl->device));
+    pl->slv.valid = false;
+    prior_keep_reset(pl);
+    if (!A && !pl->metric_on) return;
+    const size_t n = (size_t)pl->P * d;
+    if (A) {
+        if (!pl->metric_on) {
+            // the first metric: the caller's coordinates move to an array of their own, and the raw knot coordinates of the fused
+            // levels come back to the host once (the plan retains no host locations)
+            pl->Xraw.alloc(n);
+            metric_copy(pl, pl->Xraw.p, pl->X.p, n);
+            pl->metric_on = true;
+            if (pl->regular && !pl->knots_pending) {
+                std::vector<double> raw(n);
+                HIP_TRY(mraMemcpy(raw.data(), pl->Xraw.p, n * sizeof(double), hipMemcpyDeviceToHost));
+                std::copy(A, A + d * d, pl->metric_A);
+                metric_transform_X(pl);
+                set_knot_coords(pl, raw.data());         // (keeps knot_raw, sends the transformed knots)
+                return;
+            }
+        }
+        std::copy(A, A + d * d, pl->metric_A);
+        metric_transform_X(pl);
+        upload_knot_coords(pl);
+    } else {
+        metric_copy(pl, pl->X.p, pl->Xraw.p, n);
+        pl->metric_on = false;
+        upload_knot_coords(pl);                          // (metric off: the raw knots as they are)
+        pl->Xraw.release();
+        pl->knot_raw.clear(); pl->knot_raw.shrink_to_fit();
+    }
 }
 
 static void set_obs(mra_plan* pl, const double* y, double R) {
@@ -3991,6 +4100,10 @@ int mra_get_predict_rows_sd(mra_plan* pl, const int64_t* perm, const uint8_t* in
     });
 }
 
+int mra_plan_set_metric(mra_plan* pl, const double* A) {
+    return guarded(pl, [&] { require(pl, "mra_plan_set_metric: plan is NULL"); set_metric(pl, A); return MRA_OK; });
+}
+
 int mra_plan_set_obs(mra_plan* pl, const double* y, double R) {
     return guarded(pl, [&] { require(pl && y, "mra_plan_set_obs: plan or y is NULL"); set_obs(pl, y, R); return MRA_OK; });
 }
@@ -4022,6 +4135,10 @@ int mra_plan_fit_laplace(mra_plan* pl, int family, const double* z_perm, const d
 int mra_plan_set_kernel(mra_plan* pl, int kind, const double* params, int n) {
     return guarded(pl, [&] {
         require(pl, "mra_plan_set_kernel: plan is NULL");
+        if (pl->metric_on && kind == MRA_KERNEL_HOST)
+            throw MraError(MRA_ERR_INVALID, "mra_plan_set_kernel: MRA_KERNEL_HOST on a plan with a metric (such plans never read coordinates; mra_plan_set_metric(NULL) first)");
+        if (pl->metric_on && kind != MRA_KERNEL_HOST && params && n >= 4 && params[3] != 0.0)
+            throw MraError(MRA_ERR_INVALID, "mra_plan_set_kernel: circular distances on a plan with a metric (the torus has period 1 in the raw coordinate)");
         pl->slv.valid = false;
         prior_keep_reset(pl);                // on every call: the values are not compared
         if (kind == MRA_KERNEL_HOST) {
@@ -4222,6 +4339,7 @@ int mra_get_buffer(mra_plan* pl, int what, double* out, int64_t cap, int64_t* n_
         else if (what == 5) { src = pl->kstamps.p; n = (int64_t)pl->kstamps.n; }   // same, knot chain
         else if (what == 6) { src = pl->kstamps2.p; n = (int64_t)pl->kstamps2.n; } // same, fused leaf solve + update
         else if (what == 4) { src = pl->tstamps.p; n = (int64_t)pl->tstamps.n; }   // same, leaf row solves   // same, predictive cascade
+        else if (what == 13) { src = pl->X.p; n = (int64_t)pl->P * pl->d; }         // the coordinates as the kernels read them (A x under mra_plan_set_metric)
         else if (what == 11) { src = pl->y.p; n = pl->P; }                         // the observations as the device holds them (the pseudo-observations t after mra_plan_fit_laplace)
         else throw MraError(MRA_ERR_INVALID, "unknown buffer id");
         *n_avail = n;

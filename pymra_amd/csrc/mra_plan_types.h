@@ -43,6 +43,25 @@ static inline hipError_t mraSetDevice(int dev) { return g_dry ? hipSuccess : hip
 
 static thread_local std::string g_last_error;
 
+// ---- the metric of mra_plan_set_metric ------------------------------------------------------------------
+// t = A x for one row of coordinates, A d x d row-major: row i is A[i][0] x[0], then one fma per further column, in column order.
+// The ONE arithmetic of the transform: the device kernel (k_metric_apply), the knot coordinates and the sites staged on the host all
+// go through this function, and explicit fma leaves nothing to contraction: the same bits everywhere.  A = I returns x.
+template <int DIM>
+__host__ __device__ __forceinline__ void mra_metric_row(const double* __restrict__ A, const double* x, double* t) {
+#pragma unroll
+    for (int i = 0; i < DIM; ++i) {
+        double acc = A[i * DIM] * x[0];
+#pragma unroll
+        for (int k = 1; k < DIM; ++k) acc = __builtin_fma(A[i * DIM + k], x[k], acc);
+        t[i] = acc;
+    }
+}
+// the same for d known at run time (x and t must not overlap)
+static inline void mra_metric_row_d(int d, const double* A, const double* x, double* t) {
+    if (d == 1) mra_metric_row<1>(A, x, t); else if (d == 2) mra_metric_row<2>(A, x, t); else mra_metric_row<3>(A, x, t);
+}
+
 #define HIP_TRY(expr)                                                                     \
     do {                                                                                  \
         hipError_t _e = (expr);                                                           \
@@ -361,6 +380,13 @@ struct mra_plan {
     KernelParams kp{};
     bool host_cov = false;
     double R = 0.0;
+    // the metric of mra_plan_set_metric: while metric_on the kernels' X (and the knot coordinates of the fused levels) hold A x and
+    // Xraw the caller's coordinates; knot_raw[m] = the untransformed knot coordinates of fused level m as set_knot_coords lays them
+    // out (phantom knots included), so that a new A needs no host locations.  Nothing of this is allocated before the first metric.
+    bool metric_on = false;
+    double metric_A[9] = {1, 0, 0, 0, 1, 0, 0, 0, 1};
+    DevVec<double> Xraw;
+    std::vector<std::vector<double>> knot_raw;
     // per-observation noise variances (mra_plan_set_noise): while noise_on the leaves' C = v_M(o,o) + diag(r_o) - the leaf descriptors
     // carry diag_add = 0 and run_leaf_noise adds r on the diagonal; noise_sd = sqrt(r) for the pseudo-data of conditional draws.
     // By padded row, 0 at rows the plan does not observe.  Dropped by the next mra_plan_set_obs (pl->R holds again).
@@ -788,5 +814,6 @@ constexpr int MRA_HOST_RES_DOUBLES = 16, MRA_HOST_RES_LAPLACE = 8;      // the p
 void mra_laplace_reserve(mra_plan* pl);
 void mra_laplace_linearise(mra_plan* pl, int family, const double* x_in);
 void mra_laplace_reduce(mra_plan* pl, int family, double* res);
+void mra_metric_apply(mra_plan* pl);                  // X = A Xraw by row (k_metric_apply), on the plan's stream
 // with MRA_OPT_KERNEL_TIMING: `work` between two events on pl->stream, the time added to sit.ms[which] (sit.ms_sink[which] when set; one synchronisation each: a measuring mode)
 void mra_sites_timed(mra_plan* pl, int which, const std::function<void()>& work);

@@ -71,7 +71,7 @@ ERR_NAMES = {-1: "MRA_ERR_INVALID", -2: "MRA_ERR_HIP", -3: "MRA_ERR_NOT_SPD", -4
 # every symbol include/mra_hip.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "mra_device_count", "mra_release_cached_memory", "mra_plan_create", "mra_plan_destroy", "mra_plan_set_locs", "mra_plan_set_obs",
-    "mra_plan_set_noise", "mra_plan_set_noise_rows", "mra_plan_fit_laplace",
+    "mra_plan_set_noise", "mra_plan_set_noise_rows", "mra_plan_fit_laplace", "mra_plan_set_metric",
     "mra_plan_set_kernel", "mra_plan_set_locs_rows", "mra_plan_set_obs_rows", "mra_get_predict_rows", "mra_get_predict_rows_sd", "mra_eval_kernel", "mra_plan_set_cov_block", "mra_run", "mra_get_likelihood", "mra_get_predict",
     "mra_sample_slots", "mra_sample", "mra_solve", "mra_cov_apply", "mra_predict_sites", "mra_sites_cov", "mra_sample_sites_slots", "mra_sample_sites", "mra_cv", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
     "mra_get_kernel_stats", "mra_get_kernel_work", "mra_get_route", "mra_device_synchronize", "mra_plan_info", "mra_comm_unique_id", "mra_comm_init",
@@ -123,6 +123,7 @@ def load_library():
         "mra_plan_set_locs": (C.c_int, [vp, vp]),
         "mra_plan_set_obs": (C.c_int, [vp, vp, dbl]),
         "mra_plan_set_noise": (C.c_int, [vp, vp]),
+        "mra_plan_set_metric": (C.c_int, [vp, vp]),
         "mra_plan_set_noise_rows": (C.c_int, [vp, vp, vp]),
         "mra_plan_fit_laplace": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, dbl, vp]),
         "mra_plan_set_locs_rows": (C.c_int, [vp, vp, vp]),
@@ -291,6 +292,18 @@ class HipPlan:
             raise ValueError("locs must be N x d")
         src, _, _ = self._row_maps()
         self._check(self.lib.mra_plan_set_locs_rows(self._h, _ptr(X), _ptr(src)))
+
+    def set_metric(self, A):
+        """Distances become |A (a - b)| (mra_plan_set_metric): A d x d in the coordinates of ``set_locs``, None = no metric.  The
+        plan keeps the caller's coordinates and hands every kernel A x (``buffer(13)``); ``set_locs``, ``set_obs`` and the sites of
+        ``predict_sites`` and its siblings stay in the caller's coordinates.  Like ``set_kernel`` it drops the retained factors."""
+        if A is None:
+            self._check(self.lib.mra_plan_set_metric(self._h, None))
+            return
+        A = np.ascontiguousarray(A, dtype=np.float64)
+        if A.shape != (self.d, self.d):
+            raise ValueError("the metric must be a %d x %d matrix, got shape %r" % (self.d, self.d, A.shape))
+        self._check(self.lib.mra_plan_set_metric(self._h, _ptr(A)))
 
     def _noise_rows(self, R):
         r = np.ascontiguousarray(np.asarray(R, dtype=np.float64))
