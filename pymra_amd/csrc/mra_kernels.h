@@ -25,6 +25,7 @@
 
 typedef double d4 __attribute__((ext_vector_type(4)));
 typedef double d2 __attribute__((ext_vector_type(2)));
+typedef int i4 __attribute__((ext_vector_type(4)));
 
 // Pointers that reach a kernel inside a descriptor read from memory (GemmProb, PanelProb, ...) are
 // generic to the compiler, and every access through them becomes a FLAT instruction: those count on
@@ -2125,13 +2126,132 @@ struct Trsm2Prob {
 };
 
 
+// -DMRA_STAMPS: eight clock stamps per row tile, [problem][64 row tiles][8 slots]; srow is the tile's record (nullptr: no stamps).
+// 0, 1: the workgroup's clock before and after the staging of the leaf's image; 2: the tile's loads are issued from here; 3: they
+// have arrived; 4: solved and stored; 5: variance updated; 6, 7: the real-time clock at 0 and at 5
 #ifdef MRA_STAMPS
-#define MRA_TSTAMP(slot) do { if (stamps && (threadIdx.x & 63) == 0) stamps[((long)blockIdx.y * 64 + t) * 8 + (slot)] = __builtin_amdgcn_s_memtime(); } while (0)
+#define MRA_TSTAMP(slot) do { if (srow && (threadIdx.x & 63) == 0) srow[slot] = __builtin_amdgcn_s_memtime(); } while (0)
 #define MRA_TSTAMP_ARG , unsigned long long* stamps
+#define MRA_TSTAMP_ROW_ARG , unsigned long long* srow
+#define MRA_TSTAMP_ROW(prob, t) , (stamps ? stamps + ((long)(prob) * 64 + (t)) * 8 : (unsigned long long*)nullptr)
 #else
 #define MRA_TSTAMP(slot) do { } while (0)
 #define MRA_TSTAMP_ARG
+#define MRA_TSTAMP_ROW_ARG
+#define MRA_TSTAMP_ROW(prob, t)
 #endif
+
+// the address of 16-byte piece e of a leaf's LDS image: the strictly-lower tiles of L (index jb(jb-1)/2+kb), then the inverted
+// diagonal blocks; 128 pieces per tile, linear in the piece number
+__device__ __forceinline__ const double* trsm2_image_src(const Trsm2Prob& pb, int ntri, int e) {
+    const int tile = e >> 7, chunk = e & 127, row = chunk >> 3, c2 = (chunk & 7) << 1;
+    if (tile < ntri) {
+        int jb = 1;
+        while ((jb + 1) * jb / 2 <= tile) ++jb;
+        const int kb = tile - jb * (jb - 1) / 2;
+        return pb.L + (long)(jb * 16 + row) * pb.ldL + kb * 16 + c2;
+    }
+    return pb.invd + (long)(tile - ntri) * 256 + row * 16 + c2;
+}
+
+// f(step 0), f(step 1), ... f(step n - 1), 1 <= n <= N, the step number a compile-time constant (decltype(JB)::value), step 0
+// unconditional and step I + 1 nested in the branch that runs step I
+template <int I> struct Trsm2Step { static constexpr int value = I; };
+template <int I, int N, class F>
+__device__ __forceinline__ void trsm2_steps(int n, F f) {
+    if constexpr (I < N) {
+        if (I == 0 || I < n) { f(Trsm2Step<I>()); trsm2_steps<I + 1, N>(n, f); }
+    }
+}
+
+// One 16-row tile t of a problem on one wave, lane (r, q), prow = pi16(r): the whole row of tiles loaded, solved against the image
+// `img` (tiles as trsm2_image_src orders them) with two accumulators, stored, and the rows' squares added to var.  GATHER: a tile
+// below pb.gtiles, loaded through the problem's gather list sidx (in LDS); else streamed.  The two are separate instances, run from
+// separate loops: as two branches of one body the compiler interleaved them column tile by column tile, and every gathered column
+// tile waited for the registers the streamed branch might have loaded.
+template <int NTMAX, bool GATHER>
+__device__ __forceinline__ void trsm2_row_tile(const Trsm2Prob& pb, const double* __restrict__ img, const int* __restrict__ sidx, int nt, int ntri,
+                                               int t, int r, int q, int prow MRA_TSTAMP_ROW_ARG) {
+    const d4 zero = {0, 0, 0, 0};
+    MRA_TSTAMP(2);
+    double* xp = pb.X + (long)t * 16 * pb.ldx + (long)r * pb.ldx + 4 * q;
+    const double* lp = (pb.src && t >= pb.gtiles) ? pb.src + ((long)(t - pb.gtiles) * 16 + r) * pb.ldsrc + 4 * q : xp;
+    d4 x[NTMAX];
+    double ssq = 0.0;
+    const bool with_var = pb.var && t >= pb.var_tile0;
+    double* const vp = pb.var + (long)(t - pb.var_tile0) * 16 + r;
+    if (nt <= 0) {                      // nothing to solve: var + sign * 0 (kept apart so that step 0 below is on every path)
+        if (with_var && q == 0) gst(vp, gld(vp) + pb.var_sign * ssq);
+        return;
+    }
+    // the whole row of tiles is fetched first (independent loads in flight together); read one
+    // tile at a time each load would wait behind the store of the previous tile.  (Every loop over the column tiles is
+    // trsm2_steps, in which step 0 is on every path and step jb + 1 lies INSIDE step jb's branch: with `if (jb < nt)` around each
+    // step of an unrolled loop the steps were siblings to the compiler, and each one waited for vmcnt(0) - the stores of the step
+    // before it - because a path around that step might not have waited for the loads.)
+    //
+    // the rows' variance is read in front of the row's loads, not behind its stores: whoever waits for the row has it, and no wait
+    // for it drains the stores (no other tile touches these 16 entries)
+    double var0 = 0.0;
+    if (with_var && q == 0) var0 = gld(vp);
+    if (GATHER) {
+        // every element's load is issued - a list entry < 0 (the padding of the observations to 16) from row 0, a valid address -
+        // and the zeros are put in once all of them are under way: a branch per element put a round trip to LDS in front of each.
+        // (That address lies inside W at every t, r; the oversized leaves' update on the side stream may be writing W's row 0 at
+        // the same time - the value read there is dropped by the select below and never reaches a result.)
+        const double* gp = pb.gW + t * 16 + r;
+        trsm2_steps<0, NTMAX>(nt, [&](auto JB) __attribute__((always_inline)) {
+            constexpr int jb = decltype(JB)::value;
+            const i4 gi = *(const i4*)(sidx + jb * 16 + 4 * q);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) x[jb][j] = gld(gp + (long)max(gi[j], 0) * pb.gld);
+        });
+    } else {
+        trsm2_steps<0, NTMAX>(nt, [&](auto JB) __attribute__((always_inline)) { constexpr int jb = decltype(JB)::value; x[jb] = gld4(lp + jb * 16); });
+    }
+    if (GATHER) {
+        trsm2_steps<0, NTMAX>(nt, [&](auto JB) __attribute__((always_inline)) {
+            constexpr int jb = decltype(JB)::value;
+            const i4 gi = *(const i4*)(sidx + jb * 16 + 4 * q);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) x[jb][j] = gi[j] < 0 ? 0.0 : x[jb][j];
+        });
+    }
+#ifdef MRA_STAMPS
+    if (srow) { __builtin_amdgcn_s_waitcnt(0); MRA_TSTAMP(3); }
+#endif
+    trsm2_steps<0, NTMAX>(nt, [&](auto JB) __attribute__((always_inline)) {
+        constexpr int jb = decltype(JB)::value;
+        d4 acc = x[jb];
+        // two accumulators: a dependent f64 MFMA issues every ~73 ns, an independent one every ~29 ns
+        d4 upd0 = zero, upd1 = zero;
+#pragma unroll
+        for (int kb = 0; kb < jb; ++kb) {
+            const d4 a = *(const d4*)(img + (jb * (jb - 1) / 2 + kb) * 256 + prow * 16 + 4 * q);
+            upd0 = mfma16(a[0], x[kb][0], upd0);
+            upd1 = mfma16(a[1], x[kb][1], upd1);
+            upd0 = mfma16(a[2], x[kb][2], upd0);
+            upd1 = mfma16(a[3], x[kb][3], upd1);
+        }
+        if (jb > 0) acc -= upd0 + upd1;
+        const d4 ia = *(const d4*)(img + (ntri + jb) * 256 + prow * 16 + 4 * q);
+        d4 xx0 = mfma16(ia[0], acc[0], zero), xx1 = mfma16(ia[1], acc[1], zero);
+        xx0 = mfma16(ia[2], acc[2], xx0);
+        xx1 = mfma16(ia[3], acc[3], xx1);
+        const d4 xx = xx0 + xx1;
+        x[jb] = xx;
+        gst4(xp + jb * 16, xx);
+        ssq += xx[0] * xx[0] + xx[1] * xx[1] + xx[2] * xx[2] + xx[3] * xx[3];
+    });
+    MRA_TSTAMP(4);
+    if (with_var) {
+        ssq += __shfl_xor(ssq, 16, 64);
+        ssq += __shfl_xor(ssq, 32, 64);
+        if (q == 0) gst(vp, var0 + pb.var_sign * ssq);
+    }
+    MRA_TSTAMP(5);
+}
+
 template <int NTMAX>
 __global__ __launch_bounds__(512) void k_trsm_rows2(const Trsm2Prob* __restrict__ probs, int tiles_per_wg MRA_TSTAMP_ARG) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -2149,93 +2269,42 @@ __global__ __launch_bounds__(512) void k_trsm_rows2(const Trsm2Prob* __restrict_
     // (Measured at C3: this 72 KB image lets ONE workgroup run per CU although 2 x 72 KB <= 160 KB; with the inverted
     // blocks read from L2 instead the image is 56 KB, two workgroups do run per CU -- and the launch is slower, 0.93 ms
     // against 0.77: the solve moves 3.4 GB in place and sits at ~75% of what HBM streams, more waves only contend.)
-    stage_chunks<8>(lds, (ntri + nt) * 128, [&](int e) -> const double* {
-        const int tile = e >> 7, chunk = e & 127, row = chunk >> 3, c2 = (chunk & 7) << 1;
-        if (tile < ntri) {
-            int jb = 1;
-            while ((jb + 1) * jb / 2 <= tile) ++jb;
-            const int kb = tile - jb * (jb - 1) / 2;
-            return pb.L + (long)(jb * 16 + row) * pb.ldL + kb * 16 + c2;
-        }
-        return pb.invd + (long)(tile - ntri) * 256 + row * 16 + c2;
-    });
+    stage_chunks<8>(lds, (ntri + nt) * 128, [&](int e) -> const double* { return trsm2_image_src(pb, ntri, e); });
     // the gather list of the Ut tiles (the leaf's observed rows) once per workgroup: read per tile from global memory it put a
     // second round trip in front of every gathered tile's loads
     int* const sidx = (int*)(lds + (long)(ntri + nt) * 256);
     if (pb.gtiles > 0 && t_begin < pb.gtiles)
         for (int e = threadIdx.x; e < nt * 16; e += blockDim.x) sidx[e] = gldi(pb.gidx + e);
     __syncthreads();
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
+    // (the wave number through readfirstlane: t is then uniform to the compiler, and a row tile's two kinds of load - gathered or
+    // streamed - are two branches, not one predicated sequence in which each gathered column tile waits for the one before)
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4;
     const int nwave = blockDim.x >> 6;
     const int prow = pi16(r);
-    const d4 zero = {0, 0, 0, 0};
 #ifdef MRA_STAMPS
     const unsigned long long t_wg1 = __builtin_amdgcn_s_memtime();
 #endif
-    for (int t = t_begin + wave; t < t_end; t += nwave) {
 #ifdef MRA_STAMPS
-        if (stamps && lane == 0) { stamps[((long)blockIdx.y * 64 + t) * 8 + 0] = t_wg0; stamps[((long)blockIdx.y * 64 + t) * 8 + 1] = t_wg1; }
+#define MRA_T2_STAMP_HEAD(t) do { if (stamps && lane == 0) { stamps[((long)blockIdx.y * 64 + (t)) * 8 + 0] = t_wg0; stamps[((long)blockIdx.y * 64 + (t)) * 8 + 1] = t_wg1; } } while (0)
+#define MRA_T2_STAMP_TAIL(t) do { if (stamps && lane == 0) { stamps[((long)blockIdx.y * 64 + (t)) * 8 + 6] = t_real0; stamps[((long)blockIdx.y * 64 + (t)) * 8 + 7] = __builtin_amdgcn_s_memrealtime(); } } while (0)
+#else
+#define MRA_T2_STAMP_HEAD(t) do { } while (0)
+#define MRA_T2_STAMP_TAIL(t) do { } while (0)
 #endif
-        MRA_TSTAMP(2);
-        double* xp = pb.X + (long)t * 16 * pb.ldx + (long)r * pb.ldx + 4 * q;
-        const double* lp = (pb.src && t >= pb.gtiles) ? pb.src + ((long)(t - pb.gtiles) * 16 + r) * pb.ldsrc + 4 * q : xp;
-        d4 x[NTMAX];
-        double ssq = 0.0;
-        // the whole row of tiles is fetched first (independent loads in flight together); read one
-        // tile at a time each load would wait behind the store of the previous tile
-#pragma unroll
-        for (int jb = 0; jb < NTMAX; ++jb) {
-            if (jb < nt) {
-                if (t < pb.gtiles) {
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        const int gi = sidx[jb * 16 + 4 * q + j];
-                        x[jb][j] = gi < 0 ? 0.0 : gld(pb.gW + (long)gi * pb.gld + t * 16 + r);
-                    }
-                } else {
-                    x[jb] = gld4(lp + jb * 16);
-                }
-            }
-        }
-#ifdef MRA_STAMPS
-        if (stamps) { __builtin_amdgcn_s_waitcnt(0); MRA_TSTAMP(3); }
-#endif
-#pragma unroll
-        for (int jb = 0; jb < NTMAX; ++jb) {
-            if (jb < nt) {
-                d4 acc = x[jb];
-                // two accumulators: a dependent f64 MFMA issues every ~73 ns, an independent one every ~29 ns
-                d4 upd0 = zero, upd1 = zero;
-#pragma unroll
-                for (int kb = 0; kb < jb; ++kb) {
-                    const d4 a = *(const d4*)(lds + (jb * (jb - 1) / 2 + kb) * 256 + prow * 16 + 4 * q);
-                    upd0 = mfma16(a[0], x[kb][0], upd0);
-                    upd1 = mfma16(a[1], x[kb][1], upd1);
-                    upd0 = mfma16(a[2], x[kb][2], upd0);
-                    upd1 = mfma16(a[3], x[kb][3], upd1);
-                }
-                if (jb > 0) acc -= upd0 + upd1;
-                const d4 ia = *(const d4*)(lds + (ntri + jb) * 256 + prow * 16 + 4 * q);
-                d4 xx0 = mfma16(ia[0], acc[0], zero), xx1 = mfma16(ia[1], acc[1], zero);
-                xx0 = mfma16(ia[2], acc[2], xx0);
-                xx1 = mfma16(ia[3], acc[3], xx1);
-                const d4 xx = xx0 + xx1;
-                x[jb] = xx;
-                gst4(xp + jb * 16, xx);
-                ssq += xx[0] * xx[0] + xx[1] * xx[1] + xx[2] * xx[2] + xx[3] * xx[3];
-            }
-        }
-        MRA_TSTAMP(4);
-        if (pb.var && t >= pb.var_tile0) {
-            ssq += __shfl_xor(ssq, 16, 64);
-            ssq += __shfl_xor(ssq, 32, 64);
-            if (q == 0) { double* vp = pb.var + (long)(t - pb.var_tile0) * 16 + r; gst(vp, gld(vp) + pb.var_sign * ssq); }
-        }
-        MRA_TSTAMP(5);
-#ifdef MRA_STAMPS
-        if (stamps && lane == 0) { stamps[((long)blockIdx.y * 64 + t) * 8 + 6] = t_real0; stamps[((long)blockIdx.y * 64 + t) * 8 + 7] = __builtin_amdgcn_s_memrealtime(); }
-#endif
+    // the wave's gathered tiles, then its streamed ones (tile numbers only grow)
+    int t = t_begin + wave;
+    for (; t < min(t_end, pb.gtiles); t += nwave) {
+        MRA_T2_STAMP_HEAD(t);
+        trsm2_row_tile<NTMAX, true>(pb, lds, sidx, nt, ntri, t, r, q, prow MRA_TSTAMP_ROW(blockIdx.y, t));
+        MRA_T2_STAMP_TAIL(t);
     }
+    for (; t < t_end; t += nwave) {
+        MRA_T2_STAMP_HEAD(t);
+        trsm2_row_tile<NTMAX, false>(pb, lds, sidx, nt, ntri, t, r, q, prow MRA_TSTAMP_ROW(blockIdx.y, t));
+        MRA_T2_STAMP_TAIL(t);
+    }
+#undef MRA_T2_STAMP_HEAD
+#undef MRA_T2_STAMP_TAIL
 }
 
 // ------------------------------------------------------------------------------------------------

@@ -24,6 +24,15 @@ show("tile: loads issued -> arrived", s[:, 3] - s[:, 2])
 show("tile: solve (column tiles 0..nt-1)", s[:, 4] - s[:, 3])
 show("tile: variance update", s[:, 5] - s[:, 4])
 show("tile: whole", s[:, 5] - s[:, 2])
+# the first G row tiles of a leaf are its Ut rows, gathered from W; the others stream V[S,o] (c3: 12 ancestor column tiles + the y block)
+G = int(sys.argv[1]) if len(sys.argv) > 1 else 13
+for nm, sel in (("gathered tiles (Ut)", st[:, :G][ok[:, :G]]), ("streamed tiles (Tt)", st[:, G:][ok[:, G:]])):
+    if len(sel):
+        print(" %s: %d" % (nm, len(sel)))
+        show("  loads issued -> arrived", sel[:, 3] - sel[:, 2])
+        show("  solve + stores issued", sel[:, 4] - sel[:, 3])
+        show("  whole", sel[:, 5] - sel[:, 2])
+print("workgroup: staging wait per leaf as a share of its span: %.3f" % float(np.median((st[:, :, 1] - st[:, :, 0])[ok].reshape(-1)) / np.median(wg_end - wg0)))
 # the shader clock is per XCD: group the workgroups by clock domain (gaps of more than 1e8 cycles between start times)
 order = np.argsort(wg0); w0 = wg0[order]; w1 = wg_end[order]
 cuts = np.flatnonzero(np.diff(w0) > 1e8) + 1
