@@ -231,14 +231,63 @@ int mra_sample(mra_plan *plan, uint32_t flags, int64_t n_samples, uint64_t seed,
  *                                 y = Y[k] (the log-determinant d does not depend on y)
  * Columns are processed in blocks of 16 (the N of v_mfma_f64_16x16x4_f64).  quad is returned BLOCK-DIAGONAL: entries whose row and
  * column lie in the same block of 16 columns (k / 16 equal) are computed, all others are set to NaN - a cross-block entry needs the
- * forward sweeps of both blocks at once.  Callers that need a full quad of more than 16 columns pass overlapping column sets.
+ * forward sweeps of both blocks at once.  Callers that need a full quad of more than 16 columns pass MRA_SOLVE_FULL_QUAD (below).
  * The first call (and the first after mra_run, mra_run_resume, mra_sample or any set_*) runs one likelihood pass with W at every
  * row (MRA_OPT_LIK_ROWS overridden inside); later calls reuse the factors and launch only the solve kernels.  Afterwards y, every
  * option and what mra_get_likelihood / mra_get_predict return are as the caller left them (mra_get_timers / mra_get_kernel_stats
- * describe the call's own pass; all zero when none ran).  flags: 0.
- * MRA_ERR_STATE before set_locs / set_obs / set_kernel; MRA_ERR_INVALID for MRA_KERNEL_HOST plans, sharded plans, n_cols < 0 and a
- * non-finite Y at an observed row.  Work buffers are allocated on the first call.  Blocking. */
+ * describe the call's own pass; all zero when none ran).  flags: 0 or MRA_SOLVE_FULL_QUAD.
+ * MRA_SOLVE_FULL_QUAD: quad is the dense symmetric n_cols x n_cols matrix, no NaN.  Entries whose row and column share a block of 16
+ * are bit for bit those of the call without the flag; the others come from k_solve_quad_cross: the forward sweep of every block
+ * leaves its vectors (the leaves' U_y, the fronts' z: (sum nop + sum cw) x16 doubles per block, about 90 MB per block for a 1024^2
+ * tree with r = 32) in an archive, and Q_ab = sum_seg sign F_a^T F_b is summed over a fixed number of partial sums in a fixed order
+ * (the same bits on every call) and mirrored (symmetric to the bit).  At most MRA_FULL_QUAD_MAX columns (MRA_ERR_INVALID above,
+ * checked before anything is launched).  The archive is allocated by flagged calls of more than 16 columns only (grow-only in the
+ * number of blocks) and released when the solver's descriptors are rebuilt (new observations); a call without the flag allocates and
+ * computes what it did before.
+ * MRA_ERR_STATE before set_locs / set_obs / set_kernel; MRA_ERR_INVALID for unknown flags, MRA_KERNEL_HOST plans, sharded plans,
+ * n_cols < 0 and a non-finite Y at an observed row.  Work buffers are allocated on the first call.  Blocking. */
+#define MRA_SOLVE_FULL_QUAD 1u
+#define MRA_FULL_QUAD_MAX 256
 int mra_solve(mra_plan *plan, uint32_t flags, int64_t n_cols, const double *Y, double *mean, double *quad);
+
+/* A regression trend (no counterpart in the reference, whose fields have mean zero): y_o = X_o beta + x_o + eps with a flat prior on
+ * beta in R^p and K = Sigma_MRA[o, o] + D (D = R I, or the vector of mra_plan_set_noise).  With G = [y | X]^T K^-1 [y | X] (the full
+ * quad of mra_solve for the columns [y | X]), G_yy = G[0][0], b = G[1:, 0], A = G[1:, 1:]:
+ *     beta^ = A^-1 b, cov(beta^) = A^-1; profile -2 log-likelihood = d + (G_yy - b^T beta^); REML criterion = that + log det A
+ * (d: the log-determinant of the pass, constants as in mra_get_likelihood), and with m_y, m_X the zero-mean kriging means of the
+ * columns (mean of mra_solve), h(s) = x(s) - m_X(s): mean(s) = m_y(s) + h(s)^T beta^, var(s) = var_pass(s) + h(s)^T A^-1 h(s) - the
+ * universal-kriging mean and variance (var_pass: the var of mra_get_predict after a predict pass on the plan's y).
+ *
+ * mra_plan_set_trend: X_perm is p x P, row-major (covariate j at X_perm + j P), padded leaf order, 0 at phantom rows; it is copied
+ * to the device once and stays there: a property of the plan, as the noise vector is.  It survives mra_plan_set_obs*,
+ * mra_plan_set_noise*, mra_plan_set_kernel, mra_plan_set_metric, mra_plan_set_locs* and every option, and it drops no factor (X
+ * enters no factorisation).  p = 0 or X_perm = NULL with p = 0 clears it.  MRA_ERR_INVALID, checked on the host before anything
+ * changes: p < 0, p > MRA_TREND_MAX, a NULL X_perm with p > 0, an entry of the p x P array that is not finite.  Works on
+ * MRA_HOST_DRYRUN plans.  Memory: p P doubles on the device.
+ *
+ * mra_trend_fit: fits the trend to the plan's own y.  It shares the factors mra_solve keeps (one likelihood pass with W at every
+ * row if they do not stand, none otherwise), stages [y | X] device to device in blocks of 16 columns (y with NaN read as 0, as
+ * mra_solve reads Y: observed rows only), runs the forward sweeps and forms G as mra_solve with MRA_SOLVE_FULL_QUAD does (same
+ * kernels, same archive: one panel per block, at most four), downloads G and factorises A = L L^T on the host.
+ *     beta (p), cov_beta (p x p, or NULL)
+ *     info[8]: [0] d; [1] G_yy - b^T beta^; [2] log det A; [3] the profile value [0] + [1]; [4] the REML value [3] + [2];
+ *              [5] number of observed rows; [6] p; [7] min / max of diag(L)^2
+ * With MRA_TREND_PREDICT the backward sweeps and the row kernel run per block, m_y and m_X stay on the device ((1 + p) P doubles,
+ * allocated by the first such call, with 3 P more for var_pass and the results) and k_trend_rows writes
+ *     mean_perm, var_perm (P each, padded leaf order, or NULL): the universal-kriging mean and variance; unreported rows exactly 0
+ * var_pass comes from a predict pass on the plan's own y that the call runs itself (and keeps while the factors stand; the
+ * likelihood pass for the factors follows it, since a predict pass rewrites W): the first predicting call runs two passes, later
+ * calls none.  Afterwards y, every option and what mra_get_likelihood / mra_get_predict return are as the caller left them
+ * (mra_get_timers / mra_get_kernel_stats describe the call's own last pass; all zero when none ran).
+ * Refusals, in this order: those of every call on the retained factors (unknown flags: MRA_ERR_INVALID; before set_locs / set_kernel
+ * / set_obs: MRA_ERR_STATE; MRA_KERNEL_HOST plans and sharded plans: MRA_ERR_INVALID); no trend set: MRA_ERR_STATE; a NULL beta or
+ * info, mean_perm or var_perm without MRA_TREND_PREDICT: MRA_ERR_INVALID.  A pivot of A that is <= 0, NaN or below
+ * p 2^-52 max diag(A): MRA_ERR_NOT_SPD, "trend columns are linearly dependent at the observed rows" (a host check of a matrix of at
+ * most 63 x 63; beta is not written).  Blocking. */
+#define MRA_TREND_MAX 63      /* [y | X] is at most 64 columns: four blocks */
+#define MRA_TREND_PREDICT 1u
+int mra_plan_set_trend(mra_plan *plan, int32_t p, const double *X_perm);
+int mra_trend_fit(mra_plan *plan, uint32_t flags, double *beta, double *cov_beta, double *mean_perm, double *var_perm, double *info);
 
 /* The MRA covariance as an operator (no counterpart in the reference, which can only draw from it, pyMRA/MRATools.py:395-484): the
  * prior covariance of the latent field at the reported rows (real rows inside a leaf) is
@@ -398,6 +447,10 @@ int mra_cv(mra_plan *plan, uint32_t flags, double *mean_perm, double *var_perm, 
  * Gram, Cholesky, solve with the reduction, uploads, downloads);
  * 13: the coordinates as the kernels read them (P x d, padded leaf order): what mra_plan_set_locs uploaded, or A x under
  * mra_plan_set_metric;
+ * 14: the last mra_trend_fit (7 values): stream milliseconds under MRA_OPT_KERNEL_TIMING (0 without) of the device-to-device staging
+ * of [y | X], of the solver's sweeps of all blocks with the diagonal tiles of G and the archive copies, of k_solve_quad_cross with its
+ * fold, of k_trend_rows, and of the uploads and downloads; then the bytes of the leaves' Ut (a forward sweep reads them once per
+ * block) and of one block's archive panel (written once, read once);
  * copies min(capacity, available) doubles into out, returns the available count in *n_avail.
  * (W after a likelihood-only run is complete only with MRA_OPT_LIK_ROWS off: by default such a run computes W at the rows a
  * likelihood needs - the observed rows, and the knots on the level-by-level path - and leaves the others as they were.) */
@@ -570,7 +623,8 @@ int mra_get_kernel_stats(mra_plan *plan, int which, char *name, int name_cap, in
 int mra_get_kernel_work(mra_plan *plan, int which, double *out, int capacity);
 /* hipDeviceSynchronize on `device` (bench.py's barrier: the timed region needs no second GPU runtime in the process) */
 int mra_device_synchronize(int device);
-/* out[0..7] = P, ldw, Ka, n_leaves, bytes(W), bytes(leaf panels), bytes(leaf Gt), n_nodes */
+/* out[0..9] = P, ldw, Ka, n_leaves, bytes(W), bytes(leaf panels), bytes(leaf Gt), n_nodes, p of mra_plan_set_trend (0: none),
+ * bytes(resident design matrix) */
 int mra_plan_info(mra_plan *plan, int64_t *out, int capacity);
 
 /* ---- native host tree replay (no GPU involved) -------------------------------------------------------

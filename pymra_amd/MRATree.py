@@ -123,8 +123,10 @@ def _check_noise(R, N):
 class MRATree(object):
 
     def __init__(self, locs, r, cov, obs, R, M=-1, J=-1, critDepth=-1, verbose=True, device=0,
-                 want_predict=True, cov_locs=None, metric="euclidean", radius=1.0):
-        """cov_locs: N x k (k <= 3) coordinates the covariance is evaluated on, when they are not ``locs``; ``locs`` still builds
+                 want_predict=True, cov_locs=None, metric="euclidean", radius=1.0, X=None):
+        """X: None, or (N, p) covariates of a regression trend y = X beta + x + eps with a flat prior on beta (p <= 63; an intercept
+        is a column of ones): see setTrend.
+        cov_locs: N x k (k <= 3) coordinates the covariance is evaluated on, when they are not ``locs``; ``locs`` still builds
         the tree.  metric="chordal": ``locs`` are (lon, lat) in degrees on a sphere of the given radius and the covariance sees
         their chordal distances (cov_locs = mt.lonlat_to_xyz(locs, radius)); the sites of predictAt and its siblings are (lon, lat)
         too.  Under an explicit cov_locs the sites are given in covariance coordinates (n x k)."""
@@ -209,6 +211,50 @@ class MRATree(object):
             mean, var, self._sd = None, None, None
         self.root = RootView(d, u, mean, var, N, self.topology, self.cov_locs, spec)
         self._node_blocks = {}
+        self.trend, self._X = None, None
+        if X is not None:
+            self.setTrend(X, want_predict=want_predict)
+
+    # ---- regression trend (HipPlan.set_trend / trend_fit) ----------------------------------------------------------------------------
+    def setTrend(self, X, want_predict=True):
+        """Set (X: (N, p) covariates in the caller's row order, kept on the device) or clear (None) a regression trend
+        y = X beta + x + eps with a flat prior on beta, fit it by generalised least squares from this tree's factors and return the
+        likelihood.  With a trend set, getLikelihood() is the profile -2 log-likelihood (reml=True: the REML criterion), predict() the
+        universal-kriging mean and sd (the uncertainty of beta included), ``trend`` the last TrendFit (beta, cov_beta, profile, reml,
+        ...), reevaluate(cov) refits it without sending X again, and predictAt needs X_sites."""
+        N = len(self.locs)
+        self._node_blocks = {}
+        if X is None:
+            self.plan.set_trend(None)
+            self.trend, self._X = None, None
+            self.plan.run(likelihood=True, predict=want_predict)
+            d, u = self.plan.likelihood()
+            mean, var, self._sd = self.plan.predict(with_sd=True) if want_predict else (None, None, None)
+            self.root = RootView(d, u, mean, var, N, self.topology, self.cov_locs, self.kernel)
+            return self.getLikelihood()
+        if self.kernel is None:
+            raise NotImplementedError("a trend needs a device kernel: trees built from an opaque callable or a dense matrix cannot fit one")
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2 or X.shape[0] != N or X.shape[1] < 1:
+            raise ValueError("X must have shape (N, p) with N = %d and p >= 1" % N)
+        if not np.all(np.isfinite(X)):
+            raise ValueError("X must be finite")
+        self.plan.set_trend(X)
+        self._X = X
+        self._fit_trend(want_predict)
+        return self.getLikelihood()
+
+    def _fit_trend(self, want_predict):
+        fit = self.plan.trend_fit(predict=want_predict)
+        self.trend = fit
+        self._sd = np.sqrt(fit.var) if want_predict else None
+        self.root = RootView(fit.d, fit.u, fit.mean, fit.var, len(self.locs), self.topology, self.cov_locs, self.kernel)
+
+    def _no_trend(self, what):
+        if self.trend is not None:
+            raise NotImplementedError("%s does not support a regression trend yet (this tree has one: setTrend(None) clears it)" % what)
 
     def _check_spec_metric(self, spec):
         """A kernel's metric A (``mt.Matern32(..., metric=A)``) lives in the covariance coordinates: cov_d x cov_d (3 x 3 on the xyz
@@ -231,7 +277,12 @@ class MRATree(object):
             self._obs_inds = np.where(np.logical_not(np.isnan(self.obs)))[0]
         return self._obs_inds
 
-    def getLikelihood(self):
+    def getLikelihood(self, reml=False):
+        """d + u of the last pass; with a trend the profile -2 log-likelihood, or with reml=True the REML criterion (+ log det X^T K^-1 X)."""
+        if self.trend is not None and reml:
+            return np.matrix([[self.trend.reml]])
+        if reml:
+            raise ValueError("reml=True needs a trend (setTrend)")
         return self.root.d + self.root.u
 
     def predict(self):
@@ -247,6 +298,7 @@ class MRATree(object):
         leaf are 0, as in predict().  seed=None takes a 64-bit seed from NumPy's global RNG (np.random.seed makes runs repeatable).
         The scalable counterpart of pyMRA's dense simulate1D / simulateGRF (pyMRA/MRATools.py:395-484); getLikelihood() and
         predict() are unchanged afterwards."""
+        self._no_trend("simulate")
         if distr not in ("prior", "posterior"):
             raise ValueError('distr must be "prior" or "posterior"')
         if self.kernel is None:
@@ -292,6 +344,7 @@ class MRATree(object):
         score = their sum, the CV log score; n rows scored; leverage_max = max v / R (float64 loses about eps / (1 - leverage)^2);
         dlik_dR = the exact derivative of getLikelihood() with respect to a nugget added to every observed row.  getLikelihood() and
         predict() are unchanged afterwards."""
+        self._no_trend("crossValidate")
         if kind not in ("loo", "leaf"):
             raise ValueError('kind must be "loo" or "leaf"')
         if self.kernel is None:
@@ -351,16 +404,39 @@ class MRATree(object):
         workers = min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
         return leaves[kd.query(np.mod(X, 1.0) if wrap else X, workers=workers)[1]].astype(np.int32)
 
-    def predictAt(self, sites, Y=None, leaf=None):
+    def predictAt(self, sites, Y=None, leaf=None, X_sites=None):
         """Posterior mean and standard deviation of the latent field at locations that need not be rows of `locs`, from this tree's
         factors - the tree (its knots, its likelihood) stays the one that was fitted.  sites: (n, d) - under metric="chordal" (n, 2)
         longitude / latitude in degrees, under an explicit cov_locs (n, k) in the covariance coordinates, here and in locate,
         covarianceAt, simulateAt and sampleAt; Y: None (this tree's observations) or (N,) / (N, c) observation vectors in the
         caller's row order on this tree's mask, as for solve(); leaf: None (locate(sites)) or int32[n] leaf node indices.  -> (mean (n, c), sd (n,)); add R to sd ** 2 for a new observation.  At a
-        location of the tree, in that location's leaf, these are predict()'s values.  getLikelihood() and predict() are unchanged."""
+        location of the tree, in that location's leaf, these are predict()'s values.  getLikelihood() and predict() are unchanged.
+        With a trend (setTrend) X_sites, the (n, p) covariates at the sites, is mandatory and Y must be None: the result is the
+        universal-kriging mean (n, 1) and sd (n,) for this tree's observations."""
         if self.kernel is None:
             raise NotImplementedError("predictAt needs a device kernel: trees built from an opaque callable or a dense matrix cannot predict at new sites")
-        return self._predict_at(self._sites(sites), Y, leaf)
+        if self.trend is None:
+            if X_sites is not None:
+                raise ValueError("X_sites given, but this tree has no trend (setTrend)")
+            return self._predict_at(self._sites(sites), Y, leaf)
+        S = self._sites(sites)
+        if X_sites is None:
+            raise ValueError("this tree has a trend: predictAt needs X_sites, the (n, p) covariates at the sites")
+        if Y is not None:
+            raise NotImplementedError("predictAt with a trend predicts from this tree's own observations (Y must be None)")
+        p = self._X.shape[1]
+        Xs = np.asarray(X_sites, dtype=np.float64)
+        if Xs.ndim == 1 and p == 1:
+            Xs = Xs.reshape(-1, 1)
+        if Xs.shape != (len(S), p) or not np.all(np.isfinite(Xs)):
+            raise ValueError("X_sites must be a finite array of shape (n, p) = (%d, %d)" % (len(S), p))
+        # zero-mean kriging of the columns [y | X] at the sites, then the formulas of the fit on the host
+        YX = np.column_stack([np.nan_to_num(np.asarray(self.obs, dtype=np.float64).reshape(-1)), self._X])
+        m, sd = self._predict_at(S, YX, leaf)
+        h = Xs - m[:, 1:]
+        mean = m[:, 0] + h @ self.trend.beta
+        var = sd ** 2 + np.einsum("ij,jk,ik->i", h, self.trend.cov_beta, h)
+        return mean.reshape(-1, 1), np.sqrt(var)
 
     def _predict_at(self, X, Y=None, leaf=None):
         if leaf is None:
@@ -407,6 +483,7 @@ class MRATree(object):
         """(n, nsim) draws of the latent field at locations that need not be rows of `locs`: mean + F z, with mean predictAt's for
         this tree's observations (0 for distr="prior"), F the symmetric square root of covarianceAt(sites, distr, leaf) (numpy.linalg.eigh,
         eigenvalues below 0 set to 0) and z (n, nsim) given, or standard normals from numpy.random.default_rng(seed)."""
+        self._no_trend("simulateAt")
         if self.kernel is None:
             raise NotImplementedError("simulateAt needs a device kernel: trees built from an opaque callable or a dense matrix cannot simulate at new sites")
         if distr not in ("prior", "posterior"):
@@ -437,6 +514,7 @@ class MRATree(object):
         (Philox draws on the device, a pure function of the seed) or (plan.sample_sites_slots(n), nsim) latent draws - the non-leaf
         nodes' slots first, shared with simulate(), then one per site.  leaf: None (locate(sites)) or int32[n] leaf node indices.
         getLikelihood() and predict() are unchanged."""
+        self._no_trend("sampleAt")
         if distr not in ("prior", "posterior"):
             raise ValueError('distr must be "prior" or "posterior"')
         if self.kernel is None:
@@ -542,6 +620,9 @@ class MRATree(object):
         self._check_spec_metric(spec)
         self._node_blocks = {}
         self._send_kernel(spec)
+        if self.trend is not None:           # the trend is refitted from the factors of the new kernel; X stays on the device
+            self._fit_trend(want_predict)
+            return self.getLikelihood()
         self.plan.run(likelihood=True, predict=want_predict)
         d, u = self.plan.likelihood()
         mean, var, self._sd = self.plan.predict(with_sd=True) if want_predict else (None, None, None)
@@ -558,6 +639,9 @@ class MRATree(object):
             self.plan.set_noise(np.full(len(self.locs), R))
         self.R = R
         self._node_blocks = {}
+        if self.trend is not None:
+            self._fit_trend(want_predict)
+            return self.getLikelihood()
         self.plan.run(likelihood=True, predict=want_predict)
         d, u = self.plan.likelihood()
         mean, var, self._sd = self.plan.predict(with_sd=True) if want_predict else (None, None, None)
@@ -571,6 +655,7 @@ class MRATree(object):
         pass of its own (MLE loops).  x0: the start; default the mean of the previous fit when there is one (a warm start), else the
         data-based start.  Updates ``root`` and ``predict()`` to the Laplace posterior N(x^, (Sigma^-1 + D)^-1), keeps the numbers
         of the fit in ``self.laplace`` and returns -2 log q(z); ``getLikelihood()`` keeps its meaning, d + u of the last pass."""
+        self._no_trend("fitLaplace")
         if cov is not None:
             spec = probe_cov(cov, self.cov_d, self.cov_locs)
             if spec is None:

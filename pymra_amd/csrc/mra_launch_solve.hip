@@ -101,7 +101,56 @@ void mra_solver_build(mra_plan* pl) {
     if (segs.empty()) segs.push_back(SolveSeg{nullptr, 0, 1});
     if (nl) S.leaves.upload(lv);
     S.segs.upload(segs);
+    // the archive of MRA_SOLVE_FULL_QUAD: a segment's first row in a block's panel; the panels go with the descriptors they mirror
+    std::vector<long> soff(segs.size());
+    S.arch_rows = 0;
+    for (size_t k = 0; k < segs.size(); ++k) { soff[k] = S.arch_rows; S.arch_rows += segs[k].n; }
+    S.seg_off.upload(soff);
+    S.arch.release(); S.cpart.release(); S.qfull.release(); S.arch_blocks = 0;
     S.built = true;
+}
+
+void mra_solver_archive(mra_plan* pl, int n_blocks) {
+    mra_plan::Solver& S = pl->slv;
+    if (n_blocks <= S.arch_blocks) return;
+    // (4 rows of slack: the masked tail of the last segment computes addresses past its rows, it does not read them)
+    S.arch.alloc((size_t)n_blocks * (size_t)std::max<long>(S.arch_rows, 1) * 16 + 64);
+    S.qfull.alloc((size_t)n_blocks * n_blocks * 256);
+    if (!S.cpart.n) S.cpart.alloc((size_t)6 * SOLVE_QUAD_BLOCKS * 256);
+    S.arch_blocks = n_blocks;
+}
+
+// The block pairs in groups of four panels: the blocks in twos, a group per pair of twos (I <= J) - its six pairs are the four between
+// the twos and the one inside each, wanted the first time that two is seen.  64 columns: one group, six pairs, every row read once.
+void mra_solver_quad_cross(mra_plan* pl, int n_blocks) {
+    mra_plan::Solver& S = pl->slv;
+    if (n_blocks < 2) return;
+    const int nseg = (int)S.segs.n, nb = std::min(SOLVE_QUAD_BLOCKS, std::max(nseg, 1)), ldq = 16 * S.arch_blocks;
+    const long panel = std::max<long>(S.arch_rows, 1) * 16;
+    const int n2 = (n_blocks + 1) / 2;
+    std::vector<char> seen((size_t)n2, 0);
+    auto blk = [&](int two, int k) { const int b = 2 * two + k; return b < n_blocks ? b : -1; };
+    auto group = [&](int I, int J) {      // J < 0: the one two of a call of two blocks
+        QuadGroup G{};
+        G.blk[0] = blk(I, 0); G.blk[1] = blk(I, 1); G.blk[2] = J < 0 ? -1 : blk(J, 0); G.blk[3] = J < 0 ? -1 : blk(J, 1);
+        static const int pa[6] = {0, 0, 0, 1, 1, 2}, pb[6] = {1, 2, 3, 2, 3, 3};
+        for (int p = 0; p < 6; ++p) G.out[p] = G.blk[pa[p]] >= 0 && G.blk[pb[p]] >= 0;
+        if (seen[(size_t)I]) G.out[0] = 0;
+        if (J >= 0 && seen[(size_t)J]) G.out[5] = 0;
+        seen[(size_t)I] = 1;
+        if (J >= 0) seen[(size_t)J] = 1;
+        hipLaunchKernelGGL(k_solve_quad_cross, dim3((unsigned)nb), dim3(256), 0, pl->stream, S.segs.p, S.seg_off.p, nseg, S.arch.p, panel, G, S.cpart.p);
+        hipLaunchKernelGGL(k_solve_quad_cross_sum, dim3(6), dim3(256), 0, pl->stream, S.cpart.p, nb, G, S.qfull.p, ldq);
+    };
+    if (n2 == 1) { group(0, -1); return; }
+    for (int I = 0; I < n2; ++I)
+        for (int J = I + 1; J < n2; ++J) group(I, J);
+}
+
+void mra_trend_rows(mra_plan* pl) {
+    mra_plan::Trend& T = pl->trend;
+    hipLaunchKernelGGL(k_trend_rows, dim3((unsigned)((pl->P + 63) / 64)), dim3(64), 0, pl->stream, T.m.p, T.X.p, T.coef.p, T.coef.p + MRA_TREND_LD,
+                       T.var_pass.p, pl->maps.rep.p, T.p, pl->P, T.mean.p, T.var.p);
 }
 
 template <int DIM>
@@ -119,7 +168,7 @@ static void launch_rows(mra_plan* pl) {
 #undef MRA_SOLVE_ROWS
 }
 
-void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad, bool want_rows) {
+void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad, bool want_rows, int archive) {
     mra_plan::Solver& S = pl->slv;
     const unsigned nl = (unsigned)pl->leaf_nodes.size();
     if (pl->d < 1 || pl->d > 3) throw MraError(MRA_ERR_INVALID, "mra_solve: 1-, 2- or 3-D locations only");
@@ -133,7 +182,12 @@ void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad, bool want_ro
         const unsigned n = (unsigned)(S.lev_off[m + 1] - S.lev_off[m]);
         if (n) hipLaunchKernelGGL(k_solve_front_fwd, dim3(n), dim3(256), S.lev_lds[m], pl->stream, S.fronts.p + S.lev_off[m], S.kids.p);
     }
-    // 3. quadratic form (the z of the fronts are overwritten by the backward sweep)
+    // 3. quadratic form (the z of the fronts are overwritten by the backward sweep); the same vectors into the block's panel
+    if (archive >= 0) {
+        const int nseg = (int)S.segs.n;
+        hipLaunchKernelGGL(k_solve_archive, dim3((unsigned)std::min(std::max(nseg, 1), 65535)), dim3(256), 0, pl->stream, S.segs.p, S.seg_off.p, nseg,
+                           S.arch.p + (size_t)archive * (size_t)std::max<long>(S.arch_rows, 1) * 16);
+    }
     if (want_quad) {
         const int nseg = (int)S.segs.n;
         const int nb = std::min(SOLVE_QUAD_BLOCKS, std::max(nseg, 1));

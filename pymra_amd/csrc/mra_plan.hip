@@ -2739,9 +2739,11 @@ static void ensure_factors(mra_plan* pl) {
         return;
     }
     KeepResults keep(pl, nullptr, S.msave.p, S.vsave.p);
+    pl->trend.var_valid = false;         // mra_trend_fit's copy of the predictive variance belonged to the factors that stood
     sampler_prior(pl);
     HIP_TRY(hipStreamSynchronize(pl->stream));
     HIP_TRY(hipGetLastError());
+    S.pass_d = pl->res_d;
     S.valid = true;
 }
 
@@ -2851,9 +2853,24 @@ static void sample_all(mra_plan* pl, uint32_t flags, int64_t n, uint64_t seed, i
 }
 
 // ---- solver (mra_solve) ------------------------------------------------------------------------------------
+// the tiles between the nblk archived blocks, from slv.qfull into the n x n host matrix (the tiles on its diagonal are not touched)
+static void fetch_cross_tiles(mra_plan* pl, int nblk, int64_t n, double* quad) {
+    mra_plan::Solver& S = pl->slv;
+    const int ldq = 16 * S.arch_blocks;
+    std::vector<double> q((size_t)nblk * 16 * ldq);
+    HIP_TRY(hipMemcpyAsync(q.data(), S.qfull.p, q.size() * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
+    HIP_TRY(hipStreamSynchronize(pl->stream));
+    HIP_TRY(hipGetLastError());
+    for (int64_t i = 0; i < n; ++i)
+        for (int64_t j = 0; j < n; ++j)
+            if (i / 16 != j / 16) quad[i * n + j] = q[(size_t)i * ldq + j];
+}
+
 static void solve_all(mra_plan* pl, uint32_t flags, int64_t n, const double* Y, double* mean, double* quad) {
-    retained_check_plan(pl, "mra_solve", flags, 0, "cannot solve (C(S, o) is evaluated on the device)", "cannot solve");
+    retained_check_plan(pl, "mra_solve", flags, MRA_SOLVE_FULL_QUAD, "cannot solve (C(S, o) is evaluated on the device)", "cannot solve");
     if (n < 0) throw MraError(MRA_ERR_INVALID, "n_cols < 0");
+    const bool full = (flags & MRA_SOLVE_FULL_QUAD) != 0;
+    if (full && n > MRA_FULL_QUAD_MAX) throw MraError(MRA_ERR_INVALID, "mra_solve: MRA_SOLVE_FULL_QUAD takes at most MRA_FULL_QUAD_MAX = 256 columns");
     if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
     if (n == 0) return;
     if (!Y) throw MraError(MRA_ERR_INVALID, "Y is NULL");
@@ -2862,7 +2879,174 @@ static void solve_all(mra_plan* pl, uint32_t flags, int64_t n, const double* Y, 
     mra_solver_build(pl);
     ensure_factors(pl);
     mra_plan::Solver& S = pl->slv;
-    column_blocks(pl, n, Y, S.yb.p, mean, S.out.p, quad, S.quad.p, [&] { mra_solver_block(pl, mean != nullptr, quad != nullptr); });
+    const int nblk = (int)((n + 15) / 16);
+    const bool cross = full && quad && nblk > 1;      // one block: the flagless call already returns the whole matrix
+    if (cross) mra_solver_archive(pl, nblk);
+    int b = 0;
+    column_blocks(pl, n, Y, S.yb.p, mean, S.out.p, quad, S.quad.p, [&] { mra_solver_block(pl, mean != nullptr, quad != nullptr, true, cross ? b++ : -1); });
+    if (!cross) return;
+    mra_solver_quad_cross(pl, nblk);
+    fetch_cross_tiles(pl, nblk, n, quad);
+}
+
+// ---- regression trend (mra_plan_set_trend / mra_trend_fit) -----------------------------------------------------
+// X: p x P by padded row (phantom rows 0).  Every value is checked before anything changes; nothing but the trend changes.
+static void set_trend(mra_plan* pl, int32_t p, const double* X) {
+    const long P = pl->P;
+    if (p < 0) throw MraError(MRA_ERR_INVALID, "mra_plan_set_trend: p < 0");
+    if (p > MRA_TREND_MAX) throw MraError(MRA_ERR_INVALID, "mra_plan_set_trend: p > MRA_TREND_MAX = 63 ([y | X] is at most 64 columns)");
+    if (p > 0 && !X) throw MraError(MRA_ERR_INVALID, "mra_plan_set_trend: X is NULL with p > 0");
+    if (p > 0 && X) {
+        std::atomic<long> bad{-1};
+        parallel_rows((int64_t)p * P, [&](int64_t a, int64_t b) {
+            for (int64_t e = a; e < b; ++e)
+                if (!std::isfinite(X[e])) { bad = (long)e; return; }
+        });
+        if (bad >= 0) {
+            char m[160];
+            const long e = bad;
+            snprintf(m, sizeof m, "mra_plan_set_trend: X is not finite (column %ld, padded row %ld)", e / P, e % P);
+            throw MraError(MRA_ERR_INVALID, m);
+        }
+    }
+    mra_plan::Trend& T = pl->trend;
+    if (p == 0 || !X) {
+        T.p = 0;
+        T.X.release(); T.m.release();
+        return;
+    }
+    HIP_TRY(mraSetDevice(pl->device));
+    if (T.X.n != (size_t)p * P) T.X.alloc((size_t)p * P);
+    HIP_TRY(mraMemcpy(T.X.p, X, (size_t)p * P * sizeof(double), hipMemcpyHostToDevice));
+    if (T.p != p) T.m.release();
+    T.p = p;
+}
+
+static void trend_fit(mra_plan* pl, uint32_t flags, double* beta, double* cov_beta, double* mean, double* var, double* info) {
+    retained_check_plan(pl, "mra_trend_fit", flags, MRA_TREND_PREDICT, "cannot fit a trend (C(S, o) is evaluated on the device)", "cannot fit a trend");
+    mra_plan::Trend& T = pl->trend;
+    if (T.p == 0) throw MraError(MRA_ERR_STATE, "mra_trend_fit needs mra_plan_set_trend first");
+    if (!beta || !info) throw MraError(MRA_ERR_INVALID, "mra_trend_fit: beta or info is NULL");
+    const bool pred = (flags & MRA_TREND_PREDICT) != 0;
+    if (!pred && (mean || var)) throw MraError(MRA_ERR_INVALID, "mra_trend_fit: mean_perm or var_perm given without MRA_TREND_PREDICT");
+    if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
+    const long P = pl->P;
+    const int p = T.p, n = p + 1, nblk = (n + 15) / 16;
+    HIP_TRY(mraSetDevice(pl->device));
+    mra_solver_build(pl);
+    mra_plan::Solver& S = pl->slv;
+    if (pred) {
+        if (T.m.n != (size_t)n * P) T.m.alloc((size_t)n * P);
+        if (T.var_pass.n != (size_t)P) { T.var_pass.alloc((size_t)P); T.mean.alloc((size_t)P); T.var.alloc((size_t)P); T.var_valid = false; }
+        if (!T.coef.n) T.coef.alloc((size_t)MRA_TREND_MAX + 1 + (size_t)(MRA_TREND_MAX + 1) * (MRA_TREND_MAX + 1));
+        if (!(S.valid && T.var_valid)) {
+            // the variance of a predict pass on the plan's own y; that pass rewrites W, so the factors are made again behind it
+            {
+                KeepResults keep(pl, nullptr, S.msave.p, S.vsave.p);
+                run_all(pl, MRA_RUN_LIKELIHOOD | MRA_RUN_PREDICT);
+                HIP_TRY(hipMemcpyAsync(T.var_pass.p, pl->var.p, (size_t)P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+            }
+            S.valid = false;
+            ensure_factors(pl);
+            T.var_valid = true;
+        } else ensure_factors(pl);
+    } else ensure_factors(pl);
+    // G = [y | X]^T K^-1 [y | X], block by block from the device's own y and X (timed as the site calls are, into trend.ms)
+    for (double& v : T.ms) v = 0.0;
+    for (size_t t = 0; t < pl->leaf_nodes.size(); ++t)
+        T.ms[5] += 8.0 * (double)(pl->Ka - pl->asuf[pl->node_level[pl->leaf_nodes[t]]]) * (double)pl->leaf_nop[t];
+    T.ms[6] = 8.0 * 16.0 * (double)S.arch_rows;
+    struct Sink { mra_plan::Sites& s; Sink(mra_plan::Sites& t, double* ms) : s(t) { s.ms_sink = ms; } ~Sink() { s.ms_sink = nullptr; } } sink(pl->sit, T.ms);
+    if (nblk > 1) mra_solver_archive(pl, nblk);
+    std::vector<double> G((size_t)n * n, 0.0);
+    for (int b = 0; b < nblk; ++b) {
+        const int c0 = 16 * b, nc = std::min(16, n - c0);
+        mra_sites_timed(pl, 0, [&] {
+            if (b == 0) {
+                HIP_TRY(hipMemcpyAsync(S.yb.p, pl->y.p, (size_t)P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+                if (nc > 1) HIP_TRY(hipMemcpyAsync(S.yb.p + P, T.X.p, (size_t)(nc - 1) * P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+            } else HIP_TRY(hipMemcpyAsync(S.yb.p, T.X.p + (size_t)(c0 - 1) * P, (size_t)nc * P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+            if (nc < 16) HIP_TRY(hipMemsetAsync(S.yb.p + (size_t)nc * P, 0, (size_t)(16 - nc) * P * sizeof(double), pl->stream));
+        });
+        mra_sites_timed(pl, 1, [&] { mra_solver_block(pl, pred, true, true, nblk > 1 ? b : -1); });
+        if (pred)
+            mra_sites_timed(pl, 0, [&] {
+                HIP_TRY(hipMemcpyAsync(T.m.p + (size_t)c0 * P, S.out.p, (size_t)nc * P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+            });
+        double tb[256];
+        mra_sites_timed(pl, 4, [&] { HIP_TRY(hipMemcpyAsync(tb, S.quad.p, sizeof tb, hipMemcpyDeviceToHost, pl->stream)); });
+        HIP_TRY(hipStreamSynchronize(pl->stream));
+        HIP_TRY(hipGetLastError());
+        for (int i = 0; i < nc; ++i)
+            for (int j = 0; j < nc; ++j) G[(size_t)(c0 + i) * n + c0 + j] = tb[i * 16 + j];
+    }
+    if (nblk > 1) {
+        mra_sites_timed(pl, 2, [&] { mra_solver_quad_cross(pl, nblk); });
+        mra_sites_timed(pl, 4, [&] { fetch_cross_tiles(pl, nblk, n, G.data()); });
+    }
+    // A = L L^T on the host (at most 63 x 63); Li = L^-1
+    constexpr int LD = MRA_TREND_MAX + 1;
+    std::vector<double> L((size_t)p * p, 0.0), Li((size_t)LD * LD, 0.0), bt((size_t)LD, 0.0);
+    double dmax = 0.0, pmin = INFINITY, pmax = 0.0, logdet = 0.0;
+    for (int i = 0; i < p; ++i) dmax = std::max(dmax, G[(size_t)(i + 1) * n + i + 1]);
+    const double floor_ = (double)p * 2.220446049250313e-16 * dmax;
+    for (int j = 0; j < p; ++j) {
+        double piv = G[(size_t)(j + 1) * n + j + 1];
+        for (int k = 0; k < j; ++k) piv -= L[(size_t)j * p + k] * L[(size_t)j * p + k];
+        if (!(piv > 0.0) || !(piv >= floor_) || !std::isfinite(piv))
+            throw MraError(MRA_ERR_NOT_SPD, "mra_trend_fit: trend columns are linearly dependent at the observed rows");
+        const double ljj = std::sqrt(piv);
+        L[(size_t)j * p + j] = ljj;
+        pmin = std::min(pmin, piv); pmax = std::max(pmax, piv); logdet += std::log(piv);
+        for (int i = j + 1; i < p; ++i) {
+            double v = G[(size_t)(i + 1) * n + j + 1];
+            for (int k = 0; k < j; ++k) v -= L[(size_t)i * p + k] * L[(size_t)j * p + k];
+            L[(size_t)i * p + j] = v / ljj;
+        }
+    }
+    for (int c = 0; c < p; ++c)              // L Li = I, column by column
+        for (int i = c; i < p; ++i) {
+            double v = i == c ? 1.0 : 0.0;
+            for (int k = c; k < i; ++k) v -= L[(size_t)i * p + k] * Li[(size_t)k * LD + c];
+            Li[(size_t)i * LD + c] = v / L[(size_t)i * p + i];
+        }
+    std::vector<double> wv((size_t)p, 0.0);  // w = L^-1 b; beta = L^-T w
+    for (int i = 0; i < p; ++i) {
+        double v = 0.0;
+        for (int k = 0; k <= i; ++k) v += Li[(size_t)i * LD + k] * G[(size_t)(k + 1) * n];
+        wv[i] = v;
+    }
+    for (int i = 0; i < p; ++i) {
+        double v = 0.0;
+        for (int k = i; k < p; ++k) v += Li[(size_t)k * LD + i] * wv[k];
+        beta[i] = v; bt[i] = v;
+    }
+    if (cov_beta)
+        for (int i = 0; i < p; ++i)
+            for (int j = 0; j < p; ++j) {
+                double v = 0.0;
+                for (int k = std::max(i, j); k < p; ++k) v += Li[(size_t)k * LD + i] * Li[(size_t)k * LD + j];
+                cov_beta[(size_t)i * p + j] = v;
+            }
+    long nobs = 0;
+    for (size_t t = 0; t < pl->leaf_nodes.size(); ++t)
+        for (long r = pl->row0[pl->leaf_nodes[t]]; r < pl->row1[pl->leaf_nodes[t]]; ++r) nobs += pl->y_finite_host[r] ? 1 : 0;
+    double bb = 0.0;
+    for (int i = 0; i < p; ++i) bb += G[(size_t)(i + 1) * n] * beta[i];
+    info[0] = S.pass_d; info[1] = G[0] - bb; info[2] = logdet; info[3] = info[0] + info[1]; info[4] = info[3] + info[2];
+    info[5] = (double)nobs; info[6] = (double)p; info[7] = pmin / pmax;
+    if (!pred) return;
+    mra_sites_timed(pl, 4, [&] {
+        HIP_TRY(hipMemcpyAsync(T.coef.p, bt.data(), (size_t)LD * sizeof(double), hipMemcpyHostToDevice, pl->stream));
+        HIP_TRY(hipMemcpyAsync(T.coef.p + LD, Li.data(), (size_t)LD * LD * sizeof(double), hipMemcpyHostToDevice, pl->stream));
+    });
+    mra_sites_timed(pl, 3, [&] { mra_trend_rows(pl); });
+    mra_sites_timed(pl, 4, [&] {
+        if (mean) HIP_TRY(hipMemcpyAsync(mean, T.mean.p, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
+        if (var) HIP_TRY(hipMemcpyAsync(var, T.var.p, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
+    });
+    HIP_TRY(hipStreamSynchronize(pl->stream));
+    HIP_TRY(hipGetLastError());
 }
 
 // ---- covariance operator (mra_cov_apply) ------------------------------------------------------------------
@@ -4250,6 +4434,12 @@ int mra_sample(mra_plan* pl, uint32_t flags, int64_t n_samples, uint64_t seed, i
 int mra_solve(mra_plan* pl, uint32_t flags, int64_t n_cols, const double* Y, double* mean, double* quad) {
     return guarded(pl, [&] { require(pl, "mra_solve: plan is NULL"); solve_all(pl, flags, n_cols, Y, mean, quad); return MRA_OK; });
 }
+int mra_plan_set_trend(mra_plan* pl, int32_t p, const double* X_perm) {
+    return guarded(pl, [&] { require(pl, "mra_plan_set_trend: plan is NULL"); set_trend(pl, p, X_perm); return MRA_OK; });
+}
+int mra_trend_fit(mra_plan* pl, uint32_t flags, double* beta, double* cov_beta, double* mean_perm, double* var_perm, double* info) {
+    return guarded(pl, [&] { require(pl, "mra_trend_fit: plan is NULL"); trend_fit(pl, flags, beta, cov_beta, mean_perm, var_perm, info); return MRA_OK; });
+}
 int mra_cov_apply(mra_plan* pl, uint32_t flags, int64_t n_cols, const double* A, double* out, double* gram) {
     return guarded(pl, [&] { require(pl, "mra_cov_apply: plan is NULL"); cov_all(pl, flags, n_cols, A, out, gram); return MRA_OK; });
 }
@@ -4321,6 +4511,11 @@ int mra_get_buffer(mra_plan* pl, int what, double* out, int64_t cap, int64_t* n_
         if (what == 12) {            // host record: stream ms of the last mra_cv
             *n_avail = 9;
             if (out && cap > 0) memcpy(out, pl->sit.cv_ms, (size_t)std::min<int64_t>(cap, 9) * sizeof(double));
+            return MRA_OK;
+        }
+        if (what == 14) {            // host record: stream ms of the last mra_trend_fit
+            *n_avail = 7;
+            if (out && cap > 0) memcpy(out, pl->trend.ms, (size_t)std::min<int64_t>(cap, 7) * sizeof(double));
             return MRA_OK;
         }
         if (what == 10) {            // host record: the noise variance by padded row (the scalar R everywhere when no vector is set)
@@ -4580,9 +4775,9 @@ int mra_get_route(mra_plan* pl, int32_t* out, int cap) {
 
 int mra_plan_info(mra_plan* pl, int64_t* out, int cap) {
     if (!pl || !out) return 0;
-    int64_t v[8] = {pl->P, pl->ldw, pl->Ka, (int64_t)pl->leaf_nodes.size(), (int64_t)pl->W.n * 8,
-                    (int64_t)pl->panel.n * 8, (int64_t)pl->Gt.n * 8, pl->n_nodes};
-    int n = std::min(cap, 8);
+    int64_t v[10] = {pl->P, pl->ldw, pl->Ka, (int64_t)pl->leaf_nodes.size(), (int64_t)pl->W.n * 8,
+                     (int64_t)pl->panel.n * 8, (int64_t)pl->Gt.n * 8, pl->n_nodes, pl->trend.p, (int64_t)pl->trend.X.n * 8};
+    int n = std::min(cap, 10);
     for (int k = 0; k < n; ++k) out[k] = v[k];
     return n;
 }

@@ -641,7 +641,29 @@ struct mra_plan {
         DevVec<SolveSeg> segs;
         DevVec<double> yb, out, uy, nb, qpart, quad, msave, vsave;      // 16 x P in / out blocks; U_y / s / q; node buffers; Q
         size_t work_bytes = 0;
+        double pass_d = 0.0;                      // log-determinant of the pass that set `valid` (it does not depend on y)
+        // MRA_SOLVE_FULL_QUAD (and mra_trend_fit): the forward vectors of every 16-column block of a call, one panel of arch_rows x16
+        // per block (segment k of segs at row seg_off[k]), the partial sums of one group of block pairs and the dense matrix.  Allocated
+        // by flagged calls only (grow-only in the number of blocks); released when the descriptors are rebuilt.
+        long arch_rows = 0;
+        int arch_blocks = 0;                      // panels the archive holds
+        DevVec<long> seg_off;
+        DevVec<double> arch, cpart, qfull;        // qfull: (16 blocks) x (16 blocks) doubles, row stride 16 * arch_blocks
     } slv;
+    // regression trend (mra_plan_set_trend / mra_trend_fit): the design matrix by padded row, resident on the
+    // device; a property of the plan like the noise vector (no set_* drops it, it enters no factorisation).  The rest is allocated by
+    // the first predicting fit: the kriging means of [y | X], the variance of a predict pass on the plan's y (var_valid: it belongs to
+    // the factors that stand - cleared whenever ensure_factors runs a pass), beta and L^-1 for k_trend_rows, its results.
+    struct Trend {
+        int p = 0;
+        DevVec<double> X;                         // p x P
+        DevVec<double> m, var_pass, coef, mean, var;      // (1 + p) x P; P; 64 (beta) + 64 x 64 (L^-1); P; P
+        bool var_valid = false;
+        // stream ms of the last mra_trend_fit with MRA_OPT_KERNEL_TIMING: staging, sweeps, cross quad, rows, transfers; then what the
+        // sweeps of one block move: bytes of the leaves' Ut (read once by the forward sweep, twice more by the backward one) and of
+        // the block's archive panel (written once, read once)
+        double ms[7] = {0, 0, 0, 0, 0, 0, 0};
+    } trend;
     // covariance operator (mra_cov_apply): reads W of the pass mra_solve keeps (slv.valid), the plan's row maps (maps), the solver's
     // level offsets and, for the posterior, its sweeps.  Its node buffers are its own, laid out by mra_node_layout as the solver's are.
     // Built on the first call and again whenever the solver's descriptors are.
@@ -767,7 +789,15 @@ NodeLayout mra_node_layout(mra_plan* pl, int leaf_blocks, bool with_F, DevVec<do
 // mra_launch_solve.hip: descriptors + work buffers of mra_solve; one block of <= 16 columns (slv.yb -> slv.out, slv.quad; launches
 // only, on pl->stream); the 16-column glue of the sampler's MRA_OPT_SAMPLE_SOLVE path
 void mra_solver_build(mra_plan* pl);
-void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad, bool want_rows = true);      // want_rows false: stop before step 6 (beta and q stay in the leaves' gb / uy)
+// archive >= 0: the block's forward vectors are copied into that panel of the archive behind the forward sweep (after mra_solver_archive)
+void mra_solver_block(mra_plan* pl, bool want_mean, bool want_quad, bool want_rows = true, int archive = -1);      // want_rows false: stop before step 6 (beta and q stay in the leaves' gb / uy)
+// MRA_SOLVE_FULL_QUAD: room for n_blocks panels; the tiles between the n_blocks archived blocks into slv.qfull (row stride
+// 16 * slv.arch_blocks; tiles on the diagonal are not written), launches only
+constexpr int MRA_FULL_QUAD_BLOCKS = 16;
+void mra_solver_archive(mra_plan* pl, int n_blocks);
+void mra_solver_quad_cross(mra_plan* pl, int n_blocks);
+// mra_trend_fit: trend.mean / trend.var from trend.m, trend.X, trend.coef and trend.var_pass (k_trend_rows), launch only
+void mra_trend_rows(mra_plan* pl);
 void mra_solver_pseudo(mra_plan* pl, const double* y, const double* x, const SampleZ& zs, long slot0);
 void mra_solver_addmean(mra_plan* pl, double* x, int ns);
 // mra_launch_cov.hip: descriptors + work buffers of mra_cov_apply; one block of <= 16 columns (cov.ab -> cov.out, cov.gram; launches

@@ -205,6 +205,135 @@ __global__ __launch_bounds__(256) void k_solve_quad_sum(const double* __restrict
     quad[threadIdx.x] = acc;
 }
 
+// ---- full quadratic form (MRA_SOLVE_FULL_QUAD): the entries between columns of different 16-column blocks ------------------------
+// The forward vectors of a block (every segment's n x16 rows: the leaves' U_y, the fronts' z) are copied into the block's panel of the
+// archive behind its forward sweep, segment sgi at row seg_off[sgi]; one workgroup per segment, the tail of the grid strides on.
+__global__ __launch_bounds__(256) void k_solve_archive(const SolveSeg* __restrict__ segs, const long* __restrict__ seg_off, int nseg,
+                                                       double* __restrict__ panel) {
+    for (int sgi = blockIdx.x; sgi < nseg; sgi += gridDim.x) {
+        const SolveSeg S = segs[sgi];
+        double* dst = panel + seg_off[sgi] * 16;
+        for (int e = threadIdx.x; e < S.n * 16; e += 256) gst(dst + e, gld(S.p + e));
+    }
+}
+
+// Q_ab = sum over segments of sign * F_a^T F_b for the block pairs of one group: four panels u < v of the archive, their six pairs
+// (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) accumulated side by side so that a row of the archive is read once per launch.  blk[u] < 0: the
+// slot is empty (its rows are not read); out[p]: whether pair p is wanted (a pair of an earlier group, or one with an empty slot, is not).
+struct QuadGroup { int blk[4]; int out[6]; };
+// The A operand of v_mfma_f64_16x16x4_f64 is four rows of panel a, transposed, the B operand the same four rows of panel b: lane
+// (i, kk) = (lane & 15, lane >> 4) loads F[k0 + kk][i] of either - a wave's load is 4 rows x 16 doubles, 512 contiguous bytes - and
+// acc[j] is Q_ab[kk + 4 j][i].  The sign goes onto the A operand (exact).  Rows past a segment's n are not read (a masked tail: the
+// operands of those lanes are 0).  The segments are dealt to the workgroups as k_solve_quad_part deals them, a segment's 4-row chunks
+// to the workgroup's four waves in turn; the waves' sums are added in wave order, so part holds gridDim.x partial sums per pair:
+// part[(p * gridDim.x + block) * 256 + i * 16 + j].  No atomics: the same inputs give the same bits.
+__global__ __launch_bounds__(256, 2) void k_solve_quad_cross(const SolveSeg* __restrict__ segs, const long* __restrict__ seg_off, int nseg,
+                                                             const double* __restrict__ arch, long panel, QuadGroup G,
+                                                             double* __restrict__ part) {
+    __shared__ double red[4 * 256];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, kk = lane >> 4;
+    const bool on0 = G.blk[0] >= 0, on1 = G.blk[1] >= 0, on2 = G.blk[2] >= 0, on3 = G.blk[3] >= 0;
+    const double* p0 = arch + (long)(on0 ? G.blk[0] : 0) * panel + lane;
+    const double* p1 = arch + (long)(on1 ? G.blk[1] : 0) * panel + lane;
+    const double* p2 = arch + (long)(on2 ? G.blk[2] : 0) * panel + lane;
+    const double* p3 = arch + (long)(on3 ? G.blk[3] : 0) * panel + lane;
+    d4 a01 = {0, 0, 0, 0}, a02 = a01, a03 = a01, a12 = a01, a13 = a01, a23 = a01;
+    // one chunk: the four panels' loads first, then the six products
+#define MRA_QUAD_CROSS_CHUNK(K0)                                                                                                     \
+    {                                                                                                                                \
+        const bool in = (K0) + kk < n;                                                                                               \
+        const long e = off + (long)(K0) * 16;                                                                                        \
+        const double v0 = (in && on0) ? gld(p0 + e) : 0.0;                                                                           \
+        const double v1 = (in && on1) ? gld(p1 + e) : 0.0;                                                                           \
+        const double v2 = (in && on2) ? gld(p2 + e) : 0.0;                                                                           \
+        const double v3 = (in && on3) ? gld(p3 + e) : 0.0;                                                                           \
+        const double s0 = sg * v0, s1 = sg * v1, s2 = sg * v2;                                                                       \
+        a01 = mfma16(s0, v1, a01); a02 = mfma16(s0, v2, a02); a03 = mfma16(s0, v3, a03);                                             \
+        a12 = mfma16(s1, v2, a12); a13 = mfma16(s1, v3, a13); a23 = mfma16(s2, v3, a23);                                             \
+    }
+    // A leaf's segment is a few chunks per wave, so a wave meets a new descriptor every few loads: the next segment's is read while
+    // this one's rows are on their way (measured neutral at c3 and c5, DESIGN.md section 20: the wait is for the rows).
+    int sgi = blockIdx.x;
+    int n = 0, sign = 1;
+    long off = 0;
+    if (sgi < nseg) { n = segs[sgi].n; sign = segs[sgi].sign; off = seg_off[sgi] * 16; }
+    while (sgi < nseg) {
+        const int nxt = sgi + gridDim.x;
+        int n_nxt = 0, sign_nxt = 1;
+        long off_nxt = 0;
+        if (nxt < nseg) { n_nxt = segs[nxt].n; sign_nxt = segs[nxt].sign; off_nxt = seg_off[nxt] * 16; }
+        const double sg = (double)sign;
+#pragma unroll 2
+        for (int k0 = 4 * w; k0 < n; k0 += 16) MRA_QUAD_CROSS_CHUNK(k0)
+        sgi = nxt; n = n_nxt; sign = sign_nxt; off = off_nxt;
+    }
+#undef MRA_QUAD_CROSS_CHUNK
+    const int i = lane & 15;
+#define MRA_QUAD_CROSS_FOLD(P, ACC)                                                                                                  \
+    if (G.out[P]) {                                                                                                                  \
+        _Pragma("unroll") for (int j = 0; j < 4; ++j) red[w * 256 + (kk + 4 * j) * 16 + i] = ACC[j];                                 \
+        __syncthreads();                                                                                                             \
+        part[((long)(P) * gridDim.x + blockIdx.x) * 256 + threadIdx.x] =                                                             \
+            ((red[threadIdx.x] + red[256 + threadIdx.x]) + red[512 + threadIdx.x]) + red[768 + threadIdx.x];                         \
+        __syncthreads();                                                                                                             \
+    }
+    MRA_QUAD_CROSS_FOLD(0, a01) MRA_QUAD_CROSS_FOLD(1, a02) MRA_QUAD_CROSS_FOLD(2, a03)
+    MRA_QUAD_CROSS_FOLD(3, a12) MRA_QUAD_CROSS_FOLD(4, a13) MRA_QUAD_CROSS_FOLD(5, a23)
+#undef MRA_QUAD_CROSS_FOLD
+}
+// The partial sums of a group's pairs folded in block order, one workgroup per pair; the tile of pair (a, b) and its mirror go into the
+// dense ldq x ldq matrix Q (tiles on the diagonal are not touched: k_solve_quad_part / k_solve_quad_sum own them).
+__global__ __launch_bounds__(256) void k_solve_quad_cross_sum(const double* __restrict__ part, int nblk, QuadGroup G, double* __restrict__ Q,
+                                                              int ldq) {
+    int a = -1, b = -1, want = 0;
+    if (blockIdx.x == 0) { a = G.blk[0]; b = G.blk[1]; want = G.out[0]; }
+    if (blockIdx.x == 1) { a = G.blk[0]; b = G.blk[2]; want = G.out[1]; }
+    if (blockIdx.x == 2) { a = G.blk[0]; b = G.blk[3]; want = G.out[2]; }
+    if (blockIdx.x == 3) { a = G.blk[1]; b = G.blk[2]; want = G.out[3]; }
+    if (blockIdx.x == 4) { a = G.blk[1]; b = G.blk[3]; want = G.out[4]; }
+    if (blockIdx.x == 5) { a = G.blk[2]; b = G.blk[3]; want = G.out[5]; }
+    if (!want) return;
+    double acc = 0.0;
+    for (int k = 0; k < nblk; ++k) acc += part[((long)blockIdx.x * nblk + k) * 256 + threadIdx.x];
+    const int i = threadIdx.x >> 4, j = threadIdx.x & 15;
+    Q[(long)(a * 16 + i) * ldq + b * 16 + j] = acc;
+    Q[(long)(b * 16 + j) * ldq + a * 16 + i] = acc;
+}
+
+// ---- trend (mra_trend_fit): universal-kriging mean and variance by padded row ------------------------------
+// m: (1 + p) x P kriging means of [y | X] (row 0: m_y), X: p x P design matrix, both by padded row.  h = x(s) - m_X(s);
+// mean = m_y + h^T beta, var = var_pass + |L^-1 h|^2 with A = L L^T = X^T K^-1 X.  One row per lane, one wave per workgroup: L^-1
+// (64 x 64 doubles, row stride 64) and the lanes' h (hs[j * 64 + lane]: no bank conflicts) in LDS.  Unreported rows get exactly 0.
+#define MRA_TREND_LD 64
+__global__ __launch_bounds__(64) void k_trend_rows(const double* __restrict__ m, const double* __restrict__ X, const double* __restrict__ beta,
+                                                   const double* __restrict__ Linv, const double* __restrict__ var_pass,
+                                                   const unsigned char* __restrict__ rep, int p, long P, double* __restrict__ mean,
+                                                   double* __restrict__ var) {
+    __shared__ double Ls[MRA_TREND_LD * MRA_TREND_LD];
+    __shared__ double hs[(MRA_TREND_LD - 1) * 64];
+    const int lane = threadIdx.x;
+    for (int e = lane; e < p * MRA_TREND_LD; e += 64) Ls[e] = Linv[e];
+    const long s = (long)blockIdx.x * 64 + lane;
+    const bool in = s < P;
+    double mu = in ? m[s] : 0.0;
+    for (int j = 0; j < p; ++j) {
+        const double h = in ? X[(long)j * P + s] - m[(long)(j + 1) * P + s] : 0.0;
+        hs[j * 64 + lane] = h;
+        mu = __builtin_fma(h, beta[j], mu);
+    }
+    __syncthreads();
+    double add = 0.0;
+    for (int i = 0; i < p; ++i) {
+        double wi = 0.0;
+        for (int j = 0; j <= i; ++j) wi = __builtin_fma(Ls[i * MRA_TREND_LD + j], hs[j * 64 + lane], wi);
+        add = __builtin_fma(wi, wi, add);
+    }
+    if (!in) return;
+    const bool r = rep[s] != 0;
+    mean[s] = r ? mu : 0.0;
+    var[s] = r ? var_pass[s] + add : 0.0;
+}
+
 // ---- rows: mean[tile, 0:16] = W[tile, anc] beta + C(tile, obs) q, one wave per 16-row tile ---------------------------------------
 // The covariance is evaluated on the fly as the A operand (lane (r, q) evaluates C(x_row r, x_obs q + 4 s)); the Kanter taper goes
 // through sinpi / cospi (no range-reduction table on the stack).  out: 16 x P, column-major blocks (column c at out + c P);

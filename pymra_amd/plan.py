@@ -8,6 +8,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 
+import collections
+
 import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
@@ -48,6 +50,10 @@ LAPLACE_FAMILIES = {"gaussian": MRA_FAMILY_GAUSSIAN, "poisson": MRA_FAMILY_POISS
 LAPLACE_INFO = ("d", "u", "neg2logp", "sum_log_D", "sum_D_res2", "passes", "step", "converged")      # info[8] of mra_plan_fit_laplace
 MRA_SAMPLE_CONDITIONAL = 1
 MRA_COV_POSTERIOR = 1
+MRA_SOLVE_FULL_QUAD = 1
+MRA_FULL_QUAD_MAX = 256
+MRA_TREND_MAX = 63
+MRA_TREND_PREDICT = 1
 MRA_SITES_COV_MAX = 16384
 MRA_SAMPLE_SITES_LEAF_MAX = 4096
 MRA_BLOCK_W_ROWS, MRA_BLOCK_LPRIOR, MRA_BLOCK_FRONT, MRA_BLOCK_LEAF = 0, 1, 2, 3
@@ -71,7 +77,7 @@ ERR_NAMES = {-1: "MRA_ERR_INVALID", -2: "MRA_ERR_HIP", -3: "MRA_ERR_NOT_SPD", -4
 # every symbol include/mra_hip.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "mra_device_count", "mra_release_cached_memory", "mra_plan_create", "mra_plan_destroy", "mra_plan_set_locs", "mra_plan_set_obs",
-    "mra_plan_set_noise", "mra_plan_set_noise_rows", "mra_plan_fit_laplace", "mra_plan_set_metric",
+    "mra_plan_set_noise", "mra_plan_set_noise_rows", "mra_plan_fit_laplace", "mra_plan_set_metric", "mra_plan_set_trend", "mra_trend_fit",
     "mra_plan_set_kernel", "mra_plan_set_locs_rows", "mra_plan_set_obs_rows", "mra_get_predict_rows", "mra_get_predict_rows_sd", "mra_eval_kernel", "mra_plan_set_cov_block", "mra_run", "mra_get_likelihood", "mra_get_predict",
     "mra_sample_slots", "mra_sample", "mra_solve", "mra_cov_apply", "mra_predict_sites", "mra_sites_cov", "mra_sample_sites_slots", "mra_sample_sites", "mra_cv", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
     "mra_get_kernel_stats", "mra_get_kernel_work", "mra_get_route", "mra_device_synchronize", "mra_plan_info", "mra_comm_unique_id", "mra_comm_init",
@@ -87,6 +93,11 @@ class MraTopologyStruct(C.Structure):
                 ("node_leaf", C.c_void_p), ("node_parent", C.c_void_p), ("child_ptr", C.c_void_p),
                 ("child_list", C.c_void_p), ("knot_ptr", C.c_void_p), ("knot_rows", C.c_void_p),
                 ("cw", C.c_void_p)]
+
+
+# what HipPlan.trend_fit returns: beta (p), cov_beta (p x p), the profile and REML -2 log-likelihoods, d and u = G_yy - b^T beta
+# (profile = d + u), the number of observed rows, and with predict=True the universal-kriging mean and variance in the caller's order
+TrendFit = collections.namedtuple("TrendFit", "beta cov_beta profile reml d u n_obs mean var")
 
 
 class MraError(RuntimeError):
@@ -141,6 +152,8 @@ def load_library():
         "mra_sample": (C.c_int, [vp, u32, i64, C.c_uint64, i64, vp, vp]),
         "mra_solve": (C.c_int, [vp, u32, i64, vp, vp, vp]),
         "mra_cov_apply": (C.c_int, [vp, u32, i64, vp, vp, vp]),
+        "mra_plan_set_trend": (C.c_int, [vp, i32, vp]),
+        "mra_trend_fit": (C.c_int, [vp, u32, vp, vp, vp, vp, vp]),
         "mra_predict_sites": (C.c_int, [vp, u32, i64, vp, vp, i64, vp, vp, vp]),
         "mra_sites_cov": (C.c_int, [vp, u32, i64, vp, vp, vp]),
         "mra_sample_sites_slots": (C.c_int, [vp, i64, C.POINTER(i64)]),
@@ -460,10 +473,50 @@ class HipPlan:
         self._check(self.lib.mra_sample(self._h, flags, n, int(seed) & 0xFFFFFFFFFFFFFFFF, int(sample0), zp, _ptr(out)))
         return out
 
-    def solve(self, Y, want_mean=True, want_quad=True):
+    def set_trend(self, X):
+        """The design matrix of a regression trend (mra_plan_set_trend): (N, p) in the caller's order, p <= 63, copied to the device
+        once and kept across every set_*; None (or p = 0) clears it.  It drops no factor."""
+        if X is None:
+            self._check(self.lib.mra_plan_set_trend(self._h, 0, None))
+            self._trend_p = 0
+            return
+        X = np.asarray(X, dtype=np.float64)
+        if X.ndim == 1:
+            X = X.reshape(-1, 1)
+        if X.ndim != 2 or X.shape[0] != self.topo.N:
+            raise ValueError("X must have shape (N, p) = (%d, p)" % self.topo.N)
+        src, perm, _ = self._row_maps()
+        Xp = np.ascontiguousarray(np.where((perm >= 0)[None, :], X[src, :].T, 0.0))
+        self._check(self.lib.mra_plan_set_trend(self._h, int(Xp.shape[0]), _ptr(Xp) if Xp.shape[0] else None))
+        self._trend_p = int(Xp.shape[0])
+
+    def trend_fit(self, predict=False):
+        """Generalised least squares for the trend of ``set_trend`` on the plan's own y (mra_trend_fit) -> TrendFit.  predict=True:
+        also the universal-kriging mean and variance in the caller's row order (rows outside every leaf report 0).  The factors are
+        shared with solve(); y, the options and likelihood() / predict() are unchanged afterwards."""
+        p = int(getattr(self, "_trend_p", 0))
+        beta, cov = np.zeros(max(p, 1)), np.zeros((max(p, 1), max(p, 1)))
+        info = np.zeros(8)
+        mp = np.empty(self.topo.P) if predict else None
+        vp = np.empty(self.topo.P) if predict else None
+        self._check(self.lib.mra_trend_fit(self._h, MRA_TREND_PREDICT if predict else 0, _ptr(beta), _ptr(cov),
+                                           None if mp is None else _ptr(mp), None if vp is None else _ptr(vp), _ptr(info)))
+        mean = var = None
+        if predict:
+            t = self.topo
+            _, perm, in_leaf = self._row_maps()
+            good = (perm >= 0) & (in_leaf != 0)
+            mean, var = np.zeros(t.N), np.zeros(t.N)
+            mean[perm[good]] = mp[good]
+            var[perm[good]] = vp[good]
+        return TrendFit(beta[:p].copy(), cov[:p, :p].copy(), float(info[3]), float(info[4]), float(info[0]), float(info[1]), int(info[5]),
+                        mean, var)
+
+    def solve(self, Y, want_mean=True, want_quad=True, full_quad=False):
         """Factor once, solve many (include/mra_hip.h, mra_solve).  Y: (c, P) observation vectors in padded leaf order, read at the
         plan's observed rows only.  -> (mean (c, P) or None, quad (c, c) or None): mean[k] is the predictive mean for y = Y[k]
-        (unreported rows 0), quad = Y_o^T (Sigma_MRA[o, o] + R I)^-1 Y_o, BLOCK-DIAGONAL in blocks of 16 columns (NaN elsewhere).
+        (unreported rows 0), quad = Y_o^T (Sigma_MRA[o, o] + R I)^-1 Y_o, BLOCK-DIAGONAL in blocks of 16 columns (NaN elsewhere) -
+        with full_quad=True (MRA_SOLVE_FULL_QUAD, c <= 256) the dense symmetric matrix.
         The factorisation is kept between calls; y, the options and likelihood() / predict() are unchanged afterwards."""
         Y = np.ascontiguousarray(Y, dtype=np.float64)
         if Y.ndim != 2 or Y.shape[1] != self.topo.P:
@@ -471,7 +524,7 @@ class HipPlan:
         c = Y.shape[0]
         mean = np.empty((c, self.topo.P)) if want_mean else None
         quad = np.empty((c, c)) if want_quad else None
-        self._check(self.lib.mra_solve(self._h, 0, c, _ptr(Y), None if mean is None else _ptr(mean), None if quad is None else _ptr(quad)))
+        self._check(self.lib.mra_solve(self._h, MRA_SOLVE_FULL_QUAD if full_quad else 0, c, _ptr(Y), None if mean is None else _ptr(mean), None if quad is None else _ptr(quad)))
         return mean, quad
 
     def cov_apply(self, A, posterior=False, want_out=True, want_gram=True):
@@ -633,9 +686,9 @@ class HipPlan:
         return res
 
     def info(self):
-        out = np.zeros(8, dtype=np.int64)
-        self.lib.mra_plan_info(self._h, _ptr(out), 8)
-        keys = ["P", "ldw", "Ka", "n_leaves", "bytes_W", "bytes_panels", "bytes_Gt", "n_nodes"]
+        out = np.zeros(10, dtype=np.int64)
+        self.lib.mra_plan_info(self._h, _ptr(out), len(out))
+        keys = ["P", "ldw", "Ka", "n_leaves", "bytes_W", "bytes_panels", "bytes_Gt", "n_nodes", "trend_p", "bytes_trend"]
         return dict(zip(keys, (int(v) for v in out)))
 
     # -- multi-GPU ---------------------------------------------------------------------------------
