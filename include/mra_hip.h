@@ -289,6 +289,41 @@ int mra_solve(mra_plan *plan, uint32_t flags, int64_t n_cols, const double *Y, d
 int mra_plan_set_trend(mra_plan *plan, int32_t p, const double *X_perm);
 int mra_trend_fit(mra_plan *plan, uint32_t flags, double *beta, double *cov_beta, double *mean_perm, double *var_perm, double *info);
 
+/* The two together: z_p ~ p(. | eta_p) with eta = X beta + x + offset, x ~ MRA(0, Sigma), a flat prior on beta
+ * in R^p - the families, g, D, its floor and the starts of mra_plan_fit_laplace, X the resident matrix of mra_plan_set_trend.  The
+ * iteration runs on e = eta - offset = X beta + x at the observed rows.  One iteration from e: t = e + g / D and r = 1 / D into the
+ * plan's y and noise (the launch of mra_plan_fit_laplace); ONE likelihood pass with W at every row for the factors of K = Sigma_oo +
+ * diag r (MRA_OPT_PRIOR_REUSE and MRA_OPT_RESID_REUSE hold from the second pass on: only the noise changed); the GLS step of
+ * mra_trend_fit on [t | X] (same code: forward sweeps per block of 16 columns, cross tiles when p + 1 > 16, G to the host, A = L L^T,
+ * beta^ = A^-1 b) with the backward sweeps and the row kernel per block, which leave the zero-mean kriging means m_t, m_X on the
+ * device; and two launches (k_laplace_trend_part, k_laplace_sum) that form e^ = m_t + (X - m_X)^T beta^ = X beta^ + x^, make it the
+ * iterate and return step = max |e^ - e| and the sums below (fixed partial results in a fixed order: the same inputs give the same
+ * bits).  No predict pass runs.  The call stops after the pass with step <= tol * max(1, max |e^|), or after max_iter passes; a step
+ * that is NaN or inf ends it, not converged.  Plain Newton, no damping.  The Gaussian family takes two passes, the second with step 0,
+ * and its beta, cov_beta, info[0], [1], [8] are those of mra_trend_fit after mra_plan_set_obs(z - offset) + mra_plan_set_noise(aux).
+ * z_perm, aux_perm, offset_perm as in mra_plan_fit_laplace; e0_perm: P values, the start of e (NULL: the data-based start of that
+ * table, i.e. beta = 0 and x = that start).  beta (p), cov_beta (p x p = A^-1 of the last pass, or NULL).
+ * info[12]: [0] d = log|K|; [1] G_tt - b^T beta^; [2] -2 sum log p(z_p | eta^_p), every constant included; [3] sum log D_p;
+ * [4] sum D_p (t_p - e^_p)^2; [5] passes; [6] the last step; [7] converged; [8] log det A; [9] the profile value
+ * -2 log q = [0] + [1] + [2] + [3] - [4] (beta at its mode); [10] the marginal value [9] + [8] - p log 2 pi (beta integrated out, the
+ * Laplace REML criterion: the joint Hessian has det = det(Sigma^-1 + D) det A, and x^^T Sigma^-1 x^ = [1] - [4]); [11] the number
+ * of observed rows.
+ * Refusals, in this order, each checked on the host before anything changes: those of every call on the retained factors (before
+ * set_locs / set_kernel / set_obs: MRA_ERR_STATE; MRA_KERNEL_HOST plans and sharded plans: MRA_ERR_INVALID); no trend set:
+ * MRA_ERR_STATE; the argument checks of mra_plan_fit_laplace in its order (e0 in the place of x0); a NULL beta: MRA_ERR_INVALID.  On
+ * MRA_HOST_DRYRUN plans all of these are reached, then MRA_ERR_STATE (the plan cannot run).  A pivot of A that fails mra_trend_fit's
+ * test: MRA_ERR_NOT_SPD, "trend columns are linearly dependent at the observed rows", with that pass's t and r in the plan; a pass's
+ * own MRA_ERR_NOT_SPD propagates likewise.
+ * Afterwards the plan is a plan after mra_plan_set_obs(t) + mra_plan_set_noise(r) with the factors valid and the trend still set:
+ * mra_trend_fit(MRA_TREND_PREDICT) gives the mean of e and its variance with the uncertainty of beta^ in it, mra_predict_sites,
+ * mra_sites_cov and mra_solve serve the Laplace posterior, mra_get_buffer(10 / 11) give r / t.  What mra_get_likelihood /
+ * mra_get_predict return stays as the caller left it, as after every call on the retained factors; mra_get_kernel_stats sums the
+ * launches of the whole call (the new kernels under the family of the other elementwise ones), and mra_get_buffer(14) the stream
+ * milliseconds of its sweeps as for mra_trend_fit, summed over the passes, the tail of the iterations under "rows".
+ * mra_plan_fit_laplace itself ignores a trend.  Memory: as mra_trend_fit(MRA_TREND_PREDICT) without its 3 P.  Blocking. */
+int mra_plan_fit_laplace_trend(mra_plan *plan, int family, const double *z_perm, const double *aux_perm, const double *offset_perm,
+                               const double *e0_perm, int max_iter, double tol, double *beta, double *cov_beta, double *info);
+
 /* The MRA covariance as an operator (no counterpart in the reference, which can only draw from it, pyMRA/MRATools.py:395-484): the
  * prior covariance of the latent field at the reported rows (real rows inside a leaf) is
  *     Sigma = sum over non-leaf j of W_j W_j^T + sum over leaves l of v_M(K_l, K_l),   v_M(S, S) = C(S, S) - W_anc[S] W_anc[S]^T,

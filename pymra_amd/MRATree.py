@@ -211,7 +211,7 @@ class MRATree(object):
             mean, var, self._sd = None, None, None
         self.root = RootView(d, u, mean, var, N, self.topology, self.cov_locs, spec)
         self._node_blocks = {}
-        self.trend, self._X = None, None
+        self.trend, self._X, self._X_arg, self._trend_y = None, None, None, None
         if X is not None:
             self.setTrend(X, want_predict=want_predict)
 
@@ -226,15 +226,23 @@ class MRATree(object):
         self._node_blocks = {}
         if X is None:
             self.plan.set_trend(None)
-            self.trend, self._X = None, None
+            self.trend, self._X, self._X_arg, self._trend_y = None, None, None, None
             self.plan.run(likelihood=True, predict=want_predict)
             d, u = self.plan.likelihood()
             mean, var, self._sd = self.plan.predict(with_sd=True) if want_predict else (None, None, None)
             self.root = RootView(d, u, mean, var, N, self.topology, self.cov_locs, self.kernel)
             return self.getLikelihood()
+        self._send_trend(X)
+        self._trend_y = None
+        self._fit_trend(want_predict)
+        return self.getLikelihood()
+
+    def _send_trend(self, X):
+        """Check X ((N, p), finite) and send it to the device; ``_X_arg`` remembers the caller's own array."""
+        N = len(self.locs)
         if self.kernel is None:
             raise NotImplementedError("a trend needs a device kernel: trees built from an opaque callable or a dense matrix cannot fit one")
-        X = np.asarray(X, dtype=np.float64)
+        arg, X = X, np.asarray(X, dtype=np.float64)
         if X.ndim == 1:
             X = X.reshape(-1, 1)
         if X.ndim != 2 or X.shape[0] != N or X.shape[1] < 1:
@@ -242,9 +250,7 @@ class MRATree(object):
         if not np.all(np.isfinite(X)):
             raise ValueError("X must be finite")
         self.plan.set_trend(X)
-        self._X = X
-        self._fit_trend(want_predict)
-        return self.getLikelihood()
+        self._X, self._X_arg = X, arg
 
     def _fit_trend(self, want_predict):
         fit = self.plan.trend_fit(predict=want_predict)
@@ -431,7 +437,9 @@ class MRATree(object):
         if Xs.shape != (len(S), p) or not np.all(np.isfinite(Xs)):
             raise ValueError("X_sites must be a finite array of shape (n, p) = (%d, %d)" % (len(S), p))
         # zero-mean kriging of the columns [y | X] at the sites, then the formulas of the fit on the host
-        YX = np.column_stack([np.nan_to_num(np.asarray(self.obs, dtype=np.float64).reshape(-1)), self._X])
+        # (the y of the fit: this tree's observations, or the pseudo-observations t of fitLaplace(X=...))
+        y_fit = self.obs if self._trend_y is None else self._trend_y
+        YX = np.column_stack([np.nan_to_num(np.asarray(y_fit, dtype=np.float64).reshape(-1)), self._X])
         m, sd = self._predict_at(S, YX, leaf)
         h = Xs - m[:, 1:]
         mean = m[:, 0] + h @ self.trend.beta
@@ -648,13 +656,26 @@ class MRATree(object):
         self.root = RootView(d, u, mean, var, len(self.locs), self.topology, self.cov_locs, self.kernel)
         return self.getLikelihood()
 
-    def fitLaplace(self, family, aux=None, offset=None, z=None, x0=None, cov=None, max_iter=50, tol=1e-10):
+    def fitLaplace(self, family, aux=None, offset=None, z=None, x0=None, cov=None, max_iter=50, tol=1e-10, X=None, reml=False):
         """Fit non-Gaussian data on this tree by a Laplace approximation (``HipPlan.fit_laplace``): family "gaussian" (variance
         ``aux``), "poisson" (``offset`` = log exposure) or "binomial" (``aux`` trials), eta = x + offset.  z: N values, finite
         exactly where this tree observes (default: the tree's ``obs``).  cov: other parameters of a device kernel, set without a
         pass of its own (MLE loops).  x0: the start; default the mean of the previous fit when there is one (a warm start), else the
         data-based start.  Updates ``root`` and ``predict()`` to the Laplace posterior N(x^, (Sigma^-1 + D)^-1), keeps the numbers
-        of the fit in ``self.laplace`` and returns -2 log q(z); ``getLikelihood()`` keeps its meaning, d + u of the last pass."""
+        of the fit in ``self.laplace`` and returns -2 log q(z); ``getLikelihood()`` keeps its meaning, d + u of the last pass.
+        X: (N, p) covariates of a regression trend, eta = X beta + x + offset with a flat prior on beta
+        (``HipPlan.fit_laplace_trend``).  X is sent to the device only when it is not the very array sent last (the object is
+        compared, not its values: pass a new array after changing one in place); x0 is then the start of e = X beta + x, by default the
+        e^ of the previous such fit.  Returns the profile -2 log q (beta at its mode), or with reml=True the value with beta
+        integrated out; afterwards ``trend`` holds beta and cov_beta, predict() is the mean and sd of e = X beta + x with the
+        uncertainty of beta in it, and predictAt(sites, X_sites=...) serves the same at new sites (exp(mean + log exposure) is a
+        fitted count).  The plan then holds the pseudo-observations t and their noise 1 / D: a later setNoise(R) or reevaluate(cov)
+        refits a Gaussian trend on t (with the caller's R in place of 1 / D) and is no Laplace fit any more - call fitLaplace(X=X,
+        cov=...) again for other kernel parameters.  Without X a tree that has a trend is refused."""
+        if X is not None:
+            return self._fit_laplace_trend(family, aux, offset, z, x0, cov, max_iter, tol, X, reml)
+        if reml:
+            raise ValueError("reml=True needs X")
         self._no_trend("fitLaplace")
         if cov is not None:
             spec = probe_cov(cov, self.cov_d, self.cov_locs)
@@ -673,3 +694,31 @@ class MRATree(object):
         self.laplace = res
         self.root = RootView(res["d"], res["u"], mean, var, len(self.locs), self.topology, self.cov_locs, self.kernel)
         return res["lik"]
+
+    def _fit_laplace_trend(self, family, aux, offset, z, e0, cov, max_iter, tol, X, reml):
+        if cov is not None:
+            spec = probe_cov(cov, self.cov_d, self.cov_locs)
+            if spec is None:
+                raise NotImplementedError("cov must be a device kernel")
+            self._check_spec_metric(spec)
+            self._send_kernel(spec)
+        if self.trend is None or X is not self._X_arg:
+            self._send_trend(X)
+        if z is None:
+            z = self.obs
+        if e0 is None:
+            e0 = getattr(self, "_laplace_e", None)
+        self._node_blocks = {}
+        res = self.plan.fit_laplace_trend(family, z, aux=aux, offset=offset, e0=e0, max_iter=max_iter, tol=tol)
+        fit = self.plan.trend_fit(predict=True)          # the factors stand: one predict pass for the variance, one for W again
+        t = self.topology
+        tp = self.plan.buffer(11)
+        good = np.asarray(t.perm) >= 0
+        self._trend_y = np.zeros(len(self.locs))
+        self._trend_y[np.asarray(t.perm)[good]] = np.nan_to_num(tp[good])
+        self.trend = fit
+        self._sd = np.sqrt(fit.var)
+        self._laplace_e = fit.mean.copy() if res["converged"] else None      # (a fit that did not converge is no start for the next)
+        self.laplace = res
+        self.root = RootView(res["d"], res["u"], fit.mean, fit.var, len(self.locs), self.topology, self.cov_locs, self.kernel)
+        return res["reml"] if reml else res["profile"]

@@ -1,6 +1,6 @@
-// mra_laplace_kernels.h - kernels of mra_plan_fit_laplace: what runs between two Gaussian passes of the Newton
-// iteration of a Laplace approximation.  Included by mra_launch_laplace.hip only, so that the other translation units keep their
-// object code.
+// mra_laplace_kernels.h - kernels of mra_plan_fit_laplace and mra_plan_fit_laplace_trend (section 21): what runs
+// between two Gaussian passes of the Newton iteration of a Laplace approximation.  Included by mra_launch_laplace.hip only, so that the
+// other translation units keep their object code.
 //
 // Everything is by padded row.  A row is observed when its z is finite: the host uploads NaN at every row the plan does not observe.
 // eta = x + offset; g = d log p / d eta; D = max(-d2 log p / d eta2, 2^-40).
@@ -60,6 +60,24 @@ __global__ __launch_bounds__(256) void k_laplace_linearise(int family, const dou
     y[p] = t; noise[p] = r; noise_sd[p] = sqrt(r);
 }
 
+// a workgroup's 256 x LAPLACE_NRES values -> its partial results: a fixed tree, the two maxima first (they keep a NaN)
+__device__ __forceinline__ void laplace_fold(const double (&v)[LAPLACE_NRES], double (&sh)[LAPLACE_NRES][256], double* __restrict__ part) {
+#pragma unroll
+    for (int k = 0; k < LAPLACE_NRES; ++k) sh[k][threadIdx.x] = v[k];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+#pragma unroll
+            for (int k = 0; k < LAPLACE_NRES; ++k) {
+                const double a = sh[k][threadIdx.x], b = sh[k][threadIdx.x + w];
+                sh[k][threadIdx.x] = k < 2 ? laplace_max(a, b) : a + b;
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < LAPLACE_NRES) part[(long)blockIdx.x * LAPLACE_NRES + threadIdx.x] = sh[threadIdx.x][0];
+}
+
 // After the pass: with x^ = mean at the observed rows, per workgroup {max |x^ - x|, max |x^|, sum log D, sum D (t - x^)^2, sum of the
 // x-dependent part of log p(z | x^ + offset)}, D = 1 / noise and t = y of the pass.  A thread walks its rows in order, the workgroup
 // folds its 256 values in a fixed tree: the same inputs give the same bits.  The two maxima keep a NaN (laplace_max): a mean that is
@@ -80,21 +98,42 @@ __global__ __launch_bounds__(256) void k_laplace_part(int family, const double* 
         v[3] += D * dt * dt;
         v[4] += laplace_term(family, zp, aux[p], xh + off[p]).logp;
     }
-#pragma unroll
-    for (int k = 0; k < LAPLACE_NRES; ++k) sh[k][threadIdx.x] = v[k];
-    __syncthreads();
-    for (int w = 128; w > 0; w >>= 1) {
-        if ((int)threadIdx.x < w) {
-#pragma unroll
-            for (int k = 0; k < LAPLACE_NRES; ++k) {
-                const double a = sh[k][threadIdx.x], b = sh[k][threadIdx.x + w];
-                sh[k][threadIdx.x] = k < 2 ? laplace_max(a, b) : a + b;
-            }
-        }
-        __syncthreads();
-    }
-    if (threadIdx.x < LAPLACE_NRES) part[(long)blockIdx.x * LAPLACE_NRES + threadIdx.x] = sh[threadIdx.x][0];
+    laplace_fold(v, sh, part);
 }
+
+// ---- mra_plan_fit_laplace_trend: the tail of one iteration with a regression trend ------------------------------
+// m: (1 + p) x P zero-mean kriging means of [t | X] (row 0: m_t), X: p x P design matrix, both by padded row; beta: the GLS estimate
+// of this pass.  At every observed row e^ = m_t + (X - m_X)^T beta^ (the sum in k_trend_rows' order) replaces the iterate in x - read
+// first: the step is taken against it - and the workgroup's five partial results are those of k_laplace_part with x^ := e^: same
+// number of workgroups, same walk, same fold, so k_laplace_sum finishes both.  One row per lane: covariate j of 64 consecutive rows
+// is one 512-byte line of X and one of m; beta^ sits in LDS and is read by broadcast; no per-lane array.
+__global__ __launch_bounds__(256) void k_laplace_trend_part(int family, const double* __restrict__ z, const double* __restrict__ aux,
+                                                            const double* __restrict__ off, double* __restrict__ x,
+                                                            const double* __restrict__ m, const double* __restrict__ X,
+                                                            const double* __restrict__ beta, const double* __restrict__ y,
+                                                            const double* __restrict__ noise, int p, long P, double* __restrict__ part) {
+    __shared__ double sh[LAPLACE_NRES][256];
+    __shared__ double bs[64];
+    if (threadIdx.x < 64) bs[threadIdx.x] = (int)threadIdx.x < p ? beta[threadIdx.x] : 0.0;
+    __syncthreads();
+    double v[LAPLACE_NRES] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    for (long s = (long)blockIdx.x * 256 + threadIdx.x; s < P; s += (long)gridDim.x * 256) {
+        const double zp = z[s];
+        if (!(fabs(zp) < __builtin_inf())) continue;
+        double eh = m[s];
+#pragma unroll 4
+        for (int j = 0; j < p; ++j) eh = __builtin_fma(X[(long)j * P + s] - m[(long)(j + 1) * P + s], bs[j], eh);
+        const double D = 1.0 / noise[s], dt = y[s] - eh;
+        v[0] = laplace_max(v[0], fabs(eh - x[s]));
+        v[1] = laplace_max(v[1], fabs(eh));
+        v[2] += log(D);
+        v[3] += D * dt * dt;
+        v[4] += laplace_term(family, zp, aux[s], eh + off[s]).logp;
+        x[s] = eh;
+    }
+    laplace_fold(v, sh, part);
+}
+
 // the workgroups' partial results -> res[LAPLACE_NRES]: one wave per result; lane l folds workgroups l, l + 64, ... in that order, then
 // the 64 lanes fold in a fixed tree
 __global__ __launch_bounds__(64 * LAPLACE_NRES) void k_laplace_sum(const double* __restrict__ part, int nblk, double* __restrict__ res) {

@@ -1,6 +1,6 @@
-// mra_launch_laplace.hip - mra_plan_fit_laplace: the work buffers and the launches between two passes of the
-// Newton iteration - and the other elementwise kernel of the library, k_metric_apply of mra_plan_set_metric, at
-// the end.  A translation unit of its own: the kernels of the pass keep their object code.
+// mra_launch_laplace.hip - mra_plan_fit_laplace and mra_plan_fit_laplace_trend (section 21): the work buffers and
+// the launches between two passes of the Newton iteration - and the other elementwise kernel of the library, k_metric_apply of
+// mra_plan_set_metric, at the end.  A translation unit of its own: the kernels of the pass keep their object code.
 #define MRA_KERNELS_TEMPLATES_ONLY
 #include "mra_laplace_kernels.h"
 
@@ -23,6 +23,15 @@ void mra_laplace_reduce(mra_plan* pl, int family, double* res) {
     static_assert(LAPLACE_NRES == MRA_LAPLACE_NRES, "the plan's record and the kernels disagree");
     hipLaunchKernelGGL(k_laplace_part, dim3(LAPLACE_BLOCKS), dim3(256), 0, pl->stream, family, L.z.p, L.aux.p, L.off.p, L.x.p, pl->mean.p,
                        pl->y.p, pl->noise.p, pl->P, L.part.p);
+    hipLaunchKernelGGL(k_laplace_sum, dim3(1), dim3(64 * LAPLACE_NRES), 0, pl->stream, L.part.p, LAPLACE_BLOCKS, res);
+}
+
+// mra_plan_fit_laplace_trend: e^ from trend.m, trend.X and beta (device, trend.coef) into lap.x, and the five results of the iteration
+void mra_laplace_trend_reduce(mra_plan* pl, int family, double* res) {
+    mra_plan::Laplace& L = pl->lap;
+    mra_plan::Trend& T = pl->trend;
+    hipLaunchKernelGGL(k_laplace_trend_part, dim3(LAPLACE_BLOCKS), dim3(256), 0, pl->stream, family, L.z.p, L.aux.p, L.off.p, L.x.p, T.m.p,
+                       T.X.p, T.coef.p, pl->y.p, pl->noise.p, T.p, pl->P, L.part.p);
     hipLaunchKernelGGL(k_laplace_sum, dim3(1), dim3(64 * LAPLACE_NRES), 0, pl->stream, L.part.p, LAPLACE_BLOCKS, res);
 }
 

@@ -2449,6 +2449,18 @@ static void launch_result(mra_plan* pl) {
                            pl->W.p, (long)pl->ldw, pl->Ka, pl->mean.p, pl->P);
 }
 
+// the per-kernel times of the launches recorded so far (KTimer, kernel timing on) into the plan; drops their events.  The stream has
+// been synchronised.
+static void harvest_kernel_events(mra_plan* pl) {
+    for (auto& e : pl->kev) {
+        float ms = 0.f;
+        hipEventElapsedTime(&ms, e.second.first, e.second.second);
+        pl->kstat[e.first].ms += ms;
+        hipEventDestroy(e.second.first); hipEventDestroy(e.second.second);
+    }
+    pl->kev.clear();
+}
+
 // the finished pass's phase times (the inner four only with kernel timing on) and per-kernel times into the plan; drops the kernel events
 static void harvest_timers(mra_plan* pl) {
     float ms;
@@ -2459,12 +2471,7 @@ static void harvest_timers(mra_plan* pl) {
     }
     hipEventElapsedTime(&ms, pl->ev[0], pl->ev[5]);
     pl->phase_ms[4] = ms;
-    for (auto& e : pl->kev) {
-        hipEventElapsedTime(&ms, e.second.first, e.second.second);
-        pl->kstat[e.first].ms += ms;
-        hipEventDestroy(e.second.first); hipEventDestroy(e.second.second);
-    }
-    pl->kev.clear();
+    harvest_kernel_events(pl);
 }
 
 // the pass is over, whatever it found: errv is the record's error flag (0, or 1 + the node whose Cholesky failed)
@@ -2702,9 +2709,11 @@ static void sampler_prior(mra_plan* pl) { run_all(pl, MRA_RUN_LIKELIHOOD, true);
 // What every call on the retained factors refuses before it looks at its own arguments, in this order.  `who` names the export;
 // host_cannot / sharded_cannot finish "<who>: MRA_KERNEL_HOST plans ..." and "<who>: sharded plans ...".
 // (the prior basis is computed by the plan's likelihood pass, which reads the observation layout: set_obs comes first for every call)
-static void retained_check_plan(const mra_plan* pl, const char* who, uint32_t flags, uint32_t accepted, const char* host_cannot, const char* sharded_cannot) {
+// (dry_last: the caller has refusals of its own that a dry-run plan must reach; it refuses the dry run itself, behind them)
+static void retained_check_plan(const mra_plan* pl, const char* who, uint32_t flags, uint32_t accepted, const char* host_cannot, const char* sharded_cannot,
+                                bool dry_last = false) {
     char m[200];
-    if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
+    if (g_dry && !dry_last) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
     if (flags & ~accepted) { snprintf(m, sizeof m, "unknown %s flags", who); throw MraError(MRA_ERR_INVALID, m); }
     if (!(pl->have_locs && pl->have_kernel)) { snprintf(m, sizeof m, "%s needs set_locs and set_kernel first", who); throw MraError(MRA_ERR_STATE, m); }
     if (!pl->have_obs) { snprintf(m, sizeof m, "%s needs set_obs first", who); throw MraError(MRA_ERR_STATE, m); }
@@ -2922,41 +2931,30 @@ static void set_trend(mra_plan* pl, int32_t p, const double* X) {
     T.p = p;
 }
 
-static void trend_fit(mra_plan* pl, uint32_t flags, double* beta, double* cov_beta, double* mean, double* var, double* info) {
-    retained_check_plan(pl, "mra_trend_fit", flags, MRA_TREND_PREDICT, "cannot fit a trend (C(S, o) is evaluated on the device)", "cannot fit a trend");
+// mra_sites_timed adds to trend.ms while this lives (scopes may nest: the outer one's sink is put back)
+struct TrendMsSink {
+    mra_plan::Sites& s; double* prev;
+    explicit TrendMsSink(mra_plan* pl) : s(pl->sit), prev(pl->sit.ms_sink) { s.ms_sink = pl->trend.ms; }
+    ~TrendMsSink() { s.ms_sink = prev; }
+};
+
+// What the GLS step leaves on the host beside beta and cov_beta: G_tt - b^T beta^, log det A, the extreme pivots of A, and beta^ and
+// L^-1 (row stride MRA_TREND_MAX + 1) as k_trend_rows reads them.
+struct TrendGls {
+    double resid = 0.0, logdet = 0.0, pmin = INFINITY, pmax = 0.0;
+    std::vector<double> Li, bt;
+};
+
+// The GLS step of mra_trend_fit and of every iteration of mra_plan_fit_laplace_trend, on factors that stand: G = [y | X]^T K^-1 [y | X]
+// block by block from the device's own y and X, A = L L^T and beta^ = A^-1 b on the host.  pred: the backward sweeps and the row
+// kernel per block as well, the kriging means of the 1 + p columns into trend.m.  `who` names the export in the refusal.
+static void trend_gls(mra_plan* pl, const char* who, bool pred, double* beta, double* cov_beta, TrendGls& R) {
     mra_plan::Trend& T = pl->trend;
-    if (T.p == 0) throw MraError(MRA_ERR_STATE, "mra_trend_fit needs mra_plan_set_trend first");
-    if (!beta || !info) throw MraError(MRA_ERR_INVALID, "mra_trend_fit: beta or info is NULL");
-    const bool pred = (flags & MRA_TREND_PREDICT) != 0;
-    if (!pred && (mean || var)) throw MraError(MRA_ERR_INVALID, "mra_trend_fit: mean_perm or var_perm given without MRA_TREND_PREDICT");
-    if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
+    mra_plan::Solver& S = pl->slv;
     const long P = pl->P;
     const int p = T.p, n = p + 1, nblk = (n + 15) / 16;
-    HIP_TRY(mraSetDevice(pl->device));
-    mra_solver_build(pl);
-    mra_plan::Solver& S = pl->slv;
-    if (pred) {
-        if (T.m.n != (size_t)n * P) T.m.alloc((size_t)n * P);
-        if (T.var_pass.n != (size_t)P) { T.var_pass.alloc((size_t)P); T.mean.alloc((size_t)P); T.var.alloc((size_t)P); T.var_valid = false; }
-        if (!T.coef.n) T.coef.alloc((size_t)MRA_TREND_MAX + 1 + (size_t)(MRA_TREND_MAX + 1) * (MRA_TREND_MAX + 1));
-        if (!(S.valid && T.var_valid)) {
-            // the variance of a predict pass on the plan's own y; that pass rewrites W, so the factors are made again behind it
-            {
-                KeepResults keep(pl, nullptr, S.msave.p, S.vsave.p);
-                run_all(pl, MRA_RUN_LIKELIHOOD | MRA_RUN_PREDICT);
-                HIP_TRY(hipMemcpyAsync(T.var_pass.p, pl->var.p, (size_t)P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
-            }
-            S.valid = false;
-            ensure_factors(pl);
-            T.var_valid = true;
-        } else ensure_factors(pl);
-    } else ensure_factors(pl);
+    TrendMsSink sink(pl);
     // G = [y | X]^T K^-1 [y | X], block by block from the device's own y and X (timed as the site calls are, into trend.ms)
-    for (double& v : T.ms) v = 0.0;
-    for (size_t t = 0; t < pl->leaf_nodes.size(); ++t)
-        T.ms[5] += 8.0 * (double)(pl->Ka - pl->asuf[pl->node_level[pl->leaf_nodes[t]]]) * (double)pl->leaf_nop[t];
-    T.ms[6] = 8.0 * 16.0 * (double)S.arch_rows;
-    struct Sink { mra_plan::Sites& s; Sink(mra_plan::Sites& t, double* ms) : s(t) { s.ms_sink = ms; } ~Sink() { s.ms_sink = nullptr; } } sink(pl->sit, T.ms);
     if (nblk > 1) mra_solver_archive(pl, nblk);
     std::vector<double> G((size_t)n * n, 0.0);
     for (int b = 0; b < nblk; ++b) {
@@ -2986,15 +2984,20 @@ static void trend_fit(mra_plan* pl, uint32_t flags, double* beta, double* cov_be
     }
     // A = L L^T on the host (at most 63 x 63); Li = L^-1
     constexpr int LD = MRA_TREND_MAX + 1;
-    std::vector<double> L((size_t)p * p, 0.0), Li((size_t)LD * LD, 0.0), bt((size_t)LD, 0.0);
+    std::vector<double> L((size_t)p * p, 0.0);
+    std::vector<double>&Li = R.Li, &bt = R.bt;
+    Li.assign((size_t)LD * LD, 0.0); bt.assign((size_t)LD, 0.0);
     double dmax = 0.0, pmin = INFINITY, pmax = 0.0, logdet = 0.0;
     for (int i = 0; i < p; ++i) dmax = std::max(dmax, G[(size_t)(i + 1) * n + i + 1]);
     const double floor_ = (double)p * 2.220446049250313e-16 * dmax;
     for (int j = 0; j < p; ++j) {
         double piv = G[(size_t)(j + 1) * n + j + 1];
         for (int k = 0; k < j; ++k) piv -= L[(size_t)j * p + k] * L[(size_t)j * p + k];
-        if (!(piv > 0.0) || !(piv >= floor_) || !std::isfinite(piv))
-            throw MraError(MRA_ERR_NOT_SPD, "mra_trend_fit: trend columns are linearly dependent at the observed rows");
+        if (!(piv > 0.0) || !(piv >= floor_) || !std::isfinite(piv)) {
+            char msg[128];
+            snprintf(msg, sizeof msg, "%s: trend columns are linearly dependent at the observed rows", who);
+            throw MraError(MRA_ERR_NOT_SPD, msg);
+        }
         const double ljj = std::sqrt(piv);
         L[(size_t)j * p + j] = ljj;
         pmin = std::min(pmin, piv); pmax = std::max(pmax, piv); logdet += std::log(piv);
@@ -3028,13 +3031,64 @@ static void trend_fit(mra_plan* pl, uint32_t flags, double* beta, double* cov_be
                 for (int k = std::max(i, j); k < p; ++k) v += Li[(size_t)k * LD + i] * Li[(size_t)k * LD + j];
                 cov_beta[(size_t)i * p + j] = v;
             }
+    double bb = 0.0;
+    for (int i = 0; i < p; ++i) bb += G[(size_t)(i + 1) * n] * beta[i];
+    R.resid = G[0] - bb; R.logdet = logdet; R.pmin = pmin; R.pmax = pmax;
+}
+
+// trend.ms of a call that is about to run its sweeps: the times start at 0, the last two are what one block's sweeps move
+static void trend_ms_reset(mra_plan* pl) {
+    mra_plan::Trend& T = pl->trend;
+    for (double& v : T.ms) v = 0.0;
+    for (size_t t = 0; t < pl->leaf_nodes.size(); ++t)
+        T.ms[5] += 8.0 * (double)(pl->Ka - pl->asuf[pl->node_level[pl->leaf_nodes[t]]]) * (double)pl->leaf_nop[t];
+    T.ms[6] = 8.0 * 16.0 * (double)pl->slv.arch_rows;
+}
+
+static long observed_rows(const mra_plan* pl) {
     long nobs = 0;
     for (size_t t = 0; t < pl->leaf_nodes.size(); ++t)
         for (long r = pl->row0[pl->leaf_nodes[t]]; r < pl->row1[pl->leaf_nodes[t]]; ++r) nobs += pl->y_finite_host[r] ? 1 : 0;
-    double bb = 0.0;
-    for (int i = 0; i < p; ++i) bb += G[(size_t)(i + 1) * n] * beta[i];
-    info[0] = S.pass_d; info[1] = G[0] - bb; info[2] = logdet; info[3] = info[0] + info[1]; info[4] = info[3] + info[2];
-    info[5] = (double)nobs; info[6] = (double)p; info[7] = pmin / pmax;
+    return nobs;
+}
+
+static void trend_fit(mra_plan* pl, uint32_t flags, double* beta, double* cov_beta, double* mean, double* var, double* info) {
+    retained_check_plan(pl, "mra_trend_fit", flags, MRA_TREND_PREDICT, "cannot fit a trend (C(S, o) is evaluated on the device)", "cannot fit a trend");
+    mra_plan::Trend& T = pl->trend;
+    if (T.p == 0) throw MraError(MRA_ERR_STATE, "mra_trend_fit needs mra_plan_set_trend first");
+    if (!beta || !info) throw MraError(MRA_ERR_INVALID, "mra_trend_fit: beta or info is NULL");
+    const bool pred = (flags & MRA_TREND_PREDICT) != 0;
+    if (!pred && (mean || var)) throw MraError(MRA_ERR_INVALID, "mra_trend_fit: mean_perm or var_perm given without MRA_TREND_PREDICT");
+    if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
+    const long P = pl->P;
+    const int p = T.p, n = p + 1;
+    HIP_TRY(mraSetDevice(pl->device));
+    mra_solver_build(pl);
+    mra_plan::Solver& S = pl->slv;
+    if (pred) {
+        if (T.m.n != (size_t)n * P) T.m.alloc((size_t)n * P);
+        if (T.var_pass.n != (size_t)P) { T.var_pass.alloc((size_t)P); T.mean.alloc((size_t)P); T.var.alloc((size_t)P); T.var_valid = false; }
+        if (!T.coef.n) T.coef.alloc((size_t)MRA_TREND_MAX + 1 + (size_t)(MRA_TREND_MAX + 1) * (MRA_TREND_MAX + 1));
+        if (!(S.valid && T.var_valid)) {
+            // the variance of a predict pass on the plan's own y; that pass rewrites W, so the factors are made again behind it
+            {
+                KeepResults keep(pl, nullptr, S.msave.p, S.vsave.p);
+                run_all(pl, MRA_RUN_LIKELIHOOD | MRA_RUN_PREDICT);
+                HIP_TRY(hipMemcpyAsync(T.var_pass.p, pl->var.p, (size_t)P * sizeof(double), hipMemcpyDeviceToDevice, pl->stream));
+            }
+            S.valid = false;
+            ensure_factors(pl);
+            T.var_valid = true;
+        } else ensure_factors(pl);
+    } else ensure_factors(pl);
+    trend_ms_reset(pl);
+    TrendMsSink sink(pl);                    // the GLS step, the upload of beta and L^-1, k_trend_rows and the downloads: all into trend.ms
+    TrendGls R;
+    trend_gls(pl, "mra_trend_fit", pred, beta, cov_beta, R);
+    const std::vector<double>&Li = R.Li, &bt = R.bt;
+    constexpr int LD = MRA_TREND_MAX + 1;
+    info[0] = S.pass_d; info[1] = R.resid; info[2] = R.logdet; info[3] = info[0] + info[1]; info[4] = info[3] + info[2];
+    info[5] = (double)observed_rows(pl); info[6] = (double)p; info[7] = R.pmin / R.pmax;
     if (!pred) return;
     mra_sites_timed(pl, 4, [&] {
         HIP_TRY(hipMemcpyAsync(T.coef.p, bt.data(), (size_t)LD * sizeof(double), hipMemcpyHostToDevice, pl->stream));
@@ -3933,9 +3987,10 @@ static void set_noise(mra_plan* pl, const double* r) {
 // t = x + g / D with noise r = 1 / D, which one launch writes into the plan's y / noise / noise_sd; the step and the sums of the
 // result come from one reduction (two launches) after the pass.  Every argument is checked before anything changes.
 static inline double lgamma_of(double v) { int sign; return lgamma_r(v, &sign); }      // (std::lgamma writes the global signgam: not for threads)
-static void fit_laplace(mra_plan* pl, int family, const double* z, const double* aux, const double* off, const double* x0, int max_iter,
-                        double tol, double* info) {
-    const char* who = "mra_plan_fit_laplace";
+// The argument checks of mra_plan_fit_laplace and mra_plan_fit_laplace_trend (`who`; x0_name: what the start is called), in the
+// header's order, before anything changes.  seen: the rows the plan observes.
+static void laplace_check(const mra_plan* pl, const char* who, const char* x0_name, int family, const double* z, const double* aux,
+                          const double* off, const double* x0, int max_iter, double tol, const double* info, std::vector<unsigned char>& seen) {
     char m[200];
     auto invalid = [&](const char* what, long p) {
         if (p >= 0) snprintf(m, sizeof m, "%s: %s (padded row %ld)", who, what, p); else snprintf(m, sizeof m, "%s: %s", who, what);
@@ -3947,7 +4002,7 @@ static void fit_laplace(mra_plan* pl, int family, const double* z, const double*
     const bool need_aux = family != MRA_FAMILY_POISSON;
     const bool readable = z && info && (aux || !need_aux);
     // observed: a finite y inside a leaf, as mra_plan_set_noise reads it (rows outside every leaf are nobody's)
-    std::vector<unsigned char> seen((size_t)P, 0);
+    seen.assign((size_t)P, 0);
     for (size_t t = 0; t < pl->leaf_nodes.size(); ++t)
         for (long p = pl->row0[pl->leaf_nodes[t]]; p < pl->row1[pl->leaf_nodes[t]]; ++p) seen[p] = pl->y_finite_host[p];
     if (readable) {
@@ -3960,19 +4015,27 @@ static void fit_laplace(mra_plan* pl, int family, const double* z, const double*
             for (long p = 0; p < P; ++p) if (seen[p] && (aux[p] < z[p] || aux[p] <= 0.0)) invalid("binomial trials aux < z or aux <= 0 at an observed row", p);
         if (family == MRA_FAMILY_GAUSSIAN)
             for (long p = 0; p < P; ++p) if (seen[p] && aux[p] <= 0.0) invalid("Gaussian variance aux <= 0 at an observed row", p);
+        char what[64];
         for (long p = 0; p < P; ++p) {
             if (!seen[p]) continue;
             if (need_aux && !std::isfinite(aux[p])) invalid("aux is not finite at an observed row", p);
             if (off && !std::isfinite(off[p])) invalid("offset is not finite at an observed row", p);
-            if (x0 && !std::isfinite(x0[p])) invalid("x0 is not finite at an observed row", p);
+            if (x0 && !std::isfinite(x0[p])) { snprintf(what, sizeof what, "%s is not finite at an observed row", x0_name); invalid(what, p); }
         }
     }
     if (max_iter < 1) invalid("max_iter < 1", -1);
     if (!(tol > 0.0)) invalid("tol must be greater than 0", -1);
     if (!readable) invalid(!z || !info ? "z or info is NULL" : "aux is NULL (only the Poisson family reads none)", -1);
+    // (mra_plan_fit_laplace's own last refusal; mra_plan_fit_laplace_trend never gets here with a sharded plan: retained_check_plan refuses it first)
     if (pl->reduce_level >= 0 || pl->comm || pl->n_ranks > 1) invalid("sharded plans cannot iterate (the mean of a pass lives on its rank)", -1);
-    if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
+}
 
+// The data of a fit by padded row (z: NaN where the plan does not observe) and its start into the plan's Laplace buffers; the noise
+// vector goes on.  -> the constants of -2 log p that do not depend on x.
+static double laplace_upload(mra_plan* pl, int family, const double* z, const double* aux, const double* off, const double* x0,
+                             const std::vector<unsigned char>& seen) {
+    const long P = pl->P;
+    const bool need_aux = family != MRA_FAMILY_POISSON;
     // the data by padded row (z: NaN where the plan does not observe), the start, and the constants of -2 log p that do not depend on x
     std::vector<double> zh((size_t)P, std::nan("")), ah((size_t)P, 1.0), oh((size_t)P, 0.0), xh((size_t)P, 0.0);
     // (chunks of 65536 rows over a few host threads; a chunk's sum is compensated (Kahan) - a plain serial sum of 26 000 constants loses
@@ -4017,6 +4080,17 @@ static void fit_laplace(mra_plan* pl, int family, const double* z, const double*
     if (!pl->noise_on) set_leaf_diag_add(pl, 0.0);      // the noise vector goes on as in mra_plan_set_noise; every pass below rewrites it
     pl->noise_on = true;
     pl->noise_host.assign((size_t)P, 0.0);
+    return konst;
+}
+
+static void fit_laplace(mra_plan* pl, int family, const double* z, const double* aux, const double* off, const double* x0, int max_iter,
+                        double tol, double* info) {
+    std::vector<unsigned char> seen;
+    laplace_check(pl, "mra_plan_fit_laplace", "x0", family, z, aux, off, x0, max_iter, tol, info, seen);
+    if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
+    const double konst = laplace_upload(pl, family, z, aux, off, x0, seen);
+    mra_plan::Laplace& L = pl->lap;
+    const size_t bytes = (size_t)pl->P * sizeof(double);
 
     double res[MRA_LAPLACE_NRES] = {0, 0, 0, 0, 0};
     int passes = 0;
@@ -4044,6 +4118,87 @@ static void fit_laplace(mra_plan* pl, int family, const double* z, const double*
     info[2] = -2.0 * res[4] + konst;
     info[3] = res[2]; info[4] = res[3];
     info[5] = passes; info[6] = res[0]; info[7] = converged ? 1.0 : 0.0;
+}
+
+// ---- Laplace fit with a regression trend (mra_plan_fit_laplace_trend) ------------------------------------------
+// eta = X beta + x + offset with a flat prior on beta; the iteration runs on e = X beta + x at the observed rows (lap.x).  Every
+// iteration: the linearisation at e (k_laplace_linearise, as mra_plan_fit_laplace), one likelihood pass for the factors of this r
+// (ensure_factors), the GLS step of mra_trend_fit on [t | X] with the kriging means of the columns (trend_gls), and one reduction that
+// forms e^ = m_t + (X - m_X)^T beta^, makes it the iterate and returns the step and the sums (k_laplace_trend_part, k_laplace_sum).
+// No predict pass: nothing in the iteration reads a variance.  What the caller reads back from its own last mra_run stays.
+static void fit_laplace_trend(mra_plan* pl, int family, const double* z, const double* aux, const double* off, const double* e0, int max_iter,
+                              double tol, double* beta, double* cov_beta, double* info) {
+    const char* who = "mra_plan_fit_laplace_trend";
+    retained_check_plan(pl, who, 0, 0, "cannot fit a trend (C(S, o) is evaluated on the device)", "cannot fit a trend", true);
+    mra_plan::Trend& T = pl->trend;
+    if (T.p == 0) throw MraError(MRA_ERR_STATE, "mra_plan_fit_laplace_trend needs mra_plan_set_trend first");
+    std::vector<unsigned char> seen;
+    laplace_check(pl, who, "e0", family, z, aux, off, e0, max_iter, tol, info, seen);
+    if (!beta) throw MraError(MRA_ERR_INVALID, "mra_plan_fit_laplace_trend: beta is NULL");
+    if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
+    if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
+    const long P = pl->P;
+    const int p = T.p, n = p + 1;
+    constexpr int LD = MRA_TREND_MAX + 1;
+    // what can still be refused (the solver's buffers, (1 + p) P doubles for the means) before the plan changes, as in trend_fit
+    HIP_TRY(mraSetDevice(pl->device));
+    mra_solver_build(pl);
+    if (T.m.n != (size_t)n * P) T.m.alloc((size_t)n * P);
+    if (!T.coef.n) T.coef.alloc((size_t)LD + (size_t)LD * LD);
+    mra_laplace_reserve(pl);
+    const double konst = laplace_upload(pl, family, z, aux, off, e0, seen);
+    mra_plan::Laplace& L = pl->lap;
+    mra_plan::Solver& S = pl->slv;
+    const size_t bytes = (size_t)P * sizeof(double);
+    trend_ms_reset(pl);
+    TrendMsSink sink(pl);                    // the upload of beta and the tail are timed into trend.ms as the sweeps are
+
+    double res[MRA_LAPLACE_NRES] = {0, 0, 0, 0, 0};
+    int passes = 0;
+    bool converged = false;
+    TrendGls R;
+    // the kernel statistics describe the whole call: every pass opens with its own cleared (open_pass), so they are summed here.
+    // harvest: the stream has been synchronised, so the events recorded since the last pass have their times
+    mra_plan::KStat total[KF_COUNT];
+    for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = mra_plan::KStat();
+    auto fold_stats = [&](bool harvest) {
+        if (harvest) harvest_kernel_events(pl);
+        for (int k = 0; k < KF_COUNT; ++k) {
+            const mra_plan::KStat& s = pl->kstat[k];
+            total[k].launches += s.launches; total[k].ms += s.ms; total[k].flops += s.flops; total[k].flops_exec += s.flops_exec; total[k].bytes += s.bytes;
+            pl->kstat[k] = mra_plan::KStat();
+        }
+    };
+    auto publish_stats = [&] { fold_stats(true); for (int k = 0; k < KF_COUNT; ++k) pl->kstat[k] = total[k]; };
+    auto mirror = [&] { return mraMemcpy(pl->noise_host.data(), pl->noise.p, bytes, hipMemcpyDeviceToHost); };
+    try {
+        for (int it = 0; it < max_iter && !converged; ++it) {
+            { KTimer kt(pl, KF_MISC, 0); mra_laplace_linearise(pl, family, L.x.p); }
+            fold_stats(false);               // (its event is harvested by the pass that follows)
+            S.valid = false;                 // only the noise changed: the prior and its residual are reused as in any pass (options 24, 25)
+            ensure_factors(pl);
+            ++passes;
+            trend_gls(pl, who, true, beta, cov_beta, R);
+            mra_sites_timed(pl, 4, [&] { HIP_TRY(hipMemcpyAsync(T.coef.p, R.bt.data(), (size_t)LD * sizeof(double), hipMemcpyHostToDevice, pl->stream)); });
+            mra_sites_timed(pl, 3, [&] { KTimer kt(pl, KF_MISC, 0); mra_laplace_trend_reduce(pl, family, pl->host_res_dev + MRA_HOST_RES_LAPLACE); });
+            HIP_TRY(hipStreamSynchronize(pl->stream));
+            HIP_TRY(hipGetLastError());
+            std::copy(pl->host_res + MRA_HOST_RES_LAPLACE, pl->host_res + MRA_HOST_RES_LAPLACE + MRA_LAPLACE_NRES, res);
+            fold_stats(true);
+            if (!std::isfinite(res[0])) break;               // the iterate has left the doubles: not converged, as in mra_plan_fit_laplace
+            converged = res[0] <= tol * std::max(1.0, res[1]);
+        }
+    } catch (...) { hipStreamSynchronize(pl->stream); publish_stats(); mirror(); throw; }
+    publish_stats();
+    HIP_TRY(mirror());
+    info[0] = S.pass_d; info[1] = R.resid;
+    info[2] = -2.0 * res[4] + konst;
+    info[3] = res[2]; info[4] = res[3];
+    info[5] = passes; info[6] = res[0]; info[7] = converged ? 1.0 : 0.0;
+    info[8] = R.logdet;
+    info[9] = info[0] + info[1] + info[2] + info[3] - info[4];
+    info[10] = info[9] + info[8] - (double)p * std::log(6.283185307179586);
+    info[11] = (double)observed_rows(pl);
 }
 
 static void get_predict(mra_plan* pl, double* mean, double* var) {
@@ -4433,6 +4588,14 @@ int mra_sample(mra_plan* pl, uint32_t flags, int64_t n_samples, uint64_t seed, i
 
 int mra_solve(mra_plan* pl, uint32_t flags, int64_t n_cols, const double* Y, double* mean, double* quad) {
     return guarded(pl, [&] { require(pl, "mra_solve: plan is NULL"); solve_all(pl, flags, n_cols, Y, mean, quad); return MRA_OK; });
+}
+int mra_plan_fit_laplace_trend(mra_plan* pl, int family, const double* z_perm, const double* aux_perm, const double* offset_perm,
+                               const double* e0_perm, int max_iter, double tol, double* beta, double* cov_beta, double* info) {
+    return guarded(pl, [&] {
+        require(pl, "mra_plan_fit_laplace_trend: plan is NULL");
+        fit_laplace_trend(pl, family, z_perm, aux_perm, offset_perm, e0_perm, max_iter, tol, beta, cov_beta, info);
+        return MRA_OK;
+    });
 }
 int mra_plan_set_trend(mra_plan* pl, int32_t p, const double* X_perm) {
     return guarded(pl, [&] { require(pl, "mra_plan_set_trend: plan is NULL"); set_trend(pl, p, X_perm); return MRA_OK; });

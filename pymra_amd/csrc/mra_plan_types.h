@@ -844,6 +844,9 @@ constexpr int MRA_HOST_RES_DOUBLES = 16, MRA_HOST_RES_LAPLACE = 8;      // the p
 void mra_laplace_reserve(mra_plan* pl);
 void mra_laplace_linearise(mra_plan* pl, int family, const double* x_in);
 void mra_laplace_reduce(mra_plan* pl, int family, double* res);
+// mra_plan_fit_laplace_trend: the same five results with x^ := e^ = m_t + (X - m_X)^T beta^ from trend.m, trend.X and the beta at the
+// head of trend.coef; e^ replaces lap.x at the observed rows (k_laplace_trend_part, k_laplace_sum)
+void mra_laplace_trend_reduce(mra_plan* pl, int family, double* res);
 void mra_metric_apply(mra_plan* pl);                  // X = A Xraw by row (k_metric_apply), on the plan's stream
 // with MRA_OPT_KERNEL_TIMING: `work` between two events on pl->stream, the time added to sit.ms[which] (sit.ms_sink[which] when set; one synchronisation each: a measuring mode)
 void mra_sites_timed(mra_plan* pl, int which, const std::function<void()>& work);

@@ -47,6 +47,8 @@ MRA_OPT_PRIOR_REUSE = 24
 MRA_OPT_RESID_REUSE = 25
 MRA_FAMILY_GAUSSIAN, MRA_FAMILY_POISSON, MRA_FAMILY_BINOMIAL = 0, 1, 2
 LAPLACE_FAMILIES = {"gaussian": MRA_FAMILY_GAUSSIAN, "poisson": MRA_FAMILY_POISSON, "binomial": MRA_FAMILY_BINOMIAL}
+# info[8..11] of mra_plan_fit_laplace_trend, behind the eight of LAPLACE_INFO
+LAPLACE_TREND_INFO = ("logdetA", "profile", "reml", "n_obs")
 LAPLACE_INFO = ("d", "u", "neg2logp", "sum_log_D", "sum_D_res2", "passes", "step", "converged")      # info[8] of mra_plan_fit_laplace
 MRA_SAMPLE_CONDITIONAL = 1
 MRA_COV_POSTERIOR = 1
@@ -77,7 +79,7 @@ ERR_NAMES = {-1: "MRA_ERR_INVALID", -2: "MRA_ERR_HIP", -3: "MRA_ERR_NOT_SPD", -4
 # every symbol include/mra_hip.h declares (tests check that the library exports all of them)
 EXPORTS = [
     "mra_device_count", "mra_release_cached_memory", "mra_plan_create", "mra_plan_destroy", "mra_plan_set_locs", "mra_plan_set_obs",
-    "mra_plan_set_noise", "mra_plan_set_noise_rows", "mra_plan_fit_laplace", "mra_plan_set_metric", "mra_plan_set_trend", "mra_trend_fit",
+    "mra_plan_set_noise", "mra_plan_set_noise_rows", "mra_plan_fit_laplace", "mra_plan_fit_laplace_trend", "mra_plan_set_metric", "mra_plan_set_trend", "mra_trend_fit",
     "mra_plan_set_kernel", "mra_plan_set_locs_rows", "mra_plan_set_obs_rows", "mra_get_predict_rows", "mra_get_predict_rows_sd", "mra_eval_kernel", "mra_plan_set_cov_block", "mra_run", "mra_get_likelihood", "mra_get_predict",
     "mra_sample_slots", "mra_sample", "mra_solve", "mra_cov_apply", "mra_predict_sites", "mra_sites_cov", "mra_sample_sites_slots", "mra_sample_sites", "mra_cv", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
     "mra_get_kernel_stats", "mra_get_kernel_work", "mra_get_route", "mra_device_synchronize", "mra_plan_info", "mra_comm_unique_id", "mra_comm_init",
@@ -137,6 +139,7 @@ def load_library():
         "mra_plan_set_metric": (C.c_int, [vp, vp]),
         "mra_plan_set_noise_rows": (C.c_int, [vp, vp, vp]),
         "mra_plan_fit_laplace": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, dbl, vp]),
+        "mra_plan_fit_laplace_trend": (C.c_int, [vp, C.c_int, vp, vp, vp, vp, C.c_int, dbl, vp, vp, vp]),
         "mra_plan_set_locs_rows": (C.c_int, [vp, vp, vp]),
         "mra_plan_set_obs_rows": (C.c_int, [vp, vp, vp, vp, dbl]),
         "mra_get_predict_rows": (C.c_int, [vp, vp, vp, i64, vp, vp]),
@@ -385,6 +388,32 @@ class HipPlan:
         res["passes"], res["converged"] = int(res["passes"]), bool(res["converged"])
         res["info"] = info
         res["lik"] = info[0] + info[1] + info[2] + info[3] - info[4]
+        return res
+
+    def fit_laplace_trend(self, family, z, aux=None, offset=None, e0=None, max_iter=50, tol=1e-10):
+        """Non-Gaussian data with a regression trend (include/mra_hip.h, mra_plan_fit_laplace_trend): eta = X beta + x + offset with
+        the X of ``set_trend`` and a flat prior on beta; Newton / IRLS on the device for e = X beta + x, one likelihood pass and one
+        GLS step per iteration.  z, aux, offset as in ``fit_laplace``; e0: the caller's N values of the start of e (None: the
+        data-based start).  -> dict with ``fit_laplace``'s keys (``u`` is G_tt - b^T beta^, ``lik`` the profile value) plus beta,
+        cov_beta, logdetA, profile, reml (beta integrated out) and n_obs.  Afterwards the plan holds y = t and noise = 1 / D of the
+        last pass with the factors valid: ``trend_fit(predict=True)`` gives the mean and variance of e, the calls on the retained
+        factors serve the Laplace posterior; likelihood() / predict() are unchanged."""
+        fam = LAPLACE_FAMILIES.get(family, family) if isinstance(family, str) else family
+        if isinstance(fam, str):
+            raise ValueError("family must be one of %s" % sorted(LAPLACE_FAMILIES))
+        full = lambda a: None if a is None else (np.full(self.topo.N, float(a)) if np.ndim(a) == 0 else a)
+        zp, ap, op, ep = (self._padded(z, "z"), self._padded(full(aux), "aux"), self._padded(full(offset), "offset"), self._padded(e0, "e0"))
+        p = int(getattr(self, "_trend_p", 0))
+        beta, cov = np.zeros(max(p, 1)), np.zeros((max(p, 1), max(p, 1)))
+        info = np.zeros(12)
+        opt = lambda a: None if a is None else _ptr(a)
+        self._check(self.lib.mra_plan_fit_laplace_trend(self._h, int(fam), opt(zp), opt(ap), opt(op), opt(ep), int(max_iter), float(tol),
+                                                        _ptr(beta), _ptr(cov), _ptr(info)))
+        res = dict(zip(LAPLACE_INFO + LAPLACE_TREND_INFO, info.tolist()))
+        res["passes"], res["converged"], res["n_obs"] = int(res["passes"]), bool(res["converged"]), int(res["n_obs"])
+        res["info"] = info
+        res["lik"] = res["profile"]
+        res["beta"], res["cov_beta"] = beta[:p].copy(), cov[:p, :p].copy()
         return res
 
     def set_kernel(self, kind, l, sig=1.0, scale=1.0, circular=False):
