@@ -467,6 +467,36 @@ int mra_sample_sites(mra_plan *plan, uint32_t flags, int64_t n_sites, const doub
 #define MRA_CV_LEAF 1u   /* groups = the observed rows of each leaf; 0: every observed row its own group */
 int mra_cv(mra_plan *plan, uint32_t flags, double *mean_perm, double *var_perm, double *lpd_perm, double *group_lpd, double *info);
 
+/* mra_cv for a plan with a regression trend (mra_plan_set_trend): the model is y = X beta + x + eps with a flat
+ * prior on beta, as in mra_trend_fit.  With A = X^T K^-1 X = L_A L_A^T, m_y / m_X the kriging means of y and of the columns of X,
+ * h_p = X_p - m_X(p), w_p = L_A^-1 h_p, rho~_p = y_p - m_y(p) - h_p^T beta^ (y minus the universal-kriging mean) and W_G the rows w_p^T:
+ * P = K^-1 - K^-1 X A^-1 X^T K^-1 has P y = D^-1 rho~ and P[G, G] = D_G^-1 (N_G - W_G W_G^T) D_G^-1.
+ * flags: MRA_CV_LEAF as in mra_cv, and
+ *   MRA_CV_TREND_REFIT - beta is estimated again without the left-out group (universal-kriging cross-validation): mra_cv's formulas
+ *     with rho~ for rho and N~_G = N_G - W_G W_G^T for N_G; by row h~_p = (v_p + |w_p|^2) / r_p, mu_p = y_p - rho~_p / (1 - h~_p),
+ *     S_pp = r_p / (1 - h~_p).  X without the group's rows must keep full column rank, otherwise N~_G is singular;
+ *   without it the beta^ of the full fit is plugged in: rho~ with the plain N_G, which is mra_cv on y - X beta^ reported on the scale
+ *     of y.
+ * The outputs are mra_cv's.  info[12]: 0 .. 4 as mra_cv; 5: the largest leverage the mode divides by (h~ with MRA_CV_TREND_REFIT, else
+ * v / r); 6: tr K^-1 = sum (1 - v_p / r_p) / r_p; 7: |P y|^2 = sum (rho~_p / r_p)^2; 8: tr P = sum (1 - (v_p + |w_p|^2) / r_p) / r_p;
+ * 9: p; 10: [6] - [7], the exact derivative of the profile -2 log L (mra_trend_fit's info[3]) by a nugget added to every observed row;
+ * 11: [8] - [7], that of the REML criterion (info[4]).  The sums are folded over a fixed number of partial results in a fixed order:
+ * the same inputs give the same bits, whatever MRA_OPT_SITES_CHUNK_BYTES is.
+ * The call first fits the trend on the plan's own y as mra_trend_fit does, with the backward sweeps but without the predict pass of
+ * MRA_TREND_PREDICT (1 + p right-hand sides in blocks of 16; no factorisation when the factors stand), then runs mra_cv's batches
+ * with two more kernels.  Afterwards y, the options, what mra_get_likelihood / mra_get_predict return and what mra_trend_fit and mra_cv
+ * return are as before.  After mra_plan_fit_laplace_trend the call scores what the plan holds: t, 1 / D and X.
+ * Refusals: mra_cv's, in its order, with MRA_ERR_STATE when no trend is set right after the plan's own checks; on MRA_HOST_DRYRUN plans
+ * all of these are reached, then MRA_ERR_STATE (the plan cannot run).  The trend fit's MRA_ERR_NOT_SPD ("trend columns are linearly
+ * dependent at the observed rows") comes before any cross-validation kernel is launched.  With MRA_CV_TREND_REFIT a pivot of N~_G that
+ * is <= 0 or NaN, or 1 - h~_p <= 0 or NaN, gives MRA_ERR_NOT_SPD naming the leaf or the padded row: the group may carry the only
+ * information on a covariate.  That test is best effort - a rank loss in exact arithmetic can leave a tiny positive pivot in floating
+ * point, and then the results of that group are meaningless; info[5] close to 1 is the sign to look for.
+ * Memory beyond mra_cv's: (1 + p) P doubles for the means, P for |w|^2, and 16 (p rounded up to 4) doubles per tile of a batch (counted
+ * against MRA_OPT_SITES_CHUNK_BYTES).  mra_get_buffer(15) gives the stream milliseconds of the call.  Blocking. */
+#define MRA_CV_TREND_REFIT 2u        /* with MRA_CV_LEAF = 1u; without it beta^ is held fixed */
+int mra_cv_trend(mra_plan *plan, uint32_t flags, double *mean_perm, double *var_perm, double *lpd_perm, double *group_lpd, double *info /* 12 */);
+
 /* Diagnostics for tests (the reference exposes these as attributes of Node objects):
  * what = 0: whitened basis W (P x ldw, row-major) ; 1: per-node log-det terms (n_nodes);
  * 7: stream milliseconds of the last mra_predict_sites, measured while MRA_OPT_KERNEL_TIMING is on (7 values: the basis, leaf, chain
@@ -486,6 +516,8 @@ int mra_cv(mra_plan *plan, uint32_t flags, double *mean_perm, double *var_perm, 
  * of [y | X], of the solver's sweeps of all blocks with the diagonal tiles of G and the archive copies, of k_solve_quad_cross with its
  * fold, of k_trend_rows, and of the uploads and downloads; then the bytes of the leaves' Ut (a forward sweep reads them once per
  * block) and of one block's archive panel (written once, read once);
+ * 15: stream milliseconds of the last mra_cv_trend under MRA_OPT_KERNEL_TIMING (12 values: the nine of 12, then the trend's sweeps
+ * with their staging and transfers, k_cv_trend, k_cv_downdate);
  * copies min(capacity, available) doubles into out, returns the available count in *n_avail.
  * (W after a likelihood-only run is complete only with MRA_OPT_LIK_ROWS off: by default such a run computes W at the rows a
  * likelihood needs - the observed rows, and the knots on the level-by-level path - and leaves the others as they were.) */

@@ -341,7 +341,7 @@ class MRATree(object):
         mean[t.perm[rows], :] = m[:, rows].T
         return mean, quad
 
-    def crossValidate(self, kind="loo"):
+    def crossValidate(self, kind="loo", trend=None):
         """Cross-validation of the fitted model without a refit, from the factors this tree's pass left on the device: every observed
         location left out on its own (kind="loo") or the observed locations of each leaf left out together (kind="leaf": spatial block
         cross-validation on the tree's own partition).  -> CVResult, per-row fields in the caller's row order and NaN where nothing
@@ -349,13 +349,32 @@ class MRATree(object):
         lpd = the marginal log predictive density; leaf_lpd {leaf node: log predictive density of its group (kind="leaf": joint)};
         score = their sum, the CV log score; n rows scored; leverage_max = max v / R (float64 loses about eps / (1 - leverage)^2);
         dlik_dR = the exact derivative of getLikelihood() with respect to a nugget added to every observed row.  getLikelihood() and
-        predict() are unchanged afterwards."""
-        self._no_trend("crossValidate")
+        predict() are unchanged afterwards.
+        On a tree with a trend (setTrend) ``trend`` chooses what leaving a group out means: "refit" - beta is estimated again
+        without the group (universal-kriging cross-validation; X without the group must keep full column rank), "fixed" - the beta^ of
+        the full fit is plugged in.  The result also has trend (the choice), dlik_dR_reml (the derivative of
+        getLikelihood(reml=True)), and leverage_max is the largest (v + |w|^2) / R under "refit".  A tree without a trend takes
+        trend=None only (its result has trend = None and dlik_dR_reml = None)."""
+        if self.trend is None and trend is not None:
+            raise ValueError("trend=%r given, but this tree has no trend (setTrend)" % (trend,))
+        if self.trend is not None and trend is None:
+            raise NotImplementedError('crossValidate on a tree with a regression trend needs trend="refit" (beta estimated again without '
+                                      'each group) or trend="fixed" (the full fit\'s beta plugged in)')
+        if trend not in (None, "refit", "fixed"):
+            raise ValueError('trend must be "refit" or "fixed"')
+        if self.trend is not None and self._trend_y is not None:
+            raise NotImplementedError("crossValidate after fitLaplace(X=X) is not supported: the trend of this tree was fitted to the "
+                                      "pseudo-observations of a Laplace fit (HipPlan.cv_trend scores those)")
         if kind not in ("loo", "leaf"):
             raise ValueError('kind must be "loo" or "leaf"')
         if self.kernel is None:
             raise NotImplementedError("crossValidate needs a device kernel: trees built from an opaque callable or a dense matrix cannot cross-validate")
-        mean, var, lpd, group, info = self.plan.cv(leaf=(kind == "leaf"))
+        if trend is None:
+            mean, var, lpd, group, info = self.plan.cv(leaf=(kind == "leaf"))
+            dlik, dlik_reml = float(info[6] - info[7]), None
+        else:
+            mean, var, lpd, group, info = self.plan.cv_trend(leaf=(kind == "leaf"), refit=(trend == "refit"))
+            dlik, dlik_reml = float(info[10]), float(info[11])
         yp = self.plan.buffer(11)
         t = self.topology
         rows = t.perm >= 0
@@ -369,7 +388,7 @@ class MRATree(object):
         nodes = np.nonzero(~np.isnan(group))[0]
         return CVResult(kind=kind, mean=by_caller(mean), sd=by_caller(sd), z=by_caller((yp - mean) / sd), lpd=by_caller(lpd),
                         leaf_lpd={int(i): float(group[i]) for i in nodes}, score=float(info[2]), n=int(info[0]),
-                        leverage_max=float(info[5]), dlik_dR=float(info[6] - info[7]))
+                        leverage_max=float(info[5]), dlik_dR=dlik, trend=trend, dlik_dR_reml=dlik_reml)
 
     def _sites(self, sites):
         """The caller's sites, checked, in covariance coordinates: (lon, lat) degrees -> xyz under metric="chordal", else as given

@@ -1,7 +1,7 @@
 // mra_launch_sites.hip - mra_predict_sites: descriptors, work buffers and the launches of one chunk of site tiles
 // over the state a likelihood pass left in the plan, and the Gram launch of mra_sites_cov (section 13) over the same buffers.  A
 // translation unit of its own: the kernels of the pass keep their object code.  The inert, leaf Gram, zeta and draw launches of
-// mra_sample_sites (section 14) run over the same buffers, a batch of whole leaves at a time; so do the launches of mra_cv (section 18).
+// mra_sample_sites (section 14) run over the same buffers, a batch of whole leaves at a time; so do the launches of mra_cv (section 18) and mra_cv_trend (section 22).
 #define MRA_KERNELS_TEMPLATES_ONLY
 #include "mra_site_kernels.h"
 
@@ -300,5 +300,58 @@ void mra_cv_reduce(mra_plan* pl, bool by_leaf) {
             hipLaunchKernelGGL(k_cv_leaf_sum, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, pl->stream, T.cvleaf.p, T.cvleaf_row.p, nl, mra_cv_out(pl).lpd, T.cvgl.p);
         hipLaunchKernelGGL(k_cv_part, dim3(CV_BLOCKS), dim3(256), 0, pl->stream, mra_cv_rows(pl), mra_cv_out(pl), (long)pl->P, T.cvgl.p, pl->n_nodes, T.cvpart.p);
         hipLaunchKernelGGL(k_cv_sum, dim3(1), dim3(64 * MRA_CV_NRES), 0, pl->stream, T.cvpart.p, CV_BLOCKS, T.cvres.p);
+    });
+}
+
+// ---- mra_cv_trend --------------------------------------------------------------------------------------------------
+// timing entries of a call (sit.cvt_ms through the sink): mra_cv's nine, then 9 the trend's sweeps, 10 k_cv_trend, 11 k_cv_downdate
+static int cv_trend_qn(const mra_plan* pl) { return (pl->trend.p + 3) & ~3; }
+
+size_t mra_cv_trend_tile_bytes(const mra_plan* pl) { return (size_t)cv_trend_qn(pl) * 16 * sizeof(double); }
+
+void mra_cv_trend_reserve(mra_plan* pl, long n) {
+    mra_plan::Sites& T = pl->sit;
+    const size_t P = (size_t)pl->P, need = (size_t)n * cv_trend_qn(pl) * 16;
+    if (T.cvw.n < need) T.cvw.alloc(need);
+    if (T.cvwsq.n != P) T.cvwsq.alloc(P);
+    if (!T.cvtpart.n) { T.cvtpart.alloc((size_t)CV_BLOCKS * MRA_CVT_NRES); T.cvtres.alloc(MRA_CVT_NRES); }
+    HIP_TRY(hipMemsetAsync(T.cvwsq.p, 0, P * sizeof(double), pl->stream));
+}
+
+static void check_cv_trend_batch(const mra_plan* pl, long n) {
+    const mra_plan::Sites& T = pl->sit;
+    const mra_plan::Trend& R = pl->trend;
+    check_cv_batch(pl, n);
+    if (R.p < 1 || R.p > MRA_TREND_MAX || R.X.n != (size_t)R.p * pl->P || R.m.n != (size_t)(R.p + 1) * pl->P || !R.coef.n ||
+        (size_t)n * cv_trend_qn(pl) * 16 > T.cvw.n || T.cvwsq.n != (size_t)pl->P)
+        throw MraError(MRA_ERR_STATE, "mra_cv_trend: the trend's means or the batch's W are not allocated");
+}
+
+void mra_cv_trend_rows(mra_plan* pl, long n, bool add_v) {
+    check_cv_trend_batch(pl, n);
+    mra_plan::Sites& T = pl->sit;
+    const mra_plan::Trend& R = pl->trend;
+    timed(pl, 10, [&] {
+        hipLaunchKernelGGL(k_cv_trend, dim3((unsigned)n), dim3(64), 0, pl->stream, T.sslot.p, R.X.p, R.m.p + pl->P, (long)pl->P, R.p, R.coef.p,
+                           R.coef.p + MRA_TREND_MAX + 1, add_v ? 1 : 0, T.mean.p, T.var.p, T.cvw.p, T.cvwsq.p);
+    });
+}
+
+void mra_cv_trend_downdate(mra_plan* pl, long n, int nt_max) {
+    check_cv_trend_batch(pl, n);
+    if (nt_max < 1 || nt_max > 65535) throw MraError(MRA_ERR_STATE, "mra_cv_trend: a leaf of the batch has no tile or too many");
+    mra_plan::Sites& T = pl->sit;
+    timed(pl, 11, [&] {
+        hipLaunchKernelGGL(k_cv_downdate, dim3((unsigned)n, (unsigned)nt_max), dim3(64), 0, pl->stream, T.dtile.p, T.cvw.p, cv_trend_qn(pl), T.G.p);
+    });
+}
+
+void mra_cv_trend_reduce(mra_plan* pl, bool h_has_w) {
+    mra_plan::Sites& T = pl->sit;
+    if (T.cvrow.n != 5 * (size_t)pl->P || T.cvwsq.n != (size_t)pl->P || !T.cvtpart.n) throw MraError(MRA_ERR_STATE, "mra_cv_trend: the row results are not allocated");
+    timed(pl, 6, [&] {
+        hipLaunchKernelGGL(k_cv_trend_part, dim3(CV_BLOCKS), dim3(256), 0, pl->stream, mra_cv_rows(pl), mra_cv_out(pl), T.cvwsq.p, h_has_w ? 1 : 0, (long)pl->P,
+                           T.cvtpart.p);
+        hipLaunchKernelGGL(k_cv_trend_sum, dim3(1), dim3(64 * MRA_CVT_NRES), 0, pl->stream, T.cvtpart.p, CV_BLOCKS, T.cvtres.p);
     });
 }

@@ -3532,14 +3532,43 @@ static void sample_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const doub
 // The sites are the plan's own observed rows, each in its own leaf: batches of whole leaves as sample_sites_all, the four site kernels
 // with the plan's y as the one column, then the leave-one-out step or, by leaf, N_G, its Cholesky factor and the solves.  The per-row
 // results are scattered by padded row on the device and reduced there after the last batch, so nothing depends on the batches.
-static void cv_all(mra_plan* pl, uint32_t flags, double* mean, double* var, double* lpd, double* group_lpd, double* info) {
-    retained_check_plan(pl, "mra_cv", flags, MRA_CV_LEAF, "cannot cross-validate (C(s, s) is evaluated on the device)", "cannot cross-validate");
-    if (!info) throw MraError(MRA_ERR_INVALID, "mra_cv: info is NULL");
+// The trend fit of mra_cv_trend, on the plan's own y and on factors that stand: the GLS step with the backward sweeps (the kriging means
+// of [y | X] into trend.m), beta^ and L_A^-1 into trend.coef.  No predict pass: the variance mra_trend_fit(MRA_TREND_PREDICT) keeps is
+// neither read nor touched, nor are that call's times (the sweeps' go into entry 9 of the call's own).
+static void cv_trend_fit(mra_plan* pl) {
+    mra_plan::Trend& T = pl->trend;
+    const size_t P = (size_t)pl->P;
+    constexpr int LD = MRA_TREND_MAX + 1;
+    if (T.m.n != (size_t)(T.p + 1) * P) T.m.alloc((size_t)(T.p + 1) * P);
+    if (!T.coef.n) T.coef.alloc((size_t)LD + (size_t)LD * LD);
+    double keep_ms[7], beta[LD];
+    std::copy(T.ms, T.ms + 7, keep_ms);
+    for (double& v : T.ms) v = 0.0;
+    struct PutBack { double* to; const double* from; double* sum; ~PutBack() { *sum += to[0] + to[1] + to[2] + to[4]; std::copy(from, from + 7, to); } }
+        put_back{T.ms, keep_ms, (pl->sit.ms_sink ? pl->sit.ms_sink : pl->sit.ms) + 9};
+    TrendGls R;
+    trend_gls(pl, "mra_cv_trend", true, beta, nullptr, R);
+    mra_sites_timed(pl, 7, [&] {
+        HIP_TRY(hipMemcpyAsync(T.coef.p, R.bt.data(), (size_t)LD * sizeof(double), hipMemcpyHostToDevice, pl->stream));
+        HIP_TRY(hipMemcpyAsync(T.coef.p + LD, R.Li.data(), (size_t)LD * LD * sizeof(double), hipMemcpyHostToDevice, pl->stream));
+    });
+    HIP_TRY(hipStreamSynchronize(pl->stream));       // (R's host arrays are read by the copies)
+    HIP_TRY(hipGetLastError());
+}
+
+// trend (mra_cv_trend, section 22): the same call with the trend's GLS fit in front of the sweep of y, k_cv_trend behind the mean kernel
+// and, when beta is estimated again without each leaf, k_cv_downdate in front of the Cholesky; info has 12 entries.
+static void cv_all(mra_plan* pl, bool trend, uint32_t flags, double* mean, double* var, double* lpd, double* group_lpd, double* info) {
+    const char* who = trend ? "mra_cv_trend" : "mra_cv";
+    char m[240];
+    retained_check_plan(pl, who, flags, trend ? (MRA_CV_LEAF | MRA_CV_TREND_REFIT) : MRA_CV_LEAF, "cannot cross-validate (C(s, s) is evaluated on the device)",
+                        "cannot cross-validate", trend);
+    if (trend && pl->trend.p == 0) throw MraError(MRA_ERR_STATE, "mra_cv_trend needs mra_plan_set_trend first");
+    if (!info) { snprintf(m, sizeof m, "%s: info is NULL", who); throw MraError(MRA_ERR_INVALID, m); }
     if (pl->knots_pending) throw MraError(MRA_ERR_STATE, "knot rows not set");
-    const bool by_leaf = (flags & MRA_CV_LEAF) != 0;
+    const bool by_leaf = (flags & MRA_CV_LEAF) != 0, refit = trend && (flags & MRA_CV_TREND_REFIT) != 0;
     const long P = pl->P;
     const size_t nl = pl->leaf_nodes.size();
-    char m[200];
     // the observed rows, leaf by leaf in row order: site i is padded row rows[i]
     std::vector<int64_t> rows;
     std::vector<int> lslot;
@@ -3547,7 +3576,7 @@ static void cv_all(mra_plan* pl, uint32_t flags, double* mean, double* var, doub
         for (long p = pl->row0[pl->leaf_nodes[t]]; p < pl->row1[pl->leaf_nodes[t]]; ++p) {
             if (!pl->y_finite_host[p]) continue;
             if ((pl->noise_on ? pl->noise_host[(size_t)p] : pl->R) == 0.0) {
-                snprintf(m, sizeof m, "mra_cv: the noise variance is 0 at observed padded row %ld (the leave-out distributions divide by it)", p);
+                snprintf(m, sizeof m, "%s: the noise variance is 0 at observed padded row %ld (the leave-out distributions divide by it)", who, p);
                 throw MraError(MRA_ERR_INVALID, m);
             }
             rows.push_back(p); lslot.push_back((int)t);
@@ -3557,13 +3586,16 @@ static void cv_all(mra_plan* pl, uint32_t flags, double* mean, double* var, doub
         std::vector<int64_t> per_leaf(nl, 0);
         for (int64_t i = 0; i < n; ++i)
             if (++per_leaf[(size_t)lslot[(size_t)i]] == (int64_t)MRA_SAMPLE_SITES_LEAF_MAX + 1) {
-                snprintf(m, sizeof m, "mra_cv: leaf %d has more than MRA_SAMPLE_SITES_LEAF_MAX = %d observed rows (its block is dense, 128 MiB at the cap)",
-                         pl->leaf_nodes[(size_t)lslot[(size_t)i]], MRA_SAMPLE_SITES_LEAF_MAX);
+                snprintf(m, sizeof m, "%s: leaf %d has more than MRA_SAMPLE_SITES_LEAF_MAX = %d observed rows (its block is dense, 128 MiB at the cap)",
+                         who, pl->leaf_nodes[(size_t)lslot[(size_t)i]], MRA_SAMPLE_SITES_LEAF_MAX);
                 throw MraError(MRA_ERR_INVALID, m);
             }
     }
+    // (a dry-run plan reaches every refusal above; it cannot run)
+    if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run");
     const double nan = std::nan("");
-    for (int k = 0; k < 8; ++k) info[k] = 0.0;
+    for (int k = 0; k < (trend ? 12 : 8); ++k) info[k] = 0.0;
+    if (trend) info[9] = (double)pl->trend.p;
     for (double* o : {mean, var, lpd})
         if (o) std::fill(o, o + P, nan);
     if (group_lpd) std::fill(group_lpd, group_lpd + pl->n_nodes, nan);
@@ -3572,8 +3604,10 @@ static void cv_all(mra_plan* pl, uint32_t flags, double* mean, double* var, doub
     sites_ensure_state(pl);
     mra_plan::Solver& S = pl->slv;
     mra_plan::Sites& T = pl->sit;
-    for (double& v : T.cv_ms) v = 0.0;
-    SitesSink sink(T, T.cv_ms);
+    double* const ms = trend ? T.cvt_ms : T.cv_ms;
+    for (int k = 0; k < (trend ? 12 : 9); ++k) ms[k] = 0.0;
+    SitesSink sink(T, ms);
+    if (trend) cv_trend_fit(pl);
     std::vector<int64_t> slot;
     std::vector<int> tile_leaf;
     sites_tiles(lslot, n, nl, slot, tile_leaf);
@@ -3581,7 +3615,8 @@ static void cv_all(mra_plan* pl, uint32_t flags, double* mean, double* var, doub
     const long n_tiles = (long)tile_leaf.size();
     // batches of whole leaves: work arrays of the tiles + (by leaf) the leaf's block twice, N_G and X
     const size_t budget = T.chunk_bytes ? T.chunk_bytes : SITES_CHUNK_BYTES;
-    const size_t tile_bytes = mra_sites_tile_bytes(pl) + sizeof(SiteDrawTile) + 16 * (sizeof(long) + sizeof(int)) + 3 * 256 * sizeof(double);
+    const size_t tile_bytes = mra_sites_tile_bytes(pl) + sizeof(SiteDrawTile) + 16 * (sizeof(long) + sizeof(int)) + 3 * 256 * sizeof(double) +
+                              (trend ? mra_cv_trend_tile_bytes(pl) : 0);
     struct Batch { long t0, nt, n_leaves; size_t g; int nt_max; };
     std::vector<Batch> bat;
     {
@@ -3602,6 +3637,7 @@ static void cv_all(mra_plan* pl, uint32_t flags, double* mean, double* var, doub
     size_t cap_g = 0;
     for (const Batch& b : bat) { cap_t = std::max(cap_t, b.nt); cap_l = std::max(cap_l, b.n_leaves); cap_g = std::max(cap_g, b.g); }
     mra_cv_reserve(pl, cap_t, cap_g, cap_l);
+    if (trend) mra_cv_trend_reserve(pl, cap_t);
     HIP_TRY(hipMemsetAsync(T.derr.p, 0, sizeof(int), pl->stream));
     // beta (leaves' gb) and q (leaves' uy) of the plan's own observations: the solver's sweeps without its row step, once per call
     stage_columns(pl, pl->y.p, 1, S.yb.p, hipMemcpyDeviceToDevice);
@@ -3636,9 +3672,11 @@ static void cv_all(mra_plan* pl, uint32_t flags, double* mean, double* var, doub
         mra_sites_basis(pl, b.nt);
         mra_sites_var(pl, b.nt);
         mra_sites_mean(pl, b.nt, 1, 3);
+        if (trend) mra_cv_trend_rows(pl, b.nt, refit && !by_leaf);
         int e = 0;
         if (by_leaf) {
             mra_cv_gram(pl, b.nt, b.nt_max);
+            if (refit) mra_cv_trend_downdate(pl, b.nt, b.nt_max);
             mra_sites_timed(pl, 5, [&] { hipLaunchKernelGGL(k_panel_chol, dim3((unsigned)nlb), dim3(256), 0, pl->stream, T.dprob.p, T.dn.p, T.derr.p, 0); });
         } else {
             mra_cv_loo(pl, b.nt);
@@ -3647,22 +3685,34 @@ static void cv_all(mra_plan* pl, uint32_t flags, double* mean, double* var, doub
         HIP_TRY(hipMemcpyAsync(&e, T.derr.p, sizeof(int), hipMemcpyDeviceToHost, pl->stream));
         HIP_TRY(hipStreamSynchronize(pl->stream));
         HIP_TRY(hipGetLastError());
+        if (e && by_leaf && refit) {
+            snprintf(m, sizeof m, "mra_cv_trend: leaf %d: D - Sigma_post - W W^T over its observed rows is not positive definite (Cholesky pivot <= 0 or NaN; "
+                     "the leaf may carry the only information on a covariate; no jitter is added)", gr[(size_t)(e - 1)].node);
+            throw MraError(MRA_ERR_NOT_SPD, m);
+        }
         if (e && by_leaf) {
-            snprintf(m, sizeof m, "mra_cv: leaf %d: D - Sigma_post over its observed rows is not positive definite (Cholesky pivot <= 0 or NaN; no jitter is added)",
-                     gr[(size_t)(e - 1)].node);
+            snprintf(m, sizeof m, "%s: leaf %d: D - Sigma_post over its observed rows is not positive definite (Cholesky pivot <= 0 or NaN; no jitter is added)",
+                     who, gr[(size_t)(e - 1)].node);
+            throw MraError(MRA_ERR_NOT_SPD, m);
+        }
+        if (e && refit) {
+            snprintf(m, sizeof m, "mra_cv_trend: padded row %d: 1 - (v + |w|^2) / r <= 0 or NaN (the row may carry the only information on a covariate; "
+                     "no jitter is added)", e - 1);
             throw MraError(MRA_ERR_NOT_SPD, m);
         }
         if (e) {
-            snprintf(m, sizeof m, "mra_cv: padded row %d: 1 - v / r <= 0 or NaN (the posterior variance reaches the noise variance; no jitter is added)", e - 1);
+            snprintf(m, sizeof m, "%s: padded row %d: 1 - v / r <= 0 or NaN (the posterior variance reaches the noise variance; no jitter is added)", who, e - 1);
             throw MraError(MRA_ERR_NOT_SPD, m);
         }
         if (by_leaf) mra_cv_solve(pl, b.nt, nlb);
     }
     mra_cv_reduce(pl, by_leaf);
-    double res[MRA_CV_NRES];
+    if (trend) mra_cv_trend_reduce(pl, refit && !by_leaf);
+    double res[MRA_CV_NRES], rt[3] = {0.0, 0.0, 0.0};
     const CvOut O = mra_cv_out(pl);
     mra_sites_timed(pl, 8, [&] {
         HIP_TRY(hipMemcpyAsync(res, T.cvres.p, sizeof res, hipMemcpyDeviceToHost, pl->stream));
+        if (trend) HIP_TRY(hipMemcpyAsync(rt, T.cvtres.p, sizeof rt, hipMemcpyDeviceToHost, pl->stream));
         if (mean) HIP_TRY(hipMemcpyAsync(mean, O.mean, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
         if (var) HIP_TRY(hipMemcpyAsync(var, O.var, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
         if (lpd) HIP_TRY(hipMemcpyAsync(lpd, O.lpd, (size_t)P * sizeof(double), hipMemcpyDeviceToHost, pl->stream));
@@ -3676,6 +3726,11 @@ static void cv_all(mra_plan* pl, uint32_t flags, double* mean, double* var, doub
     info[1] = by_leaf ? (double)n_groups : res[0];
     info[2] = by_leaf ? res[6] : res[1];      // every row its own group: the groups' joint densities are the rows' marginal ones
     info[3] = res[1]; info[4] = res[2]; info[5] = res[3]; info[6] = res[4]; info[7] = res[5];
+    if (trend) {
+        if (refit) info[5] = rt[2];
+        info[6] = rt[0]; info[8] = rt[1];
+        info[10] = info[6] - info[7]; info[11] = info[8] - info[7];
+    }
 }
 
 // ---- caller-order variants: the permutation work of an end-to-end MRATree(...) call done inside the library -----------------
@@ -4635,7 +4690,10 @@ int mra_sample_sites(mra_plan* pl, uint32_t flags, int64_t n_sites, const double
 }
 
 int mra_cv(mra_plan* pl, uint32_t flags, double* mean_perm, double* var_perm, double* lpd_perm, double* group_lpd, double* info) {
-    return guarded(pl, [&] { require(pl, "mra_cv: plan is NULL"); cv_all(pl, flags, mean_perm, var_perm, lpd_perm, group_lpd, info); return MRA_OK; });
+    return guarded(pl, [&] { require(pl, "mra_cv: plan is NULL"); cv_all(pl, false, flags, mean_perm, var_perm, lpd_perm, group_lpd, info); return MRA_OK; });
+}
+int mra_cv_trend(mra_plan* pl, uint32_t flags, double* mean_perm, double* var_perm, double* lpd_perm, double* group_lpd, double* info) {
+    return guarded(pl, [&] { require(pl, "mra_cv_trend: plan is NULL"); cv_all(pl, true, flags, mean_perm, var_perm, lpd_perm, group_lpd, info); return MRA_OK; });
 }
 
 int mra_get_likelihood(mra_plan* pl, double* d, double* u) {
@@ -4674,6 +4732,11 @@ int mra_get_buffer(mra_plan* pl, int what, double* out, int64_t cap, int64_t* n_
         if (what == 12) {            // host record: stream ms of the last mra_cv
             *n_avail = 9;
             if (out && cap > 0) memcpy(out, pl->sit.cv_ms, (size_t)std::min<int64_t>(cap, 9) * sizeof(double));
+            return MRA_OK;
+        }
+        if (what == 15) {            // host record: stream ms of the last mra_cv_trend
+            *n_avail = 12;
+            if (out && cap > 0) memcpy(out, pl->sit.cvt_ms, (size_t)std::min<int64_t>(cap, 12) * sizeof(double));
             return MRA_OK;
         }
         if (what == 14) {            // host record: stream ms of the last mra_trend_fit

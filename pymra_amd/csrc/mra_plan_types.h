@@ -710,6 +710,10 @@ struct mra_plan {
         DevVec<int> cvleaf;                       // [n_leaves] node index
         DevVec<long> cvleaf_row;                  // [n_leaves][2] first and one-past-last padded row
         double cv_ms[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};        // stream ms of the last mra_cv: basis, leaf, chain, mean (+ sweeps), Gram, Cholesky, solve (+ reduction), uploads, downloads
+        // mra_cv_trend: per tile of a batch W^T = L_A^-1 h^T (qn x16, qn = p rounded up to 4), |w|^2 by padded
+        // row for the call, and the trend's share of the reduction
+        DevVec<double> cvw, cvwsq, cvtpart, cvtres;
+        double cvt_ms[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};      // stream ms of the last mra_cv_trend: cv_ms's nine, then the trend's sweeps, k_cv_trend, k_cv_downdate
     } sit;
     // Laplace fit (mra_plan_fit_laplace): the data of the call by padded row (z: NaN at rows the plan does not
     // observe), the linearisation point of the running pass, and the reduction's partial results.  Allocated by the first call.
@@ -835,6 +839,14 @@ void mra_cv_loo(mra_plan* pl, long n_tiles);
 void mra_cv_gram(mra_plan* pl, long n_tiles, int nt_max);
 void mra_cv_solve(mra_plan* pl, long n_tiles, long n_groups);
 void mra_cv_reduce(mra_plan* pl, bool by_leaf);
+// ... and of mra_cv_trend (section 22) on top of them: qn x16 doubles per tile and |w|^2 by padded row; k_cv_trend on a batch behind
+// mra_sites_mean (add_v: |w|^2 into the tiles' v as well); k_cv_downdate between mra_cv_gram and the Cholesky; the trend's sums into
+// res[3] = {tr K^-1, tr P, max (v + |w|^2) / r} behind mra_cv_reduce (h_has_w: k_cv_trend ran with add_v)
+size_t mra_cv_trend_tile_bytes(const mra_plan* pl);
+void mra_cv_trend_reserve(mra_plan* pl, long n_tiles);
+void mra_cv_trend_rows(mra_plan* pl, long n_tiles, bool add_v);
+void mra_cv_trend_downdate(mra_plan* pl, long n_tiles, int nt_max);
+void mra_cv_trend_reduce(mra_plan* pl, bool h_has_w);
 // mra_launch_laplace.hip: the work buffers of mra_plan_fit_laplace (and the plan's noise / noise_sd); one linearisation at x_in (lap.x
 // itself, or the mean of the last pass) -> y, noise, noise_sd, lap.x; the reduction after a pass -> res[MRA_LAPLACE_NRES] = {step,
 // max |x^|, sum log D, sum D (t - x^)^2, sum of the x-dependent part of log p}, res a device-visible pointer (the plan's pinned record).

@@ -740,3 +740,152 @@ __global__ __launch_bounds__(64 * MRA_CV_NRES) void k_cv_sum(const double* __res
     }
     if (lane == 0) res[k] = sh[k][0];
 }
+
+// ---- 8. cross-validation with a regression trend (mra_cv_trend) -------------------------------------------------
+// y = X beta + x + eps with a flat prior on beta.  After mra_trend_fit's sweeps trend.m holds the kriging means of [y | X], trend.coef
+// beta^ and L_A^-1 (A = X^T K^-1 X = L_A L_A^T).  With h_p = X_p - m_X(p) and w_p = L_A^-1 h_p: K^-1 X = D^-1 h, P y = D^-1 rho~ with
+// rho~_p = y_p - m_y(p) - h_p^T beta^, and P[G, G] = D_G^-1 (N_G - W_G W_G^T) D_G^-1.  So section 18's formulas hold with rho~ for rho
+// and, when beta is estimated again without the group, N_G - W_G W_G^T for N_G (by row: h~ = (v + |w|^2) / r for h).
+//
+// One wave per tile, after k_site_mean: h for the tile's rows out of X and m_X (lane (r, q) loads row r's covariates q, q + 4, ...: for
+// one covariate 16 neighbouring rows), W^T = L_A^-1 h^T (qn x16, qn = p rounded up to 4) block row by block row on the MFMA - L_A^-1
+// comes out of L2, 32 KB for all tiles, and only its lower triangle is read - then |w|^2 per row and m[u] += h^T beta^ (the sum in
+// k_trend_rows' order), so that k_cv_loo, k_cv_fwd and k_cv_solve see rho~ = y - m.  add_v: v[u] += |w|^2 as well, which makes
+// k_cv_loo's h the h~ of leaving a row out and estimating beta again.  Padding columns get w = 0 and keep their m and v.
+__global__ __launch_bounds__(64, 4) void k_cv_trend(const long* __restrict__ sslot, const double* __restrict__ X, const double* __restrict__ mX,
+                                                    long P, int p, const double* __restrict__ beta, const double* __restrict__ Linv,
+                                                    int add_v, double* __restrict__ m, double* __restrict__ v, double* __restrict__ w_buf,
+                                                    double* __restrict__ wsq) {
+    const long I = blockIdx.x;
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    const int qn = (p + 3) & ~3, nb = (p + 15) >> 4;
+    const long u = I * 16 + r;
+    const long row = sslot[u];
+    // h[s] = h_row[q + 4 s]: the B operand of every k-step, and the terms of h^T beta^
+    double h[16];
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+        const int j = q + 4 * s;
+        h[s] = (row >= 0 && j < p) ? gld(X + (long)j * P + row) - gld(mX + (long)j * P + row) : 0.0;
+    }
+    double* w = w_buf + I * (long)qn * 16;
+    double sq = 0.0;
+#pragma unroll
+    for (int B = 0; B < 4; ++B) {
+        if (B < nb) {                            // (uniform: the unrolled loops keep h in registers)
+            d4 acc = {0, 0, 0, 0};
+            const int i = B * 16 + r;            // the row of L_A^-1 this lane feeds
+#pragma unroll
+            for (int J = 0; J <= B; ++J) {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    const int k = J * 16 + q + 4 * s;
+                    if (J * 16 + 4 * s < qn) {
+                        const double a = (k <= i && i < p) ? gld(Linv + (long)i * (MRA_TREND_MAX + 1) + k) : 0.0;
+                        acc = mfma16(a, h[J * 4 + s], acc);
+                    }
+                }
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int wi = B * 16 + q + 4 * j;
+                if (wi < qn) gst(w + (long)wi * 16 + r, acc[j]);
+                sq = __builtin_fma(acc[j], acc[j], sq);
+            }
+        }
+    }
+    sq += __shfl_xor(sq, 16, 64);
+    sq += __shfl_xor(sq, 32, 64);
+    // h^T beta^ for row r, one covariate after the other as k_trend_rows sums them (covariate j sits in lane (r, j & 3), element j >> 2)
+    double mu = gld(m + u);
+#pragma unroll
+    for (int s = 0; s < 16; ++s) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const double hj = __shfl(h[s], r + 16 * k, 64);
+            if (4 * s + k < p) mu = __builtin_fma(hj, beta[4 * s + k], mu);
+        }
+    }
+    if (q == 0 && row >= 0) {
+        gst(m + u, mu);
+        if (add_v) gst(v + u, gld(v + u) + sq);
+        wsq[row] = sq;
+    }
+}
+
+// One wave per 16 x 16 block on or below the diagonal of a leaf's block, k_cv_gram's grid and operand pattern: N -= W_I W_J^T over the
+// qn = p rounded up to 4 rows of the tiles' W arrays, qn / 4 MFMAs.  Padding rows and columns have w = 0 and stay the identity.
+__global__ __launch_bounds__(64, 4) void k_cv_downdate(const SiteDrawTile* __restrict__ dt, const double* __restrict__ w_buf, int qn,
+                                                       double* __restrict__ G) {
+    const long I = blockIdx.x;
+    const SiteDrawTile D = dt[I];
+    const int il = (int)(I - D.first), jl = blockIdx.y;
+    if (jl > il) return;
+    const long J = (long)D.first + jl;
+    const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
+    const long ld = 16L * D.nt;
+    double* o = G + D.goff + (long)il * 16 * ld + jl * 16 + r;
+    d4 acc;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) acc[j] = gld(o + (long)(q + 4 * j) * ld);
+    const double* wI = w_buf + I * (long)qn * 16;
+    const double* wJ = w_buf + J * (long)qn * 16;
+    for (int k0 = 0; k0 < qn; k0 += 4) {
+        const long k = k0 + q;
+        acc = mfma16(-gld(wI + k * 16 + r), gld(wJ + k * 16 + r), acc);
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) gst(o + (long)(q + 4 * j) * ld, acc[j]);
+}
+
+// The trend's share of the reduction, in the pattern of k_cv_part / k_cv_sum: per workgroup {tr K^-1 = sum (1 - v / r) / r,
+// tr P = sum (1 - (v + |w|^2) / r) / r, max (v + |w|^2) / r} over the scored rows.  h_has_w: the rows' h is h~ already (k_cv_trend added
+// |w|^2 to v), else it is v / r.
+constexpr int MRA_CVT_NRES = 3;
+__global__ __launch_bounds__(256) void k_cv_trend_part(CvRows c, CvOut o, const double* __restrict__ wsq, int h_has_w, long P,
+                                                       double* __restrict__ part) {
+    __shared__ double sh[MRA_CVT_NRES][256];
+    double a[MRA_CVT_NRES] = {0.0, 0.0, 0.0};
+    for (long p = (long)blockIdx.x * 256 + threadIdx.x; p < P; p += (long)gridDim.x * 256) {
+        const double h = o.h[p];
+        if (!(h == h)) continue;
+        const double r = cv_noise(c, p), dw = wsq[p] / r;
+        const double hv = h_has_w ? h - dw : h, ht = h_has_w ? h : h + dw;
+        a[0] += (1.0 - hv) / r;
+        a[1] += (1.0 - ht) / r;
+        a[2] = ht > a[2] ? ht : a[2];
+    }
+#pragma unroll
+    for (int k = 0; k < MRA_CVT_NRES; ++k) sh[k][threadIdx.x] = a[k];
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) {
+#pragma unroll
+            for (int k = 0; k < MRA_CVT_NRES; ++k) {
+                const double x = sh[k][threadIdx.x], y = sh[k][threadIdx.x + w];
+                sh[k][threadIdx.x] = k == 2 ? (y > x ? y : x) : x + y;
+            }
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x < MRA_CVT_NRES) part[(long)blockIdx.x * MRA_CVT_NRES + threadIdx.x] = sh[threadIdx.x][0];
+}
+__global__ __launch_bounds__(64 * MRA_CVT_NRES) void k_cv_trend_sum(const double* __restrict__ part, int nblk, double* __restrict__ res) {
+    __shared__ double sh[MRA_CVT_NRES][64];
+    const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    double acc = 0.0;
+    for (int b = lane; b < nblk; b += 64) {
+        const double a = part[(long)b * MRA_CVT_NRES + k];
+        acc = k == 2 ? (a > acc ? a : acc) : acc + a;
+    }
+    sh[k][lane] = acc;
+    __syncthreads();
+    for (int w = 32; w > 0; w >>= 1) {
+        if (lane < w) {
+            const double a = sh[k][lane], b = sh[k][lane + w];
+            sh[k][lane] = k == 2 ? (b > a ? b : a) : a + b;
+        }
+        __syncthreads();
+    }
+    if (lane == 0) res[k] = sh[k][0];
+}

@@ -41,6 +41,7 @@ MRA_OPT_SAMPLE_GRAM_BYTES = 19
 MRA_OPT_SAMPLE_SOLVE = 20
 MRA_OPT_SITES_CHUNK_BYTES = 21
 MRA_CV_LEAF = 1
+MRA_CV_TREND_REFIT = 2
 MRA_OPT_LEAF_ORDER = 22
 MRA_OPT_PARENT_PAIR = 23
 MRA_OPT_PRIOR_REUSE = 24
@@ -81,7 +82,7 @@ EXPORTS = [
     "mra_device_count", "mra_release_cached_memory", "mra_plan_create", "mra_plan_destroy", "mra_plan_set_locs", "mra_plan_set_obs",
     "mra_plan_set_noise", "mra_plan_set_noise_rows", "mra_plan_fit_laplace", "mra_plan_fit_laplace_trend", "mra_plan_set_metric", "mra_plan_set_trend", "mra_trend_fit",
     "mra_plan_set_kernel", "mra_plan_set_locs_rows", "mra_plan_set_obs_rows", "mra_get_predict_rows", "mra_get_predict_rows_sd", "mra_eval_kernel", "mra_plan_set_cov_block", "mra_run", "mra_get_likelihood", "mra_get_predict",
-    "mra_sample_slots", "mra_sample", "mra_solve", "mra_cov_apply", "mra_predict_sites", "mra_sites_cov", "mra_sample_sites_slots", "mra_sample_sites", "mra_cv", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
+    "mra_sample_slots", "mra_sample", "mra_solve", "mra_cov_apply", "mra_predict_sites", "mra_sites_cov", "mra_sample_sites_slots", "mra_sample_sites", "mra_cv", "mra_cv_trend", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
     "mra_get_kernel_stats", "mra_get_kernel_work", "mra_get_route", "mra_device_synchronize", "mra_plan_info", "mra_comm_unique_id", "mra_comm_init",
     "mra_plan_set_reduce_level", "mra_reduce_size", "mra_reduce_export", "mra_reduce_import",
     "mra_run_resume", "mra_last_error", "mra_version",
@@ -162,6 +163,7 @@ def load_library():
         "mra_sample_sites_slots": (C.c_int, [vp, i64, C.POINTER(i64)]),
         "mra_sample_sites": (C.c_int, [vp, u32, i64, vp, vp, i64, C.c_uint64, i64, vp, vp]),
         "mra_cv": (C.c_int, [vp, u32, vp, vp, vp, vp, vp]),
+        "mra_cv_trend": (C.c_int, [vp, u32, vp, vp, vp, vp, vp]),
         "mra_get_buffer": (C.c_int, [vp, C.c_int, vp, i64, C.POINTER(i64)]),
         "mra_get_node_block": (C.c_int, [vp, i32, C.c_int, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
         "mra_get_timers": (C.c_int, [vp, vp, C.c_int]),
@@ -665,6 +667,21 @@ class HipPlan:
         group = np.empty(self.info()["n_nodes"])
         info = np.zeros(8)
         self._check(self.lib.mra_cv(self._h, MRA_CV_LEAF if leaf else 0, _ptr(mean), _ptr(var), _ptr(lpd), _ptr(group), _ptr(info)))
+        return mean, var, lpd, group, info
+
+    def cv_trend(self, leaf=False, refit=True):
+        """``cv`` for a plan with a regression trend (include/mra_hip.h, mra_cv_trend): the model is y = X beta + x + eps with the X
+        of ``set_trend`` and a flat prior on beta.  refit=True: beta is estimated again without the left-out group (universal-kriging
+        cross-validation; X without the group must keep full column rank); refit=False: the beta^ of the full fit is plugged in, which
+        is ``cv`` on y - X beta^ reported on the scale of y.  -> (mean, var, lpd, group_lpd, info) as ``cv``, info[12] as the header
+        lists it (5: the largest leverage the mode divides by, 6: tr K^-1, 7: |P y|^2, 8: tr P, 9: p, 10 / 11: the derivatives of the
+        profile / REML -2 log-likelihood by a nugget added to every observed row).  The trend is fitted from the factors that stand;
+        y, the options, likelihood() / predict() and what trend_fit() and cv() return are unchanged."""
+        mean, var, lpd = np.empty(self.P), np.empty(self.P), np.empty(self.P)
+        group = np.empty(self.info()["n_nodes"])
+        info = np.zeros(12)
+        flags = (MRA_CV_LEAF if leaf else 0) | (MRA_CV_TREND_REFIT if refit else 0)
+        self._check(self.lib.mra_cv_trend(self._h, flags, _ptr(mean), _ptr(var), _ptr(lpd), _ptr(group), _ptr(info)))
         return mean, var, lpd, group, info
 
     def buffer(self, what):
