@@ -16,6 +16,7 @@
 #include <rccl/rccl.h>      // types and enum values only: the library itself is loaded with dlopen at run time
 #include <set>
 #include <string>
+#include <thread>
 #include <vector>
 #include <time.h>
 
@@ -542,7 +543,7 @@ struct mra_plan {
     DevVec<int> hi_wgn_8;
     long n_hi_wg8 = 0;
     bool regular = false, use_fused = true, gemm_lds = true, use_front_fused = true, use_leaf_gemm = true, leaf_gemm_update = false;
-    PassRoute route;                    // the launch sequence of the open pass: fixed by run_all, read by every stage and by mra_run_resume
+    PassRoute route;                    // the launch sequence of the open pass: fixed by mra_run_all, read by every stage and by mra_run_resume
     bool route_set = false;             // a pass has fixed `route` (mra_get_route)
     int dbg = 0;
     int NL = 0, CWT = 0;
@@ -761,6 +762,46 @@ static inline void ensure_big_lds(mra_plan* pl, std::initializer_list<const void
     }
 }
 
+// ---- small things every host unit uses ------------------------------------------------------------------------------
+// a plan built in host memory (g_dry) has nothing to run on: the one refusal of a pass and of every call that would launch
+[[noreturn]] static inline void refuse_dry_run() { throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN plan: built in host memory for the sanitizers, it cannot run"); }
+// everything queued on the plan's stream has run, and none of it failed ... and the device's error slot as they left it (0, or 1 + what failed)
+static inline void stream_wait(mra_plan* pl) { HIP_TRY(hipStreamSynchronize(pl->stream)); HIP_TRY(hipGetLastError()); }
+static inline int stream_wait_err(mra_plan* pl, const int* err) {
+    int e = 0;
+    HIP_TRY(hipMemcpyAsync(&e, err, sizeof(int), hipMemcpyDeviceToHost, pl->stream));
+    stream_wait(pl);
+    return e;
+}
+// a few host threads over a range of rows (or of leaves: min_per_thread is the smallest share worth a thread)
+template <class F>
+static void parallel_rows(int64_t n, F fn, int64_t min_per_thread = 65536) {
+    const int T = (int)std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(4, std::thread::hardware_concurrency()), n / min_per_thread));
+    if (T <= 1) { fn(0, n); return; }
+    std::vector<std::thread> pool;
+    for (int t = 0; t < T; ++t) pool.emplace_back(fn, n * t / T, n * (t + 1) / T);
+    for (auto& th : pool) th.join();
+}
+// one launch in the plan's kernel statistics: its work now, its time (with kernel timing on) between two events on pl->stream
+struct KTimer {
+    mra_plan* pl; int fam; hipEvent_t a = nullptr, b = nullptr;
+    KTimer(mra_plan* p, int f, const Work& w) : pl(p), fam(f) {
+        pl->kstat[fam].launches += 1;
+        pl->kstat[fam].flops += w.alg;
+        pl->kstat[fam].flops_exec += w.exec;
+        pl->kstat[fam].bytes += w.bytes;
+        if (pl->ktiming) {
+            hipEventCreate(&a); hipEventCreate(&b);
+            hipEventRecord(a, pl->stream);
+        }
+    }
+    ~KTimer() {
+        if (pl->ktiming) {
+            hipEventRecord(b, pl->stream);
+            pl->kev.push_back({fam, {a, b}});
+        }
+    }
+};
 
 // ---- dispatchers defined in the mra_launch_*.hip translation units ----------------------------------------------------
 // batched C (=|-=) f(A B^T) with epilogue EPI_SET / EPI_SUB / EPI_COV / EPI_HOSTCOV; lower_tri: every problem has .lower set and M == N
@@ -862,3 +903,39 @@ void mra_laplace_trend_reduce(mra_plan* pl, int family, double* res);
 void mra_metric_apply(mra_plan* pl);                  // X = A Xraw by row (k_metric_apply), on the plan's stream
 // with MRA_OPT_KERNEL_TIMING: `work` between two events on pl->stream, the time added to sit.ms[which] (sit.ms_sink[which] when set; one synchronisation each: a measuring mode)
 void mra_sites_timed(mra_plan* pl, int which, const std::function<void()>& work);
+
+// ---- between mra_plan.hip (plans, passes, mra_sample, the C ABI) and mra_calls.hip (the calls on the retained factors) ----------------
+// mra_plan.hip, for the calls: one pass (full_rows: W at every row); the kernel times of the events recorded so far, the stream waited
+// for; the diag_add of every leaf residual problem; k_panel_chol with the caller's own log-determinant and error slots (nprob > 0) and
+// the non-leaf draws of a block of samples, slot-major into zc (Kn > 0) - the two kernels of that unit the calls launch themselves
+void mra_run_all(mra_plan* pl, uint32_t flags, bool full_rows = false);
+void mra_harvest_kernel_events(mra_plan* pl);
+void mra_set_leaf_diag_add(mra_plan* pl, double v);
+void mra_panel_chol(mra_plan* pl, const PanelProb* probs, size_t nprob, double* dn, int* err);
+void mra_sample_draw(mra_plan* pl, const SampleZ& zs, long Kn, double* zc);
+// mra_calls.hip, for mra_sample: the latent slots of the non-leaf nodes, the preamble of every call on the retained factors, the
+// sample numbers' check, room for a block's non-leaf draws, and the scope that puts the last mra_run's results back
+long mra_coarse_slots(const mra_plan* pl, std::vector<long>* zoff);
+void mra_retained_check_plan(const mra_plan* pl, const char* who, uint32_t flags, uint32_t accepted, const char* host_cannot, const char* sharded_cannot,
+                             bool dry_last = false);
+void mra_check_sample0(int64_t sample0, int64_t n);
+void mra_reserve_coarse(DevVec<double>& v, long Kn);
+struct KeepResults {
+    mra_plan* pl; double *ysave, *msave, *vsave;
+    const bool had_ran; const uint32_t had_flags; const double had_d, had_u; const bool had_pred; const size_t bytes;
+    KeepResults(mra_plan* p, double* ys, double* ms, double* vs);
+    ~KeepResults();
+};
+// ... and for the C ABI: the drivers of the exports, one each (mra_cv_all: mra_cv and mra_cv_trend)
+void mra_solve_all(mra_plan* pl, uint32_t flags, int64_t n, const double* Y, double* mean, double* quad);
+void mra_trend_set(mra_plan* pl, int32_t p, const double* X);
+void mra_trend_fit_all(mra_plan* pl, uint32_t flags, double* beta, double* cov_beta, double* mean, double* var, double* info);
+void mra_cov_all(mra_plan* pl, uint32_t flags, int64_t n, const double* A, double* out, double* gram);
+void mra_predict_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const double* sites, const int32_t* leaf, int64_t nc, const double* Y, double* mean, double* var);
+void mra_sites_cov_all(mra_plan* pl, uint32_t flags, int64_t n, const double* sites, const int32_t* leaf, double* out);
+void mra_sample_sites_all(mra_plan* pl, uint32_t flags, int64_t n, const double* sites, const int32_t* leaf, int64_t ns_all, uint64_t seed, int64_t sample0,
+                          const double* z, double* out);
+void mra_cv_all(mra_plan* pl, bool trend, uint32_t flags, double* mean, double* var, double* lpd, double* group_lpd, double* info);
+void mra_fit_laplace(mra_plan* pl, int family, const double* z, const double* aux, const double* off, const double* x0, int max_iter, double tol, double* info);
+void mra_fit_laplace_trend(mra_plan* pl, int family, const double* z, const double* aux, const double* off, const double* e0, int max_iter, double tol,
+                           double* beta, double* cov_beta, double* info);

@@ -6,7 +6,7 @@ cd "$(dirname "$0")/.."
 NAME=$1; shift
 B=build/var_$NAME
 mkdir -p $B
-UNITS="mra_plan mra_launch_gemm mra_launch_pred mra_launch_prior_row1 mra_launch_prior_row2 mra_launch_prior_knot1 mra_launch_prior_knot2"
+UNITS="mra_plan mra_calls mra_launch_gemm mra_launch_pred mra_launch_prior_row1 mra_launch_prior_row2 mra_launch_prior_row3 mra_launch_prior_knot1 mra_launch_prior_knot2 mra_launch_prior_knot3 mra_launch_solve mra_launch_cov mra_launch_sites mra_launch_laplace"
 for u in $UNITS; do
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -std=c++17 -fPIC -Wno-unused-value -Wno-unused-result -Wno-pass-failed -O3 -Rpass-analysis=kernel-resource-usage "$@" -c pymra_amd/csrc/$u.hip -o $B/$u.o 2> $B/$u.remarks.txt &
 done
