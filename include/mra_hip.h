@@ -41,6 +41,7 @@ extern "C" {
 #define MRA_KERNEL_GAUSSIAN    3   /* GaussianCovFun sig exp(-D^2/(2 l^2))              :297-301 */
 #define MRA_KERNEL_IDEN        4   /* Iden           [D == 0]                           :256-262 */
 #define MRA_KERNEL_KANTER      5   /* KanterCovFun   compact taper, radius = l          :305-324 */
+#define MRA_KERNEL_MATERN      6   /* Matern(nu)     sig 2^(1-nu)/Gamma(nu) t^nu K_nu(t), t = sqrt(2 nu) D/l :273-277 */
 #define MRA_KERNEL_HOST        100 /* values supplied block by block (any cov callable or a dense
                                       matrix, pyMRA/MRANode.py:73-80, 381-384)                   */
 
@@ -170,13 +171,19 @@ int mra_plan_fit_laplace(mra_plan *plan, int family, const double *z_perm, const
 /* Replaces: the `cov` callable when it is one of pyMRA's stationary kernels
  * (pyMRA/MRATools.py:256-301).  params = {l, sig, scale[, circular]}; value = scale * k(D; l, sig);
  * circular != 0 (1-D only): D = min(|a-b|, 1-|a-b|), the torus branch of dist() (MRATools.py:232-239).
+ * kind == MRA_KERNEL_MATERN: params = {l, sig, scale, circular, nu}, n_params >= 5, 0.1 <= nu <= 5 (sklearn's parametrisation,
+ * nu = 1.5 and 2.5 are Matern32 and Matern52).  The plan builds a table of 191 quadrature nodes for nu on the host and keeps it in a
+ * device buffer of its own, rebuilt only when nu changes.  Such plans take the level-by-level prior (mra_get_route) and every call on the
+ * retained factors.  Every refusal of this call comes before anything of the plan changes (the previous kernel and everything retained
+ * stand): circular distances on a plan that is not 1-D or has a metric, l <= 0, and MRA_ERR_INVALID for an
+ * unknown kind, n_params < 3 and, for MRA_KERNEL_MATERN, n_params < 5, l <= 0 and a nu that is not finite or outside [0.1, 5].
  * kind == MRA_KERNEL_HOST (params ignored, call after mra_plan_set_obs): covariance values come from
  * mra_plan_set_cov_block. */
 int mra_plan_set_kernel(mra_plan *plan, int kind, const double *params, int n_params);
 
 /* Diagnostics: out[i] = scale * k_kind(D[i]; l, sig) evaluated by the device code that the inference
  * kernels inline - the device counterpart of ExpCovFun/Matern32/... applied to D = dist(locs, locs2)
- * (pyMRA/MRATools.py:229-301). */
+ * (pyMRA/MRATools.py:229-301).  MRA_KERNEL_MATERN takes params = {l, sig, scale, circular, nu} as mra_plan_set_kernel does. */
 int mra_eval_kernel(int kind, const double *params, int n_params, const double *D, int64_t n, double *out);
 
 /* Replaces: the `cov` callable for anything else (MRA_KERNEL_HOST): the host evaluates
@@ -518,6 +525,8 @@ int mra_cv_trend(mra_plan *plan, uint32_t flags, double *mean_perm, double *var_
  * block) and of one block's archive panel (written once, read once);
  * 15: stream milliseconds of the last mra_cv_trend under MRA_OPT_KERNEL_TIMING (12 values: the nine of 12, then the trend's sweeps
  * with their staging and transfers, k_cv_trend, k_cv_downdate);
+ * 16: the quadrature table of an MRA_KERNEL_MATERN plan as the device holds it (191 pairs (cosh(k h), c h cosh(nu k h)), h = 0.2,
+ * c = 2^(1-nu) / Gamma(nu), the weight halved at k = 0; 0 values while the plan has another kernel);
  * copies min(capacity, available) doubles into out, returns the available count in *n_avail.
  * (W after a likelihood-only run is complete only with MRA_OPT_LIK_ROWS off: by default such a run computes W at the rows a
  * likelihood needs - the observed rows, and the knots on the level-by-level path - and leaves the others as they were.) */

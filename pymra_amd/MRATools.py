@@ -8,6 +8,7 @@ Mirrors the part of pyMRA/MRATools.py that the inference path and its callers us
 * ``Matern52``          pyMRA/MRATools.py:281-285
 * ``Matern32``          pyMRA/MRATools.py:289-293
 * ``GaussianCovFun``    pyMRA/MRATools.py:297-301
+* ``Matern``            pyMRA/MRATools.py:273-277 (there through sklearn's ``Matern(nu=...)``; here with ``locs2``)
 * ``genLocations``      pyMRA/MRATools.py:180-187
 * ``genLocations2d``    pyMRA/MRATools.py:192-203
 
@@ -23,6 +24,7 @@ from __future__ import annotations
 
 import numpy as np
 from scipy.spatial.distance import cdist, pdist, squareform
+from scipy.special import gamma, gammaln, kv
 
 # kernel kinds understood by the HIP library (include/mra_hip.h: MRA_KERNEL_*)
 KIND_EXP = 0
@@ -31,6 +33,8 @@ KIND_MATERN52 = 2
 KIND_GAUSSIAN = 3
 KIND_IDEN = 4
 KIND_KANTER = 5
+KIND_MATERN = 6            # Matern of any smoothness nu in [NU_MIN, NU_MAX]
+NU_MIN, NU_MAX = 0.1, 5.0
 
 
 class SymbolicLocs:
@@ -74,16 +78,18 @@ def _in_metric(locs, A):
 
 
 class KernelSpec:
-    """kind + (l, sig) + an overall scale; value = scale * k_kind(D; l, sig), D = |a - b| or, with a metric A, |A (a - b)|."""
-    __slots__ = ("kind", "l", "sig", "scale", "circular", "A")
+    """kind + (l, sig) + an overall scale; value = scale * k_kind(D; l, sig), D = |a - b| or, with a metric A, |A (a - b)|.
+    nu: the smoothness of KIND_MATERN (None for every other kind)."""
+    __slots__ = ("kind", "l", "sig", "scale", "circular", "A", "nu")
 
-    def __init__(self, kind, l=1.0, sig=1.0, scale=1.0, circular=False, A=None):
+    def __init__(self, kind, l=1.0, sig=1.0, scale=1.0, circular=False, A=None, nu=None):
         self.kind, self.l, self.sig, self.scale, self.circular = int(kind), float(l), float(sig), float(scale), bool(circular)
         self.A = _check_metric(A, self.circular)
+        self.nu = _check_nu(nu) if self.kind == KIND_MATERN else None
 
     def __mul__(self, c):
         if isinstance(c, (int, float, np.floating, np.integer)):
-            return KernelSpec(self.kind, self.l, self.sig, self.scale * float(c), self.circular, self.A)
+            return KernelSpec(self.kind, self.l, self.sig, self.scale * float(c), self.circular, self.A, self.nu)
         return NotImplemented
 
     __rmul__ = __mul__
@@ -98,11 +104,23 @@ class KernelSpec:
         """Host evaluation (tests / diagnostics); same arithmetic as the array path below."""
         fn = _HOST_KERNELS[self.kind]
         locs1, locs2 = _in_metric(np.asarray(locs1), self.A), _in_metric(np.asarray(locs2), self.A)
-        return self.scale * np.asarray(fn(locs1, locs2, self.l, self.sig, self.circular))
+        extra = (self.nu,) if self.kind == KIND_MATERN else ()
+        return self.scale * np.asarray(fn(locs1, locs2, self.l, self.sig, self.circular, *extra))
 
     def __repr__(self):
         base = "KernelSpec(kind=%d, l=%g, sig=%g, scale=%g" % (self.kind, self.l, self.sig, self.scale)
+        base += "" if self.nu is None else ", nu=%g" % self.nu
         return base + (")" if self.A is None else ", A=%s)" % np.array2string(self.A, separator=", ").replace("\n", ""))
+
+
+def _check_nu(nu):
+    """The smoothness of KIND_MATERN: a finite number in [NU_MIN, NU_MAX], the range the device quadrature is accurate on."""
+    if nu is None:
+        raise ValueError("KIND_MATERN needs nu")
+    nu = float(nu)
+    if not (np.isfinite(nu) and NU_MIN <= nu <= NU_MAX):
+        raise ValueError("nu must lie in [%g, %g], got %r" % (NU_MIN, NU_MAX, nu))
+    return nu
 
 
 def _symbolic(*args):
@@ -220,8 +238,49 @@ def _kanter(l1, l2, l, sig, circular):
     return R
 
 
+def _matern_quad(t, nu, h=0.1):
+    """t^nu K_nu(t) for 2^-5 <= t < 2 by the trapezoid rule on K_nu(t) = int_0^inf exp(-t cosh u) cosh(nu u) du - the device's method
+     at half its step, all terms positive - by octaves of t, each with the nodes its smallest t needs."""
+    out = np.empty_like(t)
+    e = np.floor(np.log2(t))
+    for ex in np.unique(e):
+        idx = np.flatnonzero(e == ex)
+        n = int(np.arccosh(745.0 / 2.0 ** ex) / h) + 2
+        u = h * np.arange(n)
+        w = h * np.cosh(nu * u)
+        w[0] *= 0.5
+        for i0 in range(0, len(idx), 1 << 16):          # (the len x n matrix of terms, 64 MB at a time)
+            ts = t[idx[i0:i0 + (1 << 16)]]
+            out[idx[i0:i0 + (1 << 16)]] = ts ** nu * np.sum(w * np.exp(-np.outer(ts, np.cosh(u))), axis=1)
+    return out
+
+
+def matern_nu(t, nu):
+    """M_nu(t) = 2^(1-nu) / Gamma(nu) t^nu K_nu(t) for t >= 0, M_nu(0) = 1, to 1e-15 against 40-digit values.  scipy.special.kv, but on
+    2^-5 <= t < 2 - where kv's power series loses a digit for fractional nu (1.5e-14 at nu = 0.8, t = 1.9) - the quadrature of
+    _matern_quad; 0 at t > 700 (M_nu < 1e-290, t^nu K_nu underflows); the leading terms 1 - Gamma(1-nu) / Gamma(1+nu) (t/2)^(2 nu) at
+    t < 2^-40 (what is left out is below 1e-21)."""
+    t = np.asarray(t, dtype=np.float64)
+    out = np.ones_like(t)
+    big, tiny = t > 700.0, (t > 0.0) & (t < 2.0 ** -40)
+    low = (t >= 2.0 ** -5) & (t < 2.0)
+    mid = (t >= 2.0 ** -40) & ~low & ~big
+    c = 2.0 ** (1.0 - nu) / gamma(nu)
+    out[mid] = c * (t[mid] ** nu * kv(nu, t[mid]))
+    out[low] = c * _matern_quad(t[low], nu)
+    out[big] = 0.0
+    if nu < 1.0:
+        out[tiny] = 1.0 - np.exp(gammaln(1.0 - nu) - gammaln(1.0 + nu) + 2.0 * nu * np.log(0.5 * t[tiny]))
+    return out
+
+
+def _matern(l1, l2, l, sig, circular, nu=1.5):
+    D = np.asarray(dist(l1, l2, circular))
+    return sig * matern_nu(np.sqrt(2.0 * nu) * D / l, nu)
+
+
 _HOST_KERNELS = {KIND_EXP: _exp, KIND_MATERN32: _m32, KIND_MATERN52: _m52, KIND_GAUSSIAN: _gauss,
-                 KIND_IDEN: _iden, KIND_KANTER: _kanter}
+                 KIND_IDEN: _iden, KIND_KANTER: _kanter, KIND_MATERN: _matern}
 
 
 def determine_radius(k, h, ndim=2):
@@ -298,3 +357,24 @@ def GaussianCovFun(locs, locs2=np.array([]), l=1, sig=1, circular=False, metric=
     if _symbolic(locs, locs2):
         return KernelSpec(KIND_GAUSSIAN, l, sig, 1.0, circular, metric)
     return np.matrix(_gauss(_in_metric(locs, metric), _in_metric(locs2, metric), l, sig, circular))
+
+
+def Matern(locs, locs2=np.array([]), l=1, sig=1, nu=1.5, circular=False, metric=None):
+    """Matern covariance of any smoothness 0.1 <= nu <= 5: sig * 2^(1-nu) / Gamma(nu) * t^nu * K_nu(t), t = sqrt(2 nu) D / l (sklearn's
+    parametrisation, which Matern32 and Matern52 share).  The reference's Matern(locs, l, sig, nu) has no ``locs2`` and cannot serve as
+    a tree's ``cov``; this one has the shape of its siblings and can.  With the symbolic locations of a tree it returns the kernel's
+    spec - nu of exactly 0.5, 1.5 or 2.5 the closed forms (KIND_EXP with scale sig, KIND_MATERN32, KIND_MATERN52: the same functions
+    on faster kernels), any other nu KIND_MATERN, evaluated on the device by quadrature; with arrays it evaluates on the host (``matern_nu``):
+    scipy.special.kv, except on 2^-5 <= t < 2, where kv misses 5e-15 for fractional nu and the trapezoid sum for K_nu - the integral
+    representation the device uses, at half its step - takes over.  On that range, where most covariance values of a tree lie, the
+    oracles and CPU twins built on this function therefore share the device's method; what keeps the two independent there is the
+    40-digit mpmath table (tests/golden/matern_nu.npz), which both are tested against."""
+    metric = _check_metric(metric, circular)
+    nu = _check_nu(nu)
+    if _symbolic(locs, locs2):
+        if nu == 0.5:
+            return KernelSpec(KIND_EXP, l, 1.0, float(sig), circular, metric)
+        if nu == 1.5 or nu == 2.5:
+            return KernelSpec(KIND_MATERN32 if nu == 1.5 else KIND_MATERN52, l, sig, 1.0, circular, metric)
+        return KernelSpec(KIND_MATERN, l, sig, 1.0, circular, metric, nu)
+    return np.matrix(_matern(_in_metric(locs, metric), _in_metric(locs2, metric), l, sig, circular, nu))

@@ -198,7 +198,7 @@ class MRATree(object):
         if spec is not None:
             if spec.A is not None:
                 self.plan.set_metric(spec.A)        # (before the kernel, as reevaluate sends it)
-            self.plan.set_kernel(spec.kind, spec.l, spec.sig, spec.scale, spec.circular)
+            self.plan.set_kernel(spec.kind, spec.l, spec.sig, spec.scale, spec.circular, spec.nu)
         else:
             # cov-callable plug-in for anything the device cannot evaluate itself (pyMRA/MRANode.py:73-80,
             # 381-384): the host evaluates the raw covariance blocks, the GPU does everything else
@@ -275,7 +275,7 @@ class MRATree(object):
         if (spec.A is None) != (old is None) or (spec.A is not None and not np.array_equal(spec.A, old)):
             self.plan.set_metric(spec.A)
         self.kernel = spec
-        self.plan.set_kernel(spec.kind, spec.l, spec.sig, spec.scale, spec.circular)
+        self.plan.set_kernel(spec.kind, spec.l, spec.sig, spec.scale, spec.circular, spec.nu)
 
     @property
     def obs_inds(self):

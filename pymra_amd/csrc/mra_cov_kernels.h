@@ -16,6 +16,7 @@ static const int COV_GRAM_BLOCKS = 512;
 // ---- 1. leaves: t = W[S, anc]^T Abar[S], t' = W[S, anc]^T Acheck[S] (anc x16 each), one workgroup of four waves per leaf -----------
 // W tiles transposed as the A operand (lane (r, q) reads W[row q + 4 s][column r]: 16 consecutive doubles per q), the k loop over
 // the leaf's row tiles.  anc == 0 (a single-leaf tree): nothing is read or written.
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_cov.hip */
 __global__ __launch_bounds__(256, 4) void k_cov_leaf_proj(const CovLeaf* __restrict__ lv, const double* __restrict__ W, long ldw,
                                                           const double* __restrict__ Ab, const unsigned char* __restrict__ rep,
                                                           const unsigned char* __restrict__ knot, long P) {
@@ -42,9 +43,11 @@ __global__ __launch_bounds__(256, 4) void k_cov_leaf_proj(const CovLeaf* __restr
         }
     }
 }
+#endif
 
 // ---- 2. fronts, bottom-up, one workgroup per node, one launch per level: buf <- sum over the children's chain buffers, in child-list
 // order.  Rows [0, cw) are the node's own tau_j = W_j^T Abar[rows_j]; rows [cw, cw + anc) go on to the parent.  Sums only.
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_cov.hip */
 __global__ __launch_bounds__(256) void k_cov_up(const SolveFront* __restrict__ fv, const double* const* __restrict__ kids) {
     const SolveFront N = fv[blockIdx.x];
     const int nall = (N.cw + N.anc) * 16;
@@ -54,13 +57,16 @@ __global__ __launch_bounds__(256) void k_cov_up(const SolveFront* __restrict__ f
         gst(N.buf + e, f);
     }
 }
+#endif
 
 // ---- 3. fronts, top-down: buf <- [tau_j ; tau_chain], tau_chain = the parent's whole buffer (the layout of mra_solve's [alpha ; chain])
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_cov.hip */
 __global__ __launch_bounds__(256) void k_cov_down(const SolveFront* __restrict__ fv) {
     const SolveFront N = fv[blockIdx.x];
     const int nown = N.cw * 16, nall = (N.cw + N.anc) * 16;
     for (int e = nown + threadIdx.x; e < nall; e += 256) gst(N.buf + e, gld(N.chain + (e - nown)));
 }
+#endif
 
 // ---- 4. rows, one wave per 16-row tile:
 //     out[tile] = rep o ( W[tile, anc] tau_chain + knot o ( C(tile, S_l) Acheck[S_l] - W[tile, anc] t'_l ) )
@@ -130,6 +136,7 @@ __global__ __launch_bounds__(256, 4) void k_cov_rows(const CovLeaf* __restrict__
 
 // ---- 5. posterior: Sigma_post A = Sigma A - mean_MRA((Sigma A)_o).  The right-hand sides of mra_solve's sweeps are read at observed rows
 // only, so the block is copied whole; the mean comes back in the solver's out block.
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_cov.hip */
 __global__ __launch_bounds__(256) void k_cov_to_rhs(const double* __restrict__ out, double* __restrict__ yb, long n) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) yb[i] = out[i];
@@ -140,10 +147,12 @@ __global__ __launch_bounds__(256) void k_cov_sub(double* __restrict__ out, const
     if (p >= P || !rep[p]) return;
     for (int c = 0; c < 16; ++c) out[(long)c * P + p] -= mean[(long)c * P + p];
 }
+#endif
 
 // ---- 6. gram = Abar out^T (16 x 16) over COV_GRAM_BLOCKS partial sums in a fixed order.  Workgroup b takes the row tiles
 // [b nt, (b + 1) nt), its wave w every fourth of them on the MFMA (A = Abar as 16 x k, B = out^T: both operands are read in the same
 // form, vector r at row q + 4 s); the four waves' sums are added in wave order.  part: [block][i * 16 + j].
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_cov.hip */
 __global__ __launch_bounds__(256, 4) void k_cov_gram_part(const double* __restrict__ Ab, const double* __restrict__ out,
                                                           const unsigned char* __restrict__ rep, long P, long nt,
                                                           double* __restrict__ part) {
@@ -165,7 +174,9 @@ __global__ __launch_bounds__(256, 4) void k_cov_gram_part(const double* __restri
     __syncthreads();
     part[(long)blockIdx.x * 256 + threadIdx.x] = ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
 }
+#endif
 // Sigma is symmetric, the two roundings of an entry and its mirror image are not: the mean of the two is returned.
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_cov.hip */
 __global__ __launch_bounds__(256) void k_cov_gram_sum(const double* __restrict__ part, int nblk, double* __restrict__ gram) {
     __shared__ double g[256];
     double acc = 0.0;
@@ -175,3 +186,4 @@ __global__ __launch_bounds__(256) void k_cov_gram_sum(const double* __restrict__
     const int i = threadIdx.x >> 4, j = threadIdx.x & 15;
     gram[threadIdx.x] = 0.5 * (g[i * 16 + j] + g[j * 16 + i]);
 }
+#endif

@@ -94,6 +94,15 @@ struct KernelParams {
     //   mode 3: Kanter taper of radius l (KanterCovFun, compact support), c_inv_l = 1/radius
     int mode;
     int circular;           // 1-D only: D = min(|a-b|, 1-|a-b|)  (torus of length 1, pyMRA/MRATools.py:232-239)
+    //   mode 4: Matern of any smoothness nu (MRA_KERNEL_MATERN), t = sqrt(2 nu) D / l, by quadrature (matern_nu_of_t below):
+    //           nu_tab = nu_n pairs (cosh(k h), c h cosh(nu k h)) built on the host, the plan's own device buffer;
+    //           nu_a = Gamma(1 - nu) / (Gamma(1 + nu) 4^nu) for nu < 1, else 0: M_nu(t) = 1 - nu_a t^(2 nu) + O(t^2) at t -> 0.
+    //           These four sit BEFORE the doubles every mode reads, not behind amp: anything appended behind amp changes how the
+    //           scalar loads of amp and of the kernel arguments after the struct are merged, and the six k_site_leaf instances of
+    //           modes 0 and 3 come out with two SGPR spills fewer - a different object code for kernels this mode never runs.
+    const double* nu_tab;
+    int nu_n;
+    double nu, nu_a;
     double c_inv_l, inv_2l2, a1, a2, amp;
 };
 #define MRA_FAR_AWAY 1.0e150   /* coordinate of a phantom knot: every kernel gives exactly 0 there */
@@ -200,12 +209,44 @@ __device__ __forceinline__ double sqrt_pos(double x) {
     return __builtin_fma(res, h, g);
 }
 
+// Matern of smoothness nu at t = sqrt(2 nu) D / l:  M_nu(t) = c t^nu K_nu(t), c = 2^(1-nu) / Gamma(nu), with
+//     K_nu(t) = int_0^inf exp(-t cosh u) cosh(nu u) du
+// by the trapezoid rule at step h = 0.2 over the host-built table (ch_k, w_k) = (cosh(k h), c h cosh(nu k h)), w_0 halved.  Every term
+// is positive (no cancellation), integer nu is not special, and the error falls like exp(-pi^2 / h): 1.1e-14 absolute on [0.1, 5].
+// One uniform loop: the table is read through wave-uniform addresses, and the loop is left once no lane of the wave has a term
+// above the underflow of exp (t ch_k >= 745).  Three selects around it, whose lanes do not keep the loop alive:
+//   t == 0      exactly amp (t^nu S is 0 * inf there);
+//   t >= 745    exactly 0: at a phantom knot (MRA_FAR_AWAY) t^nu overflows while S underflows, and inf * 0 would put NaN into every front;
+//   t < 2^-40   the table ends at u = 38, too early for these t, so the sum runs at the clamped t = 2^-40 and its result is dropped for
+//               the two leading terms of the series, 1 - nu_a t^(2 nu) (nu < 1; what is left out is below t^2 / (4 (1 - nu)), 1e-24)
+//               or 1 (nu >= 1, 1 - M_nu < 1e-21): clamping the VALUE would be off by 4e-4 at nu = 0.1 and 4.5e-13 at nu = 0.5.
+#define MRA_NU_T_MAX 745.0
+#define MRA_NU_T_MIN 9.094947017729282e-13      /* 2^-40 */
+__device__ __forceinline__ double matern_nu_of_t(const KernelParams& kp, double t0) {
+    const bool tiny = t0 < MRA_NU_T_MIN;
+    const bool live = !tiny && t0 < MRA_NU_T_MAX;
+    const double t = fmax(t0, MRA_NU_T_MIN);
+    const double* __restrict__ tab = kp.nu_tab;
+    double S = 0.0;
+    for (int k = 0; k < kp.nu_n; ++k) {
+        const double x = t * tab[2 * k];
+        if (!__builtin_amdgcn_ballot_w64(live && x < MRA_NU_T_MAX)) break;
+        S = __builtin_fma(tab[2 * k + 1], exp_neg(x), S);
+    }
+    const double lt = log(fmax(t0, 1.0e-300));
+    const double e = exp((tiny ? 2.0 * kp.nu : kp.nu) * lt);           // t^nu, or t^(2 nu) for the series
+    const double v = kp.amp * (tiny ? __builtin_fma(-kp.nu_a, e, 1.0) : e * S);
+    __builtin_amdgcn_sched_barrier(0);      // one value at a time: the log / exp of the four values of a tile, interleaved, spill at 128 registers
+    return (t0 == 0.0) ? kp.amp : ((t0 < MRA_NU_T_MAX) ? v : 0.0);
+}
+
 // value of the kernel at squared distance D2 (the reference evaluates the same formulas on
 // D = cdist(...), pyMRA/MRATools.py:265-301; differences are at the 1-2 ulp level).  Straight-line
 // code: the only branches are on wave-uniform kernel parameters.
 template <int MODE>
 __device__ __forceinline__ double cov_of_dist2(const KernelParams& kp, double D2) {
     if (MODE == 2) return (D2 == 0.0) ? kp.amp : 0.0;
+    if (MODE == 4) return matern_nu_of_t(kp, sqrt_pos(D2) * kp.c_inv_l);
     if (MODE == 3) {                                 // pyMRA/MRATools.py:318-323
         const double D = fmin(sqrt_pos(D2) * kp.c_inv_l, 2.0);
         const double p2 = 6.283185307179586 * D;
@@ -240,6 +281,13 @@ __device__ __forceinline__ double pair_dist2(const double* __restrict__ xa, cons
 __global__ void k_eval_kernel(const double* __restrict__ D, double* __restrict__ out, long n, KernelParams kp) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = cov_of_dist(kp, D[i]);
+}
+// the same for MRA_KERNEL_MATERN (mode 4), which the runtime cov_of_dist does not know; D past the end of the array counts as 0
+__global__ void k_eval_kernel_nu(const double* __restrict__ D, double* __restrict__ out, long n, KernelParams kp) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const double d = i < n ? D[i] : 0.0;
+    const double v = cov_of_dist2<4>(kp, d * d);
+    if (i < n) out[i] = v;
 }
 #endif
 
@@ -478,8 +526,11 @@ struct SbStep2 { const double* A; const double* B; int lda, ldb, k0s, pad; };   
 #endif
 #define GL_PF 2           /* K-steps the global loads run ahead (register sets); even */
 
+#ifndef MRA_GEMM_LDS_WPE
+#define MRA_GEMM_LDS_WPE 4      /* waves per SIMD (mra_launch_nu3.hip: 3 - the 3-D epilogue of MRA_KERNEL_MATERN spills 4 registers at 128) */
+#endif
 template <int EPI, int DIM, int MODE>
-__global__ __launch_bounds__(256, 4) void k_gemm_nt_lds(const GemmProb* __restrict__ probs, KernelParams kp, unsigned G, unsigned nprob, unsigned S = 1) {
+__global__ __launch_bounds__(256, MRA_GEMM_LDS_WPE) void k_gemm_nt_lds(const GemmProb* __restrict__ probs, KernelParams kp, unsigned G, unsigned nprob, unsigned S = 1) {
     __shared__ __attribute__((aligned(16))) double sA[2][64 * GL_LDS_LD];
     __shared__ __attribute__((aligned(16))) double sB[2][64 * GL_LDS_LD];
     constexpr bool SEGS = EPI == EPI_SET;

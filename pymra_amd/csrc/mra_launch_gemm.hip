@@ -30,13 +30,13 @@ static void launch_gemm(mra_plan* pl, const GemmProb* probs, size_t nprob, long 
         dim3 grid(gxs * (((gy + 7u) / 8u) * 8u));
 #define MRA_GEMM_LAUNCH(KERN, D, MD) hipLaunchKernelGGL((KERN<EPI, D, (EPI == EPI_COV ? MD : 0)>), grid, dim3(256), 0, pl->stream, probs + off, pl->kp, gxs, gy, S)
         if (lds) {
-            if constexpr (EPI == EPI_COV) { if (pl->d == 3) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 2); else MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 3); continue; } }
-            if (pl->d == 1) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 2); else MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 3); }
-            else { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 2); else MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 3); }
+            if constexpr (EPI == EPI_COV) { if (pl->d == 3) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 3); else if (mode == 4) mra_nu3_gemm(pl, true, grid, probs + off, gxs, gy, S); else mra_bad_mode("mra_launch_gemm", mode); continue; } }
+            if (pl->d == 1) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 3); else if (mode == 4) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 4); else mra_bad_mode("mra_launch_gemm", mode); }
+            else { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 3); else if (mode == 4) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 4); else mra_bad_mode("mra_launch_gemm", mode); }
         } else {
-            if constexpr (EPI == EPI_COV) { if (pl->d == 3) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 2); else MRA_GEMM_LAUNCH(k_gemm_nt, 3, 3); continue; } }
-            if (pl->d == 1) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 2); else MRA_GEMM_LAUNCH(k_gemm_nt, 1, 3); }
-            else { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 2); else MRA_GEMM_LAUNCH(k_gemm_nt, 2, 3); }
+            if constexpr (EPI == EPI_COV) { if (pl->d == 3) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 3); else if (mode == 4) mra_nu3_gemm(pl, false, grid, probs + off, gxs, gy, S); else mra_bad_mode("mra_launch_gemm", mode); continue; } }
+            if (pl->d == 1) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 3); else if (mode == 4) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 4); else mra_bad_mode("mra_launch_gemm", mode); }
+            else { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 3); else if (mode == 4) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 4); else mra_bad_mode("mra_launch_gemm", mode); }
         }
 #undef MRA_GEMM_LAUNCH
     }
@@ -51,15 +51,15 @@ static void launch_leaf_gemm(mra_plan* pl, const GemmProb* probs, size_t nprob) 
     const dim3 grid((unsigned)nprob);
     constexpr int CT = (EPI == EPI_SUB) ? 13 : 7;
     // COV: one row tile per wave, 8 waves, 8 column tiles per pass (leaves of up to 128 observations in one pass), 128 registers =
-    // four waves per SIMD (the Kanter taper's sin/cos need 217: two); dbg bit 32: the 2-row-tile, 4-wave, 7-column, 239-register shape
+    // four waves per SIMD (the Kanter taper's sin/cos need 217: two, and so does the quadrature loop of MRA_KERNEL_MATERN); dbg bit 32: the 2-row-tile, 4-wave, 7-column, 239-register shape
     const bool wide = (EPI == EPI_COV) && !(pl->dbg & 32);
 #define MRA_LG_LAUNCH(D, MD) do { \
-        if (wide) hipLaunchKernelGGL((k_leaf_gemm<EPI, D, (EPI == EPI_COV ? MD : 0), 1, 8, 512, (MD == 3 ? 2 : 4)>), grid, dim3(512), 0, pl->stream, probs, pl->kp); \
+        if (wide) hipLaunchKernelGGL((k_leaf_gemm<EPI, D, (EPI == EPI_COV ? MD : 0), 1, 8, 512, (MD >= 3 ? 2 : 4)>), grid, dim3(512), 0, pl->stream, probs, pl->kp); \
         else hipLaunchKernelGGL((k_leaf_gemm<EPI, D, (EPI == EPI_COV ? MD : 0), (EPI == EPI_SUB ? 1 : 2), CT, 256, 2>), grid, dim3(256), 0, pl->stream, probs, pl->kp); \
     } while (0)
-    if constexpr (EPI == EPI_COV) { if (pl->d == 3) { if (mode == 0) MRA_LG_LAUNCH(3, 0); else if (mode == 1) MRA_LG_LAUNCH(3, 1); else if (mode == 2) MRA_LG_LAUNCH(3, 2); else MRA_LG_LAUNCH(3, 3); return; } }
-    if (pl->d == 1) { if (mode == 0) MRA_LG_LAUNCH(1, 0); else if (mode == 1) MRA_LG_LAUNCH(1, 1); else if (mode == 2) MRA_LG_LAUNCH(1, 2); else MRA_LG_LAUNCH(1, 3); }
-    else { if (mode == 0) MRA_LG_LAUNCH(2, 0); else if (mode == 1) MRA_LG_LAUNCH(2, 1); else if (mode == 2) MRA_LG_LAUNCH(2, 2); else MRA_LG_LAUNCH(2, 3); }
+    if constexpr (EPI == EPI_COV) { if (pl->d == 3) { if (mode == 0) MRA_LG_LAUNCH(3, 0); else if (mode == 1) MRA_LG_LAUNCH(3, 1); else if (mode == 2) MRA_LG_LAUNCH(3, 2); else if (mode == 3) MRA_LG_LAUNCH(3, 3); else if (mode == 4) mra_nu3_leaf_gemm(pl, wide, grid, probs); else mra_bad_mode("mra_launch_leaf_gemm", mode); return; } }
+    if (pl->d == 1) { if (mode == 0) MRA_LG_LAUNCH(1, 0); else if (mode == 1) MRA_LG_LAUNCH(1, 1); else if (mode == 2) MRA_LG_LAUNCH(1, 2); else if (mode == 3) MRA_LG_LAUNCH(1, 3); else if (mode == 4) MRA_LG_LAUNCH(1, 4); else mra_bad_mode("mra_launch_leaf_gemm", mode); }
+    else { if (mode == 0) MRA_LG_LAUNCH(2, 0); else if (mode == 1) MRA_LG_LAUNCH(2, 1); else if (mode == 2) MRA_LG_LAUNCH(2, 2); else if (mode == 3) MRA_LG_LAUNCH(2, 3); else if (mode == 4) MRA_LG_LAUNCH(2, 4); else mra_bad_mode("mra_launch_leaf_gemm", mode); }
 #undef MRA_LG_LAUNCH
 }
 
@@ -95,10 +95,10 @@ void mra_launch_prior_level(mra_plan* pl, const GemmProb* probs, size_t nprob) {
     const dim3 grid((unsigned)nprob);
     // (D == 3: two workgroups per CU, 192 registers - at three the third coordinate takes the 168-register shape's parked epilogue
     // addresses from 60 to 76 bytes of scratch per lane; two cost the 2-D kernel 3 % at config 5)
-#define MRA_PL_LAUNCH(D, MD) hipLaunchKernelGGL((k_leaf_gemm<EPI_COV, D, MD, 2, 4, 256, (MD == 3 || D == 3 ? 2 : MRA_PL_WPE), 1>), grid, dim3(256), 0, pl->stream, probs, pl->kp)
-    if (pl->d == 1) { if (mode == 0) MRA_PL_LAUNCH(1, 0); else if (mode == 1) MRA_PL_LAUNCH(1, 1); else if (mode == 2) MRA_PL_LAUNCH(1, 2); else MRA_PL_LAUNCH(1, 3); }
-    else if (pl->d == 3) { if (mode == 0) MRA_PL_LAUNCH(3, 0); else if (mode == 1) MRA_PL_LAUNCH(3, 1); else if (mode == 2) MRA_PL_LAUNCH(3, 2); else MRA_PL_LAUNCH(3, 3); }
-    else { if (mode == 0) MRA_PL_LAUNCH(2, 0); else if (mode == 1) MRA_PL_LAUNCH(2, 1); else if (mode == 2) MRA_PL_LAUNCH(2, 2); else MRA_PL_LAUNCH(2, 3); }
+#define MRA_PL_LAUNCH(D, MD) hipLaunchKernelGGL((k_leaf_gemm<EPI_COV, D, MD, 2, 4, 256, (MD >= 3 || D == 3 ? 2 : MRA_PL_WPE), 1>), grid, dim3(256), 0, pl->stream, probs, pl->kp)
+    if (pl->d == 1) { if (mode == 0) MRA_PL_LAUNCH(1, 0); else if (mode == 1) MRA_PL_LAUNCH(1, 1); else if (mode == 2) MRA_PL_LAUNCH(1, 2); else if (mode == 3) MRA_PL_LAUNCH(1, 3); else if (mode == 4) MRA_PL_LAUNCH(1, 4); else mra_bad_mode("mra_launch_prior_level", mode); }
+    else if (pl->d == 3) { if (mode == 0) MRA_PL_LAUNCH(3, 0); else if (mode == 1) MRA_PL_LAUNCH(3, 1); else if (mode == 2) MRA_PL_LAUNCH(3, 2); else if (mode == 3) MRA_PL_LAUNCH(3, 3); else if (mode == 4) mra_nu3_prior_level(pl, grid, probs); else mra_bad_mode("mra_launch_prior_level", mode); }
+    else { if (mode == 0) MRA_PL_LAUNCH(2, 0); else if (mode == 1) MRA_PL_LAUNCH(2, 1); else if (mode == 2) MRA_PL_LAUNCH(2, 2); else if (mode == 3) MRA_PL_LAUNCH(2, 3); else if (mode == 4) MRA_PL_LAUNCH(2, 4); else mra_bad_mode("mra_launch_prior_level", mode); }
 #undef MRA_PL_LAUNCH
 }
 

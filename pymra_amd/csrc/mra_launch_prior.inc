@@ -27,7 +27,8 @@ static void launch_cascade(mra_plan* pl, const CascadeArgs& ar) {
     if (mode == 0) launch_cascade_inst<CWT, NLMAX, 0>(pl, ar);
     else if (mode == 1) launch_cascade_inst<CWT, NLMAX, 1>(pl, ar);
     else if (mode == 2) launch_cascade_inst<CWT, NLMAX, 2>(pl, ar);
-    else launch_cascade_inst<CWT, NLMAX, 3>(pl, ar);
+    else if (mode == 3) launch_cascade_inst<CWT, NLMAX, 3>(pl, ar);
+    else mra_bad_mode("the fused prior cascade", mode);      // (mode 4, MRA_KERNEL_MATERN, has no fused instance: path_of keeps it off this path)
 }
 void MRA_TU_NAME(mra_plan* pl, const CascadeArgs& ar) {
     if (pl->CWT == 1) launch_cascade<1, 8>(pl, ar);
@@ -49,7 +50,8 @@ static void launch_knot_chain_cw(mra_plan* pl, const KnotChainArgs& ka) {
     if (mode == 0) launch_knot_chain_inst<CWT, NLMAX, 0>(pl, ka);
     else if (mode == 1) launch_knot_chain_inst<CWT, NLMAX, 1>(pl, ka);
     else if (mode == 2) launch_knot_chain_inst<CWT, NLMAX, 2>(pl, ka);
-    else launch_knot_chain_inst<CWT, NLMAX, 3>(pl, ka);
+    else if (mode == 3) launch_knot_chain_inst<CWT, NLMAX, 3>(pl, ka);
+    else mra_bad_mode("the fused knot chain", mode);
 }
 void MRA_TU_NAME(mra_plan* pl, const KnotChainArgs& ka) {
     if (pl->CWT == 1) launch_knot_chain_cw<1, 8>(pl, ka);

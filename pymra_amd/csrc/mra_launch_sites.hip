@@ -76,49 +76,17 @@ void mra_sites_timed(mra_plan* pl, int which, const std::function<void()>& work)
 }
 static void timed(mra_plan* pl, int which, const std::function<void()>& work) { mra_sites_timed(pl, which, work); }
 
-template <int DIM, int MODE>
-static void launch_basis(mra_plan* pl, long n) {
-    mra_plan::Sites& T = pl->sit;
-    hipLaunchKernelGGL((k_site_basis<DIM, MODE>), dim3((unsigned)n), dim3(64), 0, pl->stream, pl->slv.leaves.p, T.nodes.p, T.chain_ptr.p, T.chain.p,
-                       T.tleaf.p, T.xs.p, pl->W.p, (long)pl->ldw, pl->X.p, pl->kp, T.a.p, (long)T.anc_max * 16);
-}
-template <int DIM, int MODE>
-static void launch_leaf(mra_plan* pl, long n) {
-    mra_plan::Sites& T = pl->sit;
-    hipLaunchKernelGGL((k_site_leaf<DIM, MODE>), dim3((unsigned)n), dim3(64), 0, pl->stream, pl->slv.leaves.p, T.tleaf.p, T.xs.p, pl->X.p, pl->kp,
-                       T.a.p, T.b.p, (long)T.anc_max * 16, T.t.p, (long)T.nop_max * 16, T.var.p);
-}
-template <int DIM, int MODE>
-static void launch_mean(mra_plan* pl, long n, int nc) {
-    mra_plan::Sites& T = pl->sit;
-    hipLaunchKernelGGL((k_site_mean<DIM, MODE>), dim3((unsigned)n), dim3(64), 0, pl->stream, pl->slv.leaves.p, T.tleaf.p, T.xs.p, pl->X.p, pl->kp,
-                       T.a.p, (long)T.anc_max * 16, nc, T.mean.p, n * 16);
-}
+#include "mra_launch_sites.inc"      // launch_basis, launch_leaf, launch_mean, launch_gram, launch_leaf_gram, launch_cv_gram <DIM, MODE>
 
-template <int DIM, int MODE>
-static void launch_gram(mra_plan* pl, long n, long tile0, long rows, bool post) {
-    mra_plan::Sites& T = pl->sit;
-    const dim3 grid((unsigned)n, (unsigned)rows);
-    if (post)
-        hipLaunchKernelGGL((k_site_gram<DIM, MODE, true>), grid, dim3(64), 0, pl->stream, pl->slv.leaves.p, T.nodes.p, T.chain_ptr.p, T.chain.p, T.tleaf.p,
-                           T.xs.p, pl->kp, T.a.p, T.b.p, (long)T.anc_max * 16, T.t.p, (long)T.nop_max * 16, tile0, T.gram.p, n * 16);
-    else
-        hipLaunchKernelGGL((k_site_gram<DIM, MODE, false>), grid, dim3(64), 0, pl->stream, pl->slv.leaves.p, T.nodes.p, T.chain_ptr.p, T.chain.p, T.tleaf.p,
-                           T.xs.p, pl->kp, T.a.p, T.b.p, (long)T.anc_max * 16, T.t.p, (long)T.nop_max * 16, tile0, T.gram.p, n * 16);
-}
-
-// the <DIM, MODE> instance of the plan's dimension and kernel, as the solver's row kernel is chosen
+// the <DIM, MODE> instance of the plan's dimension and kernel, as the solver's row kernel is chosen (<3, 4>: FN_nu3 of mra_launch_nu3.hip)
 #define MRA_SITES_DISPATCH(FN, ...)                                                                                  \
     do {                                                                                                             \
         if (pl->d < 1 || pl->d > 3) throw MraError(MRA_ERR_INVALID, "mra_predict_sites: 1-, 2- or 3-D locations only"); \
-        const int md_ = pl->kp.mode < 0 || pl->kp.mode > 3 ? 3 : pl->kp.mode;                                        \
-        switch ((pl->d - 1) * 4 + md_) {                                                                             \
-            case 0: FN<1, 0>(__VA_ARGS__); break; case 1: FN<1, 1>(__VA_ARGS__); break;                              \
-            case 2: FN<1, 2>(__VA_ARGS__); break; case 3: FN<1, 3>(__VA_ARGS__); break;                              \
-            case 4: FN<2, 0>(__VA_ARGS__); break; case 5: FN<2, 1>(__VA_ARGS__); break;                              \
-            case 6: FN<2, 2>(__VA_ARGS__); break; case 7: FN<2, 3>(__VA_ARGS__); break;                              \
-            case 8: FN<3, 0>(__VA_ARGS__); break; case 9: FN<3, 1>(__VA_ARGS__); break;                              \
-            case 10: FN<3, 2>(__VA_ARGS__); break; default: FN<3, 3>(__VA_ARGS__); break;                            \
+        if (pl->kp.mode < 0 || pl->kp.mode > 4) mra_bad_mode("mra_predict_sites", pl->kp.mode);                                                   \
+        switch ((pl->d - 1) * 5 + pl->kp.mode) {                                                                     \
+            case 0: FN<1, 0>(__VA_ARGS__); break; case 1: FN<1, 1>(__VA_ARGS__); break; case 2: FN<1, 2>(__VA_ARGS__); break; case 3: FN<1, 3>(__VA_ARGS__); break; case 4: FN<1, 4>(__VA_ARGS__); break;\
+            case 5: FN<2, 0>(__VA_ARGS__); break; case 6: FN<2, 1>(__VA_ARGS__); break; case 7: FN<2, 2>(__VA_ARGS__); break; case 8: FN<2, 3>(__VA_ARGS__); break; case 9: FN<2, 4>(__VA_ARGS__); break;\
+            case 10: FN<3, 0>(__VA_ARGS__); break; case 11: FN<3, 1>(__VA_ARGS__); break; case 12: FN<3, 2>(__VA_ARGS__); break; case 13: FN<3, 3>(__VA_ARGS__); break; case 14: FN##_nu3(__VA_ARGS__); break;\
         }                                                                                                            \
     } while (0)
 
@@ -165,24 +133,6 @@ void mra_sites_draw_reserve(mra_plan* pl, long n, size_t g_doubles, long n_leave
     if (T.invd.n < (size_t)n * 256) T.invd.alloc((size_t)n * 256);
     if (T.dprob.n < (size_t)n_leaves) { T.dprob.alloc((size_t)n_leaves); T.dn.alloc((size_t)n_leaves); }
     if (!T.derr.n) T.derr.alloc(1);
-}
-
-template <int DIM, int MODE>
-static void launch_leaf_gram(mra_plan* pl, long n, int nt_max, bool post) {
-    mra_plan::Sites& T = pl->sit;
-    const dim3 grid((unsigned)n, (unsigned)nt_max);
-    const long as = (long)T.anc_max * 16, ts = (long)T.nop_max * 16;
-    if (post) {
-        hipLaunchKernelGGL((k_site_inert<MODE, true>), dim3((unsigned)n), dim3(64), 0, pl->stream, pl->slv.leaves.p, T.tleaf.p, pl->kp, T.a.p, as, T.t.p, ts,
-                           T.sslot.p, T.live.p);
-        hipLaunchKernelGGL((k_site_leaf_gram<DIM, MODE, true>), grid, dim3(64), 0, pl->stream, pl->slv.leaves.p, T.tleaf.p, T.dtile.p, T.xs.p, pl->kp,
-                           T.a.p, as, T.t.p, ts, T.live.p, T.G.p);
-    } else {
-        hipLaunchKernelGGL((k_site_inert<MODE, false>), dim3((unsigned)n), dim3(64), 0, pl->stream, pl->slv.leaves.p, T.tleaf.p, pl->kp, T.a.p, as, T.t.p, ts,
-                           T.sslot.p, T.live.p);
-        hipLaunchKernelGGL((k_site_leaf_gram<DIM, MODE, false>), grid, dim3(64), 0, pl->stream, pl->slv.leaves.p, T.tleaf.p, T.dtile.p, T.xs.p, pl->kp,
-                           T.a.p, as, T.t.p, ts, T.live.p, T.G.p);
-    }
 }
 
 static void check_batch(const mra_plan* pl, long n) {
@@ -264,13 +214,6 @@ void mra_cv_loo(mra_plan* pl, long n) {
         hipLaunchKernelGGL(k_cv_loo, dim3((unsigned)((n * 16 + 255) / 256)), dim3(256), 0, pl->stream, T.sslot.p, n * 16, T.var.p, T.mean.p, mra_cv_rows(pl),
                            mra_cv_out(pl), T.derr.p);
     });
-}
-
-template <int DIM, int MODE>
-static void launch_cv_gram(mra_plan* pl, long n, int nt_max) {
-    mra_plan::Sites& T = pl->sit;
-    hipLaunchKernelGGL((k_cv_gram<DIM, MODE>), dim3((unsigned)n, (unsigned)nt_max), dim3(64), 0, pl->stream, pl->slv.leaves.p, T.tleaf.p, T.dtile.p, T.xs.p, pl->kp,
-                       T.a.p, T.b.p, (long)T.anc_max * 16, T.t.p, (long)T.nop_max * 16, T.sslot.p, mra_cv_rows(pl), T.G.p);
 }
 
 void mra_cv_gram(mra_plan* pl, long n, int nt_max) {

@@ -163,7 +163,9 @@ static void launch_rows(mra_plan* pl) {
         case 0: MRA_SOLVE_ROWS(0); break;
         case 1: MRA_SOLVE_ROWS(1); break;
         case 2: MRA_SOLVE_ROWS(2); break;
-        default: MRA_SOLVE_ROWS(3); break;
+        case 3: MRA_SOLVE_ROWS(3); break;
+        case 4: if constexpr (DIM != 3) MRA_SOLVE_ROWS(4); else mra_nu3_solve_rows(pl); break;      // (3-D: the instance of mra_launch_nu3.hip)
+        default: mra_bad_mode("mra_solve", pl->kp.mode);
     }
 #undef MRA_SOLVE_ROWS
 }

@@ -185,9 +185,38 @@ static void derive_kernel_params(KernelParams& kp) {
         case 2: c = 2.23606797749979; kp.a1 = 1.0; kp.a2 = 1.0 / 3.0; break;
         case 3: kp.mode = 1; break;
         case 5: kp.mode = 3; kp.amp = kp.scale; break;                // KanterCovFun(radius = l)
-        default: kp.mode = 2; kp.amp = kp.scale; break;
+        case MRA_KERNEL_MATERN:                                       // the caller has set kp.nu (and owns kp.nu_tab / nu_n)
+            kp.mode = 4; c = std::sqrt(2.0 * kp.nu);
+            kp.nu_a = kp.nu < 1.0 ? std::tgamma(1.0 - kp.nu) / (std::tgamma(1.0 + kp.nu) * std::pow(4.0, kp.nu)) : 0.0;
+            break;
+        default: kp.mode = 2; kp.amp = kp.scale; break;               // Iden (callers refuse unknown kinds before they get here)
     }
     kp.c_inv_l = c / kp.l;
+}
+
+// MRA_KERNEL_MATERN: the nodes of the trapezoid rule for K_nu(t) = int_0^inf exp(-t cosh u) cosh(nu u) du (matern_nu_of_t, mra_kernels.h),
+// pairs (cosh(k h), c h cosh(nu k h)) with c = 2^(1-nu) / Gamma(nu) and the weight halved at k = 0.  h = 0.2 and 191 nodes (u <= 38):
+// 1.1e-14 absolute on M_nu for 0.1 <= nu <= 5 and t >= 2^-40; h = 0.25 is 3e-12 at nu = 5.
+static const int MRA_NU_NODES = 191;
+static const double MRA_NU_H = 0.2;
+static std::vector<double> matern_nu_table(double nu) {
+    std::vector<double> t((size_t)2 * MRA_NU_NODES);
+    const double c = std::exp((1.0 - nu) * 0.6931471805599453 - std::lgamma(nu));
+    for (int k = 0; k < MRA_NU_NODES; ++k) {
+        const double u = k * MRA_NU_H;
+        t[2 * k] = std::cosh(u);
+        t[2 * k + 1] = (k ? 1.0 : 0.5) * (c * MRA_NU_H * std::cosh(nu * u));
+    }
+    return t;
+}
+// kind and parameters of mra_plan_set_kernel / mra_eval_kernel, checked before anything changes
+static void check_kernel_params(const char* who, int kind, const double* params, int n) {
+    const std::string w(who);
+    if (kind < 0 || kind > MRA_KERNEL_MATERN || n < 3) throw MraError(MRA_ERR_INVALID, w + ": unknown kernel kind or too few parameters (need l, sig, scale)");
+    if (kind != MRA_KERNEL_MATERN) return;
+    if (n < 5) throw MraError(MRA_ERR_INVALID, w + ": MRA_KERNEL_MATERN takes {l, sig, scale, circular, nu}");
+    if (!std::isfinite(params[4]) || params[4] < 0.1 || params[4] > 5.0) throw MraError(MRA_ERR_INVALID, w + ": nu must lie in [0.1, 5]");
+    if (!(params[0] > 0.0)) throw MraError(MRA_ERR_INVALID, w + ": length scale must be positive");
 }
 
 static int fail(mra_plan* p, const MraError& e) {
@@ -1501,7 +1530,8 @@ static bool ensure_lik_general(mra_plan* pl) {
 
 // ---- the route of a pass (PassRoute, mra_plan_types.h) ---------------------------------------------------------------------------
 static PassPath path_of(const mra_plan* pl) {
-    if (pl->regular && pl->use_fused && !pl->host_cov) return PassPath::Fused;
+    // (MRA_KERNEL_MATERN, mode 4: the fused cascades have no instance of it - DESIGN.md section 23 - so its regular trees take the prior level by level)
+    if (pl->regular && pl->use_fused && !pl->host_cov && pl->kp.mode != 4) return PassPath::Fused;
     return (pl->regular_hi && pl->use_fused && !pl->host_cov) ? PassPath::Hi : PassPath::Levels;     // (sharded plans too: the walk is per row tile)
 }
 
@@ -3280,10 +3310,16 @@ int mra_plan_set_kernel(mra_plan* pl, int kind, const double* params, int n) {
             throw MraError(MRA_ERR_INVALID, "mra_plan_set_kernel: MRA_KERNEL_HOST on a plan with a metric (such plans never read coordinates; mra_plan_set_metric(NULL) first)");
         if (pl->metric_on && kind != MRA_KERNEL_HOST && params && n >= 4 && params[3] != 0.0)
             throw MraError(MRA_ERR_INVALID, "mra_plan_set_kernel: circular distances on a plan with a metric (the torus has period 1 in the raw coordinate)");
+        if (kind != MRA_KERNEL_HOST) {       // refusals leave the previous kernel and everything retained in place
+            require(params, "mra_plan_set_kernel: params is NULL");
+            check_kernel_params("mra_plan_set_kernel", kind, params, n);
+            if (!(params[0] > 0.0)) throw MraError(MRA_ERR_INVALID, "length scale must be positive");
+            if (n >= 4 && params[3] != 0.0 && pl->d != 1) throw MraError(MRA_ERR_INVALID, "circular distances are defined for 1-D locations only");
+        } else if (!pl->have_obs) throw MraError(MRA_ERR_STATE, "MRA_KERNEL_HOST needs mra_plan_set_obs first (leaf blocks are per observed row)");
+        // every refusal is above: from here on the call goes through
         pl->slv.valid = false;
         prior_keep_reset(pl);                // on every call: the values are not compared
         if (kind == MRA_KERNEL_HOST) {
-            if (!pl->have_obs) throw MraError(MRA_ERR_STATE, "MRA_KERNEL_HOST needs mra_plan_set_obs first (leaf blocks are per observed row)");
             HIP_TRY(mraSetDevice(pl->device));
             // one padded block per node: non-leaf N_j x cw, leaf N_j x nop; leaves also C(x,x) per row
             pl->cov_off.assign(pl->n_nodes + 1, 0);
@@ -3314,12 +3350,16 @@ int mra_plan_set_kernel(mra_plan* pl, int kind, const double* params, int n) {
             pl->have_kernel = true;
             return MRA_OK;
         }
-        require(params, "mra_plan_set_kernel: params is NULL");
-        if (kind < 0 || kind > MRA_KERNEL_KANTER || n < 3) throw MraError(MRA_ERR_INVALID, "unknown kernel kind or too few parameters (need l, sig, scale)");
-        if (!(params[0] > 0.0)) throw MraError(MRA_ERR_INVALID, "length scale must be positive");
+        if (kind == MRA_KERNEL_MATERN && (pl->nu_tab.n == 0 || pl->nu_tab_nu != params[4])) {      // a change of l, sig or scale uploads nothing
+            HIP_TRY(mraSetDevice(pl->device));
+            pl->nu_tab.upload(matern_nu_table(params[4]));
+            pl->nu_tab_nu = params[4];
+        }
+        pl->kp.nu = kind == MRA_KERNEL_MATERN ? params[4] : 0.0; pl->kp.nu_a = 0.0;
+        pl->kp.nu_tab = kind == MRA_KERNEL_MATERN ? pl->nu_tab.p : nullptr;
+        pl->kp.nu_n = kind == MRA_KERNEL_MATERN ? MRA_NU_NODES : 0;
         pl->kp.kind = kind; pl->kp.d = pl->d; pl->kp.l = params[0]; pl->kp.sig = params[1]; pl->kp.scale = params[2];
         pl->kp.circular = (n >= 4 && params[3] != 0.0) ? 1 : 0;
-        if (pl->kp.circular && pl->d != 1) throw MraError(MRA_ERR_INVALID, "circular distances are defined for 1-D locations only");
         derive_kernel_params(pl->kp);
         pl->host_cov = false;
         pl->have_kernel = true;
@@ -3508,6 +3548,7 @@ int mra_get_buffer(mra_plan* pl, int what, double* out, int64_t cap, int64_t* n_
         else if (what == 6) { src = pl->kstamps2.p; n = (int64_t)pl->kstamps2.n; } // same, fused leaf solve + update
         else if (what == 4) { src = pl->tstamps.p; n = (int64_t)pl->tstamps.n; }   // same, leaf row solves   // same, predictive cascade
         else if (what == 13) { src = pl->X.p; n = (int64_t)pl->P * pl->d; }         // the coordinates as the kernels read them (A x under mra_plan_set_metric)
+        else if (what == 16) { src = pl->kp.nu_tab; n = pl->kp.mode == 4 ? 2 * (int64_t)pl->kp.nu_n : 0; }     // the quadrature table of MRA_KERNEL_MATERN, as the kernels are handed it
         else if (what == 11) { src = pl->y.p; n = pl->P; }                         // the observations as the device holds them (the pseudo-observations t after mra_plan_fit_laplace)
         else throw MraError(MRA_ERR_INVALID, "unknown buffer id");
         *n_avail = n;
@@ -3688,12 +3729,14 @@ int mra_plan_prepare(mra_plan* pl, int64_t* n_kernels) {
                             (const void*)k_parent_front<8>, (const void*)k_parent_front<12>, (const void*)k_parent_front_pair<17>,
                             (const void*)k_parent_front_pair<23>, (const void*)k_leaf_solve_update<8, 13, true>});
         if (pl->regular) {
-            CascadeArgs ar{};
-            ar.n_wg = 1;
-            launch_cascade_any(pl, ar);
-            KnotChainArgs ka{};
-            ka.nl = 1;
-            launch_knot_chain(pl, ka);
+            if (pl->kp.mode != 4) {          // (MRA_KERNEL_MATERN has no fused prior: path_of never takes these two)
+                CascadeArgs ar{};
+                ar.n_wg = 1;
+                launch_cascade_any(pl, ar);
+                KnotChainArgs ka{};
+                ka.nl = 1;
+                launch_knot_chain(pl, ka);
+            }
             PredArgs pa{};
             pa.n_wg = 1;
             launch_predict_any(pl, pa, 0);
@@ -3759,17 +3802,23 @@ int mra_plan_info(mra_plan* pl, int64_t* out, int cap) {
 int mra_eval_kernel(int kind, const double* params, int n_params, const double* D, int64_t n, double* out) {
     return guarded(nullptr, [&] {
         require(params && D && out, "mra_eval_kernel: params, D or out is NULL");
-        require(n_params >= 3 && n > 0 && kind >= 0 && kind <= MRA_KERNEL_KANTER, "mra_eval_kernel: unknown kernel kind, too few parameters or n <= 0");
+        require(n > 0, "mra_eval_kernel: n <= 0");
+        check_kernel_params("mra_eval_kernel", kind, params, n_params);
         KernelParams kp{};
         kp.kind = kind; kp.d = 1; kp.l = params[0]; kp.sig = params[1]; kp.scale = params[2];
         kp.circular = (n_params >= 4 && params[3] != 0.0) ? 1 : 0;
+        if (kind == MRA_KERNEL_MATERN) kp.nu = params[4];
         derive_kernel_params(kp);
         if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN: nothing runs in this mode");
-        DevVec<double> dD, dO;
+        DevVec<double> dD, dO, dT;
         dD.alloc(n);
         dO.alloc(n);
         HIP_TRY(mraMemcpy(dD.p, D, n * sizeof(double), hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(k_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dD.p, dO.p, (long)n, kp);
+        if (kind == MRA_KERNEL_MATERN) {     // a kernel of its own: k_eval_kernel and the runtime cov_of_dist keep their object code
+            dT.upload(matern_nu_table(kp.nu));
+            kp.nu_tab = dT.p; kp.nu_n = MRA_NU_NODES;
+            hipLaunchKernelGGL(k_eval_kernel_nu, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dD.p, dO.p, (long)n, kp);
+        } else hipLaunchKernelGGL(k_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dD.p, dO.p, (long)n, kp);
         HIP_TRY(hipGetLastError());
         HIP_TRY(mraMemcpy(out, dO.p, n * sizeof(double), hipMemcpyDeviceToHost));
         return MRA_OK;

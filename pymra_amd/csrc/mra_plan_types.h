@@ -79,6 +79,10 @@ struct MraError {
     std::string msg;
     MraError(int c, const std::string& m) : code(c), msg(m) {}
 };
+// the end of every dispatch chain over KernelParams::mode: a mode without an instance is an error, never another family's kernel
+[[noreturn]] static inline void mra_bad_mode(const char* who, int mode) {
+    throw MraError(MRA_ERR_STATE, std::string(who) + ": no kernel instance for covariance mode " + std::to_string(mode));
+}
 
 enum KFam {
     KF_PRIOR_RESID = 0, KF_PRIOR_CHOL, KF_PRIOR_TRSM, KF_LEAF_RESID, KF_LEAF_CHOL, KF_LEAF_SYRK,
@@ -380,6 +384,8 @@ struct mra_plan {
     uint32_t run_flags = 0;
     KernelParams kp{};
     bool host_cov = false;
+    DevVec<double> nu_tab;              // MRA_KERNEL_MATERN: the quadrature table kp.nu_tab points at, built for nu_tab_nu (host memory on
+    double nu_tab_nu = 0.0;             // MRA_HOST_DRYRUN plans); set_kernel rebuilds it when nu changes and at no other time
     double R = 0.0;
     // the metric of mra_plan_set_metric: while metric_on the kernels' X (and the knot coordinates of the fused levels) hold A x and
     // Xraw the caller's coordinates; knot_raw[m] = the untransformed knot coordinates of fused level m as set_knot_coords lays them
@@ -805,6 +811,19 @@ struct KTimer {
 
 // ---- dispatchers defined in the mra_launch_*.hip translation units ----------------------------------------------------
 // batched C (=|-=) f(A B^T) with epilogue EPI_SET / EPI_SUB / EPI_COV / EPI_HOSTCOV; lower_tri: every problem has .lower set and M == N
+// mra_launch_nu3.hip: MRA_KERNEL_MATERN (covariance mode 4) on 3-D coordinates - the launches the dispatch chains of the other units
+// hand their <3, 4> case to, with the grids they computed
+void mra_nu3_gemm(mra_plan* pl, bool lds, dim3 grid, const GemmProb* probs, unsigned gxs, unsigned gy, unsigned S);
+void mra_nu3_leaf_gemm(mra_plan* pl, bool wide, dim3 grid, const GemmProb* probs);
+void mra_nu3_prior_level(mra_plan* pl, dim3 grid, const GemmProb* probs);
+void mra_nu3_solve_rows(mra_plan* pl);
+void mra_nu3_cov_rows(mra_plan* pl);
+void launch_basis_nu3(mra_plan* pl, long n);
+void launch_leaf_nu3(mra_plan* pl, long n);
+void launch_mean_nu3(mra_plan* pl, long n, int nc);
+void launch_gram_nu3(mra_plan* pl, long n, long tile0, long rows, bool post);
+void launch_leaf_gram_nu3(mra_plan* pl, long n, int nt_max, bool post);
+void launch_cv_gram_nu3(mra_plan* pl, long n, int nt_max);
 void mra_launch_gemm(mra_plan* pl, int epi, const GemmProb* probs, size_t nprob, long maxM, long maxN, bool allow_lds = true, bool lower_tri = false);
 void mra_launch_leaf_gemm(mra_plan* pl, int epi, const GemmProb* probs, size_t nprob);
 void mra_launch_syrk_blk(mra_plan* pl, const GemmProb* probs, size_t nprob, long M, bool dma);

@@ -190,6 +190,7 @@ __global__ __launch_bounds__(64, 4) void k_site_leaf(const SolveLeaf* __restrict
 
 // ---- 3. chain: parent up to root, p_j = Lt_j^-1 b[own], b[ancestors of j] -= Zt_j p_j, var += |p_j|^2 --------------------------------
 // The solver's forward sweep (k_solve_front_fwd) on one chain, in place in b.
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_sites.hip */
 __global__ __launch_bounds__(64, 4) void k_site_chain(const SolveLeaf* __restrict__ lv, const SiteNode* __restrict__ nodes,
                                                       const int* __restrict__ chain_ptr, const int* __restrict__ chain,
                                                       const int* __restrict__ tile_leaf, double* __restrict__ b_buf, long a_stride,
@@ -229,6 +230,7 @@ __global__ __launch_bounds__(64, 4) void k_site_chain(const SolveLeaf* __restric
     }
     if (q == 0) gst(var + tile * 16 + r, gld(var + tile * 16 + r) + v);
 }
+#endif
 
 // ---- 4. mean: mean[site, 0:16] = a(site)^T beta + C(site, o) q ------------------------------------------------------------------------
 // k_solve_rows with a(s) in place of a row of W: the 16 sites are the M side here, the 16 observation vectors the N side.  Columns
@@ -440,6 +442,7 @@ __global__ __launch_bounds__(64, 4) void k_site_leaf_gram(const SolveLeaf* __res
 // the leaf draws of a block of 16 samples, staged once per leaf: zl[site * 16 + s] = zeta of the site's own slot n_coarse + (the
 // caller's index of the site) - Philox exactly as k_sample_draw, or the caller's value (zin, same layout) - and 0 for padding sites,
 // inert sites and samples past the block's count
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_sites.hip */
 __global__ __launch_bounds__(256) void k_site_zeta(SampleZ zs, long n_coarse, const long* __restrict__ sslot, const int* __restrict__ live,
                                                    const double* __restrict__ zin, long n_sites, double* __restrict__ zl) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -451,6 +454,7 @@ __global__ __launch_bounds__(256) void k_site_zeta(SampleZ zs, long n_coarse, co
         v = zin ? gld(zin + i) : philox_normal(zs.seed, (unsigned long long)(n_coarse + sslot[u]), (unsigned long long)(zs.sample0 + s));
     zl[i] = v;
 }
+#endif
 
 // One wave per (tile, block of 16 samples): the 16 sites are M, the samples N; lane (r, q) leaves (site q + 4 j, sample r).
 //   coarse term  over the leaf's chain: X[rows of block j]^T zc[slots of j] - X in x16 form (the A operand of k-step s is row k of X at
@@ -459,6 +463,7 @@ __global__ __launch_bounds__(256) void k_site_zeta(SampleZ zs, long n_coarse, co
 //                diagonal tile masked (k_panel_chol leaves that part of the block as it was)
 //   mean         the posterior mean of the plan's own observations (k_site_mean's column 0), added last; nullptr: none
 // out[sample * ldo + tile * 16 + site].
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_sites.hip */
 __global__ __launch_bounds__(64, 4) void k_site_draw(const int* __restrict__ tile_leaf, const SiteDrawTile* __restrict__ dt,
                                                      const int* __restrict__ dchain_ptr, const SiteDrawChain* __restrict__ dchain,
                                                      const double* __restrict__ x_buf, long a_stride, const double* __restrict__ zc,
@@ -501,6 +506,7 @@ __global__ __launch_bounds__(64, 4) void k_site_draw(const int* __restrict__ til
         gst(out + (long)r * ldo + u, mean ? acc[j] + gld(mean + u) : acc[j]);
     }
 }
+#endif
 
 // ---- 7. cross-validation from the retained factors (mra_cv) -----------------------------------------------------
 // The sites are the plan's own observed rows, tiled by leaf: sslot[tile * 16 + k] = the padded row of the column (-1: padding).  After the
@@ -514,6 +520,7 @@ static const int CV_BLOCKS = 1024;          // partial results of the reduction:
 __device__ __forceinline__ double cv_noise(const CvRows& c, long p) { return c.noise ? c.noise[p] : c.R; }
 
 // the coordinates of a batch's sites out of the plan's rows; padding columns repeat their tile's first site (as sites_gather)
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_sites.hip */
 __global__ __launch_bounds__(256) void k_cv_sites(const long* __restrict__ sslot, const double* __restrict__ X, int d, long n_sites,
                                                   double* __restrict__ xs) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -522,8 +529,10 @@ __global__ __launch_bounds__(256) void k_cv_sites(const long* __restrict__ sslot
     if (p < 0) p = sslot[i & ~15L];
     for (int k = 0; k < d; ++k) xs[i * d + k] = X[p * d + k];
 }
+#endif
 
 // leave one out: every observed row its own group, so N_G = r (1 - h).  1 - h <= 0 or NaN: err = the largest such padded row + 1.
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_sites.hip */
 __global__ __launch_bounds__(256) void k_cv_loo(const long* __restrict__ sslot, long n_sites, const double* __restrict__ v,
                                                 const double* __restrict__ m, CvRows c, CvOut o, int* __restrict__ err) {
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -536,6 +545,7 @@ __global__ __launch_bounds__(256) void k_cv_loo(const long* __restrict__ sslot, 
     o.mean[p] = y - e; o.var[p] = S; o.lpd[p] = -0.5 * (CV_LOG_2PI + log(S) + e * e / S);
     o.h[p] = h; o.rho[p] = rho;
 }
+#endif
 
 // One wave per 16 x 16 block on or below the diagonal of a leaf's N_G = diag(r) - [p^T p - a^T a - t^T t + C(s_u, s_w)]: tile I =
 // blockIdx.x of the batch (M), tile J = the leaf's blockIdx.y-th (N).  k_site_leaf_gram's operand pattern (both operands rows of x16
@@ -605,6 +615,7 @@ __global__ __launch_bounds__(64, 4) void k_cv_gram(const SolveLeaf* __restrict__
 // One wave per group, after k_panel_chol left N_G = L L^T in the group's block: w = L^-1 rho_G in column 0 of an x16 array (the other
 // columns are zero), and the group's joint log predictive density -1/2 [2 sum log r - log det N_G + |w|^2 + |G| log 2 pi] at its node.
 // dn: k_panel_chol's 2 sum log diag L per group of the batch (padding rows are the identity and add 0).
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_sites.hip */
 __global__ __launch_bounds__(64, 4) void k_cv_fwd(const CvGroup* __restrict__ groups, const long* __restrict__ sslot,
                                                   const double* __restrict__ m, CvRows c, const double* __restrict__ G,
                                                   const double* __restrict__ dn, double* __restrict__ w_buf, double* __restrict__ group_lpd) {
@@ -632,11 +643,13 @@ __global__ __launch_bounds__(64, 4) void k_cv_fwd(const CvGroup* __restrict__ gr
     for (int k = 32; k > 0; k >>= 1) { s += __shfl_xor(s, k, 64); cnt += __shfl_xor(cnt, k, 64); }
     if (lane == 0) group_lpd[g.node] = -0.5 * (2.0 * s - dn[blockIdx.x] + quad + cnt * CV_LOG_2PI);
 }
+#endif
 
 // One wave per (group, column tile c): X_c = L^-1 E_c by forward substitution (its rows above tile c are zero and are not computed: the
 // trailing block of L is solved), then for the tile's rows diag(N^-1)_p = the column sums of squares of X_c and (N^-1 rho)_p = X_c[:, p]^T w
 // - N^-1 = L^-T L^-1, so no backward substitution is run.  y_p - mu_p = r_p (N^-1 rho)_p, S_pp = r_p^2 diag(N^-1)_p.
 // x_buf: the batch's second block buffer, tile c of a group using the rows of the group's block from its own first row on.
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_sites.hip */
 __global__ __launch_bounds__(64, 4) void k_cv_solve(const SiteDrawTile* __restrict__ dt, const long* __restrict__ sslot,
                                                     const double* __restrict__ v, const double* __restrict__ m, CvRows c,
                                                     const double* __restrict__ G, const double* __restrict__ w_buf,
@@ -668,8 +681,10 @@ __global__ __launch_bounds__(64, 4) void k_cv_solve(const SiteDrawTile* __restri
         o.h[p] = v[u] / rr; o.rho[p] = y - m[u];
     }
 }
+#endif
 
 // leave one out: a leaf's group value is the sum of its rows' lpd, in row order (one thread per leaf); NaN for a leaf without observations
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_sites.hip */
 __global__ __launch_bounds__(256) void k_cv_leaf_sum(const int* __restrict__ leaf_node, const long* __restrict__ leaf_row, int n_leaves,
                                                      const double* __restrict__ lpd, double* __restrict__ group_lpd) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -682,10 +697,12 @@ __global__ __launch_bounds__(256) void k_cv_leaf_sum(const int* __restrict__ lea
     }
     if (any) group_lpd[leaf_node[t]] = s;
 }
+#endif
 
 // Per workgroup {rows, sum lpd, sum (y - mu)^2 / S, max h, sum (1 - h) / r, sum (rho / r)^2, sum of the groups' values}: a thread walks
 // its rows (then its nodes) in order, the workgroup folds its 256 values in a fixed tree, as k_laplace_part: the same inputs give the
 // same bits.  A row counts when it was scored (h is not NaN), a node when its group value is not NaN.
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_sites.hip */
 __global__ __launch_bounds__(256) void k_cv_part(CvRows c, CvOut o, long P, const double* __restrict__ group_lpd, int n_nodes,
                                                  double* __restrict__ part) {
     __shared__ double sh[MRA_CV_NRES][256];
@@ -720,7 +737,9 @@ __global__ __launch_bounds__(256) void k_cv_part(CvRows c, CvOut o, long P, cons
     }
     if (threadIdx.x < MRA_CV_NRES) part[(long)blockIdx.x * MRA_CV_NRES + threadIdx.x] = sh[threadIdx.x][0];
 }
+#endif
 // the workgroups' partial results -> res[MRA_CV_NRES]: one wave per result, as k_laplace_sum
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_sites.hip */
 __global__ __launch_bounds__(64 * MRA_CV_NRES) void k_cv_sum(const double* __restrict__ part, int nblk, double* __restrict__ res) {
     __shared__ double sh[MRA_CV_NRES][64];
     const int k = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -740,6 +759,7 @@ __global__ __launch_bounds__(64 * MRA_CV_NRES) void k_cv_sum(const double* __res
     }
     if (lane == 0) res[k] = sh[k][0];
 }
+#endif
 
 // ---- 8. cross-validation with a regression trend (mra_cv_trend) -------------------------------------------------
 // y = X beta + x + eps with a flat prior on beta.  After mra_trend_fit's sweeps trend.m holds the kriging means of [y | X], trend.coef
@@ -752,6 +772,7 @@ __global__ __launch_bounds__(64 * MRA_CV_NRES) void k_cv_sum(const double* __res
 // comes out of L2, 32 KB for all tiles, and only its lower triangle is read - then |w|^2 per row and m[u] += h^T beta^ (the sum in
 // k_trend_rows' order), so that k_cv_loo, k_cv_fwd and k_cv_solve see rho~ = y - m.  add_v: v[u] += |w|^2 as well, which makes
 // k_cv_loo's h the h~ of leaving a row out and estimating beta again.  Padding columns get w = 0 and keep their m and v.
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_sites.hip */
 __global__ __launch_bounds__(64, 4) void k_cv_trend(const long* __restrict__ sslot, const double* __restrict__ X, const double* __restrict__ mX,
                                                     long P, int p, const double* __restrict__ beta, const double* __restrict__ Linv,
                                                     int add_v, double* __restrict__ m, double* __restrict__ v, double* __restrict__ w_buf,
@@ -812,9 +833,11 @@ __global__ __launch_bounds__(64, 4) void k_cv_trend(const long* __restrict__ ssl
         wsq[row] = sq;
     }
 }
+#endif
 
 // One wave per 16 x 16 block on or below the diagonal of a leaf's block, k_cv_gram's grid and operand pattern: N -= W_I W_J^T over the
 // qn = p rounded up to 4 rows of the tiles' W arrays, qn / 4 MFMAs.  Padding rows and columns have w = 0 and stay the identity.
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_sites.hip */
 __global__ __launch_bounds__(64, 4) void k_cv_downdate(const SiteDrawTile* __restrict__ dt, const double* __restrict__ w_buf, int qn,
                                                        double* __restrict__ G) {
     const long I = blockIdx.x;
@@ -837,11 +860,13 @@ __global__ __launch_bounds__(64, 4) void k_cv_downdate(const SiteDrawTile* __res
 #pragma unroll
     for (int j = 0; j < 4; ++j) gst(o + (long)(q + 4 * j) * ld, acc[j]);
 }
+#endif
 
 // The trend's share of the reduction, in the pattern of k_cv_part / k_cv_sum: per workgroup {tr K^-1 = sum (1 - v / r) / r,
 // tr P = sum (1 - (v + |w|^2) / r) / r, max (v + |w|^2) / r} over the scored rows.  h_has_w: the rows' h is h~ already (k_cv_trend added
 // |w|^2 to v), else it is v / r.
 constexpr int MRA_CVT_NRES = 3;
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_sites.hip */
 __global__ __launch_bounds__(256) void k_cv_trend_part(CvRows c, CvOut o, const double* __restrict__ wsq, int h_has_w, long P,
                                                        double* __restrict__ part) {
     __shared__ double sh[MRA_CVT_NRES][256];
@@ -889,3 +914,4 @@ __global__ __launch_bounds__(64 * MRA_CVT_NRES) void k_cv_trend_sum(const double
     }
     if (lane == 0) res[k] = sh[k][0];
 }
+#endif

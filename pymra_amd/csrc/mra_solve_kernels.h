@@ -66,6 +66,7 @@ __global__ __launch_bounds__(64, 4) void k_solve_leaf_trsm(const SolveLeaf* __re
 
 // ---- leaves: products with Ut, one workgroup of four waves per leaf ------------------------------------------------------------
 // Forward: g = Ut_anc U_y (anc x16).
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_solve.hip */
 __global__ __launch_bounds__(256, 4) void k_solve_leaf_g(const SolveLeaf* __restrict__ lv) {
     const SolveLeaf L = lv[blockIdx.x];
     const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4, nop = L.nop;
@@ -80,9 +81,11 @@ __global__ __launch_bounds__(256, 4) void k_solve_leaf_g(const SolveLeaf* __rest
         for (int j = 0; j < 4; ++j) gst(L.gb + (long)(at * 16 + q + 4 * j) * 16 + r, acc[j]);
     }
 }
+#endif
 
 // Backward: s = U_y - Ut_anc^T alpha_chain in place (nop x16; phantom observations stay 0), then beta = alpha_chain - Ut_anc s
 // (anc x16, over g).  A leaf without observations has beta = alpha_chain.
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_solve.hip */
 __global__ __launch_bounds__(256, 4) void k_solve_leaf_sbeta(const SolveLeaf* __restrict__ lv) {
     const SolveLeaf L = lv[blockIdx.x];
     const int lane = threadIdx.x & 63, r = lane & 15, q = lane >> 4, nop = L.nop, w = threadIdx.x >> 6;
@@ -117,6 +120,7 @@ __global__ __launch_bounds__(256, 4) void k_solve_leaf_sbeta(const SolveLeaf* __
         for (int j = 0; j < 4; ++j) gst(L.gb + (long)(at * 16 + q + 4 * j) * 16 + r, acc[j]);
     }
 }
+#endif
 
 // ---- fronts: one workgroup per node, one launch per level (latency kernels, like k_front) ---------------------------------------
 // cw x16 substitution by wave 0: lane (c, q) sums the terms j = q (mod 4) of a row, two shuffles add the four partial sums.
@@ -146,6 +150,7 @@ __device__ __forceinline__ void solve_front_subst(const double* __restrict__ F, 
 }
 
 // Forward: f = sum over the children's g; z = Lt^-1 f[own]; g = f[anc] - Zt z.  buf <- [z ; g].
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_solve.hip */
 __global__ __launch_bounds__(256) void k_solve_front_fwd(const SolveFront* __restrict__ fv, const double* const* __restrict__ kids) {
     extern __shared__ double zs[];              // cw x16, then Lt when it is staged
     const SolveFront N = fv[blockIdx.x];
@@ -168,8 +173,10 @@ __global__ __launch_bounds__(256) void k_solve_front_fwd(const SolveFront* __res
         gst(N.buf + e, f);
     }
 }
+#endif
 
 // Backward: alpha = Lt^-T (z - Zt^T alpha_chain).  buf <- [alpha ; alpha_chain].
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_solve.hip */
 __global__ __launch_bounds__(256) void k_solve_front_bwd(const SolveFront* __restrict__ fv) {
     extern __shared__ double zs[];
     const SolveFront N = fv[blockIdx.x];
@@ -186,8 +193,10 @@ __global__ __launch_bounds__(256) void k_solve_front_bwd(const SolveFront* __res
     __syncthreads();
     for (int e = threadIdx.x; e < nall; e += 256) gst(N.buf + e, e < nown ? zs[e] : gld(N.chain + (e - nown)));
 }
+#endif
 
 // ---- quadratic form: Q = sum over segments of sign * V^T V (V: n x16), fixed summation order ------------------------------------
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_solve.hip */
 __global__ __launch_bounds__(256) void k_solve_quad_part(const SolveSeg* __restrict__ segs, int nseg, double* __restrict__ part) {
     const int i = threadIdx.x >> 4, j = threadIdx.x & 15;
     double acc = 0.0;
@@ -204,10 +213,12 @@ __global__ __launch_bounds__(256) void k_solve_quad_sum(const double* __restrict
     for (int b = 0; b < nblk; ++b) acc += part[(long)b * 256 + threadIdx.x];
     quad[threadIdx.x] = acc;
 }
+#endif
 
 // ---- full quadratic form (MRA_SOLVE_FULL_QUAD): the entries between columns of different 16-column blocks ------------------------
 // The forward vectors of a block (every segment's n x16 rows: the leaves' U_y, the fronts' z) are copied into the block's panel of the
 // archive behind its forward sweep, segment sgi at row seg_off[sgi]; one workgroup per segment, the tail of the grid strides on.
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_solve.hip */
 __global__ __launch_bounds__(256) void k_solve_archive(const SolveSeg* __restrict__ segs, const long* __restrict__ seg_off, int nseg,
                                                        double* __restrict__ panel) {
     for (int sgi = blockIdx.x; sgi < nseg; sgi += gridDim.x) {
@@ -216,6 +227,7 @@ __global__ __launch_bounds__(256) void k_solve_archive(const SolveSeg* __restric
         for (int e = threadIdx.x; e < S.n * 16; e += 256) gst(dst + e, gld(S.p + e));
     }
 }
+#endif
 
 // Q_ab = sum over segments of sign * F_a^T F_b for the block pairs of one group: four panels u < v of the archive, their six pairs
 // (0,1) (0,2) (0,3) (1,2) (1,3) (2,3) accumulated side by side so that a row of the archive is read once per launch.  blk[u] < 0: the
@@ -227,6 +239,7 @@ struct QuadGroup { int blk[4]; int out[6]; };
 // operands of those lanes are 0).  The segments are dealt to the workgroups as k_solve_quad_part deals them, a segment's 4-row chunks
 // to the workgroup's four waves in turn; the waves' sums are added in wave order, so part holds gridDim.x partial sums per pair:
 // part[(p * gridDim.x + block) * 256 + i * 16 + j].  No atomics: the same inputs give the same bits.
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_solve.hip */
 __global__ __launch_bounds__(256, 2) void k_solve_quad_cross(const SolveSeg* __restrict__ segs, const long* __restrict__ seg_off, int nseg,
                                                              const double* __restrict__ arch, long panel, QuadGroup G,
                                                              double* __restrict__ part) {
@@ -281,8 +294,10 @@ __global__ __launch_bounds__(256, 2) void k_solve_quad_cross(const SolveSeg* __r
     MRA_QUAD_CROSS_FOLD(3, a12) MRA_QUAD_CROSS_FOLD(4, a13) MRA_QUAD_CROSS_FOLD(5, a23)
 #undef MRA_QUAD_CROSS_FOLD
 }
+#endif
 // The partial sums of a group's pairs folded in block order, one workgroup per pair; the tile of pair (a, b) and its mirror go into the
 // dense ldq x ldq matrix Q (tiles on the diagonal are not touched: k_solve_quad_part / k_solve_quad_sum own them).
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_solve.hip */
 __global__ __launch_bounds__(256) void k_solve_quad_cross_sum(const double* __restrict__ part, int nblk, QuadGroup G, double* __restrict__ Q,
                                                               int ldq) {
     int a = -1, b = -1, want = 0;
@@ -299,12 +314,14 @@ __global__ __launch_bounds__(256) void k_solve_quad_cross_sum(const double* __re
     Q[(long)(a * 16 + i) * ldq + b * 16 + j] = acc;
     Q[(long)(b * 16 + j) * ldq + a * 16 + i] = acc;
 }
+#endif
 
 // ---- trend (mra_trend_fit): universal-kriging mean and variance by padded row ------------------------------
 // m: (1 + p) x P kriging means of [y | X] (row 0: m_y), X: p x P design matrix, both by padded row.  h = x(s) - m_X(s);
 // mean = m_y + h^T beta, var = var_pass + |L^-1 h|^2 with A = L L^T = X^T K^-1 X.  One row per lane, one wave per workgroup: L^-1
 // (64 x 64 doubles, row stride 64) and the lanes' h (hs[j * 64 + lane]: no bank conflicts) in LDS.  Unreported rows get exactly 0.
 #define MRA_TREND_LD 64
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_solve.hip */
 __global__ __launch_bounds__(64) void k_trend_rows(const double* __restrict__ m, const double* __restrict__ X, const double* __restrict__ beta,
                                                    const double* __restrict__ Linv, const double* __restrict__ var_pass,
                                                    const unsigned char* __restrict__ rep, int p, long P, double* __restrict__ mean,
@@ -333,6 +350,7 @@ __global__ __launch_bounds__(64) void k_trend_rows(const double* __restrict__ m,
     mean[s] = r ? mu : 0.0;
     var[s] = r ? var_pass[s] + add : 0.0;
 }
+#endif
 
 // ---- rows: mean[tile, 0:16] = W[tile, anc] beta + C(tile, obs) q, one wave per 16-row tile ---------------------------------------
 // The covariance is evaluated on the fly as the A operand (lane (r, q) evaluates C(x_row r, x_obs q + 4 s)); the Kanter taper goes
@@ -393,6 +411,7 @@ __global__ __launch_bounds__(256, 4) void k_solve_rows(const SolveLeaf* __restri
 // ---- glue ------------------------------------------------------------------------------------------------------------------------
 // pseudo-data of a block of conditional draws, 16 columns at once: Yb[s][p] = y[p] - x_s[p] - sqrt(R) eps_s[p] at observed rows, 0
 // elsewhere (the solve reads observed rows only)
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_solve.hip */
 __global__ __launch_bounds__(256) void k_solve_pseudo(const double* __restrict__ y, const double* __restrict__ x, SampleZ zs, long slot0,
                                                       double sqrtR, double* __restrict__ Yb, long P) {
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -402,7 +421,9 @@ __global__ __launch_bounds__(256) void k_solve_pseudo(const double* __restrict__
     for (int s = 0; s < 16; ++s)
         Yb[(long)s * P + p] = (ob && s < zs.ns) ? yp - x[(long)s * P + p] - sqrtR * sample_z(zs, slot0 + p, s) : 0.0;
 }
+#endif
 // the same with a noise vector: sd[p] = sqrt(r_p) by padded row
+#ifndef MRA_COV_TEMPLATES_ONLY      /* non-template kernels: defined once, in the translation unit of mra_launch_solve.hip */
 __global__ __launch_bounds__(256) void k_solve_pseudo_rows(const double* __restrict__ y, const double* __restrict__ x, SampleZ zs, long slot0,
                                                            const double* __restrict__ sd, double* __restrict__ Yb, long P) {
     const long p = (long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -417,3 +438,4 @@ __global__ __launch_bounds__(256) void k_solve_addmean(double* __restrict__ x, c
     const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) x[i] += mean[i];
 }
+#endif

@@ -418,9 +418,15 @@ class HipPlan:
         res["beta"], res["cov_beta"] = beta[:p].copy(), cov[:p, :p].copy()
         return res
 
-    def set_kernel(self, kind, l, sig=1.0, scale=1.0, circular=False):
-        par = np.array([l, sig, scale, 1.0 if circular else 0.0], dtype=np.float64)
-        self._check(self.lib.mra_plan_set_kernel(self._h, int(kind), _ptr(par), 4))
+    def set_kernel(self, kind, l, sig=1.0, scale=1.0, circular=False, nu=None):
+        """nu: the smoothness of kind 6 (MRA_KERNEL_MATERN), sent behind circular; every other kind ignores it."""
+        par = [l, sig, scale, 1.0 if circular else 0.0] + ([] if nu is None else [nu])
+        par = np.array(par, dtype=np.float64)
+        self._check(self.lib.mra_plan_set_kernel(self._h, int(kind), _ptr(par), len(par)))
+
+    def matern_table(self):
+        """The quadrature table of a kind-6 plan as the device holds it: (n, 2) rows (cosh(k h), c h cosh(nu k h)); (0, 2) otherwise."""
+        return self.buffer(16).reshape(-1, 2)
 
     def set_kernel_host(self):
         """Covariance values will be supplied block by block (``set_cov_block``); call after ``set_obs``."""
@@ -802,13 +808,13 @@ def comm_unique_id() -> bytes:
     return buf.raw
 
 
-def eval_kernel(kind, l, sig, scale, D):
-    """Device evaluation of a stationary kernel on an array of distances (tests)."""
+def eval_kernel(kind, l, sig, scale, D, nu=None):
+    """Device evaluation of a stationary kernel on an array of distances (tests); nu: the smoothness of kind 6."""
     lib = load_library()
     D = np.ascontiguousarray(D, dtype=np.float64).ravel()
     out = np.empty_like(D)
-    par = np.array([l, sig, scale], dtype=np.float64)
-    _check(lib, lib.mra_eval_kernel(int(kind), _ptr(par), 3, _ptr(D), D.size, _ptr(out)))
+    par = np.array([l, sig, scale] + ([] if nu is None else [0.0, nu]), dtype=np.float64)
+    _check(lib, lib.mra_eval_kernel(int(kind), _ptr(par), len(par), _ptr(D), D.size, _ptr(out)))
     return out
 
 
