@@ -42,6 +42,8 @@ extern "C" {
 #define MRA_KERNEL_IDEN        4   /* Iden           [D == 0]                           :256-262 */
 #define MRA_KERNEL_KANTER      5   /* KanterCovFun   compact taper, radius = l          :305-324 */
 #define MRA_KERNEL_MATERN      6   /* Matern(nu)     sig 2^(1-nu)/Gamma(nu) t^nu K_nu(t), t = sqrt(2 nu) D/l :273-277 */
+#define MRA_KERNEL_SUM         7   /* sum of 1..MRA_SUM_MAX of EXP, MATERN32, MATERN52, GAUSSIAN, IDEN: a nested model */
+#define MRA_SUM_MAX            4
 #define MRA_KERNEL_HOST        100 /* values supplied block by block (any cov callable or a dense
                                       matrix, pyMRA/MRANode.py:73-80, 381-384)                   */
 
@@ -177,13 +179,24 @@ int mra_plan_fit_laplace(mra_plan *plan, int family, const double *z_perm, const
  * retained factors.  Every refusal of this call comes before anything of the plan changes (the previous kernel and everything retained
  * stand): circular distances on a plan that is not 1-D or has a metric, l <= 0, and MRA_ERR_INVALID for an
  * unknown kind, n_params < 3 and, for MRA_KERNEL_MATERN, n_params < 5, l <= 0 and a nu that is not finite or outside [0.1, 5].
+ * kind == MRA_KERNEL_SUM: value = scale * sum over c < K of sig_c k_c(D; l_c), a nested model of 1 <= K <= MRA_SUM_MAX structures that share
+ * the plan's distance (dimension, metric, circular).  params = {K, 0, scale, circular, kind_0, l_0, sig_0, ..., kind_{K-1}, l_{K-1},
+ * sig_{K-1}}, n_params >= 4 + 3 K; kind_c is MRA_KERNEL_EXP, MATERN32, MATERN52, GAUSSIAN or IDEN, each evaluated by the formula of its own
+ * kind with sig_c as its sill (for EXP and IDEN too: sig_c = 1 is the single kind) - an IDEN component is sig_c at D == 0 and exactly 0
+ * elsewhere, a micro-scale part of the field, not noise.  The plan derives one record of 6 doubles per component {submode, c / l,
+ * 1 / (2 l^2), a1, a2, scale sig_c} into a device buffer of its own (mra_get_buffer 17), uploaded on every such call - a few hundred
+ * bytes, all that an optimiser's step over ranges and sills sends.  Such plans take the level-by-level prior (mra_get_route) and every
+ * call on the retained factors.  MRA_ERR_INVALID, before anything of the plan changes: K not an integer in 1..MRA_SUM_MAX, n_params <
+ * 4 + 3 K, a component kind outside the five (MRA_KERNEL_KANTER and MRA_KERNEL_MATERN are no components), l_c <= 0 or not finite,
+ * sig_c < 0 or not finite, circular on a plan that is not 1-D or has a metric.
  * kind == MRA_KERNEL_HOST (params ignored, call after mra_plan_set_obs): covariance values come from
  * mra_plan_set_cov_block. */
 int mra_plan_set_kernel(mra_plan *plan, int kind, const double *params, int n_params);
 
 /* Diagnostics: out[i] = scale * k_kind(D[i]; l, sig) evaluated by the device code that the inference
  * kernels inline - the device counterpart of ExpCovFun/Matern32/... applied to D = dist(locs, locs2)
- * (pyMRA/MRATools.py:229-301).  MRA_KERNEL_MATERN takes params = {l, sig, scale, circular, nu} as mra_plan_set_kernel does. */
+ * (pyMRA/MRATools.py:229-301).  MRA_KERNEL_MATERN takes params = {l, sig, scale, circular, nu} and
+ * MRA_KERNEL_SUM {K, 0, scale, circular, kind_0, l_0, sig_0, ...} as mra_plan_set_kernel does. */
 int mra_eval_kernel(int kind, const double *params, int n_params, const double *D, int64_t n, double *out);
 
 /* Replaces: the `cov` callable for anything else (MRA_KERNEL_HOST): the host evaluates
@@ -527,6 +540,8 @@ int mra_cv_trend(mra_plan *plan, uint32_t flags, double *mean_perm, double *var_
  * with their staging and transfers, k_cv_trend, k_cv_downdate);
  * 16: the quadrature table of an MRA_KERNEL_MATERN plan as the device holds it (191 pairs (cosh(k h), c h cosh(nu k h)), h = 0.2,
  * c = 2^(1-nu) / Gamma(nu), the weight halved at k = 0; 0 values while the plan has another kernel);
+ * 17: the component table of an MRA_KERNEL_SUM plan as the device holds it (K records {submode, c / l, 1 / (2 l^2), a1, a2, scale sig_c},
+ * then one value more, C(x, x) = the sum of the records' last entries as the kernels are handed it; 0 values while the plan has another kernel);
  * copies min(capacity, available) doubles into out, returns the available count in *n_avail.
  * (W after a likelihood-only run is complete only with MRA_OPT_LIK_ROWS off: by default such a run computes W at the rows a
  * likelihood needs - the observed rows, and the knots on the level-by-level path - and leaves the others as they were.) */

@@ -17,8 +17,10 @@ The device path adds one thing: when a kernel is called with the *symbolic* loca
 that ``MRATree`` uses to probe a user's ``cov`` callable, it returns a ``KernelSpec`` (kind +
 parameters, closed under multiplication by a scalar such as ``sigma*mt.Matern32(...)``,
 cf. pyMRA/tests/test-param-est.py:84) instead of numbers; ``MRATree`` then evaluates that
-kernel on the GPU.  Any callable that does not produce a ``KernelSpec`` is treated as an
-opaque function and evaluated on the host block by block.
+kernel on the GPU.  Specs add: ``mt.Matern32(a, b, l=.05, sig=.6) + mt.ExpCovFun(a, b, l=.8)`` is a
+``KernelSum`` of up to four structures, a nested model that the device evaluates as one kernel
+(DESIGN.md section 24).  Any callable that produces neither is treated as an opaque function
+and evaluated on the host block by block.
 """
 from __future__ import annotations
 
@@ -34,7 +36,9 @@ KIND_GAUSSIAN = 3
 KIND_IDEN = 4
 KIND_KANTER = 5
 KIND_MATERN = 6            # Matern of any smoothness nu in [NU_MIN, NU_MAX]
+KIND_SUM = 7               # a sum of up to SUM_MAX of the closed-form kinds below (KernelSum): a nested covariance model
 NU_MIN, NU_MAX = 0.1, 5.0
+SUM_MAX = 4
 
 
 class SymbolicLocs:
@@ -97,6 +101,12 @@ class KernelSpec:
     def __truediv__(self, c):
         return self.__mul__(1.0 / float(c))
 
+    def __add__(self, other):
+        """A nested model: the sum of two structures (or of a structure and a sum) is a KernelSum, evaluated on the device as one kernel."""
+        if isinstance(other, (KernelSpec, KernelSum)):
+            return KernelSum(_sum_parts(self) + _sum_parts(other))
+        return NotImplemented
+
     def params(self):
         return np.array([self.l, self.sig, self.scale], dtype=np.float64)
 
@@ -111,6 +121,87 @@ class KernelSpec:
         base = "KernelSpec(kind=%d, l=%g, sig=%g, scale=%g" % (self.kind, self.l, self.sig, self.scale)
         base += "" if self.nu is None else ", nu=%g" % self.nu
         return base + (")" if self.A is None else ", A=%s)" % np.array2string(self.A, separator=", ").replace("\n", ""))
+
+
+_SUM_KINDS = (KIND_EXP, KIND_MATERN32, KIND_MATERN52, KIND_GAUSSIAN, KIND_IDEN)
+_SUM_HAS_SIG = (KIND_MATERN32, KIND_MATERN52, KIND_GAUSSIAN)       # (ExpCovFun and Iden have no sig of their own: their sill is their scale)
+
+
+def _sum_parts(k):
+    """The components of a KernelSpec (itself) or of a KernelSum (each with the sum's scale folded into its own)."""
+    if isinstance(k, KernelSum):
+        return [c if k.scale == 1.0 else c * k.scale for c in k.components]
+    return [k]
+
+
+class KernelSum:
+    """scale * (k_0 + ... + k_{K-1}), 1 <= K <= SUM_MAX components, each a KernelSpec of kind EXP, MATERN32, MATERN52, GAUSSIAN or IDEN
+    with its own range, sill and scale; they share the distance: ``circular`` and the metric ``A`` are the sum's.  An Iden component
+    is a micro-scale part of the field (its sill at D == 0, 0 elsewhere), not measurement noise.  kind = KIND_SUM, nu = None.
+
+    ``l`` and ``sig`` are what ``HipPlan.set_kernel(kind, l, sig, scale, circular, nu)`` takes for kind 7, so that code written for a
+    KernelSpec sends a sum unchanged: l = the components as (kind, l_c, sig_c) triples, sig_c the component's whole sill (its scale
+    times its sig, for the kinds that have one); sig = the total sill at scale 1."""
+    __slots__ = ("components", "scale", "circular", "A")
+    kind = KIND_SUM
+    nu = None
+
+    def __init__(self, components, scale=1.0):
+        comps = tuple(components)
+        if not 1 <= len(comps) <= SUM_MAX:
+            raise ValueError("a sum of kernels has 1 to %d components, got %d" % (SUM_MAX, len(comps)))
+        for c in comps:
+            if not isinstance(c, KernelSpec):
+                raise TypeError("the components of a KernelSum are KernelSpecs, got %r" % (c,))
+            if c.kind not in _SUM_KINDS:
+                raise ValueError("a %s cannot be a component of a sum (ExpCovFun, Matern32, Matern52, GaussianCovFun and Iden can)"
+                                 % ("Kanter taper" if c.kind == KIND_KANTER else "Matern(nu)" if c.kind == KIND_MATERN else "kernel of kind %d" % c.kind))
+            if not (np.isfinite(c.l) and c.l > 0.0) or not (np.isfinite(c.scale * c.sig) and c.scale >= 0.0 and c.sig >= 0.0):
+                raise ValueError("a component needs a positive range and a sill that is not negative, got %r" % (c,))
+        first = comps[0]
+        for c in comps[1:]:
+            if c.circular != first.circular:
+                raise ValueError("the components of a sum share one distance: all circular or none")
+            if (c.A is None) != (first.A is None) or (c.A is not None and not np.array_equal(c.A, first.A)):
+                raise ValueError("the components of a sum share one distance: their metrics differ")
+        self.components, self.scale, self.circular, self.A = comps, float(scale), first.circular, first.A
+
+    @property
+    def l(self):
+        return tuple((c.kind, c.l, c.scale * (c.sig if c.kind in _SUM_HAS_SIG else 1.0)) for c in self.components)
+
+    @property
+    def sig(self):
+        return float(sum(t[2] for t in self.l))
+
+    def __add__(self, other):
+        if isinstance(other, (KernelSpec, KernelSum)):
+            return KernelSum(_sum_parts(self) + _sum_parts(other))
+        return NotImplemented
+
+    def __mul__(self, c):
+        if isinstance(c, (int, float, np.floating, np.integer)):
+            return KernelSum(self.components, self.scale * float(c))
+        return NotImplemented
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, c):
+        return self.__mul__(1.0 / float(c))
+
+    def params(self):
+        """The parameter vector of mra_plan_set_kernel(7, ...): {K, 0, scale, circular, kind_0, l_0, sig_0, ...}."""
+        return np.array([len(self.components), 0.0, self.scale, 1.0 if self.circular else 0.0] + [v for t in self.l for v in t], dtype=np.float64)
+
+    def evaluate(self, locs1, locs2):
+        """Host evaluation: the NumPy sum of the components' own evaluations, in component order, times the sum's scale."""
+        out = self.components[0].evaluate(locs1, locs2)
+        for c in self.components[1:]:
+            out = out + c.evaluate(locs1, locs2)
+        return out if self.scale == 1.0 else self.scale * out
+
+    def __repr__(self):
+        return "KernelSum(%s%s)" % (" + ".join(repr(c) for c in self.components), "" if self.scale == 1.0 else ", scale=%g" % self.scale)
 
 
 def _check_nu(nu):

@@ -92,8 +92,8 @@ class RootView:
 
 
 def probe_cov(cov, d, locs=None):
-    """Return a KernelSpec if ``cov`` is expressible as one of the device kernels, else None."""
-    if isinstance(cov, mt.KernelSpec):
+    """Return a KernelSpec - or a KernelSum, for a sum of them - if ``cov`` is expressible as one of the device kernels, else None."""
+    if isinstance(cov, (mt.KernelSpec, mt.KernelSum)):
         return cov
     if not callable(cov):
         return None
@@ -101,7 +101,7 @@ def probe_cov(cov, d, locs=None):
         out = cov(mt.SymbolicLocs("a", d, locs), mt.SymbolicLocs("b", d, locs))
     except Exception:
         return None
-    return out if isinstance(out, mt.KernelSpec) else None
+    return out if isinstance(out, (mt.KernelSpec, mt.KernelSum)) else None
 
 
 def _check_noise(R, N):

@@ -100,6 +100,8 @@ struct KernelParams {
     //           These four sit BEFORE the doubles every mode reads, not behind amp: anything appended behind amp changes how the
     //           scalar loads of amp and of the kernel arguments after the struct are merged, and the six k_site_leaf instances of
     //           modes 0 and 3 come out with two SGPR spills fewer - a different object code for kernels this mode never runs.
+    //   mode 5: a sum of nu_n <= MRA_SUM_MAX closed-form kernels (MRA_KERNEL_SUM, cov_sum_of_dist2 below).  The layout stands: nu_tab
+    //           points at nu_n records of MRA_SUM_REC doubles (the plan's own buffer), amp = the sum of the records' amp_c = C(x, x).
     const double* nu_tab;
     int nu_n;
     double nu, nu_a;
@@ -240,6 +242,44 @@ __device__ __forceinline__ double matern_nu_of_t(const KernelParams& kp, double 
     return (t0 == 0.0) ? kp.amp : ((t0 < MRA_NU_T_MAX) ? v : 0.0);
 }
 
+// A sum of closed-form kernels (MRA_KERNEL_SUM): value = sum over c < nu_n of k_c(D), each component with the
+// formula and operation order of its own mode below, added in component order.  One record of MRA_SUM_REC doubles per component:
+//   {submode, c_inv_l, inv_2l2, a1, a2, amp_c}     submode 0.0 / 1.0 / 2.0 = the modes 0 / 1 / 2 of derive_kernel_params
+// The records are read through wave-uniform addresses (the pointer is a kernel argument, the index the loop counter), so they arrive as
+// scalar loads, and the submode is tested on its high word, an integer compare on a scalar register; every branch is wave-uniform and
+// no lane leaves the loop early.  One sqrt_pos for all components.  t is clamped at 1100 BEFORE the polynomial (exp_neg clamps it
+// for itself and gives exactly 0 there): at a phantom knot a2 t^2 stays finite, so the product is 0 and never inf * 0.
+// D2 == 0: poly = 1 and exp_neg(0) = 1 exactly, so the value is the sum of the amp_c in component order - kp.amp, as the host adds it.
+#ifndef MRA_SUM_MAX
+#define MRA_SUM_MAX 4       /* (include/mra_hip.h has the same) */
+#endif
+#define MRA_SUM_REC 6
+// The records live in memory no kernel writes (the host fills them between launches): read through the constant address space, a
+// wave-uniform address is a scalar load (s_load_dwordx4) - through a plain pointer the compiler cannot rule out the kernel's own stores
+// and issues a vector load per lane.
+typedef const __attribute__((address_space(4))) double* mra_sum_rec_ptr;
+// FROM: the value the sum starts from.  The GEMM epilogues need C(a, b) - acc and hand in -acc (cov_minus below): the single kinds'
+// amp * (poly * exp) - acc is compiled to ONE fma(amp, poly * exp, -acc), and with FROM a sum of one component is that very fma - a
+// K = 1 plan gives the single kind's bits.  Without FROM (every other caller) the components are added to 0 by plain additions.
+template <bool FROM>
+__device__ __forceinline__ double cov_sum_of_dist2(const KernelParams& kp, double D2, double from = 0.0) {
+    const double D = sqrt_pos(D2);
+    mra_sum_rec_ptr rec = (mra_sum_rec_ptr)kp.nu_tab;
+    double acc = FROM ? from : 0.0;
+    for (int c = 0; c < kp.nu_n; ++c, rec += MRA_SUM_REC) {
+        const int sub = __double2hiint(rec[0]);         // 0.0, 1.0, 2.0 -> 0, 0x3ff00000, 0x40000000
+        if (sub == 0x40000000) {
+            acc += (D2 == 0.0) ? rec[5] : 0.0;
+        } else {
+            const double t = fmin((sub == 0x3ff00000) ? D2 * rec[2] : D * rec[1], 1100.0);
+            const double poly = __builtin_fma(__builtin_fma(rec[4], t, rec[3]), t, 1.0);
+            if (FROM) acc = __builtin_fma(rec[5], poly * exp_neg(t), acc);
+            else acc += rec[5] * (poly * exp_neg(t));
+        }
+    }
+    return acc;
+}
+
 // value of the kernel at squared distance D2 (the reference evaluates the same formulas on
 // D = cdist(...), pyMRA/MRATools.py:265-301; differences are at the 1-2 ulp level).  Straight-line
 // code: the only branches are on wave-uniform kernel parameters.
@@ -247,6 +287,7 @@ template <int MODE>
 __device__ __forceinline__ double cov_of_dist2(const KernelParams& kp, double D2) {
     if (MODE == 2) return (D2 == 0.0) ? kp.amp : 0.0;
     if (MODE == 4) return matern_nu_of_t(kp, sqrt_pos(D2) * kp.c_inv_l);
+    if (MODE == 5) return cov_sum_of_dist2<false>(kp, D2);
     if (MODE == 3) {                                 // pyMRA/MRATools.py:318-323
         const double D = fmin(sqrt_pos(D2) * kp.c_inv_l, 2.0);
         const double p2 = 6.283185307179586 * D;
@@ -256,6 +297,12 @@ __device__ __forceinline__ double cov_of_dist2(const KernelParams& kp, double D2
     const double t = (MODE == 1) ? D2 * kp.inv_2l2 : sqrt_pos(D2) * kp.c_inv_l;
     const double poly = __builtin_fma(__builtin_fma(kp.a2, t, kp.a1), t, 1.0);
     return kp.amp * (poly * exp_neg(t));
+}
+// C(a, b) - x, as the GEMM epilogues need it: the same expression as before for the single kinds, mode 5 starts its sum from -x
+template <int MODE>
+__device__ __forceinline__ double cov_minus(const KernelParams& kp, double D2, double x) {
+    if (MODE == 5) return cov_sum_of_dist2<true>(kp, D2, -x);
+    return cov_of_dist2<MODE>(kp, D2) - x;
 }
 __device__ __forceinline__ double cov_of_dist(const KernelParams& kp, double D) {
     return kp.mode == 0 ? cov_of_dist2<0>(kp, D * D) : (kp.mode == 1 ? cov_of_dist2<1>(kp, D * D) : (kp.mode == 2 ? cov_of_dist2<2>(kp, D * D) : cov_of_dist2<3>(kp, D * D)));
@@ -288,6 +335,11 @@ __global__ void k_eval_kernel_nu(const double* __restrict__ D, double* __restric
     const double d = i < n ? D[i] : 0.0;
     const double v = cov_of_dist2<4>(kp, d * d);
     if (i < n) out[i] = v;
+}
+// and for MRA_KERNEL_SUM (mode 5)
+__global__ void k_eval_kernel_sum(const double* __restrict__ D, double* __restrict__ out, long n, KernelParams kp) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = cov_of_dist2<5>(kp, D[i] * D[i]);
 }
 #endif
 
@@ -379,7 +431,7 @@ __device__ __forceinline__ void gemm_nt_emit(const GemmProb* __restrict__ pp, co
             double xa[DIM];
 #pragma unroll
             for (int c = 0; c < DIM; ++c) xa[c] = gld(pp->XA + (long)row * DIM + c);
-            const double cv = cov_of_dist2<MODE>(kp, pair_dist2<DIM>(xa, xb, kp.circular)) - acc[s];
+            const double cv = cov_minus<MODE>(kp, pair_dist2<DIM>(xa, xb, kp.circular), acc[s]);
             v = (bcol < 0) ? 0.0 : cv;
             if (rowmap) {
                 const int op = gldi(rowmap + row);
@@ -747,7 +799,7 @@ __global__ __launch_bounds__(256, MRA_GEMM_LDS_WPE) void k_gemm_nt_lds(const Gem
             else if (EPI == EPI_SUB) v = -acc[s];
             else if (EPI == EPI_COV) {
                 const int xrow = xrow4[s];
-                const double cv = cov_of_dist2<MODE>(kp, pair_dist2<DIM>(xa4[s], xb2[ti & 1], kp.circular)) - acc[s];
+                const double cv = cov_minus<MODE>(kp, pair_dist2<DIM>(xa4[s], xb2[ti & 1], kp.circular), acc[s]);
                 v = (bcol < 0 || xrow < 0) ? 0.0 : cv;
                 if (pb.sym_diag && row == col) v = (bcol < 0) ? 1.0 : v + pb.diag_add;
                 const int op = op4[s];
@@ -1340,6 +1392,11 @@ __global__ __launch_bounds__(NTHR, WPE) void k_leaf_gemm(const GemmProb* __restr
 #pragma unroll
                             for (int s4 = 0; s4 < 4; ++s4) {
                                 const int lc = jb * 16 + 4 * qe + s4;
+                                if (MODE == 5) {       // (a branch of its own: the statement below, rewritten through cov_minus, changes the single kinds' object code)
+                                    const double cm = cov_minus<MODE>(kp, pair_dist2<DIM>(xa, &sXB[lc * DIM], kp.circular), acc[h][jb][s4]);
+                                    v[s4] = sIB[lc] < 0 ? 0.0 : cm;
+                                    continue;
+                                }
                                 const double cv = cov_of_dist2<MODE>(kp, pair_dist2<DIM>(xa, &sXB[lc * DIM], kp.circular));
                                 v[s4] = sIB[lc] < 0 ? 0.0 : cv - acc[h][jb][s4];
                             }
@@ -1382,9 +1439,9 @@ __global__ __launch_bounds__(NTHR, WPE) void k_leaf_gemm(const GemmProb* __restr
                                 const int lc = j * 16 + 4 * qe + s4;
                                 const int ib = sIB[lc];
                                 double cv;
-                                if (EPI == EPI_COV) cv = cov_of_dist2<MODE>(kp, pair_dist2<DIM>(xa, &sXB[lc * DIM], kp.circular));
-                                else cv = gld(pp->Csrc + row * pp->ldcs + col + s4);
-                                v[s4] = ib < 0 ? 0.0 : cv - ac[s4];
+                                if (EPI == EPI_COV) cv = cov_minus<MODE>(kp, pair_dist2<DIM>(xa, &sXB[lc * DIM], kp.circular), ac[s4]);
+                                else cv = gld(pp->Csrc + row * pp->ldcs + col + s4) - ac[s4];
+                                v[s4] = ib < 0 ? 0.0 : cv;
                             }
                             if (op >= 0) {
                                 d4 v2 = v;

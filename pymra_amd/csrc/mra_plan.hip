@@ -212,11 +212,46 @@ static std::vector<double> matern_nu_table(double nu) {
 // kind and parameters of mra_plan_set_kernel / mra_eval_kernel, checked before anything changes
 static void check_kernel_params(const char* who, int kind, const double* params, int n) {
     const std::string w(who);
-    if (kind < 0 || kind > MRA_KERNEL_MATERN || n < 3) throw MraError(MRA_ERR_INVALID, w + ": unknown kernel kind or too few parameters (need l, sig, scale)");
+    if (kind < 0 || kind > MRA_KERNEL_SUM || n < 3) throw MraError(MRA_ERR_INVALID, w + ": unknown kernel kind or too few parameters (need l, sig, scale)");
+    if (kind == MRA_KERNEL_SUM) {            // params = {K, 0, scale, circular, kind_0, l_0, sig_0, ...}
+        const double K = params[0];
+        if (!(K >= 1.0 && K <= (double)MRA_SUM_MAX) || K != std::floor(K))
+            throw MraError(MRA_ERR_INVALID, w + ": unknown kernel kind or parameter layout: MRA_KERNEL_SUM takes {K, 0, scale, circular, ...} with K an integer in 1.." +
+                                            std::to_string(MRA_SUM_MAX) + ", the number of components");
+        if (n < 4 + 3 * (int)K) throw MraError(MRA_ERR_INVALID, w + ": MRA_KERNEL_SUM takes {K, 0, scale, circular, kind_0, l_0, sig_0, ...}: too few parameters");
+        for (int c = 0; c < (int)K; ++c) {
+            const double kc = params[4 + 3 * c], lc = params[5 + 3 * c], sc = params[6 + 3 * c];
+            if (!(kc == MRA_KERNEL_EXP || kc == MRA_KERNEL_MATERN32 || kc == MRA_KERNEL_MATERN52 || kc == MRA_KERNEL_GAUSSIAN || kc == MRA_KERNEL_IDEN))
+                throw MraError(MRA_ERR_INVALID, w + ": a component of MRA_KERNEL_SUM must be EXP, MATERN32, MATERN52, GAUSSIAN or IDEN");
+            if (!std::isfinite(lc) || !(lc > 0.0)) throw MraError(MRA_ERR_INVALID, w + ": length scale must be positive and finite in every component");
+            if (!std::isfinite(sc) || !(sc >= 0.0)) throw MraError(MRA_ERR_INVALID, w + ": sig must be finite and not negative in every component");
+        }
+        return;
+    }
     if (kind != MRA_KERNEL_MATERN) return;
     if (n < 5) throw MraError(MRA_ERR_INVALID, w + ": MRA_KERNEL_MATERN takes {l, sig, scale, circular, nu}");
     if (!std::isfinite(params[4]) || params[4] < 0.1 || params[4] > 5.0) throw MraError(MRA_ERR_INVALID, w + ": nu must lie in [0.1, 5]");
     if (!(params[0] > 0.0)) throw MraError(MRA_ERR_INVALID, w + ": length scale must be positive");
+}
+
+// MRA_KERNEL_SUM: one record {submode, c_inv_l, inv_2l2, a1, a2, amp_c} per component (cov_sum_of_dist2, mra_kernels.h), each derived by
+// derive_kernel_params from (kind_c, l_c, sig_c, scale) - amp_c = scale sig_c for every kind: a component's sig is its sill, which is 1
+// for the single kinds that have none (EXP, IDEN), where scale * 1 is scale - and kp.amp = their sum in component order.
+static std::vector<double> sum_records(KernelParams& kp, const double* params) {
+    const int K = (int)params[0];
+    std::vector<double> rec((size_t)MRA_SUM_REC * K);
+    double amp = 0.0;
+    for (int c = 0; c < K; ++c) {
+        KernelParams q{};
+        q.kind = (int)params[4 + 3 * c]; q.l = params[5 + 3 * c]; q.sig = params[6 + 3 * c]; q.scale = kp.scale;
+        derive_kernel_params(q);
+        double* r = &rec[(size_t)MRA_SUM_REC * c];
+        r[0] = (double)q.mode; r[1] = q.c_inv_l; r[2] = q.inv_2l2; r[3] = q.a1; r[4] = q.a2; r[5] = kp.scale * q.sig;
+        amp += r[5];
+    }
+    kp.mode = 5; kp.nu_n = K; kp.amp = amp;
+    kp.c_inv_l = 0.0; kp.inv_2l2 = 0.0; kp.a1 = 0.0; kp.a2 = 0.0; kp.nu = 0.0; kp.nu_a = 0.0;
+    return rec;
 }
 
 static int fail(mra_plan* p, const MraError& e) {
@@ -1531,7 +1566,7 @@ static bool ensure_lik_general(mra_plan* pl) {
 // ---- the route of a pass (PassRoute, mra_plan_types.h) ---------------------------------------------------------------------------
 static PassPath path_of(const mra_plan* pl) {
     // (MRA_KERNEL_MATERN, mode 4: the fused cascades have no instance of it - DESIGN.md section 23 - so its regular trees take the prior level by level)
-    if (pl->regular && pl->use_fused && !pl->host_cov && pl->kp.mode != 4) return PassPath::Fused;
+    if (pl->regular && pl->use_fused && !pl->host_cov && pl->kp.mode != 4 && pl->kp.mode != 5) return PassPath::Fused;     // (nor of mode 5, MRA_KERNEL_SUM: section 24)
     return (pl->regular_hi && pl->use_fused && !pl->host_cov) ? PassPath::Hi : PassPath::Levels;     // (sharded plans too: the walk is per row tile)
 }
 
@@ -3360,7 +3395,14 @@ int mra_plan_set_kernel(mra_plan* pl, int kind, const double* params, int n) {
         pl->kp.nu_n = kind == MRA_KERNEL_MATERN ? MRA_NU_NODES : 0;
         pl->kp.kind = kind; pl->kp.d = pl->d; pl->kp.l = params[0]; pl->kp.sig = params[1]; pl->kp.scale = params[2];
         pl->kp.circular = (n >= 4 && params[3] != 0.0) ? 1 : 0;
-        derive_kernel_params(pl->kp);
+        if (kind == MRA_KERNEL_SUM) {        // the records go up on every call (at most 192 bytes), behind whatever the stream still runs
+            HIP_TRY(mraSetDevice(pl->device));
+            if (pl->sum_tab.n == 0) pl->sum_tab.alloc((size_t)MRA_SUM_REC * MRA_SUM_MAX + 1);
+            std::vector<double> rec = sum_records(pl->kp, params);
+            rec.push_back(pl->kp.amp);       // behind the records, for mra_get_buffer(17): no kernel reads it
+            HIP_TRY(mraMemcpy(pl->sum_tab.p, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
+            pl->kp.nu_tab = pl->sum_tab.p;
+        } else derive_kernel_params(pl->kp);
         pl->host_cov = false;
         pl->have_kernel = true;
         return MRA_OK;
@@ -3549,6 +3591,7 @@ int mra_get_buffer(mra_plan* pl, int what, double* out, int64_t cap, int64_t* n_
         else if (what == 4) { src = pl->tstamps.p; n = (int64_t)pl->tstamps.n; }   // same, leaf row solves   // same, predictive cascade
         else if (what == 13) { src = pl->X.p; n = (int64_t)pl->P * pl->d; }         // the coordinates as the kernels read them (A x under mra_plan_set_metric)
         else if (what == 16) { src = pl->kp.nu_tab; n = pl->kp.mode == 4 ? 2 * (int64_t)pl->kp.nu_n : 0; }     // the quadrature table of MRA_KERNEL_MATERN, as the kernels are handed it
+        else if (what == 17) { src = pl->kp.nu_tab; n = pl->kp.mode == 5 ? MRA_SUM_REC * (int64_t)pl->kp.nu_n + 1 : 0; }     // the component records of MRA_KERNEL_SUM, then kp.amp
         else if (what == 11) { src = pl->y.p; n = pl->P; }                         // the observations as the device holds them (the pseudo-observations t after mra_plan_fit_laplace)
         else throw MraError(MRA_ERR_INVALID, "unknown buffer id");
         *n_avail = n;
@@ -3729,7 +3772,7 @@ int mra_plan_prepare(mra_plan* pl, int64_t* n_kernels) {
                             (const void*)k_parent_front<8>, (const void*)k_parent_front<12>, (const void*)k_parent_front_pair<17>,
                             (const void*)k_parent_front_pair<23>, (const void*)k_leaf_solve_update<8, 13, true>});
         if (pl->regular) {
-            if (pl->kp.mode != 4) {          // (MRA_KERNEL_MATERN has no fused prior: path_of never takes these two)
+            if (pl->kp.mode != 4 && pl->kp.mode != 5) {          // (MRA_KERNEL_MATERN and MRA_KERNEL_SUM have no fused prior: path_of never takes these two)
                 CascadeArgs ar{};
                 ar.n_wg = 1;
                 launch_cascade_any(pl, ar);
@@ -3808,7 +3851,9 @@ int mra_eval_kernel(int kind, const double* params, int n_params, const double* 
         kp.kind = kind; kp.d = 1; kp.l = params[0]; kp.sig = params[1]; kp.scale = params[2];
         kp.circular = (n_params >= 4 && params[3] != 0.0) ? 1 : 0;
         if (kind == MRA_KERNEL_MATERN) kp.nu = params[4];
-        derive_kernel_params(kp);
+        std::vector<double> rec;
+        if (kind == MRA_KERNEL_SUM) rec = sum_records(kp, params);
+        else derive_kernel_params(kp);
         if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN: nothing runs in this mode");
         DevVec<double> dD, dO, dT;
         dD.alloc(n);
@@ -3818,6 +3863,10 @@ int mra_eval_kernel(int kind, const double* params, int n_params, const double* 
             dT.upload(matern_nu_table(kp.nu));
             kp.nu_tab = dT.p; kp.nu_n = MRA_NU_NODES;
             hipLaunchKernelGGL(k_eval_kernel_nu, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dD.p, dO.p, (long)n, kp);
+        } else if (kind == MRA_KERNEL_SUM) {
+            dT.upload(rec);
+            kp.nu_tab = dT.p;
+            hipLaunchKernelGGL(k_eval_kernel_sum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dD.p, dO.p, (long)n, kp);
         } else hipLaunchKernelGGL(k_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dD.p, dO.p, (long)n, kp);
         HIP_TRY(hipGetLastError());
         HIP_TRY(mraMemcpy(out, dO.p, n * sizeof(double), hipMemcpyDeviceToHost));

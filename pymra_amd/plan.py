@@ -19,6 +19,7 @@ LIB_PATH = os.environ.get("PYMRA_AMD_LIB") or os.path.join(_HERE, "libmra_hip.so
 MRA_RUN_LIKELIHOOD = 1
 MRA_RUN_PREDICT = 2
 MRA_RUN_SPLIT = 4
+MRA_KERNEL_SUM = 7           # a sum of up to four closed-form kernels (MRATools.KernelSum)
 MRA_KERNEL_HOST = 100
 MRA_OPT_KERNEL_TIMING = 1
 MRA_OPT_FUSED = 2
@@ -418,11 +419,22 @@ class HipPlan:
         res["beta"], res["cov_beta"] = beta[:p].copy(), cov[:p, :p].copy()
         return res
 
-    def set_kernel(self, kind, l, sig=1.0, scale=1.0, circular=False, nu=None):
-        """nu: the smoothness of kind 6 (MRA_KERNEL_MATERN), sent behind circular; every other kind ignores it."""
-        par = [l, sig, scale, 1.0 if circular else 0.0] + ([] if nu is None else [nu])
-        par = np.array(par, dtype=np.float64)
+    def set_kernel(self, kind, l=None, sig=1.0, scale=1.0, circular=False, nu=None, components=None):
+        """nu: the smoothness of kind 6 (MRA_KERNEL_MATERN), sent behind circular; every other kind ignores it.
+        Kind 7 (MRA_KERNEL_SUM): components = [(kind_c, l_c, sig_c), ...], 1 to 4 of them, value = scale * sum of sig_c k_c(D; l_c);
+        they may also stand in l's place (a KernelSum's ``l`` is that list), and sig is not sent."""
+        par = _kernel_params(kind, l, sig, scale, circular, nu, components)
         self._check(self.lib.mra_plan_set_kernel(self._h, int(kind), _ptr(par), len(par)))
+
+    def sum_table(self):
+        """The component records of a kind-7 plan as the device holds them: (K, 6) rows (submode, c / l, 1 / (2 l^2), a1, a2,
+        scale sig_c); (0, 6) otherwise."""
+        return self.buffer(17)[:-1].reshape(-1, 6)
+
+    def sum_sill(self):
+        """C(x, x) of a kind-7 plan as its kernels are handed it (the records' last entries added in component order); None otherwise."""
+        b = self.buffer(17)
+        return float(b[-1]) if b.size else None
 
     def matern_table(self):
         """The quadrature table of a kind-6 plan as the device holds it: (n, 2) rows (cosh(k h), c h cosh(nu k h)); (0, 2) otherwise."""
@@ -808,12 +820,25 @@ def comm_unique_id() -> bytes:
     return buf.raw
 
 
-def eval_kernel(kind, l, sig, scale, D, nu=None):
-    """Device evaluation of a stationary kernel on an array of distances (tests); nu: the smoothness of kind 6."""
+def _kernel_params(kind, l, sig, scale, circular, nu, components):
+    """The parameter vector of mra_plan_set_kernel / mra_eval_kernel (include/mra_hip.h)."""
+    if int(kind) == MRA_KERNEL_SUM:
+        comps = l if components is None else components
+        if comps is None or np.ndim(comps) != 2 or np.shape(comps)[1] != 3:
+            raise ValueError("kind 7 takes components=[(kind, l, sig), ...]")
+        return np.array([len(comps), 0.0, scale, 1.0 if circular else 0.0] + [float(v) for c in comps for v in c], dtype=np.float64)
+    if components is not None:
+        raise ValueError("components= belongs to kind 7")
+    return np.array([l, sig, scale, 1.0 if circular else 0.0] + ([] if nu is None else [nu]), dtype=np.float64)
+
+
+def eval_kernel(kind, l=None, sig=1.0, scale=1.0, D=None, nu=None, components=None):
+    """Device evaluation of a stationary kernel on an array of distances (tests); nu: the smoothness of kind 6, components: the
+    (kind, l, sig) triples of kind 7."""
     lib = load_library()
     D = np.ascontiguousarray(D, dtype=np.float64).ravel()
     out = np.empty_like(D)
-    par = np.array([l, sig, scale] + ([] if nu is None else [0.0, nu]), dtype=np.float64)
+    par = _kernel_params(kind, l, sig, scale, False, nu, components)
     _check(lib, lib.mra_eval_kernel(int(kind), _ptr(par), len(par), _ptr(D), D.size, _ptr(out)))
     return out
 
