@@ -1,10 +1,10 @@
 # Convenience targets (the driver uses __graft_entry__.build(), which runs the same per-file hipcc commands in parallel).
 # libmra_hip.so is built from several translation units: mra_plan.hip (plan construction, launch sequence, mra_sample, C ABI, small
 # kernels), mra_calls.hip (the host drivers of the calls on the retained factors: no kernel) and the dispatchers of the heavily
-# templated kernels (mra_launch_*.hip; mra_launch_nu3: the 3-D instances of MRA_KERNEL_MATERN under names of their own; mra_launch_sum, mra_launch_sum2: every instance of MRA_KERNEL_SUM, likewise), so that `make -j8 lib` takes ~1 min instead of 2.5.
+# templated kernels (mra_launch_*.hip; mra_launch_nu3: the 3-D instances of MRA_KERNEL_MATERN under names of their own; mra_launch_sum, mra_launch_sum2: every instance of MRA_KERNEL_SUM, likewise; mra_launch_loc, mra_launch_loc2: of MRA_KERNEL_LOCAL), so that `make -j8 lib` takes ~1 min instead of 2.5.
 HIPCC ?= /opt/rocm/bin/hipcc
 CSRC   = pymra_amd/csrc
-UNITS  = mra_plan mra_calls mra_launch_gemm mra_launch_pred mra_launch_prior_row1 mra_launch_prior_row2 mra_launch_prior_row3 mra_launch_prior_knot1 mra_launch_prior_knot2 mra_launch_prior_knot3 mra_launch_solve mra_launch_cov mra_launch_sites mra_launch_laplace mra_launch_nu3 mra_launch_sum mra_launch_sum2
+UNITS  = mra_plan mra_calls mra_launch_gemm mra_launch_pred mra_launch_prior_row1 mra_launch_prior_row2 mra_launch_prior_row3 mra_launch_prior_knot1 mra_launch_prior_knot2 mra_launch_prior_knot3 mra_launch_solve mra_launch_cov mra_launch_sites mra_launch_laplace mra_launch_nu3 mra_launch_sum mra_launch_sum2 mra_launch_loc mra_launch_loc2
 HDRS   = $(CSRC)/mra_kernels.h $(CSRC)/mra_plan_types.h $(CSRC)/mra_launch_prior.inc $(CSRC)/mra_launch_sites.inc $(CSRC)/mra_solve_kernels.h $(CSRC)/mra_cov_kernels.h $(CSRC)/mra_site_kernels.h $(CSRC)/mra_laplace_kernels.h include/mra_hip.h
 CFLAGS = --offload-arch=gfx950 -std=c++17 -fPIC -Wno-unused-value -Wno-unused-result -Wno-pass-failed
 B      = build

@@ -44,6 +44,8 @@ extern "C" {
 #define MRA_KERNEL_MATERN      6   /* Matern(nu)     sig 2^(1-nu)/Gamma(nu) t^nu K_nu(t), t = sqrt(2 nu) D/l :273-277 */
 #define MRA_KERNEL_SUM         7   /* sum of 1..MRA_SUM_MAX of EXP, MATERN32, MATERN52, GAUSSIAN, IDEN: a nested model */
 #define MRA_SUM_MAX            4
+#define MRA_KERNEL_LOCAL       8   /* local ranges (nonstationary): the last coordinate column is a range lam(s) > 0;
+                                      sig (la lb / q)^(ds/2) k0(D / (l sqrt q)), q = (la^2 + lb^2) / 2, k0 = EXP, MATERN32, MATERN52 or GAUSSIAN */
 #define MRA_KERNEL_HOST        100 /* values supplied block by block (any cov callable or a dense
                                       matrix, pyMRA/MRANode.py:73-80, 381-384)                   */
 
@@ -189,6 +191,20 @@ int mra_plan_fit_laplace(mra_plan *plan, int family, const double *z_perm, const
  * call on the retained factors.  MRA_ERR_INVALID, before anything of the plan changes: K not an integer in 1..MRA_SUM_MAX, n_params <
  * 4 + 3 K, a component kind outside the five (MRA_KERNEL_KANTER and MRA_KERNEL_MATERN are no components), l_c <= 0 or not finite,
  * sig_c < 0 or not finite, circular on a plan that is not 1-D or has a metric.
+ * kind == MRA_KERNEL_LOCAL: a nonstationary covariance after Paciorek & Schervish (2006) with isotropic local kernels.  The plan's
+ * coordinates have d = 2 columns (x, lam) or d = 3 columns (x, y, lam): ds = d - 1 spatial coordinates, on which the distance D is
+ * taken, and the local range lam(s) > 0 of the location in the LAST column (the same holds for the sites of mra_predict_sites,
+ * mra_sites_cov and mra_sample_sites).  With q = (la^2 + lb^2) / 2,
+ *     value = scale * sig * (la lb / q)^(ds / 2) * k0(D / (l sqrt(q))),     k0 the base kind at range 1,
+ * params = {l, sig, scale, 0, base_kind}, n_params >= 5, base_kind MRA_KERNEL_EXP, MATERN32, MATERN52 or GAUSSIAN (each a scale mixture
+ * of Gaussians, which the validity theorem needs); sig is the sill for every base.  l multiplies the whole range field, so an
+ * optimiser's step over (l, sig) sends these parameters and nothing else; a constant field lam = lam0 is the stationary kernel of
+ * range l lam0; value(a, a) = scale sig exactly.  Such plans take the level-by-level prior (mra_get_route) and every call on the
+ * retained factors.  MRA_ERR_INVALID, before anything of the plan changes: a plan with d = 1, a base kind outside the four,
+ * circular != 0, l <= 0 or not finite, sig < 0 or not finite, a plan with a metric (mra_plan_set_metric with a non-NULL A on such a
+ * plan is refused as well: A would mix the range into the distance), and a last column that is not positive and finite at every
+ * padded row - checked on the host by whichever of mra_plan_set_locs[_rows] and this call comes second (the plan remembers the
+ * smallest value of that column, nothing else).
  * kind == MRA_KERNEL_HOST (params ignored, call after mra_plan_set_obs): covariance values come from
  * mra_plan_set_cov_block. */
 int mra_plan_set_kernel(mra_plan *plan, int kind, const double *params, int n_params);
@@ -198,6 +214,13 @@ int mra_plan_set_kernel(mra_plan *plan, int kind, const double *params, int n_pa
  * (pyMRA/MRATools.py:229-301).  MRA_KERNEL_MATERN takes params = {l, sig, scale, circular, nu} and
  * MRA_KERNEL_SUM {K, 0, scale, circular, kind_0, l_0, sig_0, ...} as mra_plan_set_kernel does. */
 int mra_eval_kernel(int kind, const double *params, int n_params, const double *D, int64_t n, double *out);
+
+/* Diagnostics, MRA_KERNEL_LOCAL: out[i] = the value for a pair at distance D[i] (over ds = 1 or 2 spatial dimensions) with the local
+ * ranges la[i] and lb[i], evaluated by the device function that the inference kernels inline.  params = {l, sig, scale, 0,
+ * base_kind} as mra_plan_set_kernel takes them; D, la, lb and out are arrays of n.  A range of 1e150 or more - a phantom knot's -
+ * gives exactly 0.  (mra_eval_kernel refuses this kind: it is no function of the distance alone.) */
+int mra_eval_kernel_local(const double *params, int n_params, int ds, const double *D, const double *la, const double *lb, int64_t n,
+                          double *out);
 
 /* Replaces: the `cov` callable for anything else (MRA_KERNEL_HOST): the host evaluates
  * C(S_j, Q_j) for a non-leaf node (N_j x rank, row-major, pyMRA/MRANode.py:384) or

@@ -19,8 +19,10 @@ parameters, closed under multiplication by a scalar such as ``sigma*mt.Matern32(
 cf. pyMRA/tests/test-param-est.py:84) instead of numbers; ``MRATree`` then evaluates that
 kernel on the GPU.  Specs add: ``mt.Matern32(a, b, l=.05, sig=.6) + mt.ExpCovFun(a, b, l=.8)`` is a
 ``KernelSum`` of up to four structures, a nested model that the device evaluates as one kernel
-(DESIGN.md section 24).  Any callable that produces neither is treated as an opaque function
-and evaluated on the host block by block.
+(DESIGN.md section 24), and ``LocalRange`` wraps one of the four stationary kernels into a nonstationary
+covariance with a local range at every location (``MRATree(..., local_range=lam)``, section 25).  Any
+callable that produces none of these is treated as an opaque function and evaluated on the host block
+by block.
 """
 from __future__ import annotations
 
@@ -37,6 +39,7 @@ KIND_IDEN = 4
 KIND_KANTER = 5
 KIND_MATERN = 6            # Matern of any smoothness nu in [NU_MIN, NU_MAX]
 KIND_SUM = 7               # a sum of up to SUM_MAX of the closed-form kinds below (KernelSum): a nested covariance model
+KIND_LOCAL = 8             # local ranges in the last coordinate column (LocalRange): a nonstationary covariance
 NU_MIN, NU_MAX = 0.1, 5.0
 SUM_MAX = 4
 
@@ -202,6 +205,111 @@ class KernelSum:
 
     def __repr__(self):
         return "KernelSum(%s%s)" % (" + ".join(repr(c) for c in self.components), "" if self.scale == 1.0 else ", scale=%g" % self.scale)
+
+
+_LOCAL_BASES = (KIND_EXP, KIND_MATERN32, KIND_MATERN52, KIND_GAUSSIAN)      # scale mixtures of Gaussians: what the validity theorem needs
+
+
+class LocalRange:
+    """A nonstationary covariance with a local range lam(s) > 0 at every location (Paciorek & Schervish 2006, isotropic local kernels;
+    DESIGN.md section 25).  The locations it is evaluated on carry their range in the LAST column: rows (x, lam) in 1-D, (x, y, lam) in
+    2-D.  With ds spatial columns, D their Euclidean distance and q = (la^2 + lb^2) / 2,
+
+        C(a, b) = scale * sig * (la lb / q)^(ds / 2) * k0(D / (l sqrt(q))),
+
+    k0 the base kernel at range 1: ``base`` is a KernelSpec of kind EXP, MATERN32, MATERN52 or GAUSSIAN without circular distance or
+    metric, whose l multiplies the whole range field.  A constant lam0 gives the stationary kernel of range l * lam0; C(a, a) is
+    scale * sig.  kind = KIND_LOCAL, circular False, A and nu None.
+
+    ``lam``: optionally the range field the spec was built for (MRATree keeps the tree's there); evaluate does not read it.
+    ``l`` is what ``HipPlan.set_kernel(kind, l, sig, scale, circular)`` takes for kind 8, so that code written for a KernelSpec sends
+    this one unchanged: the pair (base kind, l).  ``sig`` is the sill at scale 1 (1 for ExpCovFun, which has no sig)."""
+    __slots__ = ("base", "lam")
+    kind = KIND_LOCAL
+    circular = False
+    A = None
+    nu = None
+
+    def __init__(self, base, lam=None):
+        if not isinstance(base, KernelSpec):
+            raise TypeError("the base of a LocalRange is a KernelSpec, got %r" % (base,))
+        if base.kind not in _LOCAL_BASES:
+            raise ValueError("the base of a LocalRange must be ExpCovFun, Matern32, Matern52 or GaussianCovFun, got kind %d" % base.kind)
+        if base.circular:
+            raise ValueError("a LocalRange has no circular distance")
+        if base.A is not None:
+            raise ValueError("a LocalRange takes no metric: A would mix the range column into the distance")
+        if not (np.isfinite(base.l) and base.l > 0.0 and np.isfinite(base.sig) and base.sig >= 0.0 and np.isfinite(base.scale)):
+            raise ValueError("a LocalRange needs a positive l and a finite sill, got %r" % (base,))
+        self.base = base
+        self.lam = None if lam is None else _check_ranges(lam)
+
+    @property
+    def l(self):
+        return (self.base.kind, self.base.l)
+
+    @property
+    def sig(self):
+        return self.base.sig if self.base.kind != KIND_EXP else 1.0
+
+    @property
+    def scale(self):
+        return self.base.scale
+
+    def __mul__(self, c):
+        if isinstance(c, (int, float, np.floating, np.integer)):
+            return LocalRange(self.base * c, self.lam)
+        return NotImplemented
+
+    __rmul__ = __mul__
+
+    def __truediv__(self, c):
+        return self.__mul__(1.0 / float(c))
+
+    def params(self):
+        """The parameter vector of mra_plan_set_kernel(8, ...): {l, sig, scale, 0, base kind}."""
+        return np.array([self.base.l, self.sig, self.scale, 0.0, self.base.kind], dtype=np.float64)
+
+    def evaluate(self, locs1, locs2):
+        """Host evaluation in float64 NumPy on arrays (n1, ds + 1) and (n2, ds + 1) whose last column is the range: the formula
+        above, stated once - the oracles and the CPU twins use it as they use KernelSpec.evaluate."""
+        a, b = np.asarray(locs1, dtype=np.float64), np.asarray(locs2, dtype=np.float64)
+        if a.ndim != 2 or b.ndim != 2 or a.shape[1] != b.shape[1] or a.shape[1] not in (2, 3):
+            raise ValueError("a LocalRange is evaluated on (n, 2) rows (x, lam) or (n, 3) rows (x, y, lam)")
+        ds = a.shape[1] - 1
+        la, lb = a[:, -1][:, None], b[:, -1][None, :]
+        if not (np.all(a[:, -1] > 0.0) and np.all(b[:, -1] > 0.0)):
+            raise ValueError("the ranges (last column) must be positive")
+        D2 = np.zeros((len(a), len(b)))
+        for k in range(ds):
+            D2 += np.square(a[:, k][:, None] - b[:, k][None, :])
+        q = 0.5 * (la * la + lb * lb)
+        u = (la * lb) / q
+        pref = u if ds == 2 else np.sqrt(u)
+        l, kind = self.base.l, self.base.kind
+        if kind == KIND_GAUSSIAN:
+            k0 = np.exp(-D2 / (2.0 * (l * l) * q))
+        else:
+            c = {KIND_EXP: 1.0, KIND_MATERN32: np.sqrt(3.0), KIND_MATERN52: np.sqrt(5.0)}[kind]
+            t = c * np.sqrt(D2 / q) / l
+            poly = 1.0 if kind == KIND_EXP else (1.0 + t if kind == KIND_MATERN32 else 1.0 + t + t * t / 3.0)
+            k0 = poly * np.exp(-t)
+        return (self.scale * self.sig) * (pref * k0)
+
+    def __repr__(self):
+        return "LocalRange(%r%s)" % (self.base, "" if self.lam is None else ", lam=<%d ranges>" % len(self.lam))
+
+
+def _check_ranges(lam, n=None):
+    """A range field: a 1-D array (of n values, when n is given) of finite positive numbers."""
+    lam = np.asarray(lam, dtype=np.float64)
+    if lam.ndim == 2 and lam.shape[1] == 1:
+        lam = lam[:, 0]
+    if lam.ndim != 1 or (n is not None and len(lam) != n):
+        raise ValueError("local_range must be a 1-D array%s" % ("" if n is None else " of %d values" % n))
+    if not (np.all(np.isfinite(lam)) and np.all(lam > 0.0)):
+        raise ValueError("local ranges must be finite and positive")
+    return np.ascontiguousarray(lam)
 
 
 def _check_nu(nu):

@@ -123,8 +123,12 @@ def _check_noise(R, N):
 class MRATree(object):
 
     def __init__(self, locs, r, cov, obs, R, M=-1, J=-1, critDepth=-1, verbose=True, device=0,
-                 want_predict=True, cov_locs=None, metric="euclidean", radius=1.0, X=None):
-        """X: None, or (N, p) covariates of a regression trend y = X beta + x + eps with a flat prior on beta (p <= 63; an intercept
+                 want_predict=True, cov_locs=None, metric="euclidean", radius=1.0, X=None, local_range=None):
+        """local_range: None, or N positive local ranges lam(s), one per location: a nonstationary covariance (mt.LocalRange, DESIGN.md
+        section 25).  ``cov`` is then one of ExpCovFun, Matern32, Matern52 or GaussianCovFun on the spatial locations, its l a
+        multiplier of the whole range field; the covariance coordinates become [locs | lam] and the sites of predictAt and its
+        siblings are (n, d) with a mandatory local_range= of n values.  Not together with cov_locs or metric="chordal".
+        X: None, or (N, p) covariates of a regression trend y = X beta + x + eps with a flat prior on beta (p <= 63; an intercept
         is a column of ones): see setTrend.
         cov_locs: N x k (k <= 3) coordinates the covariance is evaluated on, when they are not ``locs``; ``locs`` still builds
         the tree.  metric="chordal": ``locs`` are (lon, lat) in degrees on a sphere of the given radius and the covariance sees
@@ -136,6 +140,16 @@ class MRATree(object):
         if metric not in ("euclidean", "chordal"):
             raise ValueError('metric must be "euclidean" or "chordal"')
         self.metric, self.radius = metric, float(radius)
+        self.local_range = None
+        if local_range is not None:
+            if cov_locs is not None:
+                raise ValueError("local_range builds the covariance coordinates [locs | lam] itself: do not pass cov_locs as well")
+            if metric == "chordal":
+                raise ValueError('local_range cannot be combined with metric="chordal" (the sphere would need four coordinate columns)')
+            if np.ndim(locs) != 2 or self.d not in (1, 2):
+                raise ValueError("local_range needs locs of shape (N, 1) or (N, 2): the range is the covariance's last of at most three columns")
+            self.local_range = mt._check_ranges(local_range, N)
+            cov_locs = np.column_stack([np.asarray(locs, dtype=np.float64), self.local_range])
         if metric == "chordal":
             if cov_locs is not None:
                 raise ValueError('metric="chordal" derives the covariance coordinates from locs: do not pass cov_locs as well')
@@ -171,7 +185,7 @@ class MRATree(object):
             if not (np.all(np.isfinite(ro)) and np.all(ro >= 0.0)):
                 raise ValueError("the noise variance of an observed location is negative or not finite")
 
-        spec = probe_cov(cov, self.cov_d, self.cov_locs)
+        spec = self._probe(cov)
         if spec is not None and spec.circular and self.cov_d != 1:
             raise ValueError("circular distances are defined for 1-D locations only")
         if spec is None and not callable(cov) and not isinstance(cov, np.ndarray):
@@ -261,6 +275,40 @@ class MRATree(object):
     def _no_trend(self, what):
         if self.trend is not None:
             raise NotImplementedError("%s does not support a regression trend yet (this tree has one: setTrend(None) clears it)" % what)
+
+    def _probe(self, cov):
+        """probe_cov on this tree's covariance coordinates; on a tree with local ranges ``cov`` is probed on the spatial locations and
+        must be one of the four stationary base kernels, which mt.LocalRange wraps (its ValueErrors are the refusals)."""
+        if self.local_range is None:
+            return probe_cov(cov, self.cov_d, self.cov_locs)
+        if isinstance(cov, mt.LocalRange):
+            return mt.LocalRange(cov.base, self.local_range)
+        base = probe_cov(cov, self.d, self.locs)
+        if not isinstance(base, mt.KernelSpec):
+            raise ValueError("with local_range, cov must be ExpCovFun, Matern32, Matern52 or GaussianCovFun on the spatial locations "
+                             "(not a sum, an opaque callable or a matrix)")
+        return mt.LocalRange(base, self.local_range)
+
+    def setLocalRange(self, local_range, want_predict=False):
+        """Another range field on the same tree (an MLE over a parametric lam(s; theta)): uploads the covariance coordinates
+        [locs | lam] again, which drops what set_locs drops (the retained factors and the kept prior), runs a pass and returns the
+        likelihood.  The tree, its knots and its observations stand."""
+        if self.local_range is None:
+            raise ValueError("this tree was built without local_range")
+        lam = mt._check_ranges(local_range, len(self.locs))
+        self.local_range = lam
+        self.cov_locs = np.column_stack([np.asarray(self.locs, dtype=np.float64), lam])
+        self.kernel = mt.LocalRange(self.kernel.base, lam)
+        self._node_blocks = {}
+        self.plan.set_locs(self.cov_locs)
+        if self.trend is not None:
+            self._fit_trend(want_predict)
+            return self.getLikelihood()
+        self.plan.run(likelihood=True, predict=want_predict)
+        d, u = self.plan.likelihood()
+        mean, var, self._sd = self.plan.predict(with_sd=True) if want_predict else (None, None, None)
+        self.root = RootView(d, u, mean, var, len(self.locs), self.topology, self.cov_locs, self.kernel)
+        return self.getLikelihood()
 
     def _check_spec_metric(self, spec):
         """A kernel's metric A (``mt.Matern32(..., metric=A)``) lives in the covariance coordinates: cov_d x cov_d (3 x 3 on the xyz
@@ -390,11 +438,24 @@ class MRATree(object):
                         leaf_lpd={int(i): float(group[i]) for i in nodes}, score=float(info[2]), n=int(info[0]),
                         leverage_max=float(info[5]), dlik_dR=dlik, trend=trend, dlik_dR_reml=dlik_reml)
 
-    def _sites(self, sites):
+    def _sites(self, sites, local_range=None):
         """The caller's sites, checked, in covariance coordinates: (lon, lat) degrees -> xyz under metric="chordal", else as given
         (n x k under an explicit cov_locs, n x d otherwise).  The public calls convert once and hand the result to the private
-        _locate / _predict_at / _covariance_at, which take covariance coordinates."""
+        _locate / _predict_at / _covariance_at, which take covariance coordinates.  On a tree with local ranges the sites are (n, d)
+        spatial locations and local_range their n ranges, mandatory: -> [sites | local_range]."""
         X = np.asarray(sites, dtype=np.float64)
+        if self.local_range is not None:
+            if local_range is None:
+                raise ValueError("this tree has local ranges: the sites need local_range=, one positive range per site")
+            if X.ndim == 1 and self.d == 1:
+                X = X.reshape(-1, 1)
+            if X.ndim != 2 or X.shape[1] != self.d:
+                raise ValueError("sites must have shape (n, %d)" % self.d)
+            if not np.all(np.isfinite(X)):
+                raise ValueError("sites must be finite")
+            return np.column_stack([X, mt._check_ranges(local_range, len(X))])
+        if local_range is not None:
+            raise ValueError("local_range given, but this tree was built without local ranges")
         din = 2 if self.metric == "chordal" else self.cov_d
         if X.ndim == 1 and din == 1:
             X = X.reshape(-1, 1)
@@ -406,12 +467,13 @@ class MRATree(object):
             X = mt.lonlat_to_xyz(X, self.radius)
         return X
 
-    def locate(self, sites):
+    def locate(self, sites, local_range=None):
         """int32[n]: for each site the leaf (node index) of the nearest tree location that the tree reports - locations a 1-D split
         drops never win; on a circular 1-D kernel the distance wraps at 1.  The rule serves every partition of the tree replay
         (quadrants, terciles, knot boundaries, KMeans) and sends a site that coincides with a tree location to that location's leaf.
-        Any assignment of sites to leaves gives a valid process: predictAt(leaf=...) overrides this one."""
-        return self._locate(self._sites(sites))
+        Any assignment of sites to leaves gives a valid process: predictAt(leaf=...) overrides this one.  On a tree with local ranges
+        "nearest" is nearest in space: the range column does not enter."""
+        return self._locate(self._sites(sites, local_range))
 
     def _locate(self, X):
         from scipy.spatial import cKDTree
@@ -423,13 +485,17 @@ class MRATree(object):
                 leaf_of[int(t.node_row0[i]):int(t.node_row1[i])] = i
             # (nearest in covariance coordinates: by chord is by great circle, so the date line needs no special case)
             pts = np.asarray(self.cov_locs, dtype=np.float64).reshape(len(self.locs), -1)[t.perm[rows]]
+            if self.local_range is not None:
+                pts = pts[:, :self.d]               # (the last column is a range, no coordinate: it never moves)
             wrap = self.kernel is not None and self.kernel.circular
             self._locator = (cKDTree(np.mod(pts, 1.0) if wrap else pts, boxsize=1.0 if wrap else None), leaf_of[rows], wrap)
         kd, leaves, wrap = self._locator
         workers = min(16, len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1))
+        if self.local_range is not None:
+            X = X[:, :self.d]
         return leaves[kd.query(np.mod(X, 1.0) if wrap else X, workers=workers)[1]].astype(np.int32)
 
-    def predictAt(self, sites, Y=None, leaf=None, X_sites=None):
+    def predictAt(self, sites, Y=None, leaf=None, X_sites=None, local_range=None):
         """Posterior mean and standard deviation of the latent field at locations that need not be rows of `locs`, from this tree's
         factors - the tree (its knots, its likelihood) stays the one that was fitted.  sites: (n, d) - under metric="chordal" (n, 2)
         longitude / latitude in degrees, under an explicit cov_locs (n, k) in the covariance coordinates, here and in locate,
@@ -443,8 +509,8 @@ class MRATree(object):
         if self.trend is None:
             if X_sites is not None:
                 raise ValueError("X_sites given, but this tree has no trend (setTrend)")
-            return self._predict_at(self._sites(sites), Y, leaf)
-        S = self._sites(sites)
+            return self._predict_at(self._sites(sites, local_range), Y, leaf)
+        S = self._sites(sites, local_range)
         if X_sites is None:
             raise ValueError("this tree has a trend: predictAt needs X_sites, the (n, p) covariates at the sites")
         if Y is not None:
@@ -485,7 +551,7 @@ class MRATree(object):
         mean, var = self.plan.predict_sites(X, leaf, Yp)
         return np.ascontiguousarray(mean.T), np.sqrt(var)
 
-    def covarianceAt(self, sites, distr="posterior", leaf=None):
+    def covarianceAt(self, sites, distr="posterior", leaf=None, local_range=None):
         """(n, n) joint covariance of the latent field at locations that need not be rows of `locs`, from this tree's factors:
         the posterior given this tree's observations (distr="posterior": its diagonal is predictAt's sd ** 2) or the prior
         (distr="prior").  sites: (n, d), (lon, lat) or covariance coordinates as for predictAt; leaf: None (locate(sites)) or
@@ -496,7 +562,7 @@ class MRATree(object):
             raise ValueError('distr must be "prior" or "posterior"')
         if self.kernel is None:
             raise NotImplementedError("covarianceAt needs a device kernel: trees built from an opaque callable or a dense matrix cannot evaluate it at new sites")
-        return self._covariance_at(self._sites(sites), distr, leaf)
+        return self._covariance_at(self._sites(sites, local_range), distr, leaf)
 
     def _covariance_at(self, X, distr, leaf):
         if leaf is None:
@@ -506,7 +572,7 @@ class MRATree(object):
             raise ValueError("leaf must have shape (n,) = (%d,)" % len(X))
         return self.plan.sites_cov(X, leaf, posterior=(distr == "posterior"))
 
-    def simulateAt(self, sites, nsim, distr="posterior", seed=None, leaf=None, z=None):
+    def simulateAt(self, sites, nsim, distr="posterior", seed=None, leaf=None, z=None, local_range=None):
         """(n, nsim) draws of the latent field at locations that need not be rows of `locs`: mean + F z, with mean predictAt's for
         this tree's observations (0 for distr="prior"), F the symmetric square root of covarianceAt(sites, distr, leaf) (numpy.linalg.eigh,
         eigenvalues below 0 set to 0) and z (n, nsim) given, or standard normals from numpy.random.default_rng(seed)."""
@@ -515,7 +581,7 @@ class MRATree(object):
             raise NotImplementedError("simulateAt needs a device kernel: trees built from an opaque callable or a dense matrix cannot simulate at new sites")
         if distr not in ("prior", "posterior"):
             raise ValueError('distr must be "prior" or "posterior"')
-        X = self._sites(sites)
+        X = self._sites(sites, local_range)
         if leaf is None:
             leaf = self._locate(X)
         S = self._covariance_at(X, distr, leaf)
@@ -533,7 +599,7 @@ class MRATree(object):
             x += self._predict_at(X, leaf=leaf)[0]
         return x
 
-    def sampleAt(self, sites, nsim, distr="posterior", seed=None, leaf=None, z=None):
+    def sampleAt(self, sites, nsim, distr="posterior", seed=None, leaf=None, z=None, local_range=None):
         """(n, nsim) draws of the latent field at locations that need not be rows of `locs`, at any number of sites: the scalable
         counterpart of simulateAt (no dense n x n matrix; a leaf may receive up to plan.MRA_SAMPLE_SITES_LEAF_MAX distinct sites).
         distr="posterior": draws given this tree's observations, predictAt's mean included; distr="prior": mean 0.  Their covariance
@@ -546,7 +612,7 @@ class MRATree(object):
             raise ValueError('distr must be "prior" or "posterior"')
         if self.kernel is None:
             raise NotImplementedError("sampleAt needs a device kernel: trees built from an opaque callable or a dense matrix cannot simulate at new sites")
-        X = self._sites(sites)
+        X = self._sites(sites, local_range)
         if leaf is None:
             leaf = self._locate(X)
         leaf = np.asarray(leaf)
@@ -641,7 +707,7 @@ class MRATree(object):
     # re-evaluate with other kernel parameters on the same tree (plan reuse for MLE loops,
     # README.md:96-104 builds a new MRATree per objective call)
     def reevaluate(self, cov, want_predict=False):
-        spec = probe_cov(cov, self.cov_d, self.cov_locs)
+        spec = self._probe(cov)
         if spec is None:
             raise NotImplementedError("cov must be a device kernel")
         self._check_spec_metric(spec)
@@ -697,7 +763,7 @@ class MRATree(object):
             raise ValueError("reml=True needs X")
         self._no_trend("fitLaplace")
         if cov is not None:
-            spec = probe_cov(cov, self.cov_d, self.cov_locs)
+            spec = self._probe(cov)
             if spec is None:
                 raise NotImplementedError("cov must be a device kernel")
             self._check_spec_metric(spec)
@@ -716,7 +782,7 @@ class MRATree(object):
 
     def _fit_laplace_trend(self, family, aux, offset, z, e0, cov, max_iter, tol, X, reml):
         if cov is not None:
-            spec = probe_cov(cov, self.cov_d, self.cov_locs)
+            spec = self._probe(cov)
             if spec is None:
                 raise NotImplementedError("cov must be a device kernel")
             self._check_spec_metric(spec)

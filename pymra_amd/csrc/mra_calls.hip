@@ -461,6 +461,10 @@ static std::vector<int> sites_check_sites(const mra_plan* pl, const char* who, i
                 snprintf(m, sizeof m, "%s: site %lld has a non-finite coordinate", who, (long long)i);
                 throw MraError(MRA_ERR_INVALID, m);
             }
+        if (pl->kp.mode == 6 && !(sites[i * d + d - 1] > 0.0)) {       // MRA_KERNEL_LOCAL: the site's range, as mra_plan_set_locs checks the plan's
+            snprintf(m, sizeof m, "%s: site %lld has a range (last column) that is not positive", who, (long long)i);
+            throw MraError(MRA_ERR_INVALID, m);
+        }
     }
     return lslot;
 }

@@ -84,6 +84,13 @@ __device__ __forceinline__ double cov_value(const KernelParams& kp, double D2) {
     return cov_of_dist2<MODE>(kp, D2);
 }
 
+// ... of a pair of locations: the same expression as before for the modes that are functions of the distance, cov_local for mode 6
+template <int DIM, int MODE>
+__device__ __forceinline__ double cov_value_pair(const KernelParams& kp, const double* __restrict__ xa, const double* __restrict__ xb) {
+    if constexpr (MODE == 6) return cov_local<DIM>(kp, xa, xb);
+    else return cov_value<MODE>(kp, pair_dist2<DIM>(xa, xb, kp.circular));
+}
+
 template <int DIM, int MODE>
 __global__ __launch_bounds__(256, 4) void k_cov_rows(const CovLeaf* __restrict__ lv, const int* __restrict__ tile_leaf,
                                                      const double* __restrict__ W, long ldw, const double* __restrict__ X,
@@ -120,7 +127,7 @@ __global__ __launch_bounds__(256, 4) void k_cov_rows(const CovLeaf* __restrict__
                     double xk[DIM];
 #pragma unroll
                     for (int e = 0; e < DIM; ++e) xk[e] = gld(X + k * DIM + e);
-                    const double cv = cov_value<MODE>(kp, pair_dist2<DIM>(xr, xk, kp.circular));
+                    const double cv = cov_value_pair<DIM, MODE>(kp, xr, xk);
                     const double v = gld(Ab + (long)r * P + k);
                     accl = mfma16(kn ? cv : 0.0, kn ? v : 0.0, accl);
                 }

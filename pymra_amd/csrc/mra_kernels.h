@@ -102,6 +102,9 @@ struct KernelParams {
     //           modes 0 and 3 come out with two SGPR spills fewer - a different object code for kernels this mode never runs.
     //   mode 5: a sum of nu_n <= MRA_SUM_MAX closed-form kernels (MRA_KERNEL_SUM, cov_sum_of_dist2 below).  The layout stands: nu_tab
     //           points at nu_n records of MRA_SUM_REC doubles (the plan's own buffer), amp = the sum of the records' amp_c = C(x, x).
+    //   mode 6: local ranges (MRA_KERNEL_LOCAL, cov_local below): the LAST coordinate column is the location's range, and the value is no
+    //           function of the distance alone.  The layout stands: c_inv_l, inv_2l2, a1, a2 hold the BASE kind's constants, amp =
+    //           scale sig, and nu_n = 1 says that the base is the Gaussian (t = D^2 / (2 l^2 q)); nu_tab is unused.
     const double* nu_tab;
     int nu_n;
     double nu, nu_a;
@@ -285,6 +288,7 @@ __device__ __forceinline__ double cov_sum_of_dist2(const KernelParams& kp, doubl
 // code: the only branches are on wave-uniform kernel parameters.
 template <int MODE>
 __device__ __forceinline__ double cov_of_dist2(const KernelParams& kp, double D2) {
+    static_assert(MODE != 6, "mode 6 is no function of the distance: cov_pair / cov_local");
     if (MODE == 2) return (D2 == 0.0) ? kp.amp : 0.0;
     if (MODE == 4) return matern_nu_of_t(kp, sqrt_pos(D2) * kp.c_inv_l);
     if (MODE == 5) return cov_sum_of_dist2<false>(kp, D2);
@@ -323,8 +327,62 @@ __device__ __forceinline__ double pair_dist2(const double* __restrict__ xa, cons
     return dx * dx + dy * dy;
 }
 
+// Local ranges (MRA_KERNEL_LOCAL, covariance mode 6): the first covariance that is not a function of the distance
+// alone.  Every location carries a range lam > 0 in its LAST coordinate column; with q = (la^2 + lb^2) / 2 and D the Euclidean distance
+// over the DS = DIM - 1 spatial columns
+//     C(a, b) = amp (la lb / q)^(DS / 2) k0(D / (l sqrt(q)))           (Paciorek & Schervish 2006, isotropic local kernels)
+// k0 the base kind at range 1, in the closed forms' own fields: c_inv_l = c / l, inv_2l2, a1, a2 as derive_kernel_params gives them for
+// the base kind, amp = scale sig, and nu_n = 1 for the Gaussian base (t = D^2 / (2 l^2 q)), 0 for the others (t = c D / (l sqrt(q))).
+// ONE reciprocal chain per pair - v_rcp_f64 (2^-23) and two Newton steps, no division - serves the prefactor and t.  The prefactor's
+// quotient p / q, p = la lb, takes the division's last step (the residual p - q u0 by one fma, then one correction): with la == lb the
+// products p and q are the same bits - contraction is off in this function for that: q = (la la + la la) / 2 must not become an fma - and
+// u is exactly 1, so C(a, a) is exactly amp (t = 0: poly = 1, exp_neg(0) = 1).
+// Ranges are clamped to [., MRA_FAR_AWAY] and q to [1e-300, 1e300], D2 / q to 1e300 and t to 1100 before the polynomial: nothing
+// overflows, no 0 * inf, never NaN or inf.  A phantom's range (a phantom knot of a regular tree sits at MRA_FAR_AWAY (2 + k) in EVERY
+// column, this one included) gives exactly 0 by a select on the unclamped ranges - the formula alone would give about 1e-150.
+__device__ __forceinline__ double rcp_pos(double d);            // (below, with the Cholesky's helpers: v_rcp_f64 + 2 Newton steps, about 1 ulp)
+template <int DS>
+__device__ __forceinline__ double cov_local_of(const KernelParams& kp, double D2, double la0, double lb0) {
+#pragma clang fp contract(off)
+    const double la = fmin(la0, MRA_FAR_AWAY), lb = fmin(lb0, MRA_FAR_AWAY);
+    const double p = la * lb;
+    const double a2 = la * la, b2 = lb * lb;
+    const double q = fmax(0.5 * (a2 + b2), 1.0e-300);
+    const double rq = rcp_pos(q);
+    const double u0 = p * rq;
+    const double u = __builtin_fma(__builtin_fma(-q, u0, p), rq, u0);           // p / q
+    const double pref = (DS == 2) ? u : sqrt_pos(u);
+    const double s = fmin(D2 * rq, 1.0e300);
+    const double t = fmin(kp.nu_n ? s * kp.inv_2l2 : sqrt_pos(s) * kp.c_inv_l, 1100.0);
+    const double poly = __builtin_fma(__builtin_fma(kp.a2, t, kp.a1), t, 1.0);
+    const double v = (kp.amp * pref) * (poly * exp_neg(t));
+    return (fmax(la0, lb0) >= MRA_FAR_AWAY) ? 0.0 : v;
+}
+template <int DIM>
+__device__ __forceinline__ double cov_local(const KernelParams& kp, const double* __restrict__ xa, const double* __restrict__ xb) {
+    static_assert(DIM == 2 || DIM == 3, "local ranges: (x, lam) or (x, y, lam)");
+    const double dx = xa[0] - xb[0];
+    double D2 = dx * dx;
+    if (DIM == 3) { const double dy = xa[1] - xb[1]; D2 = dx * dx + dy * dy; }
+    return cov_local_of<DIM - 1>(kp, D2, xa[DIM - 1], xb[DIM - 1]);
+}
+
+// The covariance of a PAIR of locations, which is what every kernel evaluates: for the modes that are functions of the distance, 0 to 5,
+// exactly the expression the call sites composed before - cov_of_dist2 of pair_dist2, or cov_minus around the same - and for mode 6
+// cov_local, which also reads the last column.  OF: a caller's own wrapper of cov_of_dist2 (site_cov, solve_cov, cov_value).
+template <int DIM, int MODE>
+__device__ __forceinline__ double cov_pair(const KernelParams& kp, const double* __restrict__ xa, const double* __restrict__ xb) {
+    if constexpr (MODE == 6) return cov_local<DIM>(kp, xa, xb);
+    else return cov_of_dist2<MODE>(kp, pair_dist2<DIM>(xa, xb, kp.circular));
+}
+template <int DIM, int MODE>
+__device__ __forceinline__ double cov_pair_minus(const KernelParams& kp, const double* __restrict__ xa, const double* __restrict__ xb, double x) {
+    if constexpr (MODE == 6) return cov_local<DIM>(kp, xa, xb) - x;
+    else return cov_minus<MODE>(kp, pair_dist2<DIM>(xa, xb, kp.circular), x);
+}
+
 // diagnostics / tests: kernel values for an array of distances
-#ifndef MRA_KERNELS_TEMPLATES_ONLY      /* non-template kernel: defined once, in the translation unit of mra_plan.hip */
+#ifndef MRA_KERNELS_TEMPLATES_ONLY     /* non-template kernel: defined once, in the translation unit of mra_plan.hip */
 __global__ void k_eval_kernel(const double* __restrict__ D, double* __restrict__ out, long n, KernelParams kp) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = cov_of_dist(kp, D[i]);
@@ -340,6 +398,12 @@ __global__ void k_eval_kernel_nu(const double* __restrict__ D, double* __restric
 __global__ void k_eval_kernel_sum(const double* __restrict__ D, double* __restrict__ out, long n, KernelParams kp) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) out[i] = cov_of_dist2<5>(kp, D[i] * D[i]);
+}
+// and for MRA_KERNEL_LOCAL (mode 6): the pair's distance and its two ranges; ds = 1 or 2 spatial dimensions
+__global__ void k_eval_kernel_local(const double* __restrict__ D, const double* __restrict__ la, const double* __restrict__ lb,
+                                    double* __restrict__ out, long n, int ds, KernelParams kp) {
+    long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = ds == 2 ? cov_local_of<2>(kp, D[i] * D[i], la[i], lb[i]) : cov_local_of<1>(kp, D[i] * D[i], la[i], lb[i]);
 }
 #endif
 
@@ -431,7 +495,9 @@ __device__ __forceinline__ void gemm_nt_emit(const GemmProb* __restrict__ pp, co
             double xa[DIM];
 #pragma unroll
             for (int c = 0; c < DIM; ++c) xa[c] = gld(pp->XA + (long)row * DIM + c);
-            const double cv = cov_minus<MODE>(kp, pair_dist2<DIM>(xa, xb, kp.circular), acc[s]);
+            double cv;          // (mode 6 on a branch of its own: through cov_pair_minus the two DIM >= 2 instances of mode 5 come out in another instruction order)
+            if constexpr (MODE == 6) cv = cov_local<DIM>(kp, xa, xb) - acc[s];
+            else cv = cov_minus<MODE>(kp, pair_dist2<DIM>(xa, xb, kp.circular), acc[s]);
             v = (bcol < 0) ? 0.0 : cv;
             if (rowmap) {
                 const int op = gldi(rowmap + row);
@@ -799,7 +865,7 @@ __global__ __launch_bounds__(256, MRA_GEMM_LDS_WPE) void k_gemm_nt_lds(const Gem
             else if (EPI == EPI_SUB) v = -acc[s];
             else if (EPI == EPI_COV) {
                 const int xrow = xrow4[s];
-                const double cv = cov_minus<MODE>(kp, pair_dist2<DIM>(xa4[s], xb2[ti & 1], kp.circular), acc[s]);
+                const double cv = cov_pair_minus<DIM, MODE>(kp, xa4[s], xb2[ti & 1], acc[s]);
                 v = (bcol < 0 || xrow < 0) ? 0.0 : cv;
                 if (pb.sym_diag && row == col) v = (bcol < 0) ? 1.0 : v + pb.diag_add;
                 const int op = op4[s];
@@ -1392,12 +1458,17 @@ __global__ __launch_bounds__(NTHR, WPE) void k_leaf_gemm(const GemmProb* __restr
 #pragma unroll
                             for (int s4 = 0; s4 < 4; ++s4) {
                                 const int lc = jb * 16 + 4 * qe + s4;
-                                if (MODE == 5) {       // (a branch of its own: the statement below, rewritten through cov_minus, changes the single kinds' object code)
+                                if constexpr (MODE == 5) {       // (a branch of its own: the statement below, rewritten through cov_minus, changes the single kinds' object code)
                                     const double cm = cov_minus<MODE>(kp, pair_dist2<DIM>(xa, &sXB[lc * DIM], kp.circular), acc[h][jb][s4]);
                                     v[s4] = sIB[lc] < 0 ? 0.0 : cm;
                                     continue;
                                 }
-                                const double cv = cov_of_dist2<MODE>(kp, pair_dist2<DIM>(xa, &sXB[lc * DIM], kp.circular));
+                                if constexpr (MODE == 6) {       // (and mode 6: through cov_pair_minus the statement above changes mode 5's schedule here)
+                                    const double cm = cov_local<DIM>(kp, xa, &sXB[lc * DIM]) - acc[h][jb][s4];
+                                    v[s4] = sIB[lc] < 0 ? 0.0 : cm;
+                                    continue;
+                                }
+                                const double cv = cov_pair<DIM, MODE>(kp, xa, &sXB[lc * DIM]);
                                 v[s4] = sIB[lc] < 0 ? 0.0 : cv - acc[h][jb][s4];
                             }
                             d4 upd = zero;
@@ -1439,7 +1510,7 @@ __global__ __launch_bounds__(NTHR, WPE) void k_leaf_gemm(const GemmProb* __restr
                                 const int lc = j * 16 + 4 * qe + s4;
                                 const int ib = sIB[lc];
                                 double cv;
-                                if (EPI == EPI_COV) cv = cov_minus<MODE>(kp, pair_dist2<DIM>(xa, &sXB[lc * DIM], kp.circular), ac[s4]);
+                                if (EPI == EPI_COV) cv = cov_pair_minus<DIM, MODE>(kp, xa, &sXB[lc * DIM], ac[s4]);
                                 else cv = gld(pp->Csrc + row * pp->ldcs + col + s4) - ac[s4];
                                 v[s4] = ib < 0 ? 0.0 : cv;
                             }

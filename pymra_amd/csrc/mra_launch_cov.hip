@@ -52,6 +52,7 @@ static void launch_cov_rows(mra_plan* pl) {
         case 3: MRA_COV_ROWS(3); break;
         case 4: if constexpr (DIM != 3) MRA_COV_ROWS(4); else mra_nu3_cov_rows(pl); break;      // (3-D: the instance of mra_launch_nu3.hip)
         case 5: mra_sum_cov_rows(pl); break;        // (MRA_KERNEL_SUM, every dimension: the instances of mra_launch_sum2.hip)
+        case 6: mra_loc_cov_rows(pl); break;        // (MRA_KERNEL_LOCAL, d = 2 and 3: the instances of mra_launch_loc2.hip)
         default: mra_bad_mode("mra_cov_apply", pl->kp.mode);
     }
 #undef MRA_COV_ROWS

@@ -30,13 +30,13 @@ static void launch_gemm(mra_plan* pl, const GemmProb* probs, size_t nprob, long 
         dim3 grid(gxs * (((gy + 7u) / 8u) * 8u));
 #define MRA_GEMM_LAUNCH(KERN, D, MD) hipLaunchKernelGGL((KERN<EPI, D, (EPI == EPI_COV ? MD : 0)>), grid, dim3(256), 0, pl->stream, probs + off, pl->kp, gxs, gy, S)
         if (lds) {
-            if constexpr (EPI == EPI_COV) { if (pl->d == 3) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 3); else if (mode == 4) mra_nu3_gemm(pl, true, grid, probs + off, gxs, gy, S); else if (mode == 5) mra_sum_gemm(pl, true, grid, probs + off, gxs, gy, S); else mra_bad_mode("mra_launch_gemm", mode); continue; } }
-            if (pl->d == 1) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 3); else if (mode == 4) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 4); else if (mode == 5) mra_sum_gemm(pl, true, grid, probs + off, gxs, gy, S); else mra_bad_mode("mra_launch_gemm", mode); }
-            else { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 3); else if (mode == 4) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 4); else if (mode == 5) mra_sum_gemm(pl, true, grid, probs + off, gxs, gy, S); else mra_bad_mode("mra_launch_gemm", mode); }
+            if constexpr (EPI == EPI_COV) { if (pl->d == 3) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 3, 3); else if (mode == 4) mra_nu3_gemm(pl, true, grid, probs + off, gxs, gy, S); else if (mode == 5) mra_sum_gemm(pl, true, grid, probs + off, gxs, gy, S); else if (mode == 6) mra_loc_gemm(pl, true, grid, probs + off, gxs, gy, S); else mra_bad_mode("mra_launch_gemm", mode); continue; } }
+            if (pl->d == 1) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 3); else if (mode == 4) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 1, 4); else if (mode == 5) mra_sum_gemm(pl, true, grid, probs + off, gxs, gy, S); else if (mode == 6) mra_loc_gemm(pl, true, grid, probs + off, gxs, gy, S); else mra_bad_mode("mra_launch_gemm", mode); }
+            else { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 3); else if (mode == 4) MRA_GEMM_LAUNCH(k_gemm_nt_lds, 2, 4); else if (mode == 5) mra_sum_gemm(pl, true, grid, probs + off, gxs, gy, S); else if (mode == 6) mra_loc_gemm(pl, true, grid, probs + off, gxs, gy, S); else mra_bad_mode("mra_launch_gemm", mode); }
         } else {
-            if constexpr (EPI == EPI_COV) { if (pl->d == 3) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 3); else if (mode == 4) mra_nu3_gemm(pl, false, grid, probs + off, gxs, gy, S); else if (mode == 5) mra_sum_gemm(pl, false, grid, probs + off, gxs, gy, S); else mra_bad_mode("mra_launch_gemm", mode); continue; } }
-            if (pl->d == 1) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 3); else if (mode == 4) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 4); else if (mode == 5) mra_sum_gemm(pl, false, grid, probs + off, gxs, gy, S); else mra_bad_mode("mra_launch_gemm", mode); }
-            else { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 3); else if (mode == 4) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 4); else if (mode == 5) mra_sum_gemm(pl, false, grid, probs + off, gxs, gy, S); else mra_bad_mode("mra_launch_gemm", mode); }
+            if constexpr (EPI == EPI_COV) { if (pl->d == 3) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt, 3, 3); else if (mode == 4) mra_nu3_gemm(pl, false, grid, probs + off, gxs, gy, S); else if (mode == 5) mra_sum_gemm(pl, false, grid, probs + off, gxs, gy, S); else if (mode == 6) mra_loc_gemm(pl, false, grid, probs + off, gxs, gy, S); else mra_bad_mode("mra_launch_gemm", mode); continue; } }
+            if (pl->d == 1) { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 3); else if (mode == 4) MRA_GEMM_LAUNCH(k_gemm_nt, 1, 4); else if (mode == 5) mra_sum_gemm(pl, false, grid, probs + off, gxs, gy, S); else if (mode == 6) mra_loc_gemm(pl, false, grid, probs + off, gxs, gy, S); else mra_bad_mode("mra_launch_gemm", mode); }
+            else { if (mode == 0) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 0); else if (mode == 1) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 1); else if (mode == 2) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 2); else if (mode == 3) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 3); else if (mode == 4) MRA_GEMM_LAUNCH(k_gemm_nt, 2, 4); else if (mode == 5) mra_sum_gemm(pl, false, grid, probs + off, gxs, gy, S); else if (mode == 6) mra_loc_gemm(pl, false, grid, probs + off, gxs, gy, S); else mra_bad_mode("mra_launch_gemm", mode); }
         }
 #undef MRA_GEMM_LAUNCH
     }
@@ -57,9 +57,9 @@ static void launch_leaf_gemm(mra_plan* pl, const GemmProb* probs, size_t nprob) 
         if (wide) hipLaunchKernelGGL((k_leaf_gemm<EPI, D, (EPI == EPI_COV ? MD : 0), 1, 8, 512, (MD >= 3 ? 2 : 4)>), grid, dim3(512), 0, pl->stream, probs, pl->kp); \
         else hipLaunchKernelGGL((k_leaf_gemm<EPI, D, (EPI == EPI_COV ? MD : 0), (EPI == EPI_SUB ? 1 : 2), CT, 256, 2>), grid, dim3(256), 0, pl->stream, probs, pl->kp); \
     } while (0)
-    if constexpr (EPI == EPI_COV) { if (pl->d == 3) { if (mode == 0) MRA_LG_LAUNCH(3, 0); else if (mode == 1) MRA_LG_LAUNCH(3, 1); else if (mode == 2) MRA_LG_LAUNCH(3, 2); else if (mode == 3) MRA_LG_LAUNCH(3, 3); else if (mode == 4) mra_nu3_leaf_gemm(pl, wide, grid, probs); else if (mode == 5) mra_sum_leaf_gemm(pl, wide, grid, probs); else mra_bad_mode("mra_launch_leaf_gemm", mode); return; } }
-    if (pl->d == 1) { if (mode == 0) MRA_LG_LAUNCH(1, 0); else if (mode == 1) MRA_LG_LAUNCH(1, 1); else if (mode == 2) MRA_LG_LAUNCH(1, 2); else if (mode == 3) MRA_LG_LAUNCH(1, 3); else if (mode == 4) MRA_LG_LAUNCH(1, 4); else if (mode == 5) mra_sum_leaf_gemm(pl, wide, grid, probs); else mra_bad_mode("mra_launch_leaf_gemm", mode); }
-    else { if (mode == 0) MRA_LG_LAUNCH(2, 0); else if (mode == 1) MRA_LG_LAUNCH(2, 1); else if (mode == 2) MRA_LG_LAUNCH(2, 2); else if (mode == 3) MRA_LG_LAUNCH(2, 3); else if (mode == 4) MRA_LG_LAUNCH(2, 4); else if (mode == 5) mra_sum_leaf_gemm(pl, wide, grid, probs); else mra_bad_mode("mra_launch_leaf_gemm", mode); }
+    if constexpr (EPI == EPI_COV) { if (pl->d == 3) { if (mode == 0) MRA_LG_LAUNCH(3, 0); else if (mode == 1) MRA_LG_LAUNCH(3, 1); else if (mode == 2) MRA_LG_LAUNCH(3, 2); else if (mode == 3) MRA_LG_LAUNCH(3, 3); else if (mode == 4) mra_nu3_leaf_gemm(pl, wide, grid, probs); else if (mode == 5) mra_sum_leaf_gemm(pl, wide, grid, probs); else if (mode == 6) mra_loc_leaf_gemm(pl, wide, grid, probs); else mra_bad_mode("mra_launch_leaf_gemm", mode); return; } }
+    if (pl->d == 1) { if (mode == 0) MRA_LG_LAUNCH(1, 0); else if (mode == 1) MRA_LG_LAUNCH(1, 1); else if (mode == 2) MRA_LG_LAUNCH(1, 2); else if (mode == 3) MRA_LG_LAUNCH(1, 3); else if (mode == 4) MRA_LG_LAUNCH(1, 4); else if (mode == 5) mra_sum_leaf_gemm(pl, wide, grid, probs); else if (mode == 6) mra_loc_leaf_gemm(pl, wide, grid, probs); else mra_bad_mode("mra_launch_leaf_gemm", mode); }
+    else { if (mode == 0) MRA_LG_LAUNCH(2, 0); else if (mode == 1) MRA_LG_LAUNCH(2, 1); else if (mode == 2) MRA_LG_LAUNCH(2, 2); else if (mode == 3) MRA_LG_LAUNCH(2, 3); else if (mode == 4) MRA_LG_LAUNCH(2, 4); else if (mode == 5) mra_sum_leaf_gemm(pl, wide, grid, probs); else if (mode == 6) mra_loc_leaf_gemm(pl, wide, grid, probs); else mra_bad_mode("mra_launch_leaf_gemm", mode); }
 #undef MRA_LG_LAUNCH
 }
 
@@ -96,9 +96,9 @@ void mra_launch_prior_level(mra_plan* pl, const GemmProb* probs, size_t nprob) {
     // (D == 3: two workgroups per CU, 192 registers - at three the third coordinate takes the 168-register shape's parked epilogue
     // addresses from 60 to 76 bytes of scratch per lane; two cost the 2-D kernel 3 % at config 5)
 #define MRA_PL_LAUNCH(D, MD) hipLaunchKernelGGL((k_leaf_gemm<EPI_COV, D, MD, 2, 4, 256, (MD >= 3 || D == 3 ? 2 : MRA_PL_WPE), 1>), grid, dim3(256), 0, pl->stream, probs, pl->kp)
-    if (pl->d == 1) { if (mode == 0) MRA_PL_LAUNCH(1, 0); else if (mode == 1) MRA_PL_LAUNCH(1, 1); else if (mode == 2) MRA_PL_LAUNCH(1, 2); else if (mode == 3) MRA_PL_LAUNCH(1, 3); else if (mode == 4) MRA_PL_LAUNCH(1, 4); else if (mode == 5) mra_sum_prior_level(pl, grid, probs); else mra_bad_mode("mra_launch_prior_level", mode); }
-    else if (pl->d == 3) { if (mode == 0) MRA_PL_LAUNCH(3, 0); else if (mode == 1) MRA_PL_LAUNCH(3, 1); else if (mode == 2) MRA_PL_LAUNCH(3, 2); else if (mode == 3) MRA_PL_LAUNCH(3, 3); else if (mode == 4) mra_nu3_prior_level(pl, grid, probs); else if (mode == 5) mra_sum_prior_level(pl, grid, probs); else mra_bad_mode("mra_launch_prior_level", mode); }
-    else { if (mode == 0) MRA_PL_LAUNCH(2, 0); else if (mode == 1) MRA_PL_LAUNCH(2, 1); else if (mode == 2) MRA_PL_LAUNCH(2, 2); else if (mode == 3) MRA_PL_LAUNCH(2, 3); else if (mode == 4) MRA_PL_LAUNCH(2, 4); else if (mode == 5) mra_sum_prior_level(pl, grid, probs); else mra_bad_mode("mra_launch_prior_level", mode); }
+    if (pl->d == 1) { if (mode == 0) MRA_PL_LAUNCH(1, 0); else if (mode == 1) MRA_PL_LAUNCH(1, 1); else if (mode == 2) MRA_PL_LAUNCH(1, 2); else if (mode == 3) MRA_PL_LAUNCH(1, 3); else if (mode == 4) MRA_PL_LAUNCH(1, 4); else if (mode == 5) mra_sum_prior_level(pl, grid, probs); else if (mode == 6) mra_loc_prior_level(pl, grid, probs); else mra_bad_mode("mra_launch_prior_level", mode); }
+    else if (pl->d == 3) { if (mode == 0) MRA_PL_LAUNCH(3, 0); else if (mode == 1) MRA_PL_LAUNCH(3, 1); else if (mode == 2) MRA_PL_LAUNCH(3, 2); else if (mode == 3) MRA_PL_LAUNCH(3, 3); else if (mode == 4) mra_nu3_prior_level(pl, grid, probs); else if (mode == 5) mra_sum_prior_level(pl, grid, probs); else if (mode == 6) mra_loc_prior_level(pl, grid, probs); else mra_bad_mode("mra_launch_prior_level", mode); }
+    else { if (mode == 0) MRA_PL_LAUNCH(2, 0); else if (mode == 1) MRA_PL_LAUNCH(2, 1); else if (mode == 2) MRA_PL_LAUNCH(2, 2); else if (mode == 3) MRA_PL_LAUNCH(2, 3); else if (mode == 4) MRA_PL_LAUNCH(2, 4); else if (mode == 5) mra_sum_prior_level(pl, grid, probs); else if (mode == 6) mra_loc_prior_level(pl, grid, probs); else mra_bad_mode("mra_launch_prior_level", mode); }
 #undef MRA_PL_LAUNCH
 }
 

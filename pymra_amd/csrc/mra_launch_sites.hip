@@ -78,12 +78,13 @@ static void timed(mra_plan* pl, int which, const std::function<void()>& work) { 
 
 #include "mra_launch_sites.inc"      // launch_basis, launch_leaf, launch_mean, launch_gram, launch_leaf_gram, launch_cv_gram <DIM, MODE>
 
-// the <DIM, MODE> instance of the plan's dimension and kernel, as the solver's row kernel is chosen (<3, 4>: FN_nu3 of mra_launch_nu3.hip; mode 5 in every dimension: FN_sum of mra_launch_sum2.hip)
+// the <DIM, MODE> instance of the plan's dimension and kernel, as the solver's row kernel is chosen (<3, 4>: FN_nu3 of mra_launch_nu3.hip; mode 5 in every dimension: FN_sum of mra_launch_sum2.hip; mode 6, d = 2 and 3: FN_loc of mra_launch_loc2.hip)
 #define MRA_SITES_DISPATCH(FN, ...)                                                                                  \
     do {                                                                                                             \
         if (pl->d < 1 || pl->d > 3) throw MraError(MRA_ERR_INVALID, "mra_predict_sites: 1-, 2- or 3-D locations only"); \
-        if (pl->kp.mode < 0 || pl->kp.mode > 5) mra_bad_mode("mra_predict_sites", pl->kp.mode);                                                   \
+        if (pl->kp.mode < 0 || pl->kp.mode > 6) mra_bad_mode("mra_predict_sites", pl->kp.mode);                                                   \
         if (pl->kp.mode == 5) { FN##_sum(__VA_ARGS__); break; }                                                      \
+        if (pl->kp.mode == 6) { FN##_loc(__VA_ARGS__); break; }                                                      \
         switch ((pl->d - 1) * 5 + pl->kp.mode) {                                                                     \
             case 0: FN<1, 0>(__VA_ARGS__); break; case 1: FN<1, 1>(__VA_ARGS__); break; case 2: FN<1, 2>(__VA_ARGS__); break; case 3: FN<1, 3>(__VA_ARGS__); break; case 4: FN<1, 4>(__VA_ARGS__); break;\
             case 5: FN<2, 0>(__VA_ARGS__); break; case 6: FN<2, 1>(__VA_ARGS__); break; case 7: FN<2, 2>(__VA_ARGS__); break; case 8: FN<2, 3>(__VA_ARGS__); break; case 9: FN<2, 4>(__VA_ARGS__); break;\

@@ -166,6 +166,7 @@ static void launch_rows(mra_plan* pl) {
         case 3: MRA_SOLVE_ROWS(3); break;
         case 4: if constexpr (DIM != 3) MRA_SOLVE_ROWS(4); else mra_nu3_solve_rows(pl); break;      // (3-D: the instance of mra_launch_nu3.hip)
         case 5: mra_sum_solve_rows(pl); break;      // (MRA_KERNEL_SUM, every dimension: the instances of mra_launch_sum2.hip)
+        case 6: mra_loc_solve_rows(pl); break;      // (MRA_KERNEL_LOCAL, d = 2 and 3: the instances of mra_launch_loc2.hip)
         default: mra_bad_mode("mra_solve", pl->kp.mode);
     }
 #undef MRA_SOLVE_ROWS

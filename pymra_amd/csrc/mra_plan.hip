@@ -12,6 +12,7 @@
 #include "mra_plan_types.h"
 #include "mra_topology.h"
 #include <atomic>
+#include <limits>
 #include <chrono>
 #include <memory>
 #include <mutex>
@@ -212,7 +213,17 @@ static std::vector<double> matern_nu_table(double nu) {
 // kind and parameters of mra_plan_set_kernel / mra_eval_kernel, checked before anything changes
 static void check_kernel_params(const char* who, int kind, const double* params, int n) {
     const std::string w(who);
-    if (kind < 0 || kind > MRA_KERNEL_SUM || n < 3) throw MraError(MRA_ERR_INVALID, w + ": unknown kernel kind or too few parameters (need l, sig, scale)");
+    if (kind < 0 || kind > MRA_KERNEL_LOCAL || n < 3) throw MraError(MRA_ERR_INVALID, w + ": unknown kernel kind or too few parameters (need l, sig, scale)");
+    if (kind == MRA_KERNEL_LOCAL) {          // params = {l, sig, scale, 0, base_kind}; what depends on the plan (d, metric, the ranges) is checked by mra_plan_set_kernel
+        if (n < 5) throw MraError(MRA_ERR_INVALID, w + ": MRA_KERNEL_LOCAL takes {l, sig, scale, 0, base_kind}");
+        const double b = params[4];
+        if (!(b == MRA_KERNEL_EXP || b == MRA_KERNEL_MATERN32 || b == MRA_KERNEL_MATERN52 || b == MRA_KERNEL_GAUSSIAN))
+            throw MraError(MRA_ERR_INVALID, w + ": the base kind of MRA_KERNEL_LOCAL must be EXP, MATERN32, MATERN52 or GAUSSIAN (scale mixtures of Gaussians)");
+        if (params[3] != 0.0) throw MraError(MRA_ERR_INVALID, w + ": MRA_KERNEL_LOCAL has no circular distance");
+        if (!std::isfinite(params[0]) || !(params[0] > 0.0)) throw MraError(MRA_ERR_INVALID, w + ": length scale (the multiplier l of the range field) must be positive and finite");
+        if (!std::isfinite(params[1]) || !(params[1] >= 0.0) || !std::isfinite(params[2])) throw MraError(MRA_ERR_INVALID, w + ": sig must be finite and not negative, scale finite");
+        return;
+    }
     if (kind == MRA_KERNEL_SUM) {            // params = {K, 0, scale, circular, kind_0, l_0, sig_0, ...}
         const double K = params[0];
         if (!(K >= 1.0 && K <= (double)MRA_SUM_MAX) || K != std::floor(K))
@@ -252,6 +263,31 @@ static std::vector<double> sum_records(KernelParams& kp, const double* params) {
     kp.mode = 5; kp.nu_n = K; kp.amp = amp;
     kp.c_inv_l = 0.0; kp.inv_2l2 = 0.0; kp.a1 = 0.0; kp.a2 = 0.0; kp.nu = 0.0; kp.nu_a = 0.0;
     return rec;
+}
+
+// MRA_KERNEL_LOCAL: the base kind's derived constants in the fields the closed forms use (c_inv_l, inv_2l2, a1, a2 by
+// derive_kernel_params for the base kind), amp = scale sig for every base (sig is the sill, as in MRA_KERNEL_SUM), and nu_n = 1 for
+// the Gaussian base, whose t is D^2 / (2 l^2 q) - cov_local_of, mra_kernels.h.  KernelParams keeps its layout.
+static void derive_local_params(KernelParams& kp, const double* params) {
+    KernelParams q{};
+    q.kind = (int)params[4]; q.l = params[0]; q.sig = params[1]; q.scale = params[2];
+    derive_kernel_params(q);
+    kp.mode = 6; kp.nu_n = q.mode == 1 ? 1 : 0; kp.nu_tab = nullptr; kp.nu = 0.0; kp.nu_a = 0.0;
+    kp.c_inv_l = q.c_inv_l; kp.inv_2l2 = q.inv_2l2; kp.a1 = q.a1; kp.a2 = q.a2; kp.amp = params[2] * params[1];
+}
+
+// the last coordinate column of n rows of d: its smallest value, NaN if any is not finite (MRA_KERNEL_LOCAL reads a range there)
+static double last_column_min(const double* locs, int64_t n, int d) {
+    double mn = std::numeric_limits<double>::infinity();
+    for (int64_t i = 0; i < n; ++i) {
+        const double v = locs[i * d + d - 1];
+        if (!std::isfinite(v)) return std::nan("");
+        mn = std::min(mn, v);
+    }
+    return mn;
+}
+static void require_ranges(const char* who, double mn) {
+    if (!(mn > 0.0)) throw MraError(MRA_ERR_INVALID, std::string(who) + ": MRA_KERNEL_LOCAL reads a range out of the last coordinate column, which must be positive and finite at every row");
 }
 
 static int fail(mra_plan* p, const MraError& e) {
@@ -1566,7 +1602,7 @@ static bool ensure_lik_general(mra_plan* pl) {
 // ---- the route of a pass (PassRoute, mra_plan_types.h) ---------------------------------------------------------------------------
 static PassPath path_of(const mra_plan* pl) {
     // (MRA_KERNEL_MATERN, mode 4: the fused cascades have no instance of it - DESIGN.md section 23 - so its regular trees take the prior level by level)
-    if (pl->regular && pl->use_fused && !pl->host_cov && pl->kp.mode != 4 && pl->kp.mode != 5) return PassPath::Fused;     // (nor of mode 5, MRA_KERNEL_SUM: section 24)
+    if (pl->regular && pl->use_fused && !pl->host_cov && pl->kp.mode != 4 && pl->kp.mode != 5 && pl->kp.mode != 6) return PassPath::Fused;     // (nor of mode 5, MRA_KERNEL_SUM: section 24, nor of mode 6, MRA_KERNEL_LOCAL: section 25)
     return (pl->regular_hi && pl->use_fused && !pl->host_cov) ? PassPath::Hi : PassPath::Levels;     // (sharded plans too: the walk is per row tile)
 }
 
@@ -2937,6 +2973,11 @@ static void metric_copy(mra_plan* pl, double* dst, const double* src, size_t n) 
 }
 
 static void set_locs(mra_plan* pl, const double* locs) {
+    // (every row the kernels read is one of these P, phantom padding rows included; refused before anything changes)
+    // (d = 1 plans never have that kernel - mra_plan_set_kernel refuses it - and pay nothing for it)
+    const double last_min = pl->d >= 2 ? last_column_min(locs, pl->P, pl->d) : 0.0;
+    if (pl->have_kernel && pl->kp.mode == 6) require_ranges("mra_plan_set_locs", last_min);
+    pl->last_col_min = last_min;
     HIP_TRY(mraSetDevice(pl->device));
     pl->slv.valid = false;
     prior_keep_reset(pl);
@@ -2959,6 +3000,7 @@ static void set_metric(mra_plan* pl, const double* A) {
         if (!(std::isfinite(det) && det != 0.0)) throw MraError(MRA_ERR_INVALID, "mra_plan_set_metric: A is singular (its determinant is 0 or not finite)");
         if (pl->host_cov) throw MraError(MRA_ERR_INVALID, "mra_plan_set_metric: MRA_KERNEL_HOST plans never read coordinates (apply the metric in the callable)");
         if (pl->have_kernel && pl->kp.circular) throw MraError(MRA_ERR_INVALID, "mra_plan_set_metric: the kernel is circular (the torus has period 1 in the raw coordinate)");
+        if (pl->have_kernel && pl->kp.mode == 6) throw MraError(MRA_ERR_INVALID, "mra_plan_set_metric: the kernel is MRA_KERNEL_LOCAL (A would mix the range column into the distance)");
     }
     HIP_TRY(mraSetDevice(pl->device));
     pl->slv.valid = false;
@@ -3350,6 +3392,11 @@ int mra_plan_set_kernel(mra_plan* pl, int kind, const double* params, int n) {
             check_kernel_params("mra_plan_set_kernel", kind, params, n);
             if (!(params[0] > 0.0)) throw MraError(MRA_ERR_INVALID, "length scale must be positive");
             if (n >= 4 && params[3] != 0.0 && pl->d != 1) throw MraError(MRA_ERR_INVALID, "circular distances are defined for 1-D locations only");
+            if (kind == MRA_KERNEL_LOCAL) {
+                if (pl->d < 2) throw MraError(MRA_ERR_INVALID, "mra_plan_set_kernel: MRA_KERNEL_LOCAL needs d = 2 (x, range) or d = 3 (x, y, range) coordinates");
+                if (pl->metric_on) throw MraError(MRA_ERR_INVALID, "mra_plan_set_kernel: MRA_KERNEL_LOCAL on a plan with a metric (A would mix the range column into the distance; mra_plan_set_metric(NULL) first)");
+                if (pl->have_locs) require_ranges("mra_plan_set_kernel", pl->last_col_min);
+            }
         } else if (!pl->have_obs) throw MraError(MRA_ERR_STATE, "MRA_KERNEL_HOST needs mra_plan_set_obs first (leaf blocks are per observed row)");
         // every refusal is above: from here on the call goes through
         pl->slv.valid = false;
@@ -3402,7 +3449,8 @@ int mra_plan_set_kernel(mra_plan* pl, int kind, const double* params, int n) {
             rec.push_back(pl->kp.amp);       // behind the records, for mra_get_buffer(17): no kernel reads it
             HIP_TRY(mraMemcpy(pl->sum_tab.p, rec.data(), rec.size() * sizeof(double), hipMemcpyHostToDevice));
             pl->kp.nu_tab = pl->sum_tab.p;
-        } else derive_kernel_params(pl->kp);
+        } else if (kind == MRA_KERNEL_LOCAL) derive_local_params(pl->kp, params);
+        else derive_kernel_params(pl->kp);
         pl->host_cov = false;
         pl->have_kernel = true;
         return MRA_OK;
@@ -3772,7 +3820,7 @@ int mra_plan_prepare(mra_plan* pl, int64_t* n_kernels) {
                             (const void*)k_parent_front<8>, (const void*)k_parent_front<12>, (const void*)k_parent_front_pair<17>,
                             (const void*)k_parent_front_pair<23>, (const void*)k_leaf_solve_update<8, 13, true>});
         if (pl->regular) {
-            if (pl->kp.mode != 4 && pl->kp.mode != 5) {          // (MRA_KERNEL_MATERN and MRA_KERNEL_SUM have no fused prior: path_of never takes these two)
+            if (pl->kp.mode != 4 && pl->kp.mode != 5 && pl->kp.mode != 6) {          // (MRA_KERNEL_MATERN, MRA_KERNEL_SUM and MRA_KERNEL_LOCAL have no fused prior: path_of never sends them down the fused path, whose two kernels these are)
                 CascadeArgs ar{};
                 ar.n_wg = 1;
                 launch_cascade_any(pl, ar);
@@ -3847,6 +3895,7 @@ int mra_eval_kernel(int kind, const double* params, int n_params, const double* 
         require(params && D && out, "mra_eval_kernel: params, D or out is NULL");
         require(n > 0, "mra_eval_kernel: n <= 0");
         check_kernel_params("mra_eval_kernel", kind, params, n_params);
+        if (kind == MRA_KERNEL_LOCAL) throw MraError(MRA_ERR_INVALID, "mra_eval_kernel: MRA_KERNEL_LOCAL is no function of the distance alone (mra_eval_kernel_local)");
         KernelParams kp{};
         kp.kind = kind; kp.d = 1; kp.l = params[0]; kp.sig = params[1]; kp.scale = params[2];
         kp.circular = (n_params >= 4 && params[3] != 0.0) ? 1 : 0;
@@ -3868,6 +3917,30 @@ int mra_eval_kernel(int kind, const double* params, int n_params, const double* 
             kp.nu_tab = dT.p;
             hipLaunchKernelGGL(k_eval_kernel_sum, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dD.p, dO.p, (long)n, kp);
         } else hipLaunchKernelGGL(k_eval_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dD.p, dO.p, (long)n, kp);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(mraMemcpy(out, dO.p, n * sizeof(double), hipMemcpyDeviceToHost));
+        return MRA_OK;
+    });
+}
+
+// ... and MRA_KERNEL_LOCAL on n pairs: the distance D[i] over ds = 1 or 2 spatial dimensions and the two ranges la[i], lb[i]
+int mra_eval_kernel_local(const double* params, int n_params, int ds, const double* D, const double* la, const double* lb, int64_t n, double* out) {
+    return guarded(nullptr, [&] {
+        require(params && D && la && lb && out, "mra_eval_kernel_local: params, D, la, lb or out is NULL");
+        require(n > 0, "mra_eval_kernel_local: n <= 0");
+        require(ds == 1 || ds == 2, "mra_eval_kernel_local: ds must be 1 or 2");
+        check_kernel_params("mra_eval_kernel_local", MRA_KERNEL_LOCAL, params, n_params);
+        require_ranges("mra_eval_kernel_local", std::min(last_column_min(la, n, 1), last_column_min(lb, n, 1)));
+        KernelParams kp{};
+        kp.kind = MRA_KERNEL_LOCAL; kp.d = ds + 1; kp.l = params[0]; kp.sig = params[1]; kp.scale = params[2];
+        derive_local_params(kp, params);
+        if (g_dry) throw MraError(MRA_ERR_STATE, "MRA_HOST_DRYRUN: nothing runs in this mode");
+        DevVec<double> dD, dA, dB, dO;
+        dD.alloc(n); dA.alloc(n); dB.alloc(n); dO.alloc(n);
+        HIP_TRY(mraMemcpy(dD.p, D, n * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(mraMemcpy(dA.p, la, n * sizeof(double), hipMemcpyHostToDevice));
+        HIP_TRY(mraMemcpy(dB.p, lb, n * sizeof(double), hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(k_eval_kernel_local, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, 0, dD.p, dA.p, dB.p, dO.p, (long)n, ds, kp);
         HIP_TRY(hipGetLastError());
         HIP_TRY(mraMemcpy(out, dO.p, n * sizeof(double), hipMemcpyDeviceToHost));
         return MRA_OK;

@@ -386,6 +386,9 @@ struct mra_plan {
     bool host_cov = false;
     DevVec<double> nu_tab;              // MRA_KERNEL_MATERN: the quadrature table kp.nu_tab points at, built for nu_tab_nu (host memory on
     double nu_tab_nu = 0.0;             // MRA_HOST_DRYRUN plans); set_kernel rebuilds it when nu changes and at no other time
+    // MRA_KERNEL_LOCAL reads a range out of the last coordinate column: what set_locs remembers of that column (the smallest value, NaN if
+    // any is not finite), so that whichever of set_locs and set_kernel comes second can refuse a range that is not positive and finite
+    double last_col_min = 0.0;
     DevVec<double> sum_tab;             // MRA_KERNEL_SUM: MRA_SUM_MAX records of MRA_SUM_REC doubles, kp.nu_tab of such plans; every set_kernel(7) fills it
     double R = 0.0;
     // the metric of mra_plan_set_metric: while metric_on the kernels' X (and the knot coordinates of the fused levels) hold A x and
@@ -838,6 +841,19 @@ void launch_mean_sum(mra_plan* pl, long n, int nc);
 void launch_gram_sum(mra_plan* pl, long n, long tile0, long rows, bool post);
 void launch_leaf_gram_sum(mra_plan* pl, long n, int nt_max, bool post);
 void launch_cv_gram_sum(mra_plan* pl, long n, int nt_max);
+// mra_launch_loc.hip / mra_launch_loc2.hip: MRA_KERNEL_LOCAL (covariance mode 6, local ranges in the last coordinate column), d = 2 and 3 -
+// the launches the dispatch chains hand their mode-6 case to
+void mra_loc_gemm(mra_plan* pl, bool lds, dim3 grid, const GemmProb* probs, unsigned gxs, unsigned gy, unsigned S);
+void mra_loc_leaf_gemm(mra_plan* pl, bool wide, dim3 grid, const GemmProb* probs);
+void mra_loc_prior_level(mra_plan* pl, dim3 grid, const GemmProb* probs);
+void mra_loc_solve_rows(mra_plan* pl);
+void mra_loc_cov_rows(mra_plan* pl);
+void launch_basis_loc(mra_plan* pl, long n);
+void launch_leaf_loc(mra_plan* pl, long n);
+void launch_mean_loc(mra_plan* pl, long n, int nc);
+void launch_gram_loc(mra_plan* pl, long n, long tile0, long rows, bool post);
+void launch_leaf_gram_loc(mra_plan* pl, long n, int nt_max, bool post);
+void launch_cv_gram_loc(mra_plan* pl, long n, int nt_max);
 void mra_launch_gemm(mra_plan* pl, int epi, const GemmProb* probs, size_t nprob, long maxM, long maxN, bool allow_lds = true, bool lower_tri = false);
 void mra_launch_leaf_gemm(mra_plan* pl, int epi, const GemmProb* probs, size_t nprob);
 void mra_launch_syrk_blk(mra_plan* pl, const GemmProb* probs, size_t nprob, long M, bool dma);

@@ -78,6 +78,19 @@ __device__ __forceinline__ double site_colsq(const double* __restrict__ x, int n
 // a_k = L_k^-1 (C(Q_k, s) - W[Q_k, ancestors of k] a_{<k}), the row recursion of the prior for a location that is not a row: knot
 // coordinates and W rows are gathered through the node's knot list; a phantom knot gives 0.  The covariance value is computed by the
 // lane that holds the element (knot q + 4 j of the tile, site r).
+// C(x, x): the kernel at distance 0, as before; mode 6 is exactly amp there whatever the range (cov_local_of)
+template <int MODE>
+__device__ __forceinline__ double site_cov0(const KernelParams& kp) {
+    if constexpr (MODE == 6) return kp.amp;
+    else return site_cov<MODE>(kp, 0.0);
+}
+// ... of a pair of locations: the same expression as before for the modes that are functions of the distance, cov_local for mode 6
+template <int DIM, int MODE>
+__device__ __forceinline__ double site_cov_pair(const KernelParams& kp, const double* __restrict__ xa, const double* __restrict__ xb) {
+    if constexpr (MODE == 6) return cov_local<DIM>(kp, xa, xb);
+    else return site_cov<MODE>(kp, pair_dist2<DIM>(xa, xb, kp.circular));
+}
+
 template <int DIM, int MODE>
 __global__ __launch_bounds__(64, 4) void k_site_basis(const SolveLeaf* __restrict__ lv, const SiteNode* __restrict__ nodes,
                                                       const int* __restrict__ chain_ptr, const int* __restrict__ chain,
@@ -106,7 +119,7 @@ __global__ __launch_bounds__(64, 4) void k_site_basis(const SolveLeaf* __restric
                 double xk[DIM];
 #pragma unroll
                 for (int e = 0; e < DIM; ++e) xk[e] = gld(X + (long)(kn >= 0 ? kn : 0) * DIM + e);
-                const double cv = site_cov<MODE>(kp, pair_dist2<DIM>(xk, xr, kp.circular));
+                const double cv = site_cov_pair<DIM, MODE>(kp, xk, xr);
                 acc[j] = kn >= 0 ? cv : 0.0;
             }
             const int kr = gldi(N.knots + I * 16 + r);
@@ -149,7 +162,7 @@ __global__ __launch_bounds__(64, 4) void k_site_leaf(const SolveLeaf* __restrict
             double xo[DIM];
 #pragma unroll
             for (int e = 0; e < DIM; ++e) xo[e] = gld(X + (long)(o >= 0 ? o : 0) * DIM + e);
-            const double cv = site_cov<MODE>(kp, pair_dist2<DIM>(xo, xr, kp.circular));
+            const double cv = site_cov_pair<DIM, MODE>(kp, xo, xr);
             acc[j] = o >= 0 ? cv : 0.0;
         }
         return acc;
@@ -184,7 +197,7 @@ __global__ __launch_bounds__(64, 4) void k_site_leaf(const SolveLeaf* __restrict
 #pragma unroll
         for (int j = 0; j < 4; ++j) gst(b + (long)(at * 16 + q + 4 * j) * 16 + r, acc[j]);
     }
-    const double v = site_cov<MODE>(kp, 0.0) - site_colsq(a, anc, r, q) - site_colsq(tt, nop, r, q);
+    const double v = site_cov0<MODE>(kp) - site_colsq(a, anc, r, q) - site_colsq(tt, nop, r, q);
     if (q == 0) gst(var + tile * 16 + r, fmax(v, 0.0));
 }
 
@@ -263,7 +276,7 @@ __global__ __launch_bounds__(64, 4) void k_site_mean(const SolveLeaf* __restrict
             double xo[DIM];
 #pragma unroll
             for (int e = 0; e < DIM; ++e) xo[e] = gld(X + (long)(o >= 0 ? o : 0) * DIM + e);
-            const double cv = site_cov<MODE>(kp, pair_dist2<DIM>(xr, xo, kp.circular));
+            const double cv = site_cov_pair<DIM, MODE>(kp, xr, xo);
             acc = mfma16(o >= 0 ? cv : 0.0, gld(L.uy + (long)k * 16 + r), acc);
         }
     }
@@ -349,7 +362,7 @@ __global__ __launch_bounds__(64, 4) void k_site_gram(const SolveLeaf* __restrict
             double xu[DIM];
 #pragma unroll
             for (int e = 0; e < DIM; ++e) xu[e] = gld(xs + (I * 16 + q + 4 * j) * DIM + e);
-            acc[j] += site_cov<MODE>(kp, pair_dist2<DIM>(xu, xw, kp.circular));
+            acc[j] += site_cov_pair<DIM, MODE>(kp, xu, xw);
         }
     }
     double* o = out + (long)blockIdx.y * 16 * ldo + J * 16 + r;
@@ -377,7 +390,7 @@ __global__ __launch_bounds__(64, 4) void k_site_inert(const SolveLeaf* __restric
     const int t = tile_leaf[tile];
     const int anc = lv[t].anc, nop = lv[t].nop;
     const int lane = threadIdx.x, r = lane & 15, q = lane >> 4;
-    const double c = site_cov<MODE>(kp, 0.0);
+    const double c = site_cov0<MODE>(kp);
     double g = c - site_colsq(a_buf + tile * a_stride, anc, r, q);
     if (POST) g -= site_colsq(t_buf + tile * t_stride, nop, r, q);
     if (q == 0) live[tile * 16 + r] = (sslot[tile * 16 + r] >= 0 && g > SITE_INERT_REL * c) ? 1 : 0;
@@ -433,7 +446,7 @@ __global__ __launch_bounds__(64, 4) void k_site_leaf_gram(const SolveLeaf* __res
         double xu[DIM];
 #pragma unroll
         for (int e = 0; e < DIM; ++e) xu[e] = gld(xs + (I * 16 + q + 4 * j) * DIM + e);
-        const double v = acc[j] + site_cov<MODE>(kp, pair_dist2<DIM>(xu, xw, kp.circular));
+        const double v = acc[j] + site_cov_pair<DIM, MODE>(kp, xu, xw);
         const bool both = lw && live[I * 16 + q + 4 * j];
         gst(o + (long)(q + 4 * j) * ld, both ? v : ((il == jl && q + 4 * j == r) ? 1.0 : 0.0));
     }
@@ -606,7 +619,7 @@ __global__ __launch_bounds__(64, 4) void k_cv_gram(const SolveLeaf* __restrict__
         for (int e = 0; e < DIM; ++e) xu[e] = gld(xs + (I * 16 + q + 4 * j) * DIM + e);
         const long pu = sslot[I * 16 + q + 4 * j];
         const bool on_diag = il == jl && q + 4 * j == r;
-        double v = acc[j] - site_cov<MODE>(kp, pair_dist2<DIM>(xu, xw, kp.circular));
+        double v = acc[j] - site_cov_pair<DIM, MODE>(kp, xu, xw);
         if (on_diag && pu >= 0) v += cv_noise(c, pu);
         gst(o + (long)(q + 4 * j) * ld, (lw && pu >= 0) ? v : (on_diag ? 1.0 : 0.0));
     }

@@ -367,6 +367,13 @@ __device__ __forceinline__ double solve_cov(const KernelParams& kp, double D2) {
     return cov_of_dist2<MODE>(kp, D2);
 }
 
+// ... of a pair of locations: the same expression as before for the modes that are functions of the distance, cov_local for mode 6
+template <int DIM, int MODE>
+__device__ __forceinline__ double solve_cov_pair(const KernelParams& kp, const double* __restrict__ xa, const double* __restrict__ xb) {
+    if constexpr (MODE == 6) return cov_local<DIM>(kp, xa, xb);
+    else return solve_cov<MODE>(kp, pair_dist2<DIM>(xa, xb, kp.circular));
+}
+
 template <int DIM, int MODE>
 __global__ __launch_bounds__(256, 4) void k_solve_rows(const SolveLeaf* __restrict__ lv, const int* __restrict__ tile_leaf,
                                                        const double* __restrict__ W, long ldw, const double* __restrict__ X,
@@ -396,7 +403,7 @@ __global__ __launch_bounds__(256, 4) void k_solve_rows(const SolveLeaf* __restri
                 double xo[DIM];
 #pragma unroll
                 for (int e = 0; e < DIM; ++e) xo[e] = gld(X + (long)(o >= 0 ? o : 0) * DIM + e);
-                const double cv = solve_cov<MODE>(kp, pair_dist2<DIM>(xr, xo, kp.circular));
+                const double cv = solve_cov_pair<DIM, MODE>(kp, xr, xo);
                 acc = mfma16(o >= 0 ? cv : 0.0, gld(L.uy + (long)k * 16 + r), acc);
             }
         }

@@ -20,6 +20,7 @@ MRA_RUN_LIKELIHOOD = 1
 MRA_RUN_PREDICT = 2
 MRA_RUN_SPLIT = 4
 MRA_KERNEL_SUM = 7           # a sum of up to four closed-form kernels (MRATools.KernelSum)
+MRA_KERNEL_LOCAL = 8         # local ranges in the last coordinate column (MRATools.LocalRange)
 MRA_KERNEL_HOST = 100
 MRA_OPT_KERNEL_TIMING = 1
 MRA_OPT_FUSED = 2
@@ -82,7 +83,7 @@ ERR_NAMES = {-1: "MRA_ERR_INVALID", -2: "MRA_ERR_HIP", -3: "MRA_ERR_NOT_SPD", -4
 EXPORTS = [
     "mra_device_count", "mra_release_cached_memory", "mra_plan_create", "mra_plan_destroy", "mra_plan_set_locs", "mra_plan_set_obs",
     "mra_plan_set_noise", "mra_plan_set_noise_rows", "mra_plan_fit_laplace", "mra_plan_fit_laplace_trend", "mra_plan_set_metric", "mra_plan_set_trend", "mra_trend_fit",
-    "mra_plan_set_kernel", "mra_plan_set_locs_rows", "mra_plan_set_obs_rows", "mra_get_predict_rows", "mra_get_predict_rows_sd", "mra_eval_kernel", "mra_plan_set_cov_block", "mra_run", "mra_get_likelihood", "mra_get_predict",
+    "mra_plan_set_kernel", "mra_plan_set_locs_rows", "mra_plan_set_obs_rows", "mra_get_predict_rows", "mra_get_predict_rows_sd", "mra_eval_kernel", "mra_eval_kernel_local", "mra_plan_set_cov_block", "mra_run", "mra_get_likelihood", "mra_get_predict",
     "mra_sample_slots", "mra_sample", "mra_solve", "mra_cov_apply", "mra_predict_sites", "mra_sites_cov", "mra_sample_sites_slots", "mra_sample_sites", "mra_cv", "mra_cv_trend", "mra_get_buffer", "mra_get_node_block", "mra_get_timers", "mra_plan_set_option", "mra_plan_get_option", "mra_plan_prepare", "mra_kernel_family_count",
     "mra_get_kernel_stats", "mra_get_kernel_work", "mra_get_route", "mra_device_synchronize", "mra_plan_info", "mra_comm_unique_id", "mra_comm_init",
     "mra_plan_set_reduce_level", "mra_reduce_size", "mra_reduce_export", "mra_reduce_import",
@@ -149,6 +150,7 @@ def load_library():
         "mra_plan_set_kernel": (C.c_int, [vp, C.c_int, vp, C.c_int]),
         "mra_plan_set_cov_block": (C.c_int, [vp, i32, vp, i64, i64, vp]),
         "mra_eval_kernel": (C.c_int, [C.c_int, vp, C.c_int, vp, i64, vp]),
+        "mra_eval_kernel_local": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, i64, vp]),
         "mra_run": (C.c_int, [vp, u32]),
         "mra_run_resume": (C.c_int, [vp]),
         "mra_get_likelihood": (C.c_int, [vp, C.POINTER(dbl), C.POINTER(dbl)]),
@@ -422,7 +424,8 @@ class HipPlan:
     def set_kernel(self, kind, l=None, sig=1.0, scale=1.0, circular=False, nu=None, components=None):
         """nu: the smoothness of kind 6 (MRA_KERNEL_MATERN), sent behind circular; every other kind ignores it.
         Kind 7 (MRA_KERNEL_SUM): components = [(kind_c, l_c, sig_c), ...], 1 to 4 of them, value = scale * sum of sig_c k_c(D; l_c);
-        they may also stand in l's place (a KernelSum's ``l`` is that list), and sig is not sent."""
+        they may also stand in l's place (a KernelSum's ``l`` is that list), and sig is not sent.
+        Kind 8 (MRA_KERNEL_LOCAL, local ranges in the last coordinate column): l = (base kind, l), as a LocalRange's ``l`` is."""
         par = _kernel_params(kind, l, sig, scale, circular, nu, components)
         self._check(self.lib.mra_plan_set_kernel(self._h, int(kind), _ptr(par), len(par)))
 
@@ -829,6 +832,10 @@ def _kernel_params(kind, l, sig, scale, circular, nu, components):
         return np.array([len(comps), 0.0, scale, 1.0 if circular else 0.0] + [float(v) for c in comps for v in c], dtype=np.float64)
     if components is not None:
         raise ValueError("components= belongs to kind 7")
+    if int(kind) == MRA_KERNEL_LOCAL:      # {l, sig, scale, 0, base kind}: the pair (base kind, l) stands in l's place (a LocalRange's ``l``)
+        if np.ndim(l) != 1 or len(l) != 2:
+            raise ValueError("kind 8 takes l=(base kind, l)")
+        return np.array([float(l[1]), sig, scale, 1.0 if circular else 0.0, float(l[0])], dtype=np.float64)
     return np.array([l, sig, scale, 1.0 if circular else 0.0] + ([] if nu is None else [nu]), dtype=np.float64)
 
 
@@ -840,6 +847,18 @@ def eval_kernel(kind, l=None, sig=1.0, scale=1.0, D=None, nu=None, components=No
     out = np.empty_like(D)
     par = _kernel_params(kind, l, sig, scale, False, nu, components)
     _check(lib, lib.mra_eval_kernel(int(kind), _ptr(par), len(par), _ptr(D), D.size, _ptr(out)))
+    return out
+
+
+def eval_kernel_local(base_kind, l, sig, scale, ds, D, la, lb):
+    """Device evaluation of MRA_KERNEL_LOCAL on arrays of pairs (tests): distance D over ds spatial dimensions, local ranges la, lb."""
+    lib = load_library()
+    D, la, lb = (np.ascontiguousarray(v, dtype=np.float64).ravel() for v in (D, la, lb))
+    if not (D.size == la.size == lb.size):
+        raise ValueError("D, la and lb must have the same length")
+    out = np.empty_like(D)
+    par = _kernel_params(MRA_KERNEL_LOCAL, (base_kind, l), sig, scale, False, None, None)
+    _check(lib, lib.mra_eval_kernel_local(_ptr(par), len(par), int(ds), _ptr(D), _ptr(la), _ptr(lb), D.size, _ptr(out)))
     return out
 
 
